@@ -1,9 +1,14 @@
 #!/usr/bin/env python
-"""bench.py — decode tokens/s of LLaMA-7B Q4_0 on MI355X through the drop-in C ABI (BASELINE.json metric),
-with the mat-vec kernel's HBM roofline and the restated ggml CPU path timed beside it.
+"""bench.py — decode tokens/s of LLaMA-7B Q4_0 on MI355X through the drop-in C ABI (BASELINE.json metric); with --full
+also the mat-vec kernel's HBM roofline, the oracle parity check and the restated ggml CPU path timed beside it.
 
-  python bench.py --gpus 1 --steps K --warmup W
+  python bench.py --gpus 1 --steps K --warmup W [--full] [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+
+A plain run sets up (weights, upload, prompt), warms up W steps, times K steps and prints one JSON line; --full adds every
+other leg of the decode run (parity check, roofline replays, call-sequence / device-sampling / long-context legs, steady prompt
+feed, prefill leg, CPU baseline).  --dump-outputs DIR writes the last timed step's token id and logits as DIR/*.npy; the inputs
+are seeded, so two builds given the same arguments can be compared output for output.
 
 A "step" is one greedy decode token of one sequence per pipeline slot: InferenceSession::infer_next_token
 (host argmax + Model::evaluate of N=1) exactly as crates/llm-base/src/inference_session.rs:381-424 drives it.
@@ -54,7 +59,29 @@ def parse():
     ap.add_argument("--prefill-steps", type=int, default=5, help="timed 512-token prefill steps of the default run's configs[2] leg (0 = skip)")
     ap.add_argument("--weights", default="gaussian", choices=["gaussian", "blocks"],
                     help="gaussian = BASELINE.md section 4 (N(0, 0.02^2) quantized by ggml_quantize_q*); blocks = random valid blocks (faster to make)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="--mode decode: also run everything beside the headline (oracle parity check, roofline replays, call-sequence, "
+                         "device-sampling and long-context legs, steady prompt feed, prefill leg, CPU baseline); without it the run sets "
+                         "up, warms up, times --steps tokens and prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="--mode decode, one GPU: after the timed steps write what the last timed step handed its caller as DIR/<name>.npy "
+                         "(token.npy: the token id infer_next_token returned, float64 [1]; last_logits.npy: the session's logits, float32 [n_vocab])")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and (args.mode != "decode" or args.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1):
+        ap.error("--dump-outputs is implemented for --mode decode on one GPU")
+    return args
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array, float32 or float64, 64 MB at most in all."""
+    total = sum(a.nbytes for a in arrays.values())
+    if total > 64 << 20 or any(a.dtype not in (np.float32, np.float64) for a in arrays.values()):
+        raise SystemExit(f"bench.py: --dump-outputs takes float32 / float64 arrays of 64 MB at most ({total} bytes)")
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
 
 
 def build_model(args, layer_range=None):
@@ -439,6 +466,103 @@ def prefill_leg(L, ggml, model, hp, n, steps, warmup, wname):
             "class_launches_per_step": {k: v[1] for k, v in cls.items()}}
 
 
+def roofline_leg(args, ggml, hp, sess, elapsed, fused_tokens, fused_wo_tokens):
+    """--full: the decode path's HBM roofline, taken at the context length the timed steps ended on, before the other legs move
+    the session on.  Per launch kind: two HIP events on the backend's own stream around `rs` replays of a hipGraph that holds
+    only that launch of every layer (32 per replay): the average launch PERIOD, kernel-to-kernel boundary included.
+    rocprofv3's per-kernel duration of the same launches agrees with it (profiles/), so this is the roofline figure;
+    the same for every mat-vec kind and for all 129 mat-vec launches of a token replayed together."""
+    rs = max(args.roofline_steps, 1)
+    roofline_ctx = int(sess.n_past)  # positions in the session's K/V: what the fused launch's attention reads per replay
+    kinds = {"qkv": 0, "wo": 1, "gate_up": 2, "down": 3, "lm_head": 4}
+    per_kind = {}
+    for name, k in kinds.items():
+        kms, kn, kb = ggml.bench_plan_class(ggml.KKIND_BASE + k, rs)
+        per_kind[name] = {"launches": kn, "bytes_per_launch": int(kb / max(kn, 1)),
+                          "us_per_launch": round(kms * 1e3 / max(kn * rs, 1), 3),
+                          "GBps": round(kb * rs / 1e9 / (kms / 1e3), 1) if kms > 0 else 0.0}
+    ms, launches, algo_bytes = ggml.bench_plan_class(ggml.KCLASS_MMVQ, rs)
+    # what each kind costs IN SEQUENCE: all mat-vec launches minus all but that kind.  A launch replayed alone does not show what
+    # it owes its predecessor (w1|w3 finds its first 24 MB in L2, warmed by the fused launch in front of it: kernels/decode_fused.h
+    # NextWarm) nor what it pays for its successor (that warm-up's 24 MB pass through the fused launch's window)
+    for name, kind in kinds.items():
+        if name in per_kind and per_kind[name]["launches"] > 0:
+            ms_wo, _, _ = ggml.bench_plan_class(ggml.KKIND_BASE + 8 + kind, rs)
+            us_seq = (ms - ms_wo) * 1e3 / rs / per_kind[name]["launches"]
+            per_kind[name]["in_sequence_us_per_launch"] = round(us_seq, 3)
+            per_kind[name]["in_sequence_frac"] = round(per_kind[name]["bytes_per_launch"] / 1e3 / us_seq / HBM_PEAK_GBS, 4) if us_seq > 0 else None
+    att_ms, att_n, att_bytes = ggml.bench_plan_class(ggml.KCLASS_ATTN, rs)
+    oth_ms, oth_n, _ = ggml.bench_plan_class(ggml.KCLASS_OTHER, rs)
+    # the DOMINANT kernel = the launch kind with the most device time per token (launches x period), whatever its name
+    dom_kind = max(per_kind, key=lambda k: per_kind[k]["launches"] * per_kind[k]["us_per_launch"])
+    dom = per_kind[dom_kind]
+    for k, v in per_kind.items():
+        v["us_per_token"] = round(v["launches"] * v["us_per_launch"], 2)
+        v["frac"] = round(v["GBps"] / HBM_PEAK_GBS, 4)
+    achieved = dom["GBps"]
+    wb, nparams = weight_bytes_per_token(hp, ggml.BLOCK_BYTES[hp["wtype"]], ggml.BLOCK_ELEMS[hp["wtype"]])
+    traffic, traffic_from, traffic_all, traffic_ctx = None, None, None, None
+    for tp in ("r06_pmc_traffic.json", "r05_pmc_traffic.json", "r04_pmc_traffic.json", "r03_pmc_traffic.json", "r02_pmc_traffic.json"):
+        tpath = os.path.join(ROOT, "profiles", tp)
+        if os.path.exists(tpath) and args.model == "7b" and args.wtype == "q4_0":
+            tj = json.load(open(tpath))
+            traffic_all = {k: v["hbm_bytes_per_launch"] for k, v in tj.items() if isinstance(v, dict) and "hbm_bytes_per_launch" in v}
+            traffic = traffic_all.get(dom_kind)
+            traffic_ctx = tj.get("context_positions")  # mean context of the profiled dispatches (tests/tools/pmc_traffic.py)
+            traffic_from = ("profiles/" + tp + ": a COMMITTED figure from separate rocprofv3 --pmc passes of this kernel "
+                            "(FETCH_SIZE x2 gfx950 correction + WRITE_SIZE), not measured in this run"
+                            + ("" if traffic is not None else "; it holds no entry for this launch kind"))
+            break
+    is_k = args.wtype.endswith("_k")
+    Egqa_b = hp["n_embd"] // (hp["n_head"] // hp["n_head_kv"])
+    warm_mb = int(os.environ.get("GGML_HIP_WARM_MB", "24"))  # the library's default (llm_amd/csrc/backend_state.inc opt_warm_mb)
+    row_b = hp["n_embd"] // 32 * ggml.BLOCK_BYTES[hp["wtype"]] if not args.wtype.endswith("_k") else 0
+    warm_bytes = (min((int(warm_mb * 1e6 / (2.0 * row_b)) & ~7), hp["n_ff"]) * 2 * row_b) if (row_b and fused_wo_tokens) else 0
+    W = args.wtype.upper()
+    labels = {"gate_up": f"k_mmvq_big<{W}, EPI_GATE, XSRC_NORM> (w1|w3 mat-vec, rms_norm + Q8 staging and silu(w1 x)*(w3 x) epilogue fused)",
+              "qkv": ((f"k_qkv_attn_wo<{W}> (wq|wk|wv mat-vec with rms_norm + Q8 staging, RoPE and K/V store on G - n_head workgroups, the "
+                       "attention of the token on n_head workgroups of the same launch, and wo + residual as the mat-vec workgroups' second "
+                       "phase; bytes = wq|wk|wv + wo + the K/V the attention reads)") if fused_wo_tokens else
+                      (f"k_qkv_attn<{W}> (wq|wk|wv mat-vec with rms_norm + Q8 staging, RoPE and K/V store on G - n_head workgroups + the "
+                       "attention of the token on n_head workgroups of the same launch; bytes = weights + the K/V the attention reads)"))
+                     if fused_tokens else f"k_mmvq_big<{W}, EPI_QKV, XSRC_NORM> (wq|wk|wv mat-vec, rms_norm + Q8 staging, RoPE and K/V store fused)",
+              "down": f"k_mmvq_big<{W}, EPI_ADD, XSRC_F32> (w2 mat-vec, Q8 staging of the gate and residual add fused)",
+              "wo": f"k_mmvq_big<{W}, EPI_ADD, XSRC_Q8> (wo mat-vec + residual add)",
+              "lm_head": f"k_mmvq_big<{W}, EPI_STORE, XSRC_NORM> (final norm + lm_head)"}
+    kernel_label = (f"k_mmvq_kbig / k_qkv_attn_k<{W}> (K plan on big workgroups, launch kind '{dom_kind}': the activation is normed / "
+                    "quantized to Q8_K in the launch's own staging)") if is_k else labels[dom_kind]
+    kernel_label += f"; {dom['launches']} launches per token = {dom['us_per_token']} us, the largest share of the token's device time"
+    roofline = {"bound": "hbm", "kernel": kernel_label, "kernel_kind": dom_kind,
+                "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
+                "traffic": traffic, "traffic_from": traffic_from,
+                # the PMC passes ran at their own context length: the ratio is taken against the algorithmic bytes AT THAT context (the
+                # fused launch's bytes hold the K/V the attention reads: 4 bytes x n_embd_gqa per position and launch)
+                "traffic_context_positions": traffic_ctx,
+                # ... and the fused launch also pulls the first warm_mb (24) MB of w1|w3 through its idle window for the NEXT launch
+                # (kernels/decode_fused.h NextWarm): bytes the memory side sees in THIS launch by design, not re-reads.  (Under the
+                # profiler's per-dispatch serialisation w1|w3 then fetches them again — its own figure stays at its algorithmic bytes;
+                # in a hipGraph replay it finds them in L2: in_sequence_us_per_launch below.)
+                "traffic_next_launch_warm_bytes": warm_bytes if dom_kind == "qkv" else 0,
+                "traffic_over_algo": round(traffic / (dom["bytes_per_launch"] + (warm_bytes if dom_kind == "qkv" else 0)
+                                                      + ((traffic_ctx - roofline_ctx) * Egqa_b * 4 if (traffic_ctx and dom_kind == "qkv") else 0)), 4) if traffic else None,
+                "traffic_per_kind": traffic_all,
+                "avg_launch_us": dom["us_per_launch"], "algo_bytes_per_launch": dom["bytes_per_launch"],
+                "context_positions": roofline_ctx,
+                "method": f"{rs} replays of a hipGraph with that launch of every layer between two HIP events on the "
+                          "backend stream: launch period incl. the kernel boundary (= rocprofv3's per-kernel duration)",
+                "per_kind": per_kind,
+                "all_matvecs_per_token": {"launches": launches, "algo_bytes": int(algo_bytes), "weights_bytes": wb,
+                                          "ms": round(ms / rs, 4),
+                                          "GBps": round(algo_bytes * rs / 1e9 / (ms / 1e3), 1) if ms > 0 else 0.0,
+                                          "frac": round(algo_bytes * rs / 1e9 / (ms / 1e3) / HBM_PEAK_GBS, 4) if ms > 0 else 0.0},
+                "whole_token": {"algo_bytes": int(algo_bytes), "ms": round(elapsed / args.steps * 1e3, 4),
+                                "frac": round(algo_bytes / 1e6 / (elapsed / args.steps * 1e3) / HBM_PEAK_GBS, 4)},
+                "class_ms_per_token": {"mmvq": round(ms / rs, 4), "attn": round(att_ms / rs, 4),
+                                       "other": round(oth_ms / rs, 4)},
+                "class_launches_per_token": {"mmvq": launches, "attn": att_n, "other": oth_n}}
+    return roofline
+
+
 def run_single(args):
     from llm_amd import ggml
     if not ggml.has_gpu():
@@ -456,7 +580,7 @@ def run_single(args):
     # now, this is the steady-state rate of InferenceSession::feed_prompt at the reference's default n_batch = 8
     n_again = (args.prompt - 8) // 8 * 8
     prompt2_s = 0.0
-    if n_again > 0 and sess.rewind(args.prompt - 8) == 0:
+    if args.full and n_again > 0 and sess.rewind(args.prompt - 8) == 0:
         L.ggml_hip_synchronize()
         tp2 = time.perf_counter()
         sess.feed_prompt(prompt[8:8 + n_again])
@@ -476,28 +600,21 @@ def run_single(args):
     t0 = time.perf_counter()
     tprev = t0
     for i in range(args.steps):
-        sess.infer_next_token()  # returns after the token's logits are back on the host (the reference's contract)
+        tok = sess.infer_next_token()  # returns after the token's logits are back on the host (the reference's contract)
         tnow = time.perf_counter()
         per_step[i] = tnow - tprev
         tprev = tnow
     L.ggml_hip_synchronize()
     elapsed = time.perf_counter() - t0
     tok_s = args.steps / elapsed
+    if args.dump_outputs:  # before any leg below moves the session on
+        dump_outputs(args.dump_outputs, {"token": np.array([tok], np.float64), "last_logits": sess.last_logits()})
     fused_tokens = stat("fused_attn_tokens") - fused0
     fused_wo_tokens = stat("fused_wo_tokens") - fused_wo0
     fused_timeouts = stat("fused_attn_timeouts")
     if fused_timeouts:
         raise SystemExit(f"bench.py: {fused_timeouts} attention workgroup(s) of k_qkv_attn gave up waiting for their rows")
-    parity = parity_check(args, hp, w, sess) if not args.no_parity_check else None
-    # roofline leg, taken HERE — at the context length the timed steps ended on, before the other legs move the session on.
-    # Per launch kind: two HIP events on the backend's own stream around `rs` replays of a hipGraph that holds
-    # only that launch of every layer (32 per replay): the average launch PERIOD, kernel-to-kernel boundary included.
-    # rocprofv3's per-kernel duration of the same launches agrees with it (profiles/), so this is the roofline figure;
-    # the same for every mat-vec kind and for all 129 mat-vec launches of a token replayed together.
-    rs = max(args.roofline_steps, 1)
-    roofline_ctx = int(sess.n_past)  # positions in the session's K/V: what the fused launch's attention reads per replay
-    kinds = {"qkv": 0, "wo": 1, "gate_up": 2, "down": 3, "lm_head": 4}
-    per_kind = {}
+    parity = parity_check(args, hp, w, sess) if args.full and not args.no_parity_check else None
     if stat("plan_tokens") == h0["plan_tokens"]:  # e.g. GGML_HIP_PLAN_K=0: the node-by-node executor ran, nothing to replay
         print(json.dumps({"metric": f"decode tokens/s LLaMA-{args.model.upper()} {args.wtype.upper()}", "value": round(tok_s, 2),
                           "unit": "tokens/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
@@ -508,27 +625,12 @@ def run_single(args):
                           "roofline": None, "cpu_baseline": None}), flush=True)
         sess.free()
         return
-    for name, k in kinds.items():
-        kms, kn, kb = ggml.bench_plan_class(ggml.KKIND_BASE + k, rs)
-        per_kind[name] = {"launches": kn, "bytes_per_launch": int(kb / max(kn, 1)),
-                          "us_per_launch": round(kms * 1e3 / max(kn * rs, 1), 3),
-                          "GBps": round(kb * rs / 1e9 / (kms / 1e3), 1) if kms > 0 else 0.0}
-    ms, launches, algo_bytes = ggml.bench_plan_class(ggml.KCLASS_MMVQ, rs)
-    # what each kind costs IN SEQUENCE: all mat-vec launches minus all but that kind.  A launch replayed alone does not show what
-    # it owes its predecessor (w1|w3 finds its first 24 MB in L2, warmed by the fused launch in front of it: kernels/decode_fused.h
-    # NextWarm) nor what it pays for its successor (that warm-up's 24 MB pass through the fused launch's window)
-    for name, kind in kinds.items():
-        if name in per_kind and per_kind[name]["launches"] > 0:
-            ms_wo, _, _ = ggml.bench_plan_class(ggml.KKIND_BASE + 8 + kind, rs)
-            us_seq = (ms - ms_wo) * 1e3 / rs / per_kind[name]["launches"]
-            per_kind[name]["in_sequence_us_per_launch"] = round(us_seq, 3)
-            per_kind[name]["in_sequence_frac"] = round(per_kind[name]["bytes_per_launch"] / 1e3 / us_seq / HBM_PEAK_GBS, 4) if us_seq > 0 else None
-    att_ms, att_n, att_bytes = ggml.bench_plan_class(ggml.KCLASS_ATTN, rs)
-    oth_ms, oth_n, _ = ggml.bench_plan_class(ggml.KCLASS_OTHER, rs)
+    is_k = args.wtype.endswith("_k")
+    roofline = roofline_leg(args, ggml, hp, sess, elapsed, fused_tokens, fused_wo_tokens) if args.full else None
     ht = [x / args.steps / 1e3 for x in sess.host_timing()]  # us per token
     h1 = {k: stat(k) - v for k, v in h0.items()}
     reference_sequence, dev_s, dev8_s, long_ctx = None, None, None, None
-    if not args.headline_only:
+    if args.full and not args.headline_only:
         # the same steps through the reference's OWN call sequence: InferenceSession::compute builds the graph and then calls
         # ggml_graph_compute synchronously (crates/llm-base/src/inference_session.rs:220-295) — no ggml_hip_graph_compute_begin / _end,
         # nothing built ahead: what a rustformers/llm binary gets by linking this library with no source change at all
@@ -673,81 +775,13 @@ def run_single(args):
                                      "compute_end_wait_and_copy": round(ht[4], 1), "argmax": round(ht[5], 1),
                                      "evaluate_total": round(ht[6], 1)}}
 
-    nl = hp["n_layer"]
-    # the DOMINANT kernel = the launch kind with the most device time per token (launches x period), whatever its name
-    dom_kind = max(per_kind, key=lambda k: per_kind[k]["launches"] * per_kind[k]["us_per_launch"])
-    dom = per_kind[dom_kind]
-    for k, v in per_kind.items():
-        v["us_per_token"] = round(v["launches"] * v["us_per_launch"], 2)
-        v["frac"] = round(v["GBps"] / HBM_PEAK_GBS, 4)
-    achieved = dom["GBps"]
-    wb, nparams = weight_bytes_per_token(hp, ggml.BLOCK_BYTES[hp["wtype"]], ggml.BLOCK_ELEMS[hp["wtype"]])
-    traffic, traffic_from, traffic_all, traffic_ctx = None, None, None, None
-    for tp in ("r06_pmc_traffic.json", "r05_pmc_traffic.json", "r04_pmc_traffic.json", "r03_pmc_traffic.json", "r02_pmc_traffic.json"):
-        tpath = os.path.join(ROOT, "profiles", tp)
-        if os.path.exists(tpath) and args.model == "7b" and args.wtype == "q4_0":
-            tj = json.load(open(tpath))
-            traffic_all = {k: v["hbm_bytes_per_launch"] for k, v in tj.items() if isinstance(v, dict) and "hbm_bytes_per_launch" in v}
-            traffic = traffic_all.get(dom_kind)
-            traffic_ctx = tj.get("context_positions")  # mean context of the profiled dispatches (tests/tools/pmc_traffic.py)
-            traffic_from = ("profiles/" + tp + ": a COMMITTED figure from separate rocprofv3 --pmc passes of this kernel "
-                            "(FETCH_SIZE x2 gfx950 correction + WRITE_SIZE), not measured in this run"
-                            + ("" if traffic is not None else "; it holds no entry for this launch kind"))
-            break
-    is_k = args.wtype.endswith("_k")
-    Egqa_b = hp["n_embd"] // (hp["n_head"] // hp["n_head_kv"])
-    warm_mb = int(os.environ.get("GGML_HIP_WARM_MB", "24"))  # the library's default (llm_amd/csrc/backend_state.inc opt_warm_mb)
-    row_b = hp["n_embd"] // 32 * ggml.BLOCK_BYTES[hp["wtype"]] if not args.wtype.endswith("_k") else 0
-    warm_bytes = (min((int(warm_mb * 1e6 / (2.0 * row_b)) & ~7), hp["n_ff"]) * 2 * row_b) if (row_b and fused_wo_tokens) else 0
-    W = args.wtype.upper()
-    labels = {"gate_up": f"k_mmvq_big<{W}, EPI_GATE, XSRC_NORM> (w1|w3 mat-vec, rms_norm + Q8 staging and silu(w1 x)*(w3 x) epilogue fused)",
-              "qkv": ((f"k_qkv_attn_wo<{W}> (wq|wk|wv mat-vec with rms_norm + Q8 staging, RoPE and K/V store on G - n_head workgroups, the "
-                       "attention of the token on n_head workgroups of the same launch, and wo + residual as the mat-vec workgroups' second "
-                       "phase; bytes = wq|wk|wv + wo + the K/V the attention reads)") if fused_wo_tokens else
-                      (f"k_qkv_attn<{W}> (wq|wk|wv mat-vec with rms_norm + Q8 staging, RoPE and K/V store on G - n_head workgroups + the "
-                       "attention of the token on n_head workgroups of the same launch; bytes = weights + the K/V the attention reads)"))
-                     if fused_tokens else f"k_mmvq_big<{W}, EPI_QKV, XSRC_NORM> (wq|wk|wv mat-vec, rms_norm + Q8 staging, RoPE and K/V store fused)",
-              "down": f"k_mmvq_big<{W}, EPI_ADD, XSRC_F32> (w2 mat-vec, Q8 staging of the gate and residual add fused)",
-              "wo": f"k_mmvq_big<{W}, EPI_ADD, XSRC_Q8> (wo mat-vec + residual add)",
-              "lm_head": f"k_mmvq_big<{W}, EPI_STORE, XSRC_NORM> (final norm + lm_head)"}
-    kernel_label = (f"k_mmvq_kbig / k_qkv_attn_k<{W}> (K plan on big workgroups, launch kind '{dom_kind}': the activation is normed / "
-                    "quantized to Q8_K in the launch's own staging)") if is_k else labels[dom_kind]
-    kernel_label += f"; {dom['launches']} launches per token = {dom['us_per_token']} us, the largest share of the token's device time"
-    roofline = {"bound": "hbm", "kernel": kernel_label, "kernel_kind": dom_kind,
-                "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
-                "traffic": traffic, "traffic_from": traffic_from,
-                # the PMC passes ran at their own context length: the ratio is taken against the algorithmic bytes AT THAT context (the
-                # fused launch's bytes hold the K/V the attention reads: 4 bytes x n_embd_gqa per position and launch)
-                "traffic_context_positions": traffic_ctx,
-                # ... and the fused launch also pulls the first warm_mb (24) MB of w1|w3 through its idle window for the NEXT launch
-                # (kernels/decode_fused.h NextWarm): bytes the memory side sees in THIS launch by design, not re-reads.  (Under the
-                # profiler's per-dispatch serialisation w1|w3 then fetches them again — its own figure stays at its algorithmic bytes;
-                # in a hipGraph replay it finds them in L2: in_sequence_us_per_launch below.)
-                "traffic_next_launch_warm_bytes": warm_bytes if dom_kind == "qkv" else 0,
-                "traffic_over_algo": round(traffic / (dom["bytes_per_launch"] + (warm_bytes if dom_kind == "qkv" else 0)
-                                                      + ((traffic_ctx - roofline_ctx) * Egqa_b * 4 if (traffic_ctx and dom_kind == "qkv") else 0)), 4) if traffic else None,
-                "traffic_per_kind": traffic_all,
-                "avg_launch_us": dom["us_per_launch"], "algo_bytes_per_launch": dom["bytes_per_launch"],
-                "context_positions": roofline_ctx,
-                "method": f"{rs} replays of a hipGraph with that launch of every layer between two HIP events on the "
-                          "backend stream: launch period incl. the kernel boundary (= rocprofv3's per-kernel duration)",
-                "per_kind": per_kind,
-                "all_matvecs_per_token": {"launches": launches, "algo_bytes": int(algo_bytes), "weights_bytes": wb,
-                                          "ms": round(ms / rs, 4),
-                                          "GBps": round(algo_bytes * rs / 1e9 / (ms / 1e3), 1) if ms > 0 else 0.0,
-                                          "frac": round(algo_bytes * rs / 1e9 / (ms / 1e3) / HBM_PEAK_GBS, 4) if ms > 0 else 0.0},
-                "whole_token": {"algo_bytes": int(algo_bytes), "ms": round(elapsed / args.steps * 1e3, 4),
-                                "frac": round(algo_bytes / 1e6 / (elapsed / args.steps * 1e3) / HBM_PEAK_GBS, 4)},
-                "class_ms_per_token": {"mmvq": round(ms / rs, 4), "attn": round(att_ms / rs, 4),
-                                       "other": round(oth_ms / rs, 4)},
-                "class_launches_per_token": {"mmvq": launches, "attn": att_n, "other": oth_n}}
     prefill = None
-    if args.prefill_steps > 0 and args.model != "tiny":
+    if args.full and args.prefill_steps > 0 and args.model != "tiny":
         sess.free()
         sess = None
         prefill = prefill_leg(L, ggml, model, hp, args.prefill_tokens, args.prefill_steps, 2, args.wtype)
     cpu = None
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         cpu = cpu_baseline(args, hp, w, args.cpu_secs)
     out = {"metric": f"decode tokens/s LLaMA-{args.model.upper()} {args.wtype.upper()}", "value": round(tok_s, 2),
            "unit": "tokens/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
@@ -755,7 +789,7 @@ def run_single(args):
            "ms_per_step_min_median_max": [round(float(x) * 1e3, 4) for x in (per_step.min(), np.median(per_step), per_step.max())],
            "higher_is_better": True, "scaling": "weak",
            "vs_baseline": None, "dtype": DTYPES[args.wtype], "parity_check": parity,
-           "data": "synthetic",
+           "data": "synthetic", "full": bool(args.full),
            "config": {"workload": f"LLaMA-{args.model.upper()} {args.wtype.upper()} single-token greedy decode "
                                   f"(BASELINE configs[1]), {args.prompt}-token prompt, ctx 2048, f16 KV, batch 1",
                       "n_past_at_start": args.prompt + args.warmup, "parallelism": "1 GPU",
@@ -796,7 +830,7 @@ def run_single(args):
                                       "note": "first call of the process: includes hipGraph capture of the plans",
                                       "steady": {"tokens": n_again, "ms": round(prompt2_s * 1e3, 2),
                                                  "tokens_per_s": round(n_again / prompt2_s, 1) if prompt2_s > 0 else None,
-                                                 "note": "the same 8-token chunks fed again after a rewind (plans cached)"}}, "prep": {k: round(v, 2) for k, v in prep.items()}},
+                                                 "note": "the same 8-token chunks fed again after a rewind (plans cached)"} if args.full else None}, "prep": {k: round(v, 2) for k, v in prep.items()}},
            "roofline": roofline, "cpu_baseline": cpu}
     print(json.dumps(out), flush=True)
     if sess is not None:
