@@ -607,6 +607,20 @@ GGML_API int ggml_hip_debug_exp_le0(uint16_t *out_fast, uint16_t *out_ref);
 /* Test hook: w (quantized 2-D weight with a device copy) times N = 2..8 host rows x [N][K] through k_mmq_cols as the
  * multi-token plan launches it; out [N][M].  0, or -1 when that plan would not run this shape on k_mmq_cols. */
 GGML_API int ggml_hip_debug_mul_mat_cols(const struct ggml_tensor *w, const float *x, float *out, int N);
+/* Test hooks: ONE launch of the single-token plans' mat-vec — k_mmvq_big (Q4_0 .. Q8_0) / k_mmvq_kbig (K-quants) — with the
+ * activation source and epilogue pairs the plans launch (xsrc / epi: 0 Q8 / 1 NORM / 2 F32 and 0 STORE / 1 ADD / 2 GATE / 3 QKV
+ * for _big; 1 NORM / 2 F32 / 3 SILU_MUL and 0 ROW / 1 GATE / 2 QKV for _kbig).  w0 (w1, w2): weights with device copies; x, xw /
+ * norm_w [K]; res; out, y_out (the normed row); QKV: n_past, head size D, RoPE base and scale, cache length C, mem_k [C][Egqa] /
+ * mem_v [Egqa][C] f16 in-out.  Every output and in-out host buffer holds its elements and 256 bytes more: they come back from the
+ * device as they were behind the elements (0xFF before the launch).  0, or -1 for what the plans would not launch. */
+GGML_API int ggml_hip_debug_mat_vec_big(const struct ggml_tensor *w0, const struct ggml_tensor *w1, const struct ggml_tensor *w2,
+                                        int xsrc, int epi, const float *x, const float *norm_w, float eps, const float *res, float *out,
+                                        float *y_out, int n_past, int D, float freq_base, float freq_scale, int64_t C,
+                                        uint16_t *mem_k, uint16_t *mem_v);
+GGML_API int ggml_hip_debug_mat_vec_kbig(const struct ggml_tensor *w0, const struct ggml_tensor *w1, const struct ggml_tensor *w2,
+                                         int xsrc, int epi, const float *x, const float *xw, float eps, const float *res, float *out,
+                                         float *y_out, int n_past, int D, float freq_base, float freq_scale, int64_t C,
+                                         uint16_t *mem_k, uint16_t *mem_v);
 /* Extension (layer split inside one process): slot `slot` enqueues on slot `with_slot`'s stream (with_slot < 0: on its own again).
  * Only for slots of ONE physical GPU whose work never overlaps — the stages of one split session: a wait on another queue's event
  * costs tens of microseconds per stage boundary on this runtime, the same wait inside one queue nothing.  1 = now shared, 0 = not

@@ -3,8 +3,21 @@
 // ---------------------------------------------------------------------------------------------------
 // persistent device tensors
 // ---------------------------------------------------------------------------------------------------
-size_t qw_layout(int qt, int64_t nblocks, size_t off[5]) {
+// The f16 scale planes (Q d / m, Q6_K d) are read as the aligned-pair 32-bit word that holds a scale (kernels/decode_big.h
+// `issue`, kernels/kquant_big.h `load`): when a row has an odd number of blocks, the word of its last block reaches 2 bytes past
+// the row — for the matrix's last row, past the plane.  Such a plane must end at least 2 bytes before the 256-byte boundary it is
+// rounded up to.  The rounding alone leaves no slack when the plane is a multiple of 256 bytes long (odd block count and
+// M % 128 == 0, e.g. 4096 rows of Q6_K at 11008 columns = 43 super-blocks, whose d plane is the last of the layout: the word
+// read past it lay outside the layout), so those planes get 256 bytes more.  Even block counts never read past a row:
+// their layout is unchanged.
+size_t scale_plane_end(size_t o, size_t bytes, bool odd_rows) {
+    const size_t end = (o + bytes + (odd_rows ? 2 : 0) + 255) & ~(size_t)255;
+    if (odd_rows && end < o + bytes + 2) die("weight layout: a scale plane without 2 bytes of slack");
+    return end;
+}
+size_t qw_layout(int qt, int64_t M, int64_t nb, size_t off[5]) {
     // returns total bytes; off = {qs, qs2, qh, d, m}
+    const int64_t nblocks = M * nb;
     auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
     size_t o = 0;
     off[0] = o;
@@ -14,15 +27,15 @@ size_t qw_layout(int qt, int64_t nblocks, size_t off[5]) {
     off[2] = o;
     if (qt == QT_Q5_0 || qt == QT_Q5_1) o = al(o + (size_t)nblocks * 4);
     off[3] = o;
-    o = al(o + (size_t)nblocks * 2);
+    o = scale_plane_end(o, (size_t)nblocks * 2, nb & 1);
     off[4] = o;
-    if (qt == QT_Q4_1 || qt == QT_Q5_1) o = al(o + (size_t)nblocks * 2);
+    if (qt == QT_Q4_1 || qt == QT_Q5_1) o = scale_plane_end(o, (size_t)nblocks * 2, nb & 1);
     return o;
 }
 
 QWeight qw_at(char *base, int qt, int64_t M, int64_t nb) {
     size_t off[5];
-    qw_layout(qt, M * nb, off);
+    qw_layout(qt, M, nb, off);
     QWeight w;
     w.qs = (const uint8_t *)(base + off[0]);
     w.qs2 = (const uint8_t *)(base + off[1]);
@@ -60,7 +73,8 @@ KPlanes k_planes(int kt) {
     }
 }
 double k_block_bytes(int kt) { return kt == KT_Q4_K ? 144.0 : kt == KT_Q6_K ? 210.0 : kt == KT_Q2_K ? 84.0 : kt == KT_Q3_K ? 110.0 : 176.0; }
-size_t kw_layout(int kt, int64_t nsbt, size_t off[4]) {
+size_t kw_layout(int kt, int64_t M, int64_t nsb, size_t off[4]) {
+    const int64_t nsbt = M * nsb;
     auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
     const KPlanes pl = k_planes(kt);
     size_t o = 0;
@@ -71,7 +85,7 @@ size_t kw_layout(int kt, int64_t nsbt, size_t off[4]) {
     off[2] = o;
     o = al(o + (size_t)nsbt * pl.sc);
     off[3] = o;
-    o = al(o + (size_t)nsbt * pl.d);
+    o = scale_plane_end(o, (size_t)nsbt * pl.d, pl.d == 2 && (nsb & 1));  // (Q6_K: 2-byte scales read in pairs)
     return o;
 }
 // rows row0 .. of a planar K weight (every plane is row-major)
@@ -87,7 +101,7 @@ KWeight kw_rows(KWeight w, int64_t row0, int64_t rows) {
 }
 KWeight kw_at(char *base, int kt, int64_t M, int64_t nsb) {
     size_t off[4];
-    kw_layout(kt, M * nsb, off);
+    kw_layout(kt, M, nsb, off);
     KWeight w;
     w.qs = (const uint8_t *)(base + off[0]);
     w.aux = (const uint32_t *)(base + off[1]);
@@ -143,7 +157,7 @@ DevTensor *upload_tensor(const void *data, const ggml_tensor *t, bool zero_fill,
         const int qt = qt_of(t->type);
         const int64_t M = t->ne[1], nb = t->ne[0] / 32;
         size_t off[5];
-        const size_t total = qw_layout(qt, M * nb, off);
+        const size_t total = qw_layout(qt, M, nb, off);
         dev_malloc((void **)&e->dev, total, "a weight tensor");
         e->dev_bytes = total;
         char *tmp = nullptr;
@@ -158,7 +172,7 @@ DevTensor *upload_tensor(const void *data, const ggml_tensor *t, bool zero_fill,
         const int kt = kt_of(t->type);
         const int64_t M = t->ne[1], nsb = t->ne[0] / 256;
         size_t off[4];
-        const size_t total = kw_layout(kt, M * nsb, off);
+        const size_t total = kw_layout(kt, M, nsb, off);
         dev_malloc((void **)&e->dev, total, "a weight tensor");
         e->dev_bytes = total;
         char *tmp = nullptr;
@@ -241,7 +255,7 @@ QWeight qweight_of(const ggml_tensor *t) {
     const int qt = qt_of(t->type);
     const int64_t M = t->ne[1], nb = t->ne[0] / 32;
     size_t off[5];
-    const size_t total = qw_layout(qt, M * nb, off);
+    const size_t total = qw_layout(qt, M, nb, off);
     char *raw = dev_ptr(t);
     char *soa = ws_alloc(total);
     relayout_launch(raw, qt, M, nb, soa);
@@ -260,7 +274,7 @@ KWeight kweight_of(const ggml_tensor *t) {
     const int kt = kt_of(t->type);
     const int64_t M = t->ne[1], nsb = t->ne[0] / 256;
     size_t off[4];
-    const size_t total = kw_layout(kt, M * nsb, off);
+    const size_t total = kw_layout(kt, M, nsb, off);
     char *soa = ws_alloc(total);
     relayout_k_launch(dev_ptr(t), kt, M, nsb, soa);
     return kw_at(soa, kt, M, nsb);

@@ -167,6 +167,259 @@ int ggml_hip_debug_mul_mat_cols(const struct ggml_tensor *w, const float *x, flo
     return 0;
 }
 
+// Test hooks of the decode mat-vecs: ONE launch of k_mmvq_big (Q4_0 .. Q8_0) or k_mmvq_kbig (K-quants) on host arrays, with the
+// source / epilogue pairs and the arguments the single-token plans launch them with (plan_launch_all, plan_launch_k).  Every
+// output buffer (and the K / V caches, uploaded from the host first) is followed by DEBUG_GUARD bytes; outputs and guards are
+// 0xFF (NaN) before the launch and come back whole, guard included, so a test sees an element never written and a store past
+// the end.  -1 for a shape or a pair the plans would not launch.
+namespace {
+constexpr size_t DEBUG_GUARD = 256;
+// n bytes + the guard on the device: `init`'s n bytes (nullptr: 0xFF) followed by 0xFF
+char *debug_buf(size_t n, const void *init, std::vector<char *> &owned) {
+    char *d;
+    dev_malloc((void **)&d, n + DEBUG_GUARD, "a debug buffer");
+    owned.push_back(d);
+    if (init) {
+        h2d_bulk(d, init, n);
+        HIP_CHECK(hipMemsetAsync(d + n, 0xFF, DEBUG_GUARD, g.stream));
+    } else {
+        HIP_CHECK(hipMemsetAsync(d, 0xFF, n + DEBUG_GUARD, g.stream));
+    }
+    return d;
+}
+void debug_hot_line() {
+    if (!g.hot_line) {  // as plan building makes it
+        dev_malloc(&g.hot_line, 256, "the dummy ring steps' line");
+        HIP_CHECK(hipMemsetAsync(g.hot_line, 0, 256, g.stream));
+    }
+}
+// the token's DecParams (n_past; store_at 0 = n_past) and its RoPE table, made by k_rope_table as the plans make it
+void debug_rope(int n_past, int D, float freq_base, float freq_scale, std::vector<char *> &owned, DecParams **prm, float **rope) {
+    DecParams hp;
+    memset(&hp, 0, sizeof(hp));
+    hp.n_past = n_past;
+    dev_malloc((void **)prm, sizeof(DecParams), "debug params");
+    dev_malloc((void **)rope, 256 * 4, "debug rope table");
+    owned.push_back((char *)*prm);
+    owned.push_back((char *)*rope);
+    h2d_bulk((char *)*prm, &hp, sizeof(hp));
+    const float theta_scale = powf(freq_base, -2.0f / (float)D);  // n_dims = the head size, as in LlamaMatch
+    hipLaunchKernelGGL(k_rope_table, dim3(1), dim3(128), 0, g.stream, (const DecParams *)*prm, theta_scale, freq_scale, D >> 1, *rope,
+                       (unsigned *)nullptr);
+    HIP_CHECK(hipGetLastError());
+}
+}  // namespace
+
+// k_mmvq_big: w0 (w1, w2) quantized weights with device copies, all of one type and width K.  Pairs (plan_launch_all):
+//   XSRC_NORM + EPI_QKV (wq, wk, wv), XSRC_Q8 + EPI_ADD (wo), XSRC_NORM + EPI_GATE (w1, w3), XSRC_F32 + EPI_ADD (w2),
+//   XSRC_NORM + EPI_STORE (lm_head).
+// x [K]: the f32 row (XSRC_Q8: quantized by k_quant_row first, as wo's input is a Q8 row); norm_w [K], eps: XSRC_NORM; res [M]:
+// EPI_ADD.  out: [M] (+ guard), QKV: Q [M0] after RoPE.  y_out [K] (+ guard), XSRC_NORM only: the normed row the launch staged
+// (EPI_STORE's tap; for the other epilogues the tap of an EPI_STORE launch of w0 on the same row, run after it — the same
+// staging code).  QKV: n_past, head size D, RoPE parameters, cache length C; mem_k [C][M1] / mem_v [M2][C] f16 in-out.
+int ggml_hip_debug_mat_vec_big(const struct ggml_tensor *w0, const struct ggml_tensor *w1, const struct ggml_tensor *w2, int xsrc,
+                               int epi, const float *x, const float *norm_w, float eps, const float *res, float *out, float *y_out,
+                               int n_past, int D, float freq_base, float freq_scale, int64_t C, uint16_t *mem_k, uint16_t *mem_v) {
+    SlotLock lk;
+    ensure_init();
+    finish_pending();
+    const bool pair_ok = (xsrc == XSRC_NORM && epi == EPI_QKV) || (xsrc == XSRC_Q8 && epi == EPI_ADD) ||
+                         (xsrc == XSRC_NORM && epi == EPI_GATE) || (xsrc == XSRC_F32 && epi == EPI_ADD) ||
+                         (xsrc == XSRC_NORM && epi == EPI_STORE);
+    const int nw = epi == EPI_QKV ? 3 : epi == EPI_GATE ? 2 : 1;
+    const ggml_tensor *ts[3] = {w0, w1, w2};
+    if (!pair_ok || !x) return -1;
+    for (int i = 0; i < nw; i++)
+        if (!ts[i] || qt_of(ts[i]->type) < 0 || ts[i]->type != w0->type || ts[i]->ne[0] != w0->ne[0] || !wants_soa(ts[i])) return -1;
+    const int qt = qt_of(w0->type);
+    const int64_t K = w0->ne[0], nb = K / 32, M0 = w0->ne[1], M1 = nw > 1 ? w1->ne[1] : 0, M2 = nw > 2 ? w2->ne[1] : 0;
+    if ((xsrc == XSRC_NORM && !norm_w) || (epi == EPI_ADD && !res)) return -1;
+    if (epi == EPI_GATE && M1 != M0) return -1;
+    if (epi == EPI_QKV && (!mem_k || !mem_v || D < 2 || D % 2 || D > 256 || M0 % D || M1 % D || M1 != M2 || n_past < 0 || n_past >= C))
+        return -1;
+    // staging limits (BigX): the norm 8192 elements over 1024 threads, launch_big's wave counts up to BIG_W, LDS
+    if (xsrc == XSRC_NORM && nb * 8 > (int64_t)BigX<XSRC_NORM>::MAXIT * BigX<XSRC_NORM>::NT) return -1;
+    const int min_waves = big_min_waves(xsrc, epi, nb);
+    if (min_waves > BIG_W || (size_t)((nb + 63) / 64 * 64) * 40 > 64 * 1024) return -1;
+    // launch_big's dealing: at most 64 units per wave (its abort)
+    const int64_t units = (M0 + M1 + M2) / (epi == EPI_QKV ? 2 : 1);
+    const int G = (int)std::min<int64_t>(g.num_cus, std::max<int64_t>(1, (units + BIG_W - 1) / BIG_W));
+    const int W = big_waves(units, G, min_waves);
+    if ((units + (int64_t)G * W - 1) / ((int64_t)G * W) > 64) return -1;
+
+    std::vector<char *> owned;
+    debug_hot_line();
+    const bool f16d = qt == QT_Q4_0 || qt == QT_Q5_0 || qt == QT_Q8_0;
+    DecMmvqArgs a;
+    memset(&a, 0, sizeof(a));
+    for (int i = 0; i < nw; i++) a.w[i] = qweight_of(ts[i]);
+    a.nb = nb;
+    char *dx = debug_buf((size_t)K * 4, x, owned);
+    a.xf = (const float *)dx;
+    if (xsrc == XSRC_NORM) {
+        a.xw = (const float *)debug_buf((size_t)K * 4, norm_w, owned);
+        a.eps = eps;
+    }
+    if (xsrc == XSRC_Q8) {  // the planar Q8 row, as k_quant_row makes it
+        char *dlo = debug_buf((size_t)K / 2, nullptr, owned), *dhi = debug_buf((size_t)K / 2, nullptr, owned);
+        char *dd = debug_buf((size_t)nb * 4, nullptr, owned), *ds = debug_buf((size_t)nb * 4, nullptr, owned);
+        if (f16d)
+            hipLaunchKernelGGL(k_quant_row<true>, grid1(nb * 32), dim3(256), 0, g.stream, (const float *)dx, (int)nb, (int8_t *)dlo,
+                               (int8_t *)dhi, (float *)dd, (int *)ds, (float *)nullptr, (int *)nullptr);
+        else
+            hipLaunchKernelGGL(k_quant_row<false>, grid1(nb * 32), dim3(256), 0, g.stream, (const float *)dx, (int)nb, (int8_t *)dlo,
+                               (int8_t *)dhi, (float *)dd, (int *)ds, (float *)nullptr, (int *)nullptr);
+        HIP_CHECK(hipGetLastError());
+        a.x = QAct{(const i32x4 *)dlo, (const i32x4 *)dhi, (const float *)dd, (const int *)ds};
+    }
+    if (epi == EPI_ADD) a.res = (const float *)debug_buf((size_t)M0 * 4, res, owned);
+    const size_t n_out = (size_t)M0 * 4;  // (QKV: Q)
+    char *dout = debug_buf(n_out, nullptr, owned);
+    a.dst = (float *)dout;
+    char *dy = (xsrc == XSRC_NORM && y_out) ? debug_buf((size_t)K * 4, nullptr, owned) : nullptr;
+    float *rope = nullptr;
+    char *dk = nullptr, *dv = nullptr;
+    const size_t nkv = epi == EPI_QKV ? (size_t)C * M1 * 2 : 0;
+    if (epi == EPI_QKV) {
+        DecParams *prm;
+        debug_rope(n_past, D, freq_base, freq_scale, owned, &prm, &rope);
+        dk = debug_buf(nkv, mem_k, owned);
+        dv = debug_buf(nkv, mem_v, owned);
+        a.prm = prm;
+        a.mem_k = (__half *)dk;
+        a.mem_v = (__half *)dv;
+        a.Egqa = M1;
+        a.C = C;
+        a.D = D;
+        a.theta_scale = powf(freq_base, -2.0f / (float)D);
+        a.freq_scale = freq_scale;
+    }
+    // BigArgs as plan_launch_all builds them (no timeline, no probe, no granules; wdeal chosen by launch_big)
+    const BigArgs ba{a, epi == EPI_STORE ? (float *)dy : nullptr, nullptr, 0, rope, 0, nullptr, nullptr, 0, g.hot_line};
+    switch (epi) {
+        case EPI_QKV: launch_big_t<EPI_QKV, XSRC_NORM>(qt, ba); break;
+        case EPI_GATE: launch_big_t<EPI_GATE, XSRC_NORM>(qt, ba); break;
+        case EPI_STORE: launch_big_t<EPI_STORE, XSRC_NORM>(qt, ba); break;
+        default:
+            if (xsrc == XSRC_Q8)
+                launch_big_t<EPI_ADD, XSRC_Q8>(qt, ba);
+            else
+                launch_big_t<EPI_ADD, XSRC_F32>(qt, ba);
+    }
+    if (dy && epi != EPI_STORE) {  // the normed row of the same staging code: the tap of an EPI_STORE launch of w0
+        DecMmvqArgs t = a;
+        t.w[1] = t.w[2] = QWeight{};
+        t.dst = (float *)debug_buf((size_t)M0 * 4, nullptr, owned);
+        launch_big_t<EPI_STORE, XSRC_NORM>(qt, BigArgs{t, (float *)dy, nullptr, 0, nullptr, 0, nullptr, nullptr, 0, g.hot_line});
+    }
+    d2h_queue(out, dout, n_out + DEBUG_GUARD);
+    if (dy) d2h_queue(y_out, dy, (size_t)K * 4 + DEBUG_GUARD);
+    if (dk) {
+        d2h_queue(mem_k, dk, nkv + DEBUG_GUARD);
+        d2h_queue(mem_v, dv, nkv + DEBUG_GUARD);
+    }
+    d2h_finish();
+    for (char *b : owned) HIP_CHECK(hipFree(b));
+    return 0;
+}
+
+// k_mmvq_kbig: w0 (w1, w2) K-quant weights with device copies, of width K.  Pairs (plan_launch_k), xsrc KX_* / epi KE_*:
+//   KX_NORM + KE_QKV (wq, wk, wv: one launch per run of equal types, as the plan splits a mixed file), KX_NORM + KE_ROW (1-3
+//   matrices, runs of equal types: wq|wk|wv without the RoPE epilogue, a mixed w1|w3, lm_head), KX_NORM + KE_GATE (w1, w3 of one
+//   type), KX_F32 + KE_ROW with res (wo; w2 behind the gate launch), KX_SILU_MUL + KE_ROW with res (w2 behind a mixed w1|w3).
+// x [K]: the f32 row (KX_SILU_MUL: w1 x); xw [K]: the norm weight (KX_NORM) or w3 x (KX_SILU_MUL); res [M0] nullable.
+// out: KE_ROW the matrices' rows one after the other [M0 + M1 + M2], KE_GATE [M0], KE_QKV Q [M0]; (+ guard).  y_out, KX_NORM only:
+// the normed row (KE_ROW's tap; for the other epilogues the tap of a KE_ROW launch of w0, run after it).  QKV as for
+// ggml_hip_debug_mat_vec_big.
+int ggml_hip_debug_mat_vec_kbig(const struct ggml_tensor *w0, const struct ggml_tensor *w1, const struct ggml_tensor *w2, int xsrc,
+                                int epi, const float *x, const float *xw, float eps, const float *res, float *out, float *y_out,
+                                int n_past, int D, float freq_base, float freq_scale, int64_t C, uint16_t *mem_k, uint16_t *mem_v) {
+    SlotLock lk;
+    ensure_init();
+    finish_pending();
+    const bool pair_ok = (xsrc == KX_NORM && (epi == KE_QKV || epi == KE_ROW || epi == KE_GATE)) ||
+                         ((xsrc == KX_F32 || xsrc == KX_SILU_MUL) && epi == KE_ROW);
+    const ggml_tensor *ts[3] = {w0, w1, w2};
+    const int nw = epi == KE_QKV ? 3 : epi == KE_GATE ? 2 : !w1 ? 1 : !w2 ? 2 : 3;
+    if (!pair_ok || !x || !w0 || (xsrc != KX_F32 && !xw)) return -1;
+    if ((xsrc != KX_NORM || epi != KE_ROW) && nw > 1 && epi == KE_ROW) return -1;  // several matrices: only behind the norm
+    if (res && (epi != KE_ROW || nw > 1)) return -1;
+    const int64_t K = w0->ne[0], nsb = K / 256;
+    int64_t Ms[3] = {0, 0, 0};
+    for (int i = 0; i < nw; i++) {
+        const ggml_tensor *t = ts[i];
+        if (!t || kt_of(t->type) < 0 || t->ne[0] != K || !wants_ksoa(t)) return -1;
+        Ms[i] = t->ne[1];
+        // kbig_ok: the staging limits (KBIG_SBW super-blocks per wave, the norm's two 4096-element passes) and 21 rows per wave
+        if (nsb > 64 || (xsrc == KX_NORM && K > 8192) || (Ms[i] + (int64_t)g.num_cus * 16 - 1) / ((int64_t)g.num_cus * 16) > 21) return -1;
+    }
+    if (epi == KE_GATE && (w1->type != w0->type || Ms[1] != Ms[0])) return -1;
+    if (epi == KE_QKV && (!mem_k || !mem_v || D < 2 || D % 2 || D > 256 || Ms[0] % D || Ms[1] % D || Ms[1] != Ms[2] || Ms[0] % 2 ||
+                          Ms[1] % 2 || n_past < 0 || n_past >= C))
+        return -1;
+
+    std::vector<char *> owned;
+    debug_hot_line();
+    KWeight kw[3];
+    for (int i = 0; i < nw; i++) kw[i] = kweight_of(ts[i]);
+    char *dx = debug_buf((size_t)K * 4, x, owned);
+    char *dxw = xw ? debug_buf((size_t)K * 4, xw, owned) : nullptr;
+    char *dres = res ? debug_buf((size_t)Ms[0] * 4, res, owned) : nullptr;
+    const int64_t Mrow = epi == KE_ROW ? Ms[0] + Ms[1] + Ms[2] : Ms[0];
+    const size_t n_out = (size_t)Mrow * 4;
+    char *dout = debug_buf(n_out, nullptr, owned);
+    char *dy = (xsrc == KX_NORM && y_out) ? debug_buf((size_t)K * 4, nullptr, owned) : nullptr;
+    const KBigSrc src{xsrc, (const float *)dx, (const float *)dxw, eps, epi == KE_ROW ? (float *)dy : nullptr};
+    char *dk = nullptr, *dv = nullptr;
+    const size_t nkv = epi == KE_QKV ? (size_t)C * Ms[1] * 2 : 0;
+    if (epi == KE_QKV) {  // plan_launch_k's kqkv loop: one launch per run of equal types, seg_kind = the matrices' kinds
+        DecParams *prm;
+        float *rope;
+        debug_rope(n_past, D, freq_base, freq_scale, owned, &prm, &rope);
+        dk = debug_buf(nkv, mem_k, owned);
+        dv = debug_buf(nkv, mem_v, owned);
+        const KWeight *ws3[3] = {&kw[0], &kw[1], &kw[2]};
+        float *ds3[3] = {(float *)dout, nullptr, nullptr};
+        for (int i = 0; i < 3;) {
+            int j = i + 1;
+            while (j < 3 && ws3[j]->kt == ws3[i]->kt) j++;
+            KBigArgs qa;
+            memset(&qa, 0, sizeof(qa));
+            for (int k = i; k < j; k++) qa.seg_kind[k - i] = k;
+            qa.rope = rope; qa.prm = prm; qa.mem_k = (__half *)dk; qa.mem_v = (__half *)dv; qa.Egqa = Ms[1]; qa.C = C; qa.D = D;
+            launch_kbig(j - i, ws3 + i, ds3 + i, src, nullptr, KE_QKV, &qa);
+            i = j;
+        }
+    } else if (epi == KE_GATE) {
+        const KWeight *ws2[2] = {&kw[0], &kw[1]};
+        float *ds2[2] = {(float *)dout, (float *)debug_buf((size_t)Ms[1] * 4, nullptr, owned)};
+        launch_kbig(2, ws2, ds2, src, nullptr, KE_GATE);
+    } else {  // plan_launch_k's mmvq: one launch per run of equal types
+        const KWeight *ws[3] = {&kw[0], &kw[1], &kw[2]};
+        float *ds[3] = {(float *)dout, (float *)dout + Ms[0], (float *)dout + Ms[0] + Ms[1]};
+        for (int i = 0; i < nw;) {
+            int j = i + 1;
+            while (j < nw && ws[j]->kt == ws[i]->kt) j++;
+            launch_kbig(j - i, ws + i, ds + i, src, (const float *)dres);
+            i = j;
+        }
+    }
+    if (dy && epi != KE_ROW) {  // the normed row of the same staging code: the tap of a KE_ROW launch of w0
+        const KWeight *ws1[1] = {&kw[0]};
+        float *ds1[1] = {(float *)debug_buf((size_t)Ms[0] * 4, nullptr, owned)};
+        launch_kbig(1, ws1, ds1, KBigSrc{KX_NORM, (const float *)dx, (const float *)dxw, eps, (float *)dy}, nullptr);
+    }
+    d2h_queue(out, dout, n_out + DEBUG_GUARD);
+    if (dy) d2h_queue(y_out, dy, (size_t)K * 4 + DEBUG_GUARD);
+    if (dk) {
+        d2h_queue(mem_k, dk, nkv + DEBUG_GUARD);
+        d2h_queue(mem_v, dv, nkv + DEBUG_GUARD);
+    }
+    d2h_finish();
+    for (char *b : owned) HIP_CHECK(hipFree(b));
+    return 0;
+}
+
 // Test hook: f16(exp_le0(x)) (kernels/prompt_attn.h: the fused prompt attention's exponential) and f16(expf(x)) (what k_p_soft_max
 // and ggml's table hold) for ALL 65536 f16 bit patterns x; out_fast / out_ref: 65536 f16 bit patterns each.
 __global__ void __launch_bounds__(256) k_debug_exp_le0(uint16_t *out_fast, uint16_t *out_ref) {
@@ -214,6 +467,10 @@ int64_t ggml_hip_get_stat(const char *key) {
         return n;
     }
     if (k == "plans") return (int64_t)g_plans.size();
+    if (k == "num_cus") {  // workgroups of a full-chip mat-vec launch (k_mmvq_big, k_mmvq_kbig)
+        ensure_init();
+        return (int64_t)g.num_cus;
+    }
     if (k == "fused_attn_timeouts") {  // attention workgroups of k_qkv_attn that gave up waiting (must stay 0)
         int64_t n = (int64_t)g.stat_fused_timeouts;  // tokens the host saw the error word for (re-run or fatal) + a word still set
         if (g.inited) HIP_CHECK(hipStreamSynchronize(g.stream));

@@ -435,7 +435,7 @@ int ggml_hip_quantize_resident(const struct ggml_tensor *src, struct ggml_tensor
     for (int i = 0; i < 4; i++) e->ne[i] = dst->ne[i];
     const int qt = qt_of(dst->type);
     size_t off[5];
-    const size_t total = qw_layout(qt, nblocks, off);
+    const size_t total = qw_layout(qt, M, nb, off);
     dev_malloc((void **)&e->dev, total, "a weight tensor");
     e->dev_bytes = total;
     relayout_launch(raw, qt, M, nb, e->dev);

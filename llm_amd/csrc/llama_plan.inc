@@ -787,19 +787,22 @@ static int big_waves(int64_t units, int G, int min_waves) {
         if (score(W) > score(best) + 1e-9) best = W;
     return best;
 }
+// what the staging of a k_mmvq_big launch needs: Q8 source one thread per block; f32 source 24 elements per thread; the norm 8
+// stager waves (+ the 2 RoPE-table waves of wq|wk|wv).  Above BIG_W the launch cannot stage the row (ggml_hip_debug_mat_vec_big).
+static int big_min_waves(int xsrc, int epi, int64_t nb) {
+    int min_waves = 8;
+    if (xsrc == XSRC_Q8) min_waves = (int)((nb + 63) / 64);
+    if (xsrc == XSRC_F32) min_waves = (int)((nb * 32 + 24 * 64 - 1) / (24 * 64));
+    if (xsrc == XSRC_NORM) min_waves = epi == EPI_QKV ? 10 : 8;
+    return std::max(min_waves, 8);
+}
 template <int QT, int EPI, int XSRC>
 static void launch_big(const BigArgs &a) {
 
     constexpr int RU = EPI == EPI_QKV ? 2 : 1;
     const int64_t Mtot = a.d.w[0].M + (EPI == EPI_QKV ? a.d.w[1].M + a.d.w[2].M : 0);
     const int64_t units = Mtot / RU;
-    // what the staging needs: Q8 source one thread per block; f32 source 24 elements per thread; the norm 8 stager
-    // waves (+ the 2 RoPE-table waves of wq|wk|wv)
-    int min_waves = 8;
-    if (XSRC == XSRC_Q8) min_waves = (int)((a.d.nb + 63) / 64);
-    if (XSRC == XSRC_F32) min_waves = (int)((a.d.nb * 32 + 24 * 64 - 1) / (24 * 64));
-    if (XSRC == XSRC_NORM) min_waves = EPI == EPI_QKV ? 10 : 8;
-    min_waves = std::max(min_waves, 8);
+    const int min_waves = big_min_waves(XSRC, EPI, a.d.nb);
     const int G = (int)std::min<int64_t>(g.num_cus, std::max<int64_t>(1, (units + BIG_W - 1) / BIG_W));
     const int W = big_waves(units, G, min_waves);
     if ((units + (int64_t)G * W - 1) / ((int64_t)G * W) > 64) {  // one epilogue lane per unit of a wave
