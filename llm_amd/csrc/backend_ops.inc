@@ -826,9 +826,22 @@ void op_rope(ggml_tensor *dst) {
     float freq_base, freq_scale;
     memcpy(&freq_base, dst->op_params + 4, 4);
     memcpy(&freq_scale, dst->op_params + 5, 4);
-    if ((mode & ~1) != 0) die("rope mode %d (NeoX/GLM) is outside the accelerated LLaMA path", mode);
-    BK_ASSERT(a->ne[0] % 2 == 0);
+    if (mode & 4) die("rope mode %d (GLM) is outside the accelerated path", mode);
     const float theta_scale = powf(freq_base, -2.0f / n_dims);
+    if (mode & 2) {  // NeoX: GPT-NeoX, Falcon (kernels/ops.h k_rope_neox)
+        BK_ASSERT(n_dims > 0 && n_dims % 2 == 0 && a->nb[0] == 4 && dst->nb[0] == 4);
+        const TView va = view_of(a), vd = view_of(dst);
+        const int in_place = va.p == vd.p;
+        const int64_t per_row = in_place ? (a->ne[0] / n_dims) * (n_dims / 2) : a->ne[0];
+        const int64_t total = per_row * a->ne[1] * a->ne[2] * a->ne[3];
+        if (total == 0) return;
+        Timed tm(GGML_HIP_KCLASS_OTHER, (double)ggml_nelements(a) * 8);
+        hipLaunchKernelGGL(k_rope_neox, grid1(total), dim3(256), 0, g.stream, va, vd, n_past, n_dims, theta_scale,
+                           freq_scale, mode, per_row, in_place);
+        HIP_CHECK(hipGetLastError());
+        return;
+    }
+    BK_ASSERT(a->ne[0] % 2 == 0);
     const int64_t total = (a->ne[0] / 2) * a->ne[1] * a->ne[2] * a->ne[3];
     Timed tm(GGML_HIP_KCLASS_OTHER, (double)ggml_nelements(a) * 8);
     hipLaunchKernelGGL(k_rope, grid1(total), dim3(256), 0, g.stream, view_of(a), view_of(dst), n_past, theta_scale,

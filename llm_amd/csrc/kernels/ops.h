@@ -220,6 +220,42 @@ __global__ void __launch_bounds__(256) k_rope(const TView x, const TView y, int 
     *(float *)((char *)dst + y.nb[0]) = x0 * s + x1 * c;
 }
 
+// ---- RoPE NeoX mode (mode & 2: GPT-NeoX gptneox/src/lib.rs:227-228, Falcon falcon/src/lib.rs:245-246) -----
+// ggml's rope_f32 NeoX branch: for each n_dims block ib of the row and ic = 0, 2, .., n_dims-2, the pair
+// (i0, i0 + n_dims/2), i0 = ib*n_dims + ic/2, is rotated by theta = freq_scale*p*theta_scale^(ib*n_dims/2 + ic/2),
+// the iterated f32 product running on from block to block.  Elements past (ne0/n_dims)*n_dims are not rotated.
+// Rows with i2 < n_past under mode & 1 are skipped by ggml (its i2 loop starts at n_past).  Work items per row:
+// npairs pair rotations, then (out of place only) `tail` copies of the unrotated elements; a skipped row is one
+// copy per element out of place and nothing in place.  Consecutive threads take consecutive i0: both halves of
+// a pair are read and written coalesced.  x, y: full TView strides (Falcon ropes strided views of the fused QKV).
+__global__ void __launch_bounds__(256) k_rope_neox(const TView x, const TView y, int n_past, int n_dims,
+                                                   float theta_scale, float freq_scale, int mode, int64_t per_row,
+                                                   int in_place) {
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t nrows = x.ne[1] * x.ne[2] * x.ne[3];
+    if (idx >= per_row * nrows) return;
+    const int64_t k = idx % per_row, r = idx / per_row;
+    const int64_t i1 = r % x.ne[1], i2 = (r / x.ne[1]) % x.ne[2], i3 = r / (x.ne[1] * x.ne[2]);
+    const char *src = x.p + i1 * x.nb[1] + i2 * x.nb[2] + i3 * x.nb[3];
+    char *dst = y.p + i1 * y.nb[1] + i2 * y.nb[2] + i3 * y.nb[3];
+    const int64_t half = n_dims / 2, npairs = (x.ne[0] / n_dims) * half;
+    const bool skip_row = (mode & 1) != 0 && i2 < n_past;
+    if (skip_row || k >= npairs) {  // pass-through element (only launched out of place)
+        if (in_place) return;
+        const int64_t i0 = skip_row ? k : 2 * npairs + (k - npairs);
+        if (i0 < x.ne[0]) *(float *)(dst + i0 * y.nb[0]) = *(const float *)(src + i0 * x.nb[0]);
+        return;
+    }
+    const int64_t p = (mode & 1) == 0 ? n_past + i2 : i2;
+    float theta = freq_scale * (float)p;
+    for (int64_t j = 0; j < k; j++) theta *= theta_scale;  // k = ib*half + ic/2 sequential multiplies
+    const float c = cosf(theta), s = sinf(theta);
+    const int64_t i0 = (k / half) * n_dims + k % half;
+    const float x0 = *(const float *)(src + i0 * x.nb[0]), x1 = *(const float *)(src + (i0 + half) * x.nb[0]);
+    *(float *)(dst + i0 * y.nb[0]) = x0 * c - x1 * s;
+    *(float *)(dst + (i0 + half) * y.nb[0]) = x0 * s + x1 * c;
+}
+
 // ---- generic strided copy / convert (ggml_cpy, ggml_cont, ggml_dup): the KV-cache store -------------
 // Element i of the flattened logical index space is read at src's strides and written at dst's strides
 // (shapes may differ, element counts match) — covers K (contiguous f16 run) and the V scatter-transpose
