@@ -49,10 +49,11 @@ class Resident:
         self.sctx.free()
         self.ctx.free()
 
-    def _ctx0(self, N):
+    def _ctx0(self, N, kq_copies=3):
         """The compute context of one evaluate(): every node keeps its own buffer (no scratch reuse across layers),
-        per layer and token at most ~48*n_embd f32 activations + the KQ rows (3*T*n_head f32 with the views), plus
-        per layer one f16 copy of V (Falcon's cont(transpose))."""
+        per layer and token at most ~48*n_embd f32 activations + the KQ rows (`kq_copies`*T*n_head f32 with the views:
+        BLOOM and MPT keep 4, their scale / mask / softmax are out of place), plus per layer one f16 copy of V
+        (Falcon's cont(transpose), BLOOM's and MPT's permuted copy)."""
         hp = self.hp
         E, L, T = hp["n_embd"], hp["n_layer"], self.n_past + N
-        return G.Context(64 * 1024 * 1024 + L * N * (48 * E + 3 * T * hp["n_head"]) * 4 + L * T * E * 2)
+        return G.Context(64 * 1024 * 1024 + L * N * (48 * E + kq_copies * T * hp["n_head"]) * 4 + L * T * E * 2)

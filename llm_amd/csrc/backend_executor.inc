@@ -50,13 +50,18 @@ void upload_inputs(ggml_cgraph *gr) {
     }
 }
 
+// a node whose result download_outputs copies back to its host data (CPU backend)
+bool mirrored_to_host(const ggml_tensor *n) {
+    if (n->backend != GGML_BACKEND_CPU || is_view_op(n->op) || n->op == GGML_OP_CPY) return false;
+    if (!ggml_is_contiguous(n) || n->data == nullptr) return false;
+    return !(extra_of(n) || find_tensor((uintptr_t)n->data));  // else the result aliases a device-resident tensor
+}
+
 void download_outputs(ggml_cgraph *gr) {
     bool any = false;
     for (int i = 0; i < gr->n_nodes; i++) {
         ggml_tensor *n = gr->nodes[i];
-        if (n->backend != GGML_BACKEND_CPU || is_view_op(n->op) || n->op == GGML_OP_CPY) continue;
-        if (!ggml_is_contiguous(n) || n->data == nullptr) continue;
-        if (extra_of(n) || find_tensor((uintptr_t)n->data)) continue;  // result aliases a device-resident tensor
+        if (!mirrored_to_host(n)) continue;
         d2h_queue(n->data, dev_ptr(n), ggml_nbytes(n));
         any = true;
     }
@@ -185,17 +190,34 @@ void execute_graph(ggml_cgraph *gr) {
             case GGML_OP_SCALE: {
                 // fuse scale -> diag_mask_inf -> soft_max when chained in place (llama lib.rs:268-281)
                 ggml_tensor *n1 = next, *n2 = i + 2 < gr->n_nodes ? gr->nodes[i + 2] : nullptr;
+                ggml_tensor *n3 = i + 3 < gr->n_nodes ? gr->nodes[i + 3] : nullptr;
                 if (fuse && n1 && n2 && n1->op == GGML_OP_DIAG_MASK_INF && n1->src[0] == n && n2->op == GGML_OP_SOFT_MAX &&
                     n2->src[0] == n1 && uses[i] == 1 && uses[i + 1] == 1 && n->data == n->src[0]->data &&
                     n1->data == n->data && n2->data == n->data && is_contig_f32(n)) {
                     op_scale_mask_softmax(n->src[0], n->src[1], (int)n1->op_params[0], n2);
                     done[i + 1] = done[i + 2] = 1;
+                } else if (fuse && n1 && n2 && n3 && n1->op == GGML_OP_ALIBI && n1->src[0] == n &&
+                           n2->op == GGML_OP_DIAG_MASK_INF && n2->src[0] == n1 && n3->op == GGML_OP_SOFT_MAX &&
+                           n3->src[0] == n2 && uses[i] == 1 && uses[i + 1] == 1 && uses[i + 2] == 1 &&
+                           !mirrored_to_host(n) && !mirrored_to_host(n1) && !mirrored_to_host(n2) &&
+                           is_contig_f32(n->src[0]) && is_contig_f32(n3) && ggml_nelements(n3) == ggml_nelements(n) &&
+                           n3->ne[0] == n->src[0]->ne[0] && n3->ne[1] == n->src[0]->ne[1] && n->src[0]->ne[3] == 1 &&
+                           n->src[0]->ne[2] == n1->op_params[1]) {
+                    // BLOOM / MPT (bloom lib.rs:233-246, mpt lib.rs:176-183), built out of place: S = scale(KQ), A = alibi
+                    // view of S, M = diag_mask_inf(A), P = soft_max(M) (any step may also be in place).  S, A and M have no
+                    // other reader and are not mirrored to the host, so they need not be written: one launch reads KQ and
+                    // writes P.
+                    invalidate_qact_if_overwritten(n3);
+                    op_scale_alibi_mask_softmax(n->src[0], n->src[1], n1, (int)n2->op_params[0], n3);
+                    done[i + 1] = done[i + 2] = done[i + 3] = 1;
+                    g.stat_alibi_fused++;
                 } else {
                     op_scale(n);
                 }
             } break;
             case GGML_OP_DIAG_MASK_INF: op_diag_mask_inf(n); break;
             case GGML_OP_SOFT_MAX: op_soft_max(n); break;
+            case GGML_OP_ALIBI: op_alibi(n); break;
             case GGML_OP_ROPE: op_rope(n); break;
             case GGML_OP_CPY: op_cpy(n->src[0], n->src[1]); break;
             case GGML_OP_CONT:

@@ -819,6 +819,44 @@ void op_scale_mask_softmax(const ggml_tensor *kq, const ggml_tensor *scale, int 
     HIP_CHECK(hipGetLastError());
 }
 
+// ggml_compute_forward_alibi_f32's slope table, with the C library's powf: heads k < n_floor = 2^floor(log2 n_head) take
+// m0^(k+1), the rest m1^(2(k - n_floor) + 1)
+AlibiSlopes alibi_slopes(const ggml_tensor *alibi) {
+    const int n_head = alibi->op_params[1];
+    float bias_max;
+    memcpy(&bias_max, alibi->op_params + 2, sizeof(float));
+    BK_ASSERT(n_head >= 1 && n_head <= 256);
+    AlibiSlopes s = {};
+    const int n_floor = 1 << (int)floor(log2(n_head));
+    const float m0 = powf(2.0f, -(bias_max) / n_floor);
+    const float m1 = powf(2.0f, -(bias_max / 2.0f) / n_floor);
+    for (int k = 0; k < n_head; k++) s.m[k] = k < n_floor ? powf(m0, k + 1) : powf(m1, 2 * (k - n_floor) + 1);
+    return s;
+}
+
+// KQ [n_past + N, N, n_head] f32 with contiguous rows (the layout ggml_alibi accepts); in place on its view
+void op_alibi(ggml_tensor *dst) {
+    const ggml_tensor *a = dst->src[0];
+    BK_ASSERT(is_contig_f32(a) && dst->data == a->data && a->ne[2] == dst->op_params[1] && a->ne[3] == 1);
+    const int64_t n = ggml_nelements(a);
+    if (n == 0) return;
+    Timed tm(GGML_HIP_KCLASS_OTHER, (double)n * 8);
+    hipLaunchKernelGGL(k_alibi, grid1(n), dim3(256), 0, g.stream, (float *)dev_ptr(dst), a->ne[0], a->ne[1], n,
+                       alibi_slopes(dst));
+    HIP_CHECK(hipGetLastError());
+}
+
+// fused scale -> alibi -> diag_mask_inf -> soft_max: reads KQ, writes P (which may alias KQ)
+void op_scale_alibi_mask_softmax(const ggml_tensor *kq, const ggml_tensor *scale, const ggml_tensor *alibi, int n_past,
+                                 ggml_tensor *out) {
+    BK_ASSERT(is_contig_f32(kq) && is_contig_f32(out) && kq->ne[2] == alibi->op_params[1] && kq->ne[3] == 1);
+    Timed tm(GGML_HIP_KCLASS_OTHER, (double)ggml_nelements(kq) * 8);
+    hipLaunchKernelGGL((k_soft_max<true, true>), dim3((unsigned)ggml_nrows(kq)), dim3(256), 0, g.stream,
+                       (const float *)dev_ptr(kq), (float *)dev_ptr(out), kq->ne[0], kq->ne[1],
+                       (const float *)dev_ptr(scale), n_past, alibi_slopes(alibi));
+    HIP_CHECK(hipGetLastError());
+}
+
 void op_rope(ggml_tensor *dst) {
     const ggml_tensor *a = dst->src[0];
     BK_ASSERT(a->type == GGML_TYPE_F32 && dst->type == GGML_TYPE_F32);

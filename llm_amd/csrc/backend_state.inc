@@ -126,6 +126,7 @@ struct Backend {
     int opt_kbig = 1;       // ... its decode mat-vecs as one wave of 1024-thread workgroups that stage the activation themselves (kernels/kquant_big.h)
     int opt_graph = 1;      // replay the plan from a captured hipGraph
     uint64_t stat_plan_tokens = 0, stat_generic_graphs = 0, stat_split_tokens = 0, stat_prompt_plan_tokens = 0, stat_fused_tokens = 0, stat_kplan_tokens = 0, stat_fused_heads_tokens = 0, stat_fused_wo_tokens = 0, stat_fused_affine_tokens = 0, stat_prepared_tokens = 0;
+    uint64_t stat_alibi_fused = 0;  // scale -> alibi -> diag_mask_inf -> soft_max chains run as one launch (k_alibi_soft_max)
     // prompt-GEMM launches by kernel (ggml_hip_get_stat("mmq_launches_<name>")): bench.py labels its MFMA roofline with the
     // kernels that actually ran
     enum { MMQ_K_PLAIN, MMQ_K_DMA_P8, MMQ_K_W16_P8, MMQ_K_W16_256, MMQ_K_I8, MMQ_K_COUNT };

@@ -489,6 +489,7 @@ int64_t ggml_hip_get_stat(const char *key) {
     if (k == "fused_attn_tokens") return (int64_t)g.stat_fused_tokens;  // decode tokens whose attention rode in the wq|wk|wv launch
     if (k == "peak_concurrent_calls") return (int64_t)g_calls_inside_peak.load();  // threads that were inside entry points (on different slots) at once
     if (k == "generic_graphs") return (int64_t)g.stat_generic_graphs;  // graphs run node by node
+    if (k == "alibi_fused") return (int64_t)g.stat_alibi_fused;  // ALiBi attention chains (BLOOM, MPT) run as one launch
     if (k == "ns_match") return (int64_t)g.ns_match;      // host ns spent recognising decode graphs
     if (k == "ns_launch") return (int64_t)g.ns_launch;    // ... enqueueing (param upload, graph launch, read-back queue)
     if (k == "ns_wait") return (int64_t)g.ns_wait;        // ... waiting for the device + copying results out

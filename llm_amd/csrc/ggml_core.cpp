@@ -669,9 +669,20 @@ static void out_of_path(const char *what) {
             what);
     abort();
 }
-struct ggml_tensor *ggml_alibi(struct ggml_context *, struct ggml_tensor *, int, int, float) {
-    out_of_path("ggml_alibi");
-    return nullptr;
+// ALiBi (BLOOM bloom/src/lib.rs:240, MPT mpt/src/lib.rs:180-181): a view of `a`, biased in place on execution
+// (kernels/ops.h k_alibi).  Accepted: the layout both graphs build, KQ f32 [n_past + N, N, n_head]; any other call has
+// no device implementation.
+struct ggml_tensor *ggml_alibi(struct ggml_context *ctx, struct ggml_tensor *a, int n_past, int n_head,
+                               float bias_max) {
+    GGML_ASSERT(n_past >= 0);
+    if (a->type != GGML_TYPE_F32 || n_head < 1 || n_head > 256 || a->ne[2] != n_head || a->ne[3] != 1 ||
+        a->ne[0] != n_past + a->ne[1] || !std::isfinite(bias_max))
+        out_of_path("ggml_alibi (a layout other than KQ f32 [n_past + N, N, n_head], n_head <= 256)");
+    ggml_tensor *result = unary_like(ctx, a, GGML_OP_ALIBI, true);
+    int32_t params[3] = {n_past, n_head, 0};
+    memcpy(params + 2, &bias_max, sizeof(float));
+    set_op_params(result, params, sizeof(params));
+    return result;
 }
 struct ggml_tensor *ggml_flash_attn(struct ggml_context *, struct ggml_tensor *, struct ggml_tensor *,
                                     struct ggml_tensor *, bool) {

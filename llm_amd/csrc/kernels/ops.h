@@ -156,12 +156,32 @@ __global__ void __launch_bounds__(256) k_diag_mask_inf(const float *a, float *d,
     d[i] = c > n_past + j ? -INFINITY : a[i];
 }
 
+// ---- ALiBi (ggml_alibi: BLOOM bloom/src/lib.rs:240, MPT mpt/src/lib.rs:180-181) -------------------------
+// KQ f32 [nc = n_past + N, nr = N, n_head] contiguous, in place: element (i, j, k) += (float)i * m_k, the product and
+// the sum rounded separately (__fmul_rn / __fadd_rn: never contracted into an FMA).  The slopes m_k are computed on
+// the host with libm powf (alibi_slopes in backend_ops.inc), as the reference's CPU build does, and passed by value.
+struct AlibiSlopes {
+    float m[256];
+};
+__global__ void __launch_bounds__(256) k_alibi(float *x, int64_t nc, int64_t nr, int64_t n, const AlibiSlopes sl) {
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= n) return;
+    const int64_t i = idx % nc, k = idx / (nc * nr);  // consecutive threads on consecutive key positions i
+    x[idx] = __fadd_rn(__fmul_rn((float)i, sl.m[k]), x[idx]);
+}
+
 // ---- softmax over rows (ggml_soft_max): exp through f16 like table_exp_f16, f64 row sum --------------
 // SCALE_MASK: fused scale → diag_mask_inf → soft_max (llama lib.rs:268-281); rows are [nc] with row
 // index j = (row % nr) inside each head.
-template <bool SCALE_MASK>
+// ALIBI (with SCALE_MASK; BLOOM, MPT): fused scale → alibi → diag_mask_inf → soft_max over KQ [nc, nr, n_head], the
+// slope table the one argument of the pack (head = row / nr): each element scaled, then biased by (float)i * slope
+// as k_alibi does, then masked, the rest as below, so the result equals the four launches bit for bit.  The pack is
+// empty for the plain forms, whose arguments (and code) it leaves as they were.  A thread reads x[i] and writes y[i]
+// for the same i only, so d may alias a.
+__device__ __forceinline__ float alibi_slope(int64_t head, const AlibiSlopes &sl) { return sl.m[head]; }
+template <bool SCALE_MASK, bool ALIBI = false, class... Slopes>
 __global__ void __launch_bounds__(256) k_soft_max(const float *a, float *d, int64_t nc, int64_t nr,
-                                                  const float *scale, int n_past) {
+                                                  const float *scale, int n_past, const Slopes... sl) {
     __shared__ float s_max[4];
     __shared__ double s_sum[4];
     const int64_t row = blockIdx.x;
@@ -169,10 +189,12 @@ __global__ void __launch_bounds__(256) k_soft_max(const float *a, float *d, int6
     float *y = d + row * nc;
     const float sc = SCALE_MASK ? scale[0] : 1.0f;
     const int64_t lim = SCALE_MASK ? (int64_t)n_past + (row % nr) : nc;  // columns > lim are masked
+    float slope = 0.0f;
+    if constexpr (ALIBI) slope = alibi_slope(row / nr, sl...);
     float mx = -INFINITY;
     for (int64_t i = threadIdx.x; i < nc; i += 256) {
         float v = x[i];
-        if (SCALE_MASK) v = i > lim ? -INFINITY : v * sc;
+        if (SCALE_MASK) v = i > lim ? -INFINITY : ALIBI ? __fadd_rn(__fmul_rn((float)i, slope), __fmul_rn(v, sc)) : v * sc;
         mx = fmaxf(mx, v);
     }
     mx = wave_max_f32(mx);
@@ -182,7 +204,7 @@ __global__ void __launch_bounds__(256) k_soft_max(const float *a, float *d, int6
     double sum = 0.0;
     for (int64_t i = threadIdx.x; i < nc; i += 256) {
         float v = x[i];
-        if (SCALE_MASK) v = i > lim ? -INFINITY : v * sc;
+        if (SCALE_MASK) v = i > lim ? -INFINITY : ALIBI ? __fadd_rn(__fmul_rn((float)i, slope), __fmul_rn(v, sc)) : v * sc;
         float e = 0.0f;
         if (v != -INFINITY) {
             e = round_f16(expf(round_f16(v - mx)));
