@@ -18,13 +18,50 @@ int node_index(const ggml_cgraph *gr, const ggml_tensor *t, const std::map<const
     return it == idx.end() ? -1 : it->second;
 }
 
+// The target of a LoRA patch (lora.rs:86-139): the leaf under src0 of an ADD whose src0 is not f32.  Its host bytes are the
+// source of truth at compute time — the caller copies the patched result over them afterwards, and a second adapter patches
+// the same tensor again — so they are staged raw into the workspace for this graph only (dev_ptr finds them there).  The
+// leaf never becomes a persistent or re-laid-out record, and any auto record over its range is dropped: one left behind
+// would go stale with the caller's copy, and later graphs that match it by header (weights not offloaded) would read the
+// unpatched bytes.  A target the caller already offloaded is not the reference's order (it patches at load, before
+// offloading): abort.
+void stage_add_target(ggml_tensor *leaf) {
+    const uintptr_t p = (uintptr_t)leaf->data;
+    const size_t nbytes = ggml_nbytes(leaf);
+    for (const Staged &st : g_staged)
+        if (st.host == p && st.nbytes == nbytes) return;
+    bool offloaded = extra_of(leaf) != nullptr;
+    for (auto &kv : g.tensors)
+        if (kv.second->host < p + nbytes && p < kv.second->host + std::max<size_t>(kv.second->nbytes, 1)) offloaded = true;
+    if (offloaded)
+        die("add: tensor '%s' (%s) was offloaded to the device before being patched; LoRA adapters are applied at load time, "
+            "before the weights are offloaded",
+            leaf->name, ggml_type_name(leaf->type));
+    evict_overlapping(g.auto_tensors, p, std::max<size_t>(nbytes, 1));
+    char *d = ws_alloc(std::max<size_t>(nbytes, 16));
+    h2d_small(d, leaf->data, nbytes);
+    g_staged.push_back({p, nbytes, d});
+}
+
 void upload_inputs(ggml_cgraph *gr) {
     if (gr->n_nodes == 0) return;
     // the compute context = the arena holding the tensor headers of the graph's nodes
     Arena *r0 = find_arena((uintptr_t)gr->nodes[gr->n_nodes - 1]);
+    std::vector<const ggml_tensor *> add_targets;
+    for (int i = 0; i < gr->n_nodes; i++) {
+        const ggml_tensor *n = gr->nodes[i];
+        if (n->op != GGML_OP_ADD || !n->src[0] || n->src[0]->type == GGML_TYPE_F32) continue;
+        const ggml_tensor *t = n->src[0];
+        while (t->op != GGML_OP_NONE && is_view_op(t->op) && t->src[0]) t = t->src[0];
+        if (t->op == GGML_OP_NONE) add_targets.push_back(t);
+    }
     for (int i = 0; i < gr->n_leafs; i++) {
         ggml_tensor *leaf = gr->leafs[i];
         if (leaf->data == nullptr) continue;
+        if (!add_targets.empty() && std::find(add_targets.begin(), add_targets.end(), leaf) != add_targets.end()) {
+            stage_add_target(leaf);
+            continue;
+        }
         if (extra_of(leaf)) continue;
         const uintptr_t p = (uintptr_t)leaf->data;
         if (DevTensor *e = find_tensor(p)) {
@@ -57,16 +94,20 @@ bool mirrored_to_host(const ggml_tensor *n) {
     return !(extra_of(n) || find_tensor((uintptr_t)n->data));  // else the result aliases a device-resident tensor
 }
 
+static inline uint64_t now_ns();  // (llama_plan.inc)
 void download_outputs(ggml_cgraph *gr) {
+    const uint64_t t0 = now_ns();
     bool any = false;
     for (int i = 0; i < gr->n_nodes; i++) {
         ggml_tensor *n = gr->nodes[i];
         if (!mirrored_to_host(n)) continue;
         d2h_queue(n->data, dev_ptr(n), ggml_nbytes(n));
+        g.stat_mirror_bytes += ggml_nbytes(n);
         any = true;
     }
     (void)any;
     d2h_finish();
+    g.ns_mirror += now_ns() - t0;
 }
 
 void invalidate_xf16_if_overwritten_impl(const ggml_tensor *n);
@@ -165,7 +206,12 @@ void execute_graph(ggml_cgraph *gr) {
                 }
             } break;
             case GGML_OP_NORM: op_norm(n); break;
-            case GGML_OP_ADD: op_bin(n, BIN_ADD); break;
+            case GGML_OP_ADD: {
+                if (n->src[0]->type == GGML_TYPE_F32)
+                    op_bin(n, BIN_ADD);
+                else
+                    op_add_lowp(n);  // W + s·BA of a LoRA patch: requantizing add (kernels/lora.h)
+            } break;
             case GGML_OP_MUL: {
                 const int si = n->src[0] && n->src[0]->op == GGML_OP_UNARY ? node_index(gr, n->src[0], idx) : -1;
                 if (si >= 0 && deferred_silu[si] == i)

@@ -749,6 +749,51 @@ void op_bin(ggml_tensor *dst, int op) {
     HIP_CHECK(hipGetLastError());
 }
 
+// ggml_add(W, x) with W quantized (Q4_0 / Q4_1 / Q5_0 / Q5_1 / Q8_0) or f16 and x f32: the add of a LoRA patch
+// (lora.rs:126), ggml's add_q_f32 / add_f16_f32.  dst has W's type; same shape only, as upstream asserts.
+void op_add_lowp(ggml_tensor *dst) {
+    const ggml_tensor *a = dst->src[0], *b = dst->src[1];
+    if (kt_of(a->type) >= 0)
+        die("add: '%s' is %s: LoRA on K-quant weights is not supported (targets may be Q4_0, Q4_1, Q5_0, Q5_1, Q8_0 or F16)",
+            a->name, ggml_type_name(a->type));
+    const int qt = qt_of(a->type);
+    if (qt < 0 && a->type != GGML_TYPE_F16)
+        die("add: '%s' is %s: no device add for this src0 type", a->name, ggml_type_name(a->type));
+    bool same = true;
+    for (int i = 0; i < 4; i++) same = same && a->ne[i] == b->ne[i] && a->ne[i] == dst->ne[i];
+    if (!same)
+        die("add: '%s' (%s, [%lld, %lld, %lld, %lld]) and '%s' ([%lld, %lld, %lld, %lld]) must have the same shape when src0 "
+            "is not f32",
+            a->name, ggml_type_name(a->type), (long long)a->ne[0], (long long)a->ne[1], (long long)a->ne[2],
+            (long long)a->ne[3], b->name, (long long)b->ne[0], (long long)b->ne[1], (long long)b->ne[2], (long long)b->ne[3]);
+    if (b->type != GGML_TYPE_F32 || dst->type != a->type)
+        die("add: '%s' (%s) + '%s' (%s) -> %s: the second operand must be f32 and the result of the first operand's type",
+            a->name, ggml_type_name(a->type), b->name, ggml_type_name(b->type), ggml_type_name(dst->type));
+    const size_t es = ggml_type_size(a->type);
+    BK_ASSERT(b->nb[0] == 4 && a->nb[0] == es && dst->nb[0] == es);
+    const TView va = view_of(a), vb = view_of(b), vd = view_of(dst);
+    BK_ASSERT((((uintptr_t)va.p | (uintptr_t)vd.p | a->nb[1] | a->nb[2] | a->nb[3] | dst->nb[1] | dst->nb[2] | dst->nb[3]) & 1) == 0);
+    BK_ASSERT((((uintptr_t)vb.p | b->nb[1] | b->nb[2] | b->nb[3]) & 3) == 0);
+    const int64_t n = ggml_nelements(a);
+    if (n == 0) return;
+    if (a->type == GGML_TYPE_F16) {
+        Timed tm(GGML_HIP_KCLASS_OTHER, (double)n * 8);
+        hipLaunchKernelGGL(k_add_f16, grid1(n), dim3(256), 0, g.stream, va, vb, vd, n);
+    } else {
+        BK_ASSERT(a->ne[0] % 32 == 0);
+        const int64_t bpr = a->ne[0] / 32, nblocks = n / 32;
+        Timed tm(GGML_HIP_KCLASS_OTHER, (double)nblocks * (2.0 * (double)es + 128.0));
+        switch (a->type) {
+            case GGML_TYPE_Q4_0: hipLaunchKernelGGL(k_add_q<GGML_TYPE_Q4_0>, grid1(nblocks), dim3(256), 0, g.stream, va, vb, vd, bpr, nblocks); break;
+            case GGML_TYPE_Q4_1: hipLaunchKernelGGL(k_add_q<GGML_TYPE_Q4_1>, grid1(nblocks), dim3(256), 0, g.stream, va, vb, vd, bpr, nblocks); break;
+            case GGML_TYPE_Q5_0: hipLaunchKernelGGL(k_add_q<GGML_TYPE_Q5_0>, grid1(nblocks), dim3(256), 0, g.stream, va, vb, vd, bpr, nblocks); break;
+            case GGML_TYPE_Q5_1: hipLaunchKernelGGL(k_add_q<GGML_TYPE_Q5_1>, grid1(nblocks), dim3(256), 0, g.stream, va, vb, vd, bpr, nblocks); break;
+            default: hipLaunchKernelGGL(k_add_q<GGML_TYPE_Q8_0>, grid1(nblocks), dim3(256), 0, g.stream, va, vb, vd, bpr, nblocks); break;
+        }
+    }
+    HIP_CHECK(hipGetLastError());
+}
+
 void op_unary(ggml_tensor *dst, const ggml_tensor *mul_b /* nullable: fused silu*b */, ggml_tensor *out) {
     const ggml_tensor *a = dst->src[0];
     const int32_t uop = dst->op_params[0];

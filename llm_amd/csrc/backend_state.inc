@@ -173,6 +173,7 @@ struct Backend {
     int opt_test_fused_timeout = 0;  // test hook: layer 0's attention workgroups of k_qkv_attn poll granules nobody writes
     uint64_t stat_fused_timeouts = 0;
     uint64_t ns_match = 0, ns_launch = 0, ns_wait = 0, ns_compute = 0;  // host-side time split of plan tokens
+    uint64_t ns_mirror = 0, stat_mirror_bytes = 0;  // generic graphs: host ns in download_outputs (waits for the graph), bytes mirrored
     size_t dead_shadow_bytes = 0;
     uint64_t arena_seen = 0;  // the last event of the process-wide arena log this slot has applied (sync_arenas)
     void *prep = nullptr;  // PrepMatch (llama_plan.inc): the match of a graph handed over by ggml_hip_graph_prepare, waiting for its begin()
@@ -590,6 +591,16 @@ char *arena_dev(Arena *a) {
     return a->dev;
 }
 
+// Host tensors staged raw into the workspace for the current graph only (the src0 leaves of a quantized / f16 ADD, the
+// LoRA patch: backend_executor.inc stage_add_targets).  Emptied with the workspace (ws_reset).
+struct Staged {
+    uintptr_t host;
+    size_t nbytes;
+    char *dev;
+};
+std::vector<Staged> g_staged_[GGML_HIP_MAX_BACKENDS];
+#define g_staged (g_staged_[g.slot])
+
 // device address of the raw bytes of `t` (strided views included). Aborts for SoA weights.
 char *dev_ptr(const ggml_tensor *t) {
     if (DevTensor *e = extra_of(t)) {
@@ -598,6 +609,8 @@ char *dev_ptr(const ggml_tensor *t) {
     }
     const uintptr_t p = (uintptr_t)t->data;
     if (p == 0) die("tensor '%s' has no data", t->name);
+    for (const Staged &st : g_staged)
+        if (p >= st.host && p < st.host + st.nbytes) return st.dev + (p - st.host);
     if (DevTensor *e = find_tensor(p)) {
         if (e->soa) die("tensor '%s' aliases a re-laid-out quantized weight", t->name);
         return e->dev + (p - e->host);
@@ -657,6 +670,7 @@ char *ws_alloc(size_t bytes) {
 // called at the start of every graph: rewind, and merge chunks that were added during the last graph
 void ws_reset() {
     g.ws_off = 0;
+    g_staged.clear();
     if (g.ws_chunks.size() <= 1) return;
     HIP_CHECK(hipStreamSynchronize(g.stream));
     size_t total = 0;

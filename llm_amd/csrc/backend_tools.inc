@@ -494,6 +494,8 @@ int64_t ggml_hip_get_stat(const char *key) {
     if (k == "ns_launch") return (int64_t)g.ns_launch;    // ... enqueueing (param upload, graph launch, read-back queue)
     if (k == "ns_wait") return (int64_t)g.ns_wait;        // ... waiting for the device + copying results out
     if (k == "ns_compute") return (int64_t)g.ns_compute;  // total inside ggml_graph_compute
+    if (k == "ns_mirror") return (int64_t)g.ns_mirror;    // generic graphs: download_outputs (the wait for the graph included)
+    if (k == "mirror_bytes") return (int64_t)g.stat_mirror_bytes;  // ... bytes of CPU-backend nodes copied back
     return -1;
 }
 size_t ggml_hip_read_timeline(int64_t *dst, size_t max_records) {

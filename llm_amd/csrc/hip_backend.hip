@@ -42,6 +42,7 @@
 #include "kernels/kquant.h"
 #include "kernels/kquant2.h"
 #include "kernels/quantize.h"
+#include "kernels/lora.h"
 #include "kernels/topk.h"
 #include "kernels/gemm_f16.h"
 #include "kernels/ops.h"

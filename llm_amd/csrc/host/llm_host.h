@@ -76,7 +76,7 @@ GGML_API int llm_model_stages(const llm_model *m, int *layer_begin, int *layer_e
 typedef struct llm_ggml_file llm_ggml_file;
 GGML_API llm_ggml_file *llm_ggml_file_open(const char *path);
 GGML_API void llm_ggml_file_close(llm_ggml_file *f);
-/* container: 0 ggml, 1 ggmf, 2 ggjt, 3 ggla; hp may be NULL */
+/* container: 0 ggml, 1 ggmf, 2 ggjt, 3 ggla (hp all zero: a ggla file carries r and alpha, llm_ggml_file_lora); hp may be NULL */
 GGML_API void llm_ggml_file_info(const llm_ggml_file *f, int *container, int *version, llm_llama_hparams *hp,
                                  int *n_tensors, int *n_vocab_entries);
 /* i-th tensor in file order; desc->name / desc->data point into the mapping (valid until close) */
@@ -85,6 +85,17 @@ GGML_API int llm_ggml_file_tensor(const llm_ggml_file *f, int i, llm_tensor_desc
 GGML_API int llm_ggml_file_vocab(const llm_ggml_file *f, int i, char *buf, int cap, float *score);
 /* llm::load for LLaMA: open + Llama::new over the mapping (kept alive by the model); hyperparameters from the file */
 GGML_API llm_model *llm_llama_load(const char *path, const llm_model_params *params);
+/* A ggla file (a LoRA adapter): returns 0 and its LoraParameters r and alpha; -1 for every other container */
+GGML_API int llm_ggml_file_lora(const llm_ggml_file *f, int *r, int *alpha);
+/* llm::load for LLaMA with ModelParameters::lora_adapters (crates/llm-base/src/loader.rs:486-531, 651-670): opens every
+ * adapter, reads the model into a buffer the model owns (no mmap), patches each tensor named by an adapter with
+ * LoraAdapter::patch's graph (lora.rs:71-141: W = W + (alpha / r) * mul_mat(A, B), computed through this library's ggml
+ * in a CPU context, every adapter in the order given), then Llama::new.  NULL after a LoadError-style message. */
+GGML_API llm_model *llm_llama_load_lora(const char *path, const llm_model_params *params, const char *const *lora_paths,
+                                        int n_lora);
+/* Accumulated host ns of llm_llama_load_lora: [0] model read, [1] adapter open, [2] patching as a whole, [3] the copies of
+ * the patched tensors over the weights (part of [2]); reset != 0 clears them after the read */
+GGML_API void llm_lora_timing(double *out4, int reset);
 GGML_API llm_session *llm_start_session(llm_model *m, const llm_session_config *cfg);
 /* a session of an unsplit model on another device slot of the model's GPU: own stream / shadows / K/V / plans, shared weights */
 GGML_API llm_session *llm_start_session_on(llm_model *m, const llm_session_config *cfg, int slot);

@@ -52,6 +52,11 @@ def _lib():
         L.llm_ggml_file_vocab.argtypes = [C.c_void_p, C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_float)]
         L.llm_llama_load.restype = C.c_void_p
         L.llm_llama_load.argtypes = [C.c_char_p, C.POINTER(_MP)]
+        L.llm_llama_load_lora.restype = C.c_void_p
+        L.llm_llama_load_lora.argtypes = [C.c_char_p, C.POINTER(_MP), C.POINTER(C.c_char_p), C.c_int]
+        L.llm_ggml_file_lora.restype = C.c_int
+        L.llm_ggml_file_lora.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        L.llm_lora_timing.argtypes = [C.POINTER(C.c_double), C.c_int]
         L.llm_start_session.restype = C.c_void_p
         L.llm_start_session.argtypes = [C.c_void_p, C.POINTER(_SC)]
         L.llm_session_free.argtypes = [C.c_void_p]
@@ -161,16 +166,22 @@ class Llama:
         self.ptr = L.llm_llama_new(C.byref(h), C.byref(mp), descs, len(shapes))
 
     @classmethod
-    def load(cls, path, context_size=2048, gpu_layers=-1, n_gqa=0):
+    def load(cls, path, context_size=2048, gpu_layers=-1, n_gqa=0, lora=()):
         """llm::load::<Llama>(path, …, ModelParameters{prefer_mmap: true, use_gpu: true}): the C++ container reader
-        (llm_ggml_file_open) maps the GGML/GGMF/GGJT file and the tensors point into the mapping."""
+        (llm_ggml_file_open) maps the GGML/GGMF/GGJT file and the tensors point into the mapping.
+        lora: paths of ggla adapters (ModelParameters::lora_adapters), applied in order at load time
+        (llm_llama_load_lora: the model is read into a buffer it owns, no mapping)."""
         L = _lib()
         info = inspect_file(path)
         if info is None:
             raise ValueError(f"{path}: not a loadable GGML-family container")
         self = cls.__new__(cls)
         mp = _MP(context_size, 1, gpu_layers, 0, 1.0, 10000, 0, -1, n_gqa)  # n_gqa: ModelParameters::n_gqa (80 layers and more)
-        self.ptr = L.llm_llama_load(str(path).encode(), C.byref(mp))
+        if lora:
+            paths = (C.c_char_p * len(lora))(*[str(p).encode() for p in lora])
+            self.ptr = L.llm_llama_load_lora(str(path).encode(), C.byref(mp), paths, len(lora))
+        else:
+            self.ptr = L.llm_llama_load(str(path).encode(), C.byref(mp))
         if not self.ptr:
             raise ValueError(f"{path}: load failed")
         h = info["hp"]

@@ -156,3 +156,25 @@ def write_ggjt(path, hp, w, container="ggjt", version=3, vocab=None):
                 pos = f.tell()
                 f.write(b"\0" * (((pos + 31) & ~31) - pos))
             f.write(np.ascontiguousarray(w[name]).tobytes())
+
+
+def write_ggla(path, r, alpha, tensors, version=1):
+    """Writes a LoRA adapter as llama.cpp's convert-lora-to-ggml.py does and the reference reads it
+    (crates/ggml/src/format/loader.rs:160-209, crates/llm-base/src/lora.rs:28-34): magic 'ggla', u32 version, i32 r,
+    i32 alpha, no vocabulary, then per tensor (i32 n_dims, i32 name_len, u32 type, i32 dims[], name, padding to a 32-byte
+    boundary, data).  `tensors`: {name: 2-D ndarray [ne1, ne0]}, f32 or f16 (the element type follows the dtype); the
+    writer's layout is `<model tensor>.loraA` [r, n_in] (f32 or f16) and `<model tensor>.loraB` [r, n_out] (f32)."""
+    import struct
+    with open(path, "wb") as f:
+        f.write(struct.pack("<IIii", 0x67676C61, version, r, alpha))
+        for name, arr in tensors.items():
+            arr = np.ascontiguousarray(arr)
+            typ = {np.dtype(np.float32): ggml.TYPE_F32, np.dtype(np.float16): ggml.TYPE_F16}[arr.dtype]
+            dims = tuple(reversed(arr.shape))
+            nb = name.encode()
+            f.write(struct.pack("<iiI", len(dims), len(nb), typ))
+            f.write(struct.pack(f"<{len(dims)}i", *dims))
+            f.write(nb)
+            pos = f.tell()
+            f.write(b"\0" * (((pos + 31) & ~31) - pos))
+            f.write(arr.tobytes())
