@@ -600,6 +600,15 @@ GGML_API size_t ggml_hip_read_timeline(int64_t *dst, size_t max_records);
  * mem_v [Egqa][C] f16, out [N][E] f32.  0 on success, -1 if the shape is not accepted. */
 GGML_API int ggml_hip_debug_prompt_attention(const float *q, const uint16_t *mem_k, const uint16_t *mem_v, float *out, int N, int E,
                                              int Egqa, int H, int n_past, int64_t C, float scale, int fused);
+/* Test hook: the fused prompt attention in the form the prompt plan launches it: q_raw [N][E] f32 is the UN-rotated wq product,
+ * q_raw2 (may be NULL) the second partial of a K-split GEMM, added first; rope [N][128] f32 holds (cos, sin) per pair and token
+ * (the plan's RoPE table), applied while Q is staged; the result leaves as wo's GEMM operand x16 [N][E] f16: every 32-channel
+ * block re-quantized to Q8 (block scale rounded to f16 first when f16d != 0) and stored as f16(d * q) in the GEMM's k order.
+ * x16 and out (f32 [N][E], may be NULL: the plain form's output buffer, which this form leaves unwritten) hold their elements
+ * and 256 bytes more; both are 0xFF bytes before the launch and come back whole.  0 on success, -1 if the shape is not accepted. */
+GGML_API int ggml_hip_debug_prompt_attention_plan(const float *q_raw, const float *q_raw2, const float *rope, const uint16_t *mem_k,
+                                                  const uint16_t *mem_v, uint16_t *x16, float *out, int N, int E, int Egqa, int H,
+                                                  int n_past, int64_t C, float scale, int f16d);
 /* Test hook: the fused prompt attention's exponential against expf over ALL f16 arguments: out_fast[i] = f16(exp_le0(x_i)),
  * out_ref[i] = f16(expf(x_i)) for the 65536 f16 bit patterns i (65536 f16 bit patterns each).  The softmax only ever passes
  * x <= 0 or NaN (crates/models/llama/src/lib.rs:272-280: soft_max over masked, scaled scores).  Returns 0. */

@@ -420,6 +420,40 @@ int ggml_hip_debug_mat_vec_kbig(const struct ggml_tensor *w0, const struct ggml_
     return 0;
 }
 
+// Test hook: the fused prompt attention in the form plan_launch_prompt launches it (llama_plan.inc: prompt_attention(true, ...)
+// with x16_out, rope and q_part set): q_raw [N][E] f32 the un-rotated wq product, q_raw2 (nullable) its second K-split partial —
+// uploaded N * E floats behind the first, q_part = N * E as the plan's qkv_stride is a distance inside one buffer; rope [N][128]
+// f32, (cos, sin) per pair in k_rope_table's layout; mem_k [C][Egqa] / mem_v [Egqa][C] f16 of one layer; f16d: the block scale
+// rounded to f16 first.  x16 [N][E] f16 (+ guard): wo's GEMM operand; out [N][E] f32 (+ guard, nullable): the buffer handed over
+// as `out`, which this form does not write.  Both are 0xFF before the launch and come back whole, guard included.  Returns 0,
+// or -1 for a shape the fused kernel does not take.
+int ggml_hip_debug_prompt_attention_plan(const float *q_raw, const float *q_raw2, const float *rope, const uint16_t *mem_k,
+                                         const uint16_t *mem_v, uint16_t *x16, float *out, int N, int E, int Egqa, int H, int n_past,
+                                         int64_t C, float scale, int f16d) {
+    SlotLock lk;
+    ensure_init();
+    finish_pending();
+    if (!q_raw || !rope || !mem_k || !mem_v || !x16 || N < 1 || H < 1 || E % H || n_past < 0) return -1;
+    const int64_t D = E / H, T = (int64_t)n_past + N;
+    if (Egqa < D || Egqa % D || H % (Egqa / D) || T > C || C % 8 || !prompt_attn_fits(D, T)) return -1;
+    const int64_t Hkv = Egqa / D;
+    std::vector<char *> owned;
+    const size_t nq = (size_t)N * E * 4, nkv = (size_t)C * Egqa * 2, nx = (size_t)N * E * 2;
+    char *dq = debug_buf(nq * (q_raw2 ? 2 : 1), nullptr, owned);
+    h2d_bulk(dq, q_raw, nq);
+    if (q_raw2) h2d_bulk(dq + nq, q_raw2, nq);
+    char *dr = debug_buf((size_t)N * 128 * 4, rope, owned);
+    char *dk = debug_buf(nkv, mem_k, owned), *dv = debug_buf(nkv, mem_v, owned);
+    char *dx = debug_buf(nx, nullptr, owned), *dout = debug_buf(nq, nullptr, owned);
+    prompt_attention(true, (const float *)dq, (const __half *)dk, (const __half *)dv, (float *)dout, nullptr, nullptr, N, E, Egqa, H, Hkv,
+                     D, n_past, C, scale, (_Float16 *)dx, f16d != 0, (const float *)dr, q_raw2 ? (int64_t)N * E : 0);
+    d2h_queue(x16, dx, nx + DEBUG_GUARD);
+    if (out) d2h_queue(out, dout, nq + DEBUG_GUARD);
+    d2h_finish();
+    for (char *b : owned) HIP_CHECK(hipFree(b));
+    return 0;
+}
+
 // Test hook: f16(exp_le0(x)) (kernels/prompt_attn.h: the fused prompt attention's exponential) and f16(expf(x)) (what k_p_soft_max
 // and ggml's table hold) for ALL 65536 f16 bit patterns x; out_fast / out_ref: 65536 f16 bit patterns each.
 __global__ void __launch_bounds__(256) k_debug_exp_le0(uint16_t *out_fast, uint16_t *out_ref) {

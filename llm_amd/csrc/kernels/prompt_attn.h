@@ -59,6 +59,17 @@ __device__ __forceinline__ float exp_le0(const float x0) {
     return __builtin_amdgcn_ldexpf(__builtin_amdgcn_exp2f(a_), (int)e);
 }
 
+// p = f16(f32(e * inv)): ggml's soft_max stores the f32 product and the V mat-mul converts THAT to f16, two roundings.  Written as
+// (_Float16)(e * inv) the compiler selects v_fma_mixlo_f16 — the product rounded ONCE, straight to f16 (-ffp-contract=off does not
+// stop it: no addend is contracted) — which lands one f16 ulp off wherever the f32 rounding moves the product onto an f16 tie
+// (tests/test_prompt_attn_gpu.py found it: exact scores, T = 17, p 0x1270 expected, 0x126f computed).  The empty asm makes the f32
+// product a value of its own; k_p_soft_max's product already is one (it feeds an f32 store as well).
+__device__ __forceinline__ _Float16 f16_of_f32_product(float a, float b) {
+    float t = a * b;
+    asm("" : "+v"(t));
+    return (_Float16)t;
+}
+
 // QR = queries per workgroup: 32, or 16 for rows too long for 32 score rows in LDS (T up to ~2300 keys: the last chunks of a
 // 2048-token context; the MFMA tiles stay 32 rows high, their upper half computes on duplicated queries and is dropped)
 template <int D, bool INSTR = false, int QR = PATTN_Q>
@@ -253,7 +264,7 @@ __global__ void __launch_bounds__(256, 2) k_p_attn(const PAttnArgs a) {
                 for (int rr = 0; rr < RW; rr++) x[rr] = ((const float *)rp[rr])[min(i, npad - 1)];
                 _Float16 pr[RW];
 #pragma unroll
-                for (int rr = 0; rr < RW; rr++) pr[rr] = (_Float16)((i <= lim0 + rr ? x[rr] : 0.0f) * inv[rr]);
+                for (int rr = 0; rr < RW; rr++) pr[rr] = f16_of_f32_product(i <= lim0 + rr ? x[rr] : 0.0f, inv[rr]);
                 if (i < npad) {
 #pragma unroll
                     for (int rr = 0; rr < RW; rr++) ((_Float16 *)rp[rr])[i] = pr[rr];
@@ -269,7 +280,7 @@ __global__ void __launch_bounds__(256, 2) k_p_attn(const PAttnArgs a) {
                 for (int rr = 0; rr < RW; rr++)
                     if (rr < nrow && i < npad) {
                         const float e = i <= lim0 + rr ? x[rr] : 0.0f;
-                        ((_Float16 *)(lds + (row0 + rr) * rb))[i] = (_Float16)(e * inv[rr]);
+                        ((_Float16 *)(lds + (row0 + rr) * rb))[i] = f16_of_f32_product(e, inv[rr]);
                     }
             }
         }

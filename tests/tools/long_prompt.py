@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """A 2048-token prompt fed in four 512-token batches (LLaMA-7B Q4_0 synthetic): milliseconds per batch with the fused prompt
-attention (32 queries per workgroup up to 1184 keys, 16 beyond) and with the three-launch attention.
+attention (32 queries per workgroup up to 1152 keys, 16 beyond) and with the three-launch attention.
 python tests/tools/long_prompt.py"""
 import os
 import sys
