@@ -578,6 +578,15 @@ GGML_API int ggml_hip_decode_greedy_chain(struct ggml_cgraph *last, int n, int32
  * pairs instead of n_vocab logits; only those pairs cross PCIe.  Returns 0, -1 on bad arguments. */
 GGML_API int ggml_hip_topk(const struct ggml_tensor *t, int64_t row, int k, const int32_t *extra_ids, int n_extra,
                            float *out_vals, int32_t *out_ids);
+/* Probability of one target per logits row on the device: out_probs[i] = util::softmax(row)[targets[i]] of the reference
+ * (crates/llm-base/src/util.rs:143-151) for the rows row_begin .. row_begin + n_rows - 1 of the 2-D f32 tensor `logits` — a
+ * node of the caller's most recent ggml_graph_compute, or a tensor handed to ggml_hip_transform_tensor.  What
+ * InferenceSession::perplexity (inference_session.rs:577-583) takes from every counted position: n_rows floats cross PCIe
+ * instead of n_rows * ne0.  A target whose probability underflows gives 0, a row holding NaN gives NaN.  Returns 0, or -1 on
+ * bad arguments (NULL pointers, n_rows < 1, row_begin < 0, rows beyond ne1, a tensor that is not F32 / 2-D / on the device, a
+ * target outside [0, ne0)); everything but the device image is checked before the device is touched. */
+GGML_API int ggml_hip_row_probs(const struct ggml_tensor *logits, int64_t row_begin, int64_t n_rows, const int32_t *targets,
+                                float *out_probs);
 /* ggml_quantize_q4_0 / q4_1 / q5_0 / q5_1 / q8_0 (crates/ggml/src/lib.rs:419-483, called by
  * crates/llm-base/src/quantize.rs:363-379) computed on the device: n f32 values at `src` (host memory, rows
  * of k, k % 32 == 0) -> raw GGML blocks at `dst` (host memory), byte-identical to the host functions; the 16-bin

@@ -44,6 +44,7 @@
 #include "kernels/quantize.h"
 #include "kernels/lora.h"
 #include "kernels/topk.h"
+#include "kernels/nll.h"
 #include "kernels/gemm_f16.h"
 #include "kernels/ops.h"
 #include "kernels/decode.h"
@@ -485,6 +486,42 @@ int ggml_hip_topk(const struct ggml_tensor *t, int64_t row, int k, const int32_t
     }
     d2h_queue(out_vals, (const char *)dv, (size_t)(k + n_extra) * 4);
     d2h_queue(out_ids, (const char *)di, (size_t)(k + n_extra) * 4);
+    d2h_finish();
+    return 0;
+}
+
+// ---- probability of one target per logits row (kernels/nll.h): util::softmax(row)[target] without reading the row back ----
+int ggml_hip_row_probs(const struct ggml_tensor *t, int64_t row_begin, int64_t n_rows, const int32_t *targets, float *out_probs) {
+    // everything that can be refused without a device is refused before the slot is locked or initialised
+    if (!t || !targets || !out_probs || n_rows < 1 || row_begin < 0 || t->type != GGML_TYPE_F32 || t->nb[0] != 4 || t->ne[2] != 1 ||
+        t->ne[3] != 1 || t->ne[0] < 1 || t->ne[0] > (1 << 30) || n_rows > t->ne[1] || row_begin > t->ne[1] - n_rows ||
+        n_rows > 0x7FFFFFFF || t->nb[1] % 4 != 0 || t->nb[1] < (size_t)t->ne[0] * 4 || t->data == nullptr)
+        return -1;
+    for (int64_t r = 0; r < n_rows; r++)
+        if (targets[r] < 0 || targets[r] >= t->ne[0]) return -1;  // never a read outside the row
+    SlotLock lk;
+    ensure_init();
+    {   // the tensor must have a device image (a record or an arena shadow); dev_ptr would abort otherwise
+        DevTensor *e = extra_of(t);
+        if (!e) e = find_tensor((uintptr_t)t->data);
+        if (e ? e->soa : find_arena((uintptr_t)t->data) == nullptr) return -1;
+    }
+    finish_pending();
+    const float *x = (const float *)(dev_ptr(t) + row_begin * (int64_t)t->nb[1]);
+    const int V = (int)t->ne[0];
+    char *buf = ws_alloc((size_t)n_rows * 8 + 64);
+    float *dp = (float *)buf;
+    int *dt = (int *)(buf + (size_t)n_rows * 4);
+    h2d_small((char *)dt, targets, (size_t)n_rows * 4);  // through pinned staging (the bulk ring beyond its bump region), never from caller pages
+    {
+        Timed tm(GGML_HIP_KCLASS_OTHER, (double)n_rows * V * 4);
+        const long long stride = (long long)(t->nb[1] / 4);
+        const bool keep = V <= ROW_PROB_KEEP * 1024, vec = keep && V % 4 == 0 && stride % 4 == 0 && (uintptr_t)x % 16 == 0;
+        auto kern = vec ? k_row_prob<true, true> : keep ? k_row_prob<true, false> : k_row_prob<false, false>;
+        hipLaunchKernelGGL(kern, dim3((unsigned)n_rows), dim3(1024), 0, g.stream, x, stride, V, (const int *)dt, dp);
+        HIP_CHECK(hipGetLastError());
+    }
+    d2h_queue(out_probs, (const char *)dp, (size_t)n_rows * 4);
     d2h_finish();
     return 0;
 }

@@ -581,6 +581,12 @@ struct HomeDevice {
             go(home);
     }
 };
+// May an evaluation of `len` tokens whose logits nobody looks at be only enqueued (InferenceSession::pipeline_chunk)?  Unsplit
+// models, more than one token, LLM_HOST_PIPELINE_CHUNKS != 0: the one rule of llm_feed_prompt and llm_evaluate_flags.
+bool may_pipeline_chunk(const llm_model *m, size_t len) {
+    static const bool pipeline_on = !(getenv("LLM_HOST_PIPELINE_CHUNKS") && atoi(getenv("LLM_HOST_PIPELINE_CHUNKS")) == 0);
+    return pipeline_on && m->stages.empty() && len > 1;
+}
 void model_evaluate(llm_model *m, llm_session *s, const std::vector<llm::TokenId> &toks, llm::OutputRequest &req) {
     HomeDevice hd;
     if (m->stages.empty()) {
@@ -1238,8 +1244,7 @@ void llm_feed_prompt(llm_model *m, llm_session *s, const int32_t *tokens, int n)
         // every chunk but the last is only enqueued (unsplit models): the host builds and matches the next chunk's graph while the
         // device runs this one, instead of waiting for it and for a row of logits nobody can see
         llm::OutputRequest req;
-        static const bool pipeline_on = !(getenv("LLM_HOST_PIPELINE_CHUNKS") && atoi(getenv("LLM_HOST_PIPELINE_CHUNKS")) == 0);
-        const bool more = pipeline_on && i + len < (size_t)n && m->stages.empty() && len > 1;
+        const bool more = i + len < (size_t)n && may_pipeline_chunk(m, len);
         req.intermediate_chunk = more;
         s->s->pipeline_chunk = more;
         model_evaluate(m, s, batch, req);
@@ -1575,6 +1580,56 @@ int llm_session_topk(const llm_session *s, int k, const int32_t *extra_ids, int 
     hd.go(s->stage_sessions.empty() ? s->device : s->devices.back());
     return ggml_hip_topk(t, t->ne[1] - 1, k, extra_ids, n_extra, out_vals, out_ids);
 }
+
+// ---- what InferenceSession::perplexity (host/llm_perplexity.cpp) needs from this translation unit ----
+// Model::evaluate with the two extensions of OutputRequest spelled out.  flags & 1: logits_on_device (the [n_vocab, n] logits
+// stay in HBM, last_logits is not refreshed); flags & 2: intermediate_chunk (nobody looks at this evaluation's logits before the
+// next one: it is only enqueued where feed_prompt would do so: unsplit model, more than one token).  all_logits: nullable.
+void llm_evaluate_flags(llm_model *m, llm_session *s, const int32_t *tokens, int n, int flags, float *all_logits) {
+    std::vector<llm::TokenId> toks(tokens, tokens + n);
+    std::vector<float> logits;
+    llm::OutputRequest req;
+    if (all_logits) req.all_logits = &logits;
+    req.logits_on_device = (flags & 1) != 0;
+    const bool more = (flags & 2) != 0 && !all_logits && may_pipeline_chunk(m, (size_t)n);
+    req.intermediate_chunk = more;
+    s->s->pipeline_chunk = more;
+    model_evaluate(m, s, toks, req);
+    s->s->pipeline_chunk = false;
+    if (all_logits) memcpy(all_logits, logits.data(), logits.size() * sizeof(float));
+}
+// The logits node of the last evaluated graph (its last node: [n_vocab, n] f32) and the device slot that owns it (the last
+// stage's for a layer-split model); NULL if there is no evaluated graph.
+const struct ggml_tensor *llm_session_logits_node(const llm_session *s, int *device_slot) {
+    ggml_cgraph *g = s->s->last_graph;
+    if (!g || g->n_nodes < 1) return nullptr;
+    const ggml_tensor *t = g->nodes[g->n_nodes - 1];
+    if (t->type != GGML_TYPE_F32 || (size_t)t->ne[0] != s->s->last_logits.size()) return nullptr;
+    if (device_slot) *device_slot = s->stage_sessions.empty() ? s->device : s->devices.back();
+    return t;
+}
+// common::read_last_token (model/common.rs:6-19) for an evaluation that left its logits on the device: the last row of the
+// logits node -> last_logits (n_vocab floats).  0, or -1 if there is no evaluated graph.
+int llm_session_fetch_last_logits(llm_session *s) {
+    int slot = 0;
+    const ggml_tensor *t = llm_session_logits_node(s, &slot);
+    if (!t) return -1;
+    HomeDevice hd;
+    hd.go(slot);
+    const size_t row = (size_t)t->ne[0] * sizeof(float);
+    ggml_hip_tensor_get(t, s->s->last_logits.data(), row * (size_t)(t->ne[1] - 1), row);
+    return 0;
+}
+// HomeDevice for callers outside this translation unit: the thread goes to device slot `slot` until the scope is closed, which
+// leaves the caller's main device as it was found.  Scopes nest; close them in reverse order.
+llm_device_scope *llm_device_scope_open(int slot) {
+    HomeDevice *hd = new HomeDevice();
+    hd->go(slot);
+    return reinterpret_cast<llm_device_scope *>(hd);
+}
+void llm_device_scope_close(llm_device_scope *scope) { delete reinterpret_cast<HomeDevice *>(scope); }
+int llm_model_context_size(const llm_model *m) { return (int)m->llama->params.context_size; }
+int llm_session_n_batch(const llm_session *s) { return (int)s->s->config.n_batch; }
 
 // Synthetic GGML blocks for full-size benchmarks (no checkpoints are obtainable offline): uniform random
 // quants, f16 scale d = d_scale*(0.5+u), and for the *_1 types a min that centres the block.  Fills

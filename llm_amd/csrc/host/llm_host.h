@@ -151,6 +151,29 @@ GGML_API int llm_session_topk(const llm_session *s, int k, const int32_t *extra_
                               int32_t *out_ids);
 GGML_API size_t llm_session_read_node(const llm_session *s, int index, const char *name, int occurrence, void *dst,
                                       size_t max_bytes);
+/* Model::evaluate with the extensions of OutputRequest as flags: 1 = logits_on_device (the logits stay in HBM, last_logits is
+ * not refreshed), 2 = intermediate_chunk (only enqueued where feed_prompt would do so); all_logits nullable (n * n_vocab) */
+GGML_API void llm_evaluate_flags(llm_model *m, llm_session *s, const int32_t *tokens, int n, int flags, float *all_logits);
+/* the logits node ([n_vocab, n] f32) of the last evaluated graph and the device slot that owns it; NULL without a graph */
+GGML_API const struct ggml_tensor *llm_session_logits_node(const llm_session *s, int *device_slot);
+/* read_last_token after an evaluation that left its logits on the device: last row of the logits node -> last_logits */
+GGML_API int llm_session_fetch_last_logits(llm_session *s);
+/* the thread works on device slot `slot` until the scope is closed; the caller's main device is then as it was found */
+typedef struct llm_device_scope llm_device_scope;
+GGML_API llm_device_scope *llm_device_scope_open(int slot);
+GGML_API void llm_device_scope_close(llm_device_scope *scope);
+GGML_API int llm_model_context_size(const llm_model *m);
+GGML_API int llm_session_n_batch(const llm_session *s);
+/* InferenceSession::perplexity (inference_session.rs:519-589; host/llm_perplexity.cpp) over n token ids.  Returns
+ * n_chunk = n / context_size; out_perplexity[i] (first `cap` chunks) is what the reference hands to perplexity_callback(i, .):
+ * the RUNNING exp(nll / count); out_probs (nullable) receives the probability of every counted position in order,
+ * n_chunk * (context_size - 1 - first) floats, first = min(512, context_size / 2).  bos_token replaces the first token of
+ * every chunk for the evaluation (the reference's bot_token_id().unwrap_or(1)); `tokens` is unchanged on return.
+ * -1 if bos_token or a token of a chunk lies outside [0, n_vocab) (nothing is evaluated then).
+ * on_device = 1: the logits stay in HBM and ggml_hip_row_probs reduces each counted row to its target's probability;
+ * 0: the reference's shape, all logits read back and util::softmax on the host.  Every chunk starts at n_past = 0. */
+GGML_API int llm_session_perplexity(llm_model *m, llm_session *s, const int32_t *tokens, int n, int32_t bos_token,
+                                    int on_device, float *out_perplexity, int cap, float *out_probs);
 /* synthetic GGML blocks for full-size benchmarks (deterministic in seed and block index) */
 GGML_API void llm_synth_blocks(int type, void *dst, int64_t nblocks, uint64_t seed, float d_scale);
 /* BASELINE.md section 4 weights at full size: ne1 rows of ne0 gaussians N(0, std^2) (counter-based generator, deterministic

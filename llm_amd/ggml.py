@@ -249,6 +249,7 @@ PROTOTYPES.update({
     "ggml_hip_debug_exp_le0": (C.c_int, [C.c_void_p, C.c_void_p]),
     "ggml_hip_decode_greedy_chain": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "ggml_hip_topk": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "ggml_hip_row_probs": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
     "ggml_hip_quantize": (C.c_size_t, [C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
     "ggml_hip_quantize_resident": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "ggml_hip_graph_compute_begin": (C.c_int, [C.c_void_p]),
@@ -337,6 +338,19 @@ def topk(tensor, row, k, extra_ids=()):
     if rc != 0:
         raise ValueError("ggml_hip_topk: bad arguments")
     return vals, ids
+
+
+def row_probs(node, targets, row_begin=0):
+    """ggml_hip_row_probs: util::softmax(row)[target] (crates/llm-base/src/util.rs:143-151) of the rows row_begin ..
+    row_begin + len(targets) - 1 of a 2-D f32 tensor that lives on the device (a node of the last computed graph, normally
+    the logits), reduced on the device: one float per row is read back."""
+    targets = np.ascontiguousarray(targets, dtype=np.int32)
+    out = np.zeros(targets.size, dtype=np.float32)
+    ptr = node.ptr if isinstance(node, Tensor) else node
+    rc = lib().ggml_hip_row_probs(ptr, row_begin, targets.size, targets.ctypes.data if targets.size else None, out.ctypes.data)
+    if rc != 0:
+        raise ValueError("ggml_hip_row_probs: bad arguments")
+    return out
 
 
 class Tensor:

@@ -95,6 +95,9 @@ def _lib():
         L.llm_session_topk.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         L.llm_session_read_node.restype = C.c_size_t
         L.llm_session_read_node.argtypes = [C.c_void_p, C.c_int, C.c_char_p, C.c_int, C.c_void_p, C.c_size_t]
+        L.llm_session_perplexity.restype = C.c_int
+        L.llm_session_perplexity.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int32, C.c_int, C.c_void_p, C.c_int,
+                                             C.c_void_p]
         _bound = True
     return L
 
@@ -335,9 +338,31 @@ class Session:
             raise ValueError("llm_session_topk: no evaluated graph or bad arguments")
         return vals, ids
 
+    def perplexity(self, tokens, bos=1, on_device=True, return_probs=False):
+        """InferenceSession::perplexity (inference_session.rs:519-589): one value per chunk of context_size tokens, each the
+        RUNNING exp(nll / count) the reference hands to its callback; `bos` replaces the first token of every chunk for the
+        evaluation.  on_device: the logits stay in HBM and the device reduces each counted row to its target's probability
+        (ggml_hip_row_probs); False: all logits are read back and softmaxed on the host, as the reference does.
+        return_probs: also the probability of every counted position, [n_chunk, context_size - 1 - min(512, context_size / 2)]."""
+        tokens = np.ascontiguousarray(tokens, dtype=np.int32)
+        ctx = self.model.context_size
+        n_chunk = tokens.size // ctx
+        per_chunk = max(ctx - 1 - min(512, ctx // 2), 0)
+        ppl = np.zeros(max(n_chunk, 1), np.float32)
+        probs = np.zeros((max(n_chunk, 1), per_chunk), np.float32)
+        rc = _lib().llm_session_perplexity(self.model.ptr, self.ptr, tokens.ctypes.data, tokens.size, int(bos), 1 if on_device else 0,
+                                           ppl.ctypes.data, n_chunk, probs.ctypes.data if return_probs else None)
+        if rc != n_chunk:
+            raise ValueError("llm_session_perplexity: a token id outside the vocabulary, or no logits on the device")
+        out = [float(x) for x in ppl[:n_chunk]]
+        return (out, probs[:n_chunk]) if return_probs else out
+
     def read_node(self, index=-1, name=None, occurrence=0, dtype=np.float32):
-        """Test hook: device contents of a node of the last evaluated graph."""
+        """Test hook: device contents of a node of the last evaluated graph, by index (negative: from the end, -1 = the last
+        node, the logits) or by name."""
         nm = name.encode() if name else None
+        if nm is None and index < 0:
+            index += self.graph_stats()[0]
         n = _lib().llm_session_read_node(self.ptr, index, nm, occurrence, None, 0)
         if n == 0:
             raise KeyError((index, name, occurrence))
