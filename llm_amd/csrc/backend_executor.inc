@@ -1,5 +1,5 @@
 // backend_executor.inc — part of libggml_hip.so's backend translation unit (included by hip_backend.hip, inside its anonymous
-// namespace where noted): the graph executor — node-by-node execution, the fused LLaMA plans (llama_plan.inc), output mirroring.  Inside the anonymous namespace.
+// namespace where noted): the graph executor — node-by-node execution, the fused LLaMA plans (plan_*.inc), output mirroring.  Inside the anonymous namespace.
 // ---------------------------------------------------------------------------------------------------
 // graph executor
 // ---------------------------------------------------------------------------------------------------
@@ -94,7 +94,10 @@ bool mirrored_to_host(const ggml_tensor *n) {
     return !(extra_of(n) || find_tensor((uintptr_t)n->data));  // else the result aliases a device-resident tensor
 }
 
-static inline uint64_t now_ns();  // (llama_plan.inc)
+static inline uint64_t now_ns() {
+    return (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(
+               std::chrono::steady_clock::now().time_since_epoch()).count();
+}
 void download_outputs(ggml_cgraph *gr) {
     const uint64_t t0 = now_ns();
     bool any = false;
@@ -135,16 +138,13 @@ void invalidate_xf16_if_overwritten_impl(const ggml_tensor *n) {
     if (b0 < a1 && a0 < b1) g_xf16.valid = false;
 }
 
-void finish_pending();
-#include "llama_plan.inc"
-
-void finish_pending() {
-    if (!g.pending_wait) return;
-    const uint64_t t = now_ns();
-    g.pending_wait = false;
-    token_finish();
-    g.ns_wait += now_ns() - t;
-}
+// the fused LLaMA plans, one concern per file (plan_shapes.inc says which); finish_pending is plan_run.inc's
+#include "plan_shapes.inc"
+#include "plan_match.inc"
+#include "plan_build.inc"
+#include "plan_decode.inc"
+#include "plan_prompt.inc"
+#include "plan_run.inc"
 
 void execute_graph(ggml_cgraph *gr) {
     ensure_init();

@@ -16,12 +16,10 @@ QAct quantize_activation(const ggml_tensor *src1, bool f16_d) {
     const char *x = dev_ptr(src1);
     Timed tm(GGML_HIP_KCLASS_OTHER, (double)(K * N * 4 + nblk * 40));
     const int64_t threads = (int64_t)nblk * 32;
-    if (f16_d)
-        hipLaunchKernelGGL(k_quantize_act<true>, grid1(threads), dim3(256), 0, g.stream, x, (int64_t)src1->nb[1], nb, N,
+    with_bool(f16_d, [&](auto F16D) {
+        hipLaunchKernelGGL(k_quantize_act<CT(F16D)>, grid1(threads), dim3(256), 0, g.stream, x, (int64_t)src1->nb[1], nb, N,
                            (int8_t *)lo, (int8_t *)hi, (float *)d, (int *)s);
-    else
-        hipLaunchKernelGGL(k_quantize_act<false>, grid1(threads), dim3(256), 0, g.stream, x, (int64_t)src1->nb[1], nb,
-                           N, (int8_t *)lo, (int8_t *)hi, (float *)d, (int *)s);
+    });
     HIP_CHECK(hipGetLastError());
     g_qact.valid = true;
     g_qact.src_data = src1->data;
@@ -54,14 +52,7 @@ void launch_mmvq_c(const MmvqArgs &a, int ncols, int R, int nwg, size_t lds) {
     }
 }
 void launch_mmvq(int qt, const MmvqArgs &a, int ncols, int R, int nwg, size_t lds) {
-    switch (qt) {
-        case QT_Q4_0: launch_mmvq_c<QT_Q4_0>(a, ncols, R, nwg, lds); break;
-        case QT_Q4_1: launch_mmvq_c<QT_Q4_1>(a, ncols, R, nwg, lds); break;
-        case QT_Q5_0: launch_mmvq_c<QT_Q5_0>(a, ncols, R, nwg, lds); break;
-        case QT_Q5_1: launch_mmvq_c<QT_Q5_1>(a, ncols, R, nwg, lds); break;
-        case QT_Q8_0: launch_mmvq_c<QT_Q8_0>(a, ncols, R, nwg, lds); break;
-        default: die("mmvq: bad weight type");
-    }
+    with_qt(qt, [&](auto QT) { launch_mmvq_c<CT(QT)>(a, ncols, R, nwg, lds); }, "mmvq: bad weight type");
     HIP_CHECK(hipGetLastError());
 }
 
@@ -73,12 +64,10 @@ const _Float16 *quantize_activation_f16(const ggml_tensor *src1, bool f16_d) {
     _Float16 *out = (_Float16 *)ws_alloc((size_t)N * K * 2);
     Timed tm(GGML_HIP_KCLASS_OTHER, (double)(K * N * 6));
     const int64_t threads = nb * N * 32;
-    if (f16_d)
-        hipLaunchKernelGGL(k_quant_act_f16<true>, grid1(threads), dim3(256), 0, g.stream, dev_ptr(src1),
+    with_bool(f16_d, [&](auto F16D) {
+        hipLaunchKernelGGL(k_quant_act_f16<CT(F16D)>, grid1(threads), dim3(256), 0, g.stream, dev_ptr(src1),
                            (int64_t)src1->nb[1], nb, N, out);
-    else
-        hipLaunchKernelGGL(k_quant_act_f16<false>, grid1(threads), dim3(256), 0, g.stream, dev_ptr(src1),
-                           (int64_t)src1->nb[1], nb, N, out);
+    });
     HIP_CHECK(hipGetLastError());
     g_xf16.valid = true;
     g_xf16.src_data = src1->data;
@@ -103,7 +92,7 @@ struct XI8Buf {  // int8 activations + f32 block scale + zero-point term of the 
 void quantize_activation_i8(const ggml_tensor *src1, int qt, const int8_t **q8, const float **dx, const float **xs) {
     BK_ASSERT(src1->type == GGML_TYPE_F32 && src1->nb[0] == 4 && src1->ne[2] == 1 && src1->ne[3] == 1);
     const int64_t K = src1->ne[0], N = src1->ne[1], nb = K / 32;
-    const bool f16_d = qt == QT_Q4_0 || qt == QT_Q5_0 || qt == QT_Q8_0;
+    const bool f16_d = qt_f16d(qt);
     const float zp = qt == QT_Q4_0 ? 8.0f : qt == QT_Q5_0 ? 16.0f : 0.0f;
     // Q4_0 and Q5_0 differ only in the zero point, Q4_1 and Q5_1 not at all: the cache is keyed on what was produced
     const int key = f16_d ? (int)zp : 1000;
@@ -113,12 +102,10 @@ void quantize_activation_i8(const ggml_tensor *src1, int qt, const int8_t **q8, 
         float *os = (float *)ws_alloc((size_t)N * nb * 4);
         Timed tm(GGML_HIP_KCLASS_OTHER, (double)(K * N * 5));
         const int64_t threads = nb * N * 32;
-        if (f16_d)
-            hipLaunchKernelGGL(k_quant_act_i8<true>, grid1(threads), dim3(256), 0, g.stream, dev_ptr(src1), (int64_t)src1->nb[1], nb,
+        with_bool(f16_d, [&](auto F16D) {
+            hipLaunchKernelGGL(k_quant_act_i8<CT(F16D)>, grid1(threads), dim3(256), 0, g.stream, dev_ptr(src1), (int64_t)src1->nb[1], nb,
                                N, zp, o8, od, os);
-        else
-            hipLaunchKernelGGL(k_quant_act_i8<false>, grid1(threads), dim3(256), 0, g.stream, dev_ptr(src1), (int64_t)src1->nb[1], nb,
-                               N, zp, o8, od, os);
+        });
         HIP_CHECK(hipGetLastError());
         g_xi8.valid = true;
         g_xi8.src_data = src1->data;
@@ -226,13 +213,7 @@ void mul_mat_k(const ggml_tensor *src0, const ggml_tensor *src1, ggml_tensor *ds
         const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(8, (150 * 1024) / std::max<size_t>(lds, 1)));
         const int nwg = (int)std::min<int64_t>((w.M + 3) / 4, (int64_t)g.num_cus * per_cu);
         Timed tm(GGML_HIP_KCLASS_MMVQ, (double)w.M * nsb * sb_bytes + (double)w.M * ncols * 4 + (double)lds);
-        switch (kt) {
-            case KT_Q4_K: launch_mmvq_k_c<KT_Q4_K>(a, ncols, nwg, lds); break;
-            case KT_Q6_K: launch_mmvq_k_c<KT_Q6_K>(a, ncols, nwg, lds); break;
-            case KT_Q2_K: launch_mmvq_k_c<KT_Q2_K>(a, ncols, nwg, lds); break;
-            case KT_Q3_K: launch_mmvq_k_c<KT_Q3_K>(a, ncols, nwg, lds); break;
-            default: launch_mmvq_k_c<KT_Q5_K>(a, ncols, nwg, lds); break;
-        }
+        with_kt(kt, [&](auto KT) { launch_mmvq_k_c<CT(KT)>(a, ncols, nwg, lds); });
         HIP_CHECK(hipGetLastError());
         c0 += ncols;
     }
@@ -278,7 +259,7 @@ size_t release_w16_copies() {
             e->w16_size = 0;
             e->qw.w16 = nullptr;
         }
-    if (freed) g.w16_gen++;  // prompt plans re-read their weights' w16 pointers at the next launch (llama_plan.inc)
+    if (freed) g.w16_gen++;  // prompt plans re-read their weights' w16 pointers at the next launch (plan_prompt.inc)
     return freed;
 }
 bool ensure_w16(DevTensor *e) {
@@ -298,14 +279,8 @@ bool ensure_w16(DevTensor *e) {
     const bool shared = device_sharers() > 1;
     if (!shared) e->w16 = w16;
     const unsigned nblk = (unsigned)((e->qw.M * e->qw.nb + 255) / 256);
-    switch (e->qw.qt) {
-        case QT_Q4_0: hipLaunchKernelGGL(k_dequant_w16<QT_Q4_0>, dim3(nblk), dim3(256), 0, g.stream, e->qw, (_Float16 *)w16); break;
-        case QT_Q4_1: hipLaunchKernelGGL(k_dequant_w16<QT_Q4_1>, dim3(nblk), dim3(256), 0, g.stream, e->qw, (_Float16 *)w16); break;
-        case QT_Q5_0: hipLaunchKernelGGL(k_dequant_w16<QT_Q5_0>, dim3(nblk), dim3(256), 0, g.stream, e->qw, (_Float16 *)w16); break;
-        case QT_Q5_1: hipLaunchKernelGGL(k_dequant_w16<QT_Q5_1>, dim3(nblk), dim3(256), 0, g.stream, e->qw, (_Float16 *)w16); break;
-        case QT_Q8_0: hipLaunchKernelGGL(k_dequant_w16<QT_Q8_0>, dim3(nblk), dim3(256), 0, g.stream, e->qw, (_Float16 *)w16); break;
-        default: die("w16: bad weight type");
-    }
+    with_qt(e->qw.qt, [&](auto QT) { hipLaunchKernelGGL(k_dequant_w16<CT(QT)>, dim3(nblk), dim3(256), 0, g.stream, e->qw, (_Float16 *)w16); },
+            "w16: bad weight type");
     HIP_CHECK(hipGetLastError());
     if (shared) {  // another slot's stream may read the copy as soon as the pointer is visible: complete it first
         HIP_CHECK(hipStreamSynchronize(g.stream));
@@ -462,14 +437,7 @@ void mmq_f16_launch_multi(int qt, int nseg, const MmqSegHost *segs, const _Float
         const dim3 grid((unsigned)(tiles_m * a.tiles_n), (unsigned)splits);
         Timed tm(GGML_HIP_KCLASS_MMQ_MFMA, 2.0 * rows * (double)N * (double)(nb * 32));
         g.stat_mmq[Backend::MMQ_K_PLAIN]++;
-        switch (qt) {
-            case QT_Q4_0: hipLaunchKernelGGL(k_mmq<QT_Q4_0>, grid, dim3(256), MMQ_LDS, g.stream, a); break;
-            case QT_Q4_1: hipLaunchKernelGGL(k_mmq<QT_Q4_1>, grid, dim3(256), MMQ_LDS, g.stream, a); break;
-            case QT_Q5_0: hipLaunchKernelGGL(k_mmq<QT_Q5_0>, grid, dim3(256), MMQ_LDS, g.stream, a); break;
-            case QT_Q5_1: hipLaunchKernelGGL(k_mmq<QT_Q5_1>, grid, dim3(256), MMQ_LDS, g.stream, a); break;
-            case QT_Q8_0: hipLaunchKernelGGL(k_mmq<QT_Q8_0>, grid, dim3(256), MMQ_LDS, g.stream, a); break;
-            default: die("mmq: bad weight type");
-        }
+        with_qt(qt, [&](auto QT) { hipLaunchKernelGGL(k_mmq<CT(QT)>, grid, dim3(256), MMQ_LDS, g.stream, a); }, "mmq: bad weight type");
         HIP_CHECK(hipGetLastError());
         return;
     }
@@ -496,14 +464,9 @@ void mmq_f16_launch_multi(int qt, int nseg, const MmqSegHost *segs, const _Float
         HIP_CHECK(hipFuncSetAttribute((const void *)k_mmq_dma_p8<QT_Q8_0>, hipFuncAttributeMaxDynamicSharedMemorySize, Dma8<QT_Q8_0>::LDS));
     }
     g.stat_mmq[Backend::MMQ_K_DMA_P8]++;
-    switch (qt) {
-        case QT_Q4_0: hipLaunchKernelGGL(k_mmq_dma_p8<QT_Q4_0>, pgrid, dim3(512), Dma8<QT_Q4_0>::LDS, g.stream, a, n_items, tiles_total, splits); break;
-        case QT_Q4_1: hipLaunchKernelGGL(k_mmq_dma_p8<QT_Q4_1>, pgrid, dim3(512), Dma8<QT_Q4_1>::LDS, g.stream, a, n_items, tiles_total, splits); break;
-        case QT_Q5_0: hipLaunchKernelGGL(k_mmq_dma_p8<QT_Q5_0>, pgrid, dim3(512), Dma8<QT_Q5_0>::LDS, g.stream, a, n_items, tiles_total, splits); break;
-        case QT_Q5_1: hipLaunchKernelGGL(k_mmq_dma_p8<QT_Q5_1>, pgrid, dim3(512), Dma8<QT_Q5_1>::LDS, g.stream, a, n_items, tiles_total, splits); break;
-        case QT_Q8_0: hipLaunchKernelGGL(k_mmq_dma_p8<QT_Q8_0>, pgrid, dim3(512), Dma8<QT_Q8_0>::LDS, g.stream, a, n_items, tiles_total, splits); break;
-        default: die("mmq: bad weight type");
-    }
+    with_qt(qt, [&](auto QT) {
+        hipLaunchKernelGGL(k_mmq_dma_p8<CT(QT)>, pgrid, dim3(512), Dma8<CT(QT)>::LDS, g.stream, a, n_items, tiles_total, splits);
+    }, "mmq: bad weight type");
     HIP_CHECK(hipGetLastError());
 }
 
@@ -517,7 +480,7 @@ void mmq_f16_launch(int qt, const QWeight &w, const _Float16 *x16, float *dst, i
 void mul_mat_q_mfma(const ggml_tensor *src0, const ggml_tensor *src1, ggml_tensor *dst) {
     const int qt = qt_of(src0->type);
     const int64_t K = src1->ne[0], N = src1->ne[1], nb = K / 32;
-    const bool f16_d = qt == QT_Q4_0 || qt == QT_Q5_0 || qt == QT_Q8_0;
+    const bool f16_d = qt_f16d(qt);
     if (g.opt_mmq_i8 && nb % 2 == 0) {  // integer matrix cores: ggml's exact block dots (kernels/mmq_i8.h)
         MmqI8Args ia;
         ia.w = qweight_of(src0);
@@ -535,19 +498,12 @@ void mul_mat_q_mfma(const ggml_tensor *src0, const ggml_tensor *src1, ggml_tenso
         if (splits > 1) HIP_CHECK(hipMemsetAsync(ia.dst, 0, (size_t)ia.M * N * 4, g.stream));
         const dim3 grid((unsigned)(tiles_m * ia.tiles_n), (unsigned)splits);
         Timed tm(GGML_HIP_KCLASS_MMQ_MFMA, 2.0 * (double)ia.M * (double)N * (double)K);
-        switch (qt) {
-            case QT_Q4_0: launch_mmq_i8<QT_Q4_0>(ia, grid); break;
-            case QT_Q4_1: launch_mmq_i8<QT_Q4_1>(ia, grid); break;
-            case QT_Q5_0: launch_mmq_i8<QT_Q5_0>(ia, grid); break;
-            case QT_Q5_1: launch_mmq_i8<QT_Q5_1>(ia, grid); break;
-            case QT_Q8_0: launch_mmq_i8<QT_Q8_0>(ia, grid); break;
-            default: die("mmq: bad weight type");
-        }
+        with_qt(qt, [&](auto QT) { launch_mmq_i8<CT(QT)>(ia, grid); }, "mmq: bad weight type");
         HIP_CHECK(hipGetLastError());
         return;
     }
     if (N >= W16_MIN_TOKENS) {  // a resident weight meeting a real prompt batch gets its f16 copy here too (the prompt plan
-        DevTensor *e = extra_of(src0);  // makes them for a whole model at once, llama_plan.inc)
+        DevTensor *e = extra_of(src0);  // makes them for a whole model at once, plan_build.inc)
         if (!e) e = find_tensor((uintptr_t)src0->data);
         if (e && e->soa && (uintptr_t)src0->data == e->host) ensure_w16(e);
     }
@@ -606,7 +562,7 @@ void mul_mat_q(int nmat, const ggml_tensor *const *src0s, const ggml_tensor *src
         for (int i = 0; i < nmat; i++) mul_mat_q_mfma(src0s[i], src1, dsts[i]);
         return;
     }
-    const bool f16_d = qt == QT_Q4_0 || qt == QT_Q5_0 || qt == QT_Q8_0;
+    const bool f16_d = qt_f16d(qt);
     const QAct act = quantize_activation(src1, f16_d);
     const int64_t max_cols_lds = (int64_t)(64 * 1024) / (nb * 40);
     if (max_cols_lds < 1) die("mul_mat: K=%lld too large for the LDS-staged mat-vec", (long long)K);

@@ -121,7 +121,7 @@ struct Backend {
                             // 309 vs 464 TFLOP/s-equivalent on 7B Q4_0, so the f16 kernels stay the default
     int opt_mmq_min = 32;   // token count from which mul_mat runs on the MFMA GEMM (0 = never)
     int opt_plan = 1;       // recognise the LLaMA decode graph and run the fused plan
-    int opt_plan_k = 1;     // ... and the K plan for a model whose matrices are K-quants (llama_plan.inc plan_launch_k)
+    int opt_plan_k = 1;     // ... and the K plan for a model whose matrices are K-quants (plan_decode.inc plan_launch_k)
     int opt_k_prompt_min = 12;  // tokens from which a K-quant model's batch takes the prompt plan (f16 copies) instead of the K plan's multi-token form
     int opt_kbig = 1;       // ... its decode mat-vecs as one wave of 1024-thread workgroups that stage the activation themselves (kernels/kquant_big.h)
     int opt_graph = 1;      // replay the plan from a captured hipGraph
@@ -135,7 +135,7 @@ struct Backend {
     ggml_cgraph *chain_graph = nullptr;    // ... and the cgraph that run executed
     bool pending_wait = false;  // a decode plan was launched by graph_compute_begin and not yet waited for
     bool pending_light = false;  // ... and it was a multi-token plan run: no in-launch waits (no error word to look at); if it also queued no read-back, the next begin() need not wait for it
-    // Speculative next token (option speculate_next / GGML_HIP_SPECULATE_NEXT, llama_plan.inc): behind a single-token plan run
+    // Speculative next token (option speculate_next / GGML_HIP_SPECULATE_NEXT, plan_run.inc): behind a single-token plan run
     // the device samples the greedy token itself (k_argmax_next) and runs the NEXT token's plan at once; if the caller's next
     // ggml_graph_compute asks for exactly that (same plan, position + 1, the same token) its results are already on their
     // way — the caller's sampling, graph build and this library's enqueue overlap the device instead of idling it.  Anything
@@ -156,7 +156,7 @@ struct Backend {
     size_t results_ev_copies = 0;      // read-backs that were queued when it was recorded: a later one is not covered by it
     uint64_t stat_spec_hits = 0, stat_spec_misses = 0;
     // in-launch hand-offs that gave up (kernels/common.h GRAN_SPIN_MAX): the plan's error word travels back with every token's
-    // results (llama_plan.inc token_finish)
+    // results (plan_run.inc token_finish)
     unsigned *ferr_pin = nullptr;    // the slot's error word: pinned HOST memory the kernels write straight into (zero-copy; written
                                      // only when a wait gives up, read by the host behind every token's result wait: no copy per token)
     void *ferr_plan = nullptr;       // the DecodePlan whose token is in flight
@@ -176,7 +176,7 @@ struct Backend {
     uint64_t ns_mirror = 0, stat_mirror_bytes = 0;  // generic graphs: host ns in download_outputs (waits for the graph), bytes mirrored
     size_t dead_shadow_bytes = 0;
     uint64_t arena_seen = 0;  // the last event of the process-wide arena log this slot has applied (sync_arenas)
-    void *prep = nullptr;  // PrepMatch (llama_plan.inc): the match of a graph handed over by ggml_hip_graph_prepare, waiting for its begin()
+    void *prep = nullptr;  // PrepMatch (plan_run.inc): the match of a graph handed over by ggml_hip_graph_prepare, waiting for its begin()
     int opt_gen = 0;       // bumped by every ggml_hip_set_option: a remembered match does not outlive an option change
     int xcd_labels = -1;  // 1: workgroups with equal blockIdx mod 8 of a one-workgroup-per-CU launch share an XCD, eight labels on eight XCDs (xcd_labels_ok); -1 = not looked yet
     void *hot_line = nullptr;  // 256 zero bytes on the device: what the dummy ring steps of the K plan's mat-vecs read (kernels/kquant_big.h KBigArgs::hot)
@@ -201,7 +201,7 @@ std::atomic<int> g_default_slot{0};
 // Slots that drive one physical device share its compute units.  The fused decode launches (k_qkv_attn, k_attn_split_one)
 // contain workgroups that WAIT for other workgroups of the same launch, which is only safe while every workgroup of the launch
 // can be resident: with several slots on a device their attention workgroups together must leave the producers room, and the
-// all-workgroups-wait form is refused outright (llama_plan.inc fused_qkv_shape / attn_one_ok).  A slot counts while it holds
+// all-workgroups-wait form is refused outright (plan_shapes.inc fused_qkv_shape / attn_one_ok).  A slot counts while it holds
 // mutable session state (zero-filled records: the K/V memory of a live session; Backend::session_records) — a slot that only
 // keeps a model's weights launches nothing.  g_dev_gen moves whenever the count of a device changes, so that plans captured
 // under another count re-capture.
@@ -209,7 +209,7 @@ std::atomic<int> g_dev_slots[64];   // slots of a device that hold session state
 std::atomic<uint64_t> g_dev_gen[64];
 // bumped whenever a WEIGHT record of the device is freed: the decode plans of every slot of that device hold device addresses (and
 // resident-copy pointers) of weight records, also of records a sibling slot owns (llm_start_session_on); a plan built under another
-// value is discarded at its next lookup, under its own slot's lock (llama_plan.inc try_decode_plan)
+// value is discarded at its next lookup, under its own slot's lock (plan_run.inc try_decode_plan)
 std::atomic<uint64_t> g_dev_wgen[64];
 thread_local Backend *g_cur = &g_backends[0];
 thread_local bool tl_pinned = false;
@@ -293,6 +293,40 @@ int qt_of(ggml_type t) {
         default: return -1;
     }
 }
+// The one place a run-time type becomes a template argument: f(std::integral_constant<int, QT_…>{}), and likewise for the K
+// types and for a bool.  `bad`: what to die with for a type outside the five (the node-by-node executor's launches); without it
+// such a type runs as Q8_0 / Q5_K, as the plans have always taken theirs (the matcher has checked it).
+#define CT(x) (decltype(x)::value) /* the compile-time value of the argument a with_* helper hands to f */
+template <class F>
+void with_qt(int qt, F &&f, const char *bad = nullptr) {
+    if (bad && (qt < QT_Q4_0 || qt > QT_Q8_0)) die("%s", bad);
+    switch (qt) {
+        case QT_Q4_0: f(std::integral_constant<int, QT_Q4_0>{}); break;
+        case QT_Q4_1: f(std::integral_constant<int, QT_Q4_1>{}); break;
+        case QT_Q5_0: f(std::integral_constant<int, QT_Q5_0>{}); break;
+        case QT_Q5_1: f(std::integral_constant<int, QT_Q5_1>{}); break;
+        default: f(std::integral_constant<int, QT_Q8_0>{}); break;
+    }
+}
+template <class F>
+void with_kt(int kt, F &&f) {
+    switch (kt) {
+        case KT_Q4_K: f(std::integral_constant<int, KT_Q4_K>{}); break;
+        case KT_Q6_K: f(std::integral_constant<int, KT_Q6_K>{}); break;
+        case KT_Q2_K: f(std::integral_constant<int, KT_Q2_K>{}); break;
+        case KT_Q3_K: f(std::integral_constant<int, KT_Q3_K>{}); break;
+        default: f(std::integral_constant<int, KT_Q5_K>{}); break;
+    }
+}
+template <class F>
+void with_bool(bool b, F &&f) {
+    if (b)
+        f(std::true_type{});
+    else
+        f(std::false_type{});
+}
+// the weight types whose activation rows get their block scale rounded to f16 first: the bool argument of the quantizing kernels
+static inline bool qt_f16d(int qt) { return qt == QT_Q4_0 || qt == QT_Q5_0 || qt == QT_Q8_0; }
 
 thread_local int tl_device = -1;  // the device this thread last made current
 void bind_device() {

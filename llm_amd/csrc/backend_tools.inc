@@ -80,7 +80,7 @@ int ggml_hip_bench_empty(int wgs, int threads, int lds_bytes, int kernarg_bytes,
     return 0;
 }
 
-// Test hook: the attention of a prompt batch on host arrays through either path of the prompt plan (llama_plan.inc
+// Test hook: the attention of a prompt batch on host arrays through either path of the prompt plan (plan_prompt.inc
 // prompt_attention): q [N][E] f32 with RoPE applied, mem_k [C][Egqa] / mem_v [Egqa][C] f16 of one layer, out [N][E] f32.
 // Returns 0, or -1 when `fused` is asked for a shape the fused kernel does not take.
 int ggml_hip_debug_prompt_attention(const float *q, const uint16_t *mem_k, const uint16_t *mem_v, float *out, int N, int E, int Egqa,
@@ -127,7 +127,6 @@ int ggml_hip_debug_mul_mat_cols(const struct ggml_tensor *w, const float *x, flo
     const QWeight qw = qweight_of(w);
     const int64_t K = w->ne[0], M = w->ne[1], nb = K / 32;
     if (!cols_ok((int)M, 1, nb, {M})) return -1;
-    const bool f16d = qt == QT_Q4_0 || qt == QT_Q5_0 || qt == QT_Q8_0;
     char *dx, *dlo, *dhi, *dd, *ds, *ddT, *dsT, *dout;
     dev_malloc((void **)&dx, (size_t)N * K * 4, "debug x");
     dev_malloc((void **)&dlo, (size_t)N * K / 2, "debug lo");
@@ -142,12 +141,10 @@ int ggml_hip_debug_mul_mat_cols(const struct ggml_tensor *w, const float *x, flo
     HIP_CHECK(hipMemsetAsync(dsT, 0, (size_t)nb * 32, g.stream));
     HIP_CHECK(hipMemsetAsync(dout, 0xFF, (size_t)N * M * 4, g.stream));
     const dim3 grid((unsigned)((nb * 32 + 255) / 256), (unsigned)N);
-    if (f16d)
-        hipLaunchKernelGGL(k_quant_row<true>, grid, dim3(256), 0, g.stream, (const float *)dx, (int)nb, (int8_t *)dlo, (int8_t *)dhi,
+    with_bool(qt_f16d(qt), [&](auto F16D) {
+        hipLaunchKernelGGL(k_quant_row<CT(F16D)>, grid, dim3(256), 0, g.stream, (const float *)dx, (int)nb, (int8_t *)dlo, (int8_t *)dhi,
                            (float *)dd, (int *)ds, (float *)ddT, (int *)dsT);
-    else
-        hipLaunchKernelGGL(k_quant_row<false>, grid, dim3(256), 0, g.stream, (const float *)dx, (int)nb, (int8_t *)dlo, (int8_t *)dhi,
-                           (float *)dd, (int *)ds, (float *)ddT, (int *)dsT);
+    });
     HIP_CHECK(hipGetLastError());
     ColsArgs c;
     memset(&c, 0, sizeof(c));
@@ -160,7 +157,8 @@ int ggml_hip_debug_mul_mat_cols(const struct ggml_tensor *w, const float *x, flo
     c.ldr = M;
     c.dxT = (const float *)ddT;
     c.sxT = (const int *)dsT;
-    launch_cols_t<EPI_STORE>(qt, c, (int)M);
+    with_qt(qt, [&](auto QT) { launch_cols<CT(QT), EPI_STORE>(c, (int)M); });
+    HIP_CHECK(hipGetLastError());
     d2h_queue(out, dout, (size_t)N * M * 4);
     d2h_finish();
     for (char *b : {dx, dlo, dhi, dd, ds, ddT, dsT, dout}) HIP_CHECK(hipFree(b));
@@ -237,19 +235,14 @@ int ggml_hip_debug_mat_vec_big(const struct ggml_tensor *w0, const struct ggml_t
     if (epi == EPI_GATE && M1 != M0) return -1;
     if (epi == EPI_QKV && (!mem_k || !mem_v || D < 2 || D % 2 || D > 256 || M0 % D || M1 % D || M1 != M2 || n_past < 0 || n_past >= C))
         return -1;
-    // staging limits (BigX): the norm 8192 elements over 1024 threads, launch_big's wave counts up to BIG_W, LDS
+    // staging limits (BigX): the norm 8192 elements over 1024 threads, launch_big's wave counts up to BIG_W, LDS; and the dealing
+    // launch_big would abort on
     if (xsrc == XSRC_NORM && nb * 8 > (int64_t)BigX<XSRC_NORM>::MAXIT * BigX<XSRC_NORM>::NT) return -1;
-    const int min_waves = big_min_waves(xsrc, epi, nb);
-    if (min_waves > BIG_W || (size_t)((nb + 63) / 64 * 64) * 40 > 64 * 1024) return -1;
-    // launch_big's dealing: at most 64 units per wave (its abort)
-    const int64_t units = (M0 + M1 + M2) / (epi == EPI_QKV ? 2 : 1);
-    const int G = (int)std::min<int64_t>(g.num_cus, std::max<int64_t>(1, (units + BIG_W - 1) / BIG_W));
-    const int W = big_waves(units, G, min_waves);
-    if ((units + (int64_t)G * W - 1) / ((int64_t)G * W) > 64) return -1;
+    const BigShape bsh = big_shape(xsrc, epi, nb, (M0 + M1 + M2) / (epi == EPI_QKV ? 2 : 1));
+    if (big_min_waves(xsrc, epi, nb) > BIG_W || bsh.lds > 64 * 1024 || !bsh.ok) return -1;
 
     std::vector<char *> owned;
     debug_hot_line();
-    const bool f16d = qt == QT_Q4_0 || qt == QT_Q5_0 || qt == QT_Q8_0;
     DecMmvqArgs a;
     memset(&a, 0, sizeof(a));
     for (int i = 0; i < nw; i++) a.w[i] = qweight_of(ts[i]);
@@ -263,12 +256,10 @@ int ggml_hip_debug_mat_vec_big(const struct ggml_tensor *w0, const struct ggml_t
     if (xsrc == XSRC_Q8) {  // the planar Q8 row, as k_quant_row makes it
         char *dlo = debug_buf((size_t)K / 2, nullptr, owned), *dhi = debug_buf((size_t)K / 2, nullptr, owned);
         char *dd = debug_buf((size_t)nb * 4, nullptr, owned), *ds = debug_buf((size_t)nb * 4, nullptr, owned);
-        if (f16d)
-            hipLaunchKernelGGL(k_quant_row<true>, grid1(nb * 32), dim3(256), 0, g.stream, (const float *)dx, (int)nb, (int8_t *)dlo,
+        with_bool(qt_f16d(qt), [&](auto F16D) {
+            hipLaunchKernelGGL(k_quant_row<CT(F16D)>, grid1(nb * 32), dim3(256), 0, g.stream, (const float *)dx, (int)nb, (int8_t *)dlo,
                                (int8_t *)dhi, (float *)dd, (int *)ds, (float *)nullptr, (int *)nullptr);
-        else
-            hipLaunchKernelGGL(k_quant_row<false>, grid1(nb * 32), dim3(256), 0, g.stream, (const float *)dx, (int)nb, (int8_t *)dlo,
-                               (int8_t *)dhi, (float *)dd, (int *)ds, (float *)nullptr, (int *)nullptr);
+        });
         HIP_CHECK(hipGetLastError());
         a.x = QAct{(const i32x4 *)dlo, (const i32x4 *)dhi, (const float *)dd, (const int *)ds};
     }
@@ -294,23 +285,27 @@ int ggml_hip_debug_mat_vec_big(const struct ggml_tensor *w0, const struct ggml_t
         a.theta_scale = powf(freq_base, -2.0f / (float)D);
         a.freq_scale = freq_scale;
     }
-    // BigArgs as plan_launch_all builds them (no timeline, no probe, no granules; wdeal chosen by launch_big)
+    // the launcher plan_launch_all uses (no timeline, no probe, no granules; the dealing is launch_big's)
     const BigArgs ba{a, epi == EPI_STORE ? (float *)dy : nullptr, nullptr, 0, rope, 0, nullptr, nullptr, 0, g.hot_line};
-    switch (epi) {
-        case EPI_QKV: launch_big_t<EPI_QKV, XSRC_NORM>(qt, ba); break;
-        case EPI_GATE: launch_big_t<EPI_GATE, XSRC_NORM>(qt, ba); break;
-        case EPI_STORE: launch_big_t<EPI_STORE, XSRC_NORM>(qt, ba); break;
-        default:
-            if (xsrc == XSRC_Q8)
-                launch_big_t<EPI_ADD, XSRC_Q8>(qt, ba);
-            else
-                launch_big_t<EPI_ADD, XSRC_F32>(qt, ba);
-    }
+    with_qt(qt, [&](auto QT) {
+        switch (epi) {
+            case EPI_QKV: launch_big<CT(QT), EPI_QKV, XSRC_NORM>(ba); break;
+            case EPI_GATE: launch_big<CT(QT), EPI_GATE, XSRC_NORM>(ba); break;
+            case EPI_STORE: launch_big<CT(QT), EPI_STORE, XSRC_NORM>(ba); break;
+            default:
+                if (xsrc == XSRC_Q8)
+                    launch_big<CT(QT), EPI_ADD, XSRC_Q8>(ba);
+                else
+                    launch_big<CT(QT), EPI_ADD, XSRC_F32>(ba);
+        }
+    });
+    HIP_CHECK(hipGetLastError());
     if (dy && epi != EPI_STORE) {  // the normed row of the same staging code: the tap of an EPI_STORE launch of w0
         DecMmvqArgs t = a;
         t.w[1] = t.w[2] = QWeight{};
         t.dst = (float *)debug_buf((size_t)M0 * 4, nullptr, owned);
-        launch_big_t<EPI_STORE, XSRC_NORM>(qt, BigArgs{t, (float *)dy, nullptr, 0, nullptr, 0, nullptr, nullptr, 0, g.hot_line});
+        with_qt(qt, [&](auto QT) { launch_big<CT(QT), EPI_STORE, XSRC_NORM>(BigArgs{t, (float *)dy, nullptr, 0, nullptr, 0, nullptr, nullptr, 0, g.hot_line}); });
+        HIP_CHECK(hipGetLastError());
     }
     d2h_queue(out, dout, n_out + DEBUG_GUARD);
     if (dy) d2h_queue(y_out, dy, (size_t)K * 4 + DEBUG_GUARD);
@@ -350,8 +345,8 @@ int ggml_hip_debug_mat_vec_kbig(const struct ggml_tensor *w0, const struct ggml_
         const ggml_tensor *t = ts[i];
         if (!t || kt_of(t->type) < 0 || t->ne[0] != K || !wants_ksoa(t)) return -1;
         Ms[i] = t->ne[1];
-        // kbig_ok: the staging limits (KBIG_SBW super-blocks per wave, the norm's two 4096-element passes) and 21 rows per wave
-        if (nsb > 64 || (xsrc == KX_NORM && K > 8192) || (Ms[i] + (int64_t)g.num_cus * 16 - 1) / ((int64_t)g.num_cus * 16) > 21) return -1;
+        // kbig_ok's limits: the staging (KBIG_SBW super-blocks per wave, the norm's two 4096-element passes) and 21 rows per wave
+        if (!kbig_weight_ok(kt_of(t->type), nsb, Ms[i], xsrc == KX_NORM ? K : 0)) return -1;
     }
     if (epi == KE_GATE && (w1->type != w0->type || Ms[1] != Ms[0])) return -1;
     if (epi == KE_QKV && (!mem_k || !mem_v || D < 2 || D % 2 || D > 256 || Ms[0] % D || Ms[1] % D || Ms[1] != Ms[2] || Ms[0] % 2 ||
@@ -372,7 +367,7 @@ int ggml_hip_debug_mat_vec_kbig(const struct ggml_tensor *w0, const struct ggml_
     const KBigSrc src{xsrc, (const float *)dx, (const float *)dxw, eps, epi == KE_ROW ? (float *)dy : nullptr};
     char *dk = nullptr, *dv = nullptr;
     const size_t nkv = epi == KE_QKV ? (size_t)C * Ms[1] * 2 : 0;
-    if (epi == KE_QKV) {  // plan_launch_k's kqkv loop: one launch per run of equal types, seg_kind = the matrices' kinds
+    if (epi == KE_QKV) {  // as plan_launch_k: one launch per run of equal types, seg_kind = the matrices' kinds
         DecParams *prm;
         float *rope;
         debug_rope(n_past, D, freq_base, freq_scale, owned, &prm, &rope);
@@ -380,29 +375,21 @@ int ggml_hip_debug_mat_vec_kbig(const struct ggml_tensor *w0, const struct ggml_
         dv = debug_buf(nkv, mem_v, owned);
         const KWeight *ws3[3] = {&kw[0], &kw[1], &kw[2]};
         float *ds3[3] = {(float *)dout, nullptr, nullptr};
-        for (int i = 0; i < 3;) {
-            int j = i + 1;
-            while (j < 3 && ws3[j]->kt == ws3[i]->kt) j++;
+        for_each_type_run(ws3, 3, [&](int i, int j) {
             KBigArgs qa;
             memset(&qa, 0, sizeof(qa));
             for (int k = i; k < j; k++) qa.seg_kind[k - i] = k;
             qa.rope = rope; qa.prm = prm; qa.mem_k = (__half *)dk; qa.mem_v = (__half *)dv; qa.Egqa = Ms[1]; qa.C = C; qa.D = D;
             launch_kbig(j - i, ws3 + i, ds3 + i, src, nullptr, KE_QKV, &qa);
-            i = j;
-        }
+        });
     } else if (epi == KE_GATE) {
         const KWeight *ws2[2] = {&kw[0], &kw[1]};
         float *ds2[2] = {(float *)dout, (float *)debug_buf((size_t)Ms[1] * 4, nullptr, owned)};
         launch_kbig(2, ws2, ds2, src, nullptr, KE_GATE);
-    } else {  // plan_launch_k's mmvq: one launch per run of equal types
+    } else {  // as plan_launch_k's mmvq
         const KWeight *ws[3] = {&kw[0], &kw[1], &kw[2]};
         float *ds[3] = {(float *)dout, (float *)dout + Ms[0], (float *)dout + Ms[0] + Ms[1]};
-        for (int i = 0; i < nw;) {
-            int j = i + 1;
-            while (j < nw && ws[j]->kt == ws[i]->kt) j++;
-            launch_kbig(j - i, ws + i, ds + i, src, (const float *)dres);
-            i = j;
-        }
+        for_each_type_run(ws, nw, [&](int i, int j) { launch_kbig(j - i, ws + i, ds + i, src, (const float *)dres); });
     }
     if (dy && epi != KE_ROW) {  // the normed row of the same staging code: the tap of a KE_ROW launch of w0
         const KWeight *ws1[1] = {&kw[0]};
@@ -420,7 +407,7 @@ int ggml_hip_debug_mat_vec_kbig(const struct ggml_tensor *w0, const struct ggml_
     return 0;
 }
 
-// Test hook: the fused prompt attention in the form plan_launch_prompt launches it (llama_plan.inc: prompt_attention(true, ...)
+// Test hook: the fused prompt attention in the form plan_launch_prompt launches it (plan_prompt.inc: prompt_attention(true, ...)
 // with x16_out, rope and q_part set): q_raw [N][E] f32 the un-rotated wq product, q_raw2 (nullable) its second K-split partial —
 // uploaded N * E floats behind the first, q_part = N * E as the plan's qkv_stride is a distance inside one buffer; rope [N][128]
 // f32, (cos, sin) per pair in k_rope_table's layout; mem_k [C][Egqa] / mem_v [Egqa][C] f16 of one layer; f16d: the block scale

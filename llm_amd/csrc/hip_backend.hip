@@ -888,7 +888,7 @@ void ggml_hip_internal_set_option_here(const char *key, int value) {  // acts on
         g.opt_fuse_attn = value;
         g.fused_rearm_at = 0;  // an explicit choice outlives a pending re-arm
     }
-    else if (k == "speculate_next") {  // 1 = run the greedy next token speculatively behind every single-token plan run (llama_plan.inc)
+    else if (k == "speculate_next") {  // 1 = run the greedy next token speculatively behind every single-token plan run (plan_run.inc)
         spec_cancel();
         g.opt_speculate_next = value;
     }
@@ -976,19 +976,17 @@ int ggml_hip_bench_plan_class(int kclass, int replays, double *ms_total, int64_t
     hipEvent_t a, b;
     HIP_CHECK(hipEventCreate(&a));
     HIP_CHECK(hipEventCreate(&b));
+    const LaunchCtx only{1u << kclass, kind_mask, nullptr}, counted{1u << kclass, kind_mask, &st};
     if (g.opt_graph) {
-        HIP_CHECK(hipStreamBeginCapture(g.stream, hipStreamCaptureModeThreadLocal));
-        plan_launch_decode(p, 1u << kclass, &st, kind_mask);
-        HIP_CHECK(hipStreamEndCapture(g.stream, &gr));
-        HIP_CHECK(hipGraphInstantiate(&ex, gr, nullptr, nullptr, 0));
+        capture_into(&gr, &ex, [&] { plan_launch_decode(p, AV_SHORT, counted); });
         HIP_CHECK(hipGraphLaunch(ex, g.stream));  // warm
         HIP_CHECK(hipEventRecord(a, g.stream));
         for (int i = 0; i < replays; i++) HIP_CHECK(hipGraphLaunch(ex, g.stream));
         HIP_CHECK(hipEventRecord(b, g.stream));
     } else {  // GGML_HIP_GRAPH=0 (e.g. under rocprofv3, whose kernel tracing crashes on graph launches here)
-        plan_launch_decode(p, 1u << kclass, &st, kind_mask);
+        plan_launch_decode(p, AV_SHORT, counted);
         HIP_CHECK(hipEventRecord(a, g.stream));
-        for (int i = 0; i < replays; i++) plan_launch_decode(p, 1u << kclass, nullptr, kind_mask);
+        for (int i = 0; i < replays; i++) plan_launch_decode(p, AV_SHORT, only);
         HIP_CHECK(hipEventRecord(b, g.stream));
     }
     HIP_CHECK(hipStreamSynchronize(g.stream));

@@ -1,0 +1,402 @@
+// plan_run.inc — running a plan: capture and replay of its hipGraphs, the results' way to the host, the speculative next token,
+// the re-run of a token whose in-launch hand-off gave up, the greedy chain.
+// begin capture, launch, end capture, instantiate: the launches of `launch` as a graph and its first executable instance
+template <class F>
+static void capture_into(hipGraph_t *graph, hipGraphExec_t *exec, F &&launch) {
+    HIP_CHECK(hipStreamBeginCapture(g.stream, hipStreamCaptureModeThreadLocal));
+    launch();
+    HIP_CHECK(hipStreamEndCapture(g.stream, graph));
+    HIP_CHECK(hipGraphInstantiate(exec, *graph, nullptr, nullptr, 0));
+}
+// results the host reads, queued behind the evaluation's kernels: the logits (CPU-backend node, model/common.rs:6-38) ...
+static void queue_results(const DecodePlan *p) {
+    const LlamaMatch &m = p->m;
+    if (m.logits && m.logits->backend == GGML_BACKEND_CPU) d2h_queue(m.logits->data, p->logits_out, (size_t)m.V * m.N * 4);
+    // the embedding_result node is offloaded in the reference's graph, yet common::extract_embeddings reads its HOST pointer
+    // (crates/llm-base/src/model/common.rs:41-59): a decode token's / prompt chunk's rows (16 KB per token) are mirrored to the node's
+    // host data with the logits, so that an unchanged caller reads what the device computed.  (Bigger evaluations keep the node on
+    // the device only: 8 MB per 512-token batch nobody may want — read it with ggml_hip_tensor_get, INTEGRATION.md.)
+    if (m.embedding && m.embedding->data && p->emb_out && (size_t)m.N * (size_t)m.E * 4 <= ((size_t)128 << 10))
+        d2h_queue(m.embedding->data, (const char *)p->emb_out, (size_t)m.N * (size_t)m.E * 4);
+}
+// ---- the end of a single-token plan run: wait, deliver the results, and look at the plan's error word ----
+// k_qkv_attn / k_attn_split_one contain workgroups that wait for rows or partial results of OTHER workgroups of the same launch.
+// That is only live while the whole launch is resident (one 1024-thread workgroup per CU).  Several slots of one process on a GPU
+// are accounted for (fused_qkv_shape, attn_one_ok); another PROCESS on the GPU, or a CU mask, is invisible from here: the waits are
+// bounded (GRAN_SPIN_MAX), the error word comes back with the token's results, and a token whose hand-off gave up is re-run on
+// the kernels that do not wait inside a launch (k_mmvq_big + k_attn_decode / the three split launches — bit-identical results),
+// which the slot then keeps; option fused_fallback = 0, a stage of a layer split (its garbage residual has already travelled
+// on) and a device-sampled chain abort with the message instead.  SURVEY 8b: no error returns; never silent garbage.
+static void token_results_queue(DecodePlan *p) {
+    if (p->m.N != 1 || p->m.prompt || !p->ferr) return;
+    g.ferr_plan = p;  // the word itself needs no copy: the kernels write it into pinned host memory, visible once the token's
+                      // result copies (queued behind its kernels) are done
+}
+static void token_finish(bool can_rerun = true) {
+    d2h_finish();
+    DecodePlan *p = (DecodePlan *)g.ferr_plan;
+    g.ferr_plan = nullptr;
+    if (!p || !g.ferr_pin || !*(volatile unsigned *)g.ferr_pin) return;
+    *(volatile unsigned *)g.ferr_pin = 0;
+    g.stat_fused_timeouts++;
+    spec_cancel();
+    static const char *what =
+        "an attention workgroup of k_qkv_attn / k_attn_split_one gave up waiting for rows of its own launch (these launches "
+        "need all their workgroups resident at once: is another process, or a CU mask, holding compute units of this GPU?)";
+    bool live = false;
+    for (auto *q : g_plans) live = live || q == p;
+    if (!live) die("%s", what);
+    const bool whole = p->m.wte && p->m.output;  // a stage's garbage residual has already been handed on
+    if (!g.opt_fused_fallback || !can_rerun || !whole || p->m.N != 1)
+        die("%s; set GGML_HIP_FUSE_ATTN=0 GGML_HIP_ATTN_ONE=0 to run the two-launch forms", what);
+    static bool warned = false;
+    if (!warned) fprintf(stderr, "libggml_hip: %s — re-running the token on the two-launch forms and keeping them on this device slot\n", what);
+    warned = true;
+    if (g.opt_fuse_attn || g.opt_attn_one) {  // what comes back after a clean stretch (try_decode_plan)
+        g.fused_saved_fuse_attn = g.opt_fuse_attn;
+        g.fused_saved_attn_one = g.opt_attn_one;
+    }
+    g.fused_rearm_stretch = g.fused_rearm_stretch ? g.fused_rearm_stretch * 2 : (uint64_t)std::max(0, g.opt_fused_rearm_tokens);
+    g.fused_rearm_at = g.opt_fused_rearm_tokens > 0 ? g.stat_plan_tokens + g.fused_rearm_stretch : 0;
+    g.opt_fuse_attn = 0;
+    g.opt_attn_one = 0;
+    if (!g.opt_test_fused_timeout) g.opt_affine = 0;  // (stays off when the fused forms come back: a placement the dealing cannot rely on is the likeliest cause)
+    g.opt_test_fused_timeout = 0;
+    for (auto *q : g_plans) drop_plan_graphs(q);
+    const LlamaMatch &m = p->m;
+    {   // this token and position again: a speculative run queued behind the token has moved the device's parameters on
+        DecParams hp;
+        memset(&hp, 0, sizeof(hp));
+        hp.n_past = m.n_past;
+        hp.token = m.embd ? ((const int32_t *)m.embd->data)[0] : 0;
+        hp.tokens[0] = hp.token;
+        h2d_small((char *)p->prm, &hp, sizeof(hp));
+    }
+    plan_launch_decode(p, attn_variant(m, p, m.n_past + 1));
+    queue_results(p);  // the copies try_decode_plan queued for this token, again
+    d2h_finish();
+    if (*(volatile unsigned *)g.ferr_pin) die("%s — and again on the re-run", what);
+}
+// the wait a ggml_hip_graph_compute_begin left for later (defer_wait below)
+void finish_pending() {
+    if (!g.pending_wait) return;
+    const uint64_t t = now_ns();
+    g.pending_wait = false;
+    token_finish();
+    g.ns_wait += now_ns() - t;
+}
+
+// ggml_hip_graph_prepare: the match of the NEXT token's graph, made while the device runs the current one.  Only the plain case is
+// remembered — a single-token decode graph whose weights are resident and whose plan exists; everything else takes the usual way
+// at its begin().  Nothing of the plan is touched here: the token in flight may still need DecodePlan::m for a re-run.
+struct PrepMatch {
+    ggml_cgraph *gr = nullptr;
+    LlamaMatch m;
+    DecodePlan *p = nullptr;
+    uint64_t arena_seq = 0, wgen = 0;
+    int opt_gen = 0;
+};
+static bool prepare_decode_plan(ggml_cgraph *gr) {
+    if (!g.prep) g.prep = new PrepMatch();
+    PrepMatch *pm = (PrepMatch *)g.prep;
+    pm->gr = nullptr;
+    if (!g.opt_plan || !g.opt_prepare || !gr) return false;
+    LlamaMatch m;
+    if (!match_llama_decode(gr, m) || m.prompt || m.N != 1 || !plan_weights_resident(m)) return false;
+    const std::vector<uint64_t> sig = plan_signature(m);
+    const uint64_t wgen = g_dev_wgen[g.device & 63].load(std::memory_order_acquire);
+    DecodePlan *p = nullptr;
+    for (auto *q : g_plans)
+        if (q->sig == sig && q->wgen == wgen) p = q;
+    if (!p) return false;  // the first token of a shape builds its plan the usual way
+    pm->m = m;
+    pm->p = p;
+    pm->arena_seq = g_arena_seq.load(std::memory_order_acquire);
+    pm->wgen = wgen;
+    pm->opt_gen = g.opt_gen;
+    pm->gr = gr;
+    return true;
+}
+
+static bool try_decode_plan(ggml_cgraph *gr, bool defer_wait = false) {
+    g.chain_plan = nullptr;  // any new graph ends the chainable state; a single-token plan run re-arms it below
+    if (!g.opt_plan) return false;
+    if (g.fused_rearm_at && g.stat_plan_tokens >= g.fused_rearm_at) {  // a clean stretch behind a hand-off that gave up: the fused forms again
+        g.fused_rearm_at = 0;
+        g.opt_fuse_attn = g.fused_saved_fuse_attn;
+        g.opt_attn_one = g.fused_saved_attn_one;
+        g.stat_fused_rearms++;
+        spec_cancel();
+        if (g.stream) HIP_CHECK(hipStreamSynchronize(g.stream));
+        for (auto *q : g_plans) drop_plan_graphs(q);
+    }
+    const uint64_t t0 = now_ns();
+    LlamaMatch m;
+    DecodePlan *p = nullptr;
+    if (PrepMatch *pm = (PrepMatch *)g.prep) {  // matched ahead of time (ggml_hip_graph_prepare) and nothing has happened since that could change the answer?
+        if (pm->gr == gr && pm->arena_seq == g_arena_seq.load(std::memory_order_acquire) && pm->opt_gen == g.opt_gen &&
+            pm->wgen == g_dev_wgen[g.device & 63].load(std::memory_order_acquire))
+            for (auto *q : g_plans)
+                if (q == pm->p) p = q;
+        if (p) {
+            m = pm->m;
+            p->m = m;
+            g.stat_prepared_tokens++;
+        }
+        pm->gr = nullptr;
+    }
+    if (!p) {
+        if (!match_llama_decode(gr, m)) return false;
+        if (!plan_weights_resident(m)) {
+            // first evaluation of a model: tok_embeddings is a leaf the caller never offloads (models/llama lib.rs:52);
+            // upload the graph's leaves the way the generic executor would, then look again
+            upload_inputs(gr);
+            if (!plan_weights_resident(m)) return false;
+        }
+        if (m.prompt && m.kquant && !k_prompt_weights(m, nullptr)) {  // (before anything is built or launched) no room for the copies:
+            if (m.N > MULTI_MAX_N) return false;                       // the node-by-node executor, or for up to 31 tokens the K plan's chunks
+            LlamaMatch m2;
+            tl_k_prompt_off = true;
+            const bool ok = match_llama_decode(gr, m2);
+            tl_k_prompt_off = false;
+            if (!ok) return false;
+            m = m2;
+        }
+        std::vector<uint64_t> sig = plan_signature(m);
+        const uint64_t wgen = g_dev_wgen[g.device & 63].load(std::memory_order_acquire);
+        {   // plans built before some weight record of this device was freed (perhaps by a sibling slot): gone before anything matches them
+            bool stale = false;
+            for (auto *q : g_plans) stale = stale || q->wgen != wgen;
+            if (stale) drop_all_plans();
+        }
+        for (auto *q : g_plans)
+            if (q->sig == sig) p = q;
+        if (!p) {
+            if (g_plans.size() >= 32) drop_all_plans();
+            p = build_plan(m, sig);
+            p->wgen = wgen;
+            g_plans.push_back(p);
+        } else {
+            p->m = m;  // same devices buffers, fresh tensor pointers of this evaluation (n_past, embd)
+        }
+    }
+    const uint64_t t1 = now_ns();
+    // ---- speculative next token: is this evaluation the one the device is already running? ----
+    bool spec_hit = false;
+    if (g.spec.pending) {
+        g.spec.pending = false;
+        const bool same = g.spec.plan == (void *)p && m.N == 1 && !m.prompt && m.embd && m.n_past == g.spec.n_past &&
+                          attn_variant(m, p, m.n_past + 1) == g.spec.av && g.opt_graph && !g.timing.on;
+        if (same) {
+            HIP_CHECK(hipEventSynchronize(g.spec.tok_ev));  // long done: recorded right behind the argmax kernel of the previous token
+            spec_hit = *g.spec.tok_pin == ((const int32_t *)m.embd->data)[0];
+        }
+        if (spec_hit) {
+            g.stat_spec_hits++;
+        } else {
+            g.stat_spec_misses++;
+            g.spec.cooldown = 8;  // a sampler that does not take the first maximum: stop guessing for a while
+        }
+    }
+    DecParams hp;
+    hp.n_past = m.n_past;
+    hp.token = m.embd ? ((const int32_t *)m.embd->data)[0] : 0;
+    hp.store_at = hp.pad1 = 0;
+    for (int i = 0; i < 32; i++) {
+        hp.tokens[i] = (m.embd && i < m.N && !m.prompt) ? ((const int32_t *)m.embd->data)[i] : 0;
+        if (m.wte && (hp.tokens[i] < 0 || hp.tokens[i] >= m.wte->ne[1])) die("token id %d out of range", hp.tokens[i]);
+    }
+    if (!spec_hit) h2d_small((char *)p->prm, &hp, sizeof(hp));  // (a hit: the device wrote exactly these itself)
+    if (m.prompt) {  // prompt plan: all token ids, launched eagerly
+        if (m.wte) {
+            const int32_t *ids = (const int32_t *)m.embd->data;
+            for (int i = 0; i < m.N; i++)
+                if (ids[i] < 0 || ids[i] >= m.wte->ne[1]) die("token id %d out of range", ids[i]);
+            h2d_small((char *)p->p_tok, ids, (size_t)m.N * 4);
+        }
+        plan_launch_prompt(p);
+        if (m.logits && m.logits->backend == GGML_BACKEND_CPU)  // (the logits alone: the embedding rows of a batch stay on the device, queue_results)
+            d2h_queue(m.logits->data, p->logits_out, (size_t)m.V * m.N * 4);
+        const uint64_t t2p = now_ns();
+        g.ns_match += t1 - t0;
+        g.ns_launch += t2p - t1;
+        g.stat_prompt_plan_tokens += (uint64_t)m.N;
+        if (defer_wait) {  // ggml_hip_graph_compute_begin (a batch of feed_prompt behind which another follows)
+            g.pending_wait = true;
+            g.pending_light = true;
+            return true;
+        }
+        d2h_finish();
+        g.ns_wait += now_ns() - t2p;
+        return true;
+    }
+    const bool use_graph = g.opt_graph && !g.timing.on;
+    {   // graphs captured while this device had another number of slots on it froze another choice of kernels
+        const uint64_t dgen = g_dev_gen[g.device & 63].load(std::memory_order_relaxed);
+        if (p->dev_gen != dgen) {
+            if (p->dev_gen) {
+                HIP_CHECK(hipStreamSynchronize(g.stream));
+                drop_plan_graphs(p);
+            }
+            p->dev_gen = dgen;
+        }
+    }
+    // the attention variant for this context length (a graph each of the same plan)
+    const int av = attn_variant(m, p, m.n_past + 1);
+    const bool long_ctx = av == AV_SPLIT;
+    auto launch = [&] {
+        if (m.N > 1 && !m.kquant)
+            plan_launch_multi(p);
+        else
+            plan_launch_decode(p, av);
+    };
+    if (spec_hit) {
+        // already enqueued behind the previous token (same plan, position, token and attention variant): only the results are missing
+    } else if (use_graph) {
+        if (!p->exec_v[av]) capture_into(&p->graph_v[av], &p->exec_v[av], launch);
+        HIP_CHECK(hipGraphLaunch(p->exec_v[av], g.stream));
+        p->replays++;
+    } else {
+        launch();
+    }
+    if (spec_hit) {  // the speculative run's results sit in the plan's alternates: into the caller-visible mirrors first (stream order)
+        HIP_CHECK(hipMemcpyAsync(p->logits_out, p->logits_alt, (size_t)m.V * 4, hipMemcpyDeviceToDevice, g.stream));
+        if (p->emb_out) HIP_CHECK(hipMemcpyAsync(p->emb_out, p->emb_alt, (size_t)m.E * 4, hipMemcpyDeviceToDevice, g.stream));
+    }
+    queue_results(p);
+    token_results_queue(p);
+    // ---- ... and the next one on spec: greedy token on the device, then the plan again, behind this token's result copies ----
+    if (g.spec.cooldown > 0) g.spec.cooldown--;
+    if (g.opt_speculate_next && g.spec.cooldown == 0 && use_graph && m.N == 1 && m.logits && m.wte && m.output &&
+        m.n_past + 2 < m.C && p->exec_v[av]) {
+        const int av2 = attn_variant(m, p, m.n_past + 2);
+        {
+            if (!g.results_ev) HIP_CHECK(hipEventCreateWithFlags(&g.results_ev, hipEventDisableTiming));
+            if (!g.spec.tok_ev) {
+                HIP_CHECK(hipEventCreateWithFlags(&g.spec.tok_ev, hipEventDisableTiming));
+                HIP_CHECK(hipHostMalloc((void **)&g.spec.tok_pin, 64, hipHostMallocDefault));
+                HIP_CHECK(hipMalloc((void **)&g.spec.tok_dev, 64));
+            }
+            HIP_CHECK(hipEventRecord(g.results_ev, g.stream));  // the host waits for THIS (d2h_finish), not for the stream's end
+            g.results_ev_armed = true;
+            g.results_ev_copies = stg.pending.size();
+            hipLaunchKernelGGL(k_argmax_next, dim3(1), dim3(1024), 0, g.stream, (const float *)p->logits_out, (int)m.V, p->prm, g.spec.tok_dev);
+            HIP_CHECK(hipMemcpyAsync(g.spec.tok_pin, g.spec.tok_dev, 4, hipMemcpyDeviceToHost, g.stream));
+            HIP_CHECK(hipEventRecord(g.spec.tok_ev, g.stream));
+            hipGraphExec_t &e2 = p->exec_s[av2];
+            if (!e2) {  // the plan once more, captured with its final norm / lm_head aimed at the alternates (DecodePlan::logits_alt)
+                p->spec_out = true;
+                capture_into(&p->graph_s[av2], &e2, [&] { plan_launch_decode(p, av2); });
+                p->spec_out = false;
+            }
+            HIP_CHECK(hipGraphLaunch(e2, g.stream));
+            g.spec.pending = true;
+            g.spec.plan = p;
+            g.spec.n_past = m.n_past + 1;
+            g.spec.av = av2;
+        }
+    }
+    const uint64_t t2 = now_ns();
+    g.ns_match += t1 - t0;
+    g.ns_launch += t2 - t1;
+    g.stat_plan_tokens += (uint64_t)m.N;
+    if (long_ctx) g.stat_split_tokens++;
+    if (m.N == 1 && !long_ctx) {
+        const FusedShape fs = fused_qkv_shape(m, av_heads_split(av));
+        if (fs.ok) g.stat_fused_tokens++;
+        if (fs.ok && fs.wo) g.stat_fused_wo_tokens++;
+        if (fs.ok && fs.affine) g.stat_fused_affine_tokens++;
+    }
+    if (av >= AV_FUSED2) g.stat_fused_heads_tokens++;
+    if (m.kquant) g.stat_kplan_tokens += (uint64_t)m.N;
+    g.chain_plan = (m.N == 1 && m.logits && m.wte) ? (void *)p : nullptr;  // whole model, one token: chainable
+    g.chain_graph = gr;
+    if (defer_wait) {  // ggml_hip_graph_compute_begin: the caller overlaps host work, then ..._end() waits
+        g.pending_wait = true;
+        g.pending_light = m.N > 1;  // (the waiting launches — fused attention, the one-launch split attention — are single-token forms)
+        return true;
+    }
+    token_finish();
+    g.ns_wait += now_ns() - t2;
+    return true;
+}
+
+// SURVEY section 8f N3: n greedy tokens back to back without a host round trip per token.  `last` must be the cgraph
+// of the caller's most recent ggml_graph_compute (a single-token LLaMA evaluation that ran as the fused plan, whole
+// model on this device); the plan's decode parameters still hold that token and position on the device, and its
+// logits are in HBM.  Per token: k_argmax_next (argmax -> parameters of the next replay) + one replay of the plan.
+// Returns 0 and fills out_tokens[n] (and last_logits[V] with the logits after the n-th token, if not NULL); -1 if
+// the precondition does not hold (the caller then decodes token by token).
+static int decode_greedy_chain(ggml_cgraph *last, int n, int32_t *out_tokens, float *last_logits) {
+    finish_pending();
+    if (g.spec.pending) {  // the device has already gone one token further on its own: the caller decodes token by token (and hits)
+        spec_cancel();
+        return -1;
+    }
+    DecodePlan *p = (DecodePlan *)g.chain_plan;
+    if (!p || g.chain_graph != last || n < 1) return -1;
+    bool live = false;
+    for (auto *q : g_plans) live = live || q == p;
+    const LlamaMatch &m = p->m;
+    if (!live || m.N != 1 || !m.logits || !m.wte || m.n_past + 1 + n > m.C) return -1;
+    if (p->chain_cap < n) {
+        if (p->chain_out) (void)hipFree(p->chain_out);
+        p->chain_cap = std::max(n, 256);
+        HIP_CHECK(hipMalloc((void **)&p->chain_out, (size_t)p->chain_cap * 4));
+    }
+    if (!p->chain_ring) HIP_CHECK(hipMalloc((void **)&p->chain_ring, 64 * 4));
+    const bool use_graph = g.opt_graph && !g.timing.on && (p->exec_v[0] || p->exec_v[1] || p->exec_v[2] || p->exec_v[3] || p->exec_v[4]);
+    int i0 = 0;
+    // option chain_k = K (> 1): K tokens per graph launch — every kernel of the plan reads its token and position from the
+    // DecParams that k_argmax_next advances on the device, so the launches of consecutive tokens are the same launches.  Only
+    // while the whole group stays on the short-context attention variant; the graph's sampled ids land in chain_out[i0 ..].
+    if (use_graph && g.opt_chain_k > 1) {
+        const int K = g.opt_chain_k;
+        const auto long_at = [&](int i) { return attn_variant(m, p, m.n_past + 1 + i + 1) != AV_SHORT; };
+        while (i0 + K <= n && !long_at(i0 + K - 1)) {
+            if (!p->exec_chain || p->chain_k != K) {  // (the graph writes its ids to a fixed ring: reusable at any offset)
+                if (p->exec_chain) (void)hipGraphExecDestroy(p->exec_chain);
+                if (p->graph_chain) (void)hipGraphDestroy(p->graph_chain);
+                capture_into(&p->graph_chain, &p->exec_chain, [&] {
+                    for (int k = 0; k < K; k++) {
+                        hipLaunchKernelGGL(k_argmax_next, dim3(1), dim3(1024), 0, g.stream, (const float *)p->logits_out, (int)m.V, p->prm,
+                                           p->chain_ring + k);
+                        plan_launch_decode(p, AV_SHORT);
+                    }
+                });
+                p->chain_k = K;
+            }
+            HIP_CHECK(hipGraphLaunch(p->exec_chain, g.stream));
+            if (fused_qkv_shape(m).ok) g.stat_fused_tokens += (uint64_t)K;
+            HIP_CHECK(hipMemcpyAsync(p->chain_out + i0, p->chain_ring, (size_t)K * 4, hipMemcpyDeviceToDevice, g.stream));
+            i0 += K;
+        }
+    }
+    for (int i = i0; i < n; i++) {
+        hipLaunchKernelGGL(k_argmax_next, dim3(1), dim3(1024), 0, g.stream, (const float *)p->logits_out, (int)m.V, p->prm,
+                           p->chain_out + i);
+        // the token of step i sits at position n_past + 1 + i; same rule as try_decode_plan for the attention variant
+        const int av = attn_variant(m, p, m.n_past + 1 + i + 1);
+        if (av != AV_SPLIT && fused_qkv_shape(m, av_heads_split(av)).ok) g.stat_fused_tokens++;
+        if (av >= AV_FUSED2) g.stat_fused_heads_tokens++;
+        if (use_graph) {
+            hipGraph_t &gr_v = p->graph_v[av];
+            hipGraphExec_t &e1 = p->exec_v[av], &e2 = p->exec2_v[av];
+            if (!e1) capture_into(&gr_v, &e1, [&] { plan_launch_decode(p, av); });  // the chain crossed into a variant no evaluation has captured yet
+            if (!e2) HIP_CHECK(hipGraphInstantiate(&e2, gr_v, nullptr, nullptr, 0));
+            HIP_CHECK(hipGraphLaunch((i & 1) ? e2 : e1, g.stream));
+        } else {
+            plan_launch_decode(p, av);
+        }
+    }
+    HIP_CHECK(hipGetLastError());
+    d2h_queue(out_tokens, (const char *)p->chain_out, (size_t)n * 4);
+    if (last_logits) d2h_queue(last_logits, p->logits_out, (size_t)m.V * 4);
+    token_results_queue(p);
+    token_finish(false);  // a hand-off that gave up inside the chain has already fed the sampler garbage: abort
+    p->m.n_past += n;
+    p->replays += use_graph ? (uint64_t)n : 0;
+    g.stat_plan_tokens += (uint64_t)n;
+    g.chain_plan = nullptr;  // the caller's next evaluation re-arms it
+    return 0;
+}

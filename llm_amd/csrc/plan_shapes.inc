@@ -1,0 +1,383 @@
+// plan_*.inc — the fused LLaMA plans.  The graph that crates/models/llama/src/lib.rs:166-362 builds (37 nodes per layer +
+// get_rows + final norm/mul/lm_head, rebuilt by the caller for EVERY evaluation: crates/llm-base/src/inference_session.rs:230)
+// is recognised as a whole and executed as one of four launch sequences over the same cached DecodePlan:
+//   single-token decode, block formats (plan_launch_all): 3 launches per layer with wq|wk|wv + attention + wo fused, 5 without;
+//   single-token decode and chunks of up to 31 tokens, K-quants (plan_launch_k): 10-13 launches per layer;
+//   a chunk of 2..31 tokens, block formats (plan_launch_multi): 8 launches per layer and pass of 8 columns;
+//   a prompt batch (plan_launch_prompt): 13 launches per layer around the matrix-core GEMMs, launched eagerly.
+// The first three are captured once in a hipGraph per attention variant and replayed for the following tokens with only
+// {n_past, token} changing in a device-side parameter block.  One file per concern, included in this order from
+// backend_executor.inc inside hip_backend.hip's anonymous namespace; nothing needs a forward declaration:
+//   plan_shapes.inc  LlamaMatch, DecodePlan and every "which kernel, which grid for which shape" decision (plain host functions
+//                    the matcher, the launchers, the run loop and the test hooks of backend_tools.inc all call)
+//   plan_match.inc   the structural graph matcher
+//   plan_build.inc   weights, signature and activation pool of a plan
+//   plan_decode.inc  the single-token launchers: plan_launch_all, plan_launch_k
+//   plan_prompt.inc  plan_launch_multi, prompt_attention, plan_launch_prompt
+//   plan_run.inc     capture and replay, speculation, the fused-timeout re-run, the greedy chain
+//
+// The matcher is structural (it follows src[] pointers from the logits back to get_rows and checks every view's
+// shape/stride/offset against the KV-cache layout), so any graph that is not exactly the reference's LLaMA
+// graph falls through to the generic per-node executor — same results, more launches.
+
+struct LayerW {
+    const ggml_tensor *attn_norm = nullptr, *wq = nullptr, *wk = nullptr, *wv = nullptr, *wo = nullptr,
+                      *ffn_norm = nullptr, *w1 = nullptr, *w2 = nullptr, *w3 = nullptr;
+    const ggml_tensor *cur = nullptr;  // the normed activation feeding wq/wk/wv (identity key for the KV stores)
+    bool k_store = false, v_store = false;
+};
+static const int PROMPT_PLAN_MAX = 4096;  // tokens per evaluation the prompt plan accepts
+#define MULTI_MAX_N 31  /* tokens of the multi-token plan: passes of 8 columns below the prompt plan's threshold */
+struct LlamaMatch {
+    int L = 0;
+    int64_t E = 0, H = 0, Hkv = 0, D = 0, F = 0, V = 0, C = 0, Egqa = 0;
+    int n_past = 0, n_dims = 0;
+    int N = 1;  // tokens in this evaluation: 1 = decode, 2..31 below mmq_min = a prompt chunk (multi-token plan), >= mmq_min = prompt plan
+    bool prompt = false;  // the prompt plan takes it
+    bool kquant = false;  // every matrix is a K-quant (any mix of Q2_K … Q6_K): the K plan (plan_launch_k), single-token decode only
+    float eps = 0, freq_base = 0, freq_scale = 0, kq_scale = 0;
+    ggml_type wtype = GGML_TYPE_F32;
+    const ggml_tensor *wte = nullptr, *norm = nullptr, *output = nullptr, *embd = nullptr, *memory_k = nullptr,
+                      *memory_v = nullptr;
+    ggml_tensor *logits = nullptr, *embedding = nullptr;
+    const ggml_tensor *stage_in = nullptr, *stage_out = nullptr;  // layer-split hand-off buffers (persistent f32 leaves)
+    std::vector<LayerW> layers;
+};
+// ---------------------------------------------------------------------------------------------------
+// the cached plan
+// ---------------------------------------------------------------------------------------------------
+struct DecodePlan {
+    std::vector<uint64_t> sig;
+    LlamaMatch m;  // tensors of the graph the plan was built from (weights are persistent; IO nodes by address)
+    struct LW {
+        QWeight wq, wk, wv, wo, w1, w2, w3;
+        const float *attn_norm, *ffn_norm;
+    };
+    std::vector<LW> lw;
+    struct KLW {  // K plan: the same seven matrices as planar K weights (each carries its own type)
+        KWeight wq, wk, wv, wo, w1, w2, w3;
+    };
+    std::vector<KLW> klw;
+    KWeight k_wte{}, k_output{};
+    // K plan activations: f32 rows of wk / wv / the merged heads / w3, and ONE Q8_K row (max(E, F) wide) every mat-vec reads
+    float *k_kf = nullptr, *k_vf = nullptr, *k_att = nullptr, *k_g3 = nullptr;
+    int8_t *k_q8 = nullptr;
+    float *k_d8 = nullptr;
+    int16_t *k_bs = nullptr;
+    QWeight wte, output;
+    const float *norm = nullptr;
+    __half *mem_k = nullptr, *mem_v = nullptr;
+    __half *mem_k_at(int il) const { return mem_k + (size_t)il * m.C * m.Egqa; }  // layer il's part of the caches
+    __half *mem_v_at(int il) const { return mem_v + (size_t)il * m.C * m.Egqa; }
+    // persistent activations
+    char *pool = nullptr;
+    DecParams *prm = nullptr;
+    float *rope = nullptr;      // this token's RoPE (cos, sin) table, D/2 pairs (k_rope_table)
+    unsigned *epoch = nullptr;  // k_qkv_attn (kernels/decode_fused.h): the token's granule tag, bumped by k_rope_table
+    const void *hot = nullptr;  // 256 zero bytes that every dummy ring step of k_mmvq_big reads (BigArgs::hot)
+    unsigned *ferr = nullptr;   // ... raised when an attention workgroup gave up waiting for its rows
+    unsigned long long *gran = nullptr;  // ... granules: (E + 2 Egqa) / 2 per layer
+    unsigned long long *gran_at(int il) const { return gran + (size_t)il * (size_t)((m.E + 2 * m.Egqa) / 2); }
+    unsigned long long *ogran = nullptr;      // ... E / 32 x OGRAN granules per layer: the attention output on its way to wo (WO form)
+    unsigned long long *dead_gran = nullptr;  // one layer's worth of granules nobody writes (test hook: a hand-off that never arrives)
+    uint64_t dev_gen = 0;                // g_dev_gen of the device when the graphs below were captured (see device_sharers)
+    uint64_t wgen = 0;                   // g_dev_wgen of the device when the plan was built: a weight record freed since (by ANY slot of the device) makes the plan stale
+    float *xa = nullptr, *xb = nullptr, *q = nullptr, *gate = nullptr, *logits = nullptr;
+    int8_t *e_lo = nullptr, *e_hi = nullptr, *f_lo = nullptr, *f_hi = nullptr;
+    float *e_d = nullptr, *f_d = nullptr;
+    int *e_s = nullptr, *f_s = nullptr;
+    float *e_dT = nullptr, *f_dT = nullptr;  // multi-token plan: the same scales / sums as [block][8] tables (k_mmq_cols)
+    int *e_sT = nullptr, *f_sT = nullptr;
+    // prompt plan (N > 8): f32 GEMM outputs, the f16 GEMM operand, scores, token ids
+    float *p_te = nullptr, *p_qf = nullptr, *p_kf = nullptr, *p_vf = nullptr, *p_mg = nullptr, *p_g1 = nullptr, *p_g3 = nullptr, *p_sc = nullptr;
+    _Float16 *p_x16 = nullptr, *p_p16 = nullptr;  // GEMM operand; softmax probabilities as f16 rows of (C + 8) & ~7
+    int *p_tok = nullptr;
+    float *stage_in = nullptr, *stage_out = nullptr;  // layer split: residual received / handed on
+    float *emb_out = nullptr;   // device mirror of the embedding_result node
+    char *logits_out = nullptr; // device mirror of the logits node
+    // the backend's own speculative next-token run (option speculate_next) writes its logits / embedding row HERE, never into the
+    // mirrors above: those are caller-visible (ggml_hip_topk, ggml_hip_tensor_get, llm_session_read_node read them on the device)
+    // and must keep the LAST EVALUATED token's values while the speculation is in flight or unused.  On a hit the results go to
+    // the host from here and are copied into the mirrors on the stream.
+    char *logits_alt = nullptr;
+    float *emb_alt = nullptr;
+    bool spec_out = false;  // set while the speculative graph is captured: plan_launch_* aim the final norm / lm_head at the alternates
+    hipGraph_t graph_s[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};       // ... that graph, per attention variant
+    hipGraphExec_t exec_s[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    int *chain_out = nullptr;   // ggml_hip_decode_greedy_chain: sampled ids (device)
+    int *chain_ring = nullptr;  // ... of one K-token graph launch (option chain_k), copied into chain_out behind it
+    int chain_cap = 0;
+    // one captured graph per ATTENTION VARIANT of the plan (enum below); exec2: a second instance of the same graph — a chain
+    // alternates so that a launch never waits for its own previous run
+    hipGraph_t graph_v[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    hipGraphExec_t exec_v[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}, exec2_v[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    float *att_sc = nullptr, *att_pmax = nullptr, *att_part = nullptr;  // scratch of the split attention
+    unsigned long long *att_mxg = nullptr, *att_sumg = nullptr, *att_partg = nullptr;  // ... as one launch (k_attn_split_one): range maxima / sums / partial-output granules, [L] sets of them (att_*_at)
+    unsigned long long *att_mxg_at(int il) const { return att_mxg + (size_t)il * m.H * att_S; }
+    unsigned long long *att_sumg_at(int il) const { return att_sumg + (size_t)il * m.H * att_S * 2; }
+    unsigned long long *att_partg_at(int il) const { return att_partg + (size_t)il * m.H * att_S * m.D; }
+    unsigned *att_cnt = nullptr;                                         // ... and the per-head arrival counters
+    int att_S = 1;                       // workgroups per head of the split attention
+    hipGraph_t graph_chain = nullptr;      // option chain_k: k_argmax_next + one token, K times over, as ONE graph
+    hipGraphExec_t exec_chain = nullptr;
+    int chain_k = 0;                       // tokens captured in graph_chain
+    uint64_t replays = 0;
+    uint64_t w16_gen = 0;  // g.w16_gen the QWeight::w16 pointers above were read at (0 = never)
+};
+
+std::vector<DecodePlan *> g_plans_[GGML_HIP_MAX_BACKENDS];  // per slot: a plan holds device addresses
+#define g_plans (g_plans_[g.slot])
+
+// the captured graphs of a plan (they freeze which kernels run: options and the device's slot count at capture time)
+void drop_plan_graphs(DecodePlan *p) {
+    for (int v = 0; v < 5; v++) {
+        if (p->exec_v[v]) (void)hipGraphExecDestroy(p->exec_v[v]);
+        if (p->exec2_v[v]) (void)hipGraphExecDestroy(p->exec2_v[v]);
+        if (p->graph_v[v]) (void)hipGraphDestroy(p->graph_v[v]);
+        p->exec_v[v] = p->exec2_v[v] = nullptr;
+        p->graph_v[v] = nullptr;
+        if (p->exec_s[v]) (void)hipGraphExecDestroy(p->exec_s[v]);
+        if (p->graph_s[v]) (void)hipGraphDestroy(p->graph_s[v]);
+        p->exec_s[v] = nullptr;
+        p->graph_s[v] = nullptr;
+    }
+    if (p->exec_chain) (void)hipGraphExecDestroy(p->exec_chain);
+    if (p->graph_chain) (void)hipGraphDestroy(p->graph_chain);
+    p->exec_chain = nullptr;
+    p->graph_chain = nullptr;
+    p->chain_k = 0;
+}
+void destroy_plan(DecodePlan *p) {
+    drop_plan_graphs(p);
+    if (p->chain_ring) (void)hipFree(p->chain_ring);
+    if (p->pool) (void)hipFree(p->pool);
+    delete p;
+}
+// A speculative next-token run is in flight or finished unused: nothing of it may be taken for a result any more (its plan's
+// buffers are about to be reused, dropped, or replayed for a measurement).  The stream is drained so that it is over.
+void spec_cancel() {
+    if (!g.spec.pending) return;
+    g.spec.pending = false;
+    if (g.stream) HIP_CHECK(hipStreamSynchronize(g.stream));
+}
+void drop_all_plans() {
+    spec_cancel();
+    if (g_plans.empty()) return;
+    if (g.stream) HIP_CHECK(hipStreamSynchronize(g.stream));
+    for (auto *p : g_plans) destroy_plan(p);
+    g_plans.clear();
+    g.ferr_plan = nullptr;
+}
+static inline size_t attn_decode_lds(int64_t C, int64_t D) { return (size_t)(C + D) * 4 + (size_t)C * 2; }
+static const size_t ATTN_DECODE_LDS_MAX = 150 * 1024;  // of the CU's 160 KiB (the kernel's static arrays take a little)
+// Waves per workgroup of a k_mmvq_big launch: the count in [8, 16] with the best
+//   (units / (rounds * G * W))  x  (1 - 0.015 * (16 - W))
+// i.e. how evenly `units` are dealt over G workgroups of W waves, discounted by what fewer waves cost in loads in
+// flight (measured: 8 waves stream w1|w3 12 % slower than 16).  7B: wq|wk|wv 12 waves (6144 row pairs: 2 per wave
+// instead of 2|1: 11.1 -> 9.5 us per launch), w1|w3 15; 13B: wo and w2 10 (5120 rows: 2 per wave instead of 2|1).
+static int big_waves(int64_t units, int G, int min_waves) {
+    static const int forced = getenv("GGML_HIP_BIG_WAVES") ? atoi(getenv("GGML_HIP_BIG_WAVES")) : 0;
+    if (forced >= 8 && forced <= BIG_W) return std::max(forced, min_waves);
+    auto score = [&](int W) {
+        const int64_t per_round = (int64_t)G * W, rounds = (units + per_round - 1) / per_round;
+        return (double)units / (double)(rounds * per_round) * (1.0 - 0.015 * (BIG_W - W));
+    };
+    int best = BIG_W;
+    for (int W = BIG_W - 1; W >= std::max(8, min_waves); W--)
+        if (score(W) > score(best) + 1e-9) best = W;
+    return best;
+}
+// what the staging of a k_mmvq_big launch needs: Q8 source one thread per block; f32 source 24 elements per thread; the norm 8
+// stager waves (+ the 2 RoPE-table waves of wq|wk|wv).  Above BIG_W the launch cannot stage the row (ggml_hip_debug_mat_vec_big).
+static int big_min_waves(int xsrc, int epi, int64_t nb) {
+    int min_waves = 8;
+    if (xsrc == XSRC_Q8) min_waves = (int)((nb + 63) / 64);
+    if (xsrc == XSRC_F32) min_waves = (int)((nb * 32 + 24 * 64 - 1) / (24 * 64));
+    if (xsrc == XSRC_NORM) min_waves = epi == EPI_QKV ? 10 : 8;
+    return std::max(min_waves, 8);
+}
+// workgroups of a mat-vec launch over `cus` CUs: one resident wave of workgroups, BIG_W units each before a second round starts
+static inline int big_groups(int64_t units, int cus) { return (int)std::min<int64_t>(cus, std::max<int64_t>(1, (units + BIG_W - 1) / BIG_W)); }
+static inline int64_t big_rounds(int64_t units, int G, int W) { return (units + (int64_t)G * W - 1) / ((int64_t)G * W); }
+// the dealing of one k_mmvq_big launch: G workgroups of which W waves take units, and its LDS; !ok: more than 64 units per wave
+// (one epilogue lane per unit of a wave)
+struct BigShape {
+    bool ok;
+    int G, W;
+    size_t lds;
+};
+static BigShape big_shape(int xsrc, int epi, int64_t nb, int64_t units) {
+    BigShape s;
+    s.G = big_groups(units, g.num_cus);
+    s.W = big_waves(units, s.G, big_min_waves(xsrc, epi, nb));
+    s.ok = big_rounds(units, s.G, s.W) <= 64;
+    s.lds = (size_t)((nb + 63) / 64 * 64) * 40;
+    return s;
+}
+// wq|wk|wv + attention in one launch (kernels/decode_fused.h): n_head attention workgroups + the mat-vec on the remaining
+// G - n_head.  Taken when the mat-vec deals as evenly over G - n_head workgroups as over G (7B on 256 CUs: 6144 row pairs
+// = 2 per wave of 224 x 14 as of 256 x 12) — otherwise the two-launch pair is the faster one.
+// Attention variants of the single-token plan (one hipGraph each, chosen per token by the context length: attn_variant):
+//   AV_SHORT  the attention of a head is ONE workgroup: inside the wq|wk|wv launch (k_qkv_attn) where the shape allows, else k_attn_decode
+//   AV_SPLIT  plain wq|wk|wv launch, then the position-split attention over all CUs (k_attn_split_one / the three launches)
+//   AV_FUSED2 / 3 / 4  k_qkv_attn with 2 / 3 / 4 attention workgroups per head (512 positions each: up to 1024 / 1536 / 2048)
+enum { AV_SHORT = 0, AV_SPLIT = 1, AV_FUSED2 = 2, AV_FUSED3 = 3, AV_FUSED4 = 4, AV_COUNT = 5 };
+static inline int av_heads_split(int av) { return av >= AV_FUSED2 ? av : 1; }
+struct FusedShape {
+    bool ok = false;
+    int G = 0, W = 0, S = 1;
+    bool wo = false;   // the WO form: wo + residual as the mat-vec workgroups' second phase (kernels/decode_fused.h wo_tail)
+    bool affine = false;  // head h's rows of wq|wk|wv are dealt to the mat-vec workgroups of the XCD its attention workgroup runs on (BigArgs::aff_hpl)
+};
+static FusedShape fused_qkv_shape(const LlamaMatch &m, int S = 1) {
+    FusedShape s;
+    if (!g.opt_fuse_attn || !g.opt_big || m.kquant || m.N != 1 || m.D > 128 || m.D % 32 != 0) return s;
+    const int H = (int)m.H * S;  // attention workgroups
+    const int64_t units = (m.E + 2 * m.Egqa) / 2;
+    if (H + 1 > g.num_cus) return s;
+    // several slots (sessions) on this GPU: their launches run side by side, and attention workgroups hold a CU until their
+    // producers have run — all of them together must leave most of the chip to producers, or nobody may wait at all.  Measured
+    // (bench.py --mode sessions, LLaMA-7B Q4_0, aggregate tokens/s fused / two-launch): 2 sessions 1030 / 1006, 3 sessions
+    // 1139 / 1190 — a quarter of the CUs is the limit (7B: two sessions keep the fused launch, three take the pair).
+    if (device_sharers() > 1 && (int64_t)device_sharers() * H > g.num_cus / 4) return s;
+    s.S = S;
+    // workgroups of the plain launch (launch_big) and of the mat-vec part here: one resident wave of workgroups either way
+    const int G0 = big_groups(units, g.num_cus), Gp = big_groups(units, g.num_cus - H);
+    const int Wp = big_waves(units, Gp, big_min_waves(XSRC_NORM, EPI_QKV, m.E / 32));
+    if (big_rounds(units, Gp, Wp) > 64) return s;
+    // one attention workgroup per head: measured to pay wherever the mat-vec keeps most of the chip (tests/tools/ctx_sweep.py at 200 /
+    // 400 positions, ms per token two-launch -> fused: 7B Q4_0 224 of 256 workgroups 1.37 -> 1.27; 13B Q5_1, 216: 2.81 -> 2.60 and
+    // 2.97 -> 2.69 (the WO form rides along); 65B Q8_0, 192: 12.67 -> 12.40).  Below ~70 % of the plain launch's workgroups nothing
+    // was measured: refused.
+    if (S == 1 && g.opt_fuse_attn < 2 && (Gp * 10 < G0 * 7 || Gp < 2 * H)) return s;  // 2 = wherever it is legal (tests)
+    if (S > 1) {
+        // several workgroups per head take CUs from the mat-vec for the whole launch.  Measured against the best other path
+        // (tests/tools/ctx_sweep.py, ms per token, S = 2 / 3 / 4 at 700-900 / 1100 / 1800 positions; + = the fused heads win):
+        //   7B  Q4_0 28 MB of wq|wk|wv, 192 / 160 / 128 workgroups left: + + + (641 against 610 tok/s at 1800)
+        //   7B  Q5_1 38 MB: + + + (1.68 / 1.77 / 1.84 against 1.76 / 1.91 / 1.95);  7B Q8_0 53 MB: + + + (1.86 / 1.96 / 2.01 against 1.96 / 2.05 / 2.10)
+        //   13B Q4_0 44 MB, 176 / 136 / 96 left: + + = (2.37 / 2.46 / 2.63 against 2.44 / 2.54 / 2.64);  13B Q8_0 84 MB: + + - (3.09 / 3.21 / 3.45 against 3.17 / 3.26 / 3.36)
+        //   13B Q5_1 59 MB: - - - (3.05 / 3.06 / 3.29 against 2.97 / 3.02 / 3.09);  65B Q8_0 214 MB, 128 left: - (13.32 against 12.79)
+        // No single quantity explains all of it; the rule is a fit: the mat-vec keeps 45 % of the plain launch's workgroups, and the stream — counted
+        // 1.7-fold for the types whose 5-bit unpack makes a workgroup compute-bound — is at most 90 MB.
+        const double qkv_bytes = (double)(m.E + 2 * m.Egqa) * (double)(m.E / 32) * (double)blk_bytes(qt_of(m.wtype));
+        const bool q5 = qt_of(m.wtype) == QT_Q5_0 || qt_of(m.wtype) == QT_Q5_1;
+        if (Gp < g.num_cus / 4) return s;
+        if (g.opt_fuse_attn < 2 && (Gp * 100 < G0 * 45 || qkv_bytes * (q5 ? 1.7 : 1.0) > 90e6)) return s;
+    }
+    s.ok = true;
+    s.G = H + Gp;
+    s.W = Wp;
+    // wo under the attention's tail: both directions of the launch wait for each other, so the whole launch must be resident —
+    // this slot alone on the GPU — and a workgroup's rows of wo, the gathered activation and the granule sweep must fit
+    if (g.opt_fuse_wo && device_sharers() == 1) {
+        const int64_t nbE = m.E / 32, rows = (m.E + Gp - 1) / Gp;
+        if (rows <= 16 * WO_RW && (nbE + 63) / 64 <= 4 && nbE * OGRAN <= 1024 * WO_NG_MAX) s.wo = true;
+    }
+    // XCD-affine dealing: head h's attention workgroup(s) at blockIdx = h mod n_head, the mat-vec workgroups behind them in multiples of 8, MHA
+    // (a K / V head feeds ONE attention workgroup), this slot alone on the GPU (nobody else's workgroups in the dispatcher's round robin)
+    if (g.opt_affine && g.xcd_labels == 1 && device_sharers() == 1 && m.H % 8 == 0 && Gp % 8 == 0 && m.Egqa == m.E &&
+        (m.D == 32 || m.D == 64 || m.D == 128) && m.E == m.H * m.D)
+        s.affine = true;
+    return s;
+}
+// option "attn_split": 0 off, 1 = from ATTN_SPLIT_MIN positions on, n > 1 = from n positions on
+// fused: the short-context attention is k_qkv_attn (stays ahead of the split path for longer than k_attn_decode does)
+static inline int64_t attn_split_min(bool fused = true) { return g.opt_attn_split > 1 ? g.opt_attn_split : fused ? ATTN_SPLIT_MIN_FUSED : ATTN_SPLIT_MIN; }
+static inline int64_t attn_split_min_of(const LlamaMatch &m) { return attn_split_min(fused_qkv_shape(m).ok); }
+// workgroups per head of the split attention (DecodePlan::att_S) ...
+static inline int plan_att_S(int64_t H) { return (int)std::max<int64_t>(1, std::min<int64_t>(16, g.num_cus / std::max<int64_t>(1, H))); }
+// ... and whether a single-token evaluation of H heads goes over to it from attn_split_min positions on
+static inline bool attn_split_from_min(int64_t H) { return g.opt_attn_split && g.opt_big && plan_att_S(H) >= 2; }
+// the split attention as one launch: every workgroup must be resident (they wait for each other); scores + probabilities of a
+// range stay in LDS
+static inline size_t attn_split_chunk_max(int64_t C, int S) { return ((((size_t)C + S - 1) / S) + 63) & ~(size_t)63; }  // positions of a workgroup
+static bool attn_one_ok(const LlamaMatch &m, int att_S) {
+    const size_t chunk_max = attn_split_chunk_max(m.C, att_S);
+    // (every workgroup of this launch waits for peers: it must have the GPU to itself — one slot per device)
+    return g.opt_attn_one && device_sharers() == 1 && m.N == 1 && att_S <= 16 && (int64_t)m.H * att_S <= g.num_cus && chunk_max * 6 <= 60 * 1024 && m.D % 32 == 0 && m.D <= 128;
+}
+// The attention variant of a single-token evaluation whose token sits at position T - 1 (see the enum above).  Option
+// fuse_heads (default 1): contexts beyond k_qkv_attn's 512-position register window get 2 / 4 attention workgroups per head inside
+// the wq|wk|wv launch instead of the separate split attention, where the chip has room for them.
+static int attn_variant(const LlamaMatch &m, const DecodePlan *p, int64_t T) {
+    if (m.N != 1) return AV_SHORT;
+    const bool split_ok = (!m.kquant || attn_one_ok(m, p->att_S)) && attn_split_from_min(m.H);
+    if (g.opt_fuse_heads && g.opt_attn_split == 1 && split_ok && T > FUSE_HEADS_MIN && fused_qkv_shape(m).ok) {
+        const int S = (int)((T + 511) / 512);  // workgroups per head: 512 positions each
+        if (S <= 4 && p->att_S >= S && fused_qkv_shape(m, S).ok) return S;  // = AV_FUSED2 / 3 / 4
+    }
+    return split_ok && T >= attn_split_min_of(m) ? AV_SPLIT : AV_SHORT;
+}
+// positions k_attn_decode's LDS arrays must hold for an evaluation of N tokens at context C: longer rows of a single token
+// run on the split attention
+static inline int64_t attn_decode_rows(int64_t C, int N, int64_t H) {
+    return N == 1 && attn_split_from_min(H) ? std::min<int64_t>(C, (attn_split_min() + 7) & ~(int64_t)7) : C;
+}
+// wq|wk|wv + attention of a K-quant token in one launch (k_qkv_attn_k): legal like fused_qkv_shape's S = 1 form
+static bool kfused_ok(const DecodePlan *p, int av) {
+    const LlamaMatch &m = p->m;
+    if (!g.opt_fuse_attn || av != AV_SHORT || m.N != 1 || m.D > 128 || m.D % 32 != 0 || !p->gran) return false;
+    const int H = (int)m.H;
+    if (H * 4 > g.num_cus) return false;                                                       // the mat-vec keeps >= 3/4 of the chip
+    if (device_sharers() > 1 && (int64_t)device_sharers() * H > g.num_cus / 4) return false;  // see fused_qkv_shape
+    const int64_t units = (m.E + 2 * m.Egqa) / 2, waves = (int64_t)(g.num_cus - H) * 16;
+    return (units + waves - 1) / waves <= 31;  // two parked values per unit lane
+}
+// a K matrix of M rows of nsb super-blocks that k_mmvq_kbig takes; norm_width: the row its norm staging would hold (0: none)
+static bool kbig_weight_ok(int kt, int64_t nsb, int64_t M, int64_t norm_width) {
+    return kt >= 0 && kt <= KT_Q5_K && nsb <= 64 && norm_width <= 8192 &&  // all five K types; staging limits of k_mmvq_kbig (KBIG_SBW, KBIG_SQ)
+           (M + (int64_t)g.num_cus * 16 - 1) / ((int64_t)g.num_cus * 16) <= 21;  // (three matrices per launch: 63 rows per wave)
+}
+static bool kbig_ok(const DecodePlan *p) {  // K matrices whose rows of a wave fit its 64 epilogue lanes and whose activation row fits the staging
+    if (!g.opt_kbig || p->m.N != 1) return false;
+    auto ok = [&](const KWeight &w) { return kbig_weight_ok(w.kt, w.nsb, w.M, p->m.E); };
+    for (auto &l : p->klw)
+        for (const KWeight *w : {&l.wq, &l.wk, &l.wv, &l.wo, &l.w1, &l.w2, &l.w3})
+            if (!ok(*w)) return false;
+    return !p->m.output || ok(p->k_output);
+}
+// ---- the same launches on the integer matrix cores (kernels/mmq_cols.h) ----
+struct ColsShape {
+    int G, kc;
+    size_t lds;
+};
+// grid and LDS of k_mmq_cols for `ngroups` 16-row groups (pairs for the gate) of nb blocks; G = 0: does not fit
+static ColsShape cols_shape(int ngroups, int nsub, int nb) {
+    ColsShape s{0, 0, 0};
+    if (nb % 4 != 0 || nb < 32 || ngroups < 1) return s;
+    const int max_groups = COLS_MAX_UNITS / nsub;  // per workgroup
+    s.G = std::max(std::min(g.num_cus, ngroups), (ngroups + max_groups - 1) / max_groups);
+    const int per = (ngroups + s.G - 1) / s.G;
+    s.kc = 1;
+    s.lds = (size_t)320 * nb + (size_t)per * nsub * COLS_W * 512;
+    if (s.lds > 150 * 1024) s.G = 0, s.kc = 0;
+    return s;
+}
+// whether a launch of the multi-token plan can run on k_mmq_cols (else k_mmvq_big8)
+static bool cols_ok(int M_total, int nsub, int64_t nb, std::initializer_list<int64_t> Ms) {
+    if (!g.opt_mmq_cols) return false;
+    for (int64_t M : Ms)
+        if (M % 16 != 0) return false;
+    return cols_shape(M_total / 16 / nsub, nsub, (int)nb).kc > 0;
+}
+// the mat-vecs of a chunk (wq|wk|wv, wo, w1|w3, w2, lm_head) that run on k_mmq_cols; a chunk of more than 8 tokens needs all of them
+struct MultiCols {
+    bool qkv, wo, gate, w2, out;
+};
+static MultiCols multi_cols(const LlamaMatch &m) {
+    const int64_t nbE = m.E / 32, nbF = m.F / 32;
+    if (m.N < 2) return MultiCols{false, false, false, false, false};
+    return MultiCols{cols_ok((int)(m.E + 2 * m.Egqa), 1, nbE, {m.E, m.Egqa}), cols_ok((int)m.E, 1, nbE, {m.E}),
+                     cols_ok((int)(2 * m.F), 2, nbE, {m.F}), cols_ok((int)m.E, 1, nbF, {m.E}),
+                     m.output != nullptr && cols_ok((int)m.V, 1, nbE, {m.V})};
+}
+// ---- the prompt plan's fused attention (kernels/prompt_attn.h): LDS bytes of a score row of T keys ----
+static inline int prompt_attn_row_bytes(int64_t T) { return (int)(((T + 63) & ~(int64_t)63) * 4 + 16); }
+// queries per workgroup the fused kernel takes rows of T keys with: 32, 16 (long rows), or 0 = the scores do not fit LDS
+static inline int prompt_attn_queries(int64_t D, int64_t T) {
+    if (!(D == 128 || D == 64 || D == 32)) return 0;
+    if ((size_t)PATTN_Q * prompt_attn_row_bytes(T) <= 150 * 1024) return PATTN_Q;  // (row_bytes >= 272 >= the staged Q row)
+    if ((size_t)16 * prompt_attn_row_bytes(T) <= 150 * 1024) return 16;
+    return 0;
+}
+static inline bool prompt_attn_fits(int64_t D, int64_t T) { return prompt_attn_queries(D, T) != 0; }

@@ -1,4 +1,4 @@
-"""Host reference of the prompt batch attention (llama_plan.inc prompt_attention: kernels/prompt_attn.h k_p_attn, and the
+"""Host reference of the prompt batch attention (plan_prompt.inc prompt_attention: kernels/prompt_attn.h k_p_attn, and the
 three-launch path k_gemm_f16 / k_p_soft_max / k_gemm_f16_b16) for the tests, NumPy with f64 where it matters, plus the three
 input families the tests run it on.  Not a test module (pytest collects test_*.py only).
 
@@ -20,7 +20,7 @@ LDS_LIMIT = 150 * 1024
 F16_MAX = 65504.0
 
 
-# ---- the launcher's choice of queries per workgroup (llama_plan.inc prompt_attn_row_bytes / prompt_attn_queries), restated
+# ---- the launcher's choice of queries per workgroup (plan_shapes.inc prompt_attn_row_bytes / prompt_attn_queries), restated
 def row_bytes(T):
     return ((T + 63) & ~63) * 4 + 16
 

@@ -3,7 +3,7 @@ returns, abort with a message — the Rust caller ignores ggml_graph_compute's r
 
 k_qkv_attn's attention workgroups wait for rows that other workgroups of the same launch publish; if those never run (the
 launch is not fully resident: another process on the GPU, a CU mask) the wait gives up after GRAN_SPIN_MAX polls and raises the
-plan's error word, which travels back with every token's results (llama_plan.inc token_finish).  Option test_fused_timeout
+plan's error word, which travels back with every token's results (plan_run.inc token_finish).  Option test_fused_timeout
 points layer 0's attention workgroups at granules nobody writes:
   * default (fused_fallback = 1): the token is re-run on the two-launch pair — logits bit-identical to fuse_attn = 0 — the slot
     keeps the pair from then on, and the counter says so;

@@ -1,4 +1,4 @@
-"""The K plan (llama_plan.inc plan_launch_k, kernels/kquant_plan.h): single-token decode of a LLaMA whose matrices are
+"""The K plan (plan_decode.inc plan_launch_k, kernels/kquant_plan.h): single-token decode of a LLaMA whose matrices are
 K-quants (block structs crates/ggml/sys/src/lib.rs:2977-3303, file types crates/llm-base/src/loader.rs:80-93) as 10-13 launches
 per layer from a captured hipGraph instead of the node-by-node executor.
 
@@ -356,7 +356,7 @@ def test_mixed_k_quant_file_loads_and_decodes_on_the_k_plan(G, O, tmp_path):
     assert a[0] == b[0] and np.array_equal(a[1], b[1])
 
 
-# ---- prompt batches of a K-quant model on the prompt plan (llama_plan.inc plan_launch_prompt with k_prompt_weights) -----------------
+# ---- prompt batches of a K-quant model on the prompt plan (plan_prompt.inc plan_launch_prompt with k_prompt_weights) -----------------
 KP_GQA = dict(n_vocab=512, n_embd=512, n_head=8, n_head_kv=2, n_layer=2, n_rot=64, n_ff=768, n_mult=32)
 KP_SPLITK = dict(n_vocab=256, n_embd=1024, n_head=8, n_head_kv=4, n_layer=2, n_rot=128, n_ff=2048, n_mult=32)  # every GEMM splits K in two
 

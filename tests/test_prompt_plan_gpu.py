@@ -1,4 +1,4 @@
-"""The fused prompt plan (llama_plan.inc plan_launch_prompt, kernels/prompt.h): a prompt batch of >= 32 tokens
+"""The fused prompt plan (plan_prompt.inc plan_launch_prompt, kernels/prompt.h): a prompt batch of >= 32 tokens
 (crates/llm-base/src/inference_session.rs:315-316 feeds n_batch tokens per Model::evaluate; graph of
 crates/models/llama/src/lib.rs:166-362) as 13 launches per layer instead of 24.
 
