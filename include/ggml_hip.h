@@ -510,14 +510,12 @@ enum ggml_hip_kclass {
 GGML_API void ggml_hip_timing_begin(void);
 GGML_API void ggml_hip_timing_end(void);
 GGML_API void ggml_hip_timing_query(int kclass, double *ms, int64_t *launches, double *algo_bytes);
-/* Execution mode knobs (the full list with meanings: INTEGRATION.md section 4 "Runtime knobs"): "fuse" (peephole fusion in the
- * generic executor), "plan" / "plan_k" / "plan_multi" / "plan_prompt" (fused LLaMA plans), "graph" (hipGraph replay of a plan),
- * "big", "kbig", "fuse_attn", "fuse_wo", "fuse_heads", "warm_mb", "affine", "attn_split" (decode attention split over positions:
- * from n positions on), "attn_one", "fused_fallback", "fused_rearm_tokens", "speculate_next", "act_quant", "mmq_min", "mmq_i8",
- * "mmq_w16", "w16_headroom_gb", "w16_release", "serial_stage_slots", "probe" (measurement only: the decode mat-vec returns early),
- * "timeline" (1 = 4 sampled workgroups per launch, n > 1 = n of them); an unknown key aborts with a message.
- * Also env GGML_HIP_FUSE / GGML_HIP_PLAN / GGML_HIP_GRAPH / GGML_HIP_BIG / GGML_HIP_WARM_MB / GGML_HIP_AFFINE / GGML_HIP_MMQ_*. */
+/* Runtime options, process-wide.  The keys, their meanings and their environment variables: INTEGRATION.md section 4 "Runtime
+ * knobs"; the table they come from: g_options in llm_amd/csrc/backend_state.inc.  An unknown key aborts with a message.
+ * get_option answers what the calling thread's slot holds (before that slot exists: the value that was set, else the default);
+ * -1 for a key that is an action. */
 GGML_API void ggml_hip_set_option(const char *key, int value);
+GGML_API int ggml_hip_get_option(const char *key);
 /* Replays the launches of one kernel class of the most recent fused decode plan `replays` times from a
  * dedicated hipGraph between two HIP events on the backend stream (bench.py roofline leg). 0 on success.
  * kclass may also be GGML_HIP_KKIND_BASE + {0 wq|wk|wv, 1 wo, 2 w1|w3, 3 w2, 4 lm_head}: that mat-vec alone; or

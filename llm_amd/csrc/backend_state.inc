@@ -69,9 +69,7 @@ struct Backend {
     hipStream_t own_stream = nullptr;  // != nullptr while `stream` is another slot's (ggml_hip_share_stream): this slot's own, to come back to
     std::recursive_mutex mu;       // serialises the entry points that act on this slot (SlotLock)
     hipEvent_t xfer_ev = nullptr;  // ggml_hip_copy_between_devices: "what this slot's stream has enqueued so far"
-    int opt_fuse_heads = 1;  // contexts beyond k_qkv_attn's register window: 2 / 4 attention workgroups per head inside the wq|wk|wv launch
-    int opt_attn_one = 1;    // ... its three phases as ONE launch (k_attn_split_one) where every workgroup is resident
-    int opt_attn_split = 1;  // long contexts: attention split over positions too (kernels/decode_attn_split.h)
+    int opt_fuse_heads = 1, opt_attn_one = 1, opt_attn_split = 1;  // options: what each means is said once, at its row of g_options below
     std::map<uintptr_t, Arena> arenas;          // by base
     std::map<uintptr_t, DevTensor *> tensors;   // explicit records (transform_tensor / assign_buffers_no_scratch)
     std::map<uintptr_t, DevTensor *> auto_tensors;  // persistent leaves uploaded on first use (never offloaded by
@@ -85,48 +83,22 @@ struct Backend {
     std::vector<WsChunk> ws_chunks;
     size_t ws_off = 0;  // offset in the last chunk
     Timing timing;
-    // options
-    int opt_fuse = 1;
-    int opt_plan_multi = 1; // fused plan for prompt chunks of 2..8 tokens (kernels/decode_big8.h)
-    int opt_mmq_cols = 1;    // prompt chunks of 2..8 tokens: mat-muls on the integer matrix cores (kernels/mmq_cols.h) instead of k_mmvq_big8
-    int opt_attn_fused = 1;  // prompt plan: K.Q, softmax and V.P as one launch with the scores in LDS (kernels/prompt_attn.h)
-    int opt_plan_prompt = 1; // fused plan for prompt batches of >= mmq_min tokens (kernels/prompt.h)
-    int opt_mmq_w16 = 1;     // prompt GEMM on resident f16 copies of the quantized weights when HBM has room (kernels/mmq_w16.h)
-    std::atomic<size_t> w16_bytes{0};  // HBM held by those copies (a sibling slot of the device adds to it when IT builds a copy of this slot's record)
+    int opt_fuse = 1, opt_plan = 1, opt_plan_k = 1, opt_plan_multi = 1, opt_plan_prompt = 1, opt_graph = 1, opt_big = 1, opt_kbig = 1;
+    int opt_chain_k = 0, opt_prepare = 1;
+    int opt_fuse_attn = 1, opt_fuse_wo = 1, opt_warm_mb = 24, opt_affine = 1;
+    int opt_act_quant = 0, opt_mmq_i8 = 0;
+    int opt_mmq_min = 32, opt_k_prompt_min = 12, opt_mmq_fuse = 3, opt_mmq_cols = 1, opt_mmq_t256 = 1, opt_attn_fused = 1;
+    int opt_mmq_w16 = 1, opt_w16_headroom_gb = 16;
+    int opt_probe = 0;
+    std::atomic<size_t> w16_bytes{0};  // HBM held by the resident f16 weight copies (a sibling slot of the device adds to it when IT builds a copy of this slot's record)
     uint64_t w16_gen = 1;    // bumped when copies are released: cached prompt plans re-resolve their pointers
-    int opt_w16_headroom_gb = 16;  // HBM that must stay free after a copy is made (KV caches, workspaces, other models)
-    int opt_mmq_t256 = 1;    // prompt GEMM on 256 x 256 tiles (kernels/mmq_w16_256.h) where the launch fills the chip with them; 2 = wherever legal (tests)
-    int opt_chain_k = 0;     // greedy chain: tokens per hipGraph launch (0 / 1 = one token per launch)
-    int opt_mmq_fuse = 3;    // prompt plan: wq|wk|wv (bit 0) and w1|w3 (bit 1) as one GEMM launch each
-    int opt_big = 1;        // decode mat-vec as one wave of 1024-thread workgroups (kernels/decode_big.h)
-    int opt_fuse_attn = 1;  // decode: wq|wk|wv and the attention as ONE launch (kernels/decode_fused.h) where the mat-vec deals as
-                            // evenly over the remaining workgroups; 2 = wherever legal (tests); 0 = the two-launch pair
-    int opt_fuse_wo = 1;    // ... and wo + residual as the second phase of that launch's mat-vec workgroups (the WO form), where this slot
-                            // has the GPU to itself
-    int opt_warm_mb = 24;   // WO form: MB of the first rows of w1|w3 that the mat-vec workgroups pull into L2 while the attention runs
-    int opt_prepare = 1;    // ggml_hip_graph_prepare remembers its match (0: it answers 0 and every begin() matches its graph itself)
-    int opt_affine = 1;     // XCD-affine dealing of wq|wk|wv's rows in the fused launch: head h's rows come from the XCD its attention workgroup runs on, through that L2 (BigArgs::aff_hpl)
-                            // (kernels/decode_fused.h NextWarm); 0 = off.  LLaMA-7B Q4_0, all mat-vec launches of a token, one box
-                            // (gpurun_out/r6/run34): 0 MB 1.183 ms, 16 MB 1.145, 24 MB 1.123-1.125, 28 MB 1.124, 32 MB 1.126, 40 MB 1.147,
-                            // 50 MB 1.200 (8 x 4 MB of L2: ~3 MB per XCD is what stays)
-    int opt_act_quant = 0;  // activation re-quantizer: 0 = ggml's AVX2 branch (id = 127/amax, round half to even: what the
-                            // reference's build runs, crates/ggml/sys/build.rs:46-62), 1 = its scalar branch (kernels/common.h)
-    int opt_probe = 0;      // measurement only: k_mmvq_big returns early (BigArgs::probe), tests/tools/launch_probe.py
     int num_cus = 256;
-    long long *timeline = nullptr;  // device buffer of in-kernel timestamps (option "timeline")
+    long long *timeline = nullptr;  // device buffer of in-kernel timestamps (the timeline option)
     size_t timeline_bytes = 0;
     int timeline_wgs = 4;  // sampled workgroups per launch
-    int opt_mmq_i8 = 0;     // 1 = prompt GEMM on the integer matrix cores (kernels/mmq_i8.h): ggml's exact block dots (error
-                            // 2e-5 * scale instead of 1.1e-3), but the per-block scaling of every product is VALU-bound:
-                            // 309 vs 464 TFLOP/s-equivalent on 7B Q4_0, so the f16 kernels stay the default
-    int opt_mmq_min = 32;   // token count from which mul_mat runs on the MFMA GEMM (0 = never)
-    int opt_plan = 1;       // recognise the LLaMA decode graph and run the fused plan
-    int opt_plan_k = 1;     // ... and the K plan for a model whose matrices are K-quants (plan_decode.inc plan_launch_k)
-    int opt_k_prompt_min = 12;  // tokens from which a K-quant model's batch takes the prompt plan (f16 copies) instead of the K plan's multi-token form
-    int opt_kbig = 1;       // ... its decode mat-vecs as one wave of 1024-thread workgroups that stage the activation themselves (kernels/kquant_big.h)
-    int opt_graph = 1;      // replay the plan from a captured hipGraph
+    // counters: what each counts is said once, at its row of g_counters below
     uint64_t stat_plan_tokens = 0, stat_generic_graphs = 0, stat_split_tokens = 0, stat_prompt_plan_tokens = 0, stat_fused_tokens = 0, stat_kplan_tokens = 0, stat_fused_heads_tokens = 0, stat_fused_wo_tokens = 0, stat_fused_affine_tokens = 0, stat_prepared_tokens = 0;
-    uint64_t stat_alibi_fused = 0;  // scale -> alibi -> diag_mask_inf -> soft_max chains run as one launch (k_alibi_soft_max)
+    uint64_t stat_alibi_fused = 0;
     // prompt-GEMM launches by kernel (ggml_hip_get_stat("mmq_launches_<name>")): bench.py labels its MFMA roofline with the
     // kernels that actually ran
     enum { MMQ_K_PLAIN, MMQ_K_DMA_P8, MMQ_K_W16_P8, MMQ_K_W16_256, MMQ_K_I8, MMQ_K_COUNT };
@@ -135,7 +107,7 @@ struct Backend {
     ggml_cgraph *chain_graph = nullptr;    // ... and the cgraph that run executed
     bool pending_wait = false;  // a decode plan was launched by graph_compute_begin and not yet waited for
     bool pending_light = false;  // ... and it was a multi-token plan run: no in-launch waits (no error word to look at); if it also queued no read-back, the next begin() need not wait for it
-    // Speculative next token (option speculate_next / GGML_HIP_SPECULATE_NEXT, plan_run.inc): behind a single-token plan run
+    // Speculative next token (opt_speculate_next, plan_run.inc): behind a single-token plan run
     // the device samples the greedy token itself (k_argmax_next) and runs the NEXT token's plan at once; if the caller's next
     // ggml_graph_compute asks for exactly that (same plan, position + 1, the same token) its results are already on their
     // way — the caller's sampling, graph build and this library's enqueue overlap the device instead of idling it.  Anything
@@ -160,20 +132,15 @@ struct Backend {
     unsigned *ferr_pin = nullptr;    // the slot's error word: pinned HOST memory the kernels write straight into (zero-copy; written
                                      // only when a wait gives up, read by the host behind every token's result wait: no copy per token)
     void *ferr_plan = nullptr;       // the DecodePlan whose token is in flight
-    int opt_fused_fallback = 1;      // 1 = re-run such a token on the kernels that do not wait inside a launch and keep them; 0 = abort
-    // ... and take the fused forms back once the slot has decoded this many tokens cleanly on the two-launch forms (whoever held the
-    // compute units may be gone); every further give-up doubles the stretch (VERDICT r05 weak #10: one hiccup used to cost the slot
-    // 9 % for the rest of its life).  0 = never.
-    int opt_fused_rearm_tokens = 256;
+    int opt_fused_fallback = 1, opt_fused_rearm_tokens = 256;
     uint64_t fused_rearm_at = 0;     // stat_plan_tokens at which the saved options come back (0 = nothing to restore)
     uint64_t fused_rearm_stretch = 0;
     int fused_saved_fuse_attn = 0, fused_saved_attn_one = 0;
     uint64_t stat_fused_rearms = 0;
-    uint64_t stat_cols_warm_launches = 0;  // norm launches of the chunk plan that carried warming workgroups (counted when enqueued or captured)
-    int opt_test_fused_timeout = 0;  // test hook: layer 0's attention workgroups of k_qkv_attn poll granules nobody writes
-    uint64_t stat_fused_timeouts = 0;
-    uint64_t ns_match = 0, ns_launch = 0, ns_wait = 0, ns_compute = 0;  // host-side time split of plan tokens
-    uint64_t ns_mirror = 0, stat_mirror_bytes = 0;  // generic graphs: host ns in download_outputs (waits for the graph), bytes mirrored
+    uint64_t stat_cols_warm_launches = 0;
+    int opt_test_fused_timeout = 0;
+    uint64_t stat_fused_timeouts = 0;  // tokens the host saw the error word for (re-run or fatal)
+    uint64_t ns_match = 0, ns_launch = 0, ns_wait = 0, ns_compute = 0, ns_mirror = 0, stat_mirror_bytes = 0;
     size_t dead_shadow_bytes = 0;
     uint64_t arena_seen = 0;  // the last event of the process-wide arena log this slot has applied (sync_arenas)
     void *prep = nullptr;  // PrepMatch (plan_run.inc): the match of a graph handed over by ggml_hip_graph_prepare, waiting for its begin()
@@ -181,6 +148,141 @@ struct Backend {
     int xcd_labels = -1;  // 1: workgroups with equal blockIdx mod 8 of a one-workgroup-per-CU launch share an XCD, eight labels on eight XCDs (xcd_labels_ok); -1 = not looked yet
     void *hot_line = nullptr;  // 256 zero bytes on the device: what the dummy ring steps of the K plan's mat-vecs read (kernels/kquant_big.h KBigArgs::hot)
     int session_records = 0;  // zero-filled (mutable session state) records alive on this slot, see g_dev_slots
+};
+// The runtime options: one row per key of ggml_hip_set_option / ggml_hip_get_option.  The row is the only place that says what a
+// key means, which field holds it and how it is applied; the environment variable of a key is GGML_HIP_<KEY IN CAPITALS>.  A new
+// option is one row here (and one case in ggml_hip_internal_set_option_here if storing the value is not all it does).
+enum : unsigned {
+    OPT_ENV = 1,     // has an environment variable, stored into the field when a slot is initialised (the option log is replayed after it)
+    OPT_DROPS = 2,   // cached plans froze the value: a change drops them
+    OPT_DEVICE = 4,  // acts on an initialised device: only logged while no slot exists
+    OPT_ACTION = 8,  // does something now and holds no state: never logged, reads back as -1
+};
+enum OptEffect { FX_NONE, FX_ACT_QUANT, FX_TIMELINE, FX_MMQ_W16, FX_W16_RELEASE, FX_FUSE_ATTN, FX_SPECULATE_NEXT, FX_FUSED_REARM_TOKENS, FX_TEST_FUSED_TIMEOUT, FX_SERIAL_STAGE_SLOTS };
+struct OptRow {
+    const char *key;
+    int Backend::*field;  // nullptr: the state lives elsewhere (see the row's effect)
+    unsigned flags;
+    OptEffect fx = FX_NONE;  // what setting it does besides the store (ggml_hip_internal_set_option_here)
+    int lo = 0, hi = -1;     // lo <= hi: the value is clamped to [lo, hi]
+};
+static const OptRow g_options[] = {
+    // ---- plans
+    {"fuse", &Backend::opt_fuse, OPT_ENV},  // peephole fusion in the node-by-node executor
+    {"plan", &Backend::opt_plan, OPT_ENV},  // recognise the LLaMA decode graph and run the fused plan
+    // ... and the K plan for a model whose matrices are K-quants (plan_decode.inc plan_launch_k); 2 = one launch per matrix
+    {"plan_k", &Backend::opt_plan_k, OPT_ENV | OPT_DROPS},
+    {"plan_multi", &Backend::opt_plan_multi, OPT_ENV | OPT_DROPS},    // fused plan for prompt chunks of 2..8 tokens (kernels/decode_big8.h)
+    {"plan_prompt", &Backend::opt_plan_prompt, OPT_ENV | OPT_DROPS},  // fused plan for prompt batches of >= mmq_min tokens (kernels/prompt.h)
+    {"graph", &Backend::opt_graph, OPT_ENV},                          // replay the plan from a captured hipGraph
+    {"big", &Backend::opt_big, OPT_ENV | OPT_DROPS},                  // decode mat-vec as one wave of 1024-thread workgroups (kernels/decode_big.h)
+    // K plan: its decode mat-vecs as one wave of 1024-thread workgroups that stage the activation themselves (kernels/kquant_big.h)
+    {"kbig", &Backend::opt_kbig, OPT_ENV | OPT_DROPS},
+    {"chain_k", &Backend::opt_chain_k, OPT_ENV, FX_NONE, 0, 64},  // greedy chain: tokens per hipGraph launch (0 / 1 = one token per launch)
+    // ggml_hip_graph_prepare remembers its match (0: it answers 0 and every begin() matches its graph itself)
+    {"prepare", &Backend::opt_prepare, OPT_ENV},
+    // 1 = run the greedy next token speculatively behind every single-token plan run (Backend::spec, plan_run.inc)
+    {"speculate_next", &Backend::opt_speculate_next, OPT_ENV, FX_SPECULATE_NEXT},
+    // ---- the fused decode launch
+    // decode: wq|wk|wv and the attention as ONE launch (kernels/decode_fused.h) where the mat-vec deals as evenly over the remaining
+    // workgroups; 2 = wherever legal (tests); 0 = the two-launch pair.  An explicit choice outlives a pending re-arm.
+    {"fuse_attn", &Backend::opt_fuse_attn, OPT_ENV | OPT_DROPS, FX_FUSE_ATTN},
+    // ... and wo + residual as the second phase of that launch's mat-vec workgroups (the WO form), where this slot has the GPU to itself
+    {"fuse_wo", &Backend::opt_fuse_wo, OPT_ENV | OPT_DROPS},
+    // WO form: MB of the first rows of w1|w3 that the mat-vec workgroups pull into L2 while the attention runs (kernels/decode_fused.h
+    // NextWarm); 0 = off.  LLaMA-7B Q4_0, all mat-vec launches of a token, one box: 0 MB 1.183 ms, 16 MB 1.145, 24 MB 1.123-1.125,
+    // 28 MB 1.124, 32 MB 1.126, 40 MB 1.147, 50 MB 1.200 (8 x 4 MB of L2: ~3 MB per XCD is what stays)
+    {"warm_mb", &Backend::opt_warm_mb, OPT_ENV | OPT_DROPS},
+    // XCD-affine dealing of wq|wk|wv's rows in the fused launch: head h's rows come from the XCD its attention workgroup runs on,
+    // through that L2 (BigArgs::aff_hpl)
+    {"affine", &Backend::opt_affine, OPT_ENV | OPT_DROPS},
+    // contexts beyond k_qkv_attn's register window: 2 / 4 attention workgroups per head inside the wq|wk|wv launch
+    {"fuse_heads", &Backend::opt_fuse_heads, OPT_ENV | OPT_DROPS},
+    {"attn_split", &Backend::opt_attn_split, OPT_ENV | OPT_DROPS},  // long contexts: attention split over positions too (kernels/decode_attn_split.h)
+    {"attn_one", &Backend::opt_attn_one, OPT_ENV | OPT_DROPS},      // ... its three phases as ONE launch (k_attn_split_one) where every workgroup is resident
+    // a token whose in-launch hand-off gave up: 1 = re-run it on the kernels that do not wait inside a launch and keep them; 0 = abort
+    {"fused_fallback", &Backend::opt_fused_fallback, OPT_ENV},
+    // ... and take the fused forms back once the slot has decoded this many tokens cleanly on the two-launch forms (whoever held the
+    // compute units may be gone); every further give-up doubles the stretch (one hiccup used to cost the slot 9 % for the rest of
+    // its life).  0 = never.  Setting it starts the stretch over.
+    {"fused_rearm_tokens", &Backend::opt_fused_rearm_tokens, OPT_ENV, FX_FUSED_REARM_TOKENS},
+    // ---- arithmetic
+    // activation re-quantizer: 0 = ggml's AVX2 branch (id = 127/amax, round half to even: what the reference's build runs,
+    // crates/ggml/sys/build.rs:46-62), 1 = its scalar branch (kernels/common.h); any other value counts as 1, and the environment
+    // variable also takes the word "scalar".  Lives in the device's constant memory (apply_act_quant).
+    {"act_quant", &Backend::opt_act_quant, OPT_ENV | OPT_DEVICE, FX_ACT_QUANT},
+    // 1 = prompt GEMM on the integer matrix cores (kernels/mmq_i8.h): ggml's exact block dots (error 2e-5 * scale instead of 1.1e-3),
+    // but the per-block scaling of every product is VALU-bound: 309 vs 464 TFLOP/s-equivalent on 7B Q4_0, so the f16 kernels stay
+    // the default
+    {"mmq_i8", &Backend::opt_mmq_i8, OPT_ENV},
+    // ---- prompt GEMMs
+    {"mmq_min", &Backend::opt_mmq_min, OPT_ENV},  // token count from which mul_mat runs on the MFMA GEMM (0 = never)
+    // tokens from which a K-quant model's batch takes the prompt plan (f16 copies) instead of the K plan's multi-token form
+    {"k_prompt_min", &Backend::opt_k_prompt_min, OPT_ENV},
+    {"mmq_fuse", &Backend::opt_mmq_fuse, OPT_ENV},  // prompt plan: wq|wk|wv (bit 0) and w1|w3 (bit 1) as one GEMM launch each
+    // prompt chunks of 2..8 tokens: mat-muls on the integer matrix cores (kernels/mmq_cols.h) instead of k_mmvq_big8
+    {"mmq_cols", &Backend::opt_mmq_cols, OPT_ENV | OPT_DROPS},
+    // prompt GEMM on 256 x 256 tiles (kernels/mmq_w16_256.h) where the launch fills the chip with them; 2 = wherever legal (tests)
+    {"mmq_t256", &Backend::opt_mmq_t256, OPT_ENV | OPT_DROPS},
+    // prompt plan: K.Q, softmax and V.P as one launch with the scores in LDS (kernels/prompt_attn.h)
+    {"attn_fused", &Backend::opt_attn_fused, OPT_ENV},
+    // prompt GEMM on resident f16 copies of the quantized weights when HBM has room (kernels/mmq_w16.h); the copies are a cache of
+    // this option: 0 releases them
+    {"mmq_w16", &Backend::opt_mmq_w16, OPT_ENV | OPT_DROPS | OPT_DEVICE, FX_MMQ_W16},
+    // HBM that must stay free after a copy is made (KV caches, workspaces, other models)
+    {"w16_headroom_gb", &Backend::opt_w16_headroom_gb, OPT_ENV},
+    // drop the resident f16 weight copies now (they come back with the next prompt batch)
+    {"w16_release", nullptr, OPT_DEVICE | OPT_ACTION, FX_W16_RELEASE},
+    // ---- sessions / split
+    // how many of a device's session slots are stages of ONE split session (g_dev_serial_stages, device_sharers): per device, not per slot
+    {"serial_stage_slots", nullptr, 0, FX_SERIAL_STAGE_SLOTS},
+    // ---- measurement and tests
+    // in-kernel timestamps of the decode mat-vec launches (Backend::timeline): 1 = 4 sampled workgroups per launch, n > 1 = n of
+    // them, 0 = off; reads back as the number of sampled workgroups.  Every call drops the plans and clears the buffer.
+    {"timeline", nullptr, OPT_DEVICE, FX_TIMELINE},
+    {"probe", &Backend::opt_probe, OPT_DROPS},  // measurement only: k_mmvq_big returns early (BigArgs::probe), tests/tools/launch_probe.py
+    // test hook: layer 0's attention workgroups of k_qkv_attn poll granules nobody writes; turning it off forgets the hook's own
+    // give-ups (they do not count against the rest of the process)
+    {"test_fused_timeout", &Backend::opt_test_fused_timeout, OPT_DROPS, FX_TEST_FUSED_TIMEOUT},
+};
+// the row of `key`; an unknown key is fatal (`who`: the entry point that was asked)
+const OptRow &opt_row(const char *key, const char *who) {
+    for (const OptRow &o : g_options)
+        if (!strcmp(o.key, key)) return o;
+    die("%s: unknown key '%s'", who, key);
+}
+// the value a row stores for `v`
+inline int opt_value(const OptRow &o, int v) {
+    if (o.fx == FX_ACT_QUANT) return v ? 1 : 0;
+    return o.lo <= o.hi ? std::min(o.hi, std::max(o.lo, v)) : v;
+}
+// The plain counters of ggml_hip_get_stat (the computed ones are in that function): the row says what the counter counts.
+struct StatRow {
+    const char *key;
+    uint64_t Backend::*field;
+};
+static const StatRow g_counters[] = {
+    {"plan_tokens", &Backend::stat_plan_tokens},                  // tokens executed by the fused decode plan
+    {"fused_attn_tokens", &Backend::stat_fused_tokens},           // decode tokens whose attention rode in the wq|wk|wv launch
+    {"fused_heads_tokens", &Backend::stat_fused_heads_tokens},    // ... whose k_qkv_attn had 2 / 4 attention workgroups per head
+    {"fused_wo_tokens", &Backend::stat_fused_wo_tokens},          // ... whose wo + residual rode in that launch too (the WO form)
+    {"fused_affine_tokens", &Backend::stat_fused_affine_tokens},  // ... whose wq|wk|wv rows were dealt XCD-affine and handed over through the XCD's L2
+    {"attn_split_tokens", &Backend::stat_split_tokens},           // tokens whose attention ran split over positions
+    {"kplan_tokens", &Backend::stat_kplan_tokens},                // decode tokens of K-quant models that ran as the K plan
+    {"prepared_tokens", &Backend::stat_prepared_tokens},          // decode tokens whose graph had been matched ahead of time (ggml_hip_graph_prepare)
+    {"prompt_plan_tokens", &Backend::stat_prompt_plan_tokens},    // tokens executed by the fused prompt plan
+    {"cols_warm_launches", &Backend::stat_cols_warm_launches},    // chunk-plan norm launches that carried warming workgroups (ColsWarm), counted when enqueued or captured
+    {"fused_rearms", &Backend::stat_fused_rearms},                // times the fused forms came back after a clean stretch behind a give-up
+    {"spec_hits", &Backend::stat_spec_hits},                      // evaluations that found their results already running (option speculate_next)
+    {"spec_misses", &Backend::stat_spec_misses},                  // ... speculative runs nobody asked for
+    {"generic_graphs", &Backend::stat_generic_graphs},            // graphs run node by node
+    {"alibi_fused", &Backend::stat_alibi_fused},                  // scale -> alibi -> diag_mask_inf -> soft_max chains (BLOOM, MPT) run as one launch (k_alibi_soft_max)
+    {"ns_match", &Backend::ns_match},      // host-side time split of plan tokens: ns spent recognising decode graphs
+    {"ns_launch", &Backend::ns_launch},    // ... enqueueing (param upload, graph launch, read-back queue)
+    {"ns_wait", &Backend::ns_wait},        // ... waiting for the device + copying results out
+    {"ns_compute", &Backend::ns_compute},  // total inside ggml_graph_compute
+    {"ns_mirror", &Backend::ns_mirror},    // generic graphs: host ns in download_outputs (the wait for the graph included)
+    {"mirror_bytes", &Backend::stat_mirror_bytes},  // ... bytes of CPU-backend nodes copied back
 };
 // Locking.  Every device slot has its own recursive mutex (Backend::mu): an entry point locks the slot it acts on (SlotLock),
 // so sessions on DIFFERENT slots (GPUs) of one process run concurrently — enqueue, device wait and read-back included —
@@ -217,7 +319,7 @@ thread_local bool tl_pinned = false;
 int g_cur_slot() { return (int)(g_cur - g_backends); }
 // Stage slots of ONE layer-split session that sit on one GPU (virtual slots: how the split is exercised on a 1-GPU box) never run
 // at the same time — stage i + 1 waits for stage i's residual — so together they are ONE sharer of the device: the caller that
-// builds the split says how many of the device's session slots are such stages (ggml_hip_set_option("serial_stage_slots", n): the
+// builds the split says how many of the device's session slots are such stages (the serial_stage_slots option: the
 // host mirror while exactly one split session is alive, 0 otherwise).  Round 5 counted them one by one and the stages lost the WO
 // form of the fused launch (device_sharers() == 1): most of the 86 us per hop of profiles/r05_split2.json.
 std::atomic<int> g_dev_serial_stages[64];
@@ -358,6 +460,9 @@ inline int session_slots_env() {
     static const int n = getenv("GGML_HIP_SESSION_SLOTS") ? atoi(getenv("GGML_HIP_SESSION_SLOTS")) : 0;
     return n;
 }
+// The one statement of which GPU a slot drives: slot s drives physical device (base + s) mod n.  base: GGML_HIP_DEVICE (one
+// process per GPU launchers set it to the local rank when they did not restrict visibility); several slots on one device when
+// GGML_HIP_VIRTUAL_DEVICES asks for more slots than there are devices.  -1: no device.
 inline int slot_physical_device(int slot) {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return -1;
@@ -405,53 +510,24 @@ void ensure_init() {
     hipError_t e = hipGetDeviceCount(&n);
     if (e != hipSuccess || n <= 0)
         die("no HIP device available (hipGetDeviceCount -> %d, n=%d). This library has no CPU compute path.", (int)e, n);
-    // slot s drives physical device (base + s) mod n.  base: GGML_HIP_DEVICE (one process per GPU launchers set it to the
-    // local rank when they did not restrict visibility); several slots on one device when GGML_HIP_VIRTUAL_DEVICES asks
-    // for more slots than there are devices.
     g.slot = (int)(g_cur - g_backends);
-    int base = 0;
-    if (const char *lr = getenv("GGML_HIP_DEVICE")) base = atoi(lr);
-    g.device = (base + g.slot) % n;
+    g.device = slot_physical_device(g.slot);
     if (g.device >= 64) die("device index %d: the per-device tables of this library hold 64 GPUs", g.device);
     HIP_CHECK(hipSetDevice(g.device));
     tl_device = g.device;
     HIP_CHECK(hipStreamCreateWithFlags(&g.stream, hipStreamNonBlocking));
-    if (const char *v = getenv("GGML_HIP_ATTN_SPLIT")) g.opt_attn_split = atoi(v);
-    if (const char *v = getenv("GGML_HIP_ATTN_ONE")) g.opt_attn_one = atoi(v);
-    if (const char *v = getenv("GGML_HIP_FUSE_HEADS")) g.opt_fuse_heads = atoi(v);
-    if (const char *v = getenv("GGML_HIP_FUSE")) g.opt_fuse = atoi(v);
-    if (const char *v = getenv("GGML_HIP_PLAN")) g.opt_plan = atoi(v);
-    if (const char *v = getenv("GGML_HIP_PLAN_K")) g.opt_plan_k = atoi(v);
-    if (const char *v = getenv("GGML_HIP_K_PROMPT_MIN")) g.opt_k_prompt_min = atoi(v);
-    if (const char *v = getenv("GGML_HIP_KBIG")) g.opt_kbig = atoi(v);
-    if (const char *v = getenv("GGML_HIP_GRAPH")) g.opt_graph = atoi(v);
-    if (const char *v = getenv("GGML_HIP_MMQ_MIN")) g.opt_mmq_min = atoi(v);
-    if (const char *v = getenv("GGML_HIP_BIG")) g.opt_big = atoi(v);
-    if (const char *v = getenv("GGML_HIP_FUSE_ATTN")) g.opt_fuse_attn = atoi(v);
-    if (const char *v = getenv("GGML_HIP_FUSE_WO")) g.opt_fuse_wo = atoi(v);
-    if (const char *v = getenv("GGML_HIP_WARM_MB")) g.opt_warm_mb = atoi(v);
-    if (const char *v = getenv("GGML_HIP_AFFINE")) g.opt_affine = atoi(v);
-    if (const char *v = getenv("GGML_HIP_PREPARE")) g.opt_prepare = atoi(v);
-    if (const char *v = getenv("GGML_HIP_SPECULATE_NEXT")) g.opt_speculate_next = atoi(v);
-    if (const char *v = getenv("GGML_HIP_FUSED_FALLBACK")) g.opt_fused_fallback = atoi(v);
-    if (const char *v = getenv("GGML_HIP_FUSED_REARM_TOKENS")) g.opt_fused_rearm_tokens = atoi(v);
-    if (const char *v = getenv("GGML_HIP_PLAN_MULTI")) g.opt_plan_multi = atoi(v);
-    if (const char *v = getenv("GGML_HIP_PLAN_PROMPT")) g.opt_plan_prompt = atoi(v);
-    if (const char *v = getenv("GGML_HIP_ATTN_FUSED")) g.opt_attn_fused = atoi(v);
-    if (const char *v = getenv("GGML_HIP_MMQ_COLS")) g.opt_mmq_cols = atoi(v);
-    if (const char *v = getenv("GGML_HIP_MMQ_FUSE")) g.opt_mmq_fuse = atoi(v);
-    if (const char *v = getenv("GGML_HIP_CHAIN_K")) g.opt_chain_k = std::min(64, atoi(v));
-    if (const char *v = getenv("GGML_HIP_MMQ_W16")) g.opt_mmq_w16 = atoi(v);
-    if (const char *v = getenv("GGML_HIP_MMQ_T256")) g.opt_mmq_t256 = atoi(v);
-    if (const char *v = getenv("GGML_HIP_W16_HEADROOM_GB")) g.opt_w16_headroom_gb = atoi(v);
-    if (const char *v = getenv("GGML_HIP_MMQ_I8")) g.opt_mmq_i8 = atoi(v);
+    for (const OptRow &o : g_options) {  // the environment: stored straight into the field; the option log below wins over it
+        if (!(o.flags & OPT_ENV)) continue;
+        std::string name = "GGML_HIP_";
+        for (const char *c = o.key; *c; c++) name += (char)toupper((unsigned char)*c);
+        if (const char *v = getenv(name.c_str())) g.*o.field = o.fx == FX_ACT_QUANT ? (!strcmp(v, "scalar") || atoi(v) == 1) : opt_value(o, atoi(v));
+    }
     {
         hipDeviceProp_t prop;
         HIP_CHECK(hipGetDeviceProperties(&prop, g.device));
         g.num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
         if (const char *v = getenv("GGML_HIP_BIG_WGS")) g.num_cus = std::max(1, atoi(v));
     }
-    if (const char *v = getenv("GGML_HIP_ACT_QUANT")) g.opt_act_quant = (!strcmp(v, "scalar") || atoi(v) == 1) ? 1 : 0;
     g.inited = true;
     apply_act_quant();  // several slots may share a device: the last writer wins, and all slots hold the same option
     std::map<std::string, int> log;

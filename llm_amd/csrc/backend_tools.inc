@@ -471,8 +471,9 @@ int ggml_hip_decode_greedy_chain(struct ggml_cgraph *last, int n, int32_t *out_t
 
 int64_t ggml_hip_get_stat(const char *key) {
     SlotLock lk;
+    for (const StatRow &c : g_counters)  // the plain counters (backend_state.inc); the rest is computed here
+        if (!strcmp(c.key, key)) return (int64_t)(g.*c.field);
     const std::string k(key);
-    if (k == "attn_split_tokens") return (int64_t)g.stat_split_tokens;  // tokens whose attention ran split over positions
     if (k == "w16_bytes") return (int64_t)g.w16_bytes;  // HBM held by resident f16 weight copies
     if (k.rfind("mmq_launches_", 0) == 0) {                 // prompt-GEMM launches by kernel since library load
         static const char *names[Backend::MMQ_K_COUNT] = {"plain", "dma_p8", "w16_p8", "w16_256", "i8"};
@@ -480,8 +481,6 @@ int64_t ggml_hip_get_stat(const char *key) {
             if (k.substr(13) == names[i]) return (int64_t)g.stat_mmq[i];
         return -1;
     }
-    if (k == "prompt_plan_tokens") return (int64_t)g.stat_prompt_plan_tokens;  // tokens executed by the fused prompt plan
-    if (k == "plan_tokens") return (int64_t)g.stat_plan_tokens;       // tokens executed by the fused decode plan
     if (k == "graph_replays") {
         int64_t n = 0;
         for (auto *p : g_plans) n += (int64_t)p->replays;
@@ -498,25 +497,7 @@ int64_t ggml_hip_get_stat(const char *key) {
         if (g.ferr_pin) n += *(volatile unsigned *)g.ferr_pin;
         return n;
     }
-    if (k == "fused_heads_tokens") return (int64_t)g.stat_fused_heads_tokens;  // decode tokens whose k_qkv_attn had 2 / 4 attention workgroups per head
-    if (k == "kplan_tokens") return (int64_t)g.stat_kplan_tokens;  // decode tokens of K-quant models that ran as the K plan
-    if (k == "spec_hits") return (int64_t)g.stat_spec_hits;      // evaluations that found their results already running (option speculate_next)
-    if (k == "spec_misses") return (int64_t)g.stat_spec_misses;  // ... speculative runs nobody asked for
-    if (k == "fused_wo_tokens") return (int64_t)g.stat_fused_wo_tokens;  // ... whose wo + residual rode in that launch too (the WO form)
-    if (k == "fused_affine_tokens") return (int64_t)g.stat_fused_affine_tokens;  // ... whose wq|wk|wv rows were dealt XCD-affine and handed over through the XCD's L2
-    if (k == "prepared_tokens") return (int64_t)g.stat_prepared_tokens;  // decode tokens whose graph had been matched ahead of time (ggml_hip_graph_prepare)
-    if (k == "cols_warm_launches") return (int64_t)g.stat_cols_warm_launches;  // chunk-plan norm launches with warming workgroups (ColsWarm), enqueued or captured
-    if (k == "fused_rearms") return (int64_t)g.stat_fused_rearms;  // times the fused forms came back after a clean stretch behind a give-up
-    if (k == "fused_attn_tokens") return (int64_t)g.stat_fused_tokens;  // decode tokens whose attention rode in the wq|wk|wv launch
     if (k == "peak_concurrent_calls") return (int64_t)g_calls_inside_peak.load();  // threads that were inside entry points (on different slots) at once
-    if (k == "generic_graphs") return (int64_t)g.stat_generic_graphs;  // graphs run node by node
-    if (k == "alibi_fused") return (int64_t)g.stat_alibi_fused;  // ALiBi attention chains (BLOOM, MPT) run as one launch
-    if (k == "ns_match") return (int64_t)g.ns_match;      // host ns spent recognising decode graphs
-    if (k == "ns_launch") return (int64_t)g.ns_launch;    // ... enqueueing (param upload, graph launch, read-back queue)
-    if (k == "ns_wait") return (int64_t)g.ns_wait;        // ... waiting for the device + copying results out
-    if (k == "ns_compute") return (int64_t)g.ns_compute;  // total inside ggml_graph_compute
-    if (k == "ns_mirror") return (int64_t)g.ns_mirror;    // generic graphs: download_outputs (the wait for the graph included)
-    if (k == "mirror_bytes") return (int64_t)g.stat_mirror_bytes;  // ... bytes of CPU-backend nodes copied back
     return -1;
 }
 size_t ggml_hip_read_timeline(int64_t *dst, size_t max_records) {

@@ -16,6 +16,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cctype>
 #include <chrono>
 #include <cmath>
 #include <cstdarg>
@@ -619,12 +620,8 @@ bool ggml_cuda_compute_forward(struct ggml_compute_params *p, struct ggml_tensor
 // exported: extensions
 // ===================================================================================================
 int ggml_hip_device_count(void) { return slot_count(); }
-int ggml_hip_slot_physical_device(int slot) {  // the GPU a slot drives (ensure_init's rule), without initialising it; -1: no such slot
-    int n = 0;
-    if (slot < 0 || slot >= slot_count() || hipGetDeviceCount(&n) != hipSuccess || n <= 0) return -1;
-    int base = 0;
-    if (const char *lr = getenv("GGML_HIP_DEVICE")) base = atoi(lr);
-    return (base + slot) % n;
+int ggml_hip_slot_physical_device(int slot) {  // the GPU a slot drives, without initialising it; -1: no such slot
+    return slot < 0 || slot >= slot_count() ? -1 : slot_physical_device(slot);
 }
 int ggml_hip_get_main_device(void) {  // the calling thread's slot
     if (!tl_pinned) g_cur = &g_backends[g_default_slot.load(std::memory_order_relaxed)];
@@ -780,163 +777,74 @@ void ggml_hip_timing_query(int kclass, double *ms, int64_t *launches, double *al
 void ggml_hip_set_option(const char *key, int value) {
     // Options are process-wide.  Slots that exist get the value now; a slot initialised later replays the log (ensure_init):
     // setting an option never creates a stream, a context or a buffer on a device this process has not used yet.
-    if (strcmp(key, "w16_release") != 0) {  // an action, not a state
+    const OptRow &o = opt_row(key, "ggml_hip_set_option");  // (an unknown key fails here, not at the first graph)
+    if (!(o.flags & OPT_ACTION)) {
         std::lock_guard<std::recursive_mutex> lk(g_mu);
-        g_opt_log[key] = value;
+        g_opt_log[key] = opt_value(o, value);
     }
-    bool known = false;
     for_each_slot([&] {
-        if (g.inited) {
-            ggml_hip_internal_set_option_here(key, value);
-            known = true;
-        }
+        if (g.inited) ggml_hip_internal_set_option_here(key, value);
     });
-    if (!known) {  // no slot yet: validate the key (an unknown one must fail here, not at the first graph)
-        Backend probe_state;
-        Backend *keep = g_cur;
-        g_cur = &probe_state;
-        const bool device_key = !strcmp(key, "timeline") || !strcmp(key, "act_quant") || !strcmp(key, "w16_release") || !strcmp(key, "mmq_w16");
-        if (!device_key) ggml_hip_internal_set_option_here(key, value);
-        g_cur = keep;
-    }
 }
 void ggml_hip_internal_set_option_here(const char *key, int value) {  // acts on the current slot
-    const std::string k(key);
+    const OptRow &o = opt_row(key, "ggml_hip_set_option");
+    if ((o.flags & OPT_DEVICE) && !g.inited) return;
     g.opt_gen++;
-    if (k == "fuse")
-        g.opt_fuse = value;
-    else if (k == "act_quant") {  // 0 = ggml's AVX2 activation quantizer (what the reference's build runs), 1 = its scalar branch
-        g.opt_act_quant = value ? 1 : 0;
-        apply_act_quant();
+    value = opt_value(o, value);
+    if (o.fx == FX_SPECULATE_NEXT) spec_cancel();
+    if (o.field) {
+        if ((o.flags & OPT_DROPS) && g.*o.field != value) drop_all_plans();
+        g.*o.field = value;
     }
-    else if (k == "plan")
-        g.opt_plan = value;
-    else if (k == "graph")
-        g.opt_graph = value;
-    else if (k == "timeline") {
-        drop_all_plans();
-        if (g.timeline && value && (value == 1 ? 4 : value) != g.timeline_wgs) {
-            HIP_CHECK(hipStreamSynchronize(g.stream));
-            (void)hipFree(g.timeline);
-            g.timeline = nullptr;
-        }
-        if (value && !g.timeline) {
-            g.timeline_wgs = value == 1 ? 4 : value;
-            g.timeline_bytes = (size_t)1024 * g.timeline_wgs * 8 * 8;
-            HIP_CHECK(hipMalloc((void **)&g.timeline, g.timeline_bytes));
-        }
-        if (!value && g.timeline) {
-            HIP_CHECK(hipStreamSynchronize(g.stream));
-            (void)hipFree(g.timeline);
-            g.timeline = nullptr;
-        }
-        if (g.timeline) HIP_CHECK(hipMemsetAsync(g.timeline, 0, g.timeline_bytes, g.stream));
+    switch (o.fx) {  // what a key does besides the store
+        case FX_ACT_QUANT: apply_act_quant(); break;
+        case FX_TIMELINE:
+            drop_all_plans();
+            if (g.timeline && value && (value == 1 ? 4 : value) != g.timeline_wgs) {
+                HIP_CHECK(hipStreamSynchronize(g.stream));
+                (void)hipFree(g.timeline);
+                g.timeline = nullptr;
+            }
+            if (value && !g.timeline) {
+                g.timeline_wgs = value == 1 ? 4 : value;
+                g.timeline_bytes = (size_t)1024 * g.timeline_wgs * 8 * 8;
+                HIP_CHECK(hipMalloc((void **)&g.timeline, g.timeline_bytes));
+            }
+            if (!value && g.timeline) {
+                HIP_CHECK(hipStreamSynchronize(g.stream));
+                (void)hipFree(g.timeline);
+                g.timeline = nullptr;
+            }
+            if (g.timeline) HIP_CHECK(hipMemsetAsync(g.timeline, 0, g.timeline_bytes, g.stream));
+            break;
+        case FX_MMQ_W16:
+            if (!value) release_w16_copies();
+            break;
+        case FX_W16_RELEASE: release_w16_copies(); break;
+        case FX_FUSE_ATTN: g.fused_rearm_at = 0; break;
+        case FX_FUSED_REARM_TOKENS: g.fused_rearm_stretch = 0; break;
+        case FX_TEST_FUSED_TIMEOUT:
+            if (!value) g.stat_fused_timeouts = 0;
+            break;
+        case FX_SERIAL_STAGE_SLOTS:
+            if (g_dev_serial_stages[g.device & 63].exchange(value) != value) g_dev_gen[g.device & 63].fetch_add(1);  // captured graphs froze a choice of kernels
+            break;
+        case FX_SPECULATE_NEXT:  // (cancelled before the store, above)
+        case FX_NONE: break;
     }
-    else if (k == "fuse_heads") {
-        if (g.opt_fuse_heads != value) drop_all_plans();
-        g.opt_fuse_heads = value;
+}
+int ggml_hip_get_option(const char *key) {
+    const OptRow &o = opt_row(key, "ggml_hip_get_option");
+    SlotLock lk;
+    if (o.flags & OPT_ACTION) return -1;
+    if (!g.inited) {  // what the slot will hold once it exists: the logged value, else the default
+        std::lock_guard<std::recursive_mutex> lk2(g_mu);
+        auto it = g_opt_log.find(key);
+        if (it != g_opt_log.end()) return it->second;
     }
-    else if (k == "attn_one") {
-        if (g.opt_attn_one != value) drop_all_plans();
-        g.opt_attn_one = value;
-    }
-    else if (k == "attn_split") {
-        if (g.opt_attn_split != value) drop_all_plans();
-        g.opt_attn_split = value;
-    }
-    else if (k == "mmq_fuse")
-        g.opt_mmq_fuse = value;
-    else if (k == "chain_k")
-        g.opt_chain_k = std::min(64, std::max(0, value));
-    else if (k == "mmq_t256") {
-        if (g.opt_mmq_t256 != value) drop_all_plans();
-        g.opt_mmq_t256 = value;
-    }
-    else if (k == "mmq_w16") {
-        if (g.opt_mmq_w16 != value) drop_all_plans();
-        g.opt_mmq_w16 = value;
-        if (!value) release_w16_copies();  // the copies are a cache of this option
-    }
-    else if (k == "w16_headroom_gb")
-        g.opt_w16_headroom_gb = value;
-    else if (k == "w16_release")  // drop the resident f16 weight copies now (they come back with the next prompt batch)
-        release_w16_copies();
-    else if (k == "mmq_cols") {
-        if (g.opt_mmq_cols != value) drop_all_plans();
-        g.opt_mmq_cols = value;
-    }
-    else if (k == "attn_fused")
-        g.opt_attn_fused = value;
-    else if (k == "plan_prompt") {
-        if (g.opt_plan_prompt != value) drop_all_plans();
-        g.opt_plan_prompt = value;
-    }
-    else if (k == "kbig") {
-        if (g.opt_kbig != value) drop_all_plans();
-        g.opt_kbig = value;
-    }
-    else if (k == "plan_k") {
-        if (g.opt_plan_k != value) drop_all_plans();
-        g.opt_plan_k = value;
-    }
-    else if (k == "plan_multi") {
-        if (g.opt_plan_multi != value) drop_all_plans();
-        g.opt_plan_multi = value;
-    }
-    else if (k == "fuse_attn") {
-        if (g.opt_fuse_attn != value) drop_all_plans();
-        g.opt_fuse_attn = value;
-        g.fused_rearm_at = 0;  // an explicit choice outlives a pending re-arm
-    }
-    else if (k == "speculate_next") {  // 1 = run the greedy next token speculatively behind every single-token plan run (plan_run.inc)
-        spec_cancel();
-        g.opt_speculate_next = value;
-    }
-    else if (k == "fuse_wo") {
-        if (g.opt_fuse_wo != value) drop_all_plans();
-        g.opt_fuse_wo = value;
-    }
-    else if (k == "prepare")
-        g.opt_prepare = value;
-    else if (k == "affine") {
-        if (g.opt_affine != value) drop_all_plans();
-        g.opt_affine = value;
-    }
-    else if (k == "warm_mb") {
-        if (g.opt_warm_mb != value) drop_all_plans();
-        g.opt_warm_mb = value;
-    }
-    else if (k == "big") {
-        if (g.opt_big != value) drop_all_plans();
-        g.opt_big = value;
-    }
-    else if (k == "serial_stage_slots") {  // how many of this device's session slots are stages of ONE split session (see device_sharers)
-        if (g_dev_serial_stages[g.device & 63].exchange(value) != value) g_dev_gen[g.device & 63].fetch_add(1);  // captured graphs froze a choice of kernels
-    }
-    else if (k == "fused_rearm_tokens") {  // clean tokens on the two-launch forms after which the fused forms are taken back (0 = never)
-        g.opt_fused_rearm_tokens = value;
-        g.fused_rearm_stretch = 0;
-    }
-    else if (k == "fused_fallback")  // 1 = a token whose in-launch hand-off gave up is re-run on the two-launch forms; 0 = abort
-        g.opt_fused_fallback = value;
-    else if (k == "test_fused_timeout") {  // test hook: the attention workgroups of layer 0 of k_qkv_attn never get their rows
-        if (g.opt_test_fused_timeout != value) drop_all_plans();
-        g.opt_test_fused_timeout = value;
-        if (!value) g.stat_fused_timeouts = 0;  // the hook's own give-ups do not count against the rest of the process
-
-    }
-    else if (k == "probe") {
-        if (g.opt_probe != value) drop_all_plans();
-        g.opt_probe = value;
-    }
-    else if (!strcmp(key, "mmq_min"))
-        g.opt_mmq_min = value;
-    else if (!strcmp(key, "k_prompt_min"))  // K-quant models: batch size from which the prompt plan (f16 copies) replaces the K plan's chunks
-        g.opt_k_prompt_min = value;
-    else if (!strcmp(key, "mmq_i8"))
-        g.opt_mmq_i8 = value;
-    else
-        die("ggml_hip_set_option: unknown key '%s'", key);
+    if (o.fx == FX_TIMELINE) return g.timeline ? g.timeline_wgs : 0;
+    if (o.fx == FX_SERIAL_STAGE_SLOTS) return g_dev_serial_stages[g.device & 63].load();
+    return g.*o.field;
 }
 // Roofline leg of bench.py: replays the kernels of ONE class of the most recent decode plan (e.g. the 129
 // mat-vec launches of a LLaMA-7B token) `replays` times from a hipGraph that contains nothing else, bracketed

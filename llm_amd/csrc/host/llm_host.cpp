@@ -1129,7 +1129,7 @@ llm_session *llm_start_session(llm_model *m, const llm_session_config *cfg) {
         }
         ggml_hip_bind_thread_device(home);
         // the stages of ONE split session run one after the other: on a GPU that hosts several of them (virtual slots) they are one
-        // sharer of its compute units, not G (include/ggml_hip.h "serial_stage_slots"); with a second split session alive they are not
+        // sharer of its compute units, not G (the option set below); with a second split session alive they are not
         const bool only_split_session = g_split_sessions.fetch_add(1) == 0;
         ggml_hip_set_option("serial_stage_slots", only_split_session ? (int)m->stages.size() : 0);
         // ... and stages that share a physical GPU share its queue too: the residual then crosses a stage boundary inside one stream

@@ -224,6 +224,7 @@ PROTOTYPES.update({
     "ggml_hip_timing_end": (None, []),
     "ggml_hip_timing_query": (None, [C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
     "ggml_hip_set_option": (None, [C.c_char_p, C.c_int]),
+    "ggml_hip_get_option": (C.c_int, [C.c_char_p]),
     "ggml_hip_get_stat": (C.c_int64, [C.c_char_p]),
     "ggml_hip_read_timeline": (C.c_size_t, [C.c_void_p, C.c_size_t]),
     "ggml_hip_get_main_device": (C.c_int, []),
@@ -547,6 +548,11 @@ def get_stat(key):
 
 def set_option(key, value):
     lib().ggml_hip_set_option(key.encode(), int(value))
+
+
+def get_option(key):
+    """What the current slot holds for a runtime option (before the slot exists: the value set, else the default)."""
+    return int(lib().ggml_hip_get_option(key.encode()))
 
 
 def read_timeline(max_records=4096):
