@@ -365,10 +365,28 @@ GGML_API struct ggml_tensor *ggml_rope_inplace(struct ggml_context *ctx, struct 
 GGML_API struct ggml_tensor *ggml_rope_custom_inplace(struct ggml_context *ctx, struct ggml_tensor *a,
                                                       int n_past, int n_dims, int mode, int n_ctx,
                                                       float freq_base, float freq_scale); /* :1583 */
-/* Declared by the reference surface but outside the accelerated path: these abort with a message
- * (reference: crates/ggml/src/context.rs:592-626, 385-427; used only by bloom/mpt/none). */
+/* The rest of the reference surface (crates/ggml/src/context.rs:592-626, 385-427): ggml_alibi and ggml_flash_attn run on
+ * the device in the layouts their comments state and abort with a message outside them; the host callbacks
+ * (ggml_map_*) always abort. */
 GGML_API struct ggml_tensor *ggml_alibi(struct ggml_context *ctx, struct ggml_tensor *a, int n_past, int n_head,
                                         float bias_max);
+/* Fused attention as ONE node (context.rs:614 op_flash_attn; runs on the device: kernels/flash_attn.h).
+ *   q [D, N, H, B]   k [D, M, Hkv, B]   v [M, D, Hkv, B] (transposed: the view LLaMA's graph builds)   P = M - N >= 0
+ *   result: a fresh contiguous F32 tensor with q's n_dims and ne; op GGML_OP_FLASH_ATTN, src[0..2] = q, k, v,
+ *   op_params[0] = masked.
+ *   out[:, i, h, b] = sum_j p_j v[j, :, h / r, b],  p = soft_max_j(q_i . k_j / sqrtf(D)) over the keys j <= P + i (masked)
+ *   or over all M keys (not masked), with soft_max's rounding points: scores and their scaling in f32, the exponential's
+ *   argument and value rounded to f16, an exact sum, p = f32(e * f32(1 / sum)); with f16 k/v p is rounded to f16 before
+ *   it meets v, with f32 k/v it stays f32; the products are accumulated in f32.
+ * Types (q / k, v): F32 / F32 and F16 / F16 as upstream; F32 / F16 as an extension (q is rounded to f16 when loaded, as
+ *   mul_mat rounds its src1: the layout every model of this library has).  A second extension: H may be a multiple r of
+ *   Hkv (head h reads K/V head h / r); ne[3] must agree on all three.
+ * Strides: nb[0] is the element size; nb[1..3] are free (multiples of the element size): permuted views and views into a
+ *   larger K/V cache are the normal case.  Cache rows at and beyond M are never read.
+ * Limits: D <= 1024 and M <= 37312 keys: a row's scores are held in the CU's 160 KB of LDS (internal.h FLASH_ATTN_*).
+ * Anything else — another type mix, v.ne[0] != M, v.ne[1] != D, k.ne[0] != D, M < N, head or batch counts that do not
+ *   divide / match, a sparse nb[0], a row beyond the limits — aborts HERE, while the graph is built, with a message that
+ *   names ggml_flash_attn and the rule.  ggml_flash_attn_back and ggml_flash_ff are not part of this surface. */
 GGML_API struct ggml_tensor *ggml_flash_attn(struct ggml_context *ctx, struct ggml_tensor *q,
                                              struct ggml_tensor *k, struct ggml_tensor *v, bool masked);
 GGML_API struct ggml_tensor *ggml_map_unary_f32(struct ggml_context *ctx, struct ggml_tensor *a,

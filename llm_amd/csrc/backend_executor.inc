@@ -265,6 +265,7 @@ void execute_graph(ggml_cgraph *gr) {
             case GGML_OP_SOFT_MAX: op_soft_max(n); break;
             case GGML_OP_ALIBI: op_alibi(n); break;
             case GGML_OP_ROPE: op_rope(n); break;
+            case GGML_OP_FLASH_ATTN: op_flash_attn(n); break;
             case GGML_OP_CPY: op_cpy(n->src[0], n->src[1]); break;
             case GGML_OP_CONT:
             case GGML_OP_DUP: op_cpy(n->src[0], n); break;

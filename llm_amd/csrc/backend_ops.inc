@@ -933,3 +933,79 @@ void op_get_rows(ggml_tensor *dst) {
     }
     HIP_CHECK(hipGetLastError());
 }
+
+// GGML_OP_FLASH_ATTN: q [D, N, H, B], k [D, M, Hkv, B], v [M, D, Hkv, B] -> dst [D, N, H, B] f32 in one launch (kernels/flash_attn.h).
+// ggml_flash_attn (ggml_core.cpp) has refused every layout the kernels do not take; what is asserted here is that contract.
+static inline int prompt_attn_row_bytes(int64_t T);                                                       // plan_shapes.inc
+static inline int flash_attn_tile_queries(bool kv_f16, int64_t D, int64_t N, int64_t M, bool aligned16);  // plan_shapes.inc
+void op_flash_attn(ggml_tensor *dst) {
+    const ggml_tensor *q = dst->src[0], *k = dst->src[1], *v = dst->src[2];
+    const bool kv16 = k->type == GGML_TYPE_F16;
+    const size_t es = kv16 ? 2 : 4;
+    BK_ASSERT(is_contig_f32(dst) && k->type == v->type && (kv16 || k->type == GGML_TYPE_F32));
+    BK_ASSERT(q->type == GGML_TYPE_F32 || (q->type == GGML_TYPE_F16 && kv16));
+    BK_ASSERT(q->nb[0] == ggml_type_size(q->type) && k->nb[0] == es && v->nb[0] == es);
+    FlashAttnArgs a;
+    a.D = (int)q->ne[0]; a.N = (int)q->ne[1]; a.H = (int)q->ne[2]; a.B = (int)q->ne[3]; a.M = (int)k->ne[1];
+    BK_ASSERT(a.D >= 1 && a.D <= FLASH_ATTN_MAX_D && a.N >= 1 && a.M >= a.N && a.M <= FLASH_ATTN_MAX_KEYS);
+    BK_ASSERT(k->ne[0] == a.D && v->ne[0] == a.M && v->ne[1] == a.D && k->ne[2] == v->ne[2] && k->ne[2] >= 1 && a.H % k->ne[2] == 0);
+    BK_ASSERT(k->ne[3] == a.B && v->ne[3] == a.B);
+    BK_ASSERT(dst->ne[0] == a.D && dst->ne[1] == a.N && dst->ne[2] == a.H && dst->ne[3] == a.B);
+    const int64_t rows = (int64_t)a.N * a.H * a.B;
+    if (rows == 0) return;
+    BK_ASSERT(rows < (1ll << 31));
+    a.q = dev_ptr(q); a.k = dev_ptr(k); a.v = dev_ptr(v); a.out = (float *)dev_ptr(dst);
+    a.q_nb1 = (int64_t)q->nb[1]; a.q_nb2 = (int64_t)q->nb[2]; a.q_nb3 = (int64_t)q->nb[3];
+    a.k_nb1 = (int64_t)k->nb[1]; a.k_nb2 = (int64_t)k->nb[2]; a.k_nb3 = (int64_t)k->nb[3];
+    a.v_nb1 = (int64_t)v->nb[1]; a.v_nb2 = (int64_t)v->nb[2]; a.v_nb3 = (int64_t)v->nb[3];
+    a.r = (int)(a.H / k->ne[2]);
+    a.P = a.M - a.N;
+    a.masked = dst->op_params[0] != 0;
+    a.q16 = q->type == GGML_TYPE_F16;
+    a.scale = 1.0f / sqrtf((float)a.D);
+    a.kvec = (((uintptr_t)a.k | (uintptr_t)a.k_nb1 | (uintptr_t)a.k_nb2 | (uintptr_t)a.k_nb3) & 15) == 0;
+    a.vvec = (((uintptr_t)a.v | (uintptr_t)a.v_nb1 | (uintptr_t)a.v_nb2 | (uintptr_t)a.v_nb3) & 15) == 0;
+    a.row_bytes = 0;
+    // bytes: q and the result once; per query row the keys it sees (all of them when unmasked), K and V
+    const double seen = a.masked ? (double)a.N * (a.P + (a.N + 1) * 0.5) : (double)a.N * a.M;
+    Timed tm(GGML_HIP_KCLASS_ATTN, (double)rows * a.D * (ggml_type_size(q->type) + 4.0) + 2.0 * seen * a.D * es * a.H * a.B);
+    g.stat_flash_attn_nodes++;
+    const int QR = flash_attn_tile_queries(kv16, a.D, a.N, a.M, a.kvec && a.vvec);
+    if (QR) {
+        a.row_bytes = prompt_attn_row_bytes(a.M);
+        const size_t lds = (size_t)QR * a.row_bytes;
+        BK_ASSERT(lds <= FLASH_ATTN_LDS_BYTES);
+        static DevOnce attr_set;
+        if (attr_set.first()) {
+            HIP_CHECK(hipFuncSetAttribute((const void *)k_flash_attn_tile<128, 32>, hipFuncAttributeMaxDynamicSharedMemorySize, FLASH_ATTN_LDS_BYTES));
+            HIP_CHECK(hipFuncSetAttribute((const void *)k_flash_attn_tile<64, 32>, hipFuncAttributeMaxDynamicSharedMemorySize, FLASH_ATTN_LDS_BYTES));
+            HIP_CHECK(hipFuncSetAttribute((const void *)k_flash_attn_tile<32, 32>, hipFuncAttributeMaxDynamicSharedMemorySize, FLASH_ATTN_LDS_BYTES));
+            HIP_CHECK(hipFuncSetAttribute((const void *)k_flash_attn_tile<128, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, FLASH_ATTN_LDS_BYTES));
+            HIP_CHECK(hipFuncSetAttribute((const void *)k_flash_attn_tile<64, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, FLASH_ATTN_LDS_BYTES));
+            HIP_CHECK(hipFuncSetAttribute((const void *)k_flash_attn_tile<32, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, FLASH_ATTN_LDS_BYTES));
+        }
+        const int64_t wgs = (int64_t)((a.N + QR - 1) / QR) * a.H * a.B;
+        BK_ASSERT(wgs < (1ll << 31));
+        const dim3 grid((unsigned)wgs);
+        if (QR == 32) {
+            if (a.D == 128) hipLaunchKernelGGL((k_flash_attn_tile<128, 32>), grid, dim3(256), lds, g.stream, a);
+            else if (a.D == 64) hipLaunchKernelGGL((k_flash_attn_tile<64, 32>), grid, dim3(256), lds, g.stream, a);
+            else hipLaunchKernelGGL((k_flash_attn_tile<32, 32>), grid, dim3(256), lds, g.stream, a);
+        } else {
+            if (a.D == 128) hipLaunchKernelGGL((k_flash_attn_tile<128, 16>), grid, dim3(256), lds, g.stream, a);
+            else if (a.D == 64) hipLaunchKernelGGL((k_flash_attn_tile<64, 16>), grid, dim3(256), lds, g.stream, a);
+            else hipLaunchKernelGGL((k_flash_attn_tile<32, 16>), grid, dim3(256), lds, g.stream, a);
+        }
+    } else {
+        const size_t lds = FLASH_ROW_RED + (((size_t)a.D * 4 + 15) & ~(size_t)15) + (((size_t)a.M * 4 + 15) & ~(size_t)15);
+        BK_ASSERT(lds <= FLASH_ATTN_LDS_BYTES);
+        static DevOnce attr_set;
+        if (attr_set.first()) {
+            HIP_CHECK(hipFuncSetAttribute((const void *)k_flash_attn_row<true>, hipFuncAttributeMaxDynamicSharedMemorySize, FLASH_ATTN_LDS_BYTES));
+            HIP_CHECK(hipFuncSetAttribute((const void *)k_flash_attn_row<false>, hipFuncAttributeMaxDynamicSharedMemorySize, FLASH_ATTN_LDS_BYTES));
+        }
+        if (kv16) hipLaunchKernelGGL(k_flash_attn_row<true>, dim3((unsigned)rows), dim3(256), lds, g.stream, a);
+        else hipLaunchKernelGGL(k_flash_attn_row<false>, dim3((unsigned)rows), dim3(256), lds, g.stream, a);
+    }
+    HIP_CHECK(hipGetLastError());
+}

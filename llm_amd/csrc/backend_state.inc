@@ -99,6 +99,7 @@ struct Backend {
     // counters: what each counts is said once, at its row of g_counters below
     uint64_t stat_plan_tokens = 0, stat_generic_graphs = 0, stat_split_tokens = 0, stat_prompt_plan_tokens = 0, stat_fused_tokens = 0, stat_kplan_tokens = 0, stat_fused_heads_tokens = 0, stat_fused_wo_tokens = 0, stat_fused_affine_tokens = 0, stat_prepared_tokens = 0;
     uint64_t stat_alibi_fused = 0;
+    uint64_t stat_flash_attn_nodes = 0;
     // prompt-GEMM launches by kernel (ggml_hip_get_stat("mmq_launches_<name>")): bench.py labels its MFMA roofline with the
     // kernels that actually ran
     enum { MMQ_K_PLAIN, MMQ_K_DMA_P8, MMQ_K_W16_P8, MMQ_K_W16_256, MMQ_K_I8, MMQ_K_COUNT };
@@ -277,6 +278,7 @@ static const StatRow g_counters[] = {
     {"spec_misses", &Backend::stat_spec_misses},                  // ... speculative runs nobody asked for
     {"generic_graphs", &Backend::stat_generic_graphs},            // graphs run node by node
     {"alibi_fused", &Backend::stat_alibi_fused},                  // scale -> alibi -> diag_mask_inf -> soft_max chains (BLOOM, MPT) run as one launch (k_alibi_soft_max)
+    {"flash_attn_nodes", &Backend::stat_flash_attn_nodes},        // GGML_OP_FLASH_ATTN nodes computed (one launch each: kernels/flash_attn.h)
     {"ns_match", &Backend::ns_match},      // host-side time split of plan tokens: ns spent recognising decode graphs
     {"ns_launch", &Backend::ns_launch},    // ... enqueueing (param upload, graph launch, read-back queue)
     {"ns_wait", &Backend::ns_wait},        // ... waiting for the device + copying results out

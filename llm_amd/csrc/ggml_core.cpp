@@ -684,10 +684,43 @@ struct ggml_tensor *ggml_alibi(struct ggml_context *ctx, struct ggml_tensor *a, 
     set_op_params(result, params, sizeof(params));
     return result;
 }
-struct ggml_tensor *ggml_flash_attn(struct ggml_context *, struct ggml_tensor *, struct ggml_tensor *,
-                                    struct ggml_tensor *, bool) {
-    out_of_path("ggml_flash_attn");
-    return nullptr;
+// Fused attention as one node (kernels/flash_attn.h); the contract is in include/ggml_hip.h.  Everything the kernels cannot
+// take is refused HERE, while the graph is built, with the violated rule in the message: the executor has nothing left to refuse.
+struct ggml_tensor *ggml_flash_attn(struct ggml_context *ctx, struct ggml_tensor *q, struct ggml_tensor *k,
+                                    struct ggml_tensor *v, bool masked) {
+    auto reject = [](const char *rule) {
+        char msg[256];
+        snprintf(msg, sizeof(msg), "ggml_flash_attn (%s)", rule);
+        out_of_path(msg);
+    };
+    const bool f32 = q->type == GGML_TYPE_F32 && k->type == GGML_TYPE_F32 && v->type == GGML_TYPE_F32;
+    const bool f16 = k->type == GGML_TYPE_F16 && v->type == GGML_TYPE_F16 && (q->type == GGML_TYPE_F16 || q->type == GGML_TYPE_F32);
+    if (!f32 && !f16) reject("types: q/k/v must be F32/F32/F32, F16/F16/F16 or F32/F16/F16");
+    const int64_t D = q->ne[0], N = q->ne[1], M = k->ne[1];
+    if (D < 1 || N < 1 || k->ne[0] != D) reject("shape: k.ne[0] must equal q.ne[0] = D >= 1, and q.ne[1] = N >= 1");
+    if (v->ne[0] != M) reject("shape: v.ne[0] must equal k.ne[1] = M (v is transposed: [M, D, H, B])");
+    if (v->ne[1] != D) reject("shape: v.ne[1] must equal D");
+    if (M < N) reject("shape: M < N (k.ne[1] must be at least q.ne[1])");
+    if (k->ne[2] < 1 || k->ne[2] != v->ne[2] || q->ne[2] % k->ne[2] != 0)
+        reject("heads: k.ne[2] must equal v.ne[2] and divide q.ne[2]");
+    if (q->ne[3] != k->ne[3] || q->ne[3] != v->ne[3]) reject("batch: ne[3] must agree on q, k and v");
+    if (q->nb[0] != ggml_type_size(q->type) || k->nb[0] != ggml_type_size(k->type) || v->nb[0] != ggml_type_size(v->type))
+        reject("strides: nb[0] must be dense (the element size) on q, k and v");
+    for (const ggml_tensor *t : {q, k, v})
+        for (int i = 1; i < 4; i++)
+            if (t->nb[i] % t->nb[0] != 0 || (uintptr_t)t->data % t->nb[0] != 0)
+                reject("strides: nb[1..3] and the data offset must be multiples of the element size");
+    if (D > FLASH_ATTN_MAX_D) reject("limit: D exceeds FLASH_ATTN_MAX_D = 1024 (q is held in LDS)");
+    if (M > FLASH_ATTN_MAX_KEYS) reject("limit: M exceeds FLASH_ATTN_MAX_KEYS = 37312 (the scores of a row are held in the 160 KB LDS)");
+    static_assert(FLASH_ATTN_MAX_KEYS == 37312 && FLASH_ATTN_MAX_KEYS_TILE == 2368, "the messages and the header quote these");
+    ggml_tensor *result = ggml_new_tensor(ctx, GGML_TYPE_F32, q->n_dims, q->ne);
+    result->op = GGML_OP_FLASH_ATTN;
+    result->src[0] = q;
+    result->src[1] = k;
+    result->src[2] = v;
+    const int32_t p = masked ? 1 : 0;
+    set_op_params(result, &p, sizeof(p));
+    return result;
 }
 struct ggml_tensor *ggml_map_unary_f32(struct ggml_context *, struct ggml_tensor *, ggml_unary_op_f32_t) {
     out_of_path("ggml_map_unary_f32 (host callbacks cannot run on the device)");

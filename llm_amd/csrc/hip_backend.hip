@@ -58,6 +58,7 @@
 #include "kernels/kquant_big.h"
 #include "kernels/prompt.h"
 #include "kernels/prompt_attn.h"
+#include "kernels/flash_attn.h"
 
 // Last words of the library: stderr, and (GGML_HIP_FATAL_LOG=path) a file — a test runner that captures file descriptor 2
 // swallows the message of an abort together with the process.

@@ -215,6 +215,9 @@ class Context {
     }
     Tensor op_soft_max(const Tensor &a) const { return raw(ggml_soft_max(as_ptr(), a.ptr())); }
     Tensor op_soft_max_inplace(const Tensor &a) const { return raw(ggml_soft_max_inplace(as_ptr(), a.ptr())); }
+    Tensor op_flash_attn(const Tensor &q, const Tensor &k, const Tensor &v, bool masked) const {  // context.rs:614
+        return raw(ggml_flash_attn(as_ptr(), q.ptr(), k.ptr(), v.ptr(), masked));
+    }
     Tensor op_view_1d(const Tensor &a, size_t ne0, size_t offset) const {
         return raw(ggml_view_1d(as_ptr(), a.ptr(), (int64_t)ne0, offset));
     }

@@ -381,3 +381,11 @@ static inline int prompt_attn_queries(int64_t D, int64_t T) {
     return 0;
 }
 static inline bool prompt_attn_fits(int64_t D, int64_t T) { return prompt_attn_queries(D, T) != 0; }
+// ---- GGML_OP_FLASH_ATTN (kernels/flash_attn.h): queries per workgroup of the MFMA kernel k_flash_attn_tile — 32, 16 (long rows) —
+// or 0: one row per workgroup (k_flash_attn_row).  The tile kernel takes f16 K/V of head size 32 / 64 / 128, at least two query
+// rows, rows of at most FLASH_ATTN_MAX_KEYS_TILE keys (its score rows have k_p_attn's size) and reads K rows and V rows 16 bytes
+// at a time: `aligned16` says that their first elements and every stride are multiples of 16.
+static inline int flash_attn_tile_queries(bool kv_f16, int64_t D, int64_t N, int64_t M, bool aligned16) {
+    if (!kv_f16 || N < 2 || !aligned16 || M > FLASH_ATTN_MAX_KEYS_TILE) return 0;
+    return prompt_attn_queries(D, M);
+}
