@@ -584,6 +584,13 @@ GGML_API int ggml_hip_graph_prepare(struct ggml_cgraph *cgraph);
  * memory advances by n positions; the caller adds n to its n_past.  Returns 0, or -1 if the precondition does not
  * hold (nothing was executed: decode token by token instead). */
 GGML_API int ggml_hip_decode_greedy_chain(struct ggml_cgraph *last, int n, int32_t *out_tokens, float *last_logits);
+/* One decode step of B single-token LLaMA graphs of ONE model on this slot, each the reference's unchanged graph for its own
+ * session (own memory_k / memory_v, own n_past, own token), as one pass over the weights.  Same results as ggml_graph_compute
+ * on each graph in turn (host-visible nodes filled: logits, embeddings).  Returns 0, or -1 with nothing executed.
+ * -1 unless: 2 <= B <= 8; every graph is a whole-model single-token graph of a block-format (not K-quant) model; all share the
+ * weights, dimensions, context size and RoPE parameters; f16 K/V, all distinct; every n_past below the context size, which fits
+ * the attention kernel's LDS; options plan and plan_batch on.  NULL or a B out of range is refused before any device is touched. */
+GGML_API int ggml_hip_decode_batch(struct ggml_cgraph *const *graphs, int n_graphs);
 /* Top-k prefilter of a logits row on the device: the k (<= 1024, <= ne0) largest entries of row `row` of
  * the f32 tensor `t` — a node of the caller's most recent ggml_graph_compute, normally the logits — as (value, id) pairs,
  * value descending, lower id first among equal values, followed by the entries of `extra_ids` (n_extra ids, e.g. the

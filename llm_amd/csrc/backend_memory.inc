@@ -126,6 +126,7 @@ bool wants_ksoa(const ggml_tensor *t) {
     return kt_of(t->type) >= 0 && t->ne[2] == 1 && t->ne[3] == 1 && t->ne[0] % 256 == 0 && ggml_is_contiguous(t);
 }
 
+static const size_t SESSION_GUARD_BYTES = 4096;  // behind every zero-filled (session state) record, see below
 // Uploads `nbytes` from host `data` as the device copy of `t`. Returns the record (registered in g.tensors).
 DevTensor *upload_tensor(const void *data, const ggml_tensor *t, bool zero_fill, bool is_auto = false) {
     ensure_init();
@@ -184,10 +185,16 @@ DevTensor *upload_tensor(const void *data, const ggml_tensor *t, bool zero_fill,
         e->ksoa = true;
         e->kw = kw_at(e->dev, kt, M, nsb);
     } else {
-        dev_malloc((void **)&e->dev, std::max<size_t>(nbytes, 16), "a persistent tensor");
+        // Session state (K/V memory, hand-off buffers) ends in a zeroed guard of its own.  A caller whose graph runs a little past
+        // the context — the reference's perplexity loop never lowers n_past between chunks (INTEGRATION.md section 4), a test that feeds
+        // 72 tokens into a context of 64 — gets views that end beyond the tensor (ggml does not check them); without the guard those
+        // rows are whatever the allocator put next: another session's cache, which such a caller then reads and WRITES.  With several
+        // sessions alive (and more of them per process since the batched step) what it computes must not depend on its neighbours.
+        const size_t guard = zero_fill ? SESSION_GUARD_BYTES : 0;
+        dev_malloc((void **)&e->dev, std::max<size_t>(nbytes, 16) + guard, "a persistent tensor");
         e->dev_bytes = nbytes;
         if (zero_fill)
-            HIP_CHECK(hipMemsetAsync(e->dev, 0, std::max<size_t>(nbytes, 16), g.stream));
+            HIP_CHECK(hipMemsetAsync(e->dev, 0, std::max<size_t>(nbytes, 16) + guard, g.stream));
         else
             h2d_bulk(e->dev, data, nbytes);
         HIP_CHECK(hipStreamSynchronize(g.stream));

@@ -469,6 +469,17 @@ int ggml_hip_decode_greedy_chain(struct ggml_cgraph *last, int n, int32_t *out_t
     return decode_greedy_chain(last, n, out_tokens, last_logits);
 }
 
+int ggml_hip_decode_batch(struct ggml_cgraph *const *graphs, int n_graphs) {
+    if (!graphs || n_graphs < 2 || n_graphs > BATCH_COLS_MAX) return -1;  // (before any device is touched)
+    for (int i = 0; i < n_graphs; i++)
+        if (!graphs[i]) return -1;
+    SlotLock lk;
+    const uint64_t t0 = now_ns();
+    const int r = decode_batch(graphs, n_graphs);
+    g.ns_compute += now_ns() - t0;
+    return r;
+}
+
 int64_t ggml_hip_get_stat(const char *key) {
     SlotLock lk;
     for (const StatRow &c : g_counters)  // the plain counters (backend_state.inc); the rest is computed here

@@ -1,0 +1,14 @@
+// llm_batch.cpp — the batched multi-session decode step of the session mirror bound to this library's backend: llm_evaluate_batch and
+// llm_infer_next_tokens_greedy_batch are llm_host.cpp's llm_*_batch_via with ggml_hip_decode_batch as the entry.  A file of its own
+// so that llm_host.cpp keeps linking against backends that have no such entry.
+#include "ggml_hip.h"
+#include "llm_host.h"
+
+extern "C" {
+int llm_evaluate_batch(llm_model *m, llm_session *const *sessions, const int32_t *tokens, int B, float *logits) {
+    return llm_evaluate_batch_via(ggml_hip_decode_batch, m, sessions, tokens, B, logits);
+}
+int llm_infer_next_tokens_greedy_batch(llm_model *m, llm_session *const *sessions, int B, int32_t *out_ids) {
+    return llm_infer_next_tokens_greedy_batch_via(ggml_hip_decode_batch, m, sessions, B, out_ids);
+}
+}

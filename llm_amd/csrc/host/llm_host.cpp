@@ -213,6 +213,26 @@ class InferenceSession {
         last_graph = nullptr;
     }
 
+    // Batched decode (llm_evaluate_batch): the session's single-token graph for `tok` at n_past, built as compute() builds it and
+    // its token written, but not computed — the caller hands the graphs of several sessions to the backend together.  No
+    // speculative build of the next graph.  The graph lives in its ctx0 arena until that arena is recreated.
+    ggml_cgraph *stage_single(TokenId tok, const Builder &builder, GraphOutputs &out) {
+        pre_.valid = false;
+        cur_ ^= 1;
+        Built built = build_into(cur_, 1, builder);
+        built.embd.write_data(&tok, sizeof(TokenId));
+        out = GraphOutputs{built.out.result.share(), built.out.embedding_result.share()};
+        return built.gf.raw();
+    }
+    // ... and compute()'s bookkeeping once that graph has run
+    void commit_single(ggml_cgraph *gr) {
+        last_n_nodes = gr->n_nodes;
+        last_n_leafs = gr->n_leafs;
+        last_graph = gr;
+        if (mem_per_token == 0) mem_per_token = ctx0_[cur_].used_mem() / n_embd_;
+        n_past += 1;
+    }
+
     void drop_prebuilt() {  // a speculatively built next-token graph no longer describes the session's next call
         pre_.valid = false;
         last_graph = nullptr;
@@ -530,6 +550,16 @@ class Llama {
         common::extract_embeddings(output_request, outputs.embedding_result, n_embd, input_len);
     }
 
+    // evaluate() of one token in two halves around a computation the caller arranges (llm_evaluate_batch): the graph exactly as
+    // evaluate builds it, then what evaluate does once it has been computed
+    ggml_cgraph *stage_single(InferenceSession &session, TokenId tok, GraphOutputs &out) {
+        return session.stage_single(tok, make_builder(&session, 1, session.n_past), out);
+    }
+    void finish_single(InferenceSession &session, ggml_cgraph *gr, const GraphOutputs &out) {
+        session.commit_single(gr);
+        common::read_last_token(session, out.result, hyperparameters.n_vocab, 1);
+    }
+
     Hyperparameters hyperparameters;
     ModelParameters params;
     Tensor wte, norm, output;
@@ -561,6 +591,7 @@ struct llm_session {
     bool shares_streams = false;  // its stages of one GPU enqueue on one stream (ggml_hip_share_stream), undone when the session goes
     std::vector<int> devices;
     int device = 0;  // unsplit: the model's slot (K/V, shadows and plans of the session live there)
+    const llm_model *model = nullptr;  // the model it was started from
 };
 
 namespace {
@@ -1121,6 +1152,7 @@ llm_session *llm_start_session(llm_model *m, const llm_session_config *cfg) {
         c.n_threads = cfg->n_threads > 0 ? (size_t)cfg->n_threads : 8;
     }
     llm_session *s = new llm_session();
+    s->model = m;
     if (!m->stages.empty()) {
         const int home = ggml_hip_get_main_device();
         for (size_t i = 0; i < m->stages.size(); i++) {
@@ -1178,6 +1210,7 @@ llm_session *llm_start_session_on(llm_model *m, const llm_session_config *cfg, i
         c.n_threads = cfg->n_threads > 0 ? (size_t)cfg->n_threads : 8;
     }
     llm_session *s = new llm_session();
+    s->model = m;
     HomeDevice hd;
     hd.go(slot);
     s->device = slot;
@@ -1400,6 +1433,60 @@ int llm_infer_tokens_greedy_device(llm_model *m, llm_session *s, int n, int32_t 
     }
     for (; done < n; done++) out[done] = llm_infer_next_token_greedy(m, s);
     return n;
+}
+// One decode step of B sessions of one model (batched multi-session decode): every session's single-token graph is built exactly as
+// llm_evaluate builds it and the B graphs go to the backend together (`entry` = ggml_hip_decode_batch: one pass over the weights for
+// all of them).  If the backend declines (-1: nothing was executed) the sessions are evaluated one after the other — the same
+// results, B passes.  The entry is a parameter because this file also links against backends that have none (the sanitizer jobs'
+// host stand-in); host/llm_batch.cpp binds the real one.  Returns 1 = ran batched, 0 = ran one by one, -1 = bad arguments, nothing
+// evaluated: a session listed twice, of another model or on another device slot than the calling thread's, a split model, a
+// token outside the vocabulary, a session whose context is full.  Like llm_evaluate it leaves the token history to the caller.
+int llm_evaluate_batch_via(llm_batch_entry entry, llm_model *m, llm_session *const *sessions, const int32_t *tokens, int B, float *logits) {
+    if (!m || !sessions || !tokens || B < 1) return -1;
+    if (!m->stages.empty() || !m->llama->is_first() || !m->llama->is_last()) return -1;
+    const size_t V = m->llama->hyperparameters.n_vocab;
+    for (int i = 0; i < B; i++) {
+        const llm_session *s = sessions[i];
+        if (!s || !s->s || s->model != m || !s->stage_sessions.empty() || s->device != ggml_hip_get_main_device()) return -1;
+        for (int j = 0; j < i; j++)
+            if (sessions[j] == s) return -1;
+        if (tokens[i] < 0 || (size_t)tokens[i] >= V || s->s->n_past + 1 > m->llama->params.context_size) return -1;
+    }
+    int batched = 0;
+    if (entry && B >= 2) {
+        std::vector<ggml_cgraph *> graphs((size_t)B);
+        std::vector<llm::GraphOutputs> outs((size_t)B);
+        for (int i = 0; i < B; i++) graphs[(size_t)i] = m->llama->stage_single(*sessions[i]->s, (llm::TokenId)tokens[i], outs[(size_t)i]);
+        if (entry(graphs.data(), B) == 0) {
+            for (int i = 0; i < B; i++) m->llama->finish_single(*sessions[i]->s, graphs[(size_t)i], outs[(size_t)i]);
+            batched = 1;
+        }
+    }
+    if (!batched)
+        for (int i = 0; i < B; i++) {
+            llm::OutputRequest req;
+            model_evaluate(m, sessions[i], std::vector<llm::TokenId>{(llm::TokenId)tokens[i]}, req);
+        }
+    if (logits)
+        for (int i = 0; i < B; i++) memcpy(logits + (size_t)i * V, sessions[i]->s->last_logits.data(), V * sizeof(float));
+    return batched;
+}
+// llm_infer_next_token_greedy for B sessions in one step: the first maximum of every session's last_logits, then the step above
+int llm_infer_next_tokens_greedy_batch_via(llm_batch_entry entry, llm_model *m, llm_session *const *sessions, int B, int32_t *out_ids) {
+    if (!m || !sessions || !out_ids || B < 1) return -1;
+    std::vector<int32_t> next((size_t)B);
+    for (int i = 0; i < B; i++) {
+        if (!sessions[i] || !sessions[i]->s) return -1;
+        const std::vector<float> &l = sessions[i]->s->last_logits;
+        next[(size_t)i] = (int32_t)argmax_first(l.data(), l.size());
+    }
+    const int r = llm_evaluate_batch_via(entry, m, sessions, next.data(), B, nullptr);
+    if (r < 0) return -1;
+    for (int i = 0; i < B; i++) {
+        sessions[i]->s->tokens.push_back((llm::TokenId)next[(size_t)i]);
+        out_ids[i] = next[(size_t)i];
+    }
+    return r;
 }
 // Accumulated host nanoseconds per phase (see InferenceSession::host_ns; [5] greedy argmax, [6] evaluate as a whole);
 // reset != 0 clears the accumulators after the read.

@@ -118,6 +118,24 @@ GGML_API int32_t llm_infer_next_token_topk(llm_model *m, llm_session *s, int k, 
 /* n greedy tokens with the argmax on the device (ggml_hip_decode_greedy_chain): same ids and final logits as n calls
  * of llm_infer_next_token_greedy, no per-token logits read-back; falls back to that loop when chaining is impossible */
 GGML_API int llm_infer_tokens_greedy_device(llm_model *m, llm_session *s, int n, int32_t *out);
+/* One decode step of B sessions of ONE model, token tokens[i] for sessions[i], as one pass over the weights where the backend can
+ * (ggml_hip_decode_batch: 2..8 sessions of a block-format model, f16 K/V): each session's single-token graph is built exactly as
+ * llm_evaluate builds it, and each session ends as after llm_evaluate(m, sessions[i], &tokens[i], 1, ...) — n_past, last_logits; the
+ * token history stays the caller's, as there.  logits (nullable): B * n_vocab floats, row i = session i's.
+ * Returns 1 if the step ran batched, 0 if the sessions were evaluated one after the other (the backend declined: same results),
+ * -1 on bad arguments with nothing evaluated: a session listed twice, of another model, of a layer-split model or on another device
+ * slot than the calling thread's, a token outside the vocabulary, a session whose context is full. */
+GGML_API int llm_evaluate_batch(llm_model *m, llm_session *const *sessions, const int32_t *tokens, int B, float *logits);
+/* llm_infer_next_token_greedy for B sessions in one such step: out_ids[i] = the first maximum of session i's last_logits, appended to
+ * its token history and evaluated.  Returns what llm_evaluate_batch returns. */
+GGML_API int llm_infer_next_tokens_greedy_batch(llm_model *m, llm_session *const *sessions, int B, int32_t *out_ids);
+/* the two entries above with the backend's batched step as a parameter (NULL: always one by one).  llm_host.cpp is also built against
+ * backends without ggml_hip_decode_batch; host/llm_batch.cpp binds the library's own. */
+typedef int (*llm_batch_entry)(struct ggml_cgraph *const *graphs, int n_graphs);
+GGML_API int llm_evaluate_batch_via(llm_batch_entry entry, llm_model *m, llm_session *const *sessions, const int32_t *tokens, int B,
+                                    float *logits);
+GGML_API int llm_infer_next_tokens_greedy_batch_via(llm_batch_entry entry, llm_model *m, llm_session *const *sessions, int B,
+                                                    int32_t *out_ids);
 GGML_API size_t llm_session_read_node_host(const llm_session *s, int from_end, void *dst, size_t max_bytes);
 GGML_API int llm_session_rewind(llm_session *s, int num);
 /* host nanoseconds per phase of the decode loop, accumulated: [0] adopt/build graph, [1] token write + plan,

@@ -24,6 +24,16 @@ struct DecParams {
     int pad1;
     int tokens[32];  // multi-token plan (2..31 tokens of a prompt chunk): ids of all tokens, tokens[0] == token
 };
+// Batched multi-session decode (plan_launch_batch): column c of the step is the ONE token session c evaluates, at that session's own
+// position in that session's own cache.  Uploaded once per step like DecParams; the kernels that place a column in a cache (the
+// RoPE table, the wq|wk|wv epilogues, the attention) read this table in their batched forms instead of "n_past + c of one cache".
+// The pointers are the bases of the sessions' memory_k / memory_v; the layer's offset is a launch argument.
+constexpr int BATCH_COLS_MAX = 8;
+struct BatchCols {
+    int pos[BATCH_COLS_MAX];        // n_past of column c's session = the position its token is evaluated at
+    __half *mem_k[BATCH_COLS_MAX];  // K element (layer il, pos p, chan c) at (il * C + p) * Egqa + c
+    __half *mem_v[BATCH_COLS_MAX];  // V element (layer il, chan c, pos p) at (il * Egqa + c) * C + p
+};
 
 // Greedy sampling on the device: token = first index of the maximum logit — what a host loop
 // `if (l[i] > l[best]) best = i` returns — written straight into the decode parameters of the NEXT replay of the plan
@@ -89,6 +99,12 @@ __global__ void __launch_bounds__(1024) k_argmax_next(const float *__restrict__ 
 // Block 0 also opens the token's epoch (`epoch`, nullable): the tag of the granules that k_qkv_attn's mat-vec workgroups hand
 // to its attention workgroups (kernels/decode_fused.h) — bumped on the device, once per token, so that a replayed hipGraph
 // never meets its own previous granules as current; 0 is skipped (a zeroed granule is never valid).
+__device__ __forceinline__ void rope_table_pair(int pos, int c, int kk, float theta_scale, float freq_scale, float *__restrict__ out) {
+    float theta = freq_scale * (float)pos;
+    for (int t = 0; t < kk; t++) theta *= theta_scale;
+    out[c * 128 + 2 * kk] = cosf(theta);
+    out[c * 128 + 2 * kk + 1] = sinf(theta);
+}
 __global__ void __launch_bounds__(128) k_rope_table(const DecParams *__restrict__ prm, float theta_scale, float freq_scale,
                                                     int half_d, float *__restrict__ out, unsigned *epoch = nullptr) {
     const int kk = threadIdx.x, c = blockIdx.x;  // block c: token c of a prompt chunk (position n_past + c), 128 floats each
@@ -97,10 +113,14 @@ __global__ void __launch_bounds__(128) k_rope_table(const DecParams *__restrict_
         *epoch = e ? e : 1u;
     }
     if (kk >= half_d) return;
-    float theta = freq_scale * (float)(prm->n_past + c);
-    for (int t = 0; t < kk; t++) theta *= theta_scale;
-    out[c * 128 + 2 * kk] = cosf(theta);
-    out[c * 128 + 2 * kk + 1] = sinf(theta);
+    rope_table_pair(prm->n_past + c, c, kk, theta_scale, freq_scale, out);
+}
+// batched decode: block c = the table of column c's own position
+__global__ void __launch_bounds__(128) k_rope_table_batch(const BatchCols *__restrict__ bc, float theta_scale, float freq_scale,
+                                                          int half_d, float *__restrict__ out) {
+    const int kk = threadIdx.x, c = blockIdx.x;
+    if (kk >= half_d) return;
+    rope_table_pair(bc->pos[c], c, kk, theta_scale, freq_scale, out);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -575,14 +595,16 @@ __global__ void __launch_bounds__(256) k_mmvq_dec(const DecMmvqArgs a) {
 //   * V·P    : wave w owns channels 8w..8w+7, 8 lanes per channel, a lane covers 8 consecutive positions per
 //              64-position pass → all lanes busy from 64 positions on, 8-lane DPP reduction at the end.
 // ---------------------------------------------------------------------------------------------------
+// The body of both forms below.  Query qn (blockIdx.y) sits at position *pos + pos_add of the cache (mem_k, mem_v): the chunk form
+// passes the chunk's first position and qn, the batched form column qn's own position and cache.
 template <bool F16_D>
-__global__ void __launch_bounds__(1024) k_attn_decode(const float *__restrict__ q, const __half *__restrict__ mem_k,
-                                                      const __half *__restrict__ mem_v, const DecParams *prm,
-                                                      float scale, int D, int n_rep /* H / Hkv */, int64_t Egqa,
-                                                      int64_t C, float *out_f32, int8_t *lo, int8_t *hi, float *dq,
-                                                      int *sumq, long long *ts, int n_head,
-                                                      int64_t Clds /* positions the LDS arrays hold (<= C, % 8 == 0) */,
-                                                      float *dT = nullptr, int *sT = nullptr /* as k_rmsnorm_quant */) {
+__device__ __forceinline__ void attn_decode_body(const float *__restrict__ q, const __half *__restrict__ mem_k,
+                                                 const __half *__restrict__ mem_v, const int *pos, const int pos_add,
+                                                 float scale, int D, int n_rep /* H / Hkv */, int64_t Egqa,
+                                                 int64_t C, float *out_f32, int8_t *lo, int8_t *hi, float *dq,
+                                                 int *sumq, long long *ts, int n_head,
+                                                 int64_t Clds /* positions the LDS arrays hold (<= C, % 8 == 0) */,
+                                                 float *dT, int *sT /* as k_rmsnorm_quant */) {
     const long long t_entry = ts ? (long long)wall_clock64() : 0;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float *s_s = (float *)smem;  // Clds scores
@@ -591,9 +613,9 @@ __global__ void __launch_bounds__(1024) k_attn_decode(const float *__restrict__ 
     __shared__ float s_red[16];
     __shared__ double s_redd[16];
     const int h = blockIdx.x, hk = h / n_rep;
-    const int qn = blockIdx.y;  // query token of a prompt chunk (0 for decode): position n_past + qn, row qn of q / outputs
+    const int qn = blockIdx.y;  // query token of a prompt chunk / column of a batched step (0 for decode): row qn of q / outputs
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int n_past = prm->n_past + qn;  // requested first; nothing below waits for it until the masks are needed
+    const int n_past = *pos + pos_add;  // requested first; nothing below waits for it until the masks are needed
     const int64_t Eq = (int64_t)n_head * D;
     const float *qh = q + qn * Eq + (int64_t)h * D;
     const f16x8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -773,4 +795,25 @@ __global__ void __launch_bounds__(1024) k_attn_decode(const float *__restrict__ 
             o[5] = (long long)wall_clock64(); o[6] = T; o[7] = h;
         }
     }
+}
+template <bool F16_D>
+__global__ void __launch_bounds__(1024) k_attn_decode(const float *__restrict__ q, const __half *__restrict__ mem_k,
+                                                      const __half *__restrict__ mem_v, const DecParams *prm,
+                                                      float scale, int D, int n_rep, int64_t Egqa, int64_t C, float *out_f32,
+                                                      int8_t *lo, int8_t *hi, float *dq, int *sumq, long long *ts, int n_head,
+                                                      int64_t Clds, float *dT = nullptr, int *sT = nullptr) {
+    attn_decode_body<F16_D>(q, mem_k, mem_v, &prm->n_past, (int)blockIdx.y, scale, D, n_rep, Egqa, C, out_f32, lo, hi, dq, sumq, ts,
+                            n_head, Clds, dT, sT);
+}
+// Batched decode: query column qn attends to the pos[qn] + 1 keys of ITS session's cache (BatchCols; kv_off: the layer's offset
+// into memory_k / memory_v, in elements).  The cache pointers come first, then everything as above — the speculative first pass
+// included (every session's cache is allocated for C positions).
+template <bool F16_D>
+__global__ void __launch_bounds__(1024) k_attn_decode_batch(const float *__restrict__ q, const BatchCols *__restrict__ bc, int64_t kv_off,
+                                                            float scale, int D, int n_rep, int64_t Egqa, int64_t C, int8_t *lo,
+                                                            int8_t *hi, float *dq, int *sumq, int n_head, int64_t Clds, float *dT,
+                                                            int *sT) {
+    const int qn = blockIdx.y;
+    attn_decode_body<F16_D>(q, bc->mem_k[qn] + kv_off, bc->mem_v[qn] + kv_off, &bc->pos[qn], 0, scale, D, n_rep, Egqa, C, nullptr, lo,
+                            hi, dq, sumq, nullptr, n_head, Clds, dT, sT);
 }

@@ -13,9 +13,12 @@ struct Big8Args {
     int ncols;         // 2..8 (1 works too)
     int64_t ldd, ldr;  // floats between consecutive rows of dst / res (and of the Q output for EPI_QKV)
     const float *rope; // EPI_QKV: (cos, sin) tables of the chunk's positions, 128 floats per token (k_rope_table)
+    const BatchCols *bc;  // BATCH instantiation only (EPI_QKV of a batched decode step): column c's position and cache, and ...
+    int64_t kv_off;       // ... the layer's offset into every session's memory_k / memory_v (elements); d.prm / d.mem_k / d.mem_v are not read
 };
 
-template <int QT, int EPI>
+// BATCH (EPI_QKV only): the columns are single tokens of different sessions (BatchCols) instead of consecutive positions of one.
+template <int QT, int EPI, bool BATCH = false>
 __global__ void __launch_bounds__(BIG_T) k_mmvq_big8(const Big8Args ba) {
     const DecMmvqArgs &a = ba.d;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -38,7 +41,7 @@ __global__ void __launch_bounds__(BIG_T) k_mmvq_big8(const Big8Args ba) {
 
     // ---- 1. activation loads first (see decode_big.h): up to 4 blocks per thread
     int n_past = 0;
-    if constexpr (EPI == EPI_QKV) n_past = a.prm->n_past;
+    if constexpr (EPI == EPI_QKV && !BATCH) n_past = a.prm->n_past;
     constexpr int MAXB = 4;  // ncols * nb <= 4 * T blocks (checked by the launcher)
     i32x4 xl[MAXB], xh[MAXB];
     float xdv[MAXB];
@@ -248,10 +251,16 @@ __global__ void __launch_bounds__(BIG_T) k_mmvq_big8(const Big8Args ba) {
             } else if constexpr (EPI == EPI_GATE) {
                 a.dst[(int64_t)c * ba.ldd + m0] = silu_table(myv[0][c]) * myv[1][c];
             } else {
-                const int p = n_past + c;  // position of this column's token
+                int p = n_past + c;  // position of this column's token
+                __half *mem_k = a.mem_k, *mem_v = a.mem_v;
+                if constexpr (BATCH) {
+                    p = ba.bc->pos[c];
+                    mem_k = ba.bc->mem_k[c] + ba.kv_off;
+                    mem_v = ba.bc->mem_v[c] + ba.kv_off;
+                }
                 if (sg == 2) {
-                    a.mem_v[(int64_t)m0 * a.C + p] = __float2half_rn(myv[0][c]);
-                    a.mem_v[(int64_t)(m0 + 1) * a.C + p] = __float2half_rn(myv[1][c]);
+                    mem_v[(int64_t)m0 * a.C + p] = __float2half_rn(myv[0][c]);
+                    mem_v[(int64_t)(m0 + 1) * a.C + p] = __float2half_rn(myv[1][c]);
                 } else {
                     const int kk = (m0 % a.D) >> 1;
                     const float cs = s_rope[(c * 64 + kk) * 2], sn = s_rope[(c * 64 + kk) * 2 + 1];
@@ -260,8 +269,8 @@ __global__ void __launch_bounds__(BIG_T) k_mmvq_big8(const Big8Args ba) {
                         a.dst[(int64_t)c * ba.ldd + m0] = r0;
                         a.dst[(int64_t)c * ba.ldd + m0 + 1] = r1;
                     } else {
-                        a.mem_k[(int64_t)p * a.Egqa + m0] = __float2half_rn(r0);
-                        a.mem_k[(int64_t)p * a.Egqa + m0 + 1] = __float2half_rn(r1);
+                        mem_k[(int64_t)p * a.Egqa + m0] = __float2half_rn(r0);
+                        mem_k[(int64_t)p * a.Egqa + m0 + 1] = __float2half_rn(r1);
                     }
                 }
             }

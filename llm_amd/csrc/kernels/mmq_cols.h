@@ -40,6 +40,8 @@ struct ColsArgs {
     long long *ts;     // INSTR build only (option "timeline"): 8 x int64 per sampled workgroup, as BigArgs::ts
     int ts_wgs;
     const void *hot;   // 256 bytes the dummy ring steps read (BigArgs::hot, decode_big.h); nullptr = the first bytes of the scales
+    const BatchCols *bc;  // BATCH instantiation only (EPI_QKV of a batched decode step): column c's position and cache, and ...
+    int64_t kv_off;       // ... the layer's offset into every session's memory_k / memory_v (elements); d.prm / d.mem_k / d.mem_v are not read
 };
 
 typedef int i32x4v __attribute__((ext_vector_type(4)));
@@ -70,7 +72,8 @@ __device__ __forceinline__ float cols_scale(int sumi, float dw, float mw, float 
 
 // INSTR: the measurement build (timeline stamps of wave 0 in sampled workgroups: tests/tools/cols_timeline.py), launched only
 // while option "timeline" is set; the production instantiation carries none of it.
-template <int QT, int EPI, bool INSTR = false>
+// BATCH (EPI_QKV only): the columns are single tokens of different sessions (BatchCols) instead of consecutive positions of one.
+template <int QT, int EPI, bool INSTR = false, bool BATCH = false>
 __global__ void __launch_bounds__(COLS_T) k_mmq_cols(const ColsArgs ca) {
     const DecMmvqArgs &a = ca.d;
     long long t_in = 0, t_pre = 0, t_dma = 0, t_issued = 0, t_staged = 0, t_loop = 0, t_sync2 = 0;
@@ -328,17 +331,24 @@ __global__ void __launch_bounds__(COLS_T) k_mmq_cols(const ColsArgs ca) {
         return v;
     };
     if constexpr (EPI == EPI_QKV) {
-        const int n_past = a.prm->n_past;
+        int n_past = 0;
+        if constexpr (!BATCH) n_past = a.prm->n_past;
         for (int i = tid; i < nlg * 8 * ncols; i += COLS_T) {
             const int c = i % ncols, pr = (i / ncols) & 7, lg = i / (ncols * 8);
             int sg, m0;
             group_rows(g_begin + lg, 0, sg, m0);
             const int m = m0 + 2 * pr;
             const float v0 = total(lg, 0, 2 * pr, c), v1 = total(lg, 0, 2 * pr + 1, c);
-            const int p = n_past + ca.col0 + c;
+            int p = n_past + ca.col0 + c;
+            __half *mem_k = a.mem_k, *mem_v = a.mem_v;
+            if constexpr (BATCH) {
+                p = ca.bc->pos[ca.col0 + c];
+                mem_k = ca.bc->mem_k[ca.col0 + c] + ca.kv_off;
+                mem_v = ca.bc->mem_v[ca.col0 + c] + ca.kv_off;
+            }
             if (sg == 2) {
-                a.mem_v[(int64_t)m * a.C + p] = __float2half_rn(v0);
-                a.mem_v[(int64_t)(m + 1) * a.C + p] = __float2half_rn(v1);
+                mem_v[(int64_t)m * a.C + p] = __float2half_rn(v0);
+                mem_v[(int64_t)(m + 1) * a.C + p] = __float2half_rn(v1);
             } else {
                 const int kk = (m % a.D) >> 1;
                 const float cs = ca.rope[(c * 64 + kk) * 2], sn = ca.rope[(c * 64 + kk) * 2 + 1];
@@ -347,8 +357,8 @@ __global__ void __launch_bounds__(COLS_T) k_mmq_cols(const ColsArgs ca) {
                     a.dst[(int64_t)c * ca.ldd + m] = r0;
                     a.dst[(int64_t)c * ca.ldd + m + 1] = r1;
                 } else {
-                    a.mem_k[(int64_t)p * a.Egqa + m] = __float2half_rn(r0);
-                    a.mem_k[(int64_t)p * a.Egqa + m + 1] = __float2half_rn(r1);
+                    mem_k[(int64_t)p * a.Egqa + m] = __float2half_rn(r0);
+                    mem_k[(int64_t)p * a.Egqa + m + 1] = __float2half_rn(r1);
                 }
             }
         }

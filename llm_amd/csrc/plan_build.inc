@@ -42,7 +42,8 @@ static bool plan_weights_resident(const LlamaMatch &m) {
     return true;
 }
 
-static std::vector<uint64_t> plan_signature(const LlamaMatch &m) {
+// session = false: what a batched step's graphs must share and its plan is cached by — the model and the shape, not the caches and result nodes
+static std::vector<uint64_t> plan_signature(const LlamaMatch &m, bool session = true) {
     std::vector<uint64_t> s;
     auto f2u = [](float f) { uint32_t u; memcpy(&u, &f, 4); return (uint64_t)u; };
     s.push_back((uint64_t)m.N);
@@ -50,11 +51,13 @@ static std::vector<uint64_t> plan_signature(const LlamaMatch &m) {
                        (uint64_t)m.V, (uint64_t)m.C, (uint64_t)m.n_dims, (uint64_t)m.wtype, f2u(m.eps),
                        f2u(m.freq_base), f2u(m.freq_scale), f2u(m.kq_scale)})
         s.push_back(v);
-    for (const ggml_tensor *t : {m.wte, m.norm, m.output, m.memory_k, m.memory_v, m.stage_in, m.stage_out})
-        s.push_back(t ? rec_id(t) : 0);
+    for (const ggml_tensor *t : {m.wte, m.norm, m.output, m.stage_in, m.stage_out}) s.push_back(t ? rec_id(t) : 0);
+    if (session)
+        for (const ggml_tensor *t : {m.memory_k, m.memory_v}) s.push_back(rec_id(t));
     for (auto &l : m.layers)
         for (const ggml_tensor *t : {l.attn_norm, l.wq, l.wk, l.wv, l.wo, l.ffn_norm, l.w1, l.w2, l.w3})
             s.push_back(rec_id(t));
+    if (!session) return s;
     s.push_back(m.logits ? (uint64_t)(uintptr_t)dev_ptr(m.logits) : 0);
     s.push_back(m.embedding ? (uint64_t)(uintptr_t)dev_ptr(m.embedding) : 0);
     return s;
@@ -123,7 +126,8 @@ static void xcd_labels_probe() {
     HIP_CHECK(hipFree(d));
     g.xcd_labels = ok ? 1 : 0;
 }
-static DecodePlan *build_plan(const LlamaMatch &m, std::vector<uint64_t> sig) {
+// batch: the plan of a batched step (m: its first graph's match with N = the columns)
+static DecodePlan *build_plan(const LlamaMatch &m, std::vector<uint64_t> sig, bool batch = false) {
     if (m.prompt && !m.kquant) {  // prompt plan: resident f16 copies of the GEMM weights, all or none (a model either fits twice or not)
         std::vector<const ggml_tensor *> ws;
         for (auto &l : m.layers)
@@ -155,8 +159,11 @@ static DecodePlan *build_plan(const LlamaMatch &m, std::vector<uint64_t> sig) {
     }
     if (m.stage_in) p->stage_in = (float *)dev_ptr(m.stage_in);
     if (m.stage_out) p->stage_out = (float *)dev_ptr(m.stage_out);
-    p->mem_k = (__half *)dev_ptr(m.memory_k);
-    p->mem_v = (__half *)dev_ptr(m.memory_v);
+    p->batch = batch;
+    if (!batch) {
+        p->mem_k = (__half *)dev_ptr(m.memory_k);
+        p->mem_v = (__half *)dev_ptr(m.memory_v);
+    }
     for (auto &l : m.layers) {
         DecodePlan::LW w;
         memset(&w, 0, sizeof(w));
@@ -173,8 +180,8 @@ static DecodePlan *build_plan(const LlamaMatch &m, std::vector<uint64_t> sig) {
         w.ffn_norm = (const float *)dev_ptr(l.ffn_norm);
         p->lw.push_back(w);
     }
-    if (m.embedding) p->emb_out = (float *)dev_ptr(m.embedding);
-    if (m.logits) p->logits_out = dev_ptr(m.logits);
+    if (m.embedding && !batch) p->emb_out = (float *)dev_ptr(m.embedding);
+    if (m.logits && !batch) p->logits_out = dev_ptr(m.logits);
     // one pool for all persistent activations
     size_t off = 0;
     auto take = [&](size_t bytes) { size_t o = off; off = (off + bytes + 255) & ~(size_t)255; return o; };
@@ -190,6 +197,7 @@ static DecodePlan *build_plan(const LlamaMatch &m, std::vector<uint64_t> sig) {
     const size_t o_epoch = take(256), o_gran = take(m.N == 1 ? (size_t)m.L * (size_t)((m.E + 2 * m.Egqa) / 2) * 8 : 0);
     const size_t o_dead = take(m.N == 1 ? (size_t)((m.E + 2 * m.Egqa) / 2) * 8 : 0);  // never written (tag 0): option test_fused_timeout
     const size_t o_ogran = take(m.N == 1 ? (size_t)m.L * (size_t)(m.E / 32) * OGRAN * 8 : 0);  // the heads' outputs as granules (WO form)
+    const size_t o_bcols = take(batch ? sizeof(BatchCols) : 0), o_blogits = take(batch ? R * m.V * 4 : 0), o_bemb = take(batch ? R * m.E * 4 : 0);
     const size_t o_prm = take(sizeof(DecParams)), o_rope = take(std::max<size_t>(8, R) * 128 * 4), o_xa = take(R * m.E * 4), o_xb = take(R * m.E * 4),
                  o_q = take(R * m.E * 4), o_gate = take(R * m.F * 4), o_elo = take(R * m.E / 2), o_ehi = take(R * m.E / 2),
                  o_ed = take(R * m.E / 32 * 4), o_es = take(R * m.E / 32 * 4), o_flo = take(R * m.F / 2),
@@ -211,6 +219,11 @@ static DecodePlan *build_plan(const LlamaMatch &m, std::vector<uint64_t> sig) {
     dev_malloc((void **)&p->pool, off, "a decode plan's activation pool");
     HIP_CHECK(hipMemsetAsync(p->pool, 0, off, g.stream));
     p->prm = (DecParams *)(p->pool + o_prm);
+    if (batch) {
+        p->bcols = (BatchCols *)(p->pool + o_bcols);
+        p->logits_out = p->pool + o_blogits;
+        p->emb_out = (float *)(p->pool + o_bemb);
+    }
     p->epoch = (unsigned *)(p->pool + o_epoch);
     p->hot = p->pool + o_hot;
     if (m.N == 1 && m.logits) { p->logits_alt = p->pool + o_lalt; p->emb_alt = (float *)(p->pool + o_ealt); }

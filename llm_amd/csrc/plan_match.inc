@@ -334,8 +334,7 @@ static bool match_llama_decode(ggml_cgraph *gr, LlamaMatch &m) {
         const MultiCols mc = multi_cols(m);
         MATCH(mc.qkv && mc.wo && mc.gate && mc.w2 && (mc.out || !m.output));
     } else if (m.N > 1) {  // multi-token plan (kernels/decode_big8.h): 8 Q8 columns of the widest row must fit LDS
-        const int64_t nbp = (std::max(m.E, m.F) / 32 + 63) / 64 * 64;
-        MATCH(g.opt_plan_multi && g.opt_big && 8 * nbp * 40 <= 150 * 1024 && (int64_t)m.N * std::max(m.E, m.F) / 32 <= 4 * BIG_T);
+        MATCH(g.opt_plan_multi && g.opt_big && multi_shape_ok(m, m.N));
         MATCH(m.n_past + m.N <= m.C);
     }
     for (auto &lw : m.layers)

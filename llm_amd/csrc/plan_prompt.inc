@@ -1,6 +1,7 @@
 // plan_prompt.inc — the launch sequences of evaluations of several tokens: plan_launch_multi (a chunk of 2..31 tokens, block
-// formats; captured like the decode plans) and plan_launch_prompt (a batch from mmq_min tokens on, launched eagerly).
-template <int QT, int EPI>
+// formats; captured like the decode plans), plan_launch_batch (the same launches for one token each of 2..8 sessions) and
+// plan_launch_prompt (a batch from mmq_min tokens on, launched eagerly).
+template <int QT, int EPI, bool BATCH = false>
 static void launch_big8(const Big8Args &a) {
     const int64_t Mtot = a.d.w[0].M + (EPI == EPI_QKV ? a.d.w[1].M + a.d.w[2].M : 0);
     const int64_t units = Mtot / (EPI == EPI_QKV ? 2 : 1);
@@ -10,12 +11,12 @@ static void launch_big8(const Big8Args &a) {
     const size_t lds = (size_t)8 * ((a.d.nb + 63) / 64 * 64) * 40;
     static DevOnce attr_set;
     if (attr_set.first()) {  // up to 150 KB of dynamic LDS
-        HIP_CHECK(hipFuncSetAttribute((const void *)k_mmvq_big8<QT, EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024));
+        HIP_CHECK(hipFuncSetAttribute((const void *)k_mmvq_big8<QT, EPI, BATCH>, hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024));
     }
-    hipLaunchKernelGGL((k_mmvq_big8<QT, EPI>), dim3(nwg), dim3(W * 64), lds, g.stream, a);
+    hipLaunchKernelGGL((k_mmvq_big8<QT, EPI, BATCH>), dim3(nwg), dim3(W * 64), lds, g.stream, a);
 }
 // ---- the same launches on the integer matrix cores (kernels/mmq_cols.h) ----
-template <int QT, int EPI>
+template <int QT, int EPI, bool BATCH = false>
 static void launch_cols(const ColsArgs &a0, int M_total) {
     ColsArgs a = a0;
     a.ngroups = M_total / 16 / (EPI == EPI_GATE ? 2 : 1);
@@ -24,15 +25,30 @@ static void launch_cols(const ColsArgs &a0, int M_total) {
     a.gr = a.ngroups % sh.G;
     static DevOnce attr_set;
     if (attr_set.first()) {
-        HIP_CHECK(hipFuncSetAttribute((const void *)k_mmq_cols<QT, EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024));
+        HIP_CHECK(hipFuncSetAttribute((const void *)k_mmq_cols<QT, EPI, false, BATCH>, hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024));
     }
-    if (a.ts) {  // measurement build (tests/tools/cols_timeline.py)
+    if (a.ts && !BATCH) {  // measurement build (tests/tools/cols_timeline.py)
         static DevOnce attr_set_i;
         if (attr_set_i.first())
             HIP_CHECK(hipFuncSetAttribute((const void *)k_mmq_cols<QT, EPI, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024));
         hipLaunchKernelGGL((k_mmq_cols<QT, EPI, true>), dim3(sh.G), dim3(COLS_T), sh.lds, g.stream, a);
     } else
-        hipLaunchKernelGGL((k_mmq_cols<QT, EPI>), dim3(sh.G), dim3(COLS_T), sh.lds, g.stream, a);
+        hipLaunchKernelGGL((k_mmq_cols<QT, EPI, false, BATCH>), dim3(sh.G), dim3(COLS_T), sh.lds, g.stream, a);
+}
+// k_attn_decode's batched form for layer il of a batched step: a grid of heads x columns, the whole context in its LDS arrays
+static void launch_attn_decode_batch(const DecodePlan *p, int il, int N, bool f16d) {
+    static DevOnce opted;
+    if (opted.first()) {
+        HIP_CHECK(hipFuncSetAttribute((const void *)k_attn_decode_batch<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ATTN_DECODE_LDS_MAX));
+        HIP_CHECK(hipFuncSetAttribute((const void *)k_attn_decode_batch<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ATTN_DECODE_LDS_MAX));
+    }
+    const LlamaMatch &m = p->m;
+    with_bool(f16d, [&](auto F16D) {
+        hipLaunchKernelGGL(k_attn_decode_batch<CT(F16D)>, dim3((unsigned)m.H, (unsigned)N), dim3(1024), attn_decode_lds(m.C, m.D), g.stream,
+                           (const float *)p->q, (const BatchCols *)p->bcols, p->kv_off(il), m.kq_scale, (int)m.D, (int)(m.H / m.Hkv), m.Egqa,
+                           m.C, p->e_lo, p->e_hi, p->e_d, p->e_s, (int)m.H, m.C, p->e_dT, p->e_sT);
+    });
+    HIP_CHECK(hipGetLastError());
 }
 // The multi-token plan: a prompt chunk of 2..8 tokens (InferenceSession::feed_prompt at the default n_batch = 8) as
 // 8 launches per layer — k_rmsnorm_quant (N rows), k_mmvq_big8<QKV>, k_attn_decode (grid heads x N: query n attends
@@ -40,7 +56,10 @@ static void launch_cols(const ColsArgs &a0, int M_total) {
 // (w2) — every weight matrix streamed once per chunk instead of once per token-column pass of the generic executor.
 // Each mat-vec runs on k_mmq_cols in passes of 8 columns instead where its shape allows (multi_cols; chunks of 9..31 tokens
 // only so).
-static void plan_launch_multi(DecodePlan *p) {
+// batch: the N columns are one token each of N different sessions of the model (DecodePlan::bcols says where each sits) instead of
+// N consecutive positions of one: the same launches, but the three that place a column in a cache — the RoPE tables, the
+// wq|wk|wv epilogue and the attention — in their batched forms.  Everything else is column-local and does not know the difference.
+static void plan_launch_chunk(DecodePlan *p, const bool batch) {
     const LlamaMatch &m = p->m;
     LaunchCtx cx;  // everything is launched; the timeline has one record per k_mmq_cols launch, in launch order
     const int N = m.N, qt = qt_of(m.wtype);
@@ -101,8 +120,16 @@ static void plan_launch_multi(DecodePlan *p) {
     auto block = [&](int kind, auto EPI, bool on_cols, const Big8Args &a, int M_total, const float *dT, const int *sT) {
         const int64_t nb = a.d.nb;
         const double bytes = (double)M_total * nb * bb;
+        constexpr bool qkv = CT(EPI) == EPI_QKV;  // the one epilogue with a batched form
         if (!on_cols) {
-            cx.mmvq(kind, bytes, [&] { with_qt(qt, [&](auto QT) { launch_big8<CT(QT), CT(EPI)>(a); }); });
+            cx.mmvq(kind, bytes, [&] {
+                with_qt(qt, [&](auto QT) {
+                    if constexpr (qkv) {
+                        if (batch) return launch_big8<CT(QT), CT(EPI), true>(a);
+                    }
+                    launch_big8<CT(QT), CT(EPI)>(a);
+                });
+            });
             return;
         }
         for (int c0 = 0; c0 < N; c0 += 8) {
@@ -123,7 +150,15 @@ static void plan_launch_multi(DecodePlan *p) {
             c.ts = cx.next_ts();
             c.ts_wgs = g.timeline_wgs;
             c.hot = g.hot_line;
-            cx.mmvq(kind, bytes, [&] { with_qt(qt, [&](auto QT) { launch_cols<CT(QT), CT(EPI)>(c, M_total); }); });
+            c.bc = a.bc; c.kv_off = a.kv_off;
+            cx.mmvq(kind, bytes, [&] {
+                with_qt(qt, [&](auto QT) {
+                    if constexpr (qkv) {
+                        if (batch) return launch_cols<CT(QT), CT(EPI), true>(c, M_total);
+                    }
+                    launch_cols<CT(QT), CT(EPI)>(c, M_total);
+                });
+            });
         }
     };
     if (!m.wte) {
@@ -135,8 +170,12 @@ static void plan_launch_multi(DecodePlan *p) {
         });
     }
     // RoPE tables of the chunk's N positions, shared by all layers
-    hipLaunchKernelGGL(k_rope_table, dim3((unsigned)N), dim3(128), 0, g.stream, (const DecParams *)p->prm, theta_scale,
-                       m.freq_scale, (int)(m.D >> 1), p->rope);
+    if (batch)
+        hipLaunchKernelGGL(k_rope_table_batch, dim3((unsigned)N), dim3(128), 0, g.stream, (const BatchCols *)p->bcols, theta_scale,
+                           m.freq_scale, (int)(m.D >> 1), p->rope);
+    else
+        hipLaunchKernelGGL(k_rope_table, dim3((unsigned)N), dim3(128), 0, g.stream, (const DecParams *)p->prm, theta_scale,
+                           m.freq_scale, (int)(m.D >> 1), p->rope);
     HIP_CHECK(hipGetLastError());
     for (int il = 0; il < m.L; il++) {
         const DecodePlan::LW &w = p->lw[il];
@@ -148,11 +187,18 @@ static void plan_launch_multi(DecodePlan *p) {
             a.d.x = actE; a.d.nb = nbE; a.d.dst = p->q; a.d.prm = p->prm; a.d.mem_k = p->mem_k_at(il); a.d.mem_v = p->mem_v_at(il);
             a.d.Egqa = m.Egqa; a.d.C = m.C; a.d.D = (int)m.D; a.d.theta_scale = theta_scale; a.d.freq_scale = m.freq_scale;
             a.ncols = N; a.ldd = E; a.ldr = E; a.rope = p->rope;
+            if (batch) {
+                a.d.mem_k = a.d.mem_v = nullptr;
+                a.bc = p->bcols; a.kv_off = p->kv_off(il);
+            }
             block(0, std::integral_constant<int, EPI_QKV>{}, cols.qkv, a, (int)(E + 2 * m.Egqa), p->e_dT, p->e_sT);
         }
         {
             Timed tm(GGML_HIP_KCLASS_ATTN, (double)N * (m.n_past + N) * m.Egqa * 4.0);
-            launch_attn_decode(p, il, N, m.C, f16d, nullptr, nullptr, p->e_dT, p->e_sT);
+            if (batch)
+                launch_attn_decode_batch(p, il, N, f16d);
+            else
+                launch_attn_decode(p, il, N, m.C, f16d, nullptr, nullptr, p->e_dT, p->e_sT);
         }
         {
             Big8Args a;
@@ -198,6 +244,9 @@ static void plan_launch_multi(DecodePlan *p) {
         block(4, std::integral_constant<int, EPI_STORE>{}, cols.out, a, (int)m.V, p->e_dT, p->e_sT);
     }
 }
+static void plan_launch_multi(DecodePlan *p) { plan_launch_chunk(p, false); }
+// One decode step of N = 2..8 sessions of one model as one pass over the weights (ggml_hip_decode_batch, plan_run.inc decode_batch)
+static void plan_launch_batch(DecodePlan *p) { plan_launch_chunk(p, true); }
 
 // ---------------------------------------------------------------------------------------------------
 // The prompt plan: a batch of N >= mmq_min tokens (crates/llm-base/src/inference_session.rs:315-316 feeds n_batch tokens

@@ -118,6 +118,29 @@ static bool prepare_decode_plan(ggml_cgraph *gr) {
     return true;
 }
 
+// the cached plan of signature `sig`, built for `m` if there is none; either way it holds m afterwards: the same device buffers, the
+// fresh tensor pointers of this evaluation (n_past, embd).  Also where captured graphs of another slot count of the device go.
+static DecodePlan *find_or_build_plan(const LlamaMatch &m, const std::vector<uint64_t> &sig, bool batch = false) {
+    const uint64_t wgen = g_dev_wgen[g.device & 63].load(std::memory_order_acquire);
+    {   // plans built before some weight record of this device was freed (perhaps by a sibling slot): gone before anything matches them
+        bool stale = false;
+        for (auto *q : g_plans) stale = stale || q->wgen != wgen;
+        if (stale) drop_all_plans();
+    }
+    DecodePlan *p = nullptr;
+    for (auto *q : g_plans)
+        if (q->sig == sig) p = q;
+    if (!p) {
+        if (g_plans.size() >= 32) drop_all_plans();
+        p = build_plan(m, sig, batch);
+        p->wgen = wgen;
+        g_plans.push_back(p);
+    } else {
+        p->m = m;
+    }
+    return p;
+}
+
 static bool try_decode_plan(ggml_cgraph *gr, bool defer_wait = false) {
     g.chain_plan = nullptr;  // any new graph ends the chainable state; a single-token plan run re-arms it below
     if (!g.opt_plan) return false;
@@ -162,23 +185,7 @@ static bool try_decode_plan(ggml_cgraph *gr, bool defer_wait = false) {
             if (!ok) return false;
             m = m2;
         }
-        std::vector<uint64_t> sig = plan_signature(m);
-        const uint64_t wgen = g_dev_wgen[g.device & 63].load(std::memory_order_acquire);
-        {   // plans built before some weight record of this device was freed (perhaps by a sibling slot): gone before anything matches them
-            bool stale = false;
-            for (auto *q : g_plans) stale = stale || q->wgen != wgen;
-            if (stale) drop_all_plans();
-        }
-        for (auto *q : g_plans)
-            if (q->sig == sig) p = q;
-        if (!p) {
-            if (g_plans.size() >= 32) drop_all_plans();
-            p = build_plan(m, sig);
-            p->wgen = wgen;
-            g_plans.push_back(p);
-        } else {
-            p->m = m;  // same devices buffers, fresh tensor pointers of this evaluation (n_past, embd)
-        }
+        p = find_or_build_plan(m, plan_signature(m));
     }
     const uint64_t t1 = now_ns();
     // ---- speculative next token: is this evaluation the one the device is already running? ----
@@ -398,5 +405,103 @@ static int decode_greedy_chain(ggml_cgraph *last, int n, int32_t *out_tokens, fl
     p->replays += use_graph ? (uint64_t)n : 0;
     g.stat_plan_tokens += (uint64_t)n;
     g.chain_plan = nullptr;  // the caller's next evaluation re-arms it
+    return 0;
+}
+
+// ggml_hip_decode_batch: one decode step of B = 2..8 single-token LLaMA graphs of ONE model, each the reference's unchanged graph for
+// its own session (own memory_k / memory_v, own n_past, own token), as ONE pass over the weights: the chunk plan's launches
+// (plan_launch_batch) with column c placed by the per-column table instead of "position n_past + c of one cache".  One plan per
+// (B, model, context) and one hipGraph of it; a step uploads DecParams (the token ids) and BatchCols (positions, caches) and replays.
+// -1 with nothing executed when the graphs are not that; the caller then computes them one by one.
+static int decode_batch(ggml_cgraph *const *graphs, int B) {
+    ensure_init();
+    finish_pending();
+    spec_cancel();
+    g.chain_plan = nullptr;
+    if (PrepMatch *pm = (PrepMatch *)g.prep) pm->gr = nullptr;
+    if (!g.opt_plan || !g.opt_plan_batch) return -1;
+    const uint64_t t0 = now_ns();
+    std::vector<LlamaMatch> ms((size_t)B);
+    std::vector<uint64_t> sig;
+    for (int c = 0; c < B; c++) {
+        LlamaMatch &m = ms[(size_t)c];
+        if (!match_llama_decode(graphs[c], m)) return -1;
+        if (m.N != 1 || m.prompt || m.kquant || !m.wte || !m.output || !m.embd || !m.logits || !m.embedding) return -1;
+        if (m.n_past >= m.C || qt_of(m.wtype) < 0) return -1;  // (f16 K/V, D, E, F: the matcher's own preconditions)
+        for (const ggml_tensor *t : {m.memory_k, m.memory_v}) {  // a session of another slot keeps its cache to itself (extra_of would abort)
+            const DevTensor *e = (const DevTensor *)t->extra;
+            if (e && e->magic == 0x48495054 && e->slot != g_cur_slot()) return -1;
+        }
+    }
+    // the whole context in k_attn_decode's LDS arrays (a column may sit anywhere in it), 8 Q8 columns of the widest row in k_mmvq_big8's
+    if (attn_decode_lds(ms[0].C, ms[0].D) > ATTN_DECODE_LDS_MAX || !multi_shape_ok(ms[0], B)) return -1;
+    ws_reset();
+    for (int c = 0; c < B; c++) {
+        const LlamaMatch &m = ms[(size_t)c];
+        if (!plan_weights_resident(m)) {  // first evaluation of a model or a session: its leaves go up as for any graph
+            upload_inputs(graphs[c]);
+            if (!plan_weights_resident(m)) return -1;
+        }
+        std::vector<uint64_t> s = plan_signature(m, false);  // same weight records, dims, context, RoPE parameters
+        if (c == 0) sig = std::move(s);
+        else if (s != sig) return -1;
+    }
+    std::vector<__half *> mk((size_t)B), mv((size_t)B);
+    for (int c = 0; c < B; c++) {
+        mk[(size_t)c] = (__half *)dev_ptr(ms[(size_t)c].memory_k);
+        mv[(size_t)c] = (__half *)dev_ptr(ms[(size_t)c].memory_v);
+        for (int d = 0; d < c; d++)
+            if (mk[(size_t)d] == mk[(size_t)c] || mv[(size_t)d] == mv[(size_t)c]) return -1;  // one session twice: two columns, one cache row
+    }
+    LlamaMatch mb = ms[0];  // the plan's shape: B columns
+    mb.N = B;
+    mb.n_past = 0;
+    sig[0] = (uint64_t)B;
+    sig.push_back(0x6261746368ull);  // "batch": never a chunk plan's signature
+    DecodePlan *p = find_or_build_plan(mb, sig, true);
+    for (int c = 0; c < B; c++) mb.n_past = std::max(mb.n_past, ms[(size_t)c].n_past);
+    p->m.n_past = mb.n_past;  // (the attention's byte count for the timing books)
+    const uint64_t t1 = now_ns();
+    DecParams hp;
+    BatchCols hb;
+    memset(&hp, 0, sizeof(hp));
+    memset(&hb, 0, sizeof(hb));
+    for (int c = 0; c < B; c++) {
+        const LlamaMatch &m = ms[(size_t)c];
+        hp.tokens[c] = ((const int32_t *)m.embd->data)[0];
+        if (hp.tokens[c] < 0 || hp.tokens[c] >= m.wte->ne[1]) die("token id %d out of range", hp.tokens[c]);
+        hb.pos[c] = m.n_past;
+        hb.mem_k[c] = mk[(size_t)c];
+        hb.mem_v[c] = mv[(size_t)c];
+    }
+    hp.n_past = hb.pos[0];
+    hp.token = hp.tokens[0];
+    h2d_small((char *)p->prm, &hp, sizeof(hp));
+    h2d_small((char *)p->bcols, &hb, sizeof(hb));
+    if (g.opt_graph && !g.timing.on) {
+        if (!p->exec_v[0]) capture_into(&p->graph_v[0], &p->exec_v[0], [&] { plan_launch_batch(p); });
+        HIP_CHECK(hipGraphLaunch(p->exec_v[0], g.stream));
+        p->replays++;
+    } else {
+        plan_launch_batch(p);
+    }
+    // every graph's results where an evaluation of that graph alone leaves them (queue_results): the logits in the node's host data
+    // (CPU-backend node) or its device copy, the embedding row in the node's device copy and host data
+    for (int c = 0; c < B; c++) {
+        const LlamaMatch &m = ms[(size_t)c];
+        const char *lrow = p->logits_out + (size_t)c * m.V * 4, *erow = (const char *)p->emb_out + (size_t)c * m.E * 4;
+        if (m.logits->backend == GGML_BACKEND_CPU) d2h_queue(m.logits->data, lrow, (size_t)m.V * 4);
+        else HIP_CHECK(hipMemcpyAsync(dev_ptr(m.logits), lrow, (size_t)m.V * 4, hipMemcpyDeviceToDevice, g.stream));
+        HIP_CHECK(hipMemcpyAsync(dev_ptr(m.embedding), erow, (size_t)m.E * 4, hipMemcpyDeviceToDevice, g.stream));
+        if (m.embedding->data) d2h_queue(m.embedding->data, erow, (size_t)m.E * 4);
+    }
+    const uint64_t t2 = now_ns();
+    g.stat_plan_tokens += (uint64_t)B;
+    g.stat_batch_tokens += (uint64_t)B;
+    g.stat_batch_steps++;
+    d2h_finish();
+    g.ns_match += t1 - t0;
+    g.ns_launch += t2 - t1;
+    g.ns_wait += now_ns() - t2;
     return 0;
 }

@@ -1,11 +1,13 @@
 // plan_*.inc — the fused LLaMA plans.  The graph that crates/models/llama/src/lib.rs:166-362 builds (37 nodes per layer +
 // get_rows + final norm/mul/lm_head, rebuilt by the caller for EVERY evaluation: crates/llm-base/src/inference_session.rs:230)
-// is recognised as a whole and executed as one of four launch sequences over the same cached DecodePlan:
+// is recognised as a whole and executed as one of five launch sequences over the same cached DecodePlan:
 //   single-token decode, block formats (plan_launch_all): 3 launches per layer with wq|wk|wv + attention + wo fused, 5 without;
 //   single-token decode and chunks of up to 31 tokens, K-quants (plan_launch_k): 10-13 launches per layer;
 //   a chunk of 2..31 tokens, block formats (plan_launch_multi): 8 launches per layer and pass of 8 columns;
-//   a prompt batch (plan_launch_prompt): 13 launches per layer around the matrix-core GEMMs, launched eagerly.
-// The first three are captured once in a hipGraph per attention variant and replayed for the following tokens with only
+//   a prompt batch (plan_launch_prompt): 13 launches per layer around the matrix-core GEMMs, launched eagerly;
+//   one token each of 2..8 sessions of one model (plan_launch_batch; ggml_hip_decode_batch hands over their graphs together): the
+//   chunk's launches with a per-column position and cache.
+// The first three and the last are captured once in a hipGraph per attention variant and replayed for the following tokens with only
 // {n_past, token} changing in a device-side parameter block.  One file per concern, included in this order from
 // backend_executor.inc inside hip_backend.hip's anonymous namespace; nothing needs a forward declaration:
 //   plan_shapes.inc  LlamaMatch, DecodePlan and every "which kernel, which grid for which shape" decision (plain host functions
@@ -13,8 +15,8 @@
 //   plan_match.inc   the structural graph matcher
 //   plan_build.inc   weights, signature and activation pool of a plan
 //   plan_decode.inc  the single-token launchers: plan_launch_all, plan_launch_k
-//   plan_prompt.inc  plan_launch_multi, prompt_attention, plan_launch_prompt
-//   plan_run.inc     capture and replay, speculation, the fused-timeout re-run, the greedy chain
+//   plan_prompt.inc  plan_launch_multi, plan_launch_batch, prompt_attention, plan_launch_prompt
+//   plan_run.inc     capture and replay, speculation, the fused-timeout re-run, the greedy chain, the batched step
 //
 // The matcher is structural (it follows src[] pointers from the logits back to get_rows and checks every view's
 // shape/stride/offset against the KV-cache layout), so any graph that is not exactly the reference's LLaMA
@@ -69,6 +71,11 @@ struct DecodePlan {
     __half *mem_k = nullptr, *mem_v = nullptr;
     __half *mem_k_at(int il) const { return mem_k + (size_t)il * m.C * m.Egqa; }  // layer il's part of the caches
     __half *mem_v_at(int il) const { return mem_v + (size_t)il * m.C * m.Egqa; }
+    int64_t kv_off(int il) const { return (int64_t)il * m.C * m.Egqa; }  // the same offset, for caches named by a table:
+    // a batched step's plan (plan_launch_batch; m is its first graph's match with N = the columns): the per-column table on the device,
+    // uploaded with prm for every step.  Its logits_out / emb_out are rows of the pool (one per column), not a graph's nodes; mem_k / mem_v are unused.
+    bool batch = false;
+    BatchCols *bcols = nullptr;
     // persistent activations
     char *pool = nullptr;
     DecParams *prm = nullptr;
@@ -335,6 +342,11 @@ static bool kbig_ok(const DecodePlan *p) {  // K matrices whose rows of a wave f
         for (const KWeight *w : {&l.wq, &l.wk, &l.wv, &l.wo, &l.w1, &l.w2, &l.w3})
             if (!ok(*w)) return false;
     return !p->m.output || ok(p->k_output);
+}
+// what the launches of the multi-token plan on k_mmvq_big8 need of N = 2..8 columns (kernels/decode_big8.h): 8 Q8 columns of the widest row in LDS
+static bool multi_shape_ok(const LlamaMatch &m, int N) {
+    const int64_t nbp = (std::max(m.E, m.F) / 32 + 63) / 64 * 64;
+    return 8 * nbp * 40 <= 150 * 1024 && (int64_t)N * std::max(m.E, m.F) / 32 <= 4 * BIG_T;
 }
 // ---- the same launches on the integer matrix cores (kernels/mmq_cols.h) ----
 struct ColsShape {

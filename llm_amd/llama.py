@@ -98,6 +98,10 @@ def _lib():
         L.llm_session_perplexity.restype = C.c_int
         L.llm_session_perplexity.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int32, C.c_int, C.c_void_p, C.c_int,
                                              C.c_void_p]
+        L.llm_evaluate_batch.restype = C.c_int
+        L.llm_evaluate_batch.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p, C.c_int, C.c_void_p]
+        L.llm_infer_next_tokens_greedy_batch.restype = C.c_int
+        L.llm_infer_next_tokens_greedy_batch.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_void_p]
         _bound = True
     return L
 
@@ -224,6 +228,32 @@ class Llama:
         s = Session.__new__(Session)
         s.model, s.ptr = self, ptr
         return s
+
+    def evaluate_batch(self, sessions, tokens):
+        """One decode step of several sessions of this model, tokens[i] for sessions[i], as ONE pass over the weights where the
+        backend can (llm_evaluate_batch: 2..8 sessions of a block-format model with f16 K/V; anything else is evaluated one
+        session after the other, with the same results).  Returns (ran_batched, logits [B, n_vocab]); every session ends as
+        after evaluate([token]).  ValueError, with nothing evaluated: a session listed twice, of another model or device slot,
+        a token outside the vocabulary, a session whose context is full."""
+        tokens = np.ascontiguousarray(tokens, dtype=np.int32)
+        if tokens.size != len(sessions):
+            raise ValueError("evaluate_batch: one token per session")
+        ptrs = (C.c_void_p * len(sessions))(*[s.ptr for s in sessions])
+        logits = np.zeros((len(sessions), self.hp["n_vocab"]), np.float32)
+        rc = _lib().llm_evaluate_batch(self.ptr, ptrs, tokens.ctypes.data, len(sessions), logits.ctypes.data)
+        if rc < 0:
+            raise ValueError("llm_evaluate_batch: bad arguments (nothing was evaluated)")
+        return bool(rc), logits
+
+    def infer_next_tokens_batch(self, sessions):
+        """Session.infer_next_token for several sessions of this model in one such step (llm_infer_next_tokens_greedy_batch):
+        returns (ran_batched, ids)."""
+        ptrs = (C.c_void_p * len(sessions))(*[s.ptr for s in sessions])
+        out = np.zeros(len(sessions), np.int32)
+        rc = _lib().llm_infer_next_tokens_greedy_batch(self.ptr, ptrs, len(sessions), out.ctypes.data)
+        if rc < 0:
+            raise ValueError("llm_infer_next_tokens_greedy_batch: bad arguments (nothing was evaluated)")
+        return bool(rc), out
 
     def free(self):
         if self.ptr:
