@@ -662,6 +662,14 @@ GGML_API int ggml_hip_debug_mat_vec_kbig(const struct ggml_tensor *w0, const str
                                          int xsrc, int epi, const float *x, const float *xw, float eps, const float *res, float *out,
                                          float *y_out, int n_past, int D, float freq_base, float freq_scale, int64_t C,
                                          uint16_t *mem_k, uint16_t *mem_v);
+/* ... and of the F16 plan's mat-vec k_mmvq_f16 (kernels/decode_f16.h), xsrc / epi as for _kbig, with ncols columns as a chunk of
+ * ncols tokens launches them: x [ncols][K], xw [K] (NORM) or [ncols][K] (SILU_MUL), res [ncols][M0], out [ncols][M], y_out [ncols][K];
+ * QKV: column c sits at position n_past + c.  w0 (w1, w2): contiguous F16 matrices.  -1 for K % 8 != 0, an odd row count with QKV
+ * and whatever else the plan would not launch. */
+GGML_API int ggml_hip_debug_mat_vec_f16(const struct ggml_tensor *w0, const struct ggml_tensor *w1, const struct ggml_tensor *w2,
+                                        int xsrc, int epi, const float *x, const float *xw, float eps, const float *res, float *out,
+                                        float *y_out, int n_past, int D, float freq_base, float freq_scale, int64_t C,
+                                        uint16_t *mem_k, uint16_t *mem_v, int ncols);
 /* Extension (layer split inside one process): slot `slot` enqueues on slot `with_slot`'s stream (with_slot < 0: on its own again).
  * Only for slots of ONE physical GPU whose work never overlaps — the stages of one split session: a wait on another queue's event
  * costs tens of microseconds per stage boundary on this runtime, the same wait inside one queue nothing.  1 = now shared, 0 = not

@@ -84,7 +84,7 @@ struct Backend {
     size_t ws_off = 0;  // offset in the last chunk
     Timing timing;
     int opt_fuse = 1, opt_plan = 1, opt_plan_k = 1, opt_plan_multi = 1, opt_plan_prompt = 1, opt_graph = 1, opt_big = 1, opt_kbig = 1;
-    int opt_chain_k = 0, opt_prepare = 1, opt_plan_batch = 1;
+    int opt_chain_k = 0, opt_prepare = 1, opt_plan_batch = 1, opt_plan_f16 = 1;
     int opt_fuse_attn = 1, opt_fuse_wo = 1, opt_warm_mb = 24, opt_affine = 1;
     int opt_act_quant = 0, opt_mmq_i8 = 0;
     int opt_mmq_min = 32, opt_k_prompt_min = 12, opt_mmq_fuse = 3, opt_mmq_cols = 1, opt_mmq_t256 = 1, opt_attn_fused = 1;
@@ -174,6 +174,8 @@ static const OptRow g_options[] = {
     {"plan", &Backend::opt_plan, OPT_ENV},  // recognise the LLaMA decode graph and run the fused plan
     // ... and the K plan for a model whose matrices are K-quants (plan_decode.inc plan_launch_k); 2 = one launch per matrix
     {"plan_k", &Backend::opt_plan_k, OPT_ENV | OPT_DROPS},
+    // ... and the F16 plan for a model whose matrices are F16 (plan_decode.inc plan_launch_f16); 0 = such a model runs node by node
+    {"plan_f16", &Backend::opt_plan_f16, OPT_ENV | OPT_DROPS},
     {"plan_multi", &Backend::opt_plan_multi, OPT_ENV | OPT_DROPS},    // fused plan for prompt chunks of 2..8 tokens (kernels/decode_big8.h)
     {"plan_prompt", &Backend::opt_plan_prompt, OPT_ENV | OPT_DROPS},  // fused plan for prompt batches of >= mmq_min tokens (kernels/prompt.h)
     // ggml_hip_decode_batch: one decode step of 2..8 sessions of one model as one pass over the weights (0: it answers -1, the caller steps them one by one)

@@ -407,6 +407,108 @@ int ggml_hip_debug_mat_vec_kbig(const struct ggml_tensor *w0, const struct ggml_
     return 0;
 }
 
+// k_mmvq_f16: w0 (w1, w2) F16 matrices of width K (device copies where they have one, else uploaded here).  Pairs (plan_launch_f16),
+// xsrc KX_* / epi KE_* as for ggml_hip_debug_mat_vec_kbig: KX_NORM + KE_QKV (wq, wk, wv), KX_NORM + KE_ROW (1-3 matrices), KX_NORM +
+// KE_GATE (w1, w3), KX_F32 / KX_SILU_MUL + KE_ROW (one matrix, res nullable).  ncols columns, as a chunk of ncols tokens launches them
+// (passes of 8 / 4 / 2 / 1): x [ncols][K]; xw [K] (KX_NORM) or [ncols][K] (KX_SILU_MUL); res [ncols][M0]; out [ncols][M] with M = M0 +
+// M1 + M2 (KE_ROW: the matrices' rows one after the other per column) or M0 (KE_GATE; KE_QKV: Q); y_out [ncols][K].  QKV: column c sits
+// at position n_past + c.  Everything else as for ggml_hip_debug_mat_vec_kbig.
+int ggml_hip_debug_mat_vec_f16(const struct ggml_tensor *w0, const struct ggml_tensor *w1, const struct ggml_tensor *w2, int xsrc,
+                               int epi, const float *x, const float *xw, float eps, const float *res, float *out, float *y_out,
+                               int n_past, int D, float freq_base, float freq_scale, int64_t C, uint16_t *mem_k, uint16_t *mem_v,
+                               int ncols) {
+    SlotLock lk;
+    ensure_init();
+    finish_pending();
+    const ggml_tensor *ts[3] = {w0, w1, w2};
+    const int nw = epi == KE_QKV ? 3 : epi == KE_GATE ? 2 : !w1 ? 1 : !w2 ? 2 : 3;
+    if (!x || !w0 || !out || ncols < 1 || ncols > MULTI_MAX_N || (xsrc != KX_F32 && !xw)) return -1;
+    if (xsrc != KX_NORM && nw > 1) return -1;  // several matrices: only behind the norm
+    if (res && (epi != KE_ROW || nw > 1)) return -1;
+    const int64_t K = w0->ne[0];
+    int64_t Ms[3] = {0, 0, 0};
+    for (int i = 0; i < nw; i++) {
+        const ggml_tensor *t = ts[i];
+        if (!t || t->type != GGML_TYPE_F16 || t->ne[0] != K || t->ne[2] != 1 || t->ne[3] != 1 || !ggml_is_contiguous(t)) return -1;
+        Ms[i] = t->ne[1];
+    }
+    if (K % 8 != 0) return -1;  // (before anything is uploaded: rows of 16-byte chunks)
+    if (epi == KE_QKV && (!mem_k || !mem_v || D < 2 || D % 2 || D > 256 || Ms[0] % D || Ms[1] % D || Ms[1] != Ms[2] || n_past < 0 ||
+                          n_past + ncols > C))
+        return -1;
+    std::vector<char *> owned;
+    debug_hot_line();
+    F16W fw[3];
+    for (int i = 0; i < nw; i++) {
+        const ggml_tensor *t = ts[i];
+        DevTensor *e = extra_of(t);
+        if (!e) e = find_tensor((uintptr_t)t->data);
+        const char *d = e && !e->soa && !e->ksoa ? e->dev + ((uintptr_t)t->data - e->host) : debug_buf(ggml_nbytes(t), t->data, owned);
+        fw[i] = F16W{(const __half *)d, (int64_t)t->nb[1] / 2, Ms[i]};
+    }
+    if (!f16_launch_ok(nw, fw, K, xsrc, epi)) {
+        for (char *b : owned) HIP_CHECK(hipFree(b));
+        return -1;
+    }
+    const size_t nx = (size_t)ncols * K * 4;
+    char *dx = debug_buf(nx, x, owned);
+    char *dxw = xw ? debug_buf(xsrc == KX_SILU_MUL ? nx : (size_t)K * 4, xw, owned) : nullptr;
+    char *dres = res ? debug_buf((size_t)ncols * Ms[0] * 4, res, owned) : nullptr;
+    const int64_t Mrow = epi == KE_ROW ? Ms[0] + Ms[1] + Ms[2] : Ms[0];
+    const size_t n_out = (size_t)ncols * Mrow * 4;
+    char *dout = debug_buf(n_out, nullptr, owned);
+    char *dy = (xsrc == KX_NORM && y_out) ? debug_buf(nx, nullptr, owned) : nullptr;
+    const F16Src src{xsrc, (const float *)dx, (const float *)dxw, eps, epi == KE_ROW ? (float *)dy : nullptr};
+    char *dk = nullptr, *dv = nullptr;
+    const size_t nkv = epi == KE_QKV ? (size_t)C * Ms[1] * 2 : 0;
+    if (epi == KE_QKV) {
+        DecParams hp;
+        memset(&hp, 0, sizeof(hp));
+        hp.n_past = n_past;
+        DecParams *prm = (DecParams *)debug_buf(sizeof(DecParams), &hp, owned);
+        float *rope = (float *)debug_buf((size_t)ncols * 128 * 4, nullptr, owned);
+        hipLaunchKernelGGL(k_rope_table, dim3((unsigned)ncols), dim3(128), 0, g.stream, (const DecParams *)prm, powf(freq_base, -2.0f / (float)D),
+                           freq_scale, D >> 1, rope, (unsigned *)nullptr);
+        HIP_CHECK(hipGetLastError());
+        dk = debug_buf(nkv, mem_k, owned);
+        dv = debug_buf(nkv, mem_v, owned);
+        F16Qkv qa;
+        memset(&qa, 0, sizeof(qa));
+        qa.rope = rope; qa.prm = prm; qa.mem_k = (__half *)dk; qa.mem_v = (__half *)dv; qa.Egqa = Ms[1]; qa.C = C; qa.D = D;
+        float *ds3[3] = {(float *)dout, nullptr, nullptr};
+        const int kinds[3] = {0, 1, 2};
+        launch_f16(3, fw, ds3, K, src, nullptr, ncols, KE_QKV, &qa, kinds);
+    } else if (epi == KE_GATE) {
+        float *ds2[2] = {(float *)dout, nullptr};
+        launch_f16(2, fw, ds2, K, src, nullptr, ncols, KE_GATE);
+    } else if (nw == 1) {
+        float *ds1[1] = {(float *)dout};
+        launch_f16(1, fw, ds1, K, src, (const float *)dres, ncols);
+    } else {  // several matrices behind the norm: the kernel writes [ncols][M_i] per matrix; gathered into [ncols][M0 + M1 + M2] here
+        float *ds[3] = {nullptr, nullptr, nullptr};
+        for (int i = 0; i < nw; i++) ds[i] = (float *)debug_buf((size_t)ncols * Ms[i] * 4, nullptr, owned);
+        launch_f16(nw, fw, ds, K, src, nullptr, ncols);
+        int64_t at = 0;
+        for (int i = 0; i < nw; i++) {
+            HIP_CHECK(hipMemcpy2DAsync(dout + at * 4, (size_t)Mrow * 4, ds[i], (size_t)Ms[i] * 4, (size_t)Ms[i] * 4, (size_t)ncols, hipMemcpyDeviceToDevice, g.stream));
+            at += Ms[i];
+        }
+    }
+    if (dy && epi != KE_ROW) {  // the normed rows of the same staging code: the tap of a KE_ROW launch of w0
+        float *ds1[1] = {(float *)debug_buf((size_t)ncols * Ms[0] * 4, nullptr, owned)};
+        launch_f16(1, fw, ds1, K, F16Src{KX_NORM, (const float *)dx, (const float *)dxw, eps, (float *)dy}, nullptr, ncols);
+    }
+    d2h_queue(out, dout, n_out + DEBUG_GUARD);
+    if (dy) d2h_queue(y_out, dy, nx + DEBUG_GUARD);
+    if (dk) {
+        d2h_queue(mem_k, dk, nkv + DEBUG_GUARD);
+        d2h_queue(mem_v, dv, nkv + DEBUG_GUARD);
+    }
+    d2h_finish();
+    for (char *b : owned) HIP_CHECK(hipFree(b));
+    return 0;
+}
+
 // Test hook: the fused prompt attention in the form plan_launch_prompt launches it (plan_prompt.inc: prompt_attention(true, ...)
 // with x16_out, rope and q_part set): q_raw [N][E] f32 the un-rotated wq product, q_raw2 (nullable) its second K-split partial —
 // uploaded N * E floats behind the first, q_part = N * E as the plan's qkv_stride is a distance inside one buffer; rope [N][128]

@@ -56,6 +56,7 @@
 #include "kernels/decode_attn_split.h"
 #include "kernels/kquant_plan.h"
 #include "kernels/kquant_big.h"
+#include "kernels/decode_f16.h"
 #include "kernels/prompt.h"
 #include "kernels/prompt_attn.h"
 #include "kernels/flash_attn.h"

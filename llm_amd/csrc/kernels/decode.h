@@ -812,8 +812,8 @@ template <bool F16_D>
 __global__ void __launch_bounds__(1024) k_attn_decode_batch(const float *__restrict__ q, const BatchCols *__restrict__ bc, int64_t kv_off,
                                                             float scale, int D, int n_rep, int64_t Egqa, int64_t C, int8_t *lo,
                                                             int8_t *hi, float *dq, int *sumq, int n_head, int64_t Clds, float *dT,
-                                                            int *sT) {
+                                                            int *sT, float *out_f32 = nullptr /* F16 plan: the f32 rows as well */) {
     const int qn = blockIdx.y;
-    attn_decode_body<F16_D>(q, bc->mem_k[qn] + kv_off, bc->mem_v[qn] + kv_off, &bc->pos[qn], 0, scale, D, n_rep, Egqa, C, nullptr, lo,
+    attn_decode_body<F16_D>(q, bc->mem_k[qn] + kv_off, bc->mem_v[qn] + kv_off, &bc->pos[qn], 0, scale, D, n_rep, Egqa, C, out_f32, lo,
                             hi, dq, sumq, nullptr, n_head, Clds, dT, sT);
 }

@@ -15,6 +15,12 @@ static QWeight plan_qw(const ggml_tensor *t) {
     if (!e || !e->soa || (uintptr_t)t->data != e->host) die("decode plan: weight '%s' has no resident SoA copy", t->name);
     return e->qw;
 }
+// an F16 matrix: the record's bytes are the tensor's rows — pointer, row stride and row count are all the plan keeps
+static F16W plan_f16w(const ggml_tensor *t) {
+    DevTensor *e = plan_rec(t);
+    if (!e || e->soa || e->ksoa) die("decode plan: F16 weight '%s' has no resident copy", t->name);
+    return F16W{(const __half *)(e->dev + ((uintptr_t)t->data - e->host)), (int64_t)t->nb[1] / 2, t->ne[1]};
+}
 static uint64_t rec_id(const ggml_tensor *t) {
     DevTensor *e = plan_rec(t);
     return e ? (uint64_t)(uintptr_t)e->dev : 0;
@@ -23,6 +29,7 @@ static uint64_t rec_id(const ggml_tensor *t) {
 static bool plan_weights_resident(const LlamaMatch &m) {
     auto ok_q = [](const ggml_tensor *t) {
         DevTensor *e = plan_rec(t);
+        if (t->type == GGML_TYPE_F16) return e && !e->soa && !e->ksoa && f16_weight_ok(plan_f16w(t));  // the raw rows
         return e && (e->soa || e->ksoa) && (uintptr_t)t->data == e->host;
     };
     auto ok_raw = [](const ggml_tensor *t) {
@@ -57,6 +64,18 @@ static std::vector<uint64_t> plan_signature(const LlamaMatch &m, bool session = 
     for (auto &l : m.layers)
         for (const ggml_tensor *t : {l.attn_norm, l.wq, l.wk, l.wv, l.wo, l.ffn_norm, l.w1, l.w2, l.w3})
             s.push_back(rec_id(t));
+    if (m.f16w) {  // an F16 weight record is pointer, stride and rows: a view of another part of a record is another weight
+        auto rec = [&](const ggml_tensor *t) {
+            if (!t) return;
+            s.push_back((uint64_t)(uintptr_t)t->data);
+            s.push_back((uint64_t)t->nb[1]);
+            s.push_back((uint64_t)t->ne[1]);
+        };
+        rec(m.wte);
+        rec(m.output);
+        for (auto &l : m.layers)
+            for (const ggml_tensor *t : {l.wq, l.wk, l.wv, l.wo, l.w1, l.w2, l.w3}) rec(t);
+    }
     if (!session) return s;
     s.push_back(m.logits ? (uint64_t)(uintptr_t)dev_ptr(m.logits) : 0);
     s.push_back(m.embedding ? (uint64_t)(uintptr_t)dev_ptr(m.embedding) : 0);
@@ -151,9 +170,10 @@ static DecodePlan *build_plan(const LlamaMatch &m, std::vector<uint64_t> sig, bo
     DecodePlan *p = new DecodePlan();
     p->sig = std::move(sig);
     p->m = m;
-    if (m.wte) (m.kquant ? (void)(p->k_wte = plan_kw(m.wte)) : (void)(p->wte = plan_qw(m.wte)));
+    if (m.wte) (m.f16w ? (void)(p->f_wte = plan_f16w(m.wte)) : m.kquant ? (void)(p->k_wte = plan_kw(m.wte)) : (void)(p->wte = plan_qw(m.wte)));
     if (m.output) {
-        if (m.kquant) p->k_output = plan_kw(m.output);
+        if (m.f16w) p->f_output = plan_f16w(m.output);
+        else if (m.kquant) p->k_output = plan_kw(m.output);
         else p->output = plan_qw(m.output);
         p->norm = (const float *)dev_ptr(m.norm);
     }
@@ -167,7 +187,12 @@ static DecodePlan *build_plan(const LlamaMatch &m, std::vector<uint64_t> sig, bo
     for (auto &l : m.layers) {
         DecodePlan::LW w;
         memset(&w, 0, sizeof(w));
-        if (m.kquant) {
+        if (m.f16w) {
+            DecodePlan::FLW fw;
+            fw.wq = plan_f16w(l.wq); fw.wk = plan_f16w(l.wk); fw.wv = plan_f16w(l.wv); fw.wo = plan_f16w(l.wo);
+            fw.w1 = plan_f16w(l.w1); fw.w2 = plan_f16w(l.w2); fw.w3 = plan_f16w(l.w3);
+            p->flw.push_back(fw);
+        } else if (m.kquant) {
             DecodePlan::KLW kw;
             kw.wq = plan_kw(l.wq); kw.wk = plan_kw(l.wk); kw.wv = plan_kw(l.wv); kw.wo = plan_kw(l.wo);
             kw.w1 = plan_kw(l.w1); kw.w2 = plan_kw(l.w2); kw.w3 = plan_kw(l.w3);
@@ -208,7 +233,7 @@ static DecodePlan *build_plan(const LlamaMatch &m, std::vector<uint64_t> sig, bo
                  o_fdT = take(multi ? passes * m.F / 32 * 32 : 0), o_fsT = take(multi ? passes * m.F / 32 * 32 : 0);
     const size_t kW = (size_t)std::max(m.E, m.F);
     const size_t o_kkf = take(m.kquant ? R * m.Egqa * 4 : 0), o_kvf = take(m.kquant ? R * m.Egqa * 4 : 0),
-                 o_katt = take(m.kquant ? R * m.E * 4 : 0), o_kg3 = take(m.kquant ? R * m.F * 4 : 0),
+                 o_katt = take(m.kquant || m.f16w ? R * m.E * 4 : 0), o_kg3 = take(m.kquant ? R * m.F * 4 : 0),
                  o_kq8 = take(m.kquant ? R * kW : 0), o_kd8 = take(m.kquant ? R * kW / 256 * 4 : 0), o_kbs = take(m.kquant ? R * kW / 256 * 32 : 0);
     const bool prompt = m.prompt;  // the prompt plan's buffers live only during one evaluation: shared workspace (plan_launch_prompt)
     size_t o_tok = 0, o_rope_n = 0;
@@ -253,6 +278,7 @@ static DecodePlan *build_plan(const LlamaMatch &m, std::vector<uint64_t> sig, bo
     p->e_d = (float *)(p->pool + o_ed);    p->e_s = (int *)(p->pool + o_es);
     p->f_lo = (int8_t *)(p->pool + o_flo); p->f_hi = (int8_t *)(p->pool + o_fhi);
     p->f_d = (float *)(p->pool + o_fd);    p->f_s = (int *)(p->pool + o_fs);
+    if (m.f16w) p->k_att = (float *)(p->pool + o_katt);  // the F16 plan's attention output: the f32 row wo stages
     if (m.kquant) {
         p->k_kf = (float *)(p->pool + o_kkf); p->k_vf = (float *)(p->pool + o_kvf);
         p->k_att = (float *)(p->pool + o_katt); p->k_g3 = (float *)(p->pool + o_kg3);

@@ -1,5 +1,5 @@
-// plan_decode.inc — the single-token launch sequences of a DecodePlan: plan_launch_all (block formats) and plan_launch_k
-// (K-quants, which also takes chunks of up to 31 tokens), and the launchers they share with plan_prompt.inc and the test hooks.
+// plan_decode.inc — the single-token launch sequences of a DecodePlan: plan_launch_all (block formats), plan_launch_k
+// (K-quants, which also takes chunks of up to 31 tokens) and plan_launch_f16 (F16 weights: decode, chunks and batched steps), and the launchers they share with plan_prompt.inc and the test hooks.
 // per-class launch/byte accounting of one token (filled by the launch sequences when given)
 struct PlanStats {
     double bytes[GGML_HIP_KCLASS_COUNT] = {0, 0, 0, 0};
@@ -611,9 +611,191 @@ static void plan_launch_k(DecodePlan *p, int av, LaunchCtx cx) {
     norm_quant(p->xa, p->norm, emb_dst);  // all N rows: f32 copy (embedding_result node) + Q8_K
     mmvq(4, {&p->k_output}, {(float *)logits_dst}, nullptr, KBigSrc{KX_NORM, p->xa, p->norm, m.eps, emb_dst});
 }
+// ---------------------------------------------------------------------------------------------------
+// The F16 plan: a LLaMA whose matrices are F16 (file type 1).  Five launches per layer (kernels/decode_f16.h):
+//   norm + wq|wk|wv + RoPE + K/V store | attention | wo + residual | norm + silu(w1 x) * (w3 x) | w2 + residual
+// for single-token decode, for a chunk of 2..31 tokens (the same launches with N columns, in passes of 8 / 4 / 2 / 1 columns per
+// mat-vec, whichever its LDS holds) and for a batched step (`batch`: column c sits at its own session's position and cache, BatchCols).
+// A row's result does not depend on the columns beside it (the kernel's design rule): the chunk equals N single tokens and the
+// batched step equals the chunk, bit for bit.  Same `mask` / `kind_mask` protocol as the other plans.
+// ---------------------------------------------------------------------------------------------------
+struct F16Src {
+    int xsrc;
+    const float *xf, *xw;
+    float eps;
+    float *y_out;
+};
+struct F16Qkv {
+    const float *rope;
+    const DecParams *prm;
+    const BatchCols *bc;
+    int64_t kv_off;
+    __half *mem_k, *mem_v;
+    int64_t Egqa, C;
+    int D;
+};
+template <int XSRC, int EPI, int NCOLS>
+static void launch_f16_inst(const F16Args &a, int G, size_t lds) {
+    if (lds > 64 * 1024) {  // above the 64 KiB default a kernel asks for its dynamic LDS once per device
+        static DevOnce opted;
+        if (opted.first()) HIP_CHECK(hipFuncSetAttribute((const void *)k_mmvq_f16<XSRC, EPI, NCOLS>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+    }
+    hipLaunchKernelGGL((k_mmvq_f16<XSRC, EPI, NCOLS>), dim3((unsigned)G), dim3(F16_T), lds, g.stream, a);
+}
+template <int XSRC, int EPI>
+static void launch_f16_cols(const F16Args &a, int ncols, int G, size_t lds) {
+    switch (ncols) {
+        case 8: launch_f16_inst<XSRC, EPI, 8>(a, G, lds); break;
+        case 4: launch_f16_inst<XSRC, EPI, 4>(a, G, lds); break;
+        case 2: launch_f16_inst<XSRC, EPI, 2>(a, G, lds); break;
+        default: launch_f16_inst<XSRC, EPI, 1>(a, G, lds); break;
+    }
+}
+// whether launch_f16 takes these matrices with this source / epilogue pair (the pairs plan_launch_f16 launches)
+static bool f16_launch_ok(int nseg, const F16W *ws, int64_t K, int xsrc, int epi) {
+    const bool pair_ok = (xsrc == KX_NORM && (epi == KE_QKV || epi == KE_ROW || epi == KE_GATE)) || ((xsrc == KX_F32 || xsrc == KX_SILU_MUL) && epi == KE_ROW);
+    if (!pair_ok || nseg < 1 || nseg > 3 || (epi == KE_GATE && nseg != 2)) return false;
+    int64_t Mt = 0;
+    for (int i = 0; i < nseg; i++) {
+        if (!f16_weight_ok(ws[i]) || ws[i].ld < K) return false;
+        if (epi == KE_QKV && ws[i].M % 2) return false;
+        Mt += ws[i].M;
+    }
+    if (epi == KE_GATE && ws[0].M != ws[1].M) return false;
+    return f16_launch_shape_ok(K, epi == KE_GATE ? ws[0].M : epi == KE_QKV ? Mt / 2 : Mt);
+}
+// one mat-vec of the F16 plan over N columns: dsts[i] is [N][M_i], res like dsts[0]; seg_kind (KE_QKV): which of wq / wk / wv ws[i] is
+static void launch_f16(int nseg, const F16W *ws, float *const *dsts, int64_t K, const F16Src &src, const float *res, int N, int epi = KE_ROW,
+                       const F16Qkv *qkv = nullptr, const int *seg_kind = nullptr) {
+    if (!f16_launch_ok(nseg, ws, K, src.xsrc, epi)) die("k_mmvq_f16: a launch the F16 plan's preconditions exclude (K %lld)", (long long)K);
+    int64_t Mt = 0;
+    for (int i = 0; i < nseg; i++) Mt += ws[i].M;
+    const int64_t units = epi == KE_GATE ? ws[0].M : epi == KE_QKV ? Mt / 2 : Mt;
+    const int G = big_groups(units, g.num_cus);
+    for (int c0 = 0; c0 < N;) {
+        const int ncols = f16_pass_cols(K, N - c0);
+        F16Args a;
+        memset(&a, 0, sizeof(a));
+        a.nseg = nseg;
+        a.K = (int)K;
+        for (int i = 0; i < nseg; i++) {
+            a.w[i] = ws[i].p; a.M[i] = ws[i].M; a.ld[i] = ws[i].ld;
+            a.dst[i] = dsts[i] ? dsts[i] + (int64_t)c0 * ws[i].M : nullptr;
+            if (seg_kind) a.seg_kind[i] = seg_kind[i];
+        }
+        a.res = res ? res + (int64_t)c0 * ws[0].M : nullptr;
+        a.xf = src.xf + (int64_t)c0 * K;
+        a.xw = src.xsrc == KX_SILU_MUL ? src.xw + (int64_t)c0 * K : src.xw;
+        a.eps = src.eps;
+        a.y_out = src.y_out ? src.y_out + (int64_t)c0 * K : nullptr;
+        a.col0 = c0;
+        if (qkv) {
+            a.rope = qkv->rope + (int64_t)c0 * 128; a.prm = qkv->prm; a.bc = qkv->bc; a.kv_off = qkv->kv_off;
+            a.mem_k = qkv->mem_k; a.mem_v = qkv->mem_v; a.Egqa = qkv->Egqa; a.C = qkv->C; a.D = qkv->D;
+        }
+        a.hot = g.hot_line;
+        const size_t lds = (size_t)ncols * (size_t)K * 2;
+        if (epi == KE_QKV) launch_f16_cols<KX_NORM, KE_QKV>(a, ncols, G, lds);
+        else if (epi == KE_GATE) launch_f16_cols<KX_NORM, KE_GATE>(a, ncols, G, lds);
+        else if (src.xsrc == KX_NORM) launch_f16_cols<KX_NORM, KE_ROW>(a, ncols, G, lds);
+        else if (src.xsrc == KX_F32) launch_f16_cols<KX_F32, KE_ROW>(a, ncols, G, lds);
+        else launch_f16_cols<KX_SILU_MUL, KE_ROW>(a, ncols, G, lds);
+        HIP_CHECK(hipGetLastError());
+        c0 += ncols;
+    }
+}
+static void launch_attn_decode_batch(const DecodePlan *p, int il, int N, bool f16d, float *out_f32);
+static void plan_launch_f16(DecodePlan *p, int av, LaunchCtx cx, bool batch = false) {
+    const bool long_ctx = av == AV_SPLIT;
+    const LlamaMatch &m = p->m;
+    const int64_t E = m.E, F = m.F;
+    const int N = m.N;
+    const float theta_scale = powf(m.freq_base, -2.0f / m.n_dims);
+    // bytes of one launch: the matrices, the activation rows and the outputs (`out`: bytes per output element)
+    auto mv_bytes = [&](std::initializer_list<const F16W *> wl, int64_t K, double out) {
+        double bytes = (double)N * K * 4.0;
+        for (const F16W *w : wl) bytes += (double)w->M * K * 2.0 + (double)N * w->M * out;
+        return bytes;
+    };
+    if (!m.wte) {
+        if (cx.want(GGML_HIP_KCLASS_OTHER, (double)N * E * 8.0))
+            HIP_CHECK(hipMemcpyAsync(p->xa, p->stage_in, (size_t)N * E * 4, hipMemcpyDeviceToDevice, g.stream));
+    } else {  // DecParams::tokens[0] == token: the ids of the chunk / of the step's columns
+        cx.other((double)N * E * 6.0, [&] {
+            hipLaunchKernelGGL(k_get_rows<__half>, dim3((unsigned)((E + 255) / 256), (unsigned)N), dim3(256), 0, g.stream, (const char *)p->f_wte.p,
+                               p->f_wte.ld * 2, (const int *)p->prm->tokens, p->xa, E);
+        });
+    }
+    cx.other((double)N * m.D * 4.0, [&] {  // one (cos, sin) table per column, 128 floats apart
+        if (batch)
+            hipLaunchKernelGGL(k_rope_table_batch, dim3((unsigned)N), dim3(128), 0, g.stream, (const BatchCols *)p->bcols, theta_scale, m.freq_scale,
+                               (int)(m.D >> 1), p->rope);
+        else
+            hipLaunchKernelGGL(k_rope_table, dim3((unsigned)N), dim3(128), 0, g.stream, (const DecParams *)p->prm, theta_scale, m.freq_scale,
+                               (int)(m.D >> 1), p->rope, p->epoch);  // block 0 also opens the token's epoch (the tag of k_attn_split_one's granules)
+    });
+    for (int il = 0; il < m.L; il++) {
+        const DecodePlan::FLW &w = p->flw[il];
+        const DecodePlan::LW &nw = p->lw[il];
+        {   // norm + wq|wk|wv + RoPE + K/V store
+            const F16W ws3[3] = {w.wq, w.wk, w.wv};
+            float *ds3[3] = {p->q, nullptr, nullptr};
+            const int kinds[3] = {0, 1, 2};
+            F16Qkv qa;
+            memset(&qa, 0, sizeof(qa));
+            qa.rope = p->rope; qa.prm = p->prm; qa.Egqa = m.Egqa; qa.C = m.C; qa.D = (int)m.D;
+            if (batch) { qa.bc = p->bcols; qa.kv_off = p->kv_off(il); }
+            else { qa.mem_k = p->mem_k_at(il); qa.mem_v = p->mem_v_at(il); }
+            cx.mmvq(0, mv_bytes({&w.wq, &w.wk, &w.wv}, E, 4.0), [&] {
+                launch_f16(3, ws3, ds3, E, F16Src{KX_NORM, p->xa, nw.attn_norm, m.eps, nullptr}, nullptr, N, KE_QKV, &qa, kinds);
+            });
+        }
+        {   // attention: the f32 row of the merged heads for wo's staging (the Q8 copy goes to the plan's unused Q8 row)
+            const double bytes = (double)N * ((double)(m.n_past + N) * m.Egqa * 4.0 + m.E * 9.0);
+            if (cx.want(GGML_HIP_KCLASS_ATTN, bytes)) {
+                Timed tm(GGML_HIP_KCLASS_ATTN, bytes);
+                if (batch)
+                    launch_attn_decode_batch(p, il, N, true, p->k_att);
+                else if (long_ctx) {
+                    AttnSplitOneArgs oa = split_attn_args(p, il);
+                    oa.out_f32 = p->k_att;
+                    launch_attn_split_one(p, oa, true);
+                } else
+                    launch_attn_decode(p, il, N, m.C, true, p->k_att, nullptr);
+                HIP_CHECK(hipGetLastError());
+            }
+        }
+        {
+            float *d1[1] = {p->xb};
+            cx.mmvq(1, mv_bytes({&w.wo}, E, 8.0), [&] { launch_f16(1, &w.wo, d1, E, F16Src{KX_F32, p->k_att, nullptr, 0.0f, nullptr}, p->xa, N); });
+        }
+        {
+            const F16W ws2[2] = {w.w1, w.w3};
+            float *d2[2] = {p->gate, nullptr};
+            cx.mmvq(2, (double)N * E * 4.0 + 2.0 * (double)F * E * 2.0 + (double)N * F * 4.0,
+                    [&] { launch_f16(2, ws2, d2, E, F16Src{KX_NORM, p->xb, nw.ffn_norm, m.eps, nullptr}, nullptr, N, KE_GATE); });
+        }
+        {
+            float *d1[1] = {p->xa};
+            cx.mmvq(3, mv_bytes({&w.w2}, F, 8.0), [&] { launch_f16(1, &w.w2, d1, F, F16Src{KX_F32, p->gate, nullptr, 0.0f, nullptr}, p->xb, N); });
+        }
+    }
+    if (!m.output) {
+        if (cx.want(GGML_HIP_KCLASS_OTHER, (double)N * E * 8.0))
+            HIP_CHECK(hipMemcpyAsync(p->stage_out, p->xa, (size_t)N * E * 4, hipMemcpyDeviceToDevice, g.stream));
+        return;
+    }
+    float *const emb_dst = p->spec_out && p->emb_out ? p->emb_alt : p->emb_out;  // (see DecodePlan::logits_alt)
+    char *const logits_dst = p->spec_out ? p->logits_alt : p->logits_out;
+    float *d1[1] = {(float *)logits_dst};
+    cx.mmvq(4, mv_bytes({&p->f_output}, E, 4.0),
+            [&] { launch_f16(1, &p->f_output, d1, E, F16Src{KX_NORM, p->xa, p->norm, m.eps, emb_dst}, nullptr, N); });
+}
 // the decode launches of a plan, whichever kind it is
 static void plan_launch_decode(DecodePlan *p, int av = AV_SHORT, LaunchCtx cx = {}) {
-    if (p->m.kquant)
+    if (p->m.f16w)
+        plan_launch_f16(p, av, cx);
+    else if (p->m.kquant)
         plan_launch_k(p, av, cx);
     else
         plan_launch_all(p, av, cx);

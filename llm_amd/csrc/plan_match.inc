@@ -120,9 +120,10 @@ static bool match_llama_decode(ggml_cgraph *gr, LlamaMatch &m) {
         MATCH(last->type == GGML_TYPE_F32 && last->ne[1] >= 1 && last->ne[1] <= PROMPT_PLAN_MAX && last->ne[2] == 1);
         m.N = (int)last->ne[1];
         m.output = last->src[0];
-        MATCH(is_leaf(m.output) && (qt_of(m.output->type) >= 0 || kt_of(m.output->type) >= 0));
+        MATCH(is_leaf(m.output) && (qt_of(m.output->type) >= 0 || kt_of(m.output->type) >= 0 || m.output->type == GGML_TYPE_F16));
         m.wtype = m.output->type;
         m.kquant = kt_of(m.output->type) >= 0;
+        m.f16w = m.output->type == GGML_TYPE_F16;
         m.E = m.output->ne[0];
         m.V = m.output->ne[1];
         m.logits = last;
@@ -166,9 +167,10 @@ static bool match_llama_decode(ggml_cgraph *gr, LlamaMatch &m) {
         MATCH(is_op(m2, GGML_OP_MUL_MAT));
         lw.w2 = m2->src[0];
         if (!m.output && m.wtype == GGML_TYPE_F32) {
-            MATCH(qt_of(lw.w2->type) >= 0 || kt_of(lw.w2->type) >= 0);
+            MATCH(qt_of(lw.w2->type) >= 0 || kt_of(lw.w2->type) >= 0 || lw.w2->type == GGML_TYPE_F16);
             m.wtype = lw.w2->type;
             m.kquant = kt_of(lw.w2->type) >= 0;
+            m.f16w = lw.w2->type == GGML_TYPE_F16;
         }
         const ggml_tensor *gate = m2->src[1];
         MATCH(is_op(gate, GGML_OP_MUL));
@@ -319,6 +321,19 @@ static bool match_llama_decode(ggml_cgraph *gr, LlamaMatch &m) {
     // (a K-quant model takes the prompt plan from 12 tokens on — option k_prompt_min: its multi-token mat-vecs are VALU-bound — chunks of 12 / 16 / 24 tokens
     // of LLaMA-7B Q4_K 1.70k / 1.83k / 1.85k tok/s on the K plan against 1.98k / 2.67k / 3.84k on the f16 copies; the block formats'
     // k_mmq_cols is ahead of the GEMM up to 31 tokens: 3.69k against 2.68k at 16)
+    // F16 weights (option plan_f16; 0 = the node-by-node executor, as before the F16 plan existed): decode, chunks of up to 31 tokens and
+    // batched steps on k_mmvq_f16; a batch of mmq_min tokens and more stays on the executor, which runs it on k_gemm_f16
+    if (m.f16w) {
+        MATCH(g.opt_plan_f16 && m.N >= 1 && m.N <= MULTI_MAX_N && (g.opt_mmq_min <= 0 || m.N < g.opt_mmq_min) && m.n_past + m.N <= m.C);
+        MATCH(m.D == m.n_dims && f16_plan_shape_ok(m) && attn_decode_lds(m.C, m.D) <= ATTN_DECODE_LDS_MAX);
+        for (auto &lw : m.layers)
+            for (const ggml_tensor *w : {lw.wq, lw.wk, lw.wv, lw.wo, lw.w1, lw.w2, lw.w3})
+                MATCH(is_leaf(w) && w->type == GGML_TYPE_F16 && w->ne[2] == 1 && w->ne[3] == 1 && ggml_is_contiguous(w));
+        for (const ggml_tensor *w : {m.wte, m.output})
+            MATCH(!w || (w->type == GGML_TYPE_F16 && w->ne[2] == 1 && w->ne[3] == 1 && ggml_is_contiguous(w)));
+        m.prompt = false;
+        return true;
+    }
     const bool k_early = m.kquant && g.opt_mmq_w16 && g.opt_plan_prompt && !g.opt_mmq_i8;  // (the early switch only where that plan can run)
     m.prompt = m.N > 8 && g.opt_mmq_min > 0 && m.N >= (k_early ? std::min(g.opt_mmq_min, std::max(9, g.opt_k_prompt_min)) : g.opt_mmq_min);
     if (m.kquant && tl_k_prompt_off && m.N <= MULTI_MAX_N) m.prompt = false;

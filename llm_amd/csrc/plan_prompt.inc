@@ -36,7 +36,7 @@ static void launch_cols(const ColsArgs &a0, int M_total) {
         hipLaunchKernelGGL((k_mmq_cols<QT, EPI, false, BATCH>), dim3(sh.G), dim3(COLS_T), sh.lds, g.stream, a);
 }
 // k_attn_decode's batched form for layer il of a batched step: a grid of heads x columns, the whole context in its LDS arrays
-static void launch_attn_decode_batch(const DecodePlan *p, int il, int N, bool f16d) {
+static void launch_attn_decode_batch(const DecodePlan *p, int il, int N, bool f16d, float *out_f32 = nullptr) {
     static DevOnce opted;
     if (opted.first()) {
         HIP_CHECK(hipFuncSetAttribute((const void *)k_attn_decode_batch<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ATTN_DECODE_LDS_MAX));
@@ -46,7 +46,7 @@ static void launch_attn_decode_batch(const DecodePlan *p, int il, int N, bool f1
     with_bool(f16d, [&](auto F16D) {
         hipLaunchKernelGGL(k_attn_decode_batch<CT(F16D)>, dim3((unsigned)m.H, (unsigned)N), dim3(1024), attn_decode_lds(m.C, m.D), g.stream,
                            (const float *)p->q, (const BatchCols *)p->bcols, p->kv_off(il), m.kq_scale, (int)m.D, (int)(m.H / m.Hkv), m.Egqa,
-                           m.C, p->e_lo, p->e_hi, p->e_d, p->e_s, (int)m.H, m.C, p->e_dT, p->e_sT);
+                           m.C, p->e_lo, p->e_hi, p->e_d, p->e_s, (int)m.H, m.C, p->e_dT, p->e_sT, out_f32);
     });
     HIP_CHECK(hipGetLastError());
 }
@@ -246,7 +246,12 @@ static void plan_launch_chunk(DecodePlan *p, const bool batch) {
 }
 static void plan_launch_multi(DecodePlan *p) { plan_launch_chunk(p, false); }
 // One decode step of N = 2..8 sessions of one model as one pass over the weights (ggml_hip_decode_batch, plan_run.inc decode_batch)
-static void plan_launch_batch(DecodePlan *p) { plan_launch_chunk(p, true); }
+static void plan_launch_batch(DecodePlan *p) {
+    if (p->m.f16w)
+        plan_launch_f16(p, AV_SHORT, LaunchCtx{}, true);
+    else
+        plan_launch_chunk(p, true);
+}
 
 // ---------------------------------------------------------------------------------------------------
 // The prompt plan: a batch of N >= mmq_min tokens (crates/llm-base/src/inference_session.rs:315-316 feeds n_batch tokens

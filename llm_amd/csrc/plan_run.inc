@@ -252,7 +252,7 @@ static bool try_decode_plan(ggml_cgraph *gr, bool defer_wait = false) {
     const int av = attn_variant(m, p, m.n_past + 1);
     const bool long_ctx = av == AV_SPLIT;
     auto launch = [&] {
-        if (m.N > 1 && !m.kquant)
+        if (m.N > 1 && !m.kquant && !m.f16w)
             plan_launch_multi(p);
         else
             plan_launch_decode(p, av);
@@ -427,14 +427,15 @@ static int decode_batch(ggml_cgraph *const *graphs, int B) {
         LlamaMatch &m = ms[(size_t)c];
         if (!match_llama_decode(graphs[c], m)) return -1;
         if (m.N != 1 || m.prompt || m.kquant || !m.wte || !m.output || !m.embd || !m.logits || !m.embedding) return -1;
-        if (m.n_past >= m.C || qt_of(m.wtype) < 0) return -1;  // (f16 K/V, D, E, F: the matcher's own preconditions)
+        if (m.n_past >= m.C || (qt_of(m.wtype) < 0 && !m.f16w)) return -1;  // (f16 K/V, D, E, F: the matcher's own preconditions)
         for (const ggml_tensor *t : {m.memory_k, m.memory_v}) {  // a session of another slot keeps its cache to itself (extra_of would abort)
             const DevTensor *e = (const DevTensor *)t->extra;
             if (e && e->magic == 0x48495054 && e->slot != g_cur_slot()) return -1;
         }
     }
     // the whole context in k_attn_decode's LDS arrays (a column may sit anywhere in it), 8 Q8 columns of the widest row in k_mmvq_big8's
-    if (attn_decode_lds(ms[0].C, ms[0].D) > ATTN_DECODE_LDS_MAX || !multi_shape_ok(ms[0], B)) return -1;
+    // (an F16 model: k_mmvq_f16 stages as many columns per pass as its LDS holds)
+    if (attn_decode_lds(ms[0].C, ms[0].D) > ATTN_DECODE_LDS_MAX || (!ms[0].f16w && !multi_shape_ok(ms[0], B))) return -1;
     ws_reset();
     for (int c = 0; c < B; c++) {
         const LlamaMatch &m = ms[(size_t)c];

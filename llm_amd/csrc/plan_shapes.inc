@@ -3,6 +3,7 @@
 // is recognised as a whole and executed as one of five launch sequences over the same cached DecodePlan:
 //   single-token decode, block formats (plan_launch_all): 3 launches per layer with wq|wk|wv + attention + wo fused, 5 without;
 //   single-token decode and chunks of up to 31 tokens, K-quants (plan_launch_k): 10-13 launches per layer;
+//   single-token decode, chunks of up to 31 tokens and batched steps, F16 weights (plan_launch_f16): 5 launches per layer;
 //   a chunk of 2..31 tokens, block formats (plan_launch_multi): 8 launches per layer and pass of 8 columns;
 //   a prompt batch (plan_launch_prompt): 13 launches per layer around the matrix-core GEMMs, launched eagerly;
 //   one token each of 2..8 sessions of one model (plan_launch_batch; ggml_hip_decode_batch hands over their graphs together): the
@@ -14,7 +15,7 @@
 //                    the matcher, the launchers, the run loop and the test hooks of backend_tools.inc all call)
 //   plan_match.inc   the structural graph matcher
 //   plan_build.inc   weights, signature and activation pool of a plan
-//   plan_decode.inc  the single-token launchers: plan_launch_all, plan_launch_k
+//   plan_decode.inc  the single-token launchers: plan_launch_all, plan_launch_k, plan_launch_f16
 //   plan_prompt.inc  plan_launch_multi, plan_launch_batch, prompt_attention, plan_launch_prompt
 //   plan_run.inc     capture and replay, speculation, the fused-timeout re-run, the greedy chain, the batched step
 //
@@ -22,6 +23,11 @@
 // shape/stride/offset against the KV-cache layout), so any graph that is not exactly the reference's LLaMA
 // graph falls through to the generic per-node executor — same results, more launches.
 
+// an F16 weight as the F16 plan reads it: the device pointer of the tensor's first row, the row stride in elements, the rows
+struct F16W {
+    const __half *p;
+    int64_t ld, M;
+};
 struct LayerW {
     const ggml_tensor *attn_norm = nullptr, *wq = nullptr, *wk = nullptr, *wv = nullptr, *wo = nullptr,
                       *ffn_norm = nullptr, *w1 = nullptr, *w2 = nullptr, *w3 = nullptr;
@@ -37,6 +43,7 @@ struct LlamaMatch {
     int N = 1;  // tokens in this evaluation: 1 = decode, 2..31 below mmq_min = a prompt chunk (multi-token plan), >= mmq_min = prompt plan
     bool prompt = false;  // the prompt plan takes it
     bool kquant = false;  // every matrix is a K-quant (any mix of Q2_K … Q6_K): the K plan (plan_launch_k), single-token decode only
+    bool f16w = false;    // every matrix is F16 (file type 1): the F16 plan (plan_launch_f16), decode, chunks and batched steps
     float eps = 0, freq_base = 0, freq_scale = 0, kq_scale = 0;
     ggml_type wtype = GGML_TYPE_F32;
     const ggml_tensor *wte = nullptr, *norm = nullptr, *output = nullptr, *embd = nullptr, *memory_k = nullptr,
@@ -60,6 +67,11 @@ struct DecodePlan {
         KWeight wq, wk, wv, wo, w1, w2, w3;
     };
     std::vector<KLW> klw;
+    struct FLW {  // F16 plan: the tensors' own rows (no re-layout, no copy)
+        F16W wq, wk, wv, wo, w1, w2, w3;
+    };
+    std::vector<FLW> flw;
+    F16W f_wte{}, f_output{};
     KWeight k_wte{}, k_output{};
     // K plan activations: f32 rows of wk / wv / the merged heads / w3, and ONE Q8_K row (max(E, F) wide) every mat-vec reads
     float *k_kf = nullptr, *k_vf = nullptr, *k_att = nullptr, *k_g3 = nullptr;
@@ -238,7 +250,7 @@ struct FusedShape {
 };
 static FusedShape fused_qkv_shape(const LlamaMatch &m, int S = 1) {
     FusedShape s;
-    if (!g.opt_fuse_attn || !g.opt_big || m.kquant || m.N != 1 || m.D > 128 || m.D % 32 != 0) return s;
+    if (!g.opt_fuse_attn || !g.opt_big || m.kquant || m.f16w || m.N != 1 || m.D > 128 || m.D % 32 != 0) return s;
     const int H = (int)m.H * S;  // attention workgroups
     const int64_t units = (m.E + 2 * m.Egqa) / 2;
     if (H + 1 > g.num_cus) return s;
@@ -308,7 +320,7 @@ static bool attn_one_ok(const LlamaMatch &m, int att_S) {
 // the wq|wk|wv launch instead of the separate split attention, where the chip has room for them.
 static int attn_variant(const LlamaMatch &m, const DecodePlan *p, int64_t T) {
     if (m.N != 1) return AV_SHORT;
-    const bool split_ok = (!m.kquant || attn_one_ok(m, p->att_S)) && attn_split_from_min(m.H);
+    const bool split_ok = (!(m.kquant || m.f16w) || attn_one_ok(m, p->att_S)) && attn_split_from_min(m.H);
     if (g.opt_fuse_heads && g.opt_attn_split == 1 && split_ok && T > FUSE_HEADS_MIN && fused_qkv_shape(m).ok) {
         const int S = (int)((T + 511) / 512);  // workgroups per head: 512 positions each
         if (S <= 4 && p->att_S >= S && fused_qkv_shape(m, S).ok) return S;  // = AV_FUSED2 / 3 / 4
@@ -342,6 +354,23 @@ static bool kbig_ok(const DecodePlan *p) {  // K matrices whose rows of a wave f
         for (const KWeight *w : {&l.wq, &l.wk, &l.wv, &l.wo, &l.w1, &l.w2, &l.w3})
             if (!ok(*w)) return false;
     return !p->m.output || ok(p->k_output);
+}
+// ---- k_mmvq_f16 (kernels/decode_f16.h) ----
+// columns of one pass over a matrix of width K when `left` columns remain: 8 / 4 / 2 / 1, whichever the LDS holds (launch_mmvq_kn's rule)
+static inline int f16_pass_cols(int64_t K, int left) {
+    int ncols = 8;
+    while (ncols > 1 && (ncols > left || (size_t)ncols * (size_t)K * 2 > 150 * 1024)) ncols >>= 1;
+    return ncols;
+}
+// a launch over `units` (rows; pairs of rows for the gate and wq|wk|wv) of width K: 16-byte chunks, one column in LDS, one epilogue lane per unit of a wave
+static inline bool f16_launch_shape_ok(int64_t K, int64_t units) {
+    return K >= 8 && K % 8 == 0 && (size_t)K * 2 <= 150 * 1024 && units >= 1 && units <= (int64_t)64 * 16 * g.num_cus;
+}
+static inline bool f16_weight_ok(const F16W &w) { return w.p && ((uintptr_t)w.p & 15) == 0 && w.ld % 8 == 0 && w.M >= 1; }
+// the launches of the F16 plan for this shape
+static bool f16_plan_shape_ok(const LlamaMatch &m) {
+    return f16_launch_shape_ok(m.E, (m.E + 2 * m.Egqa) / 2) && f16_launch_shape_ok(m.E, m.F) && f16_launch_shape_ok(m.F, m.E) &&
+           (!m.output || f16_launch_shape_ok(m.E, m.V)) && m.E % 2 == 0 && m.Egqa % 2 == 0 && m.D % 2 == 0;
 }
 // what the launches of the multi-token plan on k_mmvq_big8 need of N = 2..8 columns (kernels/decode_big8.h): 8 Q8 columns of the widest row in LDS
 static bool multi_shape_ok(const LlamaMatch &m, int N) {

@@ -247,6 +247,9 @@ PROTOTYPES.update({
     "ggml_hip_debug_mat_vec_kbig": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_float,
                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int64,
                                               C.c_void_p, C.c_void_p]),
+    "ggml_hip_debug_mat_vec_f16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_float,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int64,
+                                             C.c_void_p, C.c_void_p, C.c_int]),
     "ggml_hip_debug_exp_le0": (C.c_int, [C.c_void_p, C.c_void_p]),
     "ggml_hip_decode_greedy_chain": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "ggml_hip_decode_batch": (C.c_int, [C.c_void_p, C.c_int]),
@@ -548,6 +551,9 @@ def get_stat(key):
 
 
 def set_option(key, value):
+    """A runtime option of the backend (the table g_options of csrc/backend_state.inc; INTEGRATION.md lists the keys) — e.g.
+    plan_f16: 1 (default) = a LLaMA whose matrices are F16 decodes, takes prompt chunks and batched steps on the F16 plan, 0 = node
+    by node."""
     lib().ggml_hip_set_option(key.encode(), int(value))
 
 

@@ -69,6 +69,38 @@ def make_llama(hp, wtype, seed=1234, std=0.02):
     return h, out
 
 
+_F16_POOL = {}
+
+
+def _f16_pool(std):
+    """2^24 gaussians N(0, std^2) rounded to f16 (round to nearest even, numpy's conversion), made once per std."""
+    if std not in _F16_POOL:
+        _F16_POOL[std] = (std * np.random.default_rng(0xF16).standard_normal(1 << 24, dtype=np.float32)).astype(np.float16)
+    return _F16_POOL[std]
+
+
+def _f16_fast(rng, n, std):
+    """n f16 values as raw bytes: the pool repeated from a random offset on (full-size F16 models for timing: 6.7e9 fresh gaussians
+    would take a minute before a run could start; every value is still a gaussian rounded to f16)."""
+    pool = _f16_pool(std)
+    out = np.empty(n, dtype=np.float16)
+    at, off = 0, int(rng.integers(0, pool.size))
+    while at < n:
+        k = min(n - at, pool.size - off)
+        out[at:at + k] = pool[off:off + k]
+        at, off = at + k, 0
+    return out.view(np.uint8)
+
+
+def _f16_gaussian(rng, n, std):
+    """n gaussians N(0, std^2) rounded to f16, as raw bytes (numpy, in pieces of 2^24)."""
+    out = np.empty(n, dtype=np.float16)
+    for at in range(0, n, 1 << 24):
+        k = min(n - at, 1 << 24)
+        out[at:at + k] = (std * rng.standard_normal(k, dtype=np.float32)).astype(np.float16)
+    return out.view(np.uint8)
+
+
 def make_llama_fast(hp, wtype, seed=1234, d_scale=0.0043, only=None):
     """Full-size synthetic weights for bench.py: writes random GGML blocks directly (uniform quants, f16
     scales around `d_scale` so that dequantized weights have std ≈ 0.02) instead of quantizing 6.7e9
@@ -81,6 +113,9 @@ def make_llama_fast(hp, wtype, seed=1234, d_scale=0.0043, only=None):
         rng = np.random.default_rng([seed, _layer_of(name) + 1, sum(map(ord, name))])
         if ne1 is None:
             out[name] = (1.0 + 0.01 * rng.standard_normal(ne0)).astype(np.float32)
+            continue
+        if wtype == ggml.TYPE_F16:  # gaussians of std 0.02 rounded to f16 (no blocks to fill)
+            out[name] = _f16_fast(rng, ne0 * ne1, 0.02)
             continue
         nblk = ne1 * (ne0 // be)
         # per-type scale so that dequantized std stays ≈ 0.02: q4 std≈4.6, q5 std≈9.2, q8 std≈74
@@ -114,6 +149,9 @@ def make_llama_gaussian(hp, wtype, seed=1234, std=0.02, only=None):
         rng = np.random.default_rng([seed, _layer_of(name) + 1, sum(map(ord, name))])
         if ne1 is None:
             out[name] = (1.0 + 0.01 * rng.standard_normal(ne0)).astype(np.float32)
+            continue
+        if wtype == ggml.TYPE_F16:  # the gaussians themselves, rounded to f16
+            out[name] = _f16_gaussian(rng, ne0 * ne1, std)
             continue
         raw = np.empty(ne1 * (ne0 // be) * bs, dtype=np.uint8)
         fill(wtype, raw.ctypes.data, ne0, ne1, int(rng.integers(0, 2**62)), std)
