@@ -123,10 +123,7 @@ void quantize_activation_i8(const ggml_tensor *src1, int qt, const int8_t **q8, 
 }
 template <int QT>
 void launch_mmq_i8(const MmqI8Args &a, dim3 grid) {
-    static DevOnce attr;
-    if (attr.first()) {
-        HIP_CHECK(hipFuncSetAttribute((const void *)k_mmq_i8<QT>, hipFuncAttributeMaxDynamicSharedMemorySize, I8_LDS));
-    }
+    lds_opt_in<k_mmq_i8<QT>>(I8_LDS, I8_LDS);
     g.stat_mmq[Backend::MMQ_K_I8]++;
     hipLaunchKernelGGL(k_mmq_i8<QT>, grid, dim3(256), I8_LDS, g.stream, a);
 }
@@ -164,14 +161,11 @@ KAct quantize_activation_k(const ggml_tensor *src1) {
 }
 template <int KT, int NCOLS>
 void launch_mmvq_k(const MmvqKArgs &a, int nwg, size_t lds) {
-    static DevOnce opted;  // more than 64 KB of dynamic LDS needs the attribute, once per device and instantiation
     if constexpr (KT == KT_Q4_K || KT == KT_Q6_K) {
-        if (lds > 64 * 1024 && opted.first())
-            HIP_CHECK(hipFuncSetAttribute((const void *)k_mmvq_k<KT, NCOLS>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+        lds_opt_in<k_mmvq_k<KT, NCOLS>>(lds, 150 * 1024);
         hipLaunchKernelGGL((k_mmvq_k<KT, NCOLS>), dim3(nwg), dim3(256), lds, g.stream, a);
     } else {
-        if (lds > 64 * 1024 && opted.first())
-            HIP_CHECK(hipFuncSetAttribute((const void *)k_mmvq_k2<KT, NCOLS>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+        lds_opt_in<k_mmvq_k2<KT, NCOLS>>(lds, 150 * 1024);
         hipLaunchKernelGGL((k_mmvq_k2<KT, NCOLS>), dim3(nwg), dim3(256), lds, g.stream, a);
     }
 }
@@ -377,10 +371,7 @@ void mmq_w16_256_launch(int nseg, const MmqSegHost *segs, const _Float16 *x16, i
     a.split_stride = splits > 1 ? split_stride : 0;
     if (splits > 1 && zero_dst && !split_stride)
         for (int i = 0; i < nseg; i++) HIP_CHECK(hipMemsetAsync(segs[i].dst, 0, (size_t)segs[i].w.M * N * 4, g.stream));
-    static DevOnce attr_set;
-    if (attr_set.first()) {
-        HIP_CHECK(hipFuncSetAttribute((const void *)k_mmq_w16_256<0>, hipFuncAttributeMaxDynamicSharedMemorySize, T256_LDS));
-    }
+    lds_opt_in<k_mmq_w16_256<0>>(T256_LDS, T256_LDS);
     const int tiles_total = tiles_m * a.tiles_n, n_items = tiles_total * splits;
     Timed tm(GGML_HIP_KCLASS_MMQ_MFMA, 2.0 * rows * (double)N * (double)(nb * 32));
     g.stat_mmq[Backend::MMQ_K_W16_256]++;
@@ -426,18 +417,13 @@ void mmq_f16_launch_multi(int qt, int nseg, const MmqSegHost *segs, const _Float
     if (splits > 1 && zero_dst && !split_stride)
         for (int i = 0; i < nseg; i++) HIP_CHECK(hipMemsetAsync(segs[i].dst, 0, (size_t)segs[i].w.M * N * 4, g.stream));
     if (nb % 2 != 0) {  // K/32 odd (no LLaMA size; the 352-wide test models): one workgroup per tile, register-staged (kernels/mmq_plain.h)
-        static DevOnce lds_attr_set;
-        if (lds_attr_set.first()) {  // 73.7 KB of dynamic LDS: above the 64 KB a kernel gets without opting in
-            HIP_CHECK(hipFuncSetAttribute((const void *)k_mmq<QT_Q4_0>, hipFuncAttributeMaxDynamicSharedMemorySize, MMQ_LDS));
-            HIP_CHECK(hipFuncSetAttribute((const void *)k_mmq<QT_Q4_1>, hipFuncAttributeMaxDynamicSharedMemorySize, MMQ_LDS));
-            HIP_CHECK(hipFuncSetAttribute((const void *)k_mmq<QT_Q5_0>, hipFuncAttributeMaxDynamicSharedMemorySize, MMQ_LDS));
-            HIP_CHECK(hipFuncSetAttribute((const void *)k_mmq<QT_Q5_1>, hipFuncAttributeMaxDynamicSharedMemorySize, MMQ_LDS));
-            HIP_CHECK(hipFuncSetAttribute((const void *)k_mmq<QT_Q8_0>, hipFuncAttributeMaxDynamicSharedMemorySize, MMQ_LDS));
-        }
         const dim3 grid((unsigned)(tiles_m * a.tiles_n), (unsigned)splits);
         Timed tm(GGML_HIP_KCLASS_MMQ_MFMA, 2.0 * rows * (double)N * (double)(nb * 32));
         g.stat_mmq[Backend::MMQ_K_PLAIN]++;
-        with_qt(qt, [&](auto QT) { hipLaunchKernelGGL(k_mmq<CT(QT)>, grid, dim3(256), MMQ_LDS, g.stream, a); }, "mmq: bad weight type");
+        with_qt(qt, [&](auto QT) {
+            lds_opt_in<k_mmq<CT(QT)>>(MMQ_LDS, MMQ_LDS);  // 73.7 KB of dynamic LDS
+            hipLaunchKernelGGL(k_mmq<CT(QT)>, grid, dim3(256), MMQ_LDS, g.stream, a);
+        }, "mmq: bad weight type");
         HIP_CHECK(hipGetLastError());
         return;
     }
@@ -446,25 +432,16 @@ void mmq_f16_launch_multi(int qt, int nseg, const MmqSegHost *segs, const _Float
     const dim3 pgrid((unsigned)std::min(n_items, g.num_cus));
     Timed tm(GGML_HIP_KCLASS_MMQ_MFMA, 2.0 * rows * (double)N * (double)(nb * 32));
     if (all_w16) {  // both operands by DMA from resident f16 copies (kernels/mmq_w16.h)
-        static DevOnce w16_attr_set;
-        if (w16_attr_set.first())
-            HIP_CHECK(hipFuncSetAttribute((const void *)k_mmq_w16_p8, hipFuncAttributeMaxDynamicSharedMemorySize, W16_LDS));
+        lds_opt_in<k_mmq_w16_p8>(W16_LDS, W16_LDS);
         g.stat_mmq[Backend::MMQ_K_W16_P8]++;
         hipLaunchKernelGGL(k_mmq_w16_p8, pgrid, dim3(512), W16_LDS, g.stream, a, n_items, tiles_total, splits);
         HIP_CHECK(hipGetLastError());
         return;
     }
     // no resident copy (HBM full, option off): quantized blocks by LDS-DMA, dequantized in LDS (kernels/mmq_dmap8.h)
-    static DevOnce p8_attr_set;
-    if (p8_attr_set.first()) {
-        HIP_CHECK(hipFuncSetAttribute((const void *)k_mmq_dma_p8<QT_Q4_0>, hipFuncAttributeMaxDynamicSharedMemorySize, Dma8<QT_Q4_0>::LDS));
-        HIP_CHECK(hipFuncSetAttribute((const void *)k_mmq_dma_p8<QT_Q4_1>, hipFuncAttributeMaxDynamicSharedMemorySize, Dma8<QT_Q4_1>::LDS));
-        HIP_CHECK(hipFuncSetAttribute((const void *)k_mmq_dma_p8<QT_Q5_0>, hipFuncAttributeMaxDynamicSharedMemorySize, Dma8<QT_Q5_0>::LDS));
-        HIP_CHECK(hipFuncSetAttribute((const void *)k_mmq_dma_p8<QT_Q5_1>, hipFuncAttributeMaxDynamicSharedMemorySize, Dma8<QT_Q5_1>::LDS));
-        HIP_CHECK(hipFuncSetAttribute((const void *)k_mmq_dma_p8<QT_Q8_0>, hipFuncAttributeMaxDynamicSharedMemorySize, Dma8<QT_Q8_0>::LDS));
-    }
     g.stat_mmq[Backend::MMQ_K_DMA_P8]++;
     with_qt(qt, [&](auto QT) {
+        lds_opt_in<k_mmq_dma_p8<CT(QT)>>(Dma8<CT(QT)>::LDS, Dma8<CT(QT)>::LDS);
         hipLaunchKernelGGL(k_mmq_dma_p8<CT(QT)>, pgrid, dim3(512), Dma8<CT(QT)>::LDS, g.stream, a, n_items, tiles_total, splits);
     }, "mmq: bad weight type");
     HIP_CHECK(hipGetLastError());
@@ -632,10 +609,7 @@ void op_mul_mat(ggml_tensor *dst) {
             ga.causal = 0;
             ga.causal_past = 0;
             const int tiles_m = (int)((ga.M + 127) / 128);
-            static DevOnce attr_set;
-            if (attr_set.first()) {
-                HIP_CHECK(hipFuncSetAttribute((const void *)k_gemm_f16, hipFuncAttributeMaxDynamicSharedMemorySize, MMQ_LDS));
-            }
+            lds_opt_in<k_gemm_f16>(MMQ_LDS, MMQ_LDS);
             hipLaunchKernelGGL(k_gemm_f16, dim3((unsigned)(tiles_m * ga.tiles_n), (unsigned)(b->ne[2] * b->ne[3])), dim3(256),
                                MMQ_LDS, g.stream, ga);
         } else
@@ -938,6 +912,11 @@ void op_get_rows(ggml_tensor *dst) {
 // ggml_flash_attn (ggml_core.cpp) has refused every layout the kernels do not take; what is asserted here is that contract.
 static inline int prompt_attn_row_bytes(int64_t T);                                                       // plan_shapes.inc
 static inline int flash_attn_tile_queries(bool kv_f16, int64_t D, int64_t N, int64_t M, bool aligned16);  // plan_shapes.inc
+template <int D, int QR>
+static void launch_flash_attn_tile(const FlashAttnArgs &a, dim3 grid, size_t lds) {
+    lds_opt_in<k_flash_attn_tile<D, QR>>(lds, FLASH_ATTN_LDS_BYTES);
+    hipLaunchKernelGGL((k_flash_attn_tile<D, QR>), grid, dim3(256), lds, g.stream, a);
+}
 void op_flash_attn(ggml_tensor *dst) {
     const ggml_tensor *q = dst->src[0], *k = dst->src[1], *v = dst->src[2];
     const bool kv16 = k->type == GGML_TYPE_F16;
@@ -975,37 +954,25 @@ void op_flash_attn(ggml_tensor *dst) {
         a.row_bytes = prompt_attn_row_bytes(a.M);
         const size_t lds = (size_t)QR * a.row_bytes;
         BK_ASSERT(lds <= FLASH_ATTN_LDS_BYTES);
-        static DevOnce attr_set;
-        if (attr_set.first()) {
-            HIP_CHECK(hipFuncSetAttribute((const void *)k_flash_attn_tile<128, 32>, hipFuncAttributeMaxDynamicSharedMemorySize, FLASH_ATTN_LDS_BYTES));
-            HIP_CHECK(hipFuncSetAttribute((const void *)k_flash_attn_tile<64, 32>, hipFuncAttributeMaxDynamicSharedMemorySize, FLASH_ATTN_LDS_BYTES));
-            HIP_CHECK(hipFuncSetAttribute((const void *)k_flash_attn_tile<32, 32>, hipFuncAttributeMaxDynamicSharedMemorySize, FLASH_ATTN_LDS_BYTES));
-            HIP_CHECK(hipFuncSetAttribute((const void *)k_flash_attn_tile<128, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, FLASH_ATTN_LDS_BYTES));
-            HIP_CHECK(hipFuncSetAttribute((const void *)k_flash_attn_tile<64, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, FLASH_ATTN_LDS_BYTES));
-            HIP_CHECK(hipFuncSetAttribute((const void *)k_flash_attn_tile<32, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, FLASH_ATTN_LDS_BYTES));
-        }
         const int64_t wgs = (int64_t)((a.N + QR - 1) / QR) * a.H * a.B;
         BK_ASSERT(wgs < (1ll << 31));
         const dim3 grid((unsigned)wgs);
         if (QR == 32) {
-            if (a.D == 128) hipLaunchKernelGGL((k_flash_attn_tile<128, 32>), grid, dim3(256), lds, g.stream, a);
-            else if (a.D == 64) hipLaunchKernelGGL((k_flash_attn_tile<64, 32>), grid, dim3(256), lds, g.stream, a);
-            else hipLaunchKernelGGL((k_flash_attn_tile<32, 32>), grid, dim3(256), lds, g.stream, a);
+            if (a.D == 128) launch_flash_attn_tile<128, 32>(a, grid, lds);
+            else if (a.D == 64) launch_flash_attn_tile<64, 32>(a, grid, lds);
+            else launch_flash_attn_tile<32, 32>(a, grid, lds);
         } else {
-            if (a.D == 128) hipLaunchKernelGGL((k_flash_attn_tile<128, 16>), grid, dim3(256), lds, g.stream, a);
-            else if (a.D == 64) hipLaunchKernelGGL((k_flash_attn_tile<64, 16>), grid, dim3(256), lds, g.stream, a);
-            else hipLaunchKernelGGL((k_flash_attn_tile<32, 16>), grid, dim3(256), lds, g.stream, a);
+            if (a.D == 128) launch_flash_attn_tile<128, 16>(a, grid, lds);
+            else if (a.D == 64) launch_flash_attn_tile<64, 16>(a, grid, lds);
+            else launch_flash_attn_tile<32, 16>(a, grid, lds);
         }
     } else {
         const size_t lds = FLASH_ROW_RED + (((size_t)a.D * 4 + 15) & ~(size_t)15) + (((size_t)a.M * 4 + 15) & ~(size_t)15);
         BK_ASSERT(lds <= FLASH_ATTN_LDS_BYTES);
-        static DevOnce attr_set;
-        if (attr_set.first()) {
-            HIP_CHECK(hipFuncSetAttribute((const void *)k_flash_attn_row<true>, hipFuncAttributeMaxDynamicSharedMemorySize, FLASH_ATTN_LDS_BYTES));
-            HIP_CHECK(hipFuncSetAttribute((const void *)k_flash_attn_row<false>, hipFuncAttributeMaxDynamicSharedMemorySize, FLASH_ATTN_LDS_BYTES));
-        }
-        if (kv16) hipLaunchKernelGGL(k_flash_attn_row<true>, dim3((unsigned)rows), dim3(256), lds, g.stream, a);
-        else hipLaunchKernelGGL(k_flash_attn_row<false>, dim3((unsigned)rows), dim3(256), lds, g.stream, a);
+        with_bool(kv16, [&](auto KV16) {
+            lds_opt_in<k_flash_attn_row<CT(KV16)>>(lds, FLASH_ATTN_LDS_BYTES);
+            hipLaunchKernelGGL(k_flash_attn_row<CT(KV16)>, dim3((unsigned)rows), dim3(256), lds, g.stream, a);
+        });
     }
     HIP_CHECK(hipGetLastError());
 }

@@ -383,6 +383,15 @@ struct DevOnce {
         return true;
     }
 };
+// Above the 64 KiB default a kernel must ask for its dynamic LDS, once per device.  Every launch that may need more goes through
+// here first: `launch_lds` is what this launch takes, `max_bytes` the most its site ever asks for.  A launch below the default leaves
+// the flag alone, so a later large one still opts in.
+template <auto Kern>
+void lds_opt_in(size_t launch_lds, size_t max_bytes) {
+    static DevOnce opted;
+    if (launch_lds > 64 * 1024 && opted.first())
+        HIP_CHECK(hipFuncSetAttribute((const void *)Kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)max_bytes));
+}
 
 int kt_of(ggml_type t) {
     switch (t) {

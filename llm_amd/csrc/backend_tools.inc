@@ -27,10 +27,7 @@ void empty_launch(int wgs, int threads, int lds, long long *ts, int idx) {
     memset(&a, 0, sizeof(a));
     a.ts = ts;
     a.idx = idx;
-    static DevOnce attr;
-    if (attr.first()) {
-        HIP_CHECK(hipFuncSetAttribute((const void *)k_empty<NARG>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    }
+    lds_opt_in<k_empty<NARG>>((size_t)lds, 160 * 1024);
     hipLaunchKernelGGL(k_empty<NARG>, dim3(wgs), dim3(threads), (size_t)lds, g.stream, a, 0);
 }
 }  // namespace
@@ -90,11 +87,6 @@ int ggml_hip_debug_prompt_attention(const float *q, const uint16_t *mem_k, const
     finish_pending();
     const int64_t D = E / H, Hkv = Egqa / D, T = (int64_t)n_past + N, Tp = (T + 7) & ~(int64_t)7;
     if (T > C || (fused && !prompt_attn_fits(D, T))) return -1;
-    static DevOnce attr;
-    if (attr.first()) {
-        HIP_CHECK(hipFuncSetAttribute((const void *)k_gemm_f16, hipFuncAttributeMaxDynamicSharedMemorySize, MMQ_LDS));
-        HIP_CHECK(hipFuncSetAttribute((const void *)k_gemm_f16_b16, hipFuncAttributeMaxDynamicSharedMemorySize, MMQ_LDS));
-    }
     char *dq, *dk, *dv, *dout, *dsc, *dp;
     const size_t nq = (size_t)N * E * 4, nkv = (size_t)C * Egqa * 2, nsc = (size_t)H * N * T * 4, np = (size_t)H * N * Tp * 2;
     dev_malloc((void **)&dq, nq, "debug q");
@@ -364,7 +356,7 @@ int ggml_hip_debug_mat_vec_kbig(const struct ggml_tensor *w0, const struct ggml_
     const size_t n_out = (size_t)Mrow * 4;
     char *dout = debug_buf(n_out, nullptr, owned);
     char *dy = (xsrc == KX_NORM && y_out) ? debug_buf((size_t)K * 4, nullptr, owned) : nullptr;
-    const KBigSrc src{xsrc, (const float *)dx, (const float *)dxw, eps, epi == KE_ROW ? (float *)dy : nullptr};
+    const RowSrc src{xsrc, (const float *)dx, (const float *)dxw, eps, epi == KE_ROW ? (float *)dy : nullptr};
     char *dk = nullptr, *dv = nullptr;
     const size_t nkv = epi == KE_QKV ? (size_t)C * Ms[1] * 2 : 0;
     if (epi == KE_QKV) {  // as plan_launch_k: one launch per run of equal types, seg_kind = the matrices' kinds
@@ -394,7 +386,7 @@ int ggml_hip_debug_mat_vec_kbig(const struct ggml_tensor *w0, const struct ggml_
     if (dy && epi != KE_ROW) {  // the normed row of the same staging code: the tap of a KE_ROW launch of w0
         const KWeight *ws1[1] = {&kw[0]};
         float *ds1[1] = {(float *)debug_buf((size_t)Ms[0] * 4, nullptr, owned)};
-        launch_kbig(1, ws1, ds1, KBigSrc{KX_NORM, (const float *)dx, (const float *)dxw, eps, (float *)dy}, nullptr);
+        launch_kbig(1, ws1, ds1, RowSrc{KX_NORM, (const float *)dx, (const float *)dxw, eps, (float *)dy}, nullptr);
     }
     d2h_queue(out, dout, n_out + DEBUG_GUARD);
     if (dy) d2h_queue(y_out, dy, (size_t)K * 4 + DEBUG_GUARD);
@@ -458,7 +450,7 @@ int ggml_hip_debug_mat_vec_f16(const struct ggml_tensor *w0, const struct ggml_t
     const size_t n_out = (size_t)ncols * Mrow * 4;
     char *dout = debug_buf(n_out, nullptr, owned);
     char *dy = (xsrc == KX_NORM && y_out) ? debug_buf(nx, nullptr, owned) : nullptr;
-    const F16Src src{xsrc, (const float *)dx, (const float *)dxw, eps, epi == KE_ROW ? (float *)dy : nullptr};
+    const RowSrc src{xsrc, (const float *)dx, (const float *)dxw, eps, epi == KE_ROW ? (float *)dy : nullptr};
     char *dk = nullptr, *dv = nullptr;
     const size_t nkv = epi == KE_QKV ? (size_t)C * Ms[1] * 2 : 0;
     if (epi == KE_QKV) {
@@ -496,7 +488,7 @@ int ggml_hip_debug_mat_vec_f16(const struct ggml_tensor *w0, const struct ggml_t
     }
     if (dy && epi != KE_ROW) {  // the normed rows of the same staging code: the tap of a KE_ROW launch of w0
         float *ds1[1] = {(float *)debug_buf((size_t)ncols * Ms[0] * 4, nullptr, owned)};
-        launch_f16(1, fw, ds1, K, F16Src{KX_NORM, (const float *)dx, (const float *)dxw, eps, (float *)dy}, nullptr, ncols);
+        launch_f16(1, fw, ds1, K, RowSrc{KX_NORM, (const float *)dx, (const float *)dxw, eps, (float *)dy}, nullptr, ncols);
     }
     d2h_queue(out, dout, n_out + DEBUG_GUARD);
     if (dy) d2h_queue(y_out, dy, nx + DEBUG_GUARD);

@@ -5,7 +5,7 @@
 //   crates/models/llama/src/lib.rs             Llama {new, start_session, evaluate}  (:43-368)
 // The reference is Rust and no Rust toolchain exists in this image; this file keeps its structure,
 // names and call order so that the graph handed to ggml_graph_compute is node-for-node the graph the
-// Rust code builds (tests/test_graph_shape.py counts the nodes).  All compute goes through the C ABI
+// Rust code builds (tests/test_llama_gpu.py counts the nodes).  All compute goes through the C ABI
 // of include/ggml_hip.h.
 #if defined(__x86_64__)
 #include <immintrin.h>

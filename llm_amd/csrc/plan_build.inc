@@ -42,8 +42,8 @@ static bool plan_weights_resident(const LlamaMatch &m) {
     if (m.stage_in && !ok_raw(m.stage_in)) return false;
     if (m.stage_out && !ok_raw(m.stage_out)) return false;
     for (auto &l : m.layers) {
-        for (const ggml_tensor *w : {l.wq, l.wk, l.wv, l.wo, l.w1, l.w2, l.w3})
-            if (!ok_q(w)) return false;
+        for (int i = 0; i < LAYER_MATS; i++)
+            if (!ok_q(l.at(i))) return false;
         if (!ok_raw(l.attn_norm) || !ok_raw(l.ffn_norm)) return false;
     }
     return true;
@@ -61,9 +61,10 @@ static std::vector<uint64_t> plan_signature(const LlamaMatch &m, bool session = 
     for (const ggml_tensor *t : {m.wte, m.norm, m.output, m.stage_in, m.stage_out}) s.push_back(t ? rec_id(t) : 0);
     if (session)
         for (const ggml_tensor *t : {m.memory_k, m.memory_v}) s.push_back(rec_id(t));
-    for (auto &l : m.layers)
-        for (const ggml_tensor *t : {l.attn_norm, l.wq, l.wk, l.wv, l.wo, l.ffn_norm, l.w1, l.w2, l.w3})
-            s.push_back(rec_id(t));
+    for (auto &l : m.layers) {
+        for (const ggml_tensor *t : {l.attn_norm, l.ffn_norm}) s.push_back(rec_id(t));
+        for (int i = 0; i < LAYER_MATS; i++) s.push_back(rec_id(l.at(i)));
+    }
     if (m.f16w) {  // an F16 weight record is pointer, stride and rows: a view of another part of a record is another weight
         auto rec = [&](const ggml_tensor *t) {
             if (!t) return;
@@ -74,29 +75,49 @@ static std::vector<uint64_t> plan_signature(const LlamaMatch &m, bool session = 
         rec(m.wte);
         rec(m.output);
         for (auto &l : m.layers)
-            for (const ggml_tensor *t : {l.wq, l.wk, l.wv, l.wo, l.w1, l.w2, l.w3}) rec(t);
+            for (int i = 0; i < LAYER_MATS; i++) rec(l.at(i));
     }
     if (!session) return s;
     s.push_back(m.logits ? (uint64_t)(uintptr_t)dev_ptr(m.logits) : 0);
     s.push_back(m.embedding ? (uint64_t)(uintptr_t)dev_ptr(m.embedding) : 0);
     return s;
 }
+// every matrix of the model: the layers' seven each and the lm_head
+static std::vector<const ggml_tensor *> plan_matrices(const LlamaMatch &m) {
+    std::vector<const ggml_tensor *> ws;
+    for (auto &l : m.layers)
+        for (int i = 0; i < LAYER_MATS; i++) ws.push_back(l.at(i));
+    if (m.output) ws.push_back(m.output);
+    return ws;
+}
+// the bytes the resident f16 copies of `ws` would take that are not there yet (M x K x 2 each, whichever layout the record has)
+static size_t w16_need(const std::vector<const ggml_tensor *> &ws) {
+    size_t need = 0;
+    for (auto *w : ws) {
+        DevTensor *e = plan_rec(w);
+        if (e && !e->w16) need += e->ksoa ? (size_t)e->kw.M * (size_t)e->kw.nsb * 512 : (size_t)e->qw.M * e->qw.nb * 64;
+    }
+    return need;
+}
+// the layers' matrices as a plan holds them: of(tensor) for each
+template <class W, class F>
+static std::vector<LayerMats<W>> plan_layer_weights(const LlamaMatch &m, F &&of) {
+    std::vector<LayerMats<W>> v(m.layers.size());
+    for (size_t il = 0; il < v.size(); il++)
+        for (int i = 0; i < LAYER_MATS; i++) v[il].at(i) = of(m.layers[il].at(i));
+    return v;
+}
 // Prompt plan of a K-quant model: its GEMMs have no operand but the resident f16 copy of each weight (mul_mat_k_gemm,
 // backend_ops.inc) — every matrix must have one before anything is launched; they are made here, all or none, by the first batch
 // the prompt plan sees (mmq_min = 32 tokens and more; the executor alone waits for W16_MIN_TOKENS, but without a copy its K path
 // streams every matrix through the mat-vec kernel: 1.7k tok/s at n_batch = 48).  false = no room: the node-by-node executor runs.
 static bool k_prompt_weights(const LlamaMatch &m, DecodePlan *p) {
-    std::vector<const ggml_tensor *> ws;
-    for (auto &l : m.layers)
-        for (const ggml_tensor *w : {l.wq, l.wk, l.wv, l.wo, l.w1, l.w2, l.w3}) ws.push_back(w);
-    if (m.output) ws.push_back(m.output);
-    size_t need = 0;
+    const std::vector<const ggml_tensor *> ws = plan_matrices(m);
     for (auto *w : ws) {
         DevTensor *e = plan_rec(w);
         if (!e || !e->ksoa || (uintptr_t)w->data != e->host) return false;
-        if (!e->w16) need += (size_t)e->kw.M * (size_t)e->kw.nsb * 512;
     }
-    if (need) {  // all or none: a model either fits twice or it does not
+    if (const size_t need = w16_need(ws)) {  // all or none: a model either fits twice or it does not
         size_t free_b = 0, total_b = 0;
         if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || free_b < need + ((size_t)1 << 30) + w16_headroom()) return false;
         for (auto *w : ws)
@@ -113,12 +134,7 @@ static bool k_prompt_weights(const LlamaMatch &m, DecodePlan *p) {
         w.w16 = e->w16;
         return w;
     };
-    for (int il = 0; il < m.L; il++) {
-        DecodePlan::LW &w = p->lw[il];
-        const auto &l = m.layers[il];
-        w.wq = qw_of(l.wq); w.wk = qw_of(l.wk); w.wv = qw_of(l.wv); w.wo = qw_of(l.wo);
-        w.w1 = qw_of(l.w1); w.w2 = qw_of(l.w2); w.w3 = qw_of(l.w3);
-    }
+    p->lw = plan_layer_weights<QWeight>(m, qw_of);
     if (m.output) p->output = qw_of(m.output);
     p->w16_gen = g.w16_gen;
     return true;
@@ -145,20 +161,80 @@ static void xcd_labels_probe() {
     HIP_CHECK(hipFree(d));
     g.xcd_labels = ok ? 1 : 0;
 }
+// One pool for all persistent activations of a plan, declared once: take(field, bytes) gives `field` the next region of the pool,
+// 256-byte aligned, or leaves it null where the plan has no such buffer (bytes = 0) — the launchers test gran, ogran, logits_alt,
+// bcols, the [block][8] tables and the k_* rows for exactly that.  plan_pool_layout runs twice: without a base it only adds up.
+struct PoolCarver {
+    char *base;
+    size_t off = 0;
+    template <class T>
+    void take(T *&field, size_t bytes) {
+        if (base && bytes) field = (T *)(base + off);
+        off = (off + bytes + 255) & ~(size_t)255;
+    }
+};
+static void plan_pool_layout(DecodePlan *p, PoolCarver &c) {
+    const LlamaMatch &m = p->m;
+    const size_t R = (size_t)m.N;  // activation rows: 1 for decode, 2..31 for a prompt chunk, the columns of a batched step, more for the prompt plan
+    const size_t E = (size_t)m.E, F = (size_t)m.F, S = (size_t)p->att_S;
+    const bool one = m.N == 1, spec = one && m.logits, multi = m.N >= 2 && !m.prompt, kq = m.kquant;
+    // scratch of the split attention, and the hand-off granules of the in-launch attention exchanges: one set per LAYER for a single token (the tag is the token's epoch alone)
+    const size_t Lg = one ? (size_t)m.L : 1;
+    c.take(p->att_sc, (size_t)m.H * m.C * 4);
+    c.take(p->att_pmax, (size_t)m.H * S * 4);
+    c.take(p->att_part, (size_t)m.H * S * m.D * 4);
+    c.take(p->att_mxg, Lg * m.H * S * 8);
+    c.take(p->att_sumg, Lg * m.H * S * 16);
+    c.take(p->att_partg, one ? Lg * m.H * S * m.D * 8 : 0);
+    c.take(p->att_cnt, (size_t)m.H * 4);
+    c.take(p->hot, 256);
+    c.take(p->logits_alt, spec ? (size_t)m.V * 4 : 0);
+    c.take(p->emb_alt, spec ? E * 4 : 0);
+    c.take(p->epoch, 256);
+    const size_t units = (size_t)((m.E + 2 * m.Egqa) / 2);  // granules of a layer's wq|wk|wv rows
+    c.take(p->gran, one ? (size_t)m.L * units * 8 : 0);
+    c.take(p->dead_gran, one ? units * 8 : 0);  // never written (tag 0): option test_fused_timeout
+    c.take(p->ogran, one ? (size_t)m.L * (size_t)(m.E / 32) * OGRAN * 8 : 0);  // the heads' outputs as granules (WO form)
+    // a batched step's per-column table and its results, one row per column: the other plans' logits_out / emb_out are graph nodes (build_plan)
+    c.take(p->bcols, p->batch ? sizeof(BatchCols) : 0);
+    c.take(p->logits_out, p->batch ? R * m.V * 4 : 0);
+    c.take(p->emb_out, p->batch ? R * E * 4 : 0);
+    c.take(p->prm, sizeof(DecParams));
+    c.take(p->rope, std::max<size_t>(8, R) * 128 * 4);
+    c.take(p->xa, R * E * 4);
+    c.take(p->xb, R * E * 4);
+    c.take(p->q, R * E * 4);
+    c.take(p->gate, R * F * 4);
+    c.take(p->e_lo, R * E / 2);
+    c.take(p->e_hi, R * E / 2);
+    c.take(p->e_d, R * E / 32 * 4);
+    c.take(p->e_s, R * E / 32 * 4);
+    c.take(p->f_lo, R * F / 2);
+    c.take(p->f_hi, R * F / 2);
+    c.take(p->f_d, R * F / 32 * 4);
+    c.take(p->f_s, R * F / 32 * 4);
+    const size_t passes = (R + 7) / 8;  // multi-token plan: one [block][8] table per pass of 8 rows
+    c.take(p->e_dT, multi ? passes * E / 32 * 32 : 0);
+    c.take(p->e_sT, multi ? passes * E / 32 * 32 : 0);
+    c.take(p->f_dT, multi ? passes * F / 32 * 32 : 0);
+    c.take(p->f_sT, multi ? passes * F / 32 * 32 : 0);
+    const size_t kW = std::max(E, F);
+    c.take(p->k_kf, kq ? R * m.Egqa * 4 : 0);
+    c.take(p->k_vf, kq ? R * m.Egqa * 4 : 0);
+    c.take(p->k_att, kq || m.f16w ? R * E * 4 : 0);  // (the F16 plan's attention output too: the f32 row wo stages)
+    c.take(p->k_g3, kq ? R * F * 4 : 0);
+    c.take(p->k_q8, kq ? R * kW : 0);
+    c.take(p->k_d8, kq ? R * kW / 256 * 4 : 0);
+    c.take(p->k_bs, kq ? R * kW / 256 * 32 : 0);
+    // (the prompt plan's other buffers live only during one evaluation: shared workspace, plan_launch_prompt)
+    c.take(p->p_tok, m.prompt ? R * 4 : 0);
+}
 // batch: the plan of a batched step (m: its first graph's match with N = the columns)
 static DecodePlan *build_plan(const LlamaMatch &m, std::vector<uint64_t> sig, bool batch = false) {
     if (m.prompt && !m.kquant) {  // prompt plan: resident f16 copies of the GEMM weights, all or none (a model either fits twice or not)
-        std::vector<const ggml_tensor *> ws;
-        for (auto &l : m.layers)
-            for (const ggml_tensor *w : {l.wq, l.wk, l.wv, l.wo, l.w1, l.w2, l.w3}) ws.push_back(w);
-        if (m.output) ws.push_back(m.output);
-        size_t need = 0;
-        for (auto *w : ws) {
-            DevTensor *e = plan_rec(w);
-            if (e && !e->w16) need += (size_t)e->qw.M * e->qw.nb * 64;
-        }
+        const std::vector<const ggml_tensor *> ws = plan_matrices(m);
         size_t free_b = 0, total_b = 0;
-        const bool room = hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b >= need + w16_headroom();
+        const bool room = hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b >= w16_need(ws) + w16_headroom();
         if (room)
             for (auto *w : ws) ensure_w16(plan_rec(w));
     }
@@ -184,109 +260,24 @@ static DecodePlan *build_plan(const LlamaMatch &m, std::vector<uint64_t> sig, bo
         p->mem_k = (__half *)dev_ptr(m.memory_k);
         p->mem_v = (__half *)dev_ptr(m.memory_v);
     }
-    for (auto &l : m.layers) {
-        DecodePlan::LW w;
-        memset(&w, 0, sizeof(w));
-        if (m.f16w) {
-            DecodePlan::FLW fw;
-            fw.wq = plan_f16w(l.wq); fw.wk = plan_f16w(l.wk); fw.wv = plan_f16w(l.wv); fw.wo = plan_f16w(l.wo);
-            fw.w1 = plan_f16w(l.w1); fw.w2 = plan_f16w(l.w2); fw.w3 = plan_f16w(l.w3);
-            p->flw.push_back(fw);
-        } else if (m.kquant) {
-            DecodePlan::KLW kw;
-            kw.wq = plan_kw(l.wq); kw.wk = plan_kw(l.wk); kw.wv = plan_kw(l.wv); kw.wo = plan_kw(l.wo);
-            kw.w1 = plan_kw(l.w1); kw.w2 = plan_kw(l.w2); kw.w3 = plan_kw(l.w3);
-            p->klw.push_back(kw);
-        } else {
-            w.wq = plan_qw(l.wq); w.wk = plan_qw(l.wk); w.wv = plan_qw(l.wv); w.wo = plan_qw(l.wo);
-            w.w1 = plan_qw(l.w1); w.w2 = plan_qw(l.w2); w.w3 = plan_qw(l.w3);
-        }
-        w.attn_norm = (const float *)dev_ptr(l.attn_norm);
-        w.ffn_norm = (const float *)dev_ptr(l.ffn_norm);
-        p->lw.push_back(w);
-    }
+    if (m.f16w) p->flw = plan_layer_weights<F16W>(m, plan_f16w);
+    else if (m.kquant) p->klw = plan_layer_weights<KWeight>(m, plan_kw);
+    else p->lw = plan_layer_weights<QWeight>(m, plan_qw);
+    for (auto &l : m.layers) p->ln.push_back({(const float *)dev_ptr(l.attn_norm), (const float *)dev_ptr(l.ffn_norm)});
+    // the results of every plan but a batched step's are the graph's own nodes; a batched step's are rows of the pool (plan_pool_layout)
     if (m.embedding && !batch) p->emb_out = (float *)dev_ptr(m.embedding);
     if (m.logits && !batch) p->logits_out = dev_ptr(m.logits);
-    // one pool for all persistent activations
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off = (off + bytes + 255) & ~(size_t)255; return o; };
-    const size_t R = (size_t)m.N;  // activation rows: 1 for decode, 2..8 for a prompt chunk, more for the prompt plan
-    const int att_S = plan_att_S(m.H);
-    const size_t o_asc = take((size_t)m.H * m.C * 4), o_apm = take((size_t)m.H * att_S * 4), o_apt = take((size_t)m.H * att_S * m.D * 4);
-    // hand-off granules of the in-launch attention exchanges: one set per LAYER (the tag is the token's epoch alone)
-    const size_t Lg = m.N == 1 ? (size_t)m.L : 1;
-    const size_t o_amxg = take(Lg * m.H * att_S * 8), o_asmg = take(Lg * m.H * att_S * 16), o_aptg = take(m.N == 1 ? Lg * m.H * att_S * m.D * 8 : 0),
-                 o_acnt = take((size_t)m.H * 4);
-    const size_t o_hot = take(256);
-    const size_t o_lalt = take(m.N == 1 && m.logits ? (size_t)m.V * 4 : 0), o_ealt = take(m.N == 1 && m.logits ? (size_t)m.E * 4 : 0);
-    const size_t o_epoch = take(256), o_gran = take(m.N == 1 ? (size_t)m.L * (size_t)((m.E + 2 * m.Egqa) / 2) * 8 : 0);
-    const size_t o_dead = take(m.N == 1 ? (size_t)((m.E + 2 * m.Egqa) / 2) * 8 : 0);  // never written (tag 0): option test_fused_timeout
-    const size_t o_ogran = take(m.N == 1 ? (size_t)m.L * (size_t)(m.E / 32) * OGRAN * 8 : 0);  // the heads' outputs as granules (WO form)
-    const size_t o_bcols = take(batch ? sizeof(BatchCols) : 0), o_blogits = take(batch ? R * m.V * 4 : 0), o_bemb = take(batch ? R * m.E * 4 : 0);
-    const size_t o_prm = take(sizeof(DecParams)), o_rope = take(std::max<size_t>(8, R) * 128 * 4), o_xa = take(R * m.E * 4), o_xb = take(R * m.E * 4),
-                 o_q = take(R * m.E * 4), o_gate = take(R * m.F * 4), o_elo = take(R * m.E / 2), o_ehi = take(R * m.E / 2),
-                 o_ed = take(R * m.E / 32 * 4), o_es = take(R * m.E / 32 * 4), o_flo = take(R * m.F / 2),
-                 o_fhi = take(R * m.F / 2), o_fd = take(R * m.F / 32 * 4), o_fs = take(R * m.F / 32 * 4);
-    const bool multi = m.N >= 2 && !m.prompt;
-    const size_t passes = (R + 7) / 8;  // one [block][8] table per pass of 8 rows
-    const size_t o_edT = take(multi ? passes * m.E / 32 * 32 : 0), o_esT = take(multi ? passes * m.E / 32 * 32 : 0),
-                 o_fdT = take(multi ? passes * m.F / 32 * 32 : 0), o_fsT = take(multi ? passes * m.F / 32 * 32 : 0);
-    const size_t kW = (size_t)std::max(m.E, m.F);
-    const size_t o_kkf = take(m.kquant ? R * m.Egqa * 4 : 0), o_kvf = take(m.kquant ? R * m.Egqa * 4 : 0),
-                 o_katt = take(m.kquant || m.f16w ? R * m.E * 4 : 0), o_kg3 = take(m.kquant ? R * m.F * 4 : 0),
-                 o_kq8 = take(m.kquant ? R * kW : 0), o_kd8 = take(m.kquant ? R * kW / 256 * 4 : 0), o_kbs = take(m.kquant ? R * kW / 256 * 32 : 0);
-    const bool prompt = m.prompt;  // the prompt plan's buffers live only during one evaluation: shared workspace (plan_launch_prompt)
-    size_t o_tok = 0, o_rope_n = 0;
-    if (prompt) {
-        o_tok = take(R * 4);
-        o_rope_n = take(R * 128 * 4);
-    }
-    dev_malloc((void **)&p->pool, off, "a decode plan's activation pool");
-    HIP_CHECK(hipMemsetAsync(p->pool, 0, off, g.stream));
-    p->prm = (DecParams *)(p->pool + o_prm);
-    if (batch) {
-        p->bcols = (BatchCols *)(p->pool + o_bcols);
-        p->logits_out = p->pool + o_blogits;
-        p->emb_out = (float *)(p->pool + o_bemb);
-    }
-    p->epoch = (unsigned *)(p->pool + o_epoch);
-    p->hot = p->pool + o_hot;
-    if (m.N == 1 && m.logits) { p->logits_alt = p->pool + o_lalt; p->emb_alt = (float *)(p->pool + o_ealt); }
+    p->att_S = plan_att_S(m.H);
+    PoolCarver sizes{nullptr};
+    plan_pool_layout(p, sizes);
+    dev_malloc((void **)&p->pool, sizes.off, "a decode plan's activation pool");
+    HIP_CHECK(hipMemsetAsync(p->pool, 0, sizes.off, g.stream));
+    PoolCarver carve{p->pool};
+    plan_pool_layout(p, carve);
     if (!g.ferr_pin) {
         HIP_CHECK(hipHostMalloc((void **)&g.ferr_pin, 64, hipHostMallocDefault));
         *g.ferr_pin = 0;
     }
     p->ferr = g.ferr_pin;  // device-visible address of the slot's pinned word
-    if (m.N == 1) p->gran = (unsigned long long *)(p->pool + o_gran);
-    if (m.N == 1) p->dead_gran = (unsigned long long *)(p->pool + o_dead);
-    if (m.N == 1) p->ogran = (unsigned long long *)(p->pool + o_ogran);
-    p->rope = (float *)(p->pool + (prompt ? o_rope_n : o_rope));
-    if (prompt) p->p_tok = (int *)(p->pool + o_tok);
-    p->att_sc = (float *)(p->pool + o_asc);
-    p->att_pmax = (float *)(p->pool + o_apm);
-    p->att_part = (float *)(p->pool + o_apt);
-    p->att_S = att_S;
-    p->att_mxg = (unsigned long long *)(p->pool + o_amxg);
-    p->att_sumg = (unsigned long long *)(p->pool + o_asmg);
-    if (m.N == 1) p->att_partg = (unsigned long long *)(p->pool + o_aptg);
-    p->att_cnt = (unsigned *)(p->pool + o_acnt);
-    p->xa = (float *)(p->pool + o_xa);
-    p->xb = (float *)(p->pool + o_xb);
-    p->q = (float *)(p->pool + o_q);
-    p->gate = (float *)(p->pool + o_gate);
-    p->e_lo = (int8_t *)(p->pool + o_elo); p->e_hi = (int8_t *)(p->pool + o_ehi);
-    p->e_d = (float *)(p->pool + o_ed);    p->e_s = (int *)(p->pool + o_es);
-    p->f_lo = (int8_t *)(p->pool + o_flo); p->f_hi = (int8_t *)(p->pool + o_fhi);
-    p->f_d = (float *)(p->pool + o_fd);    p->f_s = (int *)(p->pool + o_fs);
-    if (m.f16w) p->k_att = (float *)(p->pool + o_katt);  // the F16 plan's attention output: the f32 row wo stages
-    if (m.kquant) {
-        p->k_kf = (float *)(p->pool + o_kkf); p->k_vf = (float *)(p->pool + o_kvf);
-        p->k_att = (float *)(p->pool + o_katt); p->k_g3 = (float *)(p->pool + o_kg3);
-        p->k_q8 = (int8_t *)(p->pool + o_kq8); p->k_d8 = (float *)(p->pool + o_kd8); p->k_bs = (int16_t *)(p->pool + o_kbs);
-    }
-    if (multi) {
-        p->e_dT = (float *)(p->pool + o_edT); p->e_sT = (int *)(p->pool + o_esT);
-        p->f_dT = (float *)(p->pool + o_fdT); p->f_sT = (int *)(p->pool + o_fsT);
-    }
     return p;
 }

@@ -66,44 +66,28 @@ static void launch_big(const BigArgs &a) {
 }
 template <int QT>
 static void launch_qkv_attn(const BigArgs &ba, const FusedAttnArgs &fa, const FusedShape &sh, size_t lds) {
-    if (lds > 64 * 1024) {  // a context whose score rows exceed the 64 KiB default: the kernel asks for its dynamic LDS once per device
-        static DevOnce done;
-        if (done.first()) {
-            HIP_CHECK(hipFuncSetAttribute((const void *)k_qkv_attn<QT, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ATTN_DECODE_LDS_MAX));
-            HIP_CHECK(hipFuncSetAttribute((const void *)k_qkv_attn<QT, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ATTN_DECODE_LDS_MAX));
-        }
-    }
     with_bool(ba.probe || ba.ts, [&](auto INSTR) {
+        lds_opt_in<k_qkv_attn<QT, CT(INSTR)>>(lds, ATTN_DECODE_LDS_MAX);  // (a context whose score rows exceed the default)
         hipLaunchKernelGGL((k_qkv_attn<QT, CT(INSTR)>), dim3(sh.G), dim3(1024), lds, g.stream, ba, fa);
     });
 }
 template <int QT>
 static void launch_qkv_attn_wo(const BigArgs &ba, const FusedAttnArgs &fa, const WoTailArgs &wt, const FusedShape &sh, size_t lds) {
     const bool two = (wt.w.nb + 63) / 64 <= 2;  // blocks of a row per lane: 2 steps up to 4096-wide rows, else up to 4
-    if (lds > 64 * 1024) {
-        static DevOnce done;
-        if (done.first()) {
-            HIP_CHECK(hipFuncSetAttribute((const void *)k_qkv_attn_wo<QT, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ATTN_DECODE_LDS_MAX));
-            HIP_CHECK(hipFuncSetAttribute((const void *)k_qkv_attn_wo<QT, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ATTN_DECODE_LDS_MAX));
-        }
-    }
-    if (two)
-        hipLaunchKernelGGL((k_qkv_attn_wo<QT, 2>), dim3(sh.G), dim3(1024), lds, g.stream, ba, fa, wt);
-    else
-        hipLaunchKernelGGL((k_qkv_attn_wo<QT, 4>), dim3(sh.G), dim3(1024), lds, g.stream, ba, fa, wt);
+    with_bool(two, [&](auto TWO) {
+        constexpr int STEPS = CT(TWO) ? 2 : 4;
+        lds_opt_in<k_qkv_attn_wo<QT, STEPS>>(lds, ATTN_DECODE_LDS_MAX);
+        hipLaunchKernelGGL((k_qkv_attn_wo<QT, STEPS>), dim3(sh.G), dim3(1024), lds, g.stream, ba, fa, wt);
+    });
 }
 // THE launch of k_attn_decode, for all three plans that have one: a grid of heads x N queries (query n attends to positions
 // <= n_past + n) of layer il, `rows` positions in its LDS arrays.  f16d / out_f32: the re-quantized row for wo as Q8 with an
 // f16-rounded scale or not (p->e_*), and (K plan) the f32 row as well; dT / sT: the chunk plan's transposed scale tables.
 static void launch_attn_decode(const DecodePlan *p, int il, int N, int64_t rows, bool f16d, float *out_f32, long long *ts,
                                float *dT = nullptr, int *sT = nullptr) {
-    static DevOnce opted;  // above the 64 KiB default a kernel must ask for its dynamic LDS once
-    if (opted.first()) {
-        HIP_CHECK(hipFuncSetAttribute((const void *)k_attn_decode<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ATTN_DECODE_LDS_MAX));
-        HIP_CHECK(hipFuncSetAttribute((const void *)k_attn_decode<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ATTN_DECODE_LDS_MAX));
-    }
     const LlamaMatch &m = p->m;
     with_bool(f16d, [&](auto F16D) {
+        lds_opt_in<k_attn_decode<CT(F16D)>>(attn_decode_lds(rows, m.D), ATTN_DECODE_LDS_MAX);
         hipLaunchKernelGGL(k_attn_decode<CT(F16D)>, dim3((unsigned)m.H, (unsigned)N), dim3(1024), attn_decode_lds(rows, m.D), g.stream,
                            (const float *)p->q, (const __half *)p->mem_k_at(il), (const __half *)p->mem_v_at(il), (const DecParams *)p->prm,
                            m.kq_scale, (int)m.D, (int)(m.H / m.Hkv), m.Egqa, m.C, out_f32, p->e_lo, p->e_hi, p->e_d, p->e_s, ts, (int)m.H,
@@ -164,6 +148,64 @@ static void for_each_type_run(const KWeight *const *ws, int n, F &&f) {
         f(i, j);
         i = j;
     }
+}
+// where a plan's final norm and lm_head write: the caller-visible mirrors, or the alternates while the speculative graph is captured (see DecodePlan::logits_alt)
+struct ResultDst {
+    float *emb;
+    char *logits;
+};
+static ResultDst plan_result_dst(const DecodePlan *p) {
+    return ResultDst{p->spec_out && p->emb_out ? p->emb_alt : p->emb_out, p->spec_out ? p->logits_alt : p->logits_out};
+}
+// ---- what the K plan and the F16 plan share: everything around their mat-vecs ----
+// The opening: the residual rows from the hand-off buffer, or the embedding rows of the N token ids (`embed`: the plan's own get_rows
+// launch, embed_bytes per element its books); then one (cos, sin) table per column, 128 floats apart (batch: each at its own session's position)
+template <class F>
+static void plan_open_rows(DecodePlan *p, LaunchCtx &cx, bool batch, double embed_bytes, F &&embed) {
+    const LlamaMatch &m = p->m;
+    const int N = m.N;
+    const float theta_scale = powf(m.freq_base, -2.0f / m.n_dims);
+    if (!m.wte) {
+        if (cx.want(GGML_HIP_KCLASS_OTHER, (double)N * m.E * 8.0))
+            HIP_CHECK(hipMemcpyAsync(p->xa, p->stage_in, (size_t)N * m.E * 4, hipMemcpyDeviceToDevice, g.stream));
+    } else {  // DecParams::tokens[0] == token: the ids of the chunk / of the step's columns
+        cx.other((double)N * m.E * embed_bytes, embed);
+    }
+    cx.other((double)N * m.D * 4.0, [&] {
+        if (batch)
+            hipLaunchKernelGGL(k_rope_table_batch, dim3((unsigned)N), dim3(128), 0, g.stream, (const BatchCols *)p->bcols, theta_scale, m.freq_scale,
+                               (int)(m.D >> 1), p->rope);
+        else
+            hipLaunchKernelGGL(k_rope_table, dim3((unsigned)N), dim3(128), 0, g.stream, (const DecParams *)p->prm, theta_scale, m.freq_scale,
+                               (int)(m.D >> 1), p->rope, p->epoch);  // block 0 also opens the token's epoch (the tag of k_attn_split_one's granules)
+    });
+}
+// The attention of layer il: the f32 row of the merged heads in p->k_att for wo's staging (the Q8_0 copy of the heads' outputs goes to
+// the plan's unused E-wide Q8_0 row).  long_ctx: every CU pulls a piece of the cache (k_attn_split_one, kernels/decode_attn_split.h)
+static void launch_attn_decode_batch(const DecodePlan *p, int il, int N, bool f16d, float *out_f32);
+static void plan_attn_f32(DecodePlan *p, LaunchCtx &cx, int il, bool long_ctx, bool batch) {
+    const LlamaMatch &m = p->m;
+    const int N = m.N;
+    const double bytes = (double)N * ((double)(m.n_past + N) * m.Egqa * 4.0 + m.E * 9.0);
+    if (!cx.want(GGML_HIP_KCLASS_ATTN, bytes)) return;
+    Timed tm(GGML_HIP_KCLASS_ATTN, bytes);
+    if (batch)
+        launch_attn_decode_batch(p, il, N, true, p->k_att);
+    else if (long_ctx) {
+        AttnSplitOneArgs oa = split_attn_args(p, il);
+        oa.out_f32 = p->k_att;
+        launch_attn_split_one(p, oa, true);
+    } else
+        launch_attn_decode(p, il, N, m.C, true, p->k_att, nullptr);
+    HIP_CHECK(hipGetLastError());
+}
+// The tail of a stage that is not the last of a layer split: its residual rows into the outgoing hand-off buffer (true: no lm_head follows)
+static bool plan_hand_on(DecodePlan *p, LaunchCtx &cx) {
+    const LlamaMatch &m = p->m;
+    if (m.output) return false;
+    if (cx.want(GGML_HIP_KCLASS_OTHER, (double)m.N * m.E * 8.0))
+        HIP_CHECK(hipMemcpyAsync(p->stage_out, p->xa, (size_t)m.N * m.E * 4, hipMemcpyDeviceToDevice, g.stream));
+    return true;
 }
 
 // enqueues the whole token on g.stream (eagerly, or into a stream capture); cx: what of it, and the books (LaunchCtx).
@@ -237,11 +279,13 @@ static void plan_launch_all(DecodePlan *p, int av, LaunchCtx cx) {
     const bool fuse_wo = fsh.ok && fsh.wo && p->ogran != nullptr;
     const double wo_bytes = (double)E * nbE * bb + nbE * 40.0 + E * 8.0;
     for (int il = 0; il < m.L; il++) {
-        const DecodePlan::LW &w = p->lw[(same_layer && cx.kind_mask != ~0u) ? 0 : il];
+        const int wl = (same_layer && cx.kind_mask != ~0u) ? 0 : il;
+        const DecodePlan::LW &w = p->lw[wl];
+        const DecodePlan::LayerNorms &ln = p->ln[wl];
         // ---- attention norm + wq|wk|wv + rope + KV store ----
         float *const xin = (il == 0 && !m.wte) ? p->stage_in : p->xa;                    // the layer's input row (residual stream)
         float *const xout = (il == m.L - 1 && !m.output) ? p->stage_out : p->xa;        // ... and where its w2 + residual goes
-        if (!fuse_x) rmsq(xin, w.attn_norm, nullptr);
+        if (!fuse_x) rmsq(xin, ln.attn_norm, nullptr);
         {
             DecMmvqArgs a;
             memset(&a, 0, sizeof(a));
@@ -250,7 +294,7 @@ static void plan_launch_all(DecodePlan *p, int av, LaunchCtx cx) {
             a.wg_begin[1] = (int)((E + 7) / 8);
             a.wg_begin[2] = a.wg_begin[1] + (int)((m.Egqa + 7) / 8);
             const int nwg = a.wg_begin[2] + (int)((m.Egqa + 7) / 8);
-            a.x = actE; a.xf = xin; a.xw = w.attn_norm; a.eps = m.eps;
+            a.x = actE; a.xf = xin; a.xw = ln.attn_norm; a.eps = m.eps;
             a.nb = nbE; a.dst = p->q; a.prm = p->prm; a.mem_k = p->mem_k_at(il); a.mem_v = p->mem_v_at(il);
             a.Egqa = m.Egqa; a.C = m.C; a.D = (int)m.D; a.theta_scale = theta_scale; a.freq_scale = m.freq_scale;
             const double qkv_bytes = (double)(E + 2 * m.Egqa) * nbE * bb + nbE * 40.0 + (E + 2 * m.Egqa) * 4.0;
@@ -288,7 +332,7 @@ static void plan_launch_all(DecodePlan *p, int av, LaunchCtx cx) {
                                 if (b && nw.n < WARM_MAX) { nw.base[nw.n] = (const uint8_t *)b; nw.row_bytes[nw.n] = (uint32_t)rb; nw.rows_of[nw.n++] = (int)wrows; }
                             });
                         nw.rows = (int)wrows;
-                        nw.bcast = (const uint8_t *)w.ffn_norm; nw.bcast_bytes = (int)(E * 4);
+                        nw.bcast = (const uint8_t *)ln.ffn_norm; nw.bcast_bytes = (int)(E * 4);
                         wt.warm_wave = 15;
                     }
                     with_qt(qt, [&](auto QT) { launch_qkv_attn_wo<CT(QT)>(ba, fa, wt, fsh, lds); });
@@ -328,11 +372,11 @@ static void plan_launch_all(DecodePlan *p, int av, LaunchCtx cx) {
             matvec(1, epi_add, x_q8, x_q8, a, nullptr, nullptr, (int)((E + 7) / 8), wo_bytes);
         }
         // ---- ffn norm + silu(w1 x) * (w3 x) ----
-        if (!fuse_x) rmsq(p->xb, w.ffn_norm, nullptr);
+        if (!fuse_x) rmsq(p->xb, ln.ffn_norm, nullptr);
         {
             DecMmvqArgs a;
             memset(&a, 0, sizeof(a));
-            a.w[0] = w.w1; a.w[1] = w.w3; a.x = actE; a.xf = p->xb; a.xw = w.ffn_norm; a.eps = m.eps; a.nb = nbE;
+            a.w[0] = w.w1; a.w[1] = w.w3; a.x = actE; a.xf = p->xb; a.xw = ln.ffn_norm; a.eps = m.eps; a.nb = nbE;
             a.dst = p->gate;
             matvec(2, epi_gate, x_norm, x_norm, a, nullptr, nullptr, (int)((F + 7) / 8), 2.0 * F * nbE * bb + nbE * 40.0 + F * 4.0);
         }
@@ -352,15 +396,14 @@ static void plan_launch_all(DecodePlan *p, int av, LaunchCtx cx) {
         }
     }
     if (!m.output) return;  // not the last stage: the last layer's w2 launch has written the residual into the outgoing hand-off buffer
-    float *const emb_dst = p->spec_out && p->emb_out ? p->emb_alt : p->emb_out;  // (see DecodePlan::logits_alt)
-    char *const logits_dst = p->spec_out ? p->logits_alt : p->logits_out;
-    if (!big) rmsq(p->xa, p->norm, emb_dst);  // final norm: f32 copy for OutputRequest.embeddings + Q8 for lm_head
+    const ResultDst dst = plan_result_dst(p);
+    if (!big) rmsq(p->xa, p->norm, dst.emb);  // final norm: f32 copy for OutputRequest.embeddings + Q8 for lm_head
     {
         DecMmvqArgs a;
         memset(&a, 0, sizeof(a));
-        a.w[0] = p->output; a.x = actE; a.nb = nbE; a.dst = (float *)logits_dst;
+        a.w[0] = p->output; a.x = actE; a.nb = nbE; a.dst = (float *)dst.logits;
         a.xf = p->xa; a.xw = p->norm; a.eps = m.eps;
-        matvec(4, epi_store, x_norm, x_q8, a, emb_dst, nullptr, (int)((m.V + 7) / 8), (double)m.V * nbE * bb + nbE * 40.0 + m.V * 4.0);
+        matvec(4, epi_store, x_norm, x_q8, a, dst.emb, nullptr, (int)((m.V + 7) / 8), (double)m.V * nbE * bb + nbE * 40.0 + m.V * 4.0);
     }
 }
 
@@ -406,8 +449,9 @@ static void launch_mmvq_kn(int nseg, const KWeight *const *ws, float *const *dst
     }
 }
 // the decode mat-vec of Q4_K / Q6_K matrices as one wave of 1024-thread workgroups that stage the activation themselves
-// (kernels/kquant_big.h): xsrc says what the row is made from (KX_NORM: rms_norm(xf) * xw; KX_F32: xf; KX_SILU_MUL: silu(xf) * xw)
-struct KBigSrc {
+// (kernels/kquant_big.h): xsrc says what the row is made from (KX_NORM: rms_norm(xf) * xw; KX_F32: xf; KX_SILU_MUL: silu(xf) * xw);
+// the F16 plan's mat-vec (k_mmvq_f16) stages its rows from the same description
+struct RowSrc {
     int xsrc;
     const float *xf, *xw;
     float eps;
@@ -415,10 +459,7 @@ struct KBigSrc {
 };
 template <int KT>
 static void launch_qkv_attn_k(const KBigArgs &ka, const FusedAttnArgs &fa, size_t lds) {
-    if (lds > 64 * 1024) {
-        static DevOnce done;
-        if (done.first()) HIP_CHECK(hipFuncSetAttribute((const void *)k_qkv_attn_k<KT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ATTN_DECODE_LDS_MAX));
-    }
+    lds_opt_in<k_qkv_attn_k<KT>>(lds, ATTN_DECODE_LDS_MAX);
     hipLaunchKernelGGL((k_qkv_attn_k<KT>), dim3((unsigned)g.num_cus), dim3(KBIG_T), lds, g.stream, ka, fa);
 }
 template <int KT>
@@ -438,7 +479,7 @@ static void launch_kbig_x(const KBigArgs &a, int xsrc, size_t lds, int epi) {
         default: hipLaunchKernelGGL((k_mmvq_kbig<KT, KX_SILU_MUL>), grid, block, lds, g.stream, a); break;
     }
 }
-static void launch_kbig(int nseg, const KWeight *const *ws, float *const *dsts, const KBigSrc &src, const float *res, int epi = KE_ROW,
+static void launch_kbig(int nseg, const KWeight *const *ws, float *const *dsts, const RowSrc &src, const float *res, int epi = KE_ROW,
                         const KBigArgs *qkv = nullptr, const FusedAttnArgs *fused = nullptr) {
     const KWeight &w = *ws[0];
     const int64_t K = w.nsb * 256, nsb = w.nsb;
@@ -484,7 +525,6 @@ static void plan_launch_k(DecodePlan *p, int av, LaunchCtx cx) {
     const int64_t E = m.E, F = m.F, nsbE = E / 256, nsbF = F / 256;
     const int N = m.N;  // 1 = decode; 2..8 = a prompt chunk (rows of every activation buffer, columns of every mat-vec)
     const KAct act{p->k_q8, p->k_d8, p->k_bs};
-    const float theta_scale = powf(m.freq_base, -2.0f / m.n_dims);
     // bytes of one launch over ws[i .. j): the activation rows + every matrix and its output (`out`: bytes per output element)
     auto run_bytes = [&](const KWeight *const *ws, int i, int j, double out) {
         double bytes = (double)N * ws[i]->nsb * 292.0;
@@ -494,7 +534,7 @@ static void plan_launch_k(DecodePlan *p, int av, LaunchCtx cx) {
     // matrices of one kind that share the activation row: one launch per run of equal types (a *_K_M file mixes Q4_K and Q6_K)
     // src: what the big-workgroup form stages the activation from (kbig); the helper-launch form reads the Q8_K row `act`
     auto mmvq = [&](int kind, std::initializer_list<const KWeight *> wl, std::initializer_list<float *> dl, const float *res,
-                    const KBigSrc &src) {
+                    const RowSrc &src) {
         const KWeight *const *ws = wl.begin();
         float *const *ds = dl.begin();
         auto run = [&](int i, int j) {
@@ -516,19 +556,10 @@ static void plan_launch_k(DecodePlan *p, int av, LaunchCtx cx) {
             hipLaunchKernelGGL(k_k_norm_quant, dim3((unsigned)nsbE, (unsigned)N), dim3(256), 0, g.stream, x, w, m.eps, (int)E, y, p->k_q8, p->k_d8, p->k_bs);
         });
     };
-    if (!m.wte) {
-        if (cx.want(GGML_HIP_KCLASS_OTHER, (double)N * E * 8.0))
-            HIP_CHECK(hipMemcpyAsync(p->xa, p->stage_in, (size_t)N * E * 4, hipMemcpyDeviceToDevice, g.stream));
-    } else {  // DecParams::tokens[0] == token: the ids of the chunk
-        cx.other((double)N * E * 4.6, [&] { dequant_k_rows(p->k_wte, (const int *)p->prm->tokens, N, p->xa, E); });
-    }
-    cx.other((double)N * m.D * 4.0, [&] {  // one (cos, sin) table per token of the chunk, 128 floats apart
-        hipLaunchKernelGGL(k_rope_table, dim3((unsigned)N), dim3(128), 0, g.stream, (const DecParams *)p->prm, theta_scale, m.freq_scale,
-                           (int)(m.D >> 1), p->rope, p->epoch);  // block 0 also opens the token's epoch (the tag of k_attn_split_one's granules)
-    });
+    plan_open_rows(p, cx, false, 4.6, [&] { dequant_k_rows(p->k_wte, (const int *)p->prm->tokens, N, p->xa, E); });
     for (int il = 0; il < m.L; il++) {
         const DecodePlan::KLW &w = p->klw[il];
-        const DecodePlan::LW &nw = p->lw[il];
+        const DecodePlan::LayerNorms &nw = p->ln[il];
         __half *mk = p->mem_k_at(il), *mv = p->mem_v_at(il);
         norm_quant(p->xa, nw.attn_norm, nullptr);
         // big-workgroup form: RoPE and the K/V store ride in the epilogue of the wq / wk / wv launches (a unit = two adjacent rows of a
@@ -537,7 +568,7 @@ static void plan_launch_k(DecodePlan *p, int av, LaunchCtx cx) {
         // ... and, while one attention workgroup per head suffices and the three matrices are of one type, the attention itself
         // (k_qkv_attn_k): no k_attn_decode launch below
         const bool kfused = kqkv && w.wq.kt == w.wk.kt && w.wk.kt == w.wv.kt && kfused_ok(p, av) && (cx.mask & (1u << GGML_HIP_KCLASS_MMVQ)) && (cx.kind_mask & 1u);
-        const KBigSrc attn_normed{KX_NORM, p->xa, nw.attn_norm, m.eps, nullptr};
+        const RowSrc attn_normed{KX_NORM, p->xa, nw.attn_norm, m.eps, nullptr};
         if (kqkv) {
             const KWeight *ws3[3] = {&w.wq, &w.wk, &w.wv};
             float *ds3[3] = {p->q, p->k_kf, p->k_vf};
@@ -566,27 +597,14 @@ static void plan_launch_k(DecodePlan *p, int av, LaunchCtx cx) {
                 hipLaunchKernelGGL(k_k_rope_store, dim3(grid1(E / 2 + m.Egqa / 2 + m.Egqa).x, (unsigned)N), dim3(256), 0, g.stream, ra);
             });
         }
-        if (!kfused) {
-            const double bytes = (double)N * ((double)(m.n_past + N) * m.Egqa * 4.0 + m.E * 9.0);
-            if (cx.want(GGML_HIP_KCLASS_ATTN, bytes)) {
-                Timed tm(GGML_HIP_KCLASS_ATTN, bytes);
-                // the Q8_0 copy of the heads' outputs goes to the (unused) E-wide Q8_0 row of the plan; wo reads the f32 row
-                if (long_ctx) {  // >= 512 positions: every CU pulls a piece of the cache (k_attn_split_one, kernels/decode_attn_split.h)
-                    AttnSplitOneArgs oa = split_attn_args(p, il);
-                    oa.out_f32 = p->k_att;
-                    launch_attn_split_one(p, oa, true);
-                } else
-                    launch_attn_decode(p, il, N, m.C, true, p->k_att, nullptr);
-                HIP_CHECK(hipGetLastError());
-            }
-        }
+        if (!kfused) plan_attn_f32(p, cx, il, long_ctx, false);
         if (!kbig) cx.other((double)N * E * 5.3, [&] { hipLaunchKernelGGL(k_k_quant, dim3((unsigned)nsbE, (unsigned)N), dim3(256), 0, g.stream, (const float *)p->k_att, p->k_q8, p->k_d8, p->k_bs); });
-        mmvq(1, {&w.wo}, {p->xb}, p->xa, KBigSrc{KX_F32, p->k_att, nullptr, 0.0f, nullptr});
+        mmvq(1, {&w.wo}, {p->xb}, p->xa, RowSrc{KX_F32, p->k_att, nullptr, 0.0f, nullptr});
         norm_quant(p->xb, nw.ffn_norm, nullptr);
         // w1 and w3 of one type: one launch whose epilogue is silu(w1 x) * (w3 x) (the product lands in p->gate, w2 stages it as a
         // plain f32 row); a mixed pair keeps two row launches and the SiLU·mul in w2's staging
         const bool kgate = kbig && w.w1.kt == w.w3.kt && w.w1.M == w.w3.M && g.opt_plan_k != 2;
-        const KBigSrc ffn_normed{KX_NORM, p->xb, nw.ffn_norm, m.eps, nullptr};
+        const RowSrc ffn_normed{KX_NORM, p->xb, nw.ffn_norm, m.eps, nullptr};
         if (kgate) {
             const KWeight *ws2[2] = {&w.w1, &w.w3};
             float *ds2[2] = {p->gate, p->k_g3};
@@ -599,17 +617,12 @@ static void plan_launch_k(DecodePlan *p, int av, LaunchCtx cx) {
             hipLaunchKernelGGL(k_k_silu_mul_quant, dim3((unsigned)nsbF, (unsigned)N), dim3(256), 0, g.stream, (const float *)p->gate, (const float *)p->k_g3,
                                p->k_q8, p->k_d8, p->k_bs);
         });
-        mmvq(3, {&w.w2}, {p->xa}, p->xb, kgate ? KBigSrc{KX_F32, p->gate, nullptr, 0.0f, nullptr} : KBigSrc{KX_SILU_MUL, p->gate, p->k_g3, 0.0f, nullptr});
+        mmvq(3, {&w.w2}, {p->xa}, p->xb, kgate ? RowSrc{KX_F32, p->gate, nullptr, 0.0f, nullptr} : RowSrc{KX_SILU_MUL, p->gate, p->k_g3, 0.0f, nullptr});
     }
-    if (!m.output) {
-        if (cx.want(GGML_HIP_KCLASS_OTHER, (double)N * E * 8.0))
-            HIP_CHECK(hipMemcpyAsync(p->stage_out, p->xa, (size_t)N * E * 4, hipMemcpyDeviceToDevice, g.stream));
-        return;
-    }
-    float *const emb_dst = p->spec_out && p->emb_out ? p->emb_alt : p->emb_out;  // (see DecodePlan::logits_alt)
-    char *const logits_dst = p->spec_out ? p->logits_alt : p->logits_out;
-    norm_quant(p->xa, p->norm, emb_dst);  // all N rows: f32 copy (embedding_result node) + Q8_K
-    mmvq(4, {&p->k_output}, {(float *)logits_dst}, nullptr, KBigSrc{KX_NORM, p->xa, p->norm, m.eps, emb_dst});
+    if (plan_hand_on(p, cx)) return;
+    const ResultDst dst = plan_result_dst(p);
+    norm_quant(p->xa, p->norm, dst.emb);  // all N rows: f32 copy (embedding_result node) + Q8_K
+    mmvq(4, {&p->k_output}, {(float *)dst.logits}, nullptr, RowSrc{KX_NORM, p->xa, p->norm, m.eps, dst.emb});
 }
 // ---------------------------------------------------------------------------------------------------
 // The F16 plan: a LLaMA whose matrices are F16 (file type 1).  Five launches per layer (kernels/decode_f16.h):
@@ -619,12 +632,6 @@ static void plan_launch_k(DecodePlan *p, int av, LaunchCtx cx) {
 // A row's result does not depend on the columns beside it (the kernel's design rule): the chunk equals N single tokens and the
 // batched step equals the chunk, bit for bit.  Same `mask` / `kind_mask` protocol as the other plans.
 // ---------------------------------------------------------------------------------------------------
-struct F16Src {
-    int xsrc;
-    const float *xf, *xw;
-    float eps;
-    float *y_out;
-};
 struct F16Qkv {
     const float *rope;
     const DecParams *prm;
@@ -636,10 +643,7 @@ struct F16Qkv {
 };
 template <int XSRC, int EPI, int NCOLS>
 static void launch_f16_inst(const F16Args &a, int G, size_t lds) {
-    if (lds > 64 * 1024) {  // above the 64 KiB default a kernel asks for its dynamic LDS once per device
-        static DevOnce opted;
-        if (opted.first()) HIP_CHECK(hipFuncSetAttribute((const void *)k_mmvq_f16<XSRC, EPI, NCOLS>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-    }
+    lds_opt_in<k_mmvq_f16<XSRC, EPI, NCOLS>>(lds, 150 * 1024);
     hipLaunchKernelGGL((k_mmvq_f16<XSRC, EPI, NCOLS>), dim3((unsigned)G), dim3(F16_T), lds, g.stream, a);
 }
 template <int XSRC, int EPI>
@@ -665,7 +669,7 @@ static bool f16_launch_ok(int nseg, const F16W *ws, int64_t K, int xsrc, int epi
     return f16_launch_shape_ok(K, epi == KE_GATE ? ws[0].M : epi == KE_QKV ? Mt / 2 : Mt);
 }
 // one mat-vec of the F16 plan over N columns: dsts[i] is [N][M_i], res like dsts[0]; seg_kind (KE_QKV): which of wq / wk / wv ws[i] is
-static void launch_f16(int nseg, const F16W *ws, float *const *dsts, int64_t K, const F16Src &src, const float *res, int N, int epi = KE_ROW,
+static void launch_f16(int nseg, const F16W *ws, float *const *dsts, int64_t K, const RowSrc &src, const float *res, int N, int epi = KE_ROW,
                        const F16Qkv *qkv = nullptr, const int *seg_kind = nullptr) {
     if (!f16_launch_ok(nseg, ws, K, src.xsrc, epi)) die("k_mmvq_f16: a launch the F16 plan's preconditions exclude (K %lld)", (long long)K);
     int64_t Mt = 0;
@@ -704,39 +708,24 @@ static void launch_f16(int nseg, const F16W *ws, float *const *dsts, int64_t K, 
         c0 += ncols;
     }
 }
-static void launch_attn_decode_batch(const DecodePlan *p, int il, int N, bool f16d, float *out_f32);
 static void plan_launch_f16(DecodePlan *p, int av, LaunchCtx cx, bool batch = false) {
     const bool long_ctx = av == AV_SPLIT;
     const LlamaMatch &m = p->m;
     const int64_t E = m.E, F = m.F;
     const int N = m.N;
-    const float theta_scale = powf(m.freq_base, -2.0f / m.n_dims);
     // bytes of one launch: the matrices, the activation rows and the outputs (`out`: bytes per output element)
     auto mv_bytes = [&](std::initializer_list<const F16W *> wl, int64_t K, double out) {
         double bytes = (double)N * K * 4.0;
         for (const F16W *w : wl) bytes += (double)w->M * K * 2.0 + (double)N * w->M * out;
         return bytes;
     };
-    if (!m.wte) {
-        if (cx.want(GGML_HIP_KCLASS_OTHER, (double)N * E * 8.0))
-            HIP_CHECK(hipMemcpyAsync(p->xa, p->stage_in, (size_t)N * E * 4, hipMemcpyDeviceToDevice, g.stream));
-    } else {  // DecParams::tokens[0] == token: the ids of the chunk / of the step's columns
-        cx.other((double)N * E * 6.0, [&] {
-            hipLaunchKernelGGL(k_get_rows<__half>, dim3((unsigned)((E + 255) / 256), (unsigned)N), dim3(256), 0, g.stream, (const char *)p->f_wte.p,
-                               p->f_wte.ld * 2, (const int *)p->prm->tokens, p->xa, E);
-        });
-    }
-    cx.other((double)N * m.D * 4.0, [&] {  // one (cos, sin) table per column, 128 floats apart
-        if (batch)
-            hipLaunchKernelGGL(k_rope_table_batch, dim3((unsigned)N), dim3(128), 0, g.stream, (const BatchCols *)p->bcols, theta_scale, m.freq_scale,
-                               (int)(m.D >> 1), p->rope);
-        else
-            hipLaunchKernelGGL(k_rope_table, dim3((unsigned)N), dim3(128), 0, g.stream, (const DecParams *)p->prm, theta_scale, m.freq_scale,
-                               (int)(m.D >> 1), p->rope, p->epoch);  // block 0 also opens the token's epoch (the tag of k_attn_split_one's granules)
+    plan_open_rows(p, cx, batch, 6.0, [&] {
+        hipLaunchKernelGGL(k_get_rows<__half>, dim3((unsigned)((E + 255) / 256), (unsigned)N), dim3(256), 0, g.stream, (const char *)p->f_wte.p,
+                           p->f_wte.ld * 2, (const int *)p->prm->tokens, p->xa, E);
     });
     for (int il = 0; il < m.L; il++) {
         const DecodePlan::FLW &w = p->flw[il];
-        const DecodePlan::LW &nw = p->lw[il];
+        const DecodePlan::LayerNorms &nw = p->ln[il];
         {   // norm + wq|wk|wv + RoPE + K/V store
             const F16W ws3[3] = {w.wq, w.wk, w.wv};
             float *ds3[3] = {p->q, nullptr, nullptr};
@@ -747,49 +736,30 @@ static void plan_launch_f16(DecodePlan *p, int av, LaunchCtx cx, bool batch = fa
             if (batch) { qa.bc = p->bcols; qa.kv_off = p->kv_off(il); }
             else { qa.mem_k = p->mem_k_at(il); qa.mem_v = p->mem_v_at(il); }
             cx.mmvq(0, mv_bytes({&w.wq, &w.wk, &w.wv}, E, 4.0), [&] {
-                launch_f16(3, ws3, ds3, E, F16Src{KX_NORM, p->xa, nw.attn_norm, m.eps, nullptr}, nullptr, N, KE_QKV, &qa, kinds);
+                launch_f16(3, ws3, ds3, E, RowSrc{KX_NORM, p->xa, nw.attn_norm, m.eps, nullptr}, nullptr, N, KE_QKV, &qa, kinds);
             });
         }
-        {   // attention: the f32 row of the merged heads for wo's staging (the Q8 copy goes to the plan's unused Q8 row)
-            const double bytes = (double)N * ((double)(m.n_past + N) * m.Egqa * 4.0 + m.E * 9.0);
-            if (cx.want(GGML_HIP_KCLASS_ATTN, bytes)) {
-                Timed tm(GGML_HIP_KCLASS_ATTN, bytes);
-                if (batch)
-                    launch_attn_decode_batch(p, il, N, true, p->k_att);
-                else if (long_ctx) {
-                    AttnSplitOneArgs oa = split_attn_args(p, il);
-                    oa.out_f32 = p->k_att;
-                    launch_attn_split_one(p, oa, true);
-                } else
-                    launch_attn_decode(p, il, N, m.C, true, p->k_att, nullptr);
-                HIP_CHECK(hipGetLastError());
-            }
-        }
+        plan_attn_f32(p, cx, il, long_ctx, batch);
         {
             float *d1[1] = {p->xb};
-            cx.mmvq(1, mv_bytes({&w.wo}, E, 8.0), [&] { launch_f16(1, &w.wo, d1, E, F16Src{KX_F32, p->k_att, nullptr, 0.0f, nullptr}, p->xa, N); });
+            cx.mmvq(1, mv_bytes({&w.wo}, E, 8.0), [&] { launch_f16(1, &w.wo, d1, E, RowSrc{KX_F32, p->k_att, nullptr, 0.0f, nullptr}, p->xa, N); });
         }
         {
             const F16W ws2[2] = {w.w1, w.w3};
             float *d2[2] = {p->gate, nullptr};
             cx.mmvq(2, (double)N * E * 4.0 + 2.0 * (double)F * E * 2.0 + (double)N * F * 4.0,
-                    [&] { launch_f16(2, ws2, d2, E, F16Src{KX_NORM, p->xb, nw.ffn_norm, m.eps, nullptr}, nullptr, N, KE_GATE); });
+                    [&] { launch_f16(2, ws2, d2, E, RowSrc{KX_NORM, p->xb, nw.ffn_norm, m.eps, nullptr}, nullptr, N, KE_GATE); });
         }
         {
             float *d1[1] = {p->xa};
-            cx.mmvq(3, mv_bytes({&w.w2}, F, 8.0), [&] { launch_f16(1, &w.w2, d1, F, F16Src{KX_F32, p->gate, nullptr, 0.0f, nullptr}, p->xb, N); });
+            cx.mmvq(3, mv_bytes({&w.w2}, F, 8.0), [&] { launch_f16(1, &w.w2, d1, F, RowSrc{KX_F32, p->gate, nullptr, 0.0f, nullptr}, p->xb, N); });
         }
     }
-    if (!m.output) {
-        if (cx.want(GGML_HIP_KCLASS_OTHER, (double)N * E * 8.0))
-            HIP_CHECK(hipMemcpyAsync(p->stage_out, p->xa, (size_t)N * E * 4, hipMemcpyDeviceToDevice, g.stream));
-        return;
-    }
-    float *const emb_dst = p->spec_out && p->emb_out ? p->emb_alt : p->emb_out;  // (see DecodePlan::logits_alt)
-    char *const logits_dst = p->spec_out ? p->logits_alt : p->logits_out;
-    float *d1[1] = {(float *)logits_dst};
+    if (plan_hand_on(p, cx)) return;
+    const ResultDst dst = plan_result_dst(p);
+    float *d1[1] = {(float *)dst.logits};
     cx.mmvq(4, mv_bytes({&p->f_output}, E, 4.0),
-            [&] { launch_f16(1, &p->f_output, d1, E, F16Src{KX_NORM, p->xa, p->norm, m.eps, emb_dst}, nullptr, N); });
+            [&] { launch_f16(1, &p->f_output, d1, E, RowSrc{KX_NORM, p->xa, p->norm, m.eps, dst.emb}, nullptr, N); });
 }
 // the decode launches of a plan, whichever kind it is
 static void plan_launch_decode(DecodePlan *p, int av = AV_SHORT, LaunchCtx cx = {}) {

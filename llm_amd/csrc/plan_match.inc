@@ -327,8 +327,10 @@ static bool match_llama_decode(ggml_cgraph *gr, LlamaMatch &m) {
         MATCH(g.opt_plan_f16 && m.N >= 1 && m.N <= MULTI_MAX_N && (g.opt_mmq_min <= 0 || m.N < g.opt_mmq_min) && m.n_past + m.N <= m.C);
         MATCH(m.D == m.n_dims && f16_plan_shape_ok(m) && attn_decode_lds(m.C, m.D) <= ATTN_DECODE_LDS_MAX);
         for (auto &lw : m.layers)
-            for (const ggml_tensor *w : {lw.wq, lw.wk, lw.wv, lw.wo, lw.w1, lw.w2, lw.w3})
+            for (int i = 0; i < LAYER_MATS; i++) {
+                const ggml_tensor *w = lw.at(i);
                 MATCH(is_leaf(w) && w->type == GGML_TYPE_F16 && w->ne[2] == 1 && w->ne[3] == 1 && ggml_is_contiguous(w));
+            }
         for (const ggml_tensor *w : {m.wte, m.output})
             MATCH(!w || (w->type == GGML_TYPE_F16 && w->ne[2] == 1 && w->ne[3] == 1 && ggml_is_contiguous(w)));
         m.prompt = false;
@@ -353,8 +355,10 @@ static bool match_llama_decode(ggml_cgraph *gr, LlamaMatch &m) {
         MATCH(m.n_past + m.N <= m.C);
     }
     for (auto &lw : m.layers)
-        for (const ggml_tensor *w : {lw.wq, lw.wk, lw.wv, lw.wo, lw.w1, lw.w2, lw.w3})
+        for (int i = 0; i < LAYER_MATS; i++) {
+            const ggml_tensor *w = lw.at(i);
             MATCH(is_leaf(w) && (m.kquant ? kt_of(w->type) >= 0 : w->type == m.wtype));
+        }
     if (m.kquant && m.prompt) {  // prompt plan on the resident f16 copies of the K weights (mul_mat_k_gemm's operands: k_prompt_weights below)
         MATCH(g.opt_plan_k && g.opt_mmq_w16 && m.E % 256 == 0 && m.F % 256 == 0);
     } else if (m.kquant) {  // K plan: decode and chunks of up to 31 tokens (every helper kernel has the row as a grid dimension, the mat-vecs take

@@ -9,10 +9,7 @@ static void launch_big8(const Big8Args &a) {
     // waves per workgroup as for k_mmvq_big; the staging needs ncols*nb <= 4 blocks per thread and 512 RoPE threads
     const int W = big_waves(units, nwg, std::max<int>(8, (int)((a.ncols * a.d.nb + 4 * 64 - 1) / (4 * 64))));
     const size_t lds = (size_t)8 * ((a.d.nb + 63) / 64 * 64) * 40;
-    static DevOnce attr_set;
-    if (attr_set.first()) {  // up to 150 KB of dynamic LDS
-        HIP_CHECK(hipFuncSetAttribute((const void *)k_mmvq_big8<QT, EPI, BATCH>, hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024));
-    }
+    lds_opt_in<k_mmvq_big8<QT, EPI, BATCH>>(lds, 152 * 1024);  // up to 150 KB of dynamic LDS
     hipLaunchKernelGGL((k_mmvq_big8<QT, EPI, BATCH>), dim3(nwg), dim3(W * 64), lds, g.stream, a);
 }
 // ---- the same launches on the integer matrix cores (kernels/mmq_cols.h) ----
@@ -23,27 +20,19 @@ static void launch_cols(const ColsArgs &a0, int M_total) {
     const ColsShape sh = cols_shape(a.ngroups, EPI == EPI_GATE ? 2 : 1, (int)a.d.nb);
     a.gq = a.ngroups / sh.G;
     a.gr = a.ngroups % sh.G;
-    static DevOnce attr_set;
-    if (attr_set.first()) {
-        HIP_CHECK(hipFuncSetAttribute((const void *)k_mmq_cols<QT, EPI, false, BATCH>, hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024));
-    }
-    if (a.ts && !BATCH) {  // measurement build (tests/tools/cols_timeline.py)
-        static DevOnce attr_set_i;
-        if (attr_set_i.first())
-            HIP_CHECK(hipFuncSetAttribute((const void *)k_mmq_cols<QT, EPI, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024));
-        hipLaunchKernelGGL((k_mmq_cols<QT, EPI, true>), dim3(sh.G), dim3(COLS_T), sh.lds, g.stream, a);
-    } else
+    if (!a.ts || BATCH) {
+        lds_opt_in<k_mmq_cols<QT, EPI, false, BATCH>>(sh.lds, 152 * 1024);
         hipLaunchKernelGGL((k_mmq_cols<QT, EPI, false, BATCH>), dim3(sh.G), dim3(COLS_T), sh.lds, g.stream, a);
+    } else {  // measurement build (tests/tools/cols_timeline.py)
+        lds_opt_in<k_mmq_cols<QT, EPI, true>>(sh.lds, 152 * 1024);
+        hipLaunchKernelGGL((k_mmq_cols<QT, EPI, true>), dim3(sh.G), dim3(COLS_T), sh.lds, g.stream, a);
+    }
 }
 // k_attn_decode's batched form for layer il of a batched step: a grid of heads x columns, the whole context in its LDS arrays
 static void launch_attn_decode_batch(const DecodePlan *p, int il, int N, bool f16d, float *out_f32 = nullptr) {
-    static DevOnce opted;
-    if (opted.first()) {
-        HIP_CHECK(hipFuncSetAttribute((const void *)k_attn_decode_batch<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ATTN_DECODE_LDS_MAX));
-        HIP_CHECK(hipFuncSetAttribute((const void *)k_attn_decode_batch<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ATTN_DECODE_LDS_MAX));
-    }
     const LlamaMatch &m = p->m;
     with_bool(f16d, [&](auto F16D) {
+        lds_opt_in<k_attn_decode_batch<CT(F16D)>>(attn_decode_lds(m.C, m.D), ATTN_DECODE_LDS_MAX);
         hipLaunchKernelGGL(k_attn_decode_batch<CT(F16D)>, dim3((unsigned)m.H, (unsigned)N), dim3(1024), attn_decode_lds(m.C, m.D), g.stream,
                            (const float *)p->q, (const BatchCols *)p->bcols, p->kv_off(il), m.kq_scale, (int)m.D, (int)(m.H / m.Hkv), m.Egqa,
                            m.C, p->e_lo, p->e_hi, p->e_d, p->e_s, (int)m.H, m.C, p->e_dT, p->e_sT, out_f32);
@@ -179,7 +168,8 @@ static void plan_launch_chunk(DecodePlan *p, const bool batch) {
     HIP_CHECK(hipGetLastError());
     for (int il = 0; il < m.L; il++) {
         const DecodePlan::LW &w = p->lw[il];
-        rmsq(p->xa, w.attn_norm, nullptr, cols_warm_of(cols.qkv, {&w.wq, &w.wk, &w.wv}, 1, nbE));
+        const DecodePlan::LayerNorms &ln = p->ln[il];
+        rmsq(p->xa, ln.attn_norm, nullptr, cols_warm_of(cols.qkv, {&w.wq, &w.wk, &w.wv}, 1, nbE));
         {
             Big8Args a;
             memset(&a, 0, sizeof(a));
@@ -207,7 +197,7 @@ static void plan_launch_chunk(DecodePlan *p, const bool batch) {
             a.ncols = N; a.ldd = E; a.ldr = E;
             block(1, std::integral_constant<int, EPI_ADD>{}, cols.wo, a, (int)E, p->e_dT, p->e_sT);
         }
-        rmsq(p->xb, w.ffn_norm, nullptr, cols_warm_of(cols.gate, {&w.w1, &w.w3}, 2, nbE));
+        rmsq(p->xb, ln.ffn_norm, nullptr, cols_warm_of(cols.gate, {&w.w1, &w.w3}, 2, nbE));
         {
             Big8Args a;
             memset(&a, 0, sizeof(a));
@@ -260,6 +250,11 @@ static void plan_launch_batch(DecodePlan *p) {
 // between two GEMMs is one launch (kernels/prompt.h): 13 launches per layer instead of 24, the same bits.
 // Launched eagerly (a few hundred launches of tens of microseconds each: no hipGraph needed).
 // ---------------------------------------------------------------------------------------------------
+template <int D, bool INSTR = false, int QR = PATTN_Q>
+static void launch_p_attn(const PAttnArgs &pa, dim3 grid, size_t lds) {
+    lds_opt_in<k_p_attn<D, INSTR, QR>>(lds, 150 * 1024);
+    hipLaunchKernelGGL((k_p_attn<D, INSTR, QR>), grid, dim3(256), lds, g.stream, pa);
+}
 // Attention of a prompt batch (lib.rs:246-307): q [N][E] f32 (RoPE applied), mk / mv this layer's cache, out [N][E] f32 in
 // the merged-heads layout.  fused: one launch with the scores in LDS (kernels/prompt_attn.h); else K.Q -> k_p_soft_max ->
 // V.P with the scores (sc: [H][N][T] f32) and probabilities (p16: [H][N][Tp] f16, Tp = T rounded up to 8) in HBM.
@@ -275,12 +270,6 @@ static void prompt_attention(bool fused, const float *q, const __half *mk, const
         pa.C = C; pa.scale = scale; pa.row_bytes = prompt_attn_row_bytes(T);
         pa.x16 = x16_out; pa.f16d = f16d ? 1 : 0;
         pa.rope = rope; pa.q_part = q_part;
-        static DevOnce pattn_attr;
-        if (pattn_attr.first()) {
-            HIP_CHECK(hipFuncSetAttribute((const void *)k_p_attn<128>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-            HIP_CHECK(hipFuncSetAttribute((const void *)k_p_attn<64>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-            HIP_CHECK(hipFuncSetAttribute((const void *)k_p_attn<32>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-        }
         const int QR = prompt_attn_queries(D, T);
         const dim3 grid((unsigned)(((N + QR - 1) / QR) * H));
         const size_t lds = (size_t)QR * std::max<size_t>(pa.row_bytes, 2 * D + 16);  // score rows (the staged Q tile borrows them)
@@ -293,25 +282,19 @@ static void prompt_attention(bool fused, const float *q, const __half *mk, const
         }
         Timed tm(GGML_HIP_KCLASS_ATTN, (double)T * Egqa * 4.0 + (double)N * E * 8.0);
         pa.ts = nullptr;
-        static DevOnce pattn_attr16;
-        if (QR == 16 && pattn_attr16.first()) {
-            HIP_CHECK(hipFuncSetAttribute((const void *)k_p_attn<128, false, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-            HIP_CHECK(hipFuncSetAttribute((const void *)k_p_attn<64, false, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-            HIP_CHECK(hipFuncSetAttribute((const void *)k_p_attn<32, false, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-        }
-        if (QR == 16) {
-            if (D == 128) hipLaunchKernelGGL((k_p_attn<128, false, 16>), grid, dim3(256), lds, g.stream, pa);
-            else if (D == 64) hipLaunchKernelGGL((k_p_attn<64, false, 16>), grid, dim3(256), lds, g.stream, pa);
-            else hipLaunchKernelGGL((k_p_attn<32, false, 16>), grid, dim3(256), lds, g.stream, pa);
-        } else if (g.timeline && D == 128 && (size_t)grid.x * 64 <= g.timeline_bytes) {  // measurement build (tests/tools/pattn_timeline.py)
-            static DevOnce pattn_attr_i;
-            if (pattn_attr_i.first())
-                HIP_CHECK(hipFuncSetAttribute((const void *)k_p_attn<128, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+        const bool instr = QR != 16 && g.timeline && D == 128 && (size_t)grid.x * 64 <= g.timeline_bytes;  // measurement build (tests/tools/pattn_timeline.py)
+        if (QR != 16 && !instr) {
+            if (D == 128) launch_p_attn<128>(pa, grid, lds);
+            else if (D == 64) launch_p_attn<64>(pa, grid, lds);
+            else launch_p_attn<32>(pa, grid, lds);
+        } else if (QR == 16) {
+            if (D == 128) launch_p_attn<128, false, 16>(pa, grid, lds);
+            else if (D == 64) launch_p_attn<64, false, 16>(pa, grid, lds);
+            else launch_p_attn<32, false, 16>(pa, grid, lds);
+        } else {
             pa.ts = g.timeline;
-            hipLaunchKernelGGL((k_p_attn<128, true>), grid, dim3(256), lds, g.stream, pa);
-        } else if (D == 128) hipLaunchKernelGGL(k_p_attn<128>, grid, dim3(256), lds, g.stream, pa);
-        else if (D == 64) hipLaunchKernelGGL(k_p_attn<64>, grid, dim3(256), lds, g.stream, pa);
-        else hipLaunchKernelGGL(k_p_attn<32>, grid, dim3(256), lds, g.stream, pa);
+            launch_p_attn<128, true>(pa, grid, lds);
+        }
         HIP_CHECK(hipGetLastError());
         return;
     }
@@ -325,6 +308,7 @@ static void prompt_attention(bool fused, const float *q, const __half *mk, const
         ga.tiles_n = (N + 127) / 128;
         const int tiles_m = (int)((T + 127) / 128);
         Timed tm(GGML_HIP_KCLASS_ATTN, (double)T * Egqa * 2.0 + (double)N * E * 4.0 + (double)H * N * T * 4.0);
+        lds_opt_in<k_gemm_f16>(MMQ_LDS, MMQ_LDS);
         hipLaunchKernelGGL(k_gemm_f16, dim3((unsigned)(tiles_m * ga.tiles_n), (unsigned)H), dim3(256), MMQ_LDS, g.stream, ga);
         HIP_CHECK(hipGetLastError());
     }
@@ -344,6 +328,7 @@ static void prompt_attention(bool fused, const float *q, const __half *mk, const
         ga.tiles_n = (N + 127) / 128;
         const int tiles_m = (int)((D + 127) / 128);
         Timed tm(GGML_HIP_KCLASS_ATTN, (double)T * Egqa * 2.0 + (double)H * N * T * 2.0 + (double)N * E * 4.0);
+        lds_opt_in<k_gemm_f16_b16>(MMQ_LDS, MMQ_LDS);
         hipLaunchKernelGGL(k_gemm_f16_b16, dim3((unsigned)(tiles_m * ga.tiles_n), (unsigned)H), dim3(256), MMQ_LDS, g.stream, ga);
         HIP_CHECK(hipGetLastError());
     }
@@ -379,12 +364,8 @@ static void plan_launch_prompt(DecodePlan *p) {
         die("prompt plan: no room for the f16 copies of the K-quant weights any more (set GGML_HIP_PLAN_K=0 to run the node-by-node executor)");
     if (!kq && p->w16_gen != g.w16_gen) {
         auto w16_of = [](const ggml_tensor *t) { DevTensor *e = plan_rec(t); return e ? e->qw.w16 : nullptr; };
-        for (int il = 0; il < m.L; il++) {
-            DecodePlan::LW &w = p->lw[il];
-            const auto &l = m.layers[il];
-            w.wq.w16 = w16_of(l.wq); w.wk.w16 = w16_of(l.wk); w.wv.w16 = w16_of(l.wv); w.wo.w16 = w16_of(l.wo);
-            w.w1.w16 = w16_of(l.w1); w.w2.w16 = w16_of(l.w2); w.w3.w16 = w16_of(l.w3);
-        }
+        for (int il = 0; il < m.L; il++)
+            for (int i = 0; i < LAYER_MATS; i++) p->lw[il].at(i).w16 = w16_of(m.layers[il].at(i));
         if (m.output) p->output.w16 = w16_of(m.output);
         p->w16_gen = g.w16_gen;
     }
@@ -440,11 +421,6 @@ static void plan_launch_prompt(DecodePlan *p) {
         mmq_f16_launch_multi(qt, nseg, segs, p->p_x16, N, nb, true, splits, false, stride);
         return splits;
     };
-    static DevOnce attr_set;
-    if (attr_set.first()) {
-        HIP_CHECK(hipFuncSetAttribute((const void *)k_gemm_f16, hipFuncAttributeMaxDynamicSharedMemorySize, MMQ_LDS));
-        HIP_CHECK(hipFuncSetAttribute((const void *)k_gemm_f16_b16, hipFuncAttributeMaxDynamicSharedMemorySize, MMQ_LDS));
-    }
     if (!m.wte) {
         HIP_CHECK(hipMemcpyAsync(p->xa, p->stage_in, (size_t)N * E * 4, hipMemcpyDeviceToDevice, g.stream));
     } else if (kq) {
@@ -461,12 +437,13 @@ static void plan_launch_prompt(DecodePlan *p) {
     HIP_CHECK(hipGetLastError());
     for (int il = 0; il < m.L; il++) {
         const DecodePlan::LW &w = p->lw[il];
+        const DecodePlan::LayerNorms &ln = p->ln[il];
         __half *mk = p->mem_k_at(il), *mv = p->mem_v_at(il);
         // inpSA (xa) = the previous layer's inpFF + its w2 output; cur = rms_norm(inpSA) * attn_norm
         if (il == 0)
-            norm_quant(p->xa, nullptr, nullptr, nullptr, w.attn_norm, nullptr);
+            norm_quant(p->xa, nullptr, nullptr, nullptr, ln.attn_norm, nullptr);
         else
-            norm_quant(p->p_te, sp_w2 > 1 ? p->p_te + te_stride : nullptr, p->xb, p->xa, w.attn_norm, nullptr);
+            norm_quant(p->p_te, sp_w2 > 1 ? p->p_te + te_stride : nullptr, p->xb, p->xa, ln.attn_norm, nullptr);
         {
             const QWeight *ws[3] = {&w.wq, &w.wk, &w.wv};
             float *ds[3] = {p->p_qf, p->p_kf, p->p_vf};
@@ -501,7 +478,7 @@ static void plan_launch_prompt(DecodePlan *p) {
             HIP_CHECK(hipGetLastError());
         }
         const int sp_wo = gemm(w.wo, p->p_te, nbE, te_stride);
-        norm_quant(p->p_te, sp_wo > 1 ? p->p_te + te_stride : nullptr, p->xa, p->xb, w.ffn_norm, nullptr);  // inpFF (xb) = wo output + inpSA
+        norm_quant(p->p_te, sp_wo > 1 ? p->p_te + te_stride : nullptr, p->xa, p->xb, ln.ffn_norm, nullptr);  // inpFF (xb) = wo output + inpSA
         {
             const QWeight *ws[2] = {&w.w1, &w.w3};
             float *ds[2] = {p->p_g1, p->p_g3};

@@ -260,8 +260,9 @@ static bool try_decode_plan(ggml_cgraph *gr, bool defer_wait = false) {
     if (spec_hit) {
         // already enqueued behind the previous token (same plan, position, token and attention variant): only the results are missing
     } else if (use_graph) {
-        if (!p->exec_v[av]) capture_into(&p->graph_v[av], &p->exec_v[av], launch);
-        HIP_CHECK(hipGraphLaunch(p->exec_v[av], g.stream));
+        VariantGraphs &vg = p->graphs[av];
+        if (!vg.exec) capture_into(&vg.graph, &vg.exec, launch);
+        HIP_CHECK(hipGraphLaunch(vg.exec, g.stream));
         p->replays++;
     } else {
         launch();
@@ -275,7 +276,7 @@ static bool try_decode_plan(ggml_cgraph *gr, bool defer_wait = false) {
     // ---- ... and the next one on spec: greedy token on the device, then the plan again, behind this token's result copies ----
     if (g.spec.cooldown > 0) g.spec.cooldown--;
     if (g.opt_speculate_next && g.spec.cooldown == 0 && use_graph && m.N == 1 && m.logits && m.wte && m.output &&
-        m.n_past + 2 < m.C && p->exec_v[av]) {
+        m.n_past + 2 < m.C && p->graphs[av].exec) {
         const int av2 = attn_variant(m, p, m.n_past + 2);
         {
             if (!g.results_ev) HIP_CHECK(hipEventCreateWithFlags(&g.results_ev, hipEventDisableTiming));
@@ -290,13 +291,13 @@ static bool try_decode_plan(ggml_cgraph *gr, bool defer_wait = false) {
             hipLaunchKernelGGL(k_argmax_next, dim3(1), dim3(1024), 0, g.stream, (const float *)p->logits_out, (int)m.V, p->prm, g.spec.tok_dev);
             HIP_CHECK(hipMemcpyAsync(g.spec.tok_pin, g.spec.tok_dev, 4, hipMemcpyDeviceToHost, g.stream));
             HIP_CHECK(hipEventRecord(g.spec.tok_ev, g.stream));
-            hipGraphExec_t &e2 = p->exec_s[av2];
-            if (!e2) {  // the plan once more, captured with its final norm / lm_head aimed at the alternates (DecodePlan::logits_alt)
+            VariantGraphs &vg2 = p->graphs[av2];
+            if (!vg2.spec_exec) {  // the plan once more, captured with its final norm / lm_head aimed at the alternates (DecodePlan::logits_alt)
                 p->spec_out = true;
-                capture_into(&p->graph_s[av2], &e2, [&] { plan_launch_decode(p, av2); });
+                capture_into(&vg2.spec_graph, &vg2.spec_exec, [&] { plan_launch_decode(p, av2); });
                 p->spec_out = false;
             }
-            HIP_CHECK(hipGraphLaunch(e2, g.stream));
+            HIP_CHECK(hipGraphLaunch(vg2.spec_exec, g.stream));
             g.spec.pending = true;
             g.spec.plan = p;
             g.spec.n_past = m.n_past + 1;
@@ -352,7 +353,7 @@ static int decode_greedy_chain(ggml_cgraph *last, int n, int32_t *out_tokens, fl
         HIP_CHECK(hipMalloc((void **)&p->chain_out, (size_t)p->chain_cap * 4));
     }
     if (!p->chain_ring) HIP_CHECK(hipMalloc((void **)&p->chain_ring, 64 * 4));
-    const bool use_graph = g.opt_graph && !g.timing.on && (p->exec_v[0] || p->exec_v[1] || p->exec_v[2] || p->exec_v[3] || p->exec_v[4]);
+    const bool use_graph = g.opt_graph && !g.timing.on && p->any_captured();
     int i0 = 0;
     // option chain_k = K (> 1): K tokens per graph launch — every kernel of the plan reads its token and position from the
     // DecParams that k_argmax_next advances on the device, so the launches of consecutive tokens are the same launches.  Only
@@ -387,11 +388,10 @@ static int decode_greedy_chain(ggml_cgraph *last, int n, int32_t *out_tokens, fl
         if (av != AV_SPLIT && fused_qkv_shape(m, av_heads_split(av)).ok) g.stat_fused_tokens++;
         if (av >= AV_FUSED2) g.stat_fused_heads_tokens++;
         if (use_graph) {
-            hipGraph_t &gr_v = p->graph_v[av];
-            hipGraphExec_t &e1 = p->exec_v[av], &e2 = p->exec2_v[av];
-            if (!e1) capture_into(&gr_v, &e1, [&] { plan_launch_decode(p, av); });  // the chain crossed into a variant no evaluation has captured yet
-            if (!e2) HIP_CHECK(hipGraphInstantiate(&e2, gr_v, nullptr, nullptr, 0));
-            HIP_CHECK(hipGraphLaunch((i & 1) ? e2 : e1, g.stream));
+            VariantGraphs &vg = p->graphs[av];
+            if (!vg.exec) capture_into(&vg.graph, &vg.exec, [&] { plan_launch_decode(p, av); });  // the chain crossed into a variant no evaluation has captured yet
+            if (!vg.exec2) HIP_CHECK(hipGraphInstantiate(&vg.exec2, vg.graph, nullptr, nullptr, 0));
+            HIP_CHECK(hipGraphLaunch((i & 1) ? vg.exec2 : vg.exec, g.stream));
         } else {
             plan_launch_decode(p, av);
         }
@@ -480,8 +480,9 @@ static int decode_batch(ggml_cgraph *const *graphs, int B) {
     h2d_small((char *)p->prm, &hp, sizeof(hp));
     h2d_small((char *)p->bcols, &hb, sizeof(hb));
     if (g.opt_graph && !g.timing.on) {
-        if (!p->exec_v[0]) capture_into(&p->graph_v[0], &p->exec_v[0], [&] { plan_launch_batch(p); });
-        HIP_CHECK(hipGraphLaunch(p->exec_v[0], g.stream));
+        VariantGraphs &vg = p->graphs[AV_SHORT];
+        if (!vg.exec) capture_into(&vg.graph, &vg.exec, [&] { plan_launch_batch(p); });
+        HIP_CHECK(hipGraphLaunch(vg.exec, g.stream));
         p->replays++;
     } else {
         plan_launch_batch(p);

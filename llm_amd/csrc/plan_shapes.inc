@@ -11,11 +11,13 @@
 // The first three and the last are captured once in a hipGraph per attention variant and replayed for the following tokens with only
 // {n_past, token} changing in a device-side parameter block.  One file per concern, included in this order from
 // backend_executor.inc inside hip_backend.hip's anonymous namespace; nothing needs a forward declaration:
-//   plan_shapes.inc  LlamaMatch, DecodePlan and every "which kernel, which grid for which shape" decision (plain host functions
+//   plan_shapes.inc  LlamaMatch, DecodePlan (the layers' matrices as LayerMats<format>, the captured graphs as one VariantGraphs
+//                    per attention variant) and every "which kernel, which grid for which shape" decision (plain host functions
 //                    the matcher, the launchers, the run loop and the test hooks of backend_tools.inc all call)
 //   plan_match.inc   the structural graph matcher
-//   plan_build.inc   weights, signature and activation pool of a plan
-//   plan_decode.inc  the single-token launchers: plan_launch_all, plan_launch_k, plan_launch_f16
+//   plan_build.inc   weights, signature and activation pool of a plan (plan_pool_layout: every buffer declared once)
+//   plan_decode.inc  the single-token launchers: plan_launch_all, plan_launch_k, plan_launch_f16, and what the last two share
+//                    around their mat-vecs (plan_open_rows, plan_attn_f32, plan_hand_on)
 //   plan_prompt.inc  plan_launch_multi, plan_launch_batch, prompt_attention, plan_launch_prompt
 //   plan_run.inc     capture and replay, speculation, the fused-timeout re-run, the greedy chain, the batched step
 //
@@ -28,9 +30,19 @@ struct F16W {
     const __half *p;
     int64_t ld, M;
 };
-struct LayerW {
-    const ggml_tensor *attn_norm = nullptr, *wq = nullptr, *wk = nullptr, *wv = nullptr, *wo = nullptr,
-                      *ffn_norm = nullptr, *w1 = nullptr, *w2 = nullptr, *w3 = nullptr;
+// the seven matrices of a layer in whatever form W a matcher or a plan holds them; at(0 .. LAYER_MATS - 1) is "for each matrix"
+static const int LAYER_MATS = 7;
+template <class W>
+struct LayerMats {
+    W wq{}, wk{}, wv{}, wo{}, w1{}, w2{}, w3{};
+    const W &at(int i) const {
+        const W *const all[LAYER_MATS] = {&wq, &wk, &wv, &wo, &w1, &w2, &w3};
+        return *all[i];
+    }
+    W &at(int i) { return const_cast<W &>(static_cast<const LayerMats *>(this)->at(i)); }
+};
+struct LayerW : LayerMats<const ggml_tensor *> {
+    const ggml_tensor *attn_norm = nullptr, *ffn_norm = nullptr;
     const ggml_tensor *cur = nullptr;  // the normed activation feeding wq/wk/wv (identity key for the KV stores)
     bool k_store = false, v_store = false;
 };
@@ -52,25 +64,45 @@ struct LlamaMatch {
     const ggml_tensor *stage_in = nullptr, *stage_out = nullptr;  // layer-split hand-off buffers (persistent f32 leaves)
     std::vector<LayerW> layers;
 };
+// Attention variants of the single-token plan (one hipGraph each, chosen per token by the context length: attn_variant):
+//   AV_SHORT  the attention of a head is ONE workgroup: inside the wq|wk|wv launch (k_qkv_attn) where the shape allows, else k_attn_decode
+//   AV_SPLIT  plain wq|wk|wv launch, then the position-split attention over all CUs (k_attn_split_one / the three launches)
+//   AV_FUSED2 / 3 / 4  k_qkv_attn with 2 / 3 / 4 attention workgroups per head (512 positions each: up to 1024 / 1536 / 2048)
+enum { AV_SHORT = 0, AV_SPLIT = 1, AV_FUSED2 = 2, AV_FUSED3 = 3, AV_FUSED4 = 4, AV_COUNT = 5 };
+static inline int av_heads_split(int av) { return av >= AV_FUSED2 ? av : 1; }
+// the captured graphs of ONE attention variant of a plan (they freeze which kernels run: options and the device's slot count at capture time)
+struct VariantGraphs {
+    hipGraph_t graph = nullptr;
+    hipGraphExec_t exec = nullptr, exec2 = nullptr;  // exec2: a second instance of the same graph — a chain alternates so that a launch never waits for its own previous run
+    hipGraph_t spec_graph = nullptr;  // the backend's own speculative next-token run: the same launches aimed at the alternates (DecodePlan::logits_alt)
+    hipGraphExec_t spec_exec = nullptr;
+    void drop() {
+        for (hipGraphExec_t e : {exec, exec2, spec_exec})
+            if (e) (void)hipGraphExecDestroy(e);
+        for (hipGraph_t gr : {graph, spec_graph})
+            if (gr) (void)hipGraphDestroy(gr);
+        *this = VariantGraphs{};
+    }
+};
 // ---------------------------------------------------------------------------------------------------
 // the cached plan
 // ---------------------------------------------------------------------------------------------------
 struct DecodePlan {
     std::vector<uint64_t> sig;
     LlamaMatch m;  // tensors of the graph the plan was built from (weights are persistent; IO nodes by address)
-    struct LW {
-        QWeight wq, wk, wv, wo, w1, w2, w3;
+    // the layers' matrices in the one form the plan's kind reads, the other two vectors empty: block formats as SoA weights (the
+    // K-quant prompt plan fills these too, from the f16 copies: k_prompt_weights), K-quants as planar K weights (each carries its own
+    // type), F16 as the tensors' own rows (no re-layout, no copy)
+    using LW = LayerMats<QWeight>;
+    using KLW = LayerMats<KWeight>;
+    using FLW = LayerMats<F16W>;
+    std::vector<LW> lw;
+    std::vector<KLW> klw;
+    std::vector<FLW> flw;
+    struct LayerNorms {
         const float *attn_norm, *ffn_norm;
     };
-    std::vector<LW> lw;
-    struct KLW {  // K plan: the same seven matrices as planar K weights (each carries its own type)
-        KWeight wq, wk, wv, wo, w1, w2, w3;
-    };
-    std::vector<KLW> klw;
-    struct FLW {  // F16 plan: the tensors' own rows (no re-layout, no copy)
-        F16W wq, wk, wv, wo, w1, w2, w3;
-    };
-    std::vector<FLW> flw;
+    std::vector<LayerNorms> ln;  // every kind of plan
     F16W f_wte{}, f_output{};
     KWeight k_wte{}, k_output{};
     // K plan activations: f32 rows of wk / wv / the merged heads / w3, and ONE Q8_K row (max(E, F) wide) every mat-vec reads
@@ -121,15 +153,15 @@ struct DecodePlan {
     char *logits_alt = nullptr;
     float *emb_alt = nullptr;
     bool spec_out = false;  // set while the speculative graph is captured: plan_launch_* aim the final norm / lm_head at the alternates
-    hipGraph_t graph_s[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};       // ... that graph, per attention variant
-    hipGraphExec_t exec_s[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     int *chain_out = nullptr;   // ggml_hip_decode_greedy_chain: sampled ids (device)
     int *chain_ring = nullptr;  // ... of one K-token graph launch (option chain_k), copied into chain_out behind it
     int chain_cap = 0;
-    // one captured graph per ATTENTION VARIANT of the plan (enum below); exec2: a second instance of the same graph — a chain
-    // alternates so that a launch never waits for its own previous run
-    hipGraph_t graph_v[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    hipGraphExec_t exec_v[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}, exec2_v[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    VariantGraphs graphs[AV_COUNT];  // per attention variant; a batched step's plan has the one of AV_SHORT
+    bool any_captured() const {
+        for (const VariantGraphs &v : graphs)
+            if (v.exec) return true;
+        return false;
+    }
     float *att_sc = nullptr, *att_pmax = nullptr, *att_part = nullptr;  // scratch of the split attention
     unsigned long long *att_mxg = nullptr, *att_sumg = nullptr, *att_partg = nullptr;  // ... as one launch (k_attn_split_one): range maxima / sums / partial-output granules, [L] sets of them (att_*_at)
     unsigned long long *att_mxg_at(int il) const { return att_mxg + (size_t)il * m.H * att_S; }
@@ -147,19 +179,8 @@ struct DecodePlan {
 std::vector<DecodePlan *> g_plans_[GGML_HIP_MAX_BACKENDS];  // per slot: a plan holds device addresses
 #define g_plans (g_plans_[g.slot])
 
-// the captured graphs of a plan (they freeze which kernels run: options and the device's slot count at capture time)
 void drop_plan_graphs(DecodePlan *p) {
-    for (int v = 0; v < 5; v++) {
-        if (p->exec_v[v]) (void)hipGraphExecDestroy(p->exec_v[v]);
-        if (p->exec2_v[v]) (void)hipGraphExecDestroy(p->exec2_v[v]);
-        if (p->graph_v[v]) (void)hipGraphDestroy(p->graph_v[v]);
-        p->exec_v[v] = p->exec2_v[v] = nullptr;
-        p->graph_v[v] = nullptr;
-        if (p->exec_s[v]) (void)hipGraphExecDestroy(p->exec_s[v]);
-        if (p->graph_s[v]) (void)hipGraphDestroy(p->graph_s[v]);
-        p->exec_s[v] = nullptr;
-        p->graph_s[v] = nullptr;
-    }
+    for (VariantGraphs &v : p->graphs) v.drop();
     if (p->exec_chain) (void)hipGraphExecDestroy(p->exec_chain);
     if (p->graph_chain) (void)hipGraphDestroy(p->graph_chain);
     p->exec_chain = nullptr;
@@ -236,12 +257,6 @@ static BigShape big_shape(int xsrc, int epi, int64_t nb, int64_t units) {
 // wq|wk|wv + attention in one launch (kernels/decode_fused.h): n_head attention workgroups + the mat-vec on the remaining
 // G - n_head.  Taken when the mat-vec deals as evenly over G - n_head workgroups as over G (7B on 256 CUs: 6144 row pairs
 // = 2 per wave of 224 x 14 as of 256 x 12) — otherwise the two-launch pair is the faster one.
-// Attention variants of the single-token plan (one hipGraph each, chosen per token by the context length: attn_variant):
-//   AV_SHORT  the attention of a head is ONE workgroup: inside the wq|wk|wv launch (k_qkv_attn) where the shape allows, else k_attn_decode
-//   AV_SPLIT  plain wq|wk|wv launch, then the position-split attention over all CUs (k_attn_split_one / the three launches)
-//   AV_FUSED2 / 3 / 4  k_qkv_attn with 2 / 3 / 4 attention workgroups per head (512 positions each: up to 1024 / 1536 / 2048)
-enum { AV_SHORT = 0, AV_SPLIT = 1, AV_FUSED2 = 2, AV_FUSED3 = 3, AV_FUSED4 = 4, AV_COUNT = 5 };
-static inline int av_heads_split(int av) { return av >= AV_FUSED2 ? av : 1; }
 struct FusedShape {
     bool ok = false;
     int G = 0, W = 0, S = 1;
@@ -351,8 +366,8 @@ static bool kbig_ok(const DecodePlan *p) {  // K matrices whose rows of a wave f
     if (!g.opt_kbig || p->m.N != 1) return false;
     auto ok = [&](const KWeight &w) { return kbig_weight_ok(w.kt, w.nsb, w.M, p->m.E); };
     for (auto &l : p->klw)
-        for (const KWeight *w : {&l.wq, &l.wk, &l.wv, &l.wo, &l.w1, &l.w2, &l.w3})
-            if (!ok(*w)) return false;
+        for (int i = 0; i < LAYER_MATS; i++)
+            if (!ok(l.at(i))) return false;
     return !p->m.output || ok(p->k_output);
 }
 // ---- k_mmvq_f16 (kernels/decode_f16.h) ----
