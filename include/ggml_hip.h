@@ -411,6 +411,16 @@ GGML_API size_t ggml_quantize_q4_1(const float *src, void *dst, int n, int k, in
 GGML_API size_t ggml_quantize_q5_0(const float *src, void *dst, int n, int k, int64_t *hist);
 GGML_API size_t ggml_quantize_q5_1(const float *src, void *dst, int n, int k, int64_t *hist);
 GGML_API size_t ggml_quantize_q8_0(const float *src, void *dst, int n, int k, int64_t *hist);
+/* The K types (bindgen: crates/ggml/sys/src/lib.rs:3472-3515): n values in rows of k, k % 256 == 0; returns the bytes
+ * written.  The encoders follow this project's own fit (oracle/SEMANTICS.md: min/max per sub-block for Q2_K / Q4_K /
+ * Q5_K, abs-max for Q3_K / Q6_K), not upstream's iterative scale search, whose source the reference tree does not
+ * carry: blocks are valid and decode everywhere, parity with upstream's bytes is unpinned.  `hist` is left untouched. */
+GGML_API size_t ggml_quantize_q2_K(const float *src, void *dst, int n, int k, int64_t *hist);
+GGML_API size_t ggml_quantize_q3_K(const float *src, void *dst, int n, int k, int64_t *hist);
+GGML_API size_t ggml_quantize_q4_K(const float *src, void *dst, int n, int k, int64_t *hist);
+GGML_API size_t ggml_quantize_q5_K(const float *src, void *dst, int n, int k, int64_t *hist);
+GGML_API size_t ggml_quantize_q6_K(const float *src, void *dst, int n, int k, int64_t *hist);
+/* start % 32 == 0 (K types: start % 256 == 0) */
 GGML_API size_t ggml_quantize_chunk(enum ggml_type type, const float *src, void *dst, int start, int n,
                                     int64_t *hist);
 GGML_API ggml_type_traits_t ggml_internal_get_type_traits(enum ggml_type i); /* lib.rs:2973 */
@@ -613,7 +623,9 @@ GGML_API int ggml_hip_row_probs(const struct ggml_tensor *logits, int64_t row_be
 /* ggml_quantize_q4_0 / q4_1 / q5_0 / q5_1 / q8_0 (crates/ggml/src/lib.rs:419-483, called by
  * crates/llm-base/src/quantize.rs:363-379) computed on the device: n f32 values at `src` (host memory, rows
  * of k, k % 32 == 0) -> raw GGML blocks at `dst` (host memory), byte-identical to the host functions; the 16-bin
- * histogram is ADDED to hist (may be NULL).  Returns the bytes written.  PCIe-bound: ~1.2 bytes moved per weight. */
+ * histogram is ADDED to hist (may be NULL).  Returns the bytes written.  PCIe-bound: ~1.2 bytes moved per weight.
+ * Also ggml_quantize_q2_K .. q6_K (k % 256 == 0, one wave per super-block: kernels/kquant_encode.h), which leave hist
+ * untouched. */
 GGML_API size_t ggml_hip_quantize(enum ggml_type type, const float *src, void *dst, int64_t n, int64_t k, int64_t *hist);
 /* The same for a matrix that already lives in HBM: `src` is a contiguous 2-D f32 or f16 tensor previously handed to
  * ggml_hip_transform_tensor; `dst` is a tensor of a 32-wide block type with the same shape whose data pointer names the

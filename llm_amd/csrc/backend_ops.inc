@@ -679,15 +679,15 @@ void op_bin(ggml_tensor *dst, int op) {
     HIP_CHECK(hipGetLastError());
 }
 
-// ggml_add(W, x) with W quantized (Q4_0 / Q4_1 / Q5_0 / Q5_1 / Q8_0) or f16 and x f32: the add of a LoRA patch
+// ggml_add(W, x) with W quantized (Q4_0 / Q4_1 / Q5_0 / Q5_1 / Q8_0, Q2_K .. Q6_K) or f16 and x f32: the add of a LoRA patch
 // (lora.rs:126), ggml's add_q_f32 / add_f16_f32.  dst has W's type; same shape only, as upstream asserts.
 void op_add_lowp(ggml_tensor *dst) {
     const ggml_tensor *a = dst->src[0], *b = dst->src[1];
-    if (kt_of(a->type) >= 0)
-        die("add: '%s' is %s: LoRA on K-quant weights is not supported (targets may be Q4_0, Q4_1, Q5_0, Q5_1, Q8_0 or F16)",
-            a->name, ggml_type_name(a->type));
+    const int kt = kt_of(a->type);
+    if (kt >= 0 && a->ne[0] % 256 != 0)
+        die("add: '%s' is %s with ne0 = %lld: a K-quant src0 needs ne0 %% 256 == 0", a->name, ggml_type_name(a->type), (long long)a->ne[0]);
     const int qt = qt_of(a->type);
-    if (qt < 0 && a->type != GGML_TYPE_F16)
+    if (qt < 0 && kt < 0 && a->type != GGML_TYPE_F16)
         die("add: '%s' is %s: no device add for this src0 type", a->name, ggml_type_name(a->type));
     bool same = true;
     for (int i = 0; i < 4; i++) same = same && a->ne[i] == b->ne[i] && a->ne[i] == dst->ne[i];
@@ -709,6 +709,17 @@ void op_add_lowp(ggml_tensor *dst) {
     if (a->type == GGML_TYPE_F16) {
         Timed tm(GGML_HIP_KCLASS_OTHER, (double)n * 8);
         hipLaunchKernelGGL(k_add_f16, grid1(n), dim3(256), 0, g.stream, va, vb, vd, n);
+    } else if (kt >= 0) {  // one wave per super-block, four per workgroup (kernels/lora.h k_add_k)
+        const int64_t spr = a->ne[0] / 256, nsb = n / 256;
+        Timed tm(GGML_HIP_KCLASS_OTHER, (double)nsb * (2.0 * (double)es + 1024.0));
+        const dim3 grid((unsigned)((nsb + 3) / 4));
+        switch (kt) {
+            case KT_Q2_K: hipLaunchKernelGGL(k_add_k<KT_Q2_K>, grid, dim3(256), 0, g.stream, va, vb, vd, spr, nsb); break;
+            case KT_Q3_K: hipLaunchKernelGGL(k_add_k<KT_Q3_K>, grid, dim3(256), 0, g.stream, va, vb, vd, spr, nsb); break;
+            case KT_Q4_K: hipLaunchKernelGGL(k_add_k<KT_Q4_K>, grid, dim3(256), 0, g.stream, va, vb, vd, spr, nsb); break;
+            case KT_Q5_K: hipLaunchKernelGGL(k_add_k<KT_Q5_K>, grid, dim3(256), 0, g.stream, va, vb, vd, spr, nsb); break;
+            default: hipLaunchKernelGGL(k_add_k<KT_Q6_K>, grid, dim3(256), 0, g.stream, va, vb, vd, spr, nsb); break;
+        }
     } else {
         BK_ASSERT(a->ne[0] % 32 == 0);
         const int64_t bpr = a->ne[0] / 32, nblocks = n / 32;

@@ -968,8 +968,207 @@ size_t quantize_rows(ggml_type type, const float *src, void *dst, int n, int k, 
             for (int i = 0; i < 16; i++) hist[i] += hs[(size_t)t][(size_t)i];
     return (size_t)nblocks * bs;
 }
+
+// ---- K-quants: ggml_quantize_q2_K .. q6_K (bindgen: crates/ggml/sys/src/lib.rs:3472-3515) ----------------------------
+// Upstream's k_quants.c is not part of the reference tree, so its iterative make_qkx / make_qx scale search cannot be
+// restated.  These encoders follow the fit every K-quant weight of this project is made with (oracle/SEMANTICS.md,
+// quantize_row_q*_K of the oracle) and produce its bytes: a min/max fit per sub-block for Q2_K / Q4_K / Q5_K (minimum
+// clamped to <= 0, super-block scales from the largest sub-block scale and minimum), an abs-max fit for Q3_K / Q6_K (the
+// first value of largest magnitude maps to -4 / -32, the first sub-block scale of largest magnitude to -32 / -128).
+// PARITY WITH UPSTREAM UNPINNED.  Written in two steps — fit (codes L[256] plus sub-block scale codes),
+// then the type's packing — the structure of the device encoder (kernels/kquant_encode.h).  No histogram: `hist` is
+// left untouched (there is no upstream source to restate one from).
+constexpr int QK_K = 256;
+inline int nearest_int(float f) { return (int)lrintf(f); }  // round half to even (default rounding mode)
+inline int iclamp(int v, int lo, int hi) { return v < lo ? lo : v > hi ? hi : v; }
+inline float f16_of(ggml_fp16_t h) { return ggml_fp16_to_fp32(h); }
+
+// SUB values per sub-block, codes 0 .. QMAX, scale / min codes 0 .. SMAX
+template <int SUB, int QMAX, int SMAX>
+void kfit_minmax(const float *x, uint8_t *L, uint8_t *ls, uint8_t *lm, ggml_fp16_t *d16, ggml_fp16_t *dmin16) {
+    constexpr int NS = QK_K / SUB;
+    float scales[NS], mins[NS], max_scale = 0.0f, max_min = 0.0f;
+    for (int j = 0; j < NS; j++) {
+        float lo = 0.0f, hi = 0.0f;
+        for (int l = 0; l < SUB; l++) {
+            const float v = x[SUB * j + l];
+            if (v < lo) lo = v;
+            if (v > hi) hi = v;
+        }
+        scales[j] = (hi - lo) / (float)QMAX;
+        mins[j] = -lo;
+        if (scales[j] > max_scale) max_scale = scales[j];
+        if (mins[j] > max_min) max_min = mins[j];
+    }
+    const float inv_scale = max_scale > 0 ? (float)SMAX / max_scale : 0.0f, inv_min = max_min > 0 ? (float)SMAX / max_min : 0.0f;
+    *d16 = ggml_fp32_to_fp16(max_scale / (float)SMAX);
+    *dmin16 = ggml_fp32_to_fp16(max_min / (float)SMAX);
+    for (int j = 0; j < NS; j++) {
+        const int s = std::min(SMAX, nearest_int(inv_scale * scales[j])), m = std::min(SMAX, nearest_int(inv_min * mins[j]));
+        ls[j] = (uint8_t)s;
+        lm[j] = (uint8_t)m;
+        const float d = f16_of(*d16) * s, dm = f16_of(*dmin16) * m;
+        for (int l = 0; l < SUB; l++)
+            L[SUB * j + l] = (uint8_t)(d != 0.0f ? iclamp(nearest_int((x[SUB * j + l] + dm) / d), 0, QMAX) : 0);
+    }
+}
+// 16 sub-blocks of 16; codes q + NEG with q in -NEG .. NEG - 1; sub-block scale codes l[j] in -SNEG .. SNEG - 1 (the
+// lower bound is reached, never exceeded).  false: the super-block is all zero (nothing written)
+template <int NEG, int SNEG>
+bool kfit_absmax(const float *x, uint8_t *L, int *l, ggml_fp16_t *d16) {
+    float sc[16], max_abs = 0.0f, max_sc = 0.0f;
+    for (int j = 0; j < 16; j++) {
+        float amax = 0.0f, vmax = 0.0f;
+        for (int i = 0; i < 16; i++) {
+            const float v = x[16 * j + i];
+            if (fabsf(v) > amax) {
+                amax = fabsf(v);
+                vmax = v;
+            }
+        }
+        sc[j] = amax > 0 ? vmax / -(float)NEG : 0.0f;
+        if (fabsf(sc[j]) > max_abs) {
+            max_abs = fabsf(sc[j]);
+            max_sc = sc[j];
+        }
+    }
+    if (max_abs == 0.0f) return false;
+    const float iscale = -(float)SNEG / max_sc;
+    *d16 = ggml_fp32_to_fp16(1.0f / iscale);
+    for (int j = 0; j < 16; j++) {
+        l[j] = iclamp(nearest_int(iscale * sc[j]), -SNEG, SNEG - 1);
+        const float d = f16_of(*d16) * l[j];
+        for (int i = 0; i < 16; i++)
+            L[16 * j + i] = (uint8_t)((d != 0.0f ? iclamp(nearest_int(x[16 * j + i] / d), -NEG, NEG - 1) : 0) + NEG);
+    }
+    return true;
+}
+// 2-bit planes of Q2_K / Q3_K: byte 32 n + l holds elements 128 n + l + {0, 32, 64, 96}
+inline void pack_2bit(const uint8_t *L, uint8_t *qs) {
+    for (int n = 0; n < 2; n++)
+        for (int l = 0; l < 32; l++) {
+            const uint8_t *p = L + 128 * n + l;
+            qs[32 * n + l] = (uint8_t)((p[0] & 3) | ((p[32] & 3) << 2) | ((p[64] & 3) << 4) | ((p[96] & 3) << 6));
+        }
+}
+// the 12 scale bytes of Q4_K / Q5_K (set_scale_min_k4 for j = 0 .. 7)
+inline void pack_scale_min_k4(const uint8_t *ls, const uint8_t *lm, uint8_t *q) {
+    for (int j = 0; j < 4; j++) {
+        q[j] = (uint8_t)(ls[j] | ((ls[j + 4] >> 4) << 6));
+        q[j + 4] = (uint8_t)(lm[j] | ((lm[j + 4] >> 4) << 6));
+        q[j + 8] = (uint8_t)((ls[j + 4] & 0xF) | ((lm[j + 4] & 0xF) << 4));
+    }
+}
+inline void put_h(uint8_t *p, ggml_fp16_t h) { memcpy(p, &h, 2); }
+
+void quant_superblock(ggml_type type, const float *x, uint8_t *o) {
+    uint8_t L[QK_K], ls[16], lm[16];
+    ggml_fp16_t d = 0, dmin = 0;
+    switch (type) {
+        case GGML_TYPE_Q2_K: {  // scales[16], qs[64], d, dmin
+            kfit_minmax<16, 3, 15>(x, L, ls, lm, &d, &dmin);
+            for (int j = 0; j < 16; j++) o[j] = (uint8_t)(ls[j] | (lm[j] << 4));
+            pack_2bit(L, o + 16);
+            put_h(o + 80, d);
+            put_h(o + 82, dmin);
+        } break;
+        case GGML_TYPE_Q3_K: {  // hmask[32], qs[64], scales[12], d
+            int l[16];
+            if (!kfit_absmax<4, 32>(x, L, l, &d)) {  // d = 0, every scale code 32 (= 0), every q = 0
+                for (int j = 0; j < 16; j++) l[j] = 0;
+                memset(L, 4, QK_K);
+            }
+            for (int m = 0; m < 32; m++) {
+                int h = 0;
+                for (int b = 0; b < 8; b++) h |= (L[32 * b + m] > 3) << b;
+                o[m] = (uint8_t)h;
+            }
+            pack_2bit(L, o + 32);
+            uint8_t *s = o + 96;
+            for (int j = 0; j < 8; j++) s[j] = (uint8_t)(((l[j] + 32) & 0xF) | (((l[j + 8] + 32) & 0xF) << 4));
+            for (int j = 0; j < 4; j++)
+                s[8 + j] = (uint8_t)(((l[j] + 32) >> 4) | (((l[j + 4] + 32) >> 4) << 2) | (((l[j + 8] + 32) >> 4) << 4) | (((l[j + 12] + 32) >> 4) << 6));
+            put_h(o + 108, d);
+        } break;
+        case GGML_TYPE_Q4_K:
+        case GGML_TYPE_Q5_K: {  // d, dmin, scales[12], [qh[32],] qs[128]
+            const bool five = type == GGML_TYPE_Q5_K;
+            if (five)
+                kfit_minmax<32, 31, 63>(x, L, ls, lm, &d, &dmin);
+            else
+                kfit_minmax<32, 15, 63>(x, L, ls, lm, &d, &dmin);
+            put_h(o, d);
+            put_h(o + 2, dmin);
+            pack_scale_min_k4(ls, lm, o + 4);
+            uint8_t *qs = o + (five ? 48 : 16);
+            for (int c = 0; c < 4; c++)
+                for (int i = 0; i < 32; i++) qs[32 * c + i] = (uint8_t)((L[64 * c + i] & 0xF) | ((L[64 * c + i + 32] & 0xF) << 4));
+            if (five)
+                for (int i = 0; i < 32; i++) {  // bit g of qh[i]: element 32 g + i has code > 15
+                    int h = 0;
+                    for (int g8 = 0; g8 < 8; g8++) h |= (L[32 * g8 + i] >> 4) << g8;
+                    o[16 + i] = (uint8_t)h;
+                }
+        } break;
+        case GGML_TYPE_Q6_K: {  // ql[128], qh[64], scales[16], d
+            int l[16];
+            if (!kfit_absmax<32, 128>(x, L, l, &d)) {
+                memset(o, 0, 210);
+                break;
+            }
+            for (int n = 0; n < 2; n++)
+                for (int i = 0; i < 32; i++) {
+                    const uint8_t *p = L + 128 * n + i;
+                    o[64 * n + i] = (uint8_t)((p[0] & 0xF) | ((p[64] & 0xF) << 4));
+                    o[64 * n + 32 + i] = (uint8_t)((p[32] & 0xF) | ((p[96] & 0xF) << 4));
+                    o[128 + 32 * n + i] = (uint8_t)((p[0] >> 4) | ((p[32] >> 4) << 2) | ((p[64] >> 4) << 4) | ((p[96] >> 4) << 6));
+                }
+            for (int j = 0; j < 16; j++) o[192 + j] = (uint8_t)(int8_t)std::min(127, l[j]);
+            put_h(o + 208, d);
+        } break;
+        default:
+            fprintf(stderr, "ggml_quantize: unsupported type %d\n", (int)type);
+            abort();
+    }
+}
+
+size_t quantize_rows_k(ggml_type type, const float *src, void *dst, int n, int k) {
+    GGML_ASSERT(k % QK_K == 0 && n % k == 0);
+    const size_t bs = TYPE_INFO[type].size;
+    uint8_t *out = (uint8_t *)dst;
+    const int nsb = n / QK_K;
+    const unsigned hw = std::thread::hardware_concurrency();
+    const int nthr = nsb >= (1 << 12) ? (int)std::min<unsigned>(hw ? hw : 1, 16) : 1;  // independent super-blocks, as quantize_rows
+    const int per = (nsb + nthr - 1) / nthr;
+    auto run = [=](int b0, int b1) {
+        for (int b = b0; b < b1; b++) quant_superblock(type, src + (size_t)b * QK_K, out + (size_t)b * bs);
+    };
+    if (nthr <= 1) {
+        run(0, nsb);
+    } else {
+        std::vector<std::thread> th;
+        for (int t = 0; t < nthr; t++) th.emplace_back(run, t * per, std::min(nsb, (t + 1) * per));
+        for (auto &x : th) x.join();
+    }
+    return (size_t)nsb * bs;
+}
 }  // namespace
 
+size_t ggml_quantize_q2_K(const float *src, void *dst, int n, int k, int64_t *) {
+    return quantize_rows_k(GGML_TYPE_Q2_K, src, dst, n, k);
+}
+size_t ggml_quantize_q3_K(const float *src, void *dst, int n, int k, int64_t *) {
+    return quantize_rows_k(GGML_TYPE_Q3_K, src, dst, n, k);
+}
+size_t ggml_quantize_q4_K(const float *src, void *dst, int n, int k, int64_t *) {
+    return quantize_rows_k(GGML_TYPE_Q4_K, src, dst, n, k);
+}
+size_t ggml_quantize_q5_K(const float *src, void *dst, int n, int k, int64_t *) {
+    return quantize_rows_k(GGML_TYPE_Q5_K, src, dst, n, k);
+}
+size_t ggml_quantize_q6_K(const float *src, void *dst, int n, int k, int64_t *) {
+    return quantize_rows_k(GGML_TYPE_Q6_K, src, dst, n, k);
+}
 size_t ggml_quantize_q4_0(const float *src, void *dst, int n, int k, int64_t *hist) {
     return quantize_rows(GGML_TYPE_Q4_0, src, dst, n, k, hist);
 }
@@ -994,6 +1193,10 @@ size_t ggml_quantize_chunk(enum ggml_type type, const float *src, void *dst, int
     if (type == GGML_TYPE_F32) {
         memcpy((float *)dst + start, src + start, (size_t)n * 4);
         return (size_t)n * 4;
+    }
+    if (type >= GGML_TYPE_Q2_K && type <= GGML_TYPE_Q6_K) {
+        GGML_ASSERT(start % QK_K == 0);
+        return quantize_rows_k(type, src + start, (uint8_t *)dst + (size_t)(start / QK_K) * TYPE_INFO[type].size, n, QK_K);
     }
     uint8_t *out = (uint8_t *)dst + (size_t)(start / QK) * TYPE_INFO[type].size;
     return quantize_rows(type, src + start, out, n, QK, hist);

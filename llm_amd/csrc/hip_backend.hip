@@ -372,7 +372,9 @@ void ggml_hip_transform_tensor(void *data, struct ggml_tensor *tensor) {
     tensor->extra = upload_tensor(data, tensor, false);
 }
 
-// ---- device quantizer (kernels/quantize.h) ----
+// ---- device quantizer (kernels/quantize.h; K types: kernels/kquant_encode.h) ----
+// the 32-wide block types: ggml_hip_quantize and ggml_hip_quantize_resident.  The K types go through ggml_hip_quantize only
+// (kt_of): a resident K weight would need the planar re-layout of its super-blocks, which the resident path does not do.
 static bool quantizable(int type) {
     return type == GGML_TYPE_Q4_0 || type == GGML_TYPE_Q4_1 || type == GGML_TYPE_Q5_0 || type == GGML_TYPE_Q5_1 || type == GGML_TYPE_Q8_0;
 }
@@ -385,25 +387,53 @@ static void launch_quantize_blocks(const void *src_dev, bool f16_src, int type, 
         hipLaunchKernelGGL(k_quantize_blocks<false>, grid1(nblocks), dim3(256), 0, g.stream, src_dev, type, nblocks, out_dev, hist_dev);
     HIP_CHECK(hipGetLastError());
 }
+// the K types (kernels/kquant_encode.h): nsb super-blocks of 256 values, one wave each
+static void launch_quantize_k(const void *src_dev, bool f16_src, int kt, int64_t nsb, uint8_t *out_dev) {
+    Timed tm(GGML_HIP_KCLASS_OTHER, (double)nsb * (f16_src ? 512 : 1024) + (double)nsb * k_block_bytes(kt));
+    const dim3 grid((unsigned)((nsb + 3) / 4));
+#define QK_LAUNCH(KT)                                                                                              \
+    case KT:                                                                                                       \
+        if (f16_src)                                                                                               \
+            hipLaunchKernelGGL((k_quantize_k<KT, true>), grid, dim3(256), 0, g.stream, src_dev, nsb, out_dev);     \
+        else                                                                                                       \
+            hipLaunchKernelGGL((k_quantize_k<KT, false>), grid, dim3(256), 0, g.stream, src_dev, nsb, out_dev);    \
+        break;
+    switch (kt) {
+        QK_LAUNCH(KT_Q2_K)
+        QK_LAUNCH(KT_Q3_K)
+        QK_LAUNCH(KT_Q4_K)
+        QK_LAUNCH(KT_Q5_K)
+        QK_LAUNCH(KT_Q6_K)
+        default: BK_ASSERT(false);
+    }
+#undef QK_LAUNCH
+    HIP_CHECK(hipGetLastError());
+}
 size_t ggml_hip_quantize(enum ggml_type type, const float *src, void *dst, int64_t n, int64_t k, int64_t *hist) {
     SlotLock lk;
     ensure_init();
-    if (!quantizable(type)) die("ggml_hip_quantize: %s has no device encoder", ggml_type_name(type));
-    if (k % 32 != 0 || n % k != 0) die("ggml_hip_quantize: n = %lld must be rows of k = %lld, k %% 32 == 0", (long long)n, (long long)k);
+    const int kt = kt_of(type);
+    if (!quantizable(type) && kt < 0) die("ggml_hip_quantize: %s has no device encoder", ggml_type_name(type));
+    const int64_t qk = kt >= 0 ? 256 : 32;  // values per block
+    if (k % qk != 0 || n % k != 0)
+        die("ggml_hip_quantize: n = %lld must be rows of k = %lld, k %% %lld == 0", (long long)n, (long long)k, (long long)qk);
     const size_t bs = ggml_type_size(type);
-    const int64_t nblocks = n / 32;
-    const int64_t piece = (int64_t)1 << 23;  // blocks per pass: 1 GiB of f32 in, <= 272 MiB out
+    const int64_t nblocks = n / qk;
+    const int64_t piece = ((int64_t)1 << 23) * 32 / qk;  // blocks per pass: 1 GiB of f32 in, <= 272 MiB out
     char *din = nullptr, *dout = nullptr;
     unsigned long long *dh = nullptr;
     const int64_t cap = std::min(nblocks, piece);
-    dev_malloc((void **)&din, (size_t)cap * 128, "the quantizer input");
+    dev_malloc((void **)&din, (size_t)cap * qk * 4, "the quantizer input");
     dev_malloc((void **)&dout, (size_t)cap * bs, "the quantizer output");
     HIP_CHECK(hipMalloc((void **)&dh, 128));
     HIP_CHECK(hipMemsetAsync(dh, 0, 128, g.stream));
     for (int64_t b0 = 0; b0 < nblocks; b0 += piece) {
         const int64_t nb = std::min(piece, nblocks - b0);
-        h2d_bulk(din, src + b0 * 32, (size_t)nb * 128);
-        launch_quantize_blocks(din, false, (int)type, nb, (uint8_t *)dout, dh);
+        h2d_bulk(din, src + b0 * qk, (size_t)nb * qk * 4);
+        if (kt >= 0)
+            launch_quantize_k(din, false, kt, nb, (uint8_t *)dout);  // no histogram: `hist` stays as it is
+        else
+            launch_quantize_blocks(din, false, (int)type, nb, (uint8_t *)dout, dh);
         d2h_queue((char *)dst + (size_t)b0 * bs, dout, (size_t)nb * bs);  // pinned staging, delivered by d2h_finish
         d2h_finish();
     }

@@ -8,9 +8,15 @@
 // selects (common.h), as every other from_float the device runs.  The block is held in registers between the read and
 // the write, so dst may be src0 (ggml_add_inplace).
 // k_add_f16: one lane per element, f16(f32(a) + b) with round to nearest even.
+// k_add_k<KT>: the same for a K-quant src0 (Q2_K .. Q6_K), one wave per 256-weight super-block, four per workgroup.  The
+// wave stages the raw super-block in LDS, each lane decodes its four elements as dequantize_row_q*_K does (kq_decode4),
+// adds its four floats of src1 and the wave requantizes with kq_encode_wave (kernels/kquant_encode.h: the oracle's fit).
+// The whole input block is in LDS before a byte of the output block is written, so dst may be src0 here too.
 // Rows are addressed through nb[1..3] of each operand (the three have the same shape); elements within a row are
-// contiguous.  Both kernels are memory bound: bytes per block and per element in DESIGN.md §4.7.
+// contiguous.  k_add_q and k_add_f16 are memory bound, k_add_k by instruction issue at about half of k_add_q's bytes per
+// second: bytes per block and per element, and the measurement, in DESIGN.md §4.7.
 #pragma once
+#include "kquant_encode.h"
 #include "quantize.h"
 
 template <int T>
@@ -75,6 +81,33 @@ __global__ void __launch_bounds__(256) k_add_q(const TView a, const TView b, con
 #pragma unroll
     for (int j = 0; j < 32; j++) y[j] = __fadd_rn(y[j], pb[j]);
     q_block(y, T, pd, nullptr, sc);
+}
+
+template <int KT>
+__global__ void __launch_bounds__(256) k_add_k(const TView a, const TView b, const TView d, int64_t sb_per_row, int64_t nsb) {
+    __shared__ KqWave s_w[4];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int64_t g = (int64_t)blockIdx.x * 4 + wv;
+    const bool active = g < nsb;  // a wave past the end runs the barriers on zeros; its loads and stores are predicated off
+    const int64_t gg = active ? g : 0;
+    const int64_t blk = gg % sb_per_row, row = gg / sb_per_row;
+    const int64_t i1 = row % a.ne[1], i23 = row / a.ne[1], i2 = i23 % a.ne[2], i3 = i23 / a.ne[2];
+    constexpr int BS = KBlock<KT>::bytes;
+    const uint16_t *pa = (const uint16_t *)(a.p + i1 * a.nb[1] + i2 * a.nb[2] + i3 * a.nb[3] + blk * BS);
+    const float *pb = (const float *)(b.p + i1 * b.nb[1] + i2 * b.nb[2] + i3 * b.nb[3]) + blk * 256 + 4 * lane;
+    uint16_t *pd = (uint16_t *)(d.p + i1 * d.nb[1] + i2 * d.nb[2] + i3 * d.nb[3] + blk * BS);
+    KqWave &w = s_w[wv];
+
+    uint16_t *s16 = (uint16_t *)w.blk;
+    for (int i = lane; i < BS / 2; i += 64) s16[i] = active ? pa[i] : (uint16_t)0;
+    f32x4 x = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (active) x = f32x4{pb[0], pb[1], pb[2], pb[3]};  // rows of src1 are 4-byte aligned, no more is asserted
+    __syncthreads();
+    f32x4 y = kq_decode4<KT>(w, lane);
+#pragma unroll
+    for (int k = 0; k < 4; k++) y[k] = __fadd_rn(y[k], x[k]);
+    kq_encode_wave<KT>(y, lane, w);  // its first barrier stands between the reads of w.blk above and the writes of the new block
+    kq_store_block<KT>(w, lane, pd, active);
 }
 
 __global__ void __launch_bounds__(256) k_add_f16(const TView a, const TView b, const TView d, int64_t n) {

@@ -34,7 +34,7 @@ BLOCK_ELEMS = {TYPE_F32: 1, TYPE_F16: 1, TYPE_Q4_0: 32, TYPE_Q4_1: 32, TYPE_Q5_0
                TYPE_Q8_1: 32, TYPE_Q2_K: 256, TYPE_Q3_K: 256, TYPE_Q4_K: 256, TYPE_Q5_K: 256, TYPE_Q6_K: 256, TYPE_Q8_K: 256,
                TYPE_I8: 1, TYPE_I16: 1, TYPE_I32: 1}
 QUANT_TYPES = (TYPE_Q4_0, TYPE_Q4_1, TYPE_Q5_0, TYPE_Q5_1, TYPE_Q8_0)
-K_TYPES = (TYPE_Q2_K, TYPE_Q3_K, TYPE_Q4_K, TYPE_Q5_K, TYPE_Q6_K)  # files arrive pre-quantized: the library has no K-quant encoder (ggml_quantize_q4_K ...)
+K_TYPES = (TYPE_Q2_K, TYPE_Q3_K, TYPE_Q4_K, TYPE_Q5_K, TYPE_Q6_K)  # encoders: ggml_quantize_q2_K ... q6_K, the oracle's min/max and abs-max fits (not upstream's scale search)
 # llama.cpp ftype codes for GGJT files (crates/ggml/sys/src/llama.rs:16-32)
 FTYPE_OF = {TYPE_F32: 0, TYPE_F16: 1, TYPE_Q4_0: 2, TYPE_Q4_1: 3, TYPE_Q8_0: 7, TYPE_Q5_0: 8, TYPE_Q5_1: 9,
             # synthetic files whose 2-D tensors are ALL of one K type carry the nearest llama.cpp code (real Q*_K_S / _M files
@@ -179,6 +179,11 @@ PROTOTYPES = {
     "ggml_quantize_q5_0": (C.c_size_t, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "ggml_quantize_q5_1": (C.c_size_t, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "ggml_quantize_q8_0": (C.c_size_t, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "ggml_quantize_q2_K": (C.c_size_t, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "ggml_quantize_q3_K": (C.c_size_t, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "ggml_quantize_q4_K": (C.c_size_t, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "ggml_quantize_q5_K": (C.c_size_t, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "ggml_quantize_q6_K": (C.c_size_t, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "ggml_quantize_chunk": (C.c_size_t, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "ggml_internal_get_type_traits": (ggml_type_traits_t, [C.c_int]),
     "ggml_cpu_has_blas": (C.c_int, []),

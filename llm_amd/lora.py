@@ -67,6 +67,9 @@ def _as_adapter(a):
 
 
 def _wtype_of(nbytes, ne0, ne1):
+    """The weight type of raw bytes whose type was not given, from their size: the first of Q4_0, Q4_1, Q5_0, Q5_1, Q8_0,
+    F16, F32 that fits.  K types are never guessed: Q4_K stores 4.5 bits per weight as Q4_0 does and Q5_K 5.5 as Q5_0
+    does, so sizes cannot tell them apart — name a K type (or a {name: type} dict) in patch_weights' `wtype`."""
     for t in (G.TYPE_Q4_0, G.TYPE_Q4_1, G.TYPE_Q5_0, G.TYPE_Q5_1, G.TYPE_Q8_0, G.TYPE_F16, G.TYPE_F32):
         if G.row_bytes(t, ne0) * ne1 == nbytes:
             return t
@@ -96,8 +99,11 @@ def patch_one(W, wtype, ne0, ne1, A, B, s):
 def patch_weights(w, shapes, adapters, wtype=None):
     """A copy of the weight dict `w` with every adapter applied in the order given (loader.rs:660-667).  shapes: name ->
     (ne0, ne1 or None); adapters: paths of ggla files or dicts {r, alpha, tensors}.  A target without its .loraA /
-    .loraB raises KeyError (LoadError::UnknownTensor)."""
+    .loraB raises KeyError (LoadError::UnknownTensor).  wtype: the type of every 2-D weight (Q4_0 .. Q8_0, Q2_K .. Q6_K,
+    F16), or a dict {name: type} for models that mix types as the *_K_S / *_K_M files do (names it lacks, and
+    wtype=None, fall back to the size: _wtype_of, which never answers a K type)."""
     ads = [_as_adapter(a) for a in adapters]
+    type_of = wtype.get if isinstance(wtype, dict) else (lambda name: wtype)
     out = dict(w)
     for name, (ne0, ne1) in shapes.items():
         for ad in ads:
@@ -106,7 +112,8 @@ def patch_weights(w, shapes, adapters, wtype=None):
             for part in (".loraA", ".loraB"):
                 if name + part not in ad["tensors"]:
                     raise KeyError(f"LoadError::UnknownTensor: {name + part}")
-            t = wtype if wtype is not None else _wtype_of(np.asarray(out[name]).nbytes, ne0, ne1 or 1)
+            t = type_of(name)
+            t = t if t is not None else _wtype_of(np.asarray(out[name]).nbytes, ne0, ne1 or 1)
             out[name], _ = patch_one(out[name], t, ne0, ne1 or 1, ad["tensors"][name + ".loraA"],
                                      ad["tensors"][name + ".loraB"], ad["scaling"])
     return out
