@@ -586,6 +586,13 @@ GGML_API void ggml_hip_graph_compute_end(void);
  * invalidate it (ggml_init / ggml_free / ggml_set_scratch on any thread, an option change, freed weights).  The token id itself
  * is read at begin(), as always. */
 GGML_API int ggml_hip_graph_prepare(struct ggml_cgraph *cgraph);
+/* A caller that is greedy by construction says so before it computes a token's graph: "the evaluation after the one I compute next
+ * will be of the first maximum of its logits".  It holds for that one graph of the calling thread's device slot.  A single-token
+ * whole-model plan run then ends in k_token_tail (argmax, next parameters and the results' way to pinned host memory in one
+ * kernel) and the next token's graph is launched right behind it; if the caller's next evaluation is that token, its results are
+ * already on their way (stats "spec_hits", "tail_tokens").  What is computed never changes: any other next call simply runs
+ * behind the ahead run.  Option speculate_next = 1 makes the same promise for every evaluation of an unchanged caller. */
+GGML_API void ggml_hip_expect_greedy_next(void);
 /* Greedy sampling on the device (the step after the path): decodes n more tokens — each the first
  * argmax of the previous logits, what `infer_next_token` with a greedy sampler yields (inference_session.rs:381-424,
  * samplers.rs:289-306) — without the per-token logits read-back and host sync.  `last` = the cgraph of the caller's
@@ -657,6 +664,13 @@ GGML_API int ggml_hip_debug_prompt_attention_plan(const float *q_raw, const floa
  * out_ref[i] = f16(expf(x_i)) for the 65536 f16 bit patterns i (65536 f16 bit patterns each).  The softmax only ever passes
  * x <= 0 or NaN (crates/models/llama/src/lib.rs:272-280: soft_max over masked, scaled scores).  Returns 0. */
 GGML_API int ggml_hip_debug_exp_le0(uint16_t *out_fast, uint16_t *out_ref);
+/* Test hook: k_token_tail (the last kernel of a greedy token's graph) alone, beside k_argmax_next on the same logits.  logits[V]
+ * and emb[E] (nullable) go to the device, each `misalign` (0..3) floats off a 16-byte boundary; both kernels start from the
+ * parameters {n_past, token 0}.  Out: the id each kernel sampled, the logits and the row as they arrived in the pinned result
+ * slot, prm_out[0..2] = n_past, token, tokens[0] as k_token_tail left them for the next replay.  0, or -1 for arguments it
+ * cannot take. */
+GGML_API int ggml_hip_debug_token_tail(const float *logits, int V, const float *emb, int E, int n_past, int misalign,
+                                       int32_t *id_tail, int32_t *id_argmax, float *slot_logits, float *slot_emb, int32_t *prm_out);
 /* Test hook: w (quantized 2-D weight with a device copy) times N = 2..8 host rows x [N][K] through k_mmq_cols as the
  * multi-token plan launches it; out [N][M].  0, or -1 when that plan would not run this shape on k_mmq_cols. */
 GGML_API int ggml_hip_debug_mul_mat_cols(const struct ggml_tensor *w, const float *x, float *out, int N);

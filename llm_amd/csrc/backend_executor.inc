@@ -155,6 +155,10 @@ void execute_graph(ggml_cgraph *gr) {
     g_xi8.valid = false;
     g_xk.valid = false;
     if (try_decode_plan(gr)) return;  // single-token LLaMA decode: fused launches + hipGraph replay
+    // node by node: no hit check was reached — a token that ran ahead is taken back now (this graph may write the cache rows it
+    // wrote), and a last evaluated token that sits in a result set 1 goes into its graph's own nodes
+    spec_cancel();
+    res_settle();
     g.stat_generic_graphs++;
     upload_inputs(gr);
 

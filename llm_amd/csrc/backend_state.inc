@@ -109,25 +109,32 @@ struct Backend {
     ggml_cgraph *chain_graph = nullptr;    // ... and the cgraph that run executed
     bool pending_wait = false;  // a decode plan was launched by graph_compute_begin and not yet waited for
     bool pending_light = false;  // ... and it was a multi-token plan run: no in-launch waits (no error word to look at); if it also queued no read-back, the next begin() need not wait for it
-    // Speculative next token (opt_speculate_next, plan_run.inc): behind a single-token plan run
-    // the device samples the greedy token itself (k_argmax_next) and runs the NEXT token's plan at once; if the caller's next
-    // ggml_graph_compute asks for exactly that (same plan, position + 1, the same token) its results are already on their
-    // way — the caller's sampling, graph build and this library's enqueue overlap the device instead of idling it.  Anything
-    // else simply runs behind the speculation (which wrote only plan-private buffers and the K/V row of a position the
-    // session has not reached).
-    int opt_speculate_next = 0;
+    // One token ahead of a greedy caller (plan_run.inc): a single-token plan run whose caller is known to take the first maximum next —
+    // ggml_hip_expect_greedy_next said so for this evaluation, or option speculate_next says so for every one — runs as a graph that
+    // ends in k_token_tail: the device samples the greedy token itself, writes the next replay's parameters and stores the token's
+    // results into a pinned slot; the NEXT token's graph is launched right behind it.  If the caller's next ggml_graph_compute asks
+    // for exactly that (same plan, position + 1, the same token) its results are already on their way: a hit enqueues one graph
+    // launch and one event record, and nothing but kernels sits between two token graphs.  Anything else simply runs behind the
+    // ahead run (which wrote only plan-private buffers and the K/V row of a position the session has not reached).
+    int opt_speculate_next = 0, opt_token_tail = 1;
+    bool greedy_hint = false;  // ggml_hip_expect_greedy_next: consumed by the next graph of this slot
     struct Spec {
         bool pending = false;
         void *plan = nullptr;
         int n_past = 0, av = 0;
-        int32_t *tok_pin = nullptr;     // pinned: the token the device sampled
-        int *tok_dev = nullptr;
-        hipEvent_t tok_ev = nullptr;    // ... is there once this event is done
+        int parity = 0;                 // the result set / slot the ahead run fills
+        int32_t fed_id = 0;             // the token the device fed it: the id that came with the previous token's slot ...
+        bool fed_id_valid = false;      // ... once that slot has been delivered (token_finish): the hit check needs no synchronisation
         int cooldown = 0;               // evaluations to sit out after a miss
     } spec;
-    hipEvent_t results_ev = nullptr;    // recorded behind a token's result copies: what the host waits for (not the stream's end)
-    bool results_ev_armed = false;
-    size_t results_ev_copies = 0;      // read-backs that were queued when it was recorded: a later one is not covered by it
+    struct TailWait {                   // the token whose results the host takes from a slot: set by begin, consumed by token_finish
+        void *plan = nullptr;
+        int q = 0;
+        void *logits_dst = nullptr, *emb_dst = nullptr;
+        bool staged = false;            // its parameters went up through the small staging: free again once its event is done
+    } tail;
+    void *res_plan = nullptr;           // the most recently evaluated plan while its last token sits in result set 1 (DecodePlan::cur_set); null: set 0 everywhere (res_settle)
+    uint64_t stat_tail_tokens = 0, stat_result_copies = 0, stat_tail_hits = 0, stat_tail_misses = 0;
     uint64_t stat_spec_hits = 0, stat_spec_misses = 0;
     // in-launch hand-offs that gave up (kernels/common.h GRAN_SPIN_MAX): the plan's error word travels back with every token's
     // results (plan_run.inc token_finish)
@@ -187,8 +194,11 @@ static const OptRow g_options[] = {
     {"chain_k", &Backend::opt_chain_k, OPT_ENV, FX_NONE, 0, 64},  // greedy chain: tokens per hipGraph launch (0 / 1 = one token per launch)
     // ggml_hip_graph_prepare remembers its match (0: it answers 0 and every begin() matches its graph itself)
     {"prepare", &Backend::opt_prepare, OPT_ENV},
-    // 1 = run the greedy next token speculatively behind every single-token plan run (Backend::spec, plan_run.inc)
+    // 1 = run the greedy next token ahead behind every single-token plan run, whoever the caller is (Backend::spec, plan_run.inc)
     {"speculate_next", &Backend::opt_speculate_next, OPT_ENV, FX_SPECULATE_NEXT},
+    // 0 = no token runs ahead of its caller, whatever ggml_hip_expect_greedy_next or speculate_next say: every single-token plan run
+    // takes the plain graph and the staged result copies
+    {"token_tail", &Backend::opt_token_tail, OPT_ENV, FX_SPECULATE_NEXT},
     // ---- the fused decode launch
     // decode: wq|wk|wv and the attention as ONE launch (kernels/decode_fused.h) where the mat-vec deals as evenly over the remaining
     // workgroups; 2 = wherever legal (tests); 0 = the two-launch pair.  An explicit choice outlives a pending re-arm.
@@ -282,7 +292,11 @@ static const StatRow g_counters[] = {
     {"cols_warm_launches", &Backend::stat_cols_warm_launches},    // chunk-plan norm launches that carried warming workgroups (ColsWarm), counted when enqueued or captured
     {"fused_rearms", &Backend::stat_fused_rearms},                // times the fused forms came back after a clean stretch behind a give-up
     {"spec_hits", &Backend::stat_spec_hits},                      // evaluations that found their results already running (option speculate_next)
-    {"spec_misses", &Backend::stat_spec_misses},                  // ... speculative runs nobody asked for
+    {"spec_misses", &Backend::stat_spec_misses},                  // ... ahead runs nobody asked for
+    {"tail_tokens", &Backend::stat_tail_tokens},                  // evaluations whose results came through k_token_tail's slot
+    {"tail_hits", &Backend::stat_tail_hits},                      // ahead runs the caller's next evaluation asked for, however they were armed ...
+    {"tail_misses", &Backend::stat_tail_misses},                  // ... and those it did not (a greedy-by-hint caller that keeps missing shows here)
+    {"result_copies", &Backend::stat_result_copies},              // stream copies enqueued for parameters or results of single-token plan runs
     {"generic_graphs", &Backend::stat_generic_graphs},            // graphs run node by node
     {"alibi_fused", &Backend::stat_alibi_fused},                  // scale -> alibi -> diag_mask_inf -> soft_max chains (BLOOM, MPT) run as one launch (k_alibi_soft_max)
     {"flash_attn_nodes", &Backend::stat_flash_attn_nodes},        // GGML_OP_FLASH_ATTN nodes computed (one launch each: kernels/flash_attn.h)
@@ -932,13 +946,7 @@ void d2h_queue(void *host_dst, const char *src, size_t n) {
     stg.pending.push_back({host_dst, s, n});
 }
 void d2h_finish() {
-    if (g.results_ev_armed && stg.pending.size() != g.results_ev_copies) g.results_ev_armed = false;  // a read-back queued behind the event
-    if (g.results_ev_armed) {  // work was enqueued BEHIND the result copies (a speculative next token): wait for the copies only
-        g.results_ev_armed = false;
-        HIP_CHECK(hipEventSynchronize(g.results_ev));
-    } else {
-        HIP_CHECK(hipStreamSynchronize(g.stream));
-    }
+    HIP_CHECK(hipStreamSynchronize(g.stream));
     for (auto &p : stg.pending) memcpy(p.host_dst, p.stage, p.n);
     stg.pending.clear();
     stg.small_off = 0;

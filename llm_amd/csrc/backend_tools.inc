@@ -558,6 +558,51 @@ int ggml_hip_debug_exp_le0(uint16_t *out_fast, uint16_t *out_ref) {
     return 0;
 }
 
+// ---- test hook: k_token_tail alone, beside k_argmax_next on the same logits (tests/test_token_tail_gpu.py) ----
+// logits[V] and emb[E] (nullable) go to the device (both `misalign` floats off a 16-byte boundary: the kernel's 4-byte paths), both
+// kernels start from parameters {n_past, token 0}.  Out: the two ids, the slot's logits / row (the bytes the host would be handed),
+// prm_out[0..2] = n_past, token, tokens[0] as k_token_tail left them.  0, or -1 for arguments it cannot take.
+int ggml_hip_debug_token_tail(const float *logits, int V, const float *emb, int E, int n_past, int misalign, int32_t *id_tail,
+                              int32_t *id_argmax, float *slot_logits, float *slot_emb, int32_t *prm_out) {
+    if (!logits || V < 1 || (emb && E < 1) || misalign < 0 || misalign > 3 || !id_tail || !id_argmax || !slot_logits || !prm_out) return -1;
+    SlotLock lk;
+    ensure_init();
+    finish_pending();
+    const size_t lb = ((size_t)(V + 4) * 4 + 255) & ~(size_t)255, eb = ((size_t)(std::max(E, 1) + 4) * 4 + 255) & ~(size_t)255;
+    const size_t emb_off = ((size_t)V * 4 + 255) & ~(size_t)255, id_off = emb_off + eb;
+    char *d = nullptr, *slot = nullptr;
+    dev_malloc((void **)&d, lb + eb + 1024, "debug token tail");
+    HIP_CHECK(hipHostMalloc((void **)&slot, id_off + 256, hipHostMallocDefault));
+    memset(slot, 0xff, id_off + 256);
+    float *dl = (float *)d + misalign, *de = (float *)(d + lb) + misalign;
+    DecParams *pa = (DecParams *)(d + lb + eb), *pb = pa + 1;
+    int *ida = (int *)(pb + 1);
+    DecParams hp;
+    memset(&hp, 0, sizeof(hp));
+    hp.n_past = n_past;
+    HIP_CHECK(hipStreamSynchronize(g.stream));
+    HIP_CHECK(hipMemcpy(dl, logits, (size_t)V * 4, hipMemcpyHostToDevice));
+    if (emb) HIP_CHECK(hipMemcpy(de, emb, (size_t)E * 4, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(pa, &hp, sizeof(hp), hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(pb, &hp, sizeof(hp), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_argmax_next, dim3(1), dim3(1024), 0, g.stream, (const float *)dl, V, pa, ida);
+    hipLaunchKernelGGL(k_token_tail, dim3(TOKEN_TAIL_WGS), dim3(1024), 0, g.stream, (const float *)dl, V, emb ? (const float *)de : (const float *)nullptr,
+                       E, pb, slot, (int)emb_off, (int)id_off);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipStreamSynchronize(g.stream));
+    HIP_CHECK(hipMemcpy(id_argmax, ida, 4, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(&hp, pb, sizeof(hp), hipMemcpyDeviceToHost));
+    prm_out[0] = hp.n_past;
+    prm_out[1] = hp.token;
+    prm_out[2] = hp.tokens[0];
+    *id_tail = *(const int32_t *)(slot + id_off);
+    memcpy(slot_logits, slot, (size_t)V * 4);
+    if (emb && slot_emb) memcpy(slot_emb, slot + emb_off, (size_t)E * 4);
+    HIP_CHECK(hipHostFree(slot));
+    HIP_CHECK(hipFree(d));
+    return 0;
+}
+
 int ggml_hip_decode_greedy_chain(struct ggml_cgraph *last, int n, int32_t *out_tokens, float *last_logits) {
     SlotLock lk;
     return decode_greedy_chain(last, n, out_tokens, last_logits);

@@ -206,7 +206,7 @@ extern "C" int ggml_hip_graph_compute_begin(struct ggml_cgraph *cgraph) {
     SlotLock lk;
     const uint64_t t0 = now_ns();
     ensure_init();
-    if (g.pending_wait && g.pending_light && stg.pending.empty() && !g.results_ev_armed) {
+    if (g.pending_wait && g.pending_light && stg.pending.empty()) {
         // a prompt chunk / batch that was only enqueued (feed_prompt's chunks but the last): nothing of it is host-visible, and
         // what this call enqueues runs behind it on the same stream — no wait
         g.pending_wait = false;
@@ -232,6 +232,13 @@ extern "C" int ggml_hip_graph_prepare(struct ggml_cgraph *cgraph) {
     SlotLock lk;
     ensure_init();
     return prepare_decode_plan(cgraph) ? 1 : 0;  // host work only: nothing is enqueued, nothing is waited for
+}
+// The caller's promise for its NEXT graph on this slot: the evaluation after that one will be of the first maximum of that one's
+// logits (a greedy sampler).  A single-token whole-model plan run then keeps the device one token ahead (Backend::spec).  One
+// graph's worth: a caller that samples any other way simply never calls this.
+extern "C" void ggml_hip_expect_greedy_next(void) {
+    SlotLock lk;
+    g.greedy_hint = true;
 }
 extern "C" void ggml_hip_graph_compute_end(void) {
     SlotLock lk;
@@ -506,7 +513,7 @@ int ggml_hip_topk(const struct ggml_tensor *t, int64_t row, int k, const int32_t
         if (e ? e->soa : find_arena((uintptr_t)t->data) == nullptr) return -1;
     }
     finish_pending();
-    const float *x = (const float *)(dev_ptr(t) + row * (int64_t)t->nb[1]);
+    const float *x = (const float *)(result_dev_ptr(t) + row * (int64_t)t->nb[1]);
     char *buf = ws_alloc((size_t)(k + n_extra) * 8 + (size_t)n_extra * 4 + 64);
     float *dv = (float *)buf;
     int *di = (int *)(buf + (size_t)(k + n_extra) * 4);
@@ -540,7 +547,7 @@ int ggml_hip_row_probs(const struct ggml_tensor *t, int64_t row_begin, int64_t n
         if (e ? e->soa : find_arena((uintptr_t)t->data) == nullptr) return -1;
     }
     finish_pending();
-    const float *x = (const float *)(dev_ptr(t) + row_begin * (int64_t)t->nb[1]);
+    const float *x = (const float *)(result_dev_ptr(t) + row_begin * (int64_t)t->nb[1]);
     const int V = (int)t->ne[0];
     char *buf = ws_alloc((size_t)n_rows * 8 + 64);
     float *dp = (float *)buf;
@@ -745,12 +752,15 @@ void ggml_hip_synchronize(void) {
 void ggml_hip_tensor_get(const struct ggml_tensor *tensor, void *host_dst, size_t offset, size_t nbytes) {
     SlotLock lk;
     ensure_init();
-    d2h_queue(host_dst, dev_ptr(tensor) + offset, nbytes);
+    finish_pending();
+    spec_guard_read(dev_ptr(tensor) + offset, nbytes);
+    d2h_queue(host_dst, result_dev_ptr(tensor) + offset, nbytes);  // (a result node: the set the last evaluated token sits in)
     d2h_finish();
 }
 void ggml_hip_tensor_set(struct ggml_tensor *tensor, const void *host_src, size_t offset, size_t nbytes) {
     SlotLock lk;
     ensure_init();
+    spec_guard_read(dev_ptr(tensor) + offset, nbytes);  // (a write into the caches: what ran ahead on the old contents is void)
     h2d_bulk(dev_ptr(tensor) + offset, host_src, nbytes);
     HIP_CHECK(hipStreamSynchronize(g.stream));
 }
@@ -759,6 +769,8 @@ void ggml_hip_tensor_set(struct ggml_tensor *tensor, const void *host_src, size_
 void ggml_hip_memcpy(void *dst, const void *src, size_t nbytes, int kind) {
     SlotLock lk;
     ensure_init();
+    if (kind != 1) spec_guard_read((const char *)dst, nbytes);  // each device operand once
+    if (kind != 0) spec_guard_read((const char *)src, nbytes);
     if (kind == 0) {
         h2d_bulk((char *)dst, src, nbytes);
         HIP_CHECK(hipStreamSynchronize(g.stream));

@@ -79,6 +79,9 @@ struct OutputRequest {
     // extension: a chunk of feed_prompt that is not its last one — nobody can observe its last-token logits (the next chunk
     // overwrites last_logits before feed_prompt returns), so they are not fetched and the evaluation need not be waited for
     bool intermediate_chunk = false;
+    // extension: the caller is greedy by construction — its next evaluation will be of the first maximum of this one's logits
+    // (llm_infer_next_token_greedy): handed to the backend as ggml_hip_expect_greedy_next before the graph is computed
+    bool greedy_next = false;
 };
 
 struct GraphOutputs {  // inference_session.rs:31-37
@@ -599,6 +602,9 @@ std::atomic<int> g_split_sessions{0};  // live sessions of layer-split models (s
 // Model::evaluate for both kinds of model
 // Every entry point leaves the caller's main device as it found it: an unsplit model runs on the slot it was loaded on
 // (llm_model::device), a split one walks its stages' slots.
+// (weak: this file also links against backends that have no such entry — the hint is then simply not given)
+extern "C" void ggml_hip_expect_greedy_next(void) __attribute__((weak));
+
 struct HomeDevice {
     int pinned = ggml_hip_thread_pinned_device();  // -1: the thread follows the process default, and must again afterwards
     int home = ggml_hip_get_main_device();
@@ -622,6 +628,7 @@ void model_evaluate(llm_model *m, llm_session *s, const std::vector<llm::TokenId
     HomeDevice hd;
     if (m->stages.empty()) {
         hd.go(s->device);  // the session's slot: the model's, or a sibling slot of the same GPU (llm_start_session_on)
+        if (req.greedy_next && toks.size() == 1 && ggml_hip_expect_greedy_next) ggml_hip_expect_greedy_next();
         if (!m->llama->is_first() || !m->llama->is_last())  // one stage of a per-process split (llm_amd/pipeline.py)
             s->s->ensure_stage_rows(m->llama->hyperparameters.n_embd, toks.size());
         m->llama->evaluate(*s->s, toks, req);
@@ -1341,6 +1348,7 @@ int32_t llm_infer_next_token_greedy(llm_model *m, llm_session *s) {
     s->s->tokens.push_back(next);
     llm::OutputRequest req;
     const double t1 = llm::InferenceSession::now_ns();
+    req.greedy_next = true;  // the call after this one evaluates the first maximum of this one's logits: the backend may run it ahead
     model_evaluate(m, s, std::vector<llm::TokenId>{next}, req);
     llm::InferenceSession::host_ns_add(5, t1 - t0);                                // argmax
     llm::InferenceSession::host_ns_add(6, llm::InferenceSession::now_ns() - t1);  // evaluate, all of it

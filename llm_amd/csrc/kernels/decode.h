@@ -35,12 +35,8 @@ struct BatchCols {
     __half *mem_v[BATCH_COLS_MAX];  // V element (layer il, chan c, pos p) at (il * Egqa + c) * C + p
 };
 
-// Greedy sampling on the device (SURVEY section 8f N3): token = first index of the maximum logit — what a host loop
-// `if (l[i] > l[best]) best = i` returns — written straight into the decode parameters of the NEXT replay of the plan
-// (token id, position + 1) and into out[0], so that a chain of greedy tokens needs neither the 128 KB logits
-// read-back nor a host round trip per token.  One 1024-thread workgroup.
-__global__ void __launch_bounds__(1024) k_argmax_next(const float *__restrict__ logits, int V, DecParams *prm,
-                                                      int *__restrict__ out) {
+// The first maximum of logits[0 .. V) over one 1024-thread workgroup; the result is valid in thread 0.
+__device__ __forceinline__ int argmax_first_block(const float *__restrict__ logits, int V) {
     __shared__ float s_v[16];
     __shared__ int s_i[16];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -85,10 +81,77 @@ __global__ void __launch_bounds__(1024) k_argmax_next(const float *__restrict__ 
                 bv = s_v[w];
                 bi = s_i[w];
             }
+    }
+    return bi;
+}
+// Greedy sampling on the device (SURVEY section 8f N3): token = first index of the maximum logit — what a host loop
+// `if (l[i] > l[best]) best = i` returns — written straight into the decode parameters of the NEXT replay of the plan
+// (token id, position + 1) and into out[0], so that a chain of greedy tokens needs neither the 128 KB logits
+// read-back nor a host round trip per token.  One 1024-thread workgroup.
+__global__ void __launch_bounds__(1024) k_argmax_next(const float *__restrict__ logits, int V, DecParams *prm,
+                                                      int *__restrict__ out) {
+    const int bi = argmax_first_block(logits, V);
+    if (threadIdx.x == 0) {
         prm->token = bi;
         prm->tokens[0] = bi;
         prm->n_past = prm->n_past + 1;
         out[0] = bi;
+    }
+}
+// The K row and the V column of position prm->n_past, every layer, saved before a greedy token's graph writes them (its first kernel
+// node): a token the device ran AHEAD of its caller and nobody asked for is taken back by k_kv_row_restore, so that the caches hold
+// exactly what a session that never ran ahead holds.  save: [L][Egqa] halves of K, then the same of V.
+__global__ void __launch_bounds__(256) k_kv_row_save(const DecParams *__restrict__ prm, const __half *__restrict__ mem_k,
+                                                     const __half *__restrict__ mem_v, __half *__restrict__ save, int L, int C, int Egqa) {
+    const int pos = prm->n_past;
+    if (pos < 0 || pos >= C) return;
+    const long n = (long)L * Egqa;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+        const long il = i / Egqa, c = i % Egqa;
+        save[i] = mem_k[(il * C + pos) * Egqa + c];
+        save[n + i] = mem_v[(il * Egqa + c) * C + pos];
+    }
+}
+__global__ void __launch_bounds__(256) k_kv_row_restore(int pos, __half *__restrict__ mem_k, __half *__restrict__ mem_v,
+                                                        const __half *__restrict__ save, int L, int C, int Egqa) {
+    if (pos < 0 || pos >= C) return;
+    const long n = (long)L * Egqa;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+        const long il = i / Egqa, c = i % Egqa;
+        mem_k[(il * C + pos) * Egqa + c] = save[i];
+        mem_v[(il * Egqa + c) * C + pos] = save[n + i];
+    }
+}
+// The last kernel of a greedy token's graph (plan_run.inc): k_argmax_next and the token's way to the host in one launch.  Workgroup 0
+// takes the first maximum of the V logits (the same scan: argmax_first_block) and writes the next replay's parameters; all workgroups
+// together store the logits, the E-wide embedding row (emb, nullable) and the id into `slot`, pinned host memory, by 16-byte stores —
+// the host reads the slot once the event behind the graph is done, so no copy command sits between two token graphs.
+// Slot layout: the logits at 0, the row at emb_off, the id at id_off (both 16-byte multiples).
+constexpr int TOKEN_TAIL_WGS = 8;
+__global__ void __launch_bounds__(1024) k_token_tail(const float *__restrict__ logits, int V, const float *__restrict__ emb, int E,
+                                                     DecParams *prm, char *__restrict__ slot, int emb_off, int id_off) {
+    const int gtid = blockIdx.x * 1024 + threadIdx.x, total = gridDim.x * 1024;
+    float *sl = (float *)slot, *se = (float *)(slot + emb_off);
+    if (((uintptr_t)logits & 15) == 0) {
+        const int V4 = V >> 2;
+        for (int i = gtid; i < V4; i += total) ((float4 *)sl)[i] = ((const float4 *)logits)[i];
+        if (gtid < (V & 3)) sl[(V4 << 2) + gtid] = logits[(V4 << 2) + gtid];  // the last partial group
+    } else {
+        for (int i = gtid; i < V; i += total) sl[i] = logits[i];
+    }
+    if (emb) {
+        if (((uintptr_t)emb & 15) == 0 && (E & 3) == 0)
+            for (int i = gtid; i < (E >> 2); i += total) ((float4 *)se)[i] = ((const float4 *)emb)[i];
+        else
+            for (int i = gtid; i < E; i += total) se[i] = emb[i];
+    }
+    if (blockIdx.x != 0) return;
+    const int bi = argmax_first_block(logits, V);
+    if (threadIdx.x == 0) {
+        prm->token = bi;
+        prm->tokens[0] = bi;
+        prm->n_past = prm->n_past + 1;
+        *(int *)(slot + id_off) = bi;
     }
 }
 

@@ -149,14 +149,12 @@ static void for_each_type_run(const KWeight *const *ws, int n, F &&f) {
         i = j;
     }
 }
-// where a plan's final norm and lm_head write: the caller-visible mirrors, or the alternates while the speculative graph is captured (see DecodePlan::logits_alt)
+// where a plan's final norm and lm_head write: result set 0, or set 1 while a greedy token's graph of parity 1 is captured (see DecodePlan::out_set)
 struct ResultDst {
     float *emb;
     char *logits;
 };
-static ResultDst plan_result_dst(const DecodePlan *p) {
-    return ResultDst{p->spec_out && p->emb_out ? p->emb_alt : p->emb_out, p->spec_out ? p->logits_alt : p->logits_out};
-}
+static ResultDst plan_result_dst(const DecodePlan *p) { return ResultDst{p->res_emb(p->out_set), p->res_logits(p->out_set)}; }
 // ---- what the K plan and the F16 plan share: everything around their mat-vecs ----
 // The opening: the residual rows from the hand-off buffer, or the embedding rows of the N token ids (`embed`: the plan's own get_rows
 // launch, embed_bytes per element its books); then one (cos, sin) table per column, 128 floats apart (batch: each at its own session's position)

@@ -9,15 +9,19 @@ static void capture_into(hipGraph_t *graph, hipGraphExec_t *exec, F &&launch) {
     HIP_CHECK(hipGraphInstantiate(exec, *graph, nullptr, nullptr, 0));
 }
 // results the host reads, queued behind the evaluation's kernels: the logits (CPU-backend node, model/common.rs:6-38) ...
+static bool emb_row_mirrored(const DecodePlan *p) {
+    const LlamaMatch &m = p->m;
+    return m.embedding && m.embedding->data && p->emb_out && (size_t)m.N * (size_t)m.E * 4 <= ((size_t)128 << 10);
+}
 static void queue_results(const DecodePlan *p) {
     const LlamaMatch &m = p->m;
+    if (m.N == 1 && !m.prompt) g.stat_result_copies += (m.logits && m.logits->backend == GGML_BACKEND_CPU ? 1 : 0) + (emb_row_mirrored(p) ? 1 : 0);
     if (m.logits && m.logits->backend == GGML_BACKEND_CPU) d2h_queue(m.logits->data, p->logits_out, (size_t)m.V * m.N * 4);
     // the embedding_result node is offloaded in the reference's graph, yet common::extract_embeddings reads its HOST pointer
     // (crates/llm-base/src/model/common.rs:41-59): a decode token's / prompt chunk's rows (16 KB per token) are mirrored to the node's
     // host data with the logits, so that an unchanged caller reads what the device computed.  (Bigger evaluations keep the node on
     // the device only: 8 MB per 512-token batch nobody may want — read it with ggml_hip_tensor_get, INTEGRATION.md.)
-    if (m.embedding && m.embedding->data && p->emb_out && (size_t)m.N * (size_t)m.E * 4 <= ((size_t)128 << 10))
-        d2h_queue(m.embedding->data, (const char *)p->emb_out, (size_t)m.N * (size_t)m.E * 4);
+    if (emb_row_mirrored(p)) d2h_queue(m.embedding->data, (const char *)p->emb_out, (size_t)m.N * (size_t)m.E * 4);
 }
 // ---- the end of a single-token plan run: wait, deliver the results, and look at the plan's error word ----
 // k_qkv_attn / k_attn_split_one contain workgroups that wait for rows or partial results of OTHER workgroups of the same launch.
@@ -32,14 +36,37 @@ static void token_results_queue(DecodePlan *p) {
     g.ferr_plan = p;  // the word itself needs no copy: the kernels write it into pinned host memory, visible once the token's
                       // result copies (queued behind its kernels) are done
 }
+// a greedy token's results: out of the slot its graph's k_token_tail filled, into the caller's memory (as d2h_finish moves its staging);
+// the id that came with them is the token the device fed the run it started behind that graph
+static void tail_deliver(const Backend::TailWait &tw) {
+    DecodePlan *tp = (DecodePlan *)tw.plan;
+    const char *sl = tp->slot[tw.q];
+    if (tw.logits_dst) memcpy(tw.logits_dst, sl, (size_t)tp->m.V * 4);
+    if (tw.emb_dst) memcpy(tw.emb_dst, sl + tp->slot_emb_off, (size_t)tp->m.E * 4);
+    if (g.spec.pending && g.spec.plan == tw.plan && g.spec.parity == (tw.q ^ 1)) {
+        g.spec.fed_id = *(const int32_t *)(sl + tp->slot_id_off);
+        g.spec.fed_id_valid = true;
+    }
+}
 static void token_finish(bool can_rerun = true) {
-    d2h_finish();
+    const Backend::TailWait tw = g.tail;
+    g.tail = Backend::TailWait{};
+    if (tw.plan) {  // the token's own event, recorded directly behind its graph: whatever runs behind that is not waited for
+        HIP_CHECK(hipEventSynchronize(((DecodePlan *)tw.plan)->slot_ev[tw.q]));
+        if (!stg.pending.empty()) d2h_finish();
+        else if (tw.staged) stg.small_off = 0;
+    } else {
+        d2h_finish();
+    }
     DecodePlan *p = (DecodePlan *)g.ferr_plan;
     g.ferr_plan = nullptr;
-    if (!p || !g.ferr_pin || !*(volatile unsigned *)g.ferr_pin) return;
+    if (!p || !g.ferr_pin || !*(volatile unsigned *)g.ferr_pin) {
+        if (tw.plan) tail_deliver(tw);
+        return;
+    }
+    spec_cancel();  // (first: a run ahead of this token, still in flight on the same launches, may raise the word again)
     *(volatile unsigned *)g.ferr_pin = 0;
     g.stat_fused_timeouts++;
-    spec_cancel();
     static const char *what =
         "an attention workgroup of k_qkv_attn / k_attn_split_one gave up waiting for rows of its own launch (these launches "
         "need all their workgroups resident at once: is another process, or a CU mask, holding compute units of this GPU?)";
@@ -71,9 +98,12 @@ static void token_finish(bool can_rerun = true) {
         hp.token = m.embd ? ((const int32_t *)m.embd->data)[0] : 0;
         hp.tokens[0] = hp.token;
         h2d_small((char *)p->prm, &hp, sizeof(hp));
+        g.stat_result_copies++;
+        p->prm_ahead = false;
     }
     plan_launch_decode(p, attn_variant(m, p, m.n_past + 1));
-    queue_results(p);  // the copies try_decode_plan queued for this token, again
+    g.res_plan = nullptr;  // (launched outside a graph: result set 0)
+    queue_results(p);  // the copies try_decode_plan queued for this token, again (a greedy token: instead of its slot)
     d2h_finish();
     if (*(volatile unsigned *)g.ferr_pin) die("%s — and again on the re-run", what);
 }
@@ -141,8 +171,20 @@ static DecodePlan *find_or_build_plan(const LlamaMatch &m, const std::vector<uin
     return p;
 }
 
+// the two result slots of a plan's greedy tokens and their events (DecodePlan::slot), made at the first such token
+static void tail_slots(DecodePlan *p) {
+    if (p->slot[0]) return;
+    p->slot_emb_off = ((size_t)p->m.V * 4 + 255) & ~(size_t)255;
+    p->slot_id_off = p->slot_emb_off + (((size_t)p->m.E * 4 + 255) & ~(size_t)255);
+    for (int q = 0; q < 2; q++) {
+        HIP_CHECK(hipHostMalloc((void **)&p->slot[q], p->slot_id_off + 256, hipHostMallocDefault));
+        HIP_CHECK(hipEventCreateWithFlags(&p->slot_ev[q], hipEventDisableTiming));
+    }
+}
 static bool try_decode_plan(ggml_cgraph *gr, bool defer_wait = false) {
     g.chain_plan = nullptr;  // any new graph ends the chainable state; a single-token plan run re-arms it below
+    const bool greedy_next = g.greedy_hint;  // ggml_hip_expect_greedy_next spoke of THIS graph, whatever it turns out to be
+    g.greedy_hint = false;
     if (!g.opt_plan) return false;
     if (g.fused_rearm_at && g.stat_plan_tokens >= g.fused_rearm_at) {  // a clean stretch behind a hand-off that gave up: the fused forms again
         g.fused_rearm_at = 0;
@@ -188,23 +230,28 @@ static bool try_decode_plan(ggml_cgraph *gr, bool defer_wait = false) {
         p = find_or_build_plan(m, plan_signature(m));
     }
     const uint64_t t1 = now_ns();
-    // ---- speculative next token: is this evaluation the one the device is already running? ----
+    // ---- one token ahead: is this evaluation the one the device is already running? ----
     bool spec_hit = false;
+    int hit_q = 0;
     if (g.spec.pending) {
         g.spec.pending = false;
         const bool same = g.spec.plan == (void *)p && m.N == 1 && !m.prompt && m.embd && m.n_past == g.spec.n_past &&
                           attn_variant(m, p, m.n_past + 1) == g.spec.av && g.opt_graph && !g.timing.on;
-        if (same) {
-            HIP_CHECK(hipEventSynchronize(g.spec.tok_ev));  // long done: recorded right behind the argmax kernel of the previous token
-            spec_hit = *g.spec.tok_pin == ((const int32_t *)m.embd->data)[0];
-        }
+        // the id the device fed that run came to the host with the previous token's slot (tail_deliver): no synchronisation here
+        spec_hit = same && g.spec.fed_id_valid && g.spec.fed_id == ((const int32_t *)m.embd->data)[0];
+        hit_q = g.spec.parity;
+        // (spec_hits / spec_misses are the books of option speculate_next, the guess about an unchanged caller; a caller that announced
+        // itself shows in tail_tokens and in result_copies standing still)
         if (spec_hit) {
-            g.stat_spec_hits++;
+            if (g.opt_speculate_next) g.stat_spec_hits++;
         } else {
-            g.stat_spec_misses++;
+            if (g.opt_speculate_next) g.stat_spec_misses++;
             g.spec.cooldown = 8;  // a sampler that does not take the first maximum: stop guessing for a while
+            spec_take_back();     // the cache rows it wrote go back to what they were, behind it and in front of this evaluation
         }
+        (spec_hit ? g.stat_tail_hits : g.stat_tail_misses)++;
     }
+    if (!spec_hit) res_settle();  // (behind the ahead run, in front of whatever this evaluation writes)
     DecParams hp;
     hp.n_past = m.n_past;
     hp.token = m.embd ? ((const int32_t *)m.embd->data)[0] : 0;
@@ -213,7 +260,11 @@ static bool try_decode_plan(ggml_cgraph *gr, bool defer_wait = false) {
         hp.tokens[i] = (m.embd && i < m.N && !m.prompt) ? ((const int32_t *)m.embd->data)[i] : 0;
         if (m.wte && (hp.tokens[i] < 0 || hp.tokens[i] >= m.wte->ne[1])) die("token id %d out of range", hp.tokens[i]);
     }
-    if (!spec_hit) h2d_small((char *)p->prm, &hp, sizeof(hp));  // (a hit: the device wrote exactly these itself)
+    if (!spec_hit) {  // (a hit: the device wrote exactly these itself)
+        h2d_small((char *)p->prm, &hp, sizeof(hp));
+        p->prm_ahead = false;
+        if (m.N == 1 && !m.prompt) g.stat_result_copies++;
+    }
     if (m.prompt) {  // prompt plan: all token ids, launched eagerly
         if (m.wte) {
             const int32_t *ids = (const int32_t *)m.embd->data;
@@ -257,8 +308,38 @@ static bool try_decode_plan(ggml_cgraph *gr, bool defer_wait = false) {
         else
             plan_launch_decode(p, av);
     };
+    // ---- a greedy token (the caller said so, or option speculate_next does): its graph ends in k_token_tail, and the next token's
+    // graph goes right behind it.  After a miss the guessing pauses; the last positions of the context have no next token. ----
+    if (g.spec.cooldown > 0) g.spec.cooldown--;
+    const bool tail = g.opt_token_tail && (g.opt_speculate_next || greedy_next) && g.spec.cooldown == 0 && use_graph && m.N == 1 && m.logits && m.wte &&
+                      m.output && m.embd && p->logits_alt && m.n_past + 2 < m.C;
+    const auto launch_tail = [&](int v, int q) {  // the plan's graph of variant v, parity q: result set q, slot q, and the slot's event directly behind it
+        VariantGraphs &vg = p->graphs[v];
+        if (!vg.tail_exec[q]) {
+            tail_slots(p);
+            p->out_set = q;
+            capture_into(&vg.tail_graph[q], &vg.tail_exec[q], [&] {
+                hipLaunchKernelGGL(k_kv_row_save, dim3(kv_row_grid(p)), dim3(256), 0, g.stream, (const DecParams *)p->prm, (const __half *)p->mem_k,
+                                   (const __half *)p->mem_v, p->kv_save[q], (int)m.L, (int)m.C, (int)m.Egqa);
+                plan_launch_decode(p, v);
+                hipLaunchKernelGGL(k_token_tail, dim3(TOKEN_TAIL_WGS), dim3(1024), 0, g.stream, (const float *)p->res_logits(q), (int)m.V,
+                                   (size_t)m.E * 4 <= ((size_t)128 << 10) ? (const float *)p->res_emb(q) : (const float *)nullptr, (int)m.E, p->prm, p->slot[q],
+                                   (int)p->slot_emb_off, (int)p->slot_id_off);
+            });
+            p->out_set = 0;
+        }
+        HIP_CHECK(hipGraphLaunch(vg.tail_exec[q], g.stream));
+        HIP_CHECK(hipEventRecord(p->slot_ev[q], g.stream));
+        p->prm_ahead = true;
+    };
+    int tail_q = -1;  // the slot this token's results come through, if any
     if (spec_hit) {
-        // already enqueued behind the previous token (same plan, position, token and attention variant): only the results are missing
+        tail_q = hit_q;  // already enqueued behind the previous token (same plan, position, token and attention variant): only the host's part is missing
+        p->replays++;
+    } else if (tail) {
+        tail_q = 0;
+        launch_tail(av, tail_q);
+        p->replays++;
     } else if (use_graph) {
         VariantGraphs &vg = p->graphs[av];
         if (!vg.exec) capture_into(&vg.graph, &vg.exec, launch);
@@ -267,42 +348,28 @@ static bool try_decode_plan(ggml_cgraph *gr, bool defer_wait = false) {
     } else {
         launch();
     }
-    if (spec_hit) {  // the speculative run's results sit in the plan's alternates: into the caller-visible mirrors first (stream order)
-        HIP_CHECK(hipMemcpyAsync(p->logits_out, p->logits_alt, (size_t)m.V * 4, hipMemcpyDeviceToDevice, g.stream));
-        if (p->emb_out) HIP_CHECK(hipMemcpyAsync(p->emb_out, p->emb_alt, (size_t)m.E * 4, hipMemcpyDeviceToDevice, g.stream));
+    if (tail_q >= 0) {  // nothing is queued: the slot holds the results once its event is done (token_finish)
+        g.stat_tail_tokens++;
+        g.tail.plan = p;
+        g.tail.q = tail_q;
+        g.tail.logits_dst = m.logits->backend == GGML_BACKEND_CPU ? m.logits->data : nullptr;
+        g.tail.emb_dst = emb_row_mirrored(p) ? m.embedding->data : nullptr;
+        g.tail.staged = !spec_hit;
+        p->cur_set = tail_q;  // what every device-side reader sees from now on (result_dev_ptr); the ahead run below writes the other set
+        g.res_plan = p;
+    } else {
+        queue_results(p);
     }
-    queue_results(p);
     token_results_queue(p);
-    // ---- ... and the next one on spec: greedy token on the device, then the plan again, behind this token's result copies ----
-    if (g.spec.cooldown > 0) g.spec.cooldown--;
-    if (g.opt_speculate_next && g.spec.cooldown == 0 && use_graph && m.N == 1 && m.logits && m.wte && m.output &&
-        m.n_past + 2 < m.C && p->graphs[av].exec) {
+    if (tail) {  // the next token, before the host waits for this one
         const int av2 = attn_variant(m, p, m.n_past + 2);
-        {
-            if (!g.results_ev) HIP_CHECK(hipEventCreateWithFlags(&g.results_ev, hipEventDisableTiming));
-            if (!g.spec.tok_ev) {
-                HIP_CHECK(hipEventCreateWithFlags(&g.spec.tok_ev, hipEventDisableTiming));
-                HIP_CHECK(hipHostMalloc((void **)&g.spec.tok_pin, 64, hipHostMallocDefault));
-                HIP_CHECK(hipMalloc((void **)&g.spec.tok_dev, 64));
-            }
-            HIP_CHECK(hipEventRecord(g.results_ev, g.stream));  // the host waits for THIS (d2h_finish), not for the stream's end
-            g.results_ev_armed = true;
-            g.results_ev_copies = stg.pending.size();
-            hipLaunchKernelGGL(k_argmax_next, dim3(1), dim3(1024), 0, g.stream, (const float *)p->logits_out, (int)m.V, p->prm, g.spec.tok_dev);
-            HIP_CHECK(hipMemcpyAsync(g.spec.tok_pin, g.spec.tok_dev, 4, hipMemcpyDeviceToHost, g.stream));
-            HIP_CHECK(hipEventRecord(g.spec.tok_ev, g.stream));
-            VariantGraphs &vg2 = p->graphs[av2];
-            if (!vg2.spec_exec) {  // the plan once more, captured with its final norm / lm_head aimed at the alternates (DecodePlan::logits_alt)
-                p->spec_out = true;
-                capture_into(&vg2.spec_graph, &vg2.spec_exec, [&] { plan_launch_decode(p, av2); });
-                p->spec_out = false;
-            }
-            HIP_CHECK(hipGraphLaunch(vg2.spec_exec, g.stream));
-            g.spec.pending = true;
-            g.spec.plan = p;
-            g.spec.n_past = m.n_past + 1;
-            g.spec.av = av2;
-        }
+        launch_tail(av2, tail_q ^ 1);
+        g.spec.pending = true;
+        g.spec.plan = p;
+        g.spec.n_past = m.n_past + 1;
+        g.spec.av = av2;
+        g.spec.parity = tail_q ^ 1;
+        g.spec.fed_id_valid = false;
     }
     const uint64_t t2 = now_ns();
     g.ns_match += t1 - t0;
@@ -337,16 +404,25 @@ static bool try_decode_plan(ggml_cgraph *gr, bool defer_wait = false) {
 // the precondition does not hold (the caller then decodes token by token).
 static int decode_greedy_chain(ggml_cgraph *last, int n, int32_t *out_tokens, float *last_logits) {
     finish_pending();
-    if (g.spec.pending) {  // the device has already gone one token further on its own: the caller decodes token by token (and hits)
-        spec_cancel();
-        return -1;
-    }
     DecodePlan *p = (DecodePlan *)g.chain_plan;
     if (!p || g.chain_graph != last || n < 1) return -1;
     bool live = false;
     for (auto *q : g_plans) live = live || q == p;
     const LlamaMatch &m = p->m;
     if (!live || m.N != 1 || !m.logits || !m.wte || m.n_past + 1 + n > m.C) return -1;
+    if (p->prm_ahead) {  // a token tail has moved the parameters on (and a run ahead of the caller may be in flight): back to the last evaluated token
+        if (!m.embd) return -1;
+        DecParams hp;
+        memset(&hp, 0, sizeof(hp));
+        hp.n_past = m.n_past;
+        hp.token = hp.tokens[0] = ((const int32_t *)m.embd->data)[0];
+        h2d_small((char *)p->prm, &hp, sizeof(hp));
+        p->prm_ahead = false;
+    }
+    spec_cancel();
+    // the first argmax reads the set the last evaluated token sits in; every replay below writes set 0
+    const float *first_logits = (const float *)plan_cur_logits(p);
+    g.res_plan = nullptr;
     if (p->chain_cap < n) {
         if (p->chain_out) (void)hipFree(p->chain_out);
         p->chain_cap = std::max(n, 256);
@@ -360,6 +436,10 @@ static int decode_greedy_chain(ggml_cgraph *last, int n, int32_t *out_tokens, fl
     // while the whole group stays on the short-context attention variant; the graph's sampled ids land in chain_out[i0 ..].
     if (use_graph && g.opt_chain_k > 1) {
         const int K = g.opt_chain_k;
+        if ((const char *)first_logits != p->logits_out) {  // the K-token graph's first argmax is captured on set 0
+            HIP_CHECK(hipMemcpyAsync(p->logits_out, first_logits, (size_t)m.V * 4, hipMemcpyDeviceToDevice, g.stream));
+            first_logits = (const float *)p->logits_out;
+        }
         const auto long_at = [&](int i) { return attn_variant(m, p, m.n_past + 1 + i + 1) != AV_SHORT; };
         while (i0 + K <= n && !long_at(i0 + K - 1)) {
             if (!p->exec_chain || p->chain_k != K) {  // (the graph writes its ids to a fixed ring: reusable at any offset)
@@ -381,8 +461,8 @@ static int decode_greedy_chain(ggml_cgraph *last, int n, int32_t *out_tokens, fl
         }
     }
     for (int i = i0; i < n; i++) {
-        hipLaunchKernelGGL(k_argmax_next, dim3(1), dim3(1024), 0, g.stream, (const float *)p->logits_out, (int)m.V, p->prm,
-                           p->chain_out + i);
+        hipLaunchKernelGGL(k_argmax_next, dim3(1), dim3(1024), 0, g.stream, i == 0 ? first_logits : (const float *)p->logits_out, (int)m.V,
+                           p->prm, p->chain_out + i);
         // the token of step i sits at position n_past + 1 + i; same rule as try_decode_plan for the attention variant
         const int av = attn_variant(m, p, m.n_past + 1 + i + 1);
         if (av != AV_SPLIT && fused_qkv_shape(m, av_heads_split(av)).ok) g.stat_fused_tokens++;
@@ -418,6 +498,7 @@ static int decode_batch(ggml_cgraph *const *graphs, int B) {
     finish_pending();
     spec_cancel();
     g.chain_plan = nullptr;
+    res_settle();  // (every column's results go to its graph's own nodes: result set 0)
     if (PrepMatch *pm = (PrepMatch *)g.prep) pm->gr = nullptr;
     if (!g.opt_plan || !g.opt_plan_batch) return -1;
     const uint64_t t0 = now_ns();

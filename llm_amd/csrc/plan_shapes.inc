@@ -74,12 +74,14 @@ static inline int av_heads_split(int av) { return av >= AV_FUSED2 ? av : 1; }
 struct VariantGraphs {
     hipGraph_t graph = nullptr;
     hipGraphExec_t exec = nullptr, exec2 = nullptr;  // exec2: a second instance of the same graph — a chain alternates so that a launch never waits for its own previous run
-    hipGraph_t spec_graph = nullptr;  // the backend's own speculative next-token run: the same launches aimed at the alternates (DecodePlan::logits_alt)
-    hipGraphExec_t spec_exec = nullptr;
+    // a greedy token's graph: the same launches aimed at result set q (DecodePlan::res_logits), then k_token_tail into slot q; tokens alternate
+    // between the two, so a launch never waits for its own previous run and never writes what the host or a device-side reader still reads
+    hipGraph_t tail_graph[2] = {nullptr, nullptr};
+    hipGraphExec_t tail_exec[2] = {nullptr, nullptr};
     void drop() {
-        for (hipGraphExec_t e : {exec, exec2, spec_exec})
+        for (hipGraphExec_t e : {exec, exec2, tail_exec[0], tail_exec[1]})
             if (e) (void)hipGraphExecDestroy(e);
-        for (hipGraph_t gr : {graph, spec_graph})
+        for (hipGraph_t gr : {graph, tail_graph[0], tail_graph[1]})
             if (gr) (void)hipGraphDestroy(gr);
         *this = VariantGraphs{};
     }
@@ -144,15 +146,25 @@ struct DecodePlan {
     _Float16 *p_x16 = nullptr, *p_p16 = nullptr;  // GEMM operand; softmax probabilities as f16 rows of (C + 8) & ~7
     int *p_tok = nullptr;
     float *stage_in = nullptr, *stage_out = nullptr;  // layer split: residual received / handed on
-    float *emb_out = nullptr;   // device mirror of the embedding_result node
-    char *logits_out = nullptr; // device mirror of the logits node
-    // the backend's own speculative next-token run (option speculate_next) writes its logits / embedding row HERE, never into the
-    // mirrors above: those are caller-visible (ggml_hip_topk, ggml_hip_tensor_get, llm_session_read_node read them on the device)
-    // and must keep the LAST EVALUATED token's values while the speculation is in flight or unused.  On a hit the results go to
-    // the host from here and are copied into the mirrors on the stream.
+    // Result set 0: the device images of the graph's own embedding_result / logits nodes.  Result set 1 (single-token plans): the same
+    // two buffers again in the plan's pool.  Greedy tokens alternate between the sets (VariantGraphs::tail_exec): the token the device
+    // runs AHEAD of its caller writes the set the last evaluated token does not sit in, so that set stays what every device-side
+    // reader must see (ggml_hip_topk, ggml_hip_tensor_get, llm_session_read_node, the greedy chain, perplexity: result_dev_ptr /
+    // plan_cur_logits).  A hit only flips cur_set; nothing is copied.  Everything that is not a greedy token writes set 0.
+    float *emb_out = nullptr;
+    char *logits_out = nullptr;
     char *logits_alt = nullptr;
     float *emb_alt = nullptr;
-    bool spec_out = false;  // set while the speculative graph is captured: plan_launch_* aim the final norm / lm_head at the alternates
+    int cur_set = 0;  // the set of the last evaluated token (meaningful while the slot's res_plan is this plan; set 0 otherwise)
+    int out_set = 0;  // the set plan_launch_* aim the final norm / lm_head at: 1 only while a graph of parity 1 is captured
+    char *res_logits(int q) const { return q ? logits_alt : logits_out; }
+    float *res_emb(int q) const { return emb_out ? (q ? emb_alt : emb_out) : nullptr; }
+    // the two result slots of the greedy tokens, pinned host memory k_token_tail stores into: logits | embedding row | id
+    char *slot[2] = {nullptr, nullptr};
+    hipEvent_t slot_ev[2] = {nullptr, nullptr};  // recorded directly behind the launch of the graph that fills the slot
+    size_t slot_emb_off = 0, slot_id_off = 0;
+    __half *kv_save[2] = {nullptr, nullptr};  // per parity: the cache rows of the position that graph writes, as they were before (k_kv_row_save)
+    bool prm_ahead = false;  // a token tail has moved the device's DecParams past m's token: whoever replays the plan next uploads them first
     int *chain_out = nullptr;   // ggml_hip_decode_greedy_chain: sampled ids (device)
     int *chain_ring = nullptr;  // ... of one K-token graph launch (option chain_k), copied into chain_out behind it
     int chain_cap = 0;
@@ -191,16 +203,73 @@ void destroy_plan(DecodePlan *p) {
     drop_plan_graphs(p);
     if (p->chain_ring) (void)hipFree(p->chain_ring);
     if (p->pool) (void)hipFree(p->pool);
+    for (int q = 0; q < 2; q++) {
+        if (p->slot[q]) (void)hipHostFree(p->slot[q]);
+        if (p->slot_ev[q]) (void)hipEventDestroy(p->slot_ev[q]);
+    }
+    if (g.res_plan == (void *)p) g.res_plan = nullptr;
     delete p;
 }
-// A speculative next-token run is in flight or finished unused: nothing of it may be taken for a result any more (its plan's
-// buffers are about to be reused, dropped, or replayed for a measurement).  The stream is drained so that it is over.
+// The device address a reader of node `t` reads: the tensor's own image, unless it lies in result set 0 of the plan whose last
+// evaluated token sits in set 1 — then the same offset of set 1 (DecodePlan::cur_set).
+char *result_dev_ptr(const ggml_tensor *t) {
+    char *d = dev_ptr(t);
+    DecodePlan *p = (DecodePlan *)g.res_plan;
+    if (!p || p->cur_set != 1 || !p->logits_alt) return d;
+    const size_t lb = (size_t)p->m.V * 4, eb = (size_t)p->m.E * 4;
+    if (p->logits_out && d >= p->logits_out && d < p->logits_out + lb) return p->logits_alt + (d - p->logits_out);
+    if (p->emb_out && d >= (char *)p->emb_out && d < (char *)p->emb_out + eb) return (char *)p->emb_alt + (d - (char *)p->emb_out);
+    return d;
+}
+// Another graph overtakes the plan whose last evaluated token sits in result set 1 (anything but a hit on that plan): its values go
+// into set 0, the graph nodes' own images, behind whatever ran ahead into set 0 — readers of that session's nodes keep seeing its
+// last evaluated token however many other sessions, chunks or generic graphs run on the slot afterwards.  Never on the hit path.
+static void res_settle() {
+    DecodePlan *p = nullptr;
+    for (auto *q : g_plans)
+        if ((void *)q == g.res_plan) p = q;
+    g.res_plan = nullptr;
+    if (!p || p->cur_set != 1 || !p->logits_alt || !p->logits_out) return;
+    HIP_CHECK(hipMemcpyAsync(p->logits_out, p->logits_alt, (size_t)p->m.V * 4, hipMemcpyDeviceToDevice, g.stream));
+    if (p->emb_out) HIP_CHECK(hipMemcpyAsync(p->emb_out, p->emb_alt, (size_t)p->m.E * 4, hipMemcpyDeviceToDevice, g.stream));
+    p->cur_set = 0;
+}
+static inline char *plan_cur_logits(const DecodePlan *p) { return p->res_logits(g.res_plan == (const void *)p ? p->cur_set : 0); }
+// A token the device ran ahead of its caller is in flight or finished unused: nothing of it may be taken for a result any more (its
+// plan's buffers are about to be reused, dropped, or replayed for a measurement).  The stream is drained so that it is over.
+// the K/V rows the pending ahead run wrote (a position its session has not reached) as they were before it, behind it on the stream
+static inline int kv_row_grid(const DecodePlan *p) { return (int)std::min<int64_t>(256, ((int64_t)p->m.L * p->m.Egqa + 255) / 256); }
+static void spec_take_back() {
+    DecodePlan *p = nullptr;
+    for (auto *q : g_plans)
+        if ((void *)q == g.spec.plan) p = q;
+    if (!p || !p->kv_save[g.spec.parity] || !p->mem_k) return;
+    hipLaunchKernelGGL(k_kv_row_restore, dim3(kv_row_grid(p)), dim3(256), 0, g.stream, g.spec.n_past, p->mem_k, p->mem_v,
+                       (const __half *)p->kv_save[g.spec.parity], (int)p->m.L, (int)p->m.C, (int)p->m.Egqa);
+    HIP_CHECK(hipGetLastError());
+}
 void spec_cancel() {
     if (!g.spec.pending) return;
     g.spec.pending = false;
+    spec_take_back();
     if (g.stream) HIP_CHECK(hipStreamSynchronize(g.stream));
 }
+// an access to device memory from outside (ggml_hip_tensor_get / _set, ggml_hip_memcpy): if it touches the caches the pending ahead
+// run reads and writes, that run is taken back first (a read then sees what a session that never ran ahead holds; after a write
+// the next evaluation runs on the new contents)
+void spec_guard_read(const char *d, size_t n) {
+    if (!g.spec.pending) return;
+    DecodePlan *p = nullptr;
+    for (auto *q : g_plans)
+        if ((void *)q == g.spec.plan) p = q;
+    if (!p || !p->mem_k) return;
+    const size_t kvb = (size_t)p->m.L * p->m.C * p->m.Egqa * 2;
+    const char *k = (const char *)p->mem_k, *v = (const char *)p->mem_v;
+    if ((d < k + kvb && k < d + n) || (d < v + kvb && v < d + n)) spec_cancel();
+}
+void finish_pending();
 void drop_all_plans() {
+    finish_pending(); // (a token whose results still sit in a plan's slot is delivered before the slot goes)
     spec_cancel();
     if (g_plans.empty()) return;
     if (g.stream) HIP_CHECK(hipStreamSynchronize(g.stream));

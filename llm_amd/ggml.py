@@ -265,6 +265,9 @@ PROTOTYPES.update({
     "ggml_hip_graph_compute_begin": (C.c_int, [C.c_void_p]),
     "ggml_hip_graph_prepare": (C.c_int, [C.c_void_p]),
     "ggml_hip_graph_compute_end": (None, []),
+    "ggml_hip_expect_greedy_next": (None, []),
+    "ggml_hip_debug_token_tail": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_void_p]),
     "ggml_hip_bench_plan_class": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int64),
                                             C.POINTER(C.c_double)]),
     "ggml_hip_comm_unique_id": (C.c_int, [C.c_void_p]),
