@@ -175,8 +175,20 @@ void execute_graph(ggml_cgraph *gr) {
     const bool fuse = g.opt_fuse != 0;
     // silu(a) whose only consumer is a later mul(silu(a), b) — the FFN gate; the reference's build order puts the
     // w3 mat-mul between the two (nodes: w1·x, silu, w3·x, mul), so the pair is not adjacent: the silu is deferred
-    // and executed fused when its mul comes up (nothing in between writes a's buffer: it is a live operand).
+    // and executed fused when its mul comes up.  That reads a when the mul runs, not when the silu would have: a node
+    // in between whose result overlaps a's bytes (an in-place op on a, a cpy into it) would change what the silu sees,
+    // so such a silu is not deferred and runs in its own place.
     std::vector<int> deferred_silu(gr->n_nodes, -1);  // index of the mul that will run it
+    auto written_between = [&](const ggml_tensor *t, int i, int j) {  // does a node of (i, j) write bytes of t?
+        const uintptr_t a0 = (uintptr_t)t->data, a1 = a0 + ggml_nbytes(t);
+        for (int k = i + 1; k < j; k++) {
+            const ggml_tensor *w = gr->nodes[k];
+            if (is_view_op(w->op) || w->data == nullptr) continue;
+            const uintptr_t b0 = (uintptr_t)w->data, b1 = b0 + ggml_nbytes(w);
+            if (b0 < a1 && a0 < b1) return true;
+        }
+        return false;
+    };
     if (fuse) {
         for (int j = 0; j < gr->n_nodes; j++) {
             ggml_tensor *mu = gr->nodes[j];
@@ -187,6 +199,7 @@ void execute_graph(ggml_cgraph *gr) {
             if (!is_contig_f32(un->src[0]) || !is_contig_f32(mu->src[1]) || !is_contig_f32(mu) ||
                 ggml_nelements(mu->src[1]) != ggml_nelements(un) || ggml_nelements(mu) != ggml_nelements(un))
                 continue;
+            if (written_between(un->src[0], i, j)) continue;
             deferred_silu[i] = j;
         }
     }

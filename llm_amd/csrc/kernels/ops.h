@@ -108,7 +108,11 @@ __device__ __forceinline__ float silu_table(float x) {
 }
 __device__ __forceinline__ float gelu_table(float x) {
     const float xf = round_f16(x);
-    const float g = 0.5f * xf * (1.0f + tanhf(0.79788456080286535587989211986876f * xf * (1.0f + 0.044715f * xf * xf)));
+    float g = 0.5f * xf * (1.0f + tanhf(0.79788456080286535587989211986876f * xf * (1.0f + 0.044715f * xf * xf)));
+    // ggml stores f16(gelu_f32(x)): one f32 rounding of the product, then one f16 rounding.  Left alone the compiler folds the
+    // last multiply into the conversion (v_fma_mixlo_f16, a single rounding), which lands on the other f16 neighbour wherever
+    // the f32 product is an exact tie (x = +-0.001339 in the table).
+    asm volatile("" : "+v"(g));
     return round_f16(g);
 }
 // MUL_B: fused `silu(a) * b` (the ggml_mul that follows silu in the FFN, llama lib.rs:328-330)
