@@ -608,6 +608,17 @@ GGML_API int ggml_hip_decode_greedy_chain(struct ggml_cgraph *last, int n, int32
  * weights, dimensions, context size and RoPE parameters; f16 K/V, all distinct; every n_past below the context size, which fits
  * the attention kernel's LDS; options plan and plan_batch on.  NULL or a B out of range is refused before any device is touched. */
 GGML_API int ggml_hip_decode_batch(struct ggml_cgraph *const *graphs, int n_graphs);
+/* n_steps greedy decode steps of those B sessions without a host round trip between them.  Step 0 is ggml_hip_decode_batch on the
+ * graphs (they carry every session's first token); each further step evaluates, for every session, the first maximum of the
+ * logits its previous step left — sampled on the device, which also moves the session's position on — as a replay of the same
+ * step.  out_ids[(i - 1) * B + c] = the token session c evaluated in step i (i = 1 .. n_steps - 1); after the last step every
+ * graph's logits and embedding nodes hold that step's results, as after ggml_hip_decode_batch.  Bit for bit what n_steps calls
+ * of ggml_hip_decode_batch by a caller that takes the first maximum compute: logits, K/V memory.  Every K/V memory advances by
+ * n_steps positions; the caller adds n_steps to each n_past.  Returns 0, or -1 with nothing executed: whatever
+ * ggml_hip_decode_batch declines, n_steps < 1 or > 4096, a session with n_past + n_steps beyond the context, option
+ * plan_batch_chain off.  n_steps == 1 is ggml_hip_decode_batch (out_ids may be NULL).  NULL, a B out of range or such an n_steps is
+ * refused before any device is touched. */
+GGML_API int ggml_hip_decode_batch_greedy(struct ggml_cgraph *const *graphs, int n_graphs, int n_steps, int32_t *out_ids);
 /* Top-k prefilter of a logits row on the device: the k (<= 1024, <= ne0) largest entries of row `row` of
  * the f32 tensor `t` — a node of the caller's most recent ggml_graph_compute, normally the logits — as (value, id) pairs,
  * value descending, lower id first among equal values, followed by the entries of `extra_ids` (n_extra ids, e.g. the
@@ -671,6 +682,11 @@ GGML_API int ggml_hip_debug_exp_le0(uint16_t *out_fast, uint16_t *out_ref);
  * cannot take. */
 GGML_API int ggml_hip_debug_token_tail(const float *logits, int V, const float *emb, int E, int n_past, int misalign,
                                        int32_t *id_tail, int32_t *id_argmax, float *slot_logits, float *slot_emb, int32_t *prm_out);
+/* Test hook: k_batch_argmax_next (the kernel between two steps of ggml_hip_decode_batch_greedy) alone.  logits [B][V], B = 1..8;
+ * pos_in[8] and tokens_in[32] are the positions and token ids a step's parameters hold before it.  Out: ids_out[B] the sampled ids,
+ * prm_out[34] = n_past, token, tokens[0..32) and pos_out[8] as the kernel left them.  0, or -1 for arguments it cannot take. */
+GGML_API int ggml_hip_debug_batch_tail(const float *logits, int B, int V, const int32_t *pos_in, const int32_t *tokens_in,
+                                       int32_t *ids_out, int32_t *prm_out, int32_t *pos_out);
 /* Test hook: w (quantized 2-D weight with a device copy) times N = 2..8 host rows x [N][K] through k_mmq_cols as the
  * multi-token plan launches it; out [N][M].  0, or -1 when that plan would not run this shape on k_mmq_cols. */
 GGML_API int ggml_hip_debug_mul_mat_cols(const struct ggml_tensor *w, const float *x, float *out, int N);

@@ -84,7 +84,7 @@ struct Backend {
     size_t ws_off = 0;  // offset in the last chunk
     Timing timing;
     int opt_fuse = 1, opt_plan = 1, opt_plan_k = 1, opt_plan_multi = 1, opt_plan_prompt = 1, opt_graph = 1, opt_big = 1, opt_kbig = 1;
-    int opt_chain_k = 0, opt_prepare = 1, opt_plan_batch = 1, opt_plan_f16 = 1;
+    int opt_chain_k = 0, opt_prepare = 1, opt_plan_batch = 1, opt_plan_f16 = 1, opt_plan_batch_chain = 1;
     int opt_fuse_attn = 1, opt_fuse_wo = 1, opt_warm_mb = 24, opt_affine = 1;
     int opt_act_quant = 0, opt_mmq_i8 = 0;
     int opt_mmq_min = 32, opt_k_prompt_min = 12, opt_mmq_fuse = 3, opt_mmq_cols = 1, opt_mmq_t256 = 1, opt_attn_fused = 1;
@@ -99,7 +99,7 @@ struct Backend {
     // counters: what each counts is said once, at its row of g_counters below
     uint64_t stat_plan_tokens = 0, stat_generic_graphs = 0, stat_split_tokens = 0, stat_prompt_plan_tokens = 0, stat_fused_tokens = 0, stat_kplan_tokens = 0, stat_fused_heads_tokens = 0, stat_fused_wo_tokens = 0, stat_fused_affine_tokens = 0, stat_prepared_tokens = 0;
     uint64_t stat_alibi_fused = 0;
-    uint64_t stat_batch_tokens = 0, stat_batch_steps = 0;
+    uint64_t stat_batch_tokens = 0, stat_batch_steps = 0, stat_batch_chain_steps = 0, stat_batch_chain_tokens = 0;
     uint64_t stat_flash_attn_nodes = 0;
     // prompt-GEMM launches by kernel (ggml_hip_get_stat("mmq_launches_<name>")): bench.py labels its MFMA roofline with the
     // kernels that actually ran
@@ -187,6 +187,9 @@ static const OptRow g_options[] = {
     {"plan_prompt", &Backend::opt_plan_prompt, OPT_ENV | OPT_DROPS},  // fused plan for prompt batches of >= mmq_min tokens (kernels/prompt.h)
     // ggml_hip_decode_batch: one decode step of 2..8 sessions of one model as one pass over the weights (0: it answers -1, the caller steps them one by one)
     {"plan_batch", &Backend::opt_plan_batch, OPT_ENV | OPT_DROPS},
+    // ggml_hip_decode_batch_greedy: n greedy steps of those sessions with the argmax on the device, the step's graph replayed (0: it
+    // answers -1, the caller takes n single steps).  It shapes no plan: the chain replays the graph of ggml_hip_decode_batch.
+    {"plan_batch_chain", &Backend::opt_plan_batch_chain, OPT_ENV},
     {"graph", &Backend::opt_graph, OPT_ENV},                          // replay the plan from a captured hipGraph
     {"big", &Backend::opt_big, OPT_ENV | OPT_DROPS},                  // decode mat-vec as one wave of 1024-thread workgroups (kernels/decode_big.h)
     // K plan: its decode mat-vecs as one wave of 1024-thread workgroups that stage the activation themselves (kernels/kquant_big.h)
@@ -289,6 +292,8 @@ static const StatRow g_counters[] = {
     {"prompt_plan_tokens", &Backend::stat_prompt_plan_tokens},    // tokens executed by the fused prompt plan
     {"batch_decode_tokens", &Backend::stat_batch_tokens},         // decode tokens that ran as columns of a batched step (ggml_hip_decode_batch); counted in plan_tokens too
     {"batch_decode_steps", &Backend::stat_batch_steps},           // ... and the steps
+    {"batch_chain_steps", &Backend::stat_batch_chain_steps},      // ... those of them that ran on device-sampled tokens (ggml_hip_decode_batch_greedy: all but a call's first)
+    {"batch_chain_tokens", &Backend::stat_batch_chain_tokens},    // ... and their tokens
     {"cols_warm_launches", &Backend::stat_cols_warm_launches},    // chunk-plan norm launches that carried warming workgroups (ColsWarm), counted when enqueued or captured
     {"fused_rearms", &Backend::stat_fused_rearms},                // times the fused forms came back after a clean stretch behind a give-up
     {"spec_hits", &Backend::stat_spec_hits},                      // evaluations that found their results already running (option speculate_next)

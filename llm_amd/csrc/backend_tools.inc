@@ -619,6 +619,62 @@ int ggml_hip_decode_batch(struct ggml_cgraph *const *graphs, int n_graphs) {
     return r;
 }
 
+int ggml_hip_decode_batch_greedy(struct ggml_cgraph *const *graphs, int n_graphs, int n_steps, int32_t *out_ids) {
+    if (!graphs || n_graphs < 2 || n_graphs > BATCH_COLS_MAX || n_steps < 1 || n_steps > BATCH_CHAIN_MAX_STEPS) return -1;  // (before any device is touched)
+    if (n_steps > 1 && !out_ids) return -1;
+    for (int i = 0; i < n_graphs; i++)
+        if (!graphs[i]) return -1;
+    SlotLock lk;
+    const uint64_t t0 = now_ns();
+    const int r = decode_batch_steps(graphs, n_graphs, n_steps, out_ids, true);
+    g.ns_compute += now_ns() - t0;
+    return r;
+}
+
+// ---- test hook: k_batch_argmax_next alone (tests/test_batch_chain_gpu.py) ----
+// logits [B][V], pos_in[8] and tokens_in[32] go to the device as a step's BatchCols::pos and DecParams::tokens (n_past = pos_in[0],
+// token = tokens_in[0]); the kernel runs once on B workgroups.  Out: ids_out[B], prm_out[34] = n_past, token, tokens[0..32),
+// pos_out[8].  0, or -1 for arguments it cannot take.
+int ggml_hip_debug_batch_tail(const float *logits, int B, int V, const int32_t *pos_in, const int32_t *tokens_in, int32_t *ids_out,
+                              int32_t *prm_out, int32_t *pos_out) {
+    if (!logits || B < 1 || B > BATCH_COLS_MAX || V < 1 || !pos_in || !tokens_in || !ids_out || !prm_out || !pos_out) return -1;
+    SlotLock lk;
+    ensure_init();
+    finish_pending();
+    const size_t lb = ((size_t)B * V * 4 + 255) & ~(size_t)255;
+    char *d = nullptr;
+    dev_malloc((void **)&d, lb + 1024, "debug batch tail");
+    DecParams *dp = (DecParams *)(d + lb);
+    BatchCols *db = (BatchCols *)(d + lb + 256);
+    int *dids = (int *)(d + lb + 768);
+    static_assert(sizeof(DecParams) <= 256 && sizeof(BatchCols) <= 512 && BATCH_COLS_MAX * 4 <= 256, "debug batch tail: layout");
+    DecParams hp;
+    BatchCols hb;
+    memset(&hp, 0, sizeof(hp));
+    memset(&hb, 0, sizeof(hb));
+    for (int i = 0; i < 32; i++) hp.tokens[i] = tokens_in[i];
+    for (int i = 0; i < BATCH_COLS_MAX; i++) hb.pos[i] = pos_in[i];
+    hp.n_past = pos_in[0];
+    hp.token = tokens_in[0];
+    HIP_CHECK(hipStreamSynchronize(g.stream));
+    HIP_CHECK(hipMemcpy(d, logits, (size_t)B * V * 4, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(dp, &hp, sizeof(hp), hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(db, &hb, sizeof(hb), hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemset(dids, 0xff, BATCH_COLS_MAX * 4));
+    hipLaunchKernelGGL(k_batch_argmax_next, dim3((unsigned)B), dim3(1024), 0, g.stream, (const float *)d, V, dp, db, dids);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipStreamSynchronize(g.stream));
+    HIP_CHECK(hipMemcpy(ids_out, dids, (size_t)B * 4, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(&hp, dp, sizeof(hp), hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(&hb, db, sizeof(hb), hipMemcpyDeviceToHost));
+    prm_out[0] = hp.n_past;
+    prm_out[1] = hp.token;
+    for (int i = 0; i < 32; i++) prm_out[2 + i] = hp.tokens[i];
+    for (int i = 0; i < BATCH_COLS_MAX; i++) pos_out[i] = hb.pos[i];
+    HIP_CHECK(hipFree(d));
+    return 0;
+}
+
 int64_t ggml_hip_get_stat(const char *key) {
     SlotLock lk;
     for (const StatRow &c : g_counters)  // the plain counters (backend_state.inc); the rest is computed here

@@ -1,6 +1,7 @@
 // llm_batch.cpp — the batched multi-session decode step of the session mirror bound to this library's backend: llm_evaluate_batch and
-// llm_infer_next_tokens_greedy_batch are llm_host.cpp's llm_*_batch_via with ggml_hip_decode_batch as the entry.  A file of its own
-// so that llm_host.cpp keeps linking against backends that have no such entry.
+// llm_infer_next_tokens_greedy_batch are llm_host.cpp's llm_*_batch_via with ggml_hip_decode_batch as the entry, and
+// llm_infer_tokens_greedy_batch_device the chained one with ggml_hip_decode_batch_greedy beside it.  A file of its own so that
+// llm_host.cpp keeps linking against backends that have no such entries.
 #include "ggml_hip.h"
 #include "llm_host.h"
 
@@ -10,5 +11,8 @@ int llm_evaluate_batch(llm_model *m, llm_session *const *sessions, const int32_t
 }
 int llm_infer_next_tokens_greedy_batch(llm_model *m, llm_session *const *sessions, int B, int32_t *out_ids) {
     return llm_infer_next_tokens_greedy_batch_via(ggml_hip_decode_batch, m, sessions, B, out_ids);
+}
+int llm_infer_tokens_greedy_batch_device(llm_model *m, llm_session *const *sessions, int B, int n, int32_t *out_ids) {
+    return llm_infer_tokens_greedy_batch_via(ggml_hip_decode_batch, ggml_hip_decode_batch_greedy, m, sessions, B, n, out_ids);
 }
 }

@@ -1449,17 +1449,25 @@ int llm_infer_tokens_greedy_device(llm_model *m, llm_session *s, int n, int32_t 
 // host stand-in); host/llm_batch.cpp binds the real one.  Returns 1 = ran batched, 0 = ran one by one, -1 = bad arguments, nothing
 // evaluated: a session listed twice, of another model or on another device slot than the calling thread's, a split model, a
 // token outside the vocabulary, a session whose context is full.  Like llm_evaluate it leaves the token history to the caller.
-int llm_evaluate_batch_via(llm_batch_entry entry, llm_model *m, llm_session *const *sessions, const int32_t *tokens, int B, float *logits) {
-    if (!m || !sessions || !tokens || B < 1) return -1;
-    if (!m->stages.empty() || !m->llama->is_first() || !m->llama->is_last()) return -1;
-    const size_t V = m->llama->hyperparameters.n_vocab;
+// what a batched step asks of its sessions, whatever their tokens: B different whole-model sessions of m on the calling thread's
+// slot, each with room for n more tokens
+static bool batch_sessions_ok(const llm_model *m, llm_session *const *sessions, int B, size_t n) {
+    if (!m || !sessions || B < 1) return false;
+    if (!m->stages.empty() || !m->llama->is_first() || !m->llama->is_last()) return false;
     for (int i = 0; i < B; i++) {
         const llm_session *s = sessions[i];
-        if (!s || !s->s || s->model != m || !s->stage_sessions.empty() || s->device != ggml_hip_get_main_device()) return -1;
+        if (!s || !s->s || s->model != m || !s->stage_sessions.empty() || s->device != ggml_hip_get_main_device()) return false;
         for (int j = 0; j < i; j++)
-            if (sessions[j] == s) return -1;
-        if (tokens[i] < 0 || (size_t)tokens[i] >= V || s->s->n_past + 1 > m->llama->params.context_size) return -1;
+            if (sessions[j] == s) return false;
+        if (s->s->n_past + n > m->llama->params.context_size) return false;
     }
+    return true;
+}
+int llm_evaluate_batch_via(llm_batch_entry entry, llm_model *m, llm_session *const *sessions, const int32_t *tokens, int B, float *logits) {
+    if (!tokens || !batch_sessions_ok(m, sessions, B, 1)) return -1;
+    const size_t V = m->llama->hyperparameters.n_vocab;
+    for (int i = 0; i < B; i++)
+        if (tokens[i] < 0 || (size_t)tokens[i] >= V) return -1;
     int batched = 0;
     if (entry && B >= 2) {
         std::vector<ggml_cgraph *> graphs((size_t)B);
@@ -1495,6 +1503,39 @@ int llm_infer_next_tokens_greedy_batch_via(llm_batch_entry entry, llm_model *m, 
         out_ids[i] = next[(size_t)i];
     }
     return r;
+}
+// n greedy tokens for each of B sessions with the sampler on the device (`chain` = ggml_hip_decode_batch_greedy): row 0 of out_ids
+// [n][B] is the first maximum of every session's last_logits, as above; the sessions' graphs for those tokens go to the backend once,
+// which evaluates them and n - 1 more steps on the tokens it samples itself (rows 1 .. n - 1).  Every session ends as after n calls
+// of llm_infer_next_tokens_greedy_batch_via — n_past, token history, last_logits, K/V — and that loop is what runs, through `step`,
+// when there is no chain entry or it declines.  Returns 1 = ran chained, 0 = ran as that loop, -1 = nothing evaluated, no session
+// moved: the bad arguments of llm_evaluate_batch_via, n < 1, a session without room for n tokens.
+int llm_infer_tokens_greedy_batch_via(llm_batch_entry step, llm_batch_chain_entry chain, llm_model *m, llm_session *const *sessions, int B,
+                                      int n, int32_t *out_ids) {
+    if (!out_ids || n < 1 || !batch_sessions_ok(m, sessions, B, (size_t)n)) return -1;
+    if (chain && B >= 2) {
+        std::vector<ggml_cgraph *> graphs((size_t)B);
+        std::vector<llm::GraphOutputs> outs((size_t)B);
+        for (int i = 0; i < B; i++) {
+            const std::vector<float> &l = sessions[i]->s->last_logits;
+            out_ids[i] = (int32_t)argmax_first(l.data(), l.size());
+            graphs[(size_t)i] = m->llama->stage_single(*sessions[i]->s, (llm::TokenId)out_ids[i], outs[(size_t)i]);
+        }
+        if (chain(graphs.data(), B, n, out_ids + B) == 0) {
+            std::vector<llm::TokenId> col((size_t)n);
+            for (int i = 0; i < B; i++) {
+                llm::InferenceSession &s = *sessions[i]->s;
+                m->llama->finish_single(s, graphs[(size_t)i], outs[(size_t)i]);  // (the graph's nodes hold the LAST step's results)
+                s.tokens.push_back((llm::TokenId)out_ids[i]);
+                for (int k = 1; k < n; k++) col[(size_t)k] = (llm::TokenId)out_ids[(size_t)k * B + i];
+                if (n > 1) s.advance_device_chain(col.data() + 1, (size_t)(n - 1));
+            }
+            return 1;
+        }
+    }
+    for (int k = 0; k < n; k++)
+        if (llm_infer_next_tokens_greedy_batch_via(step, m, sessions, B, out_ids + (size_t)k * B) < 0) return -1;
+    return 0;
 }
 // Accumulated host nanoseconds per phase (see InferenceSession::host_ns; [5] greedy argmax, [6] evaluate as a whole);
 // reset != 0 clears the accumulators after the read.

@@ -136,6 +136,18 @@ GGML_API int llm_evaluate_batch_via(llm_batch_entry entry, llm_model *m, llm_ses
                                     float *logits);
 GGML_API int llm_infer_next_tokens_greedy_batch_via(llm_batch_entry entry, llm_model *m, llm_session *const *sessions, int B,
                                                     int32_t *out_ids);
+/* n greedy tokens for each of B sessions of one model, sampled on the device (ggml_hip_decode_batch_greedy: every step one pass
+ * over the weights, no host round trip between steps).  out_ids [n][B]: row k holds the k-th token of every session; row 0 is
+ * the first maximum of each session's current last_logits.  Every session ends exactly as after n calls of
+ * llm_infer_next_tokens_greedy_batch: n_past, token history, last_logits (after the n-th token), K/V.  Returns 1 if the chain
+ * ran, 0 if the backend declined and that loop ran instead (same results), -1 with nothing evaluated and no session moved: the
+ * bad arguments of llm_evaluate_batch, n < 1, a session with n_past + n beyond the context size.  No stop tokens: the caller
+ * trims. */
+GGML_API int llm_infer_tokens_greedy_batch_device(llm_model *m, llm_session *const *sessions, int B, int n, int32_t *out_ids);
+/* ... with the backend's single step and its chain as parameters (either may be NULL), as the two _via entries above */
+typedef int (*llm_batch_chain_entry)(struct ggml_cgraph *const *graphs, int n_graphs, int n_steps, int32_t *out_ids);
+GGML_API int llm_infer_tokens_greedy_batch_via(llm_batch_entry step, llm_batch_chain_entry chain, llm_model *m,
+                                               llm_session *const *sessions, int B, int n, int32_t *out_ids);
 GGML_API size_t llm_session_read_node_host(const llm_session *s, int from_end, void *dst, size_t max_bytes);
 GGML_API int llm_session_rewind(llm_session *s, int num);
 /* host nanoseconds per phase of the decode loop, accumulated: [0] adopt/build graph, [1] token write + plan,

@@ -98,6 +98,26 @@ __global__ void __launch_bounds__(1024) k_argmax_next(const float *__restrict__ 
         out[0] = bi;
     }
 }
+// The same for a batched step (plan_launch_batch): workgroup c samples column c's row of logits [B][V] and writes the parameters the
+// step's next replay reads for that column — its token id, its position + 1 — and out[c].  Workgroup 0 also keeps the two fields a
+// step uploads for column 0 (token, n_past) in line.  Grid = B workgroups, each on its own row and its own entries: nothing is
+// handed between workgroups, and entries from B on are not touched.
+__global__ void __launch_bounds__(1024) k_batch_argmax_next(const float *__restrict__ logits, int V, DecParams *prm, BatchCols *bc,
+                                                            int *__restrict__ out) {
+    const int c = blockIdx.x;
+    if (c >= BATCH_COLS_MAX) return;
+    const int bi = argmax_first_block(logits + (size_t)c * V, V);
+    if (threadIdx.x == 0) {
+        const int pos = bc->pos[c] + 1;
+        prm->tokens[c] = bi;
+        bc->pos[c] = pos;
+        out[c] = bi;
+        if (c == 0) {
+            prm->token = bi;
+            prm->n_past = pos;
+        }
+    }
+}
 // The K row and the V column of position prm->n_past, every layer, saved before a greedy token's graph writes them (its first kernel
 // node): a token the device ran AHEAD of its caller and nobody asked for is taken back by k_kv_row_restore, so that the caches hold
 // exactly what a session that never ran ahead holds.  save: [L][Egqa] halves of K, then the same of V.

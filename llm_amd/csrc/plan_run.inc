@@ -493,14 +493,24 @@ static int decode_greedy_chain(ggml_cgraph *last, int n, int32_t *out_tokens, fl
 // (plan_launch_batch) with column c placed by the per-column table instead of "position n_past + c of one cache".  One plan per
 // (B, model, context) and one hipGraph of it; a step uploads DecParams (the token ids) and BatchCols (positions, caches) and replays.
 // -1 with nothing executed when the graphs are not that; the caller then computes them one by one.
-static int decode_batch(ggml_cgraph *const *graphs, int B) {
+//
+// ggml_hip_decode_batch_greedy: the same step, then n_steps - 1 more of the same B sessions, each on the first maximum of its
+// column's logits, without a host round trip between them: k_batch_argmax_next (kernels/decode.h) samples every column on the device
+// and writes the parameters the step's kernels read (DecParams::tokens[c], BatchCols::pos[c]), and the SAME graph is replayed — the
+// launches n batched steps of a greedy caller make, on the same inputs, so the same bits.  The tail kernel is an ordinary launch
+// between two graph launches; the step's graph is the one ggml_hip_decode_batch captured.  The sampled ids [n_steps - 1][B] collect
+// on the device and come back with the results of the last step, which go where a single step leaves them.  Nothing of this
+// outlives the call: the next step of any kind uploads its own parameters.
+constexpr int BATCH_CHAIN_MAX_STEPS = 4096;
+static int decode_batch_steps(ggml_cgraph *const *graphs, int B, int n_steps, int32_t *out_ids, bool chain) {
     ensure_init();
     finish_pending();
     spec_cancel();
     g.chain_plan = nullptr;
     res_settle();  // (every column's results go to its graph's own nodes: result set 0)
     if (PrepMatch *pm = (PrepMatch *)g.prep) pm->gr = nullptr;
-    if (!g.opt_plan || !g.opt_plan_batch) return -1;
+    if (!g.opt_plan || !g.opt_plan_batch || (chain && !g.opt_plan_batch_chain)) return -1;
+    if (n_steps < 1 || n_steps > BATCH_CHAIN_MAX_STEPS) return -1;
     const uint64_t t0 = now_ns();
     std::vector<LlamaMatch> ms((size_t)B);
     std::vector<uint64_t> sig;
@@ -508,7 +518,7 @@ static int decode_batch(ggml_cgraph *const *graphs, int B) {
         LlamaMatch &m = ms[(size_t)c];
         if (!match_llama_decode(graphs[c], m)) return -1;
         if (m.N != 1 || m.prompt || m.kquant || !m.wte || !m.output || !m.embd || !m.logits || !m.embedding) return -1;
-        if (m.n_past >= m.C || (qt_of(m.wtype) < 0 && !m.f16w)) return -1;  // (f16 K/V, D, E, F: the matcher's own preconditions)
+        if (m.n_past + n_steps > m.C || (qt_of(m.wtype) < 0 && !m.f16w)) return -1;  // (f16 K/V, D, E, F: the matcher's own preconditions)
         for (const ggml_tensor *t : {m.memory_k, m.memory_v}) {  // a session of another slot keeps its cache to itself (extra_of would abort)
             const DevTensor *e = (const DevTensor *)t->extra;
             if (e && e->magic == 0x48495054 && e->slot != g_cur_slot()) return -1;
@@ -560,13 +570,32 @@ static int decode_batch(ggml_cgraph *const *graphs, int B) {
     hp.token = hp.tokens[0];
     h2d_small((char *)p->prm, &hp, sizeof(hp));
     h2d_small((char *)p->bcols, &hb, sizeof(hb));
-    if (g.opt_graph && !g.timing.on) {
-        VariantGraphs &vg = p->graphs[AV_SHORT];
-        if (!vg.exec) capture_into(&vg.graph, &vg.exec, [&] { plan_launch_batch(p); });
-        HIP_CHECK(hipGraphLaunch(vg.exec, g.stream));
-        p->replays++;
-    } else {
-        plan_launch_batch(p);
+    const auto step = [&] {
+        if (g.opt_graph && !g.timing.on) {
+            VariantGraphs &vg = p->graphs[AV_SHORT];
+            if (!vg.exec) capture_into(&vg.graph, &vg.exec, [&] { plan_launch_batch(p); });
+            HIP_CHECK(hipGraphLaunch(vg.exec, g.stream));
+            p->replays++;
+        } else {
+            plan_launch_batch(p);
+        }
+    };
+    step();
+    if (n_steps > 1) {  // the device samples every column and moves the step's parameters on; ids of step i at chain_out[(i - 1) * B ..]
+        const int n_ids = (n_steps - 1) * B;
+        if (p->chain_cap < n_ids) {
+            if (p->chain_out) (void)hipFree(p->chain_out);
+            p->chain_cap = std::max(n_ids, 256);
+            HIP_CHECK(hipMalloc((void **)&p->chain_out, (size_t)p->chain_cap * 4));
+        }
+        for (int i = 1; i < n_steps; i++) {
+            hipLaunchKernelGGL(k_batch_argmax_next, dim3((unsigned)B), dim3(1024), 0, g.stream, (const float *)p->logits_out, (int)ms[0].V, p->prm,
+                               p->bcols, p->chain_out + (size_t)(i - 1) * B);
+            step();
+        }
+        HIP_CHECK(hipGetLastError());
+        if (out_ids) d2h_queue(out_ids, (const char *)p->chain_out, (size_t)n_ids * 4);
+        p->m.n_past = mb.n_past + n_steps - 1;
     }
     // every graph's results where an evaluation of that graph alone leaves them (queue_results): the logits in the node's host data
     // (CPU-backend node) or its device copy, the embedding row in the node's device copy and host data
@@ -579,12 +608,15 @@ static int decode_batch(ggml_cgraph *const *graphs, int B) {
         if (m.embedding->data) d2h_queue(m.embedding->data, erow, (size_t)m.E * 4);
     }
     const uint64_t t2 = now_ns();
-    g.stat_plan_tokens += (uint64_t)B;
-    g.stat_batch_tokens += (uint64_t)B;
-    g.stat_batch_steps++;
+    g.stat_plan_tokens += (uint64_t)B * (uint64_t)n_steps;
+    g.stat_batch_tokens += (uint64_t)B * (uint64_t)n_steps;
+    g.stat_batch_steps += (uint64_t)n_steps;
+    g.stat_batch_chain_steps += (uint64_t)(n_steps - 1);
+    g.stat_batch_chain_tokens += (uint64_t)(n_steps - 1) * (uint64_t)B;
     d2h_finish();
     g.ns_match += t1 - t0;
     g.ns_launch += t2 - t1;
     g.ns_wait += now_ns() - t2;
     return 0;
 }
+static int decode_batch(ggml_cgraph *const *graphs, int B) { return decode_batch_steps(graphs, B, 1, nullptr, false); }

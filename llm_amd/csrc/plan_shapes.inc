@@ -165,7 +165,7 @@ struct DecodePlan {
     size_t slot_emb_off = 0, slot_id_off = 0;
     __half *kv_save[2] = {nullptr, nullptr};  // per parity: the cache rows of the position that graph writes, as they were before (k_kv_row_save)
     bool prm_ahead = false;  // a token tail has moved the device's DecParams past m's token: whoever replays the plan next uploads them first
-    int *chain_out = nullptr;   // ggml_hip_decode_greedy_chain: sampled ids (device)
+    int *chain_out = nullptr;   // ggml_hip_decode_greedy_chain / ggml_hip_decode_batch_greedy: sampled ids (device)
     int *chain_ring = nullptr;  // ... of one K-token graph launch (option chain_k), copied into chain_out behind it
     int chain_cap = 0;
     VariantGraphs graphs[AV_COUNT];  // per attention variant; a batched step's plan has the one of AV_SHORT
@@ -202,6 +202,7 @@ void drop_plan_graphs(DecodePlan *p) {
 void destroy_plan(DecodePlan *p) {
     drop_plan_graphs(p);
     if (p->chain_ring) (void)hipFree(p->chain_ring);
+    if (p->chain_out) (void)hipFree(p->chain_out);
     if (p->pool) (void)hipFree(p->pool);
     for (int q = 0; q < 2; q++) {
         if (p->slot[q]) (void)hipHostFree(p->slot[q]);

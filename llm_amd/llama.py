@@ -102,6 +102,8 @@ def _lib():
         L.llm_evaluate_batch.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p, C.c_int, C.c_void_p]
         L.llm_infer_next_tokens_greedy_batch.restype = C.c_int
         L.llm_infer_next_tokens_greedy_batch.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_void_p]
+        L.llm_infer_tokens_greedy_batch_device.restype = C.c_int
+        L.llm_infer_tokens_greedy_batch_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_void_p]
         _bound = True
     return L
 
@@ -253,6 +255,18 @@ class Llama:
         rc = _lib().llm_infer_next_tokens_greedy_batch(self.ptr, ptrs, len(sessions), out.ctypes.data)
         if rc < 0:
             raise ValueError("llm_infer_next_tokens_greedy_batch: bad arguments (nothing was evaluated)")
+        return bool(rc), out
+
+    def infer_tokens_batch(self, sessions, n):
+        """n greedy tokens for each of several sessions of this model, sampled on the device where the backend can
+        (llm_infer_tokens_greedy_batch_device: every step one pass over the weights, no host round trip between steps; anything
+        else runs as n steps of infer_next_tokens_batch, with the same results).  Returns (ran_chained, ids [n, B]).  ValueError,
+        with nothing evaluated: the bad arguments of evaluate_batch, n < 1, a session without room for n tokens."""
+        ptrs = (C.c_void_p * len(sessions))(*[s.ptr for s in sessions])
+        out = np.zeros((max(int(n), 0), len(sessions)), np.int32)
+        rc = _lib().llm_infer_tokens_greedy_batch_device(self.ptr, ptrs, len(sessions), int(n), out.ctypes.data)
+        if rc < 0:
+            raise ValueError("llm_infer_tokens_greedy_batch_device: bad arguments (nothing was evaluated)")
         return bool(rc), out
 
     def free(self):
