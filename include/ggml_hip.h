@@ -682,6 +682,20 @@ GGML_API int ggml_hip_debug_exp_le0(uint16_t *out_fast, uint16_t *out_ref);
  * cannot take. */
 GGML_API int ggml_hip_debug_token_tail(const float *logits, int V, const float *emb, int E, int n_past, int misalign,
                                        int32_t *id_tail, int32_t *id_argmax, float *slot_logits, float *slot_emb, int32_t *prm_out);
+/* Test hook: k_token_tail preparing the next token (option tail_prepare), beside the three launches it stands for.  logits[V];
+ * wte_raw: V rows of E elements in the block format `wtype` (GGML_TYPE_Q4_0 .. Q8_0); mem_k [L][C][Egqa], mem_v [L][Egqa][C] f16.
+ * The parameters start at position n_past (n_past + 1 < C), the granule epoch at epoch_in.  One launch of the tail of parity
+ * `parity` (0 / 1) prepares position n_past + 1 — with `zeroed` != 0 the same launch is given a zeroed argument struct and must
+ * write none of it; beside it k_argmax_next, then k_get_rows_q, k_rope_table and k_kv_row_save run on a second set of parameters.
+ * Out, from the tail / from those launches (_ref): row [E], table [128] (the first 2 * half_d are written), the epoch, save
+ * [2 * L * Egqa] f16 (K rows, then V columns) — 0xFF bytes where never written; id_out: the id in the tail's slot; prm_out[0..4] =
+ * n_past, token, tokens[0] and the two position words of the tails as the launch left them.  0, or -1 for arguments it cannot take. */
+GGML_API int ggml_hip_debug_token_tail_prepare(const float *logits, int V, const void *wte_raw, int wtype, int E, int n_past,
+                                               uint32_t epoch_in, int parity, int zeroed, int L, int C, int Egqa,
+                                               const uint16_t *mem_k, const uint16_t *mem_v, float theta_scale, float freq_scale,
+                                               int half_d, int32_t *id_out, int32_t *prm_out, float *row, float *table,
+                                               uint32_t *epoch_out, uint16_t *save, float *row_ref, float *table_ref,
+                                               uint32_t *epoch_ref, uint16_t *save_ref);
 /* Test hook: k_batch_argmax_next (the kernel between two steps of ggml_hip_decode_batch_greedy) alone.  logits [B][V], B = 1..8;
  * pos_in[8] and tokens_in[32] are the positions and token ids a step's parameters hold before it.  Out: ids_out[B] the sampled ids,
  * prm_out[34] = n_past, token, tokens[0..32) and pos_out[8] as the kernel left them.  0, or -1 for arguments it cannot take. */

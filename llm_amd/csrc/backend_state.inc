@@ -116,13 +116,14 @@ struct Backend {
     // for exactly that (same plan, position + 1, the same token) its results are already on their way: a hit enqueues one graph
     // launch and one event record, and nothing but kernels sits between two token graphs.  Anything else simply runs behind the
     // ahead run (which wrote only plan-private buffers and the K/V row of a position the session has not reached).
-    int opt_speculate_next = 0, opt_token_tail = 1;
+    int opt_speculate_next = 0, opt_token_tail = 1, opt_tail_prepare = 1;
     bool greedy_hint = false;  // ggml_hip_expect_greedy_next: consumed by the next graph of this slot
     struct Spec {
         bool pending = false;
         void *plan = nullptr;
         int n_past = 0, av = 0;
         int parity = 0;                 // the result set / slot the ahead run fills
+        bool prepared = false;          // it ran as a TAIL_AHEAD graph: no prologue launch (stat tail_prepared_tokens on a hit)
         int32_t fed_id = 0;             // the token the device fed it: the id that came with the previous token's slot ...
         bool fed_id_valid = false;      // ... once that slot has been delivered (token_finish): the hit check needs no synchronisation
         int cooldown = 0;               // evaluations to sit out after a miss
@@ -135,7 +136,7 @@ struct Backend {
     } tail;
     void *res_plan = nullptr;           // the most recently evaluated plan while its last token sits in result set 1 (DecodePlan::cur_set); null: set 0 everywhere (res_settle)
     uint64_t stat_tail_tokens = 0, stat_result_copies = 0, stat_tail_hits = 0, stat_tail_misses = 0;
-    uint64_t stat_spec_hits = 0, stat_spec_misses = 0;
+    uint64_t stat_spec_hits = 0, stat_spec_misses = 0, stat_tail_prepared_tokens = 0;
     // in-launch hand-offs that gave up (kernels/common.h GRAN_SPIN_MAX): the plan's error word travels back with every token's
     // results (plan_run.inc token_finish)
     unsigned *ferr_pin = nullptr;    // the slot's error word: pinned HOST memory the kernels write straight into (zero-copy; written
@@ -202,6 +203,10 @@ static const OptRow g_options[] = {
     // 0 = no token runs ahead of its caller, whatever ggml_hip_expect_greedy_next or speculate_next say: every single-token plan run
     // takes the plain graph and the staged result copies
     {"token_tail", &Backend::opt_token_tail, OPT_ENV, FX_SPECULATE_NEXT},
+    // a greedy token's k_token_tail also prepares the next token (embedding row, RoPE table and epoch, saved cache rows: TailPrep), so
+    // that the graph launched directly behind it opens with its layer-0 launch; the block-format plan on the big workgroups only.
+    // 0 = every greedy token's graph opens with k_kv_row_save, get_rows and k_rope_table.  (The captured graphs froze it.)
+    {"tail_prepare", &Backend::opt_tail_prepare, OPT_ENV | OPT_DROPS},
     // ---- the fused decode launch
     // decode: wq|wk|wv and the attention as ONE launch (kernels/decode_fused.h) where the mat-vec deals as evenly over the remaining
     // workgroups; 2 = wherever legal (tests); 0 = the two-launch pair.  An explicit choice outlives a pending re-arm.
@@ -301,7 +306,8 @@ static const StatRow g_counters[] = {
     {"tail_tokens", &Backend::stat_tail_tokens},                  // evaluations whose results came through k_token_tail's slot
     {"tail_hits", &Backend::stat_tail_hits},                      // ahead runs the caller's next evaluation asked for, however they were armed ...
     {"tail_misses", &Backend::stat_tail_misses},                  // ... and those it did not (a greedy-by-hint caller that keeps missing shows here)
-    {"result_copies", &Backend::stat_result_copies},              // stream copies enqueued for parameters or results of single-token plan runs
+    {"tail_prepared_tokens", &Backend::stat_tail_prepared_tokens},  // evaluations whose graph ran with no prologue launch (a hit on a TAIL_AHEAD graph: option tail_prepare)
+    {"result_copies", &Backend::stat_result_copies},             // stream copies enqueued for parameters or results of single-token plan runs
     {"generic_graphs", &Backend::stat_generic_graphs},            // graphs run node by node
     {"alibi_fused", &Backend::stat_alibi_fused},                  // scale -> alibi -> diag_mask_inf -> soft_max chains (BLOOM, MPT) run as one launch (k_alibi_soft_max)
     {"flash_attn_nodes", &Backend::stat_flash_attn_nodes},        // GGML_OP_FLASH_ATTN nodes computed (one launch each: kernels/flash_attn.h)

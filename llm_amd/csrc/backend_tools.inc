@@ -587,7 +587,7 @@ int ggml_hip_debug_token_tail(const float *logits, int V, const float *emb, int 
     HIP_CHECK(hipMemcpy(pb, &hp, sizeof(hp), hipMemcpyHostToDevice));
     hipLaunchKernelGGL(k_argmax_next, dim3(1), dim3(1024), 0, g.stream, (const float *)dl, V, pa, ida);
     hipLaunchKernelGGL(k_token_tail, dim3(TOKEN_TAIL_WGS), dim3(1024), 0, g.stream, (const float *)dl, V, emb ? (const float *)de : (const float *)nullptr,
-                       E, pb, slot, (int)emb_off, (int)id_off);
+                       E, pb, slot, (int)emb_off, (int)id_off, TailPrep{});
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipStreamSynchronize(g.stream));
     HIP_CHECK(hipMemcpy(id_argmax, ida, 4, hipMemcpyDeviceToHost));
@@ -600,6 +600,99 @@ int ggml_hip_debug_token_tail(const float *logits, int V, const float *emb, int 
     if (emb && slot_emb) memcpy(slot_emb, slot + emb_off, (size_t)E * 4);
     HIP_CHECK(hipHostFree(slot));
     HIP_CHECK(hipFree(d));
+    return 0;
+}
+
+// ---- test hook: k_token_tail with a TailPrep, beside the three launches it stands for (tests/test_token_tail_prepare_gpu.py) ----
+// logits[V]; wte_raw: V rows of E elements in ggml's block format `wtype` (Q4_0 .. Q8_0), relaid as an upload relays them; mem_k
+// [L][C][Egqa] / mem_v [L][Egqa][C] f16; the parameters start at {n_past, token 0, pos_tail = n_past, n_past}, the epoch at epoch_in.
+// One launch of k_token_tail of parity `parity` (a graph's tail_prep_args: it reads pos_tail[parity], writes pos_tail[parity ^ 1])
+// prepares position n_past + 1; `zeroed` != 0: the same launch with a zeroed TailPrep.  Beside it, on a second set of parameters:
+// k_argmax_next, then k_get_rows_q, k_rope_table and k_kv_row_save as a token's graph opens with them.  Out, from the tail / from the
+// reference launches: row [E], table [128], epoch, save [2 * L * Egqa] halves — each 0xFF where never written — and prm_out[0..4] =
+// n_past, token, tokens[0], pos_tail[0], pos_tail[1] as the tail left them, id_out = the id in its slot.  0, or -1 for arguments
+// it cannot take.
+int ggml_hip_debug_token_tail_prepare(const float *logits, int V, const void *wte_raw, int wtype, int E, int n_past, uint32_t epoch_in,
+                                      int parity, int zeroed, int L, int C, int Egqa, const uint16_t *mem_k, const uint16_t *mem_v,
+                                      float theta_scale, float freq_scale, int half_d, int32_t *id_out, int32_t *prm_out, float *row,
+                                      float *table, uint32_t *epoch_out, uint16_t *save, float *row_ref, float *table_ref,
+                                      uint32_t *epoch_ref, uint16_t *save_ref) {
+    const int qt = qt_of((ggml_type)wtype);
+    if (!logits || V < 1 || !wte_raw || qt < 0 || E < 32 || E % 32 || n_past < 0 || n_past + 1 >= C || (parity & ~1) || L < 1 || Egqa < 1 ||
+        !mem_k || !mem_v || half_d < 1 || half_d > 64 || !id_out || !prm_out || !row || !table || !epoch_out || !save || !row_ref ||
+        !table_ref || !epoch_ref || !save_ref)
+        return -1;
+    SlotLock lk;
+    ensure_init();
+    finish_pending();
+    std::vector<char *> owned;
+    const int64_t nb = E / 32;
+    const size_t raw_bytes = (size_t)V * nb * (size_t)blk_bytes(qt), nkv = (size_t)L * C * Egqa * 2, nsave = (size_t)L * Egqa * 4;
+    char *draw = debug_buf(raw_bytes, wte_raw, owned);
+    size_t off[5];
+    char *dsoa = debug_buf(qw_layout(qt, V, nb, off), nullptr, owned);
+    relayout_launch(draw, qt, V, nb, dsoa);
+    const QWeight w = qw_at(dsoa, qt, V, nb);
+    char *dl = debug_buf((size_t)V * 4, logits, owned);
+    char *dk = debug_buf(nkv, mem_k, owned), *dv = debug_buf(nkv, mem_v, owned);
+    DecParams hp;
+    memset(&hp, 0, sizeof(hp));
+    hp.n_past = hp.pos_tail[0] = hp.pos_tail[1] = n_past;
+    DecParams *prm[2];
+    unsigned *ep[2];
+    char *drow[2], *dtab[2], *dsave[2];
+    for (int i = 0; i < 2; i++) {  // 0: the tail's, 1: the reference launches'
+        prm[i] = (DecParams *)debug_buf(sizeof(hp), &hp, owned);
+        ep[i] = (unsigned *)debug_buf(4, &epoch_in, owned);
+        drow[i] = debug_buf((size_t)E * 4, nullptr, owned);
+        dtab[i] = debug_buf(128 * 4, nullptr, owned);
+        dsave[i] = debug_buf(nsave, nullptr, owned);
+    }
+    int *ida = (int *)debug_buf(4, nullptr, owned);
+    char *slot = nullptr;
+    const size_t id_off = ((size_t)V * 4 + 255) & ~(size_t)255;
+    HIP_CHECK(hipHostMalloc((void **)&slot, id_off + 256, hipHostMallocDefault));
+    memset(slot, 0xff, id_off + 256);
+    TailPrep tp;
+    memset(&tp, 0, sizeof(tp));
+    if (!zeroed) {
+        tp.xnext = (float *)drow[0];
+        tp.wte = w;
+        tp.rope = (float *)dtab[0]; tp.epoch = ep[0];
+        tp.theta_scale = theta_scale; tp.freq_scale = freq_scale; tp.half_d = half_d;
+        tp.mem_k = (const __half *)dk; tp.mem_v = (const __half *)dv; tp.save = (__half *)dsave[0];
+        tp.L = L; tp.C = C; tp.Egqa = Egqa;
+        tp.pos_in = &prm[0]->pos_tail[parity]; tp.pos_out = &prm[0]->pos_tail[parity ^ 1];
+    }
+    hipLaunchKernelGGL(k_token_tail, dim3(token_tail_grid(!zeroed, (long)L * Egqa)), dim3(1024), 0, g.stream, (const float *)dl, V,
+                       (const float *)nullptr, 0, prm[0], slot, (int)id_off, (int)id_off, tp);
+    hipLaunchKernelGGL(k_argmax_next, dim3(1), dim3(1024), 0, g.stream, (const float *)dl, V, prm[1], ida);
+    hipLaunchKernelGGL(k_kv_row_save, dim3((unsigned)std::min<int64_t>(256, ((int64_t)L * Egqa + 255) / 256)), dim3(256), 0, g.stream,
+                       (const DecParams *)prm[1], (const __half *)dk, (const __half *)dv, (__half *)dsave[1], L, C, Egqa);
+    hipLaunchKernelGGL(k_get_rows_q, dim3((unsigned)((nb + 255) / 256), 1), dim3(256), 0, g.stream, w, (const int *)&prm[1]->token,
+                       (float *)drow[1], (int64_t)E);
+    hipLaunchKernelGGL(k_rope_table, dim3(1), dim3(128), 0, g.stream, (const DecParams *)prm[1], theta_scale, freq_scale, half_d,
+                       (float *)dtab[1], ep[1]);
+    HIP_CHECK(hipGetLastError());
+    float *rows[2] = {row, row_ref}, *tabs[2] = {table, table_ref};
+    uint32_t *eps[2] = {epoch_out, epoch_ref};
+    uint16_t *saves[2] = {save, save_ref};
+    for (int i = 0; i < 2; i++) {
+        d2h_queue(rows[i], drow[i], (size_t)E * 4);
+        d2h_queue(tabs[i], dtab[i], 128 * 4);
+        d2h_queue(eps[i], (const char *)ep[i], 4);
+        d2h_queue(saves[i], dsave[i], nsave);
+    }
+    d2h_queue(&hp, (const char *)prm[0], sizeof(hp));
+    d2h_finish();
+    prm_out[0] = hp.n_past;
+    prm_out[1] = hp.token;
+    prm_out[2] = hp.tokens[0];
+    prm_out[3] = hp.pos_tail[0];
+    prm_out[4] = hp.pos_tail[1];
+    *id_out = *(const int32_t *)(slot + id_off);
+    HIP_CHECK(hipHostFree(slot));
+    for (char *b : owned) HIP_CHECK(hipFree(b));
     return 0;
 }
 

@@ -23,6 +23,8 @@ struct DecParams {
                   // roofline leg: a replay of the mat-vec class alone runs on stale activations and parks its rows in the last slot)
     int pad1;
     int tokens[32];  // multi-token plan (2..31 tokens of a prompt chunk): ids of all tokens, tokens[0] == token
+    int pos_tail[2];  // k_token_tail of parity q (TailPrep): n_past again, in a word that launch does not write — it reads [q], its
+                      // workgroup 0 writes [q ^ 1] for the tail that follows; a host upload sets both
 };
 // Batched multi-session decode (plan_launch_batch): column c of the step is the ONE token session c evaluates, at that session's own
 // position in that session's own cache.  Uploaded once per step like DecParams; the kernels that place a column in a cache (the
@@ -147,30 +149,128 @@ __global__ void __launch_bounds__(256) k_kv_row_restore(int pos, __half *__restr
 // together store the logits, the E-wide embedding row (emb, nullable) and the id into `slot`, pinned host memory, by 16-byte stores —
 // the host reads the slot once the event behind the graph is done, so no copy command sits between two token graphs.
 // Slot layout: the logits at 0, the row at emb_off, the id at id_off (both 16-byte multiples).
+//
+// With a TailPrep (xnext set; a zeroed one changes nothing) the launch also does what the NEXT token's graph would open with, for
+// position n_past + 1, so that a graph launched directly behind this one starts with its layer-0 launch:
+//   workgroup 0                     after its argmax (it takes no share of the copies then): row `id` of wte dequantized into xnext,
+//                                   k_get_rows_q's arithmetic (x*d, then + m), four consecutive elements and one 16-byte store per thread
+//   workgroups 1 .. TOKEN_TAIL_WGS-1  the copies into the slot
+//   workgroup TOKEN_TAIL_WGS        the (cos, sin) table of that position and the next granule epoch, as k_rope_table
+//   the workgroups behind it        the K row and the V column of that position, every layer, into `save` (k_kv_row_save's layout)
+// No workgroup reads a word another one of the launch writes: workgroup 0 alone reads and rewrites prm->n_past; the others take the
+// position from *pos_in, which the host's upload or the previous tail wrote, and workgroup 0 leaves it for the tail that follows
+// in *pos_out (DecParams::pos_tail, one word per parity).
+struct TailPrep {
+    float *xnext;  // the prepared embedding row [wte.nb * 32]; null: the whole struct is off
+    QWeight wte;
+    float *rope;
+    unsigned *epoch;
+    float theta_scale, freq_scale;
+    int half_d;
+    const __half *mem_k, *mem_v;
+    __half *save;  // null: no save
+    int L, C, Egqa;
+    const int *pos_in;
+    int *pos_out;
+};
 constexpr int TOKEN_TAIL_WGS = 8;
-__global__ void __launch_bounds__(1024) k_token_tail(const float *__restrict__ logits, int V, const float *__restrict__ emb, int E,
-                                                     DecParams *prm, char *__restrict__ slot, int emb_off, int id_off) {
-    const int gtid = blockIdx.x * 1024 + threadIdx.x, total = gridDim.x * 1024;
-    float *sl = (float *)slot, *se = (float *)(slot + emb_off);
-    if (((uintptr_t)logits & 15) == 0) {
-        const int V4 = V >> 2;
-        for (int i = gtid; i < V4; i += total) ((float4 *)sl)[i] = ((const float4 *)logits)[i];
-        if (gtid < (V & 3)) sl[(V4 << 2) + gtid] = logits[(V4 << 2) + gtid];  // the last partial group
-    } else {
-        for (int i = gtid; i < V; i += total) sl[i] = logits[i];
+constexpr int TOKEN_TAIL_SAVE_WGS_MAX = 128;
+// workgroups of a k_token_tail launch: the plain one, or with a TailPrep that saves n_save = L * Egqa elements of K and of V
+static inline int token_tail_grid(bool prep, long n_save) {
+    if (!prep) return TOKEN_TAIL_WGS;
+    const long s = (n_save + 1023) / 1024;
+    return TOKEN_TAIL_WGS + 1 + (int)(s < TOKEN_TAIL_SAVE_WGS_MAX ? s : TOKEN_TAIL_SAVE_WGS_MAX);
+}
+__device__ __forceinline__ void rope_table_pair(int pos, int c, int kk, float theta_scale, float freq_scale, float *__restrict__ out);
+// row `row` of a block-format weight as f32, by the 1024 threads of one workgroup: thread t of a pass holds elements 4t .. 4t + 3
+// (block t / 8; the low nibbles / first plane are elements 0..15 of a block, the high nibbles / second plane 16..31)
+__device__ __forceinline__ void tail_embed_row(const QWeight &w, int64_t row, float *__restrict__ dst) {
+    const int qt = w.qt;
+    const bool has_m = qt == QT_Q4_1 || qt == QT_Q5_1;
+    const bool has_h = qt == QT_Q5_0 || qt == QT_Q5_1;
+    const int zero = qt == QT_Q4_0 ? 8 : qt == QT_Q5_0 ? 16 : 0;
+    for (int64_t e4 = threadIdx.x; e4 < w.nb * 8; e4 += 1024) {
+        const int64_t i = row * w.nb + (e4 >> 3);
+        const int o = (int)(e4 & 7) * 4, j0 = o & 15;
+        const bool up = o >= 16;
+        const float d = __half2float(w.d[i]);
+        float v[4];
+        if (qt == QT_Q8_0) {
+            const int8_t *q = (const int8_t *)((up ? w.qs2 : w.qs) + i * 16 + j0);
+#pragma unroll
+            for (int u = 0; u < 4; u++) v[u] = q[u] * d;
+        } else {
+            const uint8_t *qs = w.qs + i * 16 + j0;
+            const float m = has_m ? __half2float(w.m[i]) : 0.0f;
+            const uint32_t qh = has_h ? w.qh[i] : 0u;
+#pragma unroll
+            for (int u = 0; u < 4; u++) {
+                const int j = j0 + u;
+                const int xh = !has_h ? 0 : up ? (int)((qh >> (j + 12)) & 0x10u) : (int)(((qh >> j) << 4) & 0x10u);
+                const int x = ((up ? (qs[u] >> 4) : (qs[u] & 0x0F)) | xh) - zero;
+                v[u] = has_m ? x * d + m : x * d;  // separate multiply and add, as k_get_rows_q
+            }
+        }
+        ((float4 *)dst)[e4] = make_float4(v[0], v[1], v[2], v[3]);
     }
-    if (emb) {
-        if (((uintptr_t)emb & 15) == 0 && (E & 3) == 0)
-            for (int i = gtid; i < (E >> 2); i += total) ((float4 *)se)[i] = ((const float4 *)emb)[i];
-        else
-            for (int i = gtid; i < E; i += total) se[i] = emb[i];
+}
+__global__ void __launch_bounds__(1024) k_token_tail(const float *__restrict__ logits, int V, const float *__restrict__ emb, int E,
+                                                     DecParams *prm, char *__restrict__ slot, int emb_off, int id_off, const TailPrep tp) {
+    const bool prep = tp.xnext != nullptr;
+    if ((int)blockIdx.x >= TOKEN_TAIL_WGS) {  // (only a launch with a TailPrep has these)
+        if (!prep) return;
+        const int pos = *tp.pos_in + 1;
+        if (blockIdx.x == TOKEN_TAIL_WGS) {
+            const int kk = threadIdx.x;
+            if (tp.epoch && kk == 0) {
+                const unsigned e = *tp.epoch + 1u;
+                *tp.epoch = e ? e : 1u;
+            }
+            if (kk < tp.half_d) rope_table_pair(pos, 0, kk, tp.theta_scale, tp.freq_scale, tp.rope);
+            return;
+        }
+        if (!tp.save || pos < 0 || pos >= tp.C) return;
+        const long n = (long)tp.L * tp.Egqa, C = tp.C, nwg = (long)gridDim.x - (TOKEN_TAIL_WGS + 1);
+        for (long i = ((long)blockIdx.x - (TOKEN_TAIL_WGS + 1)) * 1024 + threadIdx.x; i < n; i += nwg * 1024) {
+            const long il = i / tp.Egqa, c = i % tp.Egqa;
+            tp.save[i] = tp.mem_k[(il * C + pos) * tp.Egqa + c];
+            tp.save[n + i] = tp.mem_v[(il * tp.Egqa + c) * C + pos];
+        }
+        return;
+    }
+    const int first = prep ? 1 : 0;  // the copying workgroups: first .. TOKEN_TAIL_WGS - 1
+    if ((int)blockIdx.x >= first) {
+        const int gtid = ((int)blockIdx.x - first) * 1024 + threadIdx.x, total = (TOKEN_TAIL_WGS - first) * 1024;
+        float *sl = (float *)slot, *se = (float *)(slot + emb_off);
+        if (((uintptr_t)logits & 15) == 0) {
+            const int V4 = V >> 2;
+            for (int i = gtid; i < V4; i += total) ((float4 *)sl)[i] = ((const float4 *)logits)[i];
+            if (gtid < (V & 3)) sl[(V4 << 2) + gtid] = logits[(V4 << 2) + gtid];  // the last partial group
+        } else {
+            for (int i = gtid; i < V; i += total) sl[i] = logits[i];
+        }
+        if (emb) {
+            if (((uintptr_t)emb & 15) == 0 && (E & 3) == 0)
+                for (int i = gtid; i < (E >> 2); i += total) ((float4 *)se)[i] = ((const float4 *)emb)[i];
+            else
+                for (int i = gtid; i < E; i += total) se[i] = emb[i];
+        }
     }
     if (blockIdx.x != 0) return;
-    const int bi = argmax_first_block(logits, V);
+    __shared__ int s_bi;
+    const int bi0 = argmax_first_block(logits, V);
+    if (threadIdx.x == 0) s_bi = bi0;
+    if (prep) {
+        __syncthreads();
+        const int bi = s_bi;
+        if (bi >= 0 && bi < tp.wte.M) tail_embed_row(tp.wte, bi, tp.xnext);
+    }
     if (threadIdx.x == 0) {
+        const int bi = bi0, pos = prm->n_past + 1;
         prm->token = bi;
         prm->tokens[0] = bi;
-        prm->n_past = prm->n_past + 1;
+        prm->n_past = pos;
+        if (prep) *tp.pos_out = pos;
         *(int *)(slot + id_off) = bi;
     }
 }

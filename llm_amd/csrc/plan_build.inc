@@ -192,6 +192,7 @@ static void plan_pool_layout(DecodePlan *p, PoolCarver &c) {
     c.take(p->emb_alt, spec ? E * 4 : 0);
     c.take(p->kv_save[0], spec ? (size_t)m.L * m.Egqa * 4 : 0);
     c.take(p->kv_save[1], spec ? (size_t)m.L * m.Egqa * 4 : 0);
+    c.take(p->xnext, spec && m.wte && !kq && !m.f16w ? E * 4 : 0);
     c.take(p->epoch, 256);
     const size_t units = (size_t)((m.E + 2 * m.Egqa) / 2);  // granules of a layer's wq|wk|wv rows
     c.take(p->gran, one ? (size_t)m.L * units * 8 : 0);

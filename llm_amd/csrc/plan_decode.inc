@@ -253,7 +253,10 @@ static void plan_launch_all(DecodePlan *p, int av, LaunchCtx cx) {
     // A stage of a layer split: its first layer reads the residual straight from the hand-off buffer (xin below) and its last layer's
     // w2 launch writes straight into the outgoing one — no copy node at either end of the stage (each was a copy-engine start + a
     // boundary on the token's path: ~5 us per stage boundary and side)
-    if (m.wte)  // token embedding: get_rows(wte, embd)
+    // A greedy token's graph launched directly behind another one (TAIL_AHEAD, plan_run.inc) opens with neither launch below: that
+    // graph's k_token_tail has left this token's row in p->xnext, its table in p->rope and its epoch open
+    const bool prepared = p->open_prepared;
+    if (m.wte && !prepared)  // token embedding: get_rows(wte, embd)
         cx.other((double)E * 4.6, [&] {
             hipLaunchKernelGGL(k_get_rows_q, dim3((unsigned)((nbE + 255) / 256), 1), dim3(256), 0, g.stream, p->wte,
                                (const int *)&p->prm->token, p->xa, E);
@@ -264,7 +267,7 @@ static void plan_launch_all(DecodePlan *p, int av, LaunchCtx cx) {
     // class alone (roofline leg) takes it along when the fused launch is part of that class — the hand-off wait is then
     // inside the measured time, not skipped on stale-but-equal tags
     const bool rope_for_fused = fsh.ok && (cx.mask & (1u << GGML_HIP_KCLASS_MMVQ)) && (cx.kind_mask & 1u) && !(cx.mask & (1u << GGML_HIP_KCLASS_OTHER));
-    if (big && (cx.want(GGML_HIP_KCLASS_OTHER, (double)m.D * 4.0) || rope_for_fused)) {
+    if (big && !prepared && (cx.want(GGML_HIP_KCLASS_OTHER, (double)m.D * 4.0) || rope_for_fused)) {
         hipLaunchKernelGGL(k_rope_table, dim3(1), dim3(128), 0, g.stream, (const DecParams *)p->prm, theta_scale,
                            m.freq_scale, (int)(m.D >> 1), p->rope, p->epoch);
         HIP_CHECK(hipGetLastError());
@@ -281,7 +284,7 @@ static void plan_launch_all(DecodePlan *p, int av, LaunchCtx cx) {
         const DecodePlan::LW &w = p->lw[wl];
         const DecodePlan::LayerNorms &ln = p->ln[wl];
         // ---- attention norm + wq|wk|wv + rope + KV store ----
-        float *const xin = (il == 0 && !m.wte) ? p->stage_in : p->xa;                    // the layer's input row (residual stream)
+        float *const xin = il != 0 ? p->xa : !m.wte ? p->stage_in : prepared ? p->xnext : p->xa;  // the layer's input row (residual stream)
         float *const xout = (il == m.L - 1 && !m.output) ? p->stage_out : p->xa;        // ... and where its w2 + residual goes
         if (!fuse_x) rmsq(xin, ln.attn_norm, nullptr);
         {

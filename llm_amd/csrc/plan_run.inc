@@ -181,6 +181,28 @@ static void tail_slots(DecodePlan *p) {
         HIP_CHECK(hipEventCreateWithFlags(&p->slot_ev[q], hipEventDisableTiming));
     }
 }
+// whether the plan's greedy tokens prepare their successors (option tail_prepare): the block-format plan on the big workgroups, whole
+// model.  K-quant plans, F16 plans, option big = 0 and the stages of a split keep their prologue launches.
+static bool tail_prepares(const DecodePlan *p) {
+    const LlamaMatch &m = p->m;
+    return g.opt_tail_prepare && g.opt_big && !m.kquant && !m.f16w && m.N == 1 && m.wte && m.output && qt_of(m.wtype) >= 0 && p->xnext && p->kv_save[0] && p->mem_k &&
+           p->mem_v && m.D / 2 <= 64 && m.E % 32 == 0;
+}
+// what the tail of the graph of parity q prepares: the next token's row, its table and epoch, and the cache rows the graph of parity
+// q ^ 1 will write, into that parity's save area (where spec_take_back looks for them)
+static TailPrep tail_prep_args(const DecodePlan *p, int q) {
+    const LlamaMatch &m = p->m;
+    TailPrep tp;
+    memset(&tp, 0, sizeof(tp));
+    tp.xnext = p->xnext;
+    tp.wte = p->wte;
+    tp.rope = p->rope; tp.epoch = p->epoch;
+    tp.theta_scale = powf(m.freq_base, -2.0f / m.n_dims); tp.freq_scale = m.freq_scale; tp.half_d = (int)(m.D >> 1);
+    tp.mem_k = p->mem_k; tp.mem_v = p->mem_v; tp.save = p->kv_save[q ^ 1];
+    tp.L = m.L; tp.C = (int)m.C; tp.Egqa = (int)m.Egqa;
+    tp.pos_in = &p->prm->pos_tail[q]; tp.pos_out = &p->prm->pos_tail[q ^ 1];
+    return tp;
+}
 static bool try_decode_plan(ggml_cgraph *gr, bool defer_wait = false) {
     g.chain_plan = nullptr;  // any new graph ends the chainable state; a single-token plan run re-arms it below
     const bool greedy_next = g.greedy_hint;  // ggml_hip_expect_greedy_next spoke of THIS graph, whatever it turns out to be
@@ -244,6 +266,7 @@ static bool try_decode_plan(ggml_cgraph *gr, bool defer_wait = false) {
         // itself shows in tail_tokens and in result_copies standing still)
         if (spec_hit) {
             if (g.opt_speculate_next) g.stat_spec_hits++;
+            if (g.spec.prepared) g.stat_tail_prepared_tokens++;
         } else {
             if (g.opt_speculate_next) g.stat_spec_misses++;
             g.spec.cooldown = 8;  // a sampler that does not take the first maximum: stop guessing for a while
@@ -256,6 +279,7 @@ static bool try_decode_plan(ggml_cgraph *gr, bool defer_wait = false) {
     hp.n_past = m.n_past;
     hp.token = m.embd ? ((const int32_t *)m.embd->data)[0] : 0;
     hp.store_at = hp.pad1 = 0;
+    hp.pos_tail[0] = hp.pos_tail[1] = m.n_past;
     for (int i = 0; i < 32; i++) {
         hp.tokens[i] = (m.embd && i < m.N && !m.prompt) ? ((const int32_t *)m.embd->data)[i] : 0;
         if (m.wte && (hp.tokens[i] < 0 || hp.tokens[i] >= m.wte->ne[1])) die("token id %d out of range", hp.tokens[i]);
@@ -313,24 +337,34 @@ static bool try_decode_plan(ggml_cgraph *gr, bool defer_wait = false) {
     if (g.spec.cooldown > 0) g.spec.cooldown--;
     const bool tail = g.opt_token_tail && (g.opt_speculate_next || greedy_next) && g.spec.cooldown == 0 && use_graph && m.N == 1 && m.logits && m.wte &&
                       m.output && m.embd && p->logits_alt && m.n_past + 2 < m.C;
-    const auto launch_tail = [&](int v, int q) {  // the plan's graph of variant v, parity q: result set q, slot q, and the slot's event directly behind it
+    // The plan's graph of variant v, parity q: result set q, slot q, and the slot's event directly behind it.  `ahead`: launched directly
+    // behind another tail graph of this plan — the second call below and nothing else; where the plan's tails prepare the next token
+    // (tail_prepares) that is flavour TAIL_AHEAD, whose first kernel is the layer-0 launch, and every other launch is TAIL_FIRST.
+    const bool prep = tail_prepares(p);
+    const auto launch_tail = [&](int v, int q, bool ahead) {
         VariantGraphs &vg = p->graphs[v];
-        if (!vg.tail_exec[q]) {
+        const int fl = prep && ahead ? TAIL_AHEAD : TAIL_FIRST;
+        if (!vg.tail_exec[fl][q]) {
             tail_slots(p);
             p->out_set = q;
-            capture_into(&vg.tail_graph[q], &vg.tail_exec[q], [&] {
-                hipLaunchKernelGGL(k_kv_row_save, dim3(kv_row_grid(p)), dim3(256), 0, g.stream, (const DecParams *)p->prm, (const __half *)p->mem_k,
-                                   (const __half *)p->mem_v, p->kv_save[q], (int)m.L, (int)m.C, (int)m.Egqa);
+            p->open_prepared = fl == TAIL_AHEAD;
+            capture_into(&vg.tail_graph[fl][q], &vg.tail_exec[fl][q], [&] {
+                if (!prep)  // (a preparing tail has saved this graph's rows already, or the token was asked for and is never taken back)
+                    hipLaunchKernelGGL(k_kv_row_save, dim3(kv_row_grid(p)), dim3(256), 0, g.stream, (const DecParams *)p->prm, (const __half *)p->mem_k,
+                                       (const __half *)p->mem_v, p->kv_save[q], (int)m.L, (int)m.C, (int)m.Egqa);
                 plan_launch_decode(p, v);
-                hipLaunchKernelGGL(k_token_tail, dim3(TOKEN_TAIL_WGS), dim3(1024), 0, g.stream, (const float *)p->res_logits(q), (int)m.V,
+                const TailPrep tp = prep ? tail_prep_args(p, q) : TailPrep{};
+                hipLaunchKernelGGL(k_token_tail, dim3(token_tail_grid(prep, (long)m.L * m.Egqa)), dim3(1024), 0, g.stream, (const float *)p->res_logits(q), (int)m.V,
                                    (size_t)m.E * 4 <= ((size_t)128 << 10) ? (const float *)p->res_emb(q) : (const float *)nullptr, (int)m.E, p->prm, p->slot[q],
-                                   (int)p->slot_emb_off, (int)p->slot_id_off);
+                                   (int)p->slot_emb_off, (int)p->slot_id_off, tp);
             });
             p->out_set = 0;
+            p->open_prepared = false;
         }
-        HIP_CHECK(hipGraphLaunch(vg.tail_exec[q], g.stream));
+        HIP_CHECK(hipGraphLaunch(vg.tail_exec[fl][q], g.stream));
         HIP_CHECK(hipEventRecord(p->slot_ev[q], g.stream));
         p->prm_ahead = true;
+        return fl;
     };
     int tail_q = -1;  // the slot this token's results come through, if any
     if (spec_hit) {
@@ -338,7 +372,7 @@ static bool try_decode_plan(ggml_cgraph *gr, bool defer_wait = false) {
         p->replays++;
     } else if (tail) {
         tail_q = 0;
-        launch_tail(av, tail_q);
+        launch_tail(av, tail_q, false);
         p->replays++;
     } else if (use_graph) {
         VariantGraphs &vg = p->graphs[av];
@@ -363,7 +397,9 @@ static bool try_decode_plan(ggml_cgraph *gr, bool defer_wait = false) {
     token_results_queue(p);
     if (tail) {  // the next token, before the host waits for this one
         const int av2 = attn_variant(m, p, m.n_past + 2);
-        launch_tail(av2, tail_q ^ 1);
+        // (directly behind this token's own tail graph: launched above, or — a hit — behind the previous token with nothing of this
+        // plan in between; whatever else comes between two evaluations finds the ahead run pending and takes it back)
+        g.spec.prepared = launch_tail(av2, tail_q ^ 1, true) == TAIL_AHEAD;
         g.spec.pending = true;
         g.spec.plan = p;
         g.spec.n_past = m.n_past + 1;

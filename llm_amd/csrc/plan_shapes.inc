@@ -69,19 +69,25 @@ struct LlamaMatch {
 //   AV_SPLIT  plain wq|wk|wv launch, then the position-split attention over all CUs (k_attn_split_one / the three launches)
 //   AV_FUSED2 / 3 / 4  k_qkv_attn with 2 / 3 / 4 attention workgroups per head (512 positions each: up to 1024 / 1536 / 2048)
 enum { AV_SHORT = 0, AV_SPLIT = 1, AV_FUSED2 = 2, AV_FUSED3 = 3, AV_FUSED4 = 4, AV_COUNT = 5 };
+enum { TAIL_FIRST = 0, TAIL_AHEAD = 1 };  // flavours of a greedy token's graph (VariantGraphs::tail_exec)
 static inline int av_heads_split(int av) { return av >= AV_FUSED2 ? av : 1; }
 // the captured graphs of ONE attention variant of a plan (they freeze which kernels run: options and the device's slot count at capture time)
 struct VariantGraphs {
     hipGraph_t graph = nullptr;
     hipGraphExec_t exec = nullptr, exec2 = nullptr;  // exec2: a second instance of the same graph — a chain alternates so that a launch never waits for its own previous run
     // a greedy token's graph: the same launches aimed at result set q (DecodePlan::res_logits), then k_token_tail into slot q; tokens alternate
-    // between the two, so a launch never waits for its own previous run and never writes what the host or a device-side reader still reads
-    hipGraph_t tail_graph[2] = {nullptr, nullptr};
-    hipGraphExec_t tail_exec[2] = {nullptr, nullptr};
+    // between the two, so a launch never waits for its own previous run and never writes what the host or a device-side reader still reads.
+    // Two flavours each, [flavour][q] (tail_prepares: the block-format plan on the big workgroups under option tail_prepare; every other
+    // plan has flavour TAIL_FIRST alone, with its k_kv_row_save in front):
+    //   TAIL_FIRST  behind a host upload of the parameters: get_rows and the RoPE table, the layers, the tail — which prepares the next token
+    //   TAIL_AHEAD  directly behind another tail graph of the same plan, and only there: the layers on what that graph's tail prepared
+    //               (row, table, epoch, saved cache rows), the tail; its first kernel is the layer-0 launch
+    hipGraph_t tail_graph[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
+    hipGraphExec_t tail_exec[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
     void drop() {
-        for (hipGraphExec_t e : {exec, exec2, tail_exec[0], tail_exec[1]})
+        for (hipGraphExec_t e : {exec, exec2, tail_exec[0][0], tail_exec[0][1], tail_exec[1][0], tail_exec[1][1]})
             if (e) (void)hipGraphExecDestroy(e);
-        for (hipGraph_t gr : {graph, tail_graph[0], tail_graph[1]})
+        for (hipGraph_t gr : {graph, tail_graph[0][0], tail_graph[0][1], tail_graph[1][0], tail_graph[1][1]})
             if (gr) (void)hipGraphDestroy(gr);
         *this = VariantGraphs{};
     }
@@ -164,6 +170,9 @@ struct DecodePlan {
     hipEvent_t slot_ev[2] = {nullptr, nullptr};  // recorded directly behind the launch of the graph that fills the slot
     size_t slot_emb_off = 0, slot_id_off = 0;
     __half *kv_save[2] = {nullptr, nullptr};  // per parity: the cache rows of the position that graph writes, as they were before (k_kv_row_save)
+    float *xnext = nullptr;  // the NEXT token's embedding row, dequantized by k_token_tail (TailPrep): layer 0's input in a TAIL_AHEAD graph.  Not xa:
+                             // that is the residual stream and the last layer's output, which readers of the finished token may still look at
+    bool open_prepared = false;  // set only while a TAIL_AHEAD graph is captured: plan_launch_all has no get_rows and no k_rope_table, layer 0 reads xnext
     bool prm_ahead = false;  // a token tail has moved the device's DecParams past m's token: whoever replays the plan next uploads them first
     int *chain_out = nullptr;   // ggml_hip_decode_greedy_chain / ggml_hip_decode_batch_greedy: sampled ids (device)
     int *chain_ring = nullptr;  // ... of one K-token graph launch (option chain_k), copied into chain_out behind it
