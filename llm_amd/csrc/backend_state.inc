@@ -61,6 +61,8 @@ struct Timing {
 // GGML_HIP_VIRTUAL_DEVICES=n maps n slots onto the visible devices round-robin (several slots on ONE GPU: how the split is
 // tested on a 1-GPU box).  One thread drives a SLOT at a time (Backend::mu); slots run concurrently.
 #define GGML_HIP_MAX_BACKENDS 16
+struct DecodePlan;  // plan_shapes.inc
+struct PrepMatch;   // plan_run.inc
 struct Backend {
     int slot = 0;
     bool inited = false;
@@ -105,7 +107,7 @@ struct Backend {
     // kernels that actually ran
     enum { MMQ_K_PLAIN, MMQ_K_DMA_P8, MMQ_K_W16_P8, MMQ_K_W16_256, MMQ_K_I8, MMQ_K_COUNT };
     uint64_t stat_mmq[MMQ_K_COUNT] = {0, 0, 0, 0, 0};
-    void *chain_plan = nullptr;            // the plan a greedy chain may continue (set by its last single-token run)
+    DecodePlan *chain_plan = nullptr;      // the plan a greedy chain may continue (set by its last single-token run)
     ggml_cgraph *chain_graph = nullptr;    // ... and the cgraph that run executed
     bool pending_wait = false;  // a decode plan was launched by graph_compute_begin and not yet waited for
     bool pending_light = false;  // ... and it was a multi-token plan run: no in-launch waits (no error word to look at); if it also queued no read-back, the next begin() need not wait for it
@@ -120,7 +122,7 @@ struct Backend {
     bool greedy_hint = false;  // ggml_hip_expect_greedy_next: consumed by the next graph of this slot
     struct Spec {
         bool pending = false;
-        void *plan = nullptr;
+        DecodePlan *plan = nullptr;
         int n_past = 0, av = 0;
         int parity = 0;                 // the result set / slot the ahead run fills
         bool prepared = false;          // it ran as a TAIL_AHEAD graph: no prologue launch (stat tail_prepared_tokens on a hit)
@@ -129,19 +131,19 @@ struct Backend {
         int cooldown = 0;               // evaluations to sit out after a miss
     } spec;
     struct TailWait {                   // the token whose results the host takes from a slot: set by begin, consumed by token_finish
-        void *plan = nullptr;
+        DecodePlan *plan = nullptr;
         int q = 0;
         void *logits_dst = nullptr, *emb_dst = nullptr;
         bool staged = false;            // its parameters went up through the small staging: free again once its event is done
     } tail;
-    void *res_plan = nullptr;           // the most recently evaluated plan while its last token sits in result set 1 (DecodePlan::cur_set); null: set 0 everywhere (res_settle)
+    DecodePlan *res_plan = nullptr;     // the most recently evaluated plan while its last token sits in result set 1 (DecodePlan::cur_set); null: set 0 everywhere (res_settle)
     uint64_t stat_tail_tokens = 0, stat_result_copies = 0, stat_tail_hits = 0, stat_tail_misses = 0;
     uint64_t stat_spec_hits = 0, stat_spec_misses = 0, stat_tail_prepared_tokens = 0;
     // in-launch hand-offs that gave up (kernels/common.h GRAN_SPIN_MAX): the plan's error word travels back with every token's
     // results (plan_run.inc token_finish)
     unsigned *ferr_pin = nullptr;    // the slot's error word: pinned HOST memory the kernels write straight into (zero-copy; written
                                      // only when a wait gives up, read by the host behind every token's result wait: no copy per token)
-    void *ferr_plan = nullptr;       // the DecodePlan whose token is in flight
+    DecodePlan *ferr_plan = nullptr; // the plan whose token is in flight
     int opt_fused_fallback = 1, opt_fused_rearm_tokens = 256;
     uint64_t fused_rearm_at = 0;     // stat_plan_tokens at which the saved options come back (0 = nothing to restore)
     uint64_t fused_rearm_stretch = 0;
@@ -153,7 +155,7 @@ struct Backend {
     uint64_t ns_match = 0, ns_launch = 0, ns_wait = 0, ns_compute = 0, ns_mirror = 0, stat_mirror_bytes = 0;
     size_t dead_shadow_bytes = 0;
     uint64_t arena_seen = 0;  // the last event of the process-wide arena log this slot has applied (sync_arenas)
-    void *prep = nullptr;  // PrepMatch (plan_run.inc): the match of a graph handed over by ggml_hip_graph_prepare, waiting for its begin()
+    PrepMatch *prep = nullptr;  // (plan_run.inc) the match of a graph handed over by ggml_hip_graph_prepare, waiting for its begin()
     int opt_gen = 0;       // bumped by every ggml_hip_set_option: a remembered match does not outlive an option change
     int xcd_labels = -1;  // 1: workgroups with equal blockIdx mod 8 of a one-workgroup-per-CU launch share an XCD, eight labels on eight XCDs (xcd_labels_ok); -1 = not looked yet
     void *hot_line = nullptr;  // 256 zero bytes on the device: what the dummy ring steps of the K plan's mat-vecs read (kernels/kquant_big.h KBigArgs::hot)

@@ -8,10 +8,15 @@ struct PlanStats {
 // What a launch sequence is asked to enqueue, and its books.  `mask` selects kernel classes (bit k = GGML_HIP_KCLASS k) and
 // `kind_mask` mat-vec kinds (bit k = GGML_HIP_KKIND k: 0 wq|wk|wv, 1 wo, 2 w1|w3, 3 w2, 4 lm_head): the roofline leg replays one
 // class or kind alone to time it without event overhead.  `st`, when given, takes the launches and algorithmic bytes per class.
+// The last two are what the capture of a greedy token's graph chooses (plan_run.inc launch_tail); every other launch of a plan — an
+// evaluation's plain graph, the re-run, the chain, a roofline leg — keeps their defaults.
 struct LaunchCtx {
     unsigned mask = ~0u, kind_mask = ~0u;
     PlanStats *st = nullptr;
     int ts_idx = 0;  // timeline: one timeline_wgs x 8 x int64 record per big launch, in launch order
+    int out_set = 0;        // the result set the final norm / lm_head aim at (DecodePlan::res_logits): 1 only in a graph of parity 1
+    bool prepared = false;  // a TAIL_AHEAD graph of the block-format plan (tail_prepares: no other plan is asked for it): plan_launch_all
+                            // opens with neither get_rows nor k_rope_table, layer 0 reads xnext
     bool want(int k, double bytes) {
         if (!(mask & (1u << k))) return false;
         if (st) {
@@ -149,12 +154,12 @@ static void for_each_type_run(const KWeight *const *ws, int n, F &&f) {
         i = j;
     }
 }
-// where a plan's final norm and lm_head write: result set 0, or set 1 while a greedy token's graph of parity 1 is captured (see DecodePlan::out_set)
+// where a plan's final norm and lm_head write: result set 0, or set 1 in a greedy token's graph of parity 1 (LaunchCtx::out_set)
 struct ResultDst {
     float *emb;
     char *logits;
 };
-static ResultDst plan_result_dst(const DecodePlan *p) { return ResultDst{p->res_emb(p->out_set), p->res_logits(p->out_set)}; }
+static ResultDst plan_result_dst(const DecodePlan *p, const LaunchCtx &cx) { return ResultDst{p->res_emb(cx.out_set), p->res_logits(cx.out_set)}; }
 // ---- what the K plan and the F16 plan share: everything around their mat-vecs ----
 // The opening: the residual rows from the hand-off buffer, or the embedding rows of the N token ids (`embed`: the plan's own get_rows
 // launch, embed_bytes per element its books); then one (cos, sin) table per column, 128 floats apart (batch: each at its own session's position)
@@ -255,7 +260,7 @@ static void plan_launch_all(DecodePlan *p, int av, LaunchCtx cx) {
     // boundary on the token's path: ~5 us per stage boundary and side)
     // A greedy token's graph launched directly behind another one (TAIL_AHEAD, plan_run.inc) opens with neither launch below: that
     // graph's k_token_tail has left this token's row in p->xnext, its table in p->rope and its epoch open
-    const bool prepared = p->open_prepared;
+    const bool prepared = cx.prepared;
     if (m.wte && !prepared)  // token embedding: get_rows(wte, embd)
         cx.other((double)E * 4.6, [&] {
             hipLaunchKernelGGL(k_get_rows_q, dim3((unsigned)((nbE + 255) / 256), 1), dim3(256), 0, g.stream, p->wte,
@@ -397,7 +402,7 @@ static void plan_launch_all(DecodePlan *p, int av, LaunchCtx cx) {
         }
     }
     if (!m.output) return;  // not the last stage: the last layer's w2 launch has written the residual into the outgoing hand-off buffer
-    const ResultDst dst = plan_result_dst(p);
+    const ResultDst dst = plan_result_dst(p, cx);
     if (!big) rmsq(p->xa, p->norm, dst.emb);  // final norm: f32 copy for OutputRequest.embeddings + Q8 for lm_head
     {
         DecMmvqArgs a;
@@ -621,7 +626,7 @@ static void plan_launch_k(DecodePlan *p, int av, LaunchCtx cx) {
         mmvq(3, {&w.w2}, {p->xa}, p->xb, kgate ? RowSrc{KX_F32, p->gate, nullptr, 0.0f, nullptr} : RowSrc{KX_SILU_MUL, p->gate, p->k_g3, 0.0f, nullptr});
     }
     if (plan_hand_on(p, cx)) return;
-    const ResultDst dst = plan_result_dst(p);
+    const ResultDst dst = plan_result_dst(p, cx);
     norm_quant(p->xa, p->norm, dst.emb);  // all N rows: f32 copy (embedding_result node) + Q8_K
     mmvq(4, {&p->k_output}, {(float *)dst.logits}, nullptr, RowSrc{KX_NORM, p->xa, p->norm, m.eps, dst.emb});
 }
@@ -757,7 +762,7 @@ static void plan_launch_f16(DecodePlan *p, int av, LaunchCtx cx, bool batch = fa
         }
     }
     if (plan_hand_on(p, cx)) return;
-    const ResultDst dst = plan_result_dst(p);
+    const ResultDst dst = plan_result_dst(p, cx);
     float *d1[1] = {(float *)dst.logits};
     cx.mmvq(4, mv_bytes({&p->f_output}, E, 4.0),
             [&] { launch_f16(1, &p->f_output, d1, E, RowSrc{KX_NORM, p->xa, p->norm, m.eps, dst.emb}, nullptr, N); });

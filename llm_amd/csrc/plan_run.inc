@@ -1,5 +1,9 @@
 // plan_run.inc — running a plan: capture and replay of its hipGraphs, the results' way to the host, the speculative next token,
-// the re-run of a token whose in-launch hand-off gave up, the greedy chain.
+// the re-run of a token whose in-launch hand-off gave up, the greedy chain, the batched step.
+// An evaluation (try_decode_plan) is the sequence of its steps, each a function of its own in front of it: resolve_plan (the graph's
+// match and plan), settle_ahead (was the run ahead of the caller this evaluation?), host_dec_params (the parameters the host uploads;
+// also the re-run's and the chain's), run_prompt_plan, plan_sync_dev_gen, launch_tail (a greedy token's graph; result set and
+// prepared opening are arguments of the launch sequence, LaunchCtx), plain_graph (every other graph) and count_token_forms.
 // begin capture, launch, end capture, instantiate: the launches of `launch` as a graph and its first executable instance
 template <class F>
 static void capture_into(hipGraph_t *graph, hipGraphExec_t *exec, F &&launch) {
@@ -8,10 +12,40 @@ static void capture_into(hipGraph_t *graph, hipGraphExec_t *exec, F &&launch) {
     HIP_CHECK(hipStreamEndCapture(g.stream, graph));
     HIP_CHECK(hipGraphInstantiate(exec, *graph, nullptr, nullptr, 0));
 }
+// the plain graphs of attention variant v (result set 0, no tail), captured from `launch` if there is none yet: .exec is ready to launch
+template <class F>
+static VariantGraphs &plain_graph(DecodePlan *p, int v, F &&launch) {
+    VariantGraphs &vg = p->graphs[v];
+    if (!vg.exec) capture_into(&vg.graph, &vg.exec, launch);
+    return vg;
+}
+// room for n sampled ids in the plan's chain_out
+static void chain_out_reserve(DecodePlan *p, int n) {
+    if (p->chain_cap >= n) return;
+    if (p->chain_out) (void)hipFree(p->chain_out);
+    p->chain_cap = std::max(n, 256);
+    HIP_CHECK(hipMalloc((void **)&p->chain_out, (size_t)p->chain_cap * 4));
+}
+// The DecParams the host uploads for the evaluation m describes: its position, its token ids (a prompt plan takes its ids from p_tok),
+// each checked against the vocabulary.  pos_tail is n_past for every caller.  Only k_token_tail with a TailPrep reads it, i.e. a
+// tail graph; the two callers that are not an evaluation (token_finish's re-run, decode_greedy_chain) have cancelled the ahead run
+// and cleared prm_ahead, so the next tail graph is launched by an evaluation that found nothing pending: behind its own upload.
+static DecParams host_dec_params(const LlamaMatch &m) {
+    DecParams hp;
+    memset(&hp, 0, sizeof(hp));
+    hp.n_past = hp.pos_tail[0] = hp.pos_tail[1] = m.n_past;
+    hp.token = m.embd ? ((const int32_t *)m.embd->data)[0] : 0;
+    for (int i = 0; i < 32; i++) {
+        hp.tokens[i] = (m.embd && i < m.N && !m.prompt) ? ((const int32_t *)m.embd->data)[i] : 0;
+        if (m.wte && (hp.tokens[i] < 0 || hp.tokens[i] >= m.wte->ne[1])) die("token id %d out of range", hp.tokens[i]);
+    }
+    return hp;
+}
 // results the host reads, queued behind the evaluation's kernels: the logits (CPU-backend node, model/common.rs:6-38) ...
+static bool emb_rows_fit(const LlamaMatch &m) { return (size_t)m.N * (size_t)m.E * 4 <= ((size_t)128 << 10); }  // (what is mirrored at all, see queue_results)
 static bool emb_row_mirrored(const DecodePlan *p) {
     const LlamaMatch &m = p->m;
-    return m.embedding && m.embedding->data && p->emb_out && (size_t)m.N * (size_t)m.E * 4 <= ((size_t)128 << 10);
+    return m.embedding && m.embedding->data && p->emb_out && emb_rows_fit(m);
 }
 static void queue_results(const DecodePlan *p) {
     const LlamaMatch &m = p->m;
@@ -39,7 +73,7 @@ static void token_results_queue(DecodePlan *p) {
 // a greedy token's results: out of the slot its graph's k_token_tail filled, into the caller's memory (as d2h_finish moves its staging);
 // the id that came with them is the token the device fed the run it started behind that graph
 static void tail_deliver(const Backend::TailWait &tw) {
-    DecodePlan *tp = (DecodePlan *)tw.plan;
+    const DecodePlan *tp = tw.plan;
     const char *sl = tp->slot[tw.q];
     if (tw.logits_dst) memcpy(tw.logits_dst, sl, (size_t)tp->m.V * 4);
     if (tw.emb_dst) memcpy(tw.emb_dst, sl + tp->slot_emb_off, (size_t)tp->m.E * 4);
@@ -52,13 +86,13 @@ static void token_finish(bool can_rerun = true) {
     const Backend::TailWait tw = g.tail;
     g.tail = Backend::TailWait{};
     if (tw.plan) {  // the token's own event, recorded directly behind its graph: whatever runs behind that is not waited for
-        HIP_CHECK(hipEventSynchronize(((DecodePlan *)tw.plan)->slot_ev[tw.q]));
+        HIP_CHECK(hipEventSynchronize(tw.plan->slot_ev[tw.q]));
         if (!stg.pending.empty()) d2h_finish();
         else if (tw.staged) stg.small_off = 0;
     } else {
         d2h_finish();
     }
-    DecodePlan *p = (DecodePlan *)g.ferr_plan;
+    DecodePlan *p = g.ferr_plan;
     g.ferr_plan = nullptr;
     if (!p || !g.ferr_pin || !*(volatile unsigned *)g.ferr_pin) {
         if (tw.plan) tail_deliver(tw);
@@ -70,9 +104,7 @@ static void token_finish(bool can_rerun = true) {
     static const char *what =
         "an attention workgroup of k_qkv_attn / k_attn_split_one gave up waiting for rows of its own launch (these launches "
         "need all their workgroups resident at once: is another process, or a CU mask, holding compute units of this GPU?)";
-    bool live = false;
-    for (auto *q : g_plans) live = live || q == p;
-    if (!live) die("%s", what);
+    if (!live_plan(p)) die("%s", what);
     const bool whole = p->m.wte && p->m.output;  // a stage's garbage residual has already been handed on
     if (!g.opt_fused_fallback || !can_rerun || !whole || p->m.N != 1)
         die("%s; set GGML_HIP_FUSE_ATTN=0 GGML_HIP_ATTN_ONE=0 to run the two-launch forms", what);
@@ -92,11 +124,7 @@ static void token_finish(bool can_rerun = true) {
     for (auto *q : g_plans) drop_plan_graphs(q);
     const LlamaMatch &m = p->m;
     {   // this token and position again: a speculative run queued behind the token has moved the device's parameters on
-        DecParams hp;
-        memset(&hp, 0, sizeof(hp));
-        hp.n_past = m.n_past;
-        hp.token = m.embd ? ((const int32_t *)m.embd->data)[0] : 0;
-        hp.tokens[0] = hp.token;
+        const DecParams hp = host_dec_params(m);
         h2d_small((char *)p->prm, &hp, sizeof(hp));
         g.stat_result_copies++;
         p->prm_ahead = false;
@@ -128,7 +156,7 @@ struct PrepMatch {
 };
 static bool prepare_decode_plan(ggml_cgraph *gr) {
     if (!g.prep) g.prep = new PrepMatch();
-    PrepMatch *pm = (PrepMatch *)g.prep;
+    PrepMatch *pm = g.prep;
     pm->gr = nullptr;
     if (!g.opt_plan || !g.opt_prepare || !gr) return false;
     LlamaMatch m;
@@ -203,6 +231,147 @@ static TailPrep tail_prep_args(const DecodePlan *p, int q) {
     tp.pos_in = &p->prm->pos_tail[q]; tp.pos_out = &p->prm->pos_tail[q ^ 1];
     return tp;
 }
+// ---- an evaluation's steps, in the order try_decode_plan takes them ----
+// The plan for this graph, holding its match (copied into m as well); null: not a graph for the plans (nothing has been enqueued but
+// perhaps the graph's leaves).  A match made ahead of time (ggml_hip_graph_prepare) is taken if nothing has happened since that could
+// change the answer; otherwise the matcher, the leaves' upload, the K-prompt fallback and find_or_build_plan.
+static DecodePlan *resolve_plan(ggml_cgraph *gr, LlamaMatch &m) {
+    if (PrepMatch *pm = g.prep) {
+        DecodePlan *p = nullptr;
+        if (pm->gr == gr && pm->arena_seq == g_arena_seq.load(std::memory_order_acquire) && pm->opt_gen == g.opt_gen &&
+            pm->wgen == g_dev_wgen[g.device & 63].load(std::memory_order_acquire))
+            p = live_plan(pm->p);
+        pm->gr = nullptr;
+        if (p) {
+            m = pm->m;
+            p->m = m;
+            g.stat_prepared_tokens++;
+            return p;
+        }
+    }
+    if (!match_llama_decode(gr, m)) return nullptr;
+    if (!plan_weights_resident(m)) {
+        // first evaluation of a model: tok_embeddings is a leaf the caller never offloads (models/llama lib.rs:52);
+        // upload the graph's leaves the way the generic executor would, then look again
+        upload_inputs(gr);
+        if (!plan_weights_resident(m)) return nullptr;
+    }
+    if (m.prompt && m.kquant && !k_prompt_weights(m, nullptr)) {  // (before anything is built or launched) no room for the copies:
+        if (m.N > MULTI_MAX_N) return nullptr;                     // the node-by-node executor, or for up to 31 tokens the K plan's chunks
+        LlamaMatch m2;
+        tl_k_prompt_off = true;
+        const bool ok = match_llama_decode(gr, m2);
+        tl_k_prompt_off = false;
+        if (!ok) return nullptr;
+        m = m2;
+    }
+    return find_or_build_plan(m, plan_signature(m));
+}
+// One token ahead: is this evaluation the one the device is already running?  Returns the parity of the ahead run on a hit, -1
+// otherwise.  A miss keeps the books, pauses the guessing and takes the run's cache rows back; whatever is not a hit settles the
+// result sets (behind the ahead run, in front of whatever this evaluation writes).
+static int settle_ahead(DecodePlan *p, const LlamaMatch &m) {
+    int hit_q = -1;
+    if (g.spec.pending) {
+        g.spec.pending = false;
+        const bool same = g.spec.plan == p && m.N == 1 && !m.prompt && m.embd && m.n_past == g.spec.n_past &&
+                          attn_variant(m, p, m.n_past + 1) == g.spec.av && g.opt_graph && !g.timing.on;
+        // the id the device fed that run came to the host with the previous token's slot (tail_deliver): no synchronisation here
+        const bool hit = same && g.spec.fed_id_valid && g.spec.fed_id == ((const int32_t *)m.embd->data)[0];
+        // (spec_hits / spec_misses are the books of option speculate_next, the guess about an unchanged caller; a caller that announced
+        // itself shows in tail_tokens and in result_copies standing still)
+        if (hit) {
+            hit_q = g.spec.parity;
+            if (g.opt_speculate_next) g.stat_spec_hits++;
+            if (g.spec.prepared) g.stat_tail_prepared_tokens++;
+        } else {
+            if (g.opt_speculate_next) g.stat_spec_misses++;
+            g.spec.cooldown = 8;  // a sampler that does not take the first maximum: stop guessing for a while
+            spec_take_back();     // the cache rows it wrote go back to what they were, behind it and in front of this evaluation
+        }
+        (hit ? g.stat_tail_hits : g.stat_tail_misses)++;
+    }
+    if (hit_q < 0) res_settle();
+    return hit_q;
+}
+// The prompt plan's evaluation behind the parameter upload: all token ids, launched eagerly, the logits queued, the books, the wait
+// (or, defer_wait, the note for ggml_hip_graph_compute_end: a batch of feed_prompt behind which another follows).
+static void run_prompt_plan(DecodePlan *p, const LlamaMatch &m, bool defer_wait, uint64_t t0, uint64_t t1) {
+    if (m.wte) {
+        const int32_t *ids = (const int32_t *)m.embd->data;
+        for (int i = 0; i < m.N; i++)
+            if (ids[i] < 0 || ids[i] >= m.wte->ne[1]) die("token id %d out of range", ids[i]);
+        h2d_small((char *)p->p_tok, ids, (size_t)m.N * 4);
+    }
+    plan_launch_prompt(p);
+    if (m.logits && m.logits->backend == GGML_BACKEND_CPU)  // (the logits alone: the embedding rows of a batch stay on the device, queue_results)
+        d2h_queue(m.logits->data, p->logits_out, (size_t)m.V * m.N * 4);
+    const uint64_t t2 = now_ns();
+    g.ns_match += t1 - t0;
+    g.ns_launch += t2 - t1;
+    g.stat_prompt_plan_tokens += (uint64_t)m.N;
+    if (defer_wait) {
+        g.pending_wait = true;
+        g.pending_light = true;
+        return;
+    }
+    d2h_finish();
+    g.ns_wait += now_ns() - t2;
+}
+// graphs captured while this device had another number of slots on it froze another choice of kernels: dropped behind what they run
+static void plan_sync_dev_gen(DecodePlan *p) {
+    const uint64_t dgen = g_dev_gen[g.device & 63].load(std::memory_order_relaxed);
+    if (p->dev_gen == dgen) return;
+    if (p->dev_gen) {
+        HIP_CHECK(hipStreamSynchronize(g.stream));
+        drop_plan_graphs(p);
+    }
+    p->dev_gen = dgen;
+}
+// Launches the plan's greedy-token graph of variant v, parity q — result set q, slot q — and records the slot's event directly behind
+// it; returns its flavour.  `ahead`: directly behind another tail graph of this plan (the evaluation's second launch and nothing
+// else); where the plan's tails prepare the next token (tail_prepares) that is flavour TAIL_AHEAD, whose first kernel is the layer-0
+// launch, and every other launch is TAIL_FIRST.  The set and the prepared opening reach the launch sequence as its arguments.
+static int launch_tail(DecodePlan *p, int v, int q, bool ahead) {
+    const LlamaMatch &m = p->m;
+    const bool prep = tail_prepares(p);
+    const int fl = prep && ahead ? TAIL_AHEAD : TAIL_FIRST;
+    VariantGraphs &vg = p->graphs[v];
+    if (!vg.tail_exec[fl][q]) {
+        tail_slots(p);
+        LaunchCtx cx;
+        cx.out_set = q;
+        cx.prepared = fl == TAIL_AHEAD;
+        capture_into(&vg.tail_graph[fl][q], &vg.tail_exec[fl][q], [&] {
+            if (!prep)  // (a preparing tail has saved this graph's rows already, or the token was asked for and is never taken back)
+                hipLaunchKernelGGL(k_kv_row_save, dim3(kv_row_grid(p)), dim3(256), 0, g.stream, (const DecParams *)p->prm, (const __half *)p->mem_k,
+                                   (const __half *)p->mem_v, p->kv_save[q], (int)m.L, (int)m.C, (int)m.Egqa);
+            plan_launch_decode(p, v, cx);
+            const TailPrep tp = prep ? tail_prep_args(p, q) : TailPrep{};
+            hipLaunchKernelGGL(k_token_tail, dim3(token_tail_grid(prep, (long)m.L * m.Egqa)), dim3(1024), 0, g.stream, (const float *)p->res_logits(q), (int)m.V,
+                               emb_rows_fit(m) ? (const float *)p->res_emb(q) : (const float *)nullptr, (int)m.E, p->prm, p->slot[q], (int)p->slot_emb_off,
+                               (int)p->slot_id_off, tp);
+        });
+    }
+    HIP_CHECK(hipGraphLaunch(vg.tail_exec[fl][q], g.stream));
+    HIP_CHECK(hipEventRecord(p->slot_ev[q], g.stream));
+    p->prm_ahead = true;
+    return fl;
+}
+// the per-token counters of the forms a single-token or chunk evaluation ran as (the greedy chain keeps fewer of them: see there)
+static void count_token_forms(const LlamaMatch &m, int av) {
+    const bool long_ctx = av == AV_SPLIT;
+    g.stat_plan_tokens += (uint64_t)m.N;
+    if (long_ctx) g.stat_split_tokens++;
+    if (m.N == 1 && !long_ctx) {
+        const FusedShape fs = fused_qkv_shape(m, av_heads_split(av));
+        if (fs.ok) g.stat_fused_tokens++;
+        if (fs.ok && fs.wo) g.stat_fused_wo_tokens++;
+        if (fs.ok && fs.affine) g.stat_fused_affine_tokens++;
+    }
+    if (av >= AV_FUSED2) g.stat_fused_heads_tokens++;
+    if (m.kquant) g.stat_kplan_tokens += (uint64_t)m.N;
+}
 static bool try_decode_plan(ggml_cgraph *gr, bool defer_wait = false) {
     g.chain_plan = nullptr;  // any new graph ends the chainable state; a single-token plan run re-arms it below
     const bool greedy_next = g.greedy_hint;  // ggml_hip_expect_greedy_next spoke of THIS graph, whatever it turns out to be
@@ -219,113 +388,25 @@ static bool try_decode_plan(ggml_cgraph *gr, bool defer_wait = false) {
     }
     const uint64_t t0 = now_ns();
     LlamaMatch m;
-    DecodePlan *p = nullptr;
-    if (PrepMatch *pm = (PrepMatch *)g.prep) {  // matched ahead of time (ggml_hip_graph_prepare) and nothing has happened since that could change the answer?
-        if (pm->gr == gr && pm->arena_seq == g_arena_seq.load(std::memory_order_acquire) && pm->opt_gen == g.opt_gen &&
-            pm->wgen == g_dev_wgen[g.device & 63].load(std::memory_order_acquire))
-            for (auto *q : g_plans)
-                if (q == pm->p) p = q;
-        if (p) {
-            m = pm->m;
-            p->m = m;
-            g.stat_prepared_tokens++;
-        }
-        pm->gr = nullptr;
-    }
-    if (!p) {
-        if (!match_llama_decode(gr, m)) return false;
-        if (!plan_weights_resident(m)) {
-            // first evaluation of a model: tok_embeddings is a leaf the caller never offloads (models/llama lib.rs:52);
-            // upload the graph's leaves the way the generic executor would, then look again
-            upload_inputs(gr);
-            if (!plan_weights_resident(m)) return false;
-        }
-        if (m.prompt && m.kquant && !k_prompt_weights(m, nullptr)) {  // (before anything is built or launched) no room for the copies:
-            if (m.N > MULTI_MAX_N) return false;                       // the node-by-node executor, or for up to 31 tokens the K plan's chunks
-            LlamaMatch m2;
-            tl_k_prompt_off = true;
-            const bool ok = match_llama_decode(gr, m2);
-            tl_k_prompt_off = false;
-            if (!ok) return false;
-            m = m2;
-        }
-        p = find_or_build_plan(m, plan_signature(m));
-    }
+    DecodePlan *p = resolve_plan(gr, m);
+    if (!p) return false;
     const uint64_t t1 = now_ns();
-    // ---- one token ahead: is this evaluation the one the device is already running? ----
-    bool spec_hit = false;
-    int hit_q = 0;
-    if (g.spec.pending) {
-        g.spec.pending = false;
-        const bool same = g.spec.plan == (void *)p && m.N == 1 && !m.prompt && m.embd && m.n_past == g.spec.n_past &&
-                          attn_variant(m, p, m.n_past + 1) == g.spec.av && g.opt_graph && !g.timing.on;
-        // the id the device fed that run came to the host with the previous token's slot (tail_deliver): no synchronisation here
-        spec_hit = same && g.spec.fed_id_valid && g.spec.fed_id == ((const int32_t *)m.embd->data)[0];
-        hit_q = g.spec.parity;
-        // (spec_hits / spec_misses are the books of option speculate_next, the guess about an unchanged caller; a caller that announced
-        // itself shows in tail_tokens and in result_copies standing still)
-        if (spec_hit) {
-            if (g.opt_speculate_next) g.stat_spec_hits++;
-            if (g.spec.prepared) g.stat_tail_prepared_tokens++;
-        } else {
-            if (g.opt_speculate_next) g.stat_spec_misses++;
-            g.spec.cooldown = 8;  // a sampler that does not take the first maximum: stop guessing for a while
-            spec_take_back();     // the cache rows it wrote go back to what they were, behind it and in front of this evaluation
-        }
-        (spec_hit ? g.stat_tail_hits : g.stat_tail_misses)++;
-    }
-    if (!spec_hit) res_settle();  // (behind the ahead run, in front of whatever this evaluation writes)
-    DecParams hp;
-    hp.n_past = m.n_past;
-    hp.token = m.embd ? ((const int32_t *)m.embd->data)[0] : 0;
-    hp.store_at = hp.pad1 = 0;
-    hp.pos_tail[0] = hp.pos_tail[1] = m.n_past;
-    for (int i = 0; i < 32; i++) {
-        hp.tokens[i] = (m.embd && i < m.N && !m.prompt) ? ((const int32_t *)m.embd->data)[i] : 0;
-        if (m.wte && (hp.tokens[i] < 0 || hp.tokens[i] >= m.wte->ne[1])) die("token id %d out of range", hp.tokens[i]);
-    }
+    const int hit_q = settle_ahead(p, m);
+    const bool spec_hit = hit_q >= 0;
+    const DecParams hp = host_dec_params(m);  // (checks the ids on a hit too)
     if (!spec_hit) {  // (a hit: the device wrote exactly these itself)
         h2d_small((char *)p->prm, &hp, sizeof(hp));
         p->prm_ahead = false;
         if (m.N == 1 && !m.prompt) g.stat_result_copies++;
     }
-    if (m.prompt) {  // prompt plan: all token ids, launched eagerly
-        if (m.wte) {
-            const int32_t *ids = (const int32_t *)m.embd->data;
-            for (int i = 0; i < m.N; i++)
-                if (ids[i] < 0 || ids[i] >= m.wte->ne[1]) die("token id %d out of range", ids[i]);
-            h2d_small((char *)p->p_tok, ids, (size_t)m.N * 4);
-        }
-        plan_launch_prompt(p);
-        if (m.logits && m.logits->backend == GGML_BACKEND_CPU)  // (the logits alone: the embedding rows of a batch stay on the device, queue_results)
-            d2h_queue(m.logits->data, p->logits_out, (size_t)m.V * m.N * 4);
-        const uint64_t t2p = now_ns();
-        g.ns_match += t1 - t0;
-        g.ns_launch += t2p - t1;
-        g.stat_prompt_plan_tokens += (uint64_t)m.N;
-        if (defer_wait) {  // ggml_hip_graph_compute_begin (a batch of feed_prompt behind which another follows)
-            g.pending_wait = true;
-            g.pending_light = true;
-            return true;
-        }
-        d2h_finish();
-        g.ns_wait += now_ns() - t2p;
+    if (m.prompt) {
+        run_prompt_plan(p, m, defer_wait, t0, t1);
         return true;
     }
     const bool use_graph = g.opt_graph && !g.timing.on;
-    {   // graphs captured while this device had another number of slots on it froze another choice of kernels
-        const uint64_t dgen = g_dev_gen[g.device & 63].load(std::memory_order_relaxed);
-        if (p->dev_gen != dgen) {
-            if (p->dev_gen) {
-                HIP_CHECK(hipStreamSynchronize(g.stream));
-                drop_plan_graphs(p);
-            }
-            p->dev_gen = dgen;
-        }
-    }
+    plan_sync_dev_gen(p);
     // the attention variant for this context length (a graph each of the same plan)
     const int av = attn_variant(m, p, m.n_past + 1);
-    const bool long_ctx = av == AV_SPLIT;
     auto launch = [&] {
         if (m.N > 1 && !m.kquant && !m.f16w)
             plan_launch_multi(p);
@@ -337,47 +418,16 @@ static bool try_decode_plan(ggml_cgraph *gr, bool defer_wait = false) {
     if (g.spec.cooldown > 0) g.spec.cooldown--;
     const bool tail = g.opt_token_tail && (g.opt_speculate_next || greedy_next) && g.spec.cooldown == 0 && use_graph && m.N == 1 && m.logits && m.wte &&
                       m.output && m.embd && p->logits_alt && m.n_past + 2 < m.C;
-    // The plan's graph of variant v, parity q: result set q, slot q, and the slot's event directly behind it.  `ahead`: launched directly
-    // behind another tail graph of this plan — the second call below and nothing else; where the plan's tails prepare the next token
-    // (tail_prepares) that is flavour TAIL_AHEAD, whose first kernel is the layer-0 launch, and every other launch is TAIL_FIRST.
-    const bool prep = tail_prepares(p);
-    const auto launch_tail = [&](int v, int q, bool ahead) {
-        VariantGraphs &vg = p->graphs[v];
-        const int fl = prep && ahead ? TAIL_AHEAD : TAIL_FIRST;
-        if (!vg.tail_exec[fl][q]) {
-            tail_slots(p);
-            p->out_set = q;
-            p->open_prepared = fl == TAIL_AHEAD;
-            capture_into(&vg.tail_graph[fl][q], &vg.tail_exec[fl][q], [&] {
-                if (!prep)  // (a preparing tail has saved this graph's rows already, or the token was asked for and is never taken back)
-                    hipLaunchKernelGGL(k_kv_row_save, dim3(kv_row_grid(p)), dim3(256), 0, g.stream, (const DecParams *)p->prm, (const __half *)p->mem_k,
-                                       (const __half *)p->mem_v, p->kv_save[q], (int)m.L, (int)m.C, (int)m.Egqa);
-                plan_launch_decode(p, v);
-                const TailPrep tp = prep ? tail_prep_args(p, q) : TailPrep{};
-                hipLaunchKernelGGL(k_token_tail, dim3(token_tail_grid(prep, (long)m.L * m.Egqa)), dim3(1024), 0, g.stream, (const float *)p->res_logits(q), (int)m.V,
-                                   (size_t)m.E * 4 <= ((size_t)128 << 10) ? (const float *)p->res_emb(q) : (const float *)nullptr, (int)m.E, p->prm, p->slot[q],
-                                   (int)p->slot_emb_off, (int)p->slot_id_off, tp);
-            });
-            p->out_set = 0;
-            p->open_prepared = false;
-        }
-        HIP_CHECK(hipGraphLaunch(vg.tail_exec[fl][q], g.stream));
-        HIP_CHECK(hipEventRecord(p->slot_ev[q], g.stream));
-        p->prm_ahead = true;
-        return fl;
-    };
     int tail_q = -1;  // the slot this token's results come through, if any
     if (spec_hit) {
         tail_q = hit_q;  // already enqueued behind the previous token (same plan, position, token and attention variant): only the host's part is missing
         p->replays++;
     } else if (tail) {
         tail_q = 0;
-        launch_tail(av, tail_q, false);
+        launch_tail(p, av, tail_q, false);
         p->replays++;
     } else if (use_graph) {
-        VariantGraphs &vg = p->graphs[av];
-        if (!vg.exec) capture_into(&vg.graph, &vg.exec, launch);
-        HIP_CHECK(hipGraphLaunch(vg.exec, g.stream));
+        HIP_CHECK(hipGraphLaunch(plain_graph(p, av, launch).exec, g.stream));
         p->replays++;
     } else {
         launch();
@@ -399,7 +449,7 @@ static bool try_decode_plan(ggml_cgraph *gr, bool defer_wait = false) {
         const int av2 = attn_variant(m, p, m.n_past + 2);
         // (directly behind this token's own tail graph: launched above, or — a hit — behind the previous token with nothing of this
         // plan in between; whatever else comes between two evaluations finds the ahead run pending and takes it back)
-        g.spec.prepared = launch_tail(av2, tail_q ^ 1, true) == TAIL_AHEAD;
+        g.spec.prepared = launch_tail(p, av2, tail_q ^ 1, true) == TAIL_AHEAD;
         g.spec.pending = true;
         g.spec.plan = p;
         g.spec.n_past = m.n_past + 1;
@@ -410,17 +460,8 @@ static bool try_decode_plan(ggml_cgraph *gr, bool defer_wait = false) {
     const uint64_t t2 = now_ns();
     g.ns_match += t1 - t0;
     g.ns_launch += t2 - t1;
-    g.stat_plan_tokens += (uint64_t)m.N;
-    if (long_ctx) g.stat_split_tokens++;
-    if (m.N == 1 && !long_ctx) {
-        const FusedShape fs = fused_qkv_shape(m, av_heads_split(av));
-        if (fs.ok) g.stat_fused_tokens++;
-        if (fs.ok && fs.wo) g.stat_fused_wo_tokens++;
-        if (fs.ok && fs.affine) g.stat_fused_affine_tokens++;
-    }
-    if (av >= AV_FUSED2) g.stat_fused_heads_tokens++;
-    if (m.kquant) g.stat_kplan_tokens += (uint64_t)m.N;
-    g.chain_plan = (m.N == 1 && m.logits && m.wte) ? (void *)p : nullptr;  // whole model, one token: chainable
+    count_token_forms(m, av);
+    g.chain_plan = (m.N == 1 && m.logits && m.wte) ? p : nullptr;  // whole model, one token: chainable
     g.chain_graph = gr;
     if (defer_wait) {  // ggml_hip_graph_compute_begin: the caller overlaps host work, then ..._end() waits
         g.pending_wait = true;
@@ -440,18 +481,13 @@ static bool try_decode_plan(ggml_cgraph *gr, bool defer_wait = false) {
 // the precondition does not hold (the caller then decodes token by token).
 static int decode_greedy_chain(ggml_cgraph *last, int n, int32_t *out_tokens, float *last_logits) {
     finish_pending();
-    DecodePlan *p = (DecodePlan *)g.chain_plan;
+    DecodePlan *p = live_plan(g.chain_plan);
     if (!p || g.chain_graph != last || n < 1) return -1;
-    bool live = false;
-    for (auto *q : g_plans) live = live || q == p;
     const LlamaMatch &m = p->m;
-    if (!live || m.N != 1 || !m.logits || !m.wte || m.n_past + 1 + n > m.C) return -1;
+    if (m.N != 1 || !m.logits || !m.wte || m.n_past + 1 + n > m.C) return -1;
     if (p->prm_ahead) {  // a token tail has moved the parameters on (and a run ahead of the caller may be in flight): back to the last evaluated token
         if (!m.embd) return -1;
-        DecParams hp;
-        memset(&hp, 0, sizeof(hp));
-        hp.n_past = m.n_past;
-        hp.token = hp.tokens[0] = ((const int32_t *)m.embd->data)[0];
+        const DecParams hp = host_dec_params(m);
         h2d_small((char *)p->prm, &hp, sizeof(hp));
         p->prm_ahead = false;
     }
@@ -459,11 +495,7 @@ static int decode_greedy_chain(ggml_cgraph *last, int n, int32_t *out_tokens, fl
     // the first argmax reads the set the last evaluated token sits in; every replay below writes set 0
     const float *first_logits = (const float *)plan_cur_logits(p);
     g.res_plan = nullptr;
-    if (p->chain_cap < n) {
-        if (p->chain_out) (void)hipFree(p->chain_out);
-        p->chain_cap = std::max(n, 256);
-        HIP_CHECK(hipMalloc((void **)&p->chain_out, (size_t)p->chain_cap * 4));
-    }
+    chain_out_reserve(p, n);
     if (!p->chain_ring) HIP_CHECK(hipMalloc((void **)&p->chain_ring, 64 * 4));
     const bool use_graph = g.opt_graph && !g.timing.on && p->any_captured();
     int i0 = 0;
@@ -501,11 +533,11 @@ static int decode_greedy_chain(ggml_cgraph *last, int n, int32_t *out_tokens, fl
                            p->prm, p->chain_out + i);
         // the token of step i sits at position n_past + 1 + i; same rule as try_decode_plan for the attention variant
         const int av = attn_variant(m, p, m.n_past + 1 + i + 1);
+        // (the chain's books are not count_token_forms': no fused_wo_tokens, fused_affine_tokens or split_tokens — values tests read; left as they are)
         if (av != AV_SPLIT && fused_qkv_shape(m, av_heads_split(av)).ok) g.stat_fused_tokens++;
         if (av >= AV_FUSED2) g.stat_fused_heads_tokens++;
         if (use_graph) {
-            VariantGraphs &vg = p->graphs[av];
-            if (!vg.exec) capture_into(&vg.graph, &vg.exec, [&] { plan_launch_decode(p, av); });  // the chain crossed into a variant no evaluation has captured yet
+            VariantGraphs &vg = plain_graph(p, av, [&] { plan_launch_decode(p, av); });  // (captured here: the chain crossed into a variant no evaluation has captured yet)
             if (!vg.exec2) HIP_CHECK(hipGraphInstantiate(&vg.exec2, vg.graph, nullptr, nullptr, 0));
             HIP_CHECK(hipGraphLaunch((i & 1) ? vg.exec2 : vg.exec, g.stream));
         } else {
@@ -544,7 +576,7 @@ static int decode_batch_steps(ggml_cgraph *const *graphs, int B, int n_steps, in
     spec_cancel();
     g.chain_plan = nullptr;
     res_settle();  // (every column's results go to its graph's own nodes: result set 0)
-    if (PrepMatch *pm = (PrepMatch *)g.prep) pm->gr = nullptr;
+    if (g.prep) g.prep->gr = nullptr;
     if (!g.opt_plan || !g.opt_plan_batch || (chain && !g.opt_plan_batch_chain)) return -1;
     if (n_steps < 1 || n_steps > BATCH_CHAIN_MAX_STEPS) return -1;
     const uint64_t t0 = now_ns();
@@ -590,7 +622,7 @@ static int decode_batch_steps(ggml_cgraph *const *graphs, int B, int n_steps, in
     for (int c = 0; c < B; c++) mb.n_past = std::max(mb.n_past, ms[(size_t)c].n_past);
     p->m.n_past = mb.n_past;  // (the attention's byte count for the timing books)
     const uint64_t t1 = now_ns();
-    DecParams hp;
+    DecParams hp;  // (not host_dec_params: one id per column, from B matches; a batched step has no tail graph to read pos_tail)
     BatchCols hb;
     memset(&hp, 0, sizeof(hp));
     memset(&hb, 0, sizeof(hb));
@@ -608,9 +640,7 @@ static int decode_batch_steps(ggml_cgraph *const *graphs, int B, int n_steps, in
     h2d_small((char *)p->bcols, &hb, sizeof(hb));
     const auto step = [&] {
         if (g.opt_graph && !g.timing.on) {
-            VariantGraphs &vg = p->graphs[AV_SHORT];
-            if (!vg.exec) capture_into(&vg.graph, &vg.exec, [&] { plan_launch_batch(p); });
-            HIP_CHECK(hipGraphLaunch(vg.exec, g.stream));
+            HIP_CHECK(hipGraphLaunch(plain_graph(p, AV_SHORT, [&] { plan_launch_batch(p); }).exec, g.stream));
             p->replays++;
         } else {
             plan_launch_batch(p);
@@ -619,11 +649,7 @@ static int decode_batch_steps(ggml_cgraph *const *graphs, int B, int n_steps, in
     step();
     if (n_steps > 1) {  // the device samples every column and moves the step's parameters on; ids of step i at chain_out[(i - 1) * B ..]
         const int n_ids = (n_steps - 1) * B;
-        if (p->chain_cap < n_ids) {
-            if (p->chain_out) (void)hipFree(p->chain_out);
-            p->chain_cap = std::max(n_ids, 256);
-            HIP_CHECK(hipMalloc((void **)&p->chain_out, (size_t)p->chain_cap * 4));
-        }
+        chain_out_reserve(p, n_ids);
         for (int i = 1; i < n_steps; i++) {
             hipLaunchKernelGGL(k_batch_argmax_next, dim3((unsigned)B), dim3(1024), 0, g.stream, (const float *)p->logits_out, (int)ms[0].V, p->prm,
                                p->bcols, p->chain_out + (size_t)(i - 1) * B);

@@ -10,16 +10,19 @@
 //   chunk's launches with a per-column position and cache.
 // The first three and the last are captured once in a hipGraph per attention variant and replayed for the following tokens with only
 // {n_past, token} changing in a device-side parameter block.  One file per concern, included in this order from
-// backend_executor.inc inside hip_backend.hip's anonymous namespace; nothing needs a forward declaration:
+// backend_executor.inc inside hip_backend.hip's anonymous namespace; the only forward declarations are DecodePlan and PrepMatch in
+// front of Backend (backend_state.inc), whose fields name the slot's plans by their type:
 //   plan_shapes.inc  LlamaMatch, DecodePlan (the layers' matrices as LayerMats<format>, the captured graphs as one VariantGraphs
-//                    per attention variant) and every "which kernel, which grid for which shape" decision (plain host functions
-//                    the matcher, the launchers, the run loop and the test hooks of backend_tools.inc all call)
+//                    per attention variant), live_plan (what a remembered plan pointer still names) and every "which kernel, which
+//                    grid for which shape" decision (plain host functions the matcher, the launchers, the run loop and the test
+//                    hooks of backend_tools.inc all call)
 //   plan_match.inc   the structural graph matcher
 //   plan_build.inc   weights, signature and activation pool of a plan (plan_pool_layout: every buffer declared once)
 //   plan_decode.inc  the single-token launchers: plan_launch_all, plan_launch_k, plan_launch_f16, and what the last two share
 //                    around their mat-vecs (plan_open_rows, plan_attn_f32, plan_hand_on)
 //   plan_prompt.inc  plan_launch_multi, plan_launch_batch, prompt_attention, plan_launch_prompt
-//   plan_run.inc     capture and replay, speculation, the fused-timeout re-run, the greedy chain, the batched step
+//   plan_run.inc     capture and replay, an evaluation as its steps (try_decode_plan), speculation, the fused-timeout re-run, the
+//                    greedy chain, the batched step
 //
 // The matcher is structural (it follows src[] pointers from the logits back to get_rows and checks every view's
 // shape/stride/offset against the KV-cache layout), so any graph that is not exactly the reference's LLaMA
@@ -162,7 +165,6 @@ struct DecodePlan {
     char *logits_alt = nullptr;
     float *emb_alt = nullptr;
     int cur_set = 0;  // the set of the last evaluated token (meaningful while the slot's res_plan is this plan; set 0 otherwise)
-    int out_set = 0;  // the set plan_launch_* aim the final norm / lm_head at: 1 only while a graph of parity 1 is captured
     char *res_logits(int q) const { return q ? logits_alt : logits_out; }
     float *res_emb(int q) const { return emb_out ? (q ? emb_alt : emb_out) : nullptr; }
     // the two result slots of the greedy tokens, pinned host memory k_token_tail stores into: logits | embedding row | id
@@ -172,7 +174,6 @@ struct DecodePlan {
     __half *kv_save[2] = {nullptr, nullptr};  // per parity: the cache rows of the position that graph writes, as they were before (k_kv_row_save)
     float *xnext = nullptr;  // the NEXT token's embedding row, dequantized by k_token_tail (TailPrep): layer 0's input in a TAIL_AHEAD graph.  Not xa:
                              // that is the residual stream and the last layer's output, which readers of the finished token may still look at
-    bool open_prepared = false;  // set only while a TAIL_AHEAD graph is captured: plan_launch_all has no get_rows and no k_rope_table, layer 0 reads xnext
     bool prm_ahead = false;  // a token tail has moved the device's DecParams past m's token: whoever replays the plan next uploads them first
     int *chain_out = nullptr;   // ggml_hip_decode_greedy_chain / ggml_hip_decode_batch_greedy: sampled ids (device)
     int *chain_ring = nullptr;  // ... of one K-token graph launch (option chain_k), copied into chain_out behind it
@@ -199,6 +200,13 @@ struct DecodePlan {
 
 std::vector<DecodePlan *> g_plans_[GGML_HIP_MAX_BACKENDS];  // per slot: a plan holds device addresses
 #define g_plans (g_plans_[g.slot])
+// the plan of this slot that `p` names, or null: a pointer remembered across evaluations (Backend::chain_plan, res_plan, ferr_plan,
+// spec.plan, PrepMatch::p) may have outlived its plan (drop_all_plans) and is only compared here, never dereferenced
+static DecodePlan *live_plan(const DecodePlan *p) {
+    for (auto *q : g_plans)
+        if (q == p) return q;
+    return nullptr;
+}
 
 void drop_plan_graphs(DecodePlan *p) {
     for (VariantGraphs &v : p->graphs) v.drop();
@@ -217,14 +225,14 @@ void destroy_plan(DecodePlan *p) {
         if (p->slot[q]) (void)hipHostFree(p->slot[q]);
         if (p->slot_ev[q]) (void)hipEventDestroy(p->slot_ev[q]);
     }
-    if (g.res_plan == (void *)p) g.res_plan = nullptr;
+    if (g.res_plan == p) g.res_plan = nullptr;
     delete p;
 }
 // The device address a reader of node `t` reads: the tensor's own image, unless it lies in result set 0 of the plan whose last
 // evaluated token sits in set 1 — then the same offset of set 1 (DecodePlan::cur_set).
 char *result_dev_ptr(const ggml_tensor *t) {
     char *d = dev_ptr(t);
-    DecodePlan *p = (DecodePlan *)g.res_plan;
+    const DecodePlan *p = g.res_plan;
     if (!p || p->cur_set != 1 || !p->logits_alt) return d;
     const size_t lb = (size_t)p->m.V * 4, eb = (size_t)p->m.E * 4;
     if (p->logits_out && d >= p->logits_out && d < p->logits_out + lb) return p->logits_alt + (d - p->logits_out);
@@ -235,24 +243,20 @@ char *result_dev_ptr(const ggml_tensor *t) {
 // into set 0, the graph nodes' own images, behind whatever ran ahead into set 0 — readers of that session's nodes keep seeing its
 // last evaluated token however many other sessions, chunks or generic graphs run on the slot afterwards.  Never on the hit path.
 static void res_settle() {
-    DecodePlan *p = nullptr;
-    for (auto *q : g_plans)
-        if ((void *)q == g.res_plan) p = q;
+    DecodePlan *p = live_plan(g.res_plan);
     g.res_plan = nullptr;
     if (!p || p->cur_set != 1 || !p->logits_alt || !p->logits_out) return;
     HIP_CHECK(hipMemcpyAsync(p->logits_out, p->logits_alt, (size_t)p->m.V * 4, hipMemcpyDeviceToDevice, g.stream));
     if (p->emb_out) HIP_CHECK(hipMemcpyAsync(p->emb_out, p->emb_alt, (size_t)p->m.E * 4, hipMemcpyDeviceToDevice, g.stream));
     p->cur_set = 0;
 }
-static inline char *plan_cur_logits(const DecodePlan *p) { return p->res_logits(g.res_plan == (const void *)p ? p->cur_set : 0); }
+static inline char *plan_cur_logits(const DecodePlan *p) { return p->res_logits(g.res_plan == p ? p->cur_set : 0); }
 // A token the device ran ahead of its caller is in flight or finished unused: nothing of it may be taken for a result any more (its
 // plan's buffers are about to be reused, dropped, or replayed for a measurement).  The stream is drained so that it is over.
 // the K/V rows the pending ahead run wrote (a position its session has not reached) as they were before it, behind it on the stream
 static inline int kv_row_grid(const DecodePlan *p) { return (int)std::min<int64_t>(256, ((int64_t)p->m.L * p->m.Egqa + 255) / 256); }
 static void spec_take_back() {
-    DecodePlan *p = nullptr;
-    for (auto *q : g_plans)
-        if ((void *)q == g.spec.plan) p = q;
+    DecodePlan *p = live_plan(g.spec.plan);
     if (!p || !p->kv_save[g.spec.parity] || !p->mem_k) return;
     hipLaunchKernelGGL(k_kv_row_restore, dim3(kv_row_grid(p)), dim3(256), 0, g.stream, g.spec.n_past, p->mem_k, p->mem_v,
                        (const __half *)p->kv_save[g.spec.parity], (int)p->m.L, (int)p->m.C, (int)p->m.Egqa);
@@ -269,9 +273,7 @@ void spec_cancel() {
 // the next evaluation runs on the new contents)
 void spec_guard_read(const char *d, size_t n) {
     if (!g.spec.pending) return;
-    DecodePlan *p = nullptr;
-    for (auto *q : g_plans)
-        if ((void *)q == g.spec.plan) p = q;
+    const DecodePlan *p = live_plan(g.spec.plan);
     if (!p || !p->mem_k) return;
     const size_t kvb = (size_t)p->m.L * p->m.C * p->m.Egqa * 2;
     const char *k = (const char *)p->mem_k, *v = (const char *)p->mem_v;
