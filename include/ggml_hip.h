@@ -619,6 +619,23 @@ GGML_API int ggml_hip_decode_batch(struct ggml_cgraph *const *graphs, int n_grap
  * plan_batch_chain off.  n_steps == 1 is ggml_hip_decode_batch (out_ids may be NULL).  NULL, a B out of range or such an n_steps is
  * refused before any device is touched. */
 GGML_API int ggml_hip_decode_batch_greedy(struct ggml_cgraph *const *graphs, int n_graphs, int n_steps, int32_t *out_ids);
+/* The same chain with the shape of the reference's default sampler (crates/llm-base/src/samplers.rs:97-188) on the device instead
+ * of the first maximum: repetition penalty `penalty` over a session's last 64 tokens, top-k `k`, top-p `top_p`, temperature
+ * `temperature`, one xorshift64* draw — in the arithmetic of llm_amd/csrc/kernels/sampler_math.h (IEEE basic operations only, no
+ * library exponential), which llm_sample_exact restates on the host: a caller that samples each step with that function from the
+ * logits ggml_hip_decode_batch leaves draws the same ids, and the logits and K/V memory agree bit for bit.
+ * windows [B][64]: session c's last window_n[c] (0 .. 64) tokens, oldest first, INCLUDING the token its graph evaluates; the device
+ * keeps the window moving over the ids it samples.  rng [B]: the sessions' generator states, advanced by n_steps - 1 draws each on
+ * return.  out_ids as above.  Returns 0, or -1 with nothing executed and no generator moved: whatever
+ * ggml_hip_decode_batch_greedy declines, k < 1, k > 256 or k > n_vocab, temperature <= 0, top_p <= 0, penalty <= 0, a window
+ * entry outside the vocabulary, option plan_batch_sample off.  Counted in batch_sample_steps / batch_sample_tokens (not in
+ * batch_chain_*). */
+typedef struct {
+    int32_t k;
+    float top_p, temperature, penalty;
+} ggml_hip_sampler;
+GGML_API int ggml_hip_decode_batch_sampled(struct ggml_cgraph *const *graphs, int n_graphs, int n_steps, const ggml_hip_sampler *params,
+                                           const int32_t *windows, const int32_t *window_n, uint64_t *rng, int32_t *out_ids);
 /* Top-k prefilter of a logits row on the device: the k (<= 1024, <= ne0) largest entries of row `row` of
  * the f32 tensor `t` — a node of the caller's most recent ggml_graph_compute, normally the logits — as (value, id) pairs,
  * value descending, lower id first among equal values, followed by the entries of `extra_ids` (n_extra ids, e.g. the
@@ -701,6 +718,14 @@ GGML_API int ggml_hip_debug_token_tail_prepare(const float *logits, int V, const
  * prm_out[34] = n_past, token, tokens[0..32) and pos_out[8] as the kernel left them.  0, or -1 for arguments it cannot take. */
 GGML_API int ggml_hip_debug_batch_tail(const float *logits, int B, int V, const int32_t *pos_in, const int32_t *tokens_in,
                                        int32_t *ids_out, int32_t *prm_out, int32_t *pos_out);
+/* Test hook: k_batch_sample_next (the kernel between two steps of ggml_hip_decode_batch_sampled) alone, n_draws (1 .. 4096) launches
+ * on the same rows.  logits [B][V], B = 1..8; pos_in[8] / tokens_in[32] as above; hist [8][64] and hist_n[8] are the columns'
+ * history rings (hist_n[c] tokens pushed so far: min(hist_n, 64) entries hold, the next goes to slot hist_n % 64), rng[8] the
+ * generator states: all three in / out, all 8 entries.  Out: ids_out [n_draws][B], prm_out[34], pos_out[8] as above.  0, or -1
+ * for arguments it cannot take (the sampler parameters ggml_hip_decode_batch_sampled declines among them). */
+GGML_API int ggml_hip_debug_batch_sample(const float *logits, int B, int V, const ggml_hip_sampler *params, const int32_t *pos_in,
+                                         const int32_t *tokens_in, int32_t *hist, int32_t *hist_n, uint64_t *rng, int n_draws,
+                                         int32_t *ids_out, int32_t *prm_out, int32_t *pos_out);
 /* Test hook: w (quantized 2-D weight with a device copy) times N = 2..8 host rows x [N][K] through k_mmq_cols as the
  * multi-token plan launches it; out [N][M].  0, or -1 when that plan would not run this shape on k_mmq_cols. */
 GGML_API int ggml_hip_debug_mul_mat_cols(const struct ggml_tensor *w, const float *x, float *out, int N);

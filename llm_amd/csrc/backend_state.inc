@@ -86,7 +86,7 @@ struct Backend {
     size_t ws_off = 0;  // offset in the last chunk
     Timing timing;
     int opt_fuse = 1, opt_plan = 1, opt_plan_k = 1, opt_plan_multi = 1, opt_plan_prompt = 1, opt_graph = 1, opt_big = 1, opt_kbig = 1;
-    int opt_chain_k = 0, opt_prepare = 1, opt_plan_batch = 1, opt_plan_f16 = 1, opt_plan_batch_chain = 1;
+    int opt_chain_k = 0, opt_prepare = 1, opt_plan_batch = 1, opt_plan_f16 = 1, opt_plan_batch_chain = 1, opt_plan_batch_sample = 1;
     int opt_fuse_attn = 1, opt_fuse_wo = 1, opt_warm_mb = 24, opt_affine = 1;
     int opt_act_quant = 0, opt_mmq_i8 = 0;
     int opt_mmq_min = 32, opt_k_prompt_min = 12, opt_mmq_fuse = 3, opt_mmq_cols = 1, opt_mmq_t256 = 1, opt_attn_fused = 1;
@@ -102,6 +102,7 @@ struct Backend {
     uint64_t stat_plan_tokens = 0, stat_generic_graphs = 0, stat_split_tokens = 0, stat_prompt_plan_tokens = 0, stat_fused_tokens = 0, stat_kplan_tokens = 0, stat_fused_heads_tokens = 0, stat_fused_wo_tokens = 0, stat_fused_affine_tokens = 0, stat_prepared_tokens = 0;
     uint64_t stat_alibi_fused = 0;
     uint64_t stat_batch_tokens = 0, stat_batch_steps = 0, stat_batch_chain_steps = 0, stat_batch_chain_tokens = 0;
+    uint64_t stat_batch_sample_steps = 0, stat_batch_sample_tokens = 0;
     uint64_t stat_flash_attn_nodes = 0;
     // prompt-GEMM launches by kernel (ggml_hip_get_stat("mmq_launches_<name>")): bench.py labels its MFMA roofline with the
     // kernels that actually ran
@@ -193,6 +194,9 @@ static const OptRow g_options[] = {
     // ggml_hip_decode_batch_greedy: n greedy steps of those sessions with the argmax on the device, the step's graph replayed (0: it
     // answers -1, the caller takes n single steps).  It shapes no plan: the chain replays the graph of ggml_hip_decode_batch.
     {"plan_batch_chain", &Backend::opt_plan_batch_chain, OPT_ENV},
+    // ggml_hip_decode_batch_sampled: the same chain with the top-k / top-p / temperature sampler on the device (0: it answers -1, the
+    // caller samples on the host and takes single steps).  It shapes no plan either.
+    {"plan_batch_sample", &Backend::opt_plan_batch_sample, OPT_ENV},
     {"graph", &Backend::opt_graph, OPT_ENV},                          // replay the plan from a captured hipGraph
     {"big", &Backend::opt_big, OPT_ENV | OPT_DROPS},                  // decode mat-vec as one wave of 1024-thread workgroups (kernels/decode_big.h)
     // K plan: its decode mat-vecs as one wave of 1024-thread workgroups that stage the activation themselves (kernels/kquant_big.h)
@@ -301,6 +305,8 @@ static const StatRow g_counters[] = {
     {"batch_decode_steps", &Backend::stat_batch_steps},           // ... and the steps
     {"batch_chain_steps", &Backend::stat_batch_chain_steps},      // ... those of them that ran on device-sampled tokens (ggml_hip_decode_batch_greedy: all but a call's first)
     {"batch_chain_tokens", &Backend::stat_batch_chain_tokens},    // ... and their tokens
+    {"batch_sample_steps", &Backend::stat_batch_sample_steps},    // batched steps that ran on tokens the device SAMPLED (ggml_hip_decode_batch_sampled: all but a call's first; not in batch_chain_*)
+    {"batch_sample_tokens", &Backend::stat_batch_sample_tokens},  // ... and their tokens
     {"cols_warm_launches", &Backend::stat_cols_warm_launches},    // chunk-plan norm launches that carried warming workgroups (ColsWarm), counted when enqueued or captured
     {"fused_rearms", &Backend::stat_fused_rearms},                // times the fused forms came back after a clean stretch behind a give-up
     {"spec_hits", &Backend::stat_spec_hits},                      // evaluations that found their results already running (option speculate_next)

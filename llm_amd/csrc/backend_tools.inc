@@ -724,6 +724,20 @@ int ggml_hip_decode_batch_greedy(struct ggml_cgraph *const *graphs, int n_graphs
     return r;
 }
 
+int ggml_hip_decode_batch_sampled(struct ggml_cgraph *const *graphs, int n_graphs, int n_steps, const ggml_hip_sampler *params,
+                                  const int32_t *windows, const int32_t *window_n, uint64_t *rng, int32_t *out_ids) {
+    if (!graphs || n_graphs < 2 || n_graphs > BATCH_COLS_MAX || n_steps < 1 || n_steps > BATCH_CHAIN_MAX_STEPS) return -1;  // (before any device is touched)
+    if (!params || !windows || !window_n || !rng || (n_steps > 1 && !out_ids)) return -1;
+    for (int i = 0; i < n_graphs; i++)
+        if (!graphs[i]) return -1;
+    SlotLock lk;
+    const uint64_t t0 = now_ns();
+    const BatchSample smp = {params, windows, window_n, rng};
+    const int r = decode_batch_steps(graphs, n_graphs, n_steps, out_ids, true, &smp);
+    g.ns_compute += now_ns() - t0;
+    return r;
+}
+
 // ---- test hook: k_batch_argmax_next alone (tests/test_batch_chain_gpu.py) ----
 // logits [B][V], pos_in[8] and tokens_in[32] go to the device as a step's BatchCols::pos and DecParams::tokens (n_past = pos_in[0],
 // token = tokens_in[0]); the kernel runs once on B workgroups.  Out: ids_out[B], prm_out[34] = n_past, token, tokens[0..32),
@@ -764,6 +778,78 @@ int ggml_hip_debug_batch_tail(const float *logits, int B, int V, const int32_t *
     prm_out[1] = hp.token;
     for (int i = 0; i < 32; i++) prm_out[2 + i] = hp.tokens[i];
     for (int i = 0; i < BATCH_COLS_MAX; i++) pos_out[i] = hb.pos[i];
+    HIP_CHECK(hipFree(d));
+    return 0;
+}
+
+// ---- test hook: k_batch_sample_next alone (tests/test_batch_sample_gpu.py) ----
+// As above, with the columns' rings, counts and generator states (8 entries each, in / out) and n_draws launches on the same rows.
+int ggml_hip_debug_batch_sample(const float *logits, int B, int V, const ggml_hip_sampler *params, const int32_t *pos_in,
+                                const int32_t *tokens_in, int32_t *hist, int32_t *hist_n, uint64_t *rng, int n_draws, int32_t *ids_out,
+                                int32_t *prm_out, int32_t *pos_out) {
+    if (!logits || B < 1 || B > BATCH_COLS_MAX || V < 1 || !params || !pos_in || !tokens_in || !hist || !hist_n || !rng || !ids_out ||
+        !prm_out || !pos_out || n_draws < 1 || n_draws > BATCH_CHAIN_MAX_STEPS)
+        return -1;
+    if (params->k < 1 || params->k > SAMPLER_K_MAX || params->k > V || !(params->temperature > 0.0f) || !(params->top_p > 0.0f) ||
+        !(params->penalty > 0.0f))
+        return -1;
+    for (int c = 0; c < BATCH_COLS_MAX; c++) {
+        if (hist_n[c] < 0) return -1;
+        for (int i = 0; i < std::min(hist_n[c], SAMPLER_WINDOW); i++)
+            if (c < B && (hist[c * SAMPLER_WINDOW + i] < 0 || hist[c * SAMPLER_WINDOW + i] >= V)) return -1;
+    }
+    SlotLock lk;
+    ensure_init();
+    finish_pending();
+    const size_t lb = ((size_t)B * V * 4 + 255) & ~(size_t)255, sb = (sizeof(SampleCols) + 255) & ~(size_t)255;
+    const size_t ib = ((size_t)n_draws * B * 4 + 255) & ~(size_t)255;
+    char *d = nullptr;
+    dev_malloc((void **)&d, lb + 1024 + sb + ib, "debug batch sample");
+    DecParams *dp = (DecParams *)(d + lb);
+    BatchCols *db = (BatchCols *)(d + lb + 256);
+    unsigned long long *dr = (unsigned long long *)(d + lb + 768);
+    SampleCols *ds = (SampleCols *)(d + lb + 1024);
+    int *dids = (int *)(d + lb + 1024 + sb);
+    static_assert(sizeof(DecParams) <= 256 && sizeof(BatchCols) <= 512 && BATCH_COLS_MAX * 8 <= 256, "debug batch sample: layout");
+    DecParams hp;
+    BatchCols hb;
+    SampleCols hs;
+    memset(&hp, 0, sizeof(hp));
+    memset(&hb, 0, sizeof(hb));
+    memset(&hs, 0, sizeof(hs));
+    for (int i = 0; i < 32; i++) hp.tokens[i] = tokens_in[i];
+    for (int i = 0; i < BATCH_COLS_MAX; i++) hb.pos[i] = pos_in[i];
+    hp.n_past = pos_in[0];
+    hp.token = tokens_in[0];
+    memcpy(hs.hist, hist, sizeof(hs.hist));
+    memcpy(hs.hist_n, hist_n, sizeof(hs.hist_n));
+    hs.k = params->k;
+    hs.top_p = params->top_p;
+    hs.temperature = params->temperature;
+    hs.penalty = params->penalty;
+    HIP_CHECK(hipStreamSynchronize(g.stream));
+    HIP_CHECK(hipMemcpy(d, logits, (size_t)B * V * 4, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(dp, &hp, sizeof(hp), hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(db, &hb, sizeof(hb), hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(ds, &hs, sizeof(hs), hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(dr, rng, BATCH_COLS_MAX * 8, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemset(dids, 0xff, (size_t)n_draws * B * 4));
+    for (int i = 0; i < n_draws; i++)
+        hipLaunchKernelGGL(k_batch_sample_next, dim3((unsigned)B), dim3(1024), 0, g.stream, (const float *)d, V, dp, db, ds, dr,
+                           dids + (size_t)i * B);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipStreamSynchronize(g.stream));
+    HIP_CHECK(hipMemcpy(ids_out, dids, (size_t)n_draws * B * 4, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(&hp, dp, sizeof(hp), hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(&hb, db, sizeof(hb), hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(&hs, ds, sizeof(hs), hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(rng, dr, BATCH_COLS_MAX * 8, hipMemcpyDeviceToHost));
+    prm_out[0] = hp.n_past;
+    prm_out[1] = hp.token;
+    for (int i = 0; i < 32; i++) prm_out[2 + i] = hp.tokens[i];
+    for (int i = 0; i < BATCH_COLS_MAX; i++) pos_out[i] = hb.pos[i];
+    memcpy(hist, hs.hist, sizeof(hs.hist));
+    memcpy(hist_n, hs.hist_n, sizeof(hs.hist_n));
     HIP_CHECK(hipFree(d));
     return 0;
 }

@@ -49,6 +49,7 @@
 #include "kernels/gemm_f16.h"
 #include "kernels/ops.h"
 #include "kernels/decode.h"
+#include "kernels/sample.h"
 #include "kernels/decode_big.h"
 #include "kernels/decode_fused.h"
 #include "kernels/decode_big8.h"

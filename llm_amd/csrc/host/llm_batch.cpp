@@ -15,4 +15,12 @@ int llm_infer_next_tokens_greedy_batch(llm_model *m, llm_session *const *session
 int llm_infer_tokens_greedy_batch_device(llm_model *m, llm_session *const *sessions, int B, int n, int32_t *out_ids) {
     return llm_infer_tokens_greedy_batch_via(ggml_hip_decode_batch, ggml_hip_decode_batch_greedy, m, sessions, B, n, out_ids);
 }
+int llm_infer_next_tokens_sampled_batch(llm_model *m, llm_session *const *sessions, int B, const llm_sampler_params *params, uint64_t *rngs,
+                                        int32_t *out_ids) {
+    return llm_infer_next_tokens_sampled_batch_via(ggml_hip_decode_batch, m, sessions, B, params, rngs, out_ids);
+}
+int llm_infer_tokens_sampled_batch_device(llm_model *m, llm_session *const *sessions, int B, int n, const llm_sampler_params *params,
+                                          uint64_t *rngs, int32_t *out_ids) {
+    return llm_infer_tokens_sampled_batch_via(ggml_hip_decode_batch, ggml_hip_decode_batch_sampled, m, sessions, B, n, params, rngs, out_ids);
+}
 }

@@ -11,6 +11,7 @@
 #include <immintrin.h>
 #endif
 #include "llm_host.h"
+#include "kernels/sampler_math.h"
 
 #include <algorithm>
 #include <atomic>
@@ -1535,6 +1536,120 @@ int llm_infer_tokens_greedy_batch_via(llm_batch_entry step, llm_batch_chain_entr
     }
     for (int k = 0; k < n; k++)
         if (llm_infer_next_tokens_greedy_batch_via(step, m, sessions, B, out_ids + (size_t)k * B) < 0) return -1;
+    return 0;
+}
+// ---- the sampled batched chain's host side.  The sampler is kernels/sampler_math.h — the header k_batch_sample_next compiles — so
+// the ids drawn here and on the device are the same ids.
+static bool sampler_params_ok(const llm_sampler_params *p, size_t V) {
+    return p && p->k >= 1 && (size_t)p->k <= V && p->temperature > 0.0f && p->top_p > 0.0f && p->penalty > 0.0f;
+}
+// One draw by the written spec: the k largest raw logits and the window's tokens (the last 64 of `window`, each id once) as
+// candidates, the window's penalised, the k best kept; top-p; temperature; one xorshift64* step of *rng.  -1 on bad arguments
+// (k outside 1 .. V, a non-positive temperature / top_p / penalty, a window token outside the vocabulary); *rng unmoved then.
+int32_t llm_sample_exact(const float *logits, int V, const int32_t *window, int n_window, const llm_sampler_params *params, uint64_t *rng) {
+    if (!logits || V < 1 || n_window < 0 || (n_window > 0 && !window) || !rng || !sampler_params_ok(params, (size_t)V)) return -1;
+    if (n_window > SAMPLER_WINDOW) {
+        window += n_window - SAMPLER_WINDOW;
+        n_window = SAMPLER_WINDOW;
+    }
+    const int k = params->k;
+    struct Cand { float v; int32_t id; };
+    std::vector<Cand> c;
+    c.reserve((size_t)k + (size_t)n_window);
+    for (int i = 0; i < n_window; i++) {
+        const int32_t id = window[i];
+        if (id < 0 || id >= V) return -1;
+        bool dup = false;
+        for (const Cand &x : c) dup = dup || x.id == id;
+        if (!dup) c.push_back({sampler_penalise(logits[id], params->penalty), id});
+    }
+    const size_t n_win = c.size();
+    std::vector<int32_t> order((size_t)V);
+    for (int i = 0; i < V; i++) order[(size_t)i] = i;
+    std::partial_sort(order.begin(), order.begin() + k, order.end(),
+                      [&](int32_t a, int32_t b) { return logits[a] > logits[b] || (logits[a] == logits[b] && a < b); });
+    for (int i = 0; i < k; i++) {
+        bool in_window = false;
+        for (size_t j = 0; j < n_win; j++) in_window = in_window || c[j].id == order[(size_t)i];
+        if (!in_window) c.push_back({logits[order[(size_t)i]], order[(size_t)i]});
+    }
+    std::sort(c.begin(), c.end(), [](const Cand &a, const Cand &b) { return a.v > b.v || (a.v == b.v && a.id < b.id); });
+    c.resize((size_t)k);  // (the raw top-k alone are k candidates)
+    std::vector<float> q((size_t)k), p((size_t)k);
+    for (int i = 0; i < k; i++) {
+        q[(size_t)i] = sampler_q(c[(size_t)i].v, c[0].v);
+        p[(size_t)i] = sampler_p(c[(size_t)i].v, c[0].v, params->temperature);
+    }
+    return c[(size_t)sampler_pick(q.data(), p.data(), k, params->top_p, rng)].id;
+}
+// the draw for one session: from its last_logits and the last 64 tokens of its history
+static int32_t sample_session(const llm::InferenceSession &s, const llm_sampler_params *params, uint64_t *rng) {
+    std::vector<int32_t> w;
+    const std::vector<llm::TokenId> &h = s.tokens;
+    for (size_t i = h.size() > (size_t)SAMPLER_WINDOW ? h.size() - (size_t)SAMPLER_WINDOW : 0; i < h.size(); i++) w.push_back((int32_t)h[i]);
+    return llm_sample_exact(s.last_logits.data(), (int)s.last_logits.size(), w.data(), (int)w.size(), params, rng);
+}
+// llm_infer_next_tokens_greedy_batch_via with that sampler: every session draws from its own generator (rngs[i]), the id is appended
+// to its history and evaluated in one batched step.  -1: nothing evaluated, no session and no generator moved.
+int llm_infer_next_tokens_sampled_batch_via(llm_batch_entry entry, llm_model *m, llm_session *const *sessions, int B,
+                                            const llm_sampler_params *params, uint64_t *rngs, int32_t *out_ids) {
+    if (!out_ids || !rngs || !batch_sessions_ok(m, sessions, B, 1)) return -1;
+    if (!sampler_params_ok(params, m->llama->hyperparameters.n_vocab)) return -1;
+    std::vector<int32_t> next((size_t)B);
+    std::vector<uint64_t> r(rngs, rngs + B);
+    for (int i = 0; i < B; i++)
+        if ((next[(size_t)i] = sample_session(*sessions[i]->s, params, &r[(size_t)i])) < 0) return -1;
+    const int rc = llm_evaluate_batch_via(entry, m, sessions, next.data(), B, nullptr);
+    if (rc < 0) return -1;
+    for (int i = 0; i < B; i++) {
+        sessions[i]->s->tokens.push_back((llm::TokenId)next[(size_t)i]);
+        out_ids[i] = next[(size_t)i];
+        rngs[i] = r[(size_t)i];
+    }
+    return rc;
+}
+// llm_infer_tokens_greedy_batch_via with that sampler (`chain` = ggml_hip_decode_batch_sampled): the host draws row 0 of out_ids
+// [n][B] as above, the device rows 1 .. n - 1 — each column's window moves on over the ids the device draws, and the generator states
+// come back advanced by n draws in all.  Every session and generator ends as after n calls of the stepped form, which is what runs
+// when there is no chain entry or it declines.  Returns 1 / 0 / -1 as the greedy form.
+int llm_infer_tokens_sampled_batch_via(llm_batch_entry step, llm_batch_sample_entry chain, llm_model *m, llm_session *const *sessions, int B,
+                                       int n, const llm_sampler_params *params, uint64_t *rngs, int32_t *out_ids) {
+    if (!out_ids || !rngs || n < 1 || !batch_sessions_ok(m, sessions, B, (size_t)n)) return -1;
+    if (!sampler_params_ok(params, m->llama->hyperparameters.n_vocab)) return -1;
+    if (chain && B >= 2) {
+        std::vector<ggml_cgraph *> graphs((size_t)B);
+        std::vector<llm::GraphOutputs> outs((size_t)B);
+        std::vector<uint64_t> r(rngs, rngs + B);
+        std::vector<int32_t> first((size_t)B), windows((size_t)B * SAMPLER_WINDOW, 0), window_n((size_t)B);
+        for (int i = 0; i < B; i++)
+            if ((first[(size_t)i] = sample_session(*sessions[i]->s, params, &r[(size_t)i])) < 0) return -1;
+        for (int i = 0; i < B; i++) {
+            graphs[(size_t)i] = m->llama->stage_single(*sessions[i]->s, (llm::TokenId)first[(size_t)i], outs[(size_t)i]);
+            // the window the device starts from: the session's history with this token at its end
+            const std::vector<llm::TokenId> &h = sessions[i]->s->tokens;
+            const size_t keep = std::min(h.size(), (size_t)SAMPLER_WINDOW - 1);
+            int32_t *w = windows.data() + (size_t)i * SAMPLER_WINDOW;
+            for (size_t j = 0; j < keep; j++) w[j] = (int32_t)h[h.size() - keep + j];
+            w[keep] = first[(size_t)i];
+            window_n[(size_t)i] = (int32_t)keep + 1;
+        }
+        std::vector<int32_t> rest((size_t)(n - 1) * (size_t)B + 1);
+        if (chain(graphs.data(), B, n, params, windows.data(), window_n.data(), r.data(), rest.data()) == 0) {
+            std::vector<llm::TokenId> col((size_t)n);
+            for (int i = 0; i < B; i++) {
+                llm::InferenceSession &s = *sessions[i]->s;
+                m->llama->finish_single(s, graphs[(size_t)i], outs[(size_t)i]);  // (the graph's nodes hold the LAST step's results)
+                s.tokens.push_back((llm::TokenId)first[(size_t)i]);
+                out_ids[i] = first[(size_t)i];
+                for (int k = 1; k < n; k++) col[(size_t)k] = (llm::TokenId)(out_ids[(size_t)k * B + i] = rest[(size_t)(k - 1) * B + i]);
+                if (n > 1) s.advance_device_chain(col.data() + 1, (size_t)(n - 1));
+                rngs[i] = r[(size_t)i];
+            }
+            return 1;
+        }
+    }
+    for (int k = 0; k < n; k++)
+        if (llm_infer_next_tokens_sampled_batch_via(step, m, sessions, B, params, rngs, out_ids + (size_t)k * B) < 0) return -1;
     return 0;
 }
 // Accumulated host nanoseconds per phase (see InferenceSession::host_ns; [5] greedy argmax, [6] evaluate as a whole);

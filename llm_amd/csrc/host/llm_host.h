@@ -148,6 +148,34 @@ GGML_API int llm_infer_tokens_greedy_batch_device(llm_model *m, llm_session *con
 typedef int (*llm_batch_chain_entry)(struct ggml_cgraph *const *graphs, int n_graphs, int n_steps, int32_t *out_ids);
 GGML_API int llm_infer_tokens_greedy_batch_via(llm_batch_entry step, llm_batch_chain_entry chain, llm_model *m,
                                                llm_session *const *sessions, int B, int n, int32_t *out_ids);
+/* The sampler of the sampled batched chain: {k, top_p, temperature, penalty} — repetition penalty over the last 64 tokens, top-k,
+ * top-p, temperature, a xorshift64* draw, specified on IEEE basic operations only (llm_amd/csrc/kernels/sampler_math.h, which the
+ * device kernel compiles too).  The reference's default chain (samplers.rs:97-188) is {40, 0.95, 0.8, 1.30}. */
+typedef ggml_hip_sampler llm_sampler_params;
+/* One draw from a row of V logits (free of NaN): `window` holds the most recent tokens, oldest first (its last 64 count, each id once).
+ * Returns the id and steps *rng once; -1 (and *rng unmoved) for k outside 1 .. V, a non-positive temperature, top_p or
+ * penalty, or a window token outside the vocabulary.  Needs no device. */
+GGML_API int32_t llm_sample_exact(const float *logits, int V, const int32_t *window, int n_window, const llm_sampler_params *params,
+                                  uint64_t *rng);
+/* llm_infer_next_tokens_greedy_batch with that sampler: out_ids[i] is drawn from session i's last_logits and the last 64 tokens of
+ * its history with generator rngs[i], appended to the history and evaluated.  Returns what llm_evaluate_batch returns; on -1 no
+ * session and no generator has moved. */
+GGML_API int llm_infer_next_tokens_sampled_batch(llm_model *m, llm_session *const *sessions, int B, const llm_sampler_params *params,
+                                                 uint64_t *rngs, int32_t *out_ids);
+/* n such tokens for each of B sessions, rows 1 .. n - 1 drawn on the device (ggml_hip_decode_batch_sampled).  out_ids [n][B].  Every
+ * session ends exactly as after n calls of llm_infer_next_tokens_sampled_batch — n_past, token history, last_logits, K/V — and every
+ * generator too.  Returns 1 if the chain ran, 0 if the backend declined and that loop ran instead (same results), -1 with nothing
+ * evaluated and no session or generator moved: the bad arguments of the greedy chain and of llm_sample_exact. */
+GGML_API int llm_infer_tokens_sampled_batch_device(llm_model *m, llm_session *const *sessions, int B, int n,
+                                                   const llm_sampler_params *params, uint64_t *rngs, int32_t *out_ids);
+/* ... with the backend's entries as parameters (either may be NULL), as the greedy _via entries */
+typedef int (*llm_batch_sample_entry)(struct ggml_cgraph *const *graphs, int n_graphs, int n_steps, const ggml_hip_sampler *params,
+                                      const int32_t *windows, const int32_t *window_n, uint64_t *rng, int32_t *out_ids);
+GGML_API int llm_infer_next_tokens_sampled_batch_via(llm_batch_entry entry, llm_model *m, llm_session *const *sessions, int B,
+                                                     const llm_sampler_params *params, uint64_t *rngs, int32_t *out_ids);
+GGML_API int llm_infer_tokens_sampled_batch_via(llm_batch_entry step, llm_batch_sample_entry chain, llm_model *m,
+                                                llm_session *const *sessions, int B, int n, const llm_sampler_params *params,
+                                                uint64_t *rngs, int32_t *out_ids);
 GGML_API size_t llm_session_read_node_host(const llm_session *s, int from_end, void *dst, size_t max_bytes);
 GGML_API int llm_session_rewind(llm_session *s, int num);
 /* host nanoseconds per phase of the decode loop, accumulated: [0] adopt/build graph, [1] token write + plan,

@@ -19,16 +19,16 @@ __device__ __forceinline__ unsigned long long topk_key(float v, int id) {
     return ((unsigned long long)o << 32) | (unsigned long long)(0xFFFFFFFFu - (uint32_t)id);
 }
 
-__global__ void __launch_bounds__(1024) k_topk(const float *__restrict__ x, int n, int k, const int *__restrict__ extra_ids,
-                                               int n_extra, float *out_vals, int *out_ids) {
+// The k-th largest key of x[0 .. n) (1 <= k <= n) over one 1024-thread workgroup: the eight radix passes.  Every thread gets the key.
+__device__ __forceinline__ unsigned long long topk_kth_key(const float *__restrict__ x, int n, int k) {
     __shared__ unsigned int s_hist[256];
-    __shared__ unsigned long long s_prefix, s_keys[TOPK_MAX];
-    __shared__ int s_remaining, s_cnt;
+    __shared__ unsigned long long s_prefix;
+    __shared__ int s_remaining;
     const int tid = threadIdx.x;
+    __syncthreads();  // (a caller's earlier use of these words is over)
     if (tid == 0) {
         s_prefix = 0;
         s_remaining = k;
-        s_cnt = 0;
     }
     unsigned long long mask = 0;
     for (int pass = 0; pass < 8; pass++) {
@@ -55,17 +55,12 @@ __global__ void __launch_bounds__(1024) k_topk(const float *__restrict__ x, int 
         mask |= 0xFFull << shift;
         __syncthreads();
     }
-    const unsigned long long kth = s_prefix;  // the k-th largest key
-    int P = 1;
-    while (P < k) P <<= 1;
-    for (int i = tid; i < P; i += 1024) s_keys[i] = 0;
-    __syncthreads();
-    for (int i = tid; i < n; i += 1024) {
-        const unsigned long long key = topk_key(x[i], i);
-        if (key >= kth) s_keys[atomicAdd(&s_cnt, 1)] = key;
-    }
-    __syncthreads();
-    // bitonic sort, descending, P <= 1024 elements (one compare-exchange per thread and step)
+    return s_prefix;
+}
+// bitonic sort of s_keys[0 .. P), descending, P a power of two <= 1024, by one 1024-thread workgroup (one compare-exchange per
+// thread and step); the caller's writes to s_keys are behind a barrier
+__device__ __forceinline__ void topk_bitonic_desc(unsigned long long *s_keys, int P) {
+    const int tid = threadIdx.x;
     for (int size = 2; size <= P; size <<= 1) {
         for (int stride = size >> 1; stride > 0; stride >>= 1) {
             const int i = tid;
@@ -83,6 +78,25 @@ __global__ void __launch_bounds__(1024) k_topk(const float *__restrict__ x, int 
             __syncthreads();
         }
     }
+}
+
+__global__ void __launch_bounds__(1024) k_topk(const float *__restrict__ x, int n, int k, const int *__restrict__ extra_ids,
+                                               int n_extra, float *out_vals, int *out_ids) {
+    __shared__ unsigned long long s_keys[TOPK_MAX];
+    __shared__ int s_cnt;
+    const int tid = threadIdx.x;
+    if (tid == 0) s_cnt = 0;
+    const unsigned long long kth = topk_kth_key(x, n, k);  // the k-th largest key
+    int P = 1;
+    while (P < k) P <<= 1;
+    for (int i = tid; i < P; i += 1024) s_keys[i] = 0;
+    __syncthreads();
+    for (int i = tid; i < n; i += 1024) {
+        const unsigned long long key = topk_key(x[i], i);
+        if (key >= kth) s_keys[atomicAdd(&s_cnt, 1)] = key;
+    }
+    __syncthreads();
+    topk_bitonic_desc(s_keys, P);
     for (int i = tid; i < k; i += 1024) {
         const int id = (int)(0xFFFFFFFFu - (uint32_t)(s_keys[i] & 0xFFFFFFFFull));
         out_ids[i] = id;

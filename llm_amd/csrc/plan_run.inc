@@ -569,15 +569,50 @@ static int decode_greedy_chain(ggml_cgraph *last, int n, int32_t *out_tokens, fl
 // between two graph launches; the step's graph is the one ggml_hip_decode_batch captured.  The sampled ids [n_steps - 1][B] collect
 // on the device and come back with the results of the last step, which go where a single step leaves them.  Nothing of this
 // outlives the call: the next step of any kind uploads its own parameters.
+//
+// ggml_hip_decode_batch_sampled: the same chain with k_batch_sample_next (kernels/sample.h) as the tail — repetition penalty over the
+// column's last 64 tokens, top-k, top-p, temperature and one xorshift64* draw, in the arithmetic of kernels/sampler_math.h, which
+// the host mirror compiles too.  The columns' history rings and the four parameters go up once per call (DecodePlan::scols); the
+// generator states sit in front of the sampled ids in chain_out and come back with them in one copy.
 constexpr int BATCH_CHAIN_MAX_STEPS = 4096;
-static int decode_batch_steps(ggml_cgraph *const *graphs, int B, int n_steps, int32_t *out_ids, bool chain) {
+constexpr int SAMPLE_RNG_WORDS = BATCH_COLS_MAX * 2;  // chain_out of a sampled chain: BATCH_COLS_MAX 64-bit generator states, then the ids
+struct BatchSample {
+    const ggml_hip_sampler *prm;
+    const int32_t *windows;   // [B][64]: column c's last window_n[c] tokens, oldest first
+    const int32_t *window_n;  // [B], 0 .. 64
+    uint64_t *rng;            // [B], in / out
+};
+// what the sampled chain's tail can take (checked before anything runs)
+static bool batch_sample_ok(const BatchSample &s, int B, int64_t V) {
+    const ggml_hip_sampler &q = *s.prm;
+    if (q.k < 1 || q.k > SAMPLER_K_MAX || q.k > V) return false;
+    if (!(q.temperature > 0.0f) || !(q.top_p > 0.0f) || !(q.penalty > 0.0f)) return false;
+    for (int c = 0; c < B; c++) {
+        if (s.window_n[c] < 0 || s.window_n[c] > SAMPLER_WINDOW) return false;
+        for (int i = 0; i < s.window_n[c]; i++)
+            if (s.windows[c * SAMPLER_WINDOW + i] < 0 || s.windows[c * SAMPLER_WINDOW + i] >= V) return false;
+    }
+    return true;
+}
+static void sample_cols_fill(SampleCols &hs, const BatchSample &s, int B) {
+    memset(&hs, 0, sizeof(hs));
+    for (int c = 0; c < B; c++) {
+        hs.hist_n[c] = s.window_n[c];
+        for (int i = 0; i < s.window_n[c]; i++) hs.hist[c][i] = s.windows[c * SAMPLER_WINDOW + i];
+    }
+    hs.k = s.prm->k;
+    hs.top_p = s.prm->top_p;
+    hs.temperature = s.prm->temperature;
+    hs.penalty = s.prm->penalty;
+}
+static int decode_batch_steps(ggml_cgraph *const *graphs, int B, int n_steps, int32_t *out_ids, bool chain, const BatchSample *smp = nullptr) {
     ensure_init();
     finish_pending();
     spec_cancel();
     g.chain_plan = nullptr;
     res_settle();  // (every column's results go to its graph's own nodes: result set 0)
     if (g.prep) g.prep->gr = nullptr;
-    if (!g.opt_plan || !g.opt_plan_batch || (chain && !g.opt_plan_batch_chain)) return -1;
+    if (!g.opt_plan || !g.opt_plan_batch || (chain && !g.opt_plan_batch_chain) || (smp && !g.opt_plan_batch_sample)) return -1;
     if (n_steps < 1 || n_steps > BATCH_CHAIN_MAX_STEPS) return -1;
     const uint64_t t0 = now_ns();
     std::vector<LlamaMatch> ms((size_t)B);
@@ -595,6 +630,7 @@ static int decode_batch_steps(ggml_cgraph *const *graphs, int B, int n_steps, in
     // the whole context in k_attn_decode's LDS arrays (a column may sit anywhere in it), 8 Q8 columns of the widest row in k_mmvq_big8's
     // (an F16 model: k_mmvq_f16 stages as many columns per pass as its LDS holds)
     if (attn_decode_lds(ms[0].C, ms[0].D) > ATTN_DECODE_LDS_MAX || (!ms[0].f16w && !multi_shape_ok(ms[0], B))) return -1;
+    if (smp && !batch_sample_ok(*smp, B, ms[0].V)) return -1;
     ws_reset();
     for (int c = 0; c < B; c++) {
         const LlamaMatch &m = ms[(size_t)c];
@@ -638,6 +674,7 @@ static int decode_batch_steps(ggml_cgraph *const *graphs, int B, int n_steps, in
     hp.token = hp.tokens[0];
     h2d_small((char *)p->prm, &hp, sizeof(hp));
     h2d_small((char *)p->bcols, &hb, sizeof(hb));
+    std::vector<int32_t> sample_back;  // a sampled chain's read-back: generator states, then ids
     const auto step = [&] {
         if (g.opt_graph && !g.timing.on) {
             HIP_CHECK(hipGraphLaunch(plain_graph(p, AV_SHORT, [&] { plan_launch_batch(p); }).exec, g.stream));
@@ -649,14 +686,32 @@ static int decode_batch_steps(ggml_cgraph *const *graphs, int B, int n_steps, in
     step();
     if (n_steps > 1) {  // the device samples every column and moves the step's parameters on; ids of step i at chain_out[(i - 1) * B ..]
         const int n_ids = (n_steps - 1) * B;
-        chain_out_reserve(p, n_ids);
+        chain_out_reserve(p, n_ids + (smp ? SAMPLE_RNG_WORDS : 0));
+        int *ids = p->chain_out + (smp ? SAMPLE_RNG_WORDS : 0);
+        if (smp) {
+            SampleCols hs;
+            sample_cols_fill(hs, *smp, B);
+            uint64_t hr[BATCH_COLS_MAX] = {0};
+            for (int c = 0; c < B; c++) hr[c] = smp->rng[c];
+            h2d_small((char *)p->scols, &hs, sizeof(hs));
+            h2d_small((char *)p->chain_out, hr, sizeof(hr));
+        }
         for (int i = 1; i < n_steps; i++) {
-            hipLaunchKernelGGL(k_batch_argmax_next, dim3((unsigned)B), dim3(1024), 0, g.stream, (const float *)p->logits_out, (int)ms[0].V, p->prm,
-                               p->bcols, p->chain_out + (size_t)(i - 1) * B);
+            if (smp)
+                hipLaunchKernelGGL(k_batch_sample_next, dim3((unsigned)B), dim3(1024), 0, g.stream, (const float *)p->logits_out, (int)ms[0].V,
+                                   p->prm, p->bcols, p->scols, (unsigned long long *)p->chain_out, ids + (size_t)(i - 1) * B);
+            else
+                hipLaunchKernelGGL(k_batch_argmax_next, dim3((unsigned)B), dim3(1024), 0, g.stream, (const float *)p->logits_out, (int)ms[0].V,
+                                   p->prm, p->bcols, ids + (size_t)(i - 1) * B);
             step();
         }
         HIP_CHECK(hipGetLastError());
-        if (out_ids) d2h_queue(out_ids, (const char *)p->chain_out, (size_t)n_ids * 4);
+        if (smp) {  // the generator states and the ids: one copy
+            sample_back.resize((size_t)(SAMPLE_RNG_WORDS + n_ids));
+            d2h_queue(sample_back.data(), (const char *)p->chain_out, sample_back.size() * 4);
+        } else if (out_ids) {
+            d2h_queue(out_ids, (const char *)p->chain_out, (size_t)n_ids * 4);
+        }
         p->m.n_past = mb.n_past + n_steps - 1;
     }
     // every graph's results where an evaluation of that graph alone leaves them (queue_results): the logits in the node's host data
@@ -673,9 +728,18 @@ static int decode_batch_steps(ggml_cgraph *const *graphs, int B, int n_steps, in
     g.stat_plan_tokens += (uint64_t)B * (uint64_t)n_steps;
     g.stat_batch_tokens += (uint64_t)B * (uint64_t)n_steps;
     g.stat_batch_steps += (uint64_t)n_steps;
-    g.stat_batch_chain_steps += (uint64_t)(n_steps - 1);
-    g.stat_batch_chain_tokens += (uint64_t)(n_steps - 1) * (uint64_t)B;
+    if (smp) {  // (a sampled step is not a greedy one: batch_chain_* count ggml_hip_decode_batch_greedy's alone)
+        g.stat_batch_sample_steps += (uint64_t)(n_steps - 1);
+        g.stat_batch_sample_tokens += (uint64_t)(n_steps - 1) * (uint64_t)B;
+    } else {
+        g.stat_batch_chain_steps += (uint64_t)(n_steps - 1);
+        g.stat_batch_chain_tokens += (uint64_t)(n_steps - 1) * (uint64_t)B;
+    }
     d2h_finish();
+    if (!sample_back.empty()) {
+        memcpy(smp->rng, sample_back.data(), (size_t)B * 8);
+        if (out_ids) memcpy(out_ids, sample_back.data() + SAMPLE_RNG_WORDS, (sample_back.size() - SAMPLE_RNG_WORDS) * 4);
+    }
     g.ns_match += t1 - t0;
     g.ns_launch += t2 - t1;
     g.ns_wait += now_ns() - t2;

@@ -131,6 +131,7 @@ struct DecodePlan {
     // uploaded with prm for every step.  Its logits_out / emb_out are rows of the pool (one per column), not a graph's nodes; mem_k / mem_v are unused.
     bool batch = false;
     BatchCols *bcols = nullptr;
+    SampleCols *scols = nullptr;  // ggml_hip_decode_batch_sampled: the columns' history rings and the sampler's parameters (k_batch_sample_next)
     // persistent activations
     char *pool = nullptr;
     DecParams *prm = nullptr;

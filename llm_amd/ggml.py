@@ -260,6 +260,9 @@ PROTOTYPES.update({
     "ggml_hip_decode_batch": (C.c_int, [C.c_void_p, C.c_int]),
     "ggml_hip_decode_batch_greedy": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "ggml_hip_debug_batch_tail": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ggml_hip_decode_batch_sampled": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ggml_hip_debug_batch_sample": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ggml_hip_topk": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "ggml_hip_row_probs": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
     "ggml_hip_quantize": (C.c_size_t, [C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),

@@ -104,8 +104,35 @@ def _lib():
         L.llm_infer_next_tokens_greedy_batch.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_void_p]
         L.llm_infer_tokens_greedy_batch_device.restype = C.c_int
         L.llm_infer_tokens_greedy_batch_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_void_p]
+        L.llm_sample_exact.restype = C.c_int32
+        L.llm_sample_exact.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.llm_infer_next_tokens_sampled_batch.restype = C.c_int
+        L.llm_infer_next_tokens_sampled_batch.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.llm_infer_tokens_sampled_batch_device.restype = C.c_int
+        L.llm_infer_tokens_sampled_batch_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                                            C.c_void_p]
         _bound = True
     return L
+
+
+class SamplerParams(C.Structure):
+    """llm_sampler_params / ggml_hip_sampler: the sampled batched chain's {k, top_p, temperature, penalty}."""
+    _fields_ = [("k", C.c_int32), ("top_p", C.c_float), ("temperature", C.c_float), ("penalty", C.c_float)]
+
+
+def sample_exact(logits, window, rng, k=40, top_p=0.95, temperature=0.8, penalty=1.30):
+    """llm_sample_exact: one draw from a row of logits by the sampled chain's sampler (no device needed).  window: the most recent
+    tokens, oldest first; rng: a uint64 array of one element, stepped in place.  Returns the id; ValueError on bad arguments."""
+    logits = np.ascontiguousarray(logits, dtype=np.float32)
+    window = np.ascontiguousarray(window, dtype=np.int32)
+    if not (isinstance(rng, np.ndarray) and rng.dtype == np.uint64 and rng.size == 1 and rng.flags.c_contiguous):
+        raise ValueError("sample_exact: rng is a uint64 array of one element")
+    prm = SamplerParams(int(k), float(top_p), float(temperature), float(penalty))
+    rc = _lib().llm_sample_exact(logits.ctypes.data, logits.size, window.ctypes.data if window.size else None, window.size,
+                                 C.addressof(prm), rng.ctypes.data)
+    if rc < 0:
+        raise ValueError("llm_sample_exact: bad arguments")
+    return int(rc)
 
 
 def inspect_file(path):
@@ -267,6 +294,42 @@ class Llama:
         rc = _lib().llm_infer_tokens_greedy_batch_device(self.ptr, ptrs, len(sessions), int(n), out.ctypes.data)
         if rc < 0:
             raise ValueError("llm_infer_tokens_greedy_batch_device: bad arguments (nothing was evaluated)")
+        return bool(rc), out
+
+    @staticmethod
+    def _rngs(rngs, B):
+        if not (isinstance(rngs, np.ndarray) and rngs.dtype == np.uint64 and rngs.size == B and rngs.flags.c_contiguous):
+            raise ValueError("rngs: a contiguous uint64 array with one generator state per session (updated in place)")
+        return rngs
+
+    def infer_next_tokens_sampled_batch(self, sessions, rngs, k=40, top_p=0.95, temperature=0.8, penalty=1.30):
+        """infer_next_tokens_batch with the shape of the reference's default sampler instead of the first maximum
+        (llm_infer_next_tokens_sampled_batch): repetition penalty over each session's last 64 tokens, top-k, top-p, temperature, one
+        xorshift64* draw from rngs[i] (a uint64 array, updated in place).  Returns (ran_batched, ids).  ValueError, with nothing
+        evaluated and no generator moved: the bad arguments of evaluate_batch, k outside 1 .. n_vocab, a non-positive top_p,
+        temperature or penalty."""
+        ptrs = (C.c_void_p * len(sessions))(*[s.ptr for s in sessions])
+        rngs = self._rngs(rngs, len(sessions))
+        prm = SamplerParams(int(k), float(top_p), float(temperature), float(penalty))
+        out = np.zeros(len(sessions), np.int32)
+        rc = _lib().llm_infer_next_tokens_sampled_batch(self.ptr, ptrs, len(sessions), C.addressof(prm), rngs.ctypes.data, out.ctypes.data)
+        if rc < 0:
+            raise ValueError("llm_infer_next_tokens_sampled_batch: bad arguments (nothing was evaluated)")
+        return bool(rc), out
+
+    def infer_tokens_sampled_batch(self, sessions, n, rngs, k=40, top_p=0.95, temperature=0.8, penalty=1.30):
+        """n such tokens for each session, all but the first drawn on the device where the backend can
+        (llm_infer_tokens_sampled_batch_device: no host round trip between steps; k <= 256); anything else runs as n steps of
+        infer_next_tokens_sampled_batch, with the same ids, sessions and generator states.  Returns (ran_chained, ids [n, B]).
+        ValueError as above, and for n < 1 or a session without room for n tokens."""
+        ptrs = (C.c_void_p * len(sessions))(*[s.ptr for s in sessions])
+        rngs = self._rngs(rngs, len(sessions))
+        prm = SamplerParams(int(k), float(top_p), float(temperature), float(penalty))
+        out = np.zeros((max(int(n), 0), len(sessions)), np.int32)
+        rc = _lib().llm_infer_tokens_sampled_batch_device(self.ptr, ptrs, len(sessions), int(n), C.addressof(prm), rngs.ctypes.data,
+                                                          out.ctypes.data)
+        if rc < 0:
+            raise ValueError("llm_infer_tokens_sampled_batch_device: bad arguments (nothing was evaluated)")
         return bool(rc), out
 
     def free(self):
