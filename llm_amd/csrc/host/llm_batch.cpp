@@ -1,7 +1,7 @@
 // llm_batch.cpp — the batched multi-session decode step of the session mirror bound to this library's backend: llm_evaluate_batch and
-// llm_infer_next_tokens_greedy_batch are llm_host.cpp's llm_*_batch_via with ggml_hip_decode_batch as the entry, and
+// llm_infer_next_tokens_greedy_batch are llm_infer.cpp's llm_*_batch_via with ggml_hip_decode_batch as the entry, and
 // llm_infer_tokens_greedy_batch_device the chained one with ggml_hip_decode_batch_greedy beside it.  A file of its own so that
-// llm_host.cpp keeps linking against backends that have no such entries.
+// llm_infer.cpp keeps linking against backends that have no such entries.
 #include "ggml_hip.h"
 #include "llm_host.h"
 

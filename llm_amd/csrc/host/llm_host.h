@@ -1,4 +1,4 @@
-/* llm_host.h — C entry points of the host-side mirror (llm_host.cpp) of the reference's
+/* llm_host.h — C entry points of the host-side mirror (llm_session.hpp and the llm_*.cpp beside it) of the reference's
  * crates/llm-base InferenceSession + crates/models/llama, so that tests and bench.py (Python, ctypes)
  * can drive the SAME call sequence a Rust user of rustformers/llm drives:
  *   llm::load → Model::start_session → InferenceSession::{feed_prompt, infer_next_token} → Model::evaluate.
@@ -129,7 +129,7 @@ GGML_API int llm_evaluate_batch(llm_model *m, llm_session *const *sessions, cons
 /* llm_infer_next_token_greedy for B sessions in one such step: out_ids[i] = the first maximum of session i's last_logits, appended to
  * its token history and evaluated.  Returns what llm_evaluate_batch returns. */
 GGML_API int llm_infer_next_tokens_greedy_batch(llm_model *m, llm_session *const *sessions, int B, int32_t *out_ids);
-/* the two entries above with the backend's batched step as a parameter (NULL: always one by one).  llm_host.cpp is also built against
+/* the two entries above with the backend's batched step as a parameter (NULL: always one by one).  llm_infer.cpp is also built against
  * backends without ggml_hip_decode_batch; host/llm_batch.cpp binds the library's own. */
 typedef int (*llm_batch_entry)(struct ggml_cgraph *const *graphs, int n_graphs);
 GGML_API int llm_evaluate_batch_via(llm_batch_entry entry, llm_model *m, llm_session *const *sessions, const int32_t *tokens, int B,

@@ -1,0 +1,385 @@
+// llm_infer.cpp — the host mirror's token steps (inference_session.rs:381-424 infer_next_token with the sampler spelled out): the
+// greedy argmax and step, the top-k measurement step, the greedy device chain, the batched steps and chains of several sessions
+// with the backend's entries as parameters (llm_batch.cpp binds the real ones), and llm_sample_exact.
+#if defined(__x86_64__)
+#include <immintrin.h>
+#endif
+#include "llm_session.hpp"
+#include "kernels/sampler_math.h"
+
+using namespace llm_host;
+
+// Greedy sampling on the host: the index the loop `best = 0; if (l[i] > l[best]) best = i` returns (first maximum; NaNs never win;
+// a NaN in front keeps index 0).  The AVX2 version finds the maximum with the same `>` rule lane by lane, then the first
+// position that holds it: 7 -> ~1.5 us for 32000 logits, on the critical path of every decoded token.
+static size_t argmax_first_scalar(const float *l, size_t n) {
+    size_t best = 0;
+    for (size_t i = 1; i < n; i++)
+        if (l[i] > l[best]) best = i;
+    return best;
+}
+#if defined(__x86_64__)
+__attribute__((target("avx2"))) static size_t argmax_first_avx2(const float *l, size_t n) {
+    if (n < 16) return argmax_first_scalar(l, n);
+    __m256 mx = _mm256_set1_ps(l[0]);
+    size_t i = 0;
+    for (; i + 8 <= n; i += 8) {
+        const __m256 v = _mm256_loadu_ps(l + i);
+        mx = _mm256_blendv_ps(mx, v, _mm256_cmp_ps(v, mx, _CMP_GT_OQ));
+    }
+    float lanes[8];
+    _mm256_storeu_ps(lanes, mx);
+    float m = l[0];
+    for (int k = 0; k < 8; k++) m = lanes[k] > m ? lanes[k] : m;
+    for (; i < n; i++) m = l[i] > m ? l[i] : m;
+    if (!(m == m)) return 0;  // l[0] is NaN: nothing compares greater
+    const __m256 mv = _mm256_set1_ps(m);
+    for (i = 0; i + 8 <= n; i += 8) {
+        const int mask = _mm256_movemask_ps(_mm256_cmp_ps(_mm256_loadu_ps(l + i), mv, _CMP_EQ_OQ));
+        if (mask) return i + (size_t)__builtin_ctz((unsigned)mask);
+    }
+    for (; i < n; i++)
+        if (l[i] == m) return i;
+    return 0;
+}
+#endif
+static size_t argmax_first(const float *l, size_t n) {
+#if defined(__x86_64__)
+    static const bool have_avx2 = __builtin_cpu_supports("avx2");
+    if (have_avx2) return argmax_first_avx2(l, n);
+#endif
+    return argmax_first_scalar(l, n);
+}
+static int32_t argmax_of(const llm_session *s) { return (int32_t)argmax_first(s->s->last_logits.data(), s->s->last_logits.size()); }
+
+// inference_session.rs:388-390: a session without room for n more tokens ends the process as the reference's error would
+static void require_room(const llm_model *m, const llm_session *s, size_t n, const char *who) {
+    if (s->s->n_past + n < m->llama->params.context_size) return;
+    fprintf(stderr, "%s: InferenceError::ContextFull\n", who);
+    abort();
+}
+
+// what a batched step asks of its sessions, whatever their tokens: B different whole-model sessions of m on the calling thread's
+// slot, each with room for n more tokens
+static bool batch_sessions_ok(const llm_model *m, llm_session *const *sessions, int B, size_t n) {
+    if (!m || !sessions || B < 1) return false;
+    if (!m->stages.empty() || !m->llama->is_first() || !m->llama->is_last()) return false;
+    for (int i = 0; i < B; i++) {
+        const llm_session *s = sessions[i];
+        if (!s || !s->s || s->model != m || !s->stage_sessions.empty() || s->device != ggml_hip_get_main_device()) return false;
+        for (int j = 0; j < i; j++)
+            if (sessions[j] == s) return false;
+        if (s->s->n_past + n > m->llama->params.context_size) return false;
+    }
+    return true;
+}
+
+// ---- the three pieces every batched step and chain is made of
+namespace {
+// Stage: the single-token graph of each of B sessions for its id, built exactly as llm_evaluate builds it and not computed — the
+// caller hands `graphs` to a backend entry; finish(i) is what evaluate does for session i once an entry has computed them
+struct Staged {
+    llm_model *m;
+    llm_session *const *sessions;
+    std::vector<ggml_cgraph *> graphs;
+    std::vector<llm::GraphOutputs> outs;
+    Staged(llm_model *m, llm_session *const *sessions, const int32_t *ids, int B) : m(m), sessions(sessions), graphs((size_t)B), outs((size_t)B) {
+        for (int i = 0; i < B; i++) graphs[(size_t)i] = m->llama->stage_single(*sessions[i]->s, (llm::TokenId)ids[i], outs[(size_t)i]);
+    }
+    void finish(int i) { m->llama->finish_single(*sessions[i]->s, graphs[(size_t)i], outs[(size_t)i]); }
+};
+// Commit a chain: an entry ran the staged graphs of row 0 of ids [n][B] and n - 1 more steps on the ids of rows 1 .. n - 1, which it
+// sampled itself.  Every session ends as after n steps: the graph's bookkeeping and last_logits (its nodes hold the LAST step's
+// results), its column at the end of its history, n_past moved by n.
+void commit_chain(Staged &st, int B, int n, const int32_t *ids) {
+    std::vector<llm::TokenId> col((size_t)n);
+    for (int i = 0; i < B; i++) {
+        llm::InferenceSession &s = *st.sessions[i]->s;
+        st.finish(i);
+        for (int k = 0; k < n; k++) col[(size_t)k] = (llm::TokenId)ids[(size_t)k * B + i];
+        s.tokens.push_back(col[0]);
+        if (n > 1) s.advance_device_chain(col.data() + 1, (size_t)(n - 1));
+    }
+}
+// Commit a step: the ids a batched step evaluated go to the end of the sessions' histories and out to the caller
+void commit_step(llm_session *const *sessions, int B, const int32_t *next, int32_t *out_ids) {
+    for (int i = 0; i < B; i++) {
+        sessions[i]->s->tokens.push_back((llm::TokenId)next[i]);
+        out_ids[i] = next[i];
+    }
+}
+}  // namespace
+
+// ---- the sampled batched chain's host side.  The sampler is kernels/sampler_math.h — the header k_batch_sample_next compiles — so
+// the ids drawn here and on the device are the same ids.
+static bool sampler_params_ok(const llm_sampler_params *p, size_t V) {
+    return p && p->k >= 1 && (size_t)p->k <= V && p->temperature > 0.0f && p->top_p > 0.0f && p->penalty > 0.0f;
+}
+// the draw for each of B sessions: from its last_logits and the last 64 tokens of its history, with its own generator.  All B ids
+// are drawn before anything is staged, so a draw that fails (false) leaves every session and — the caller hands in copies —
+// every generator unmoved
+static bool sample_sessions(llm_session *const *sessions, int B, const llm_sampler_params *params, uint64_t *rngs, int32_t *ids) {
+    for (int i = 0; i < B; i++) {
+        const llm::InferenceSession &s = *sessions[i]->s;
+        const std::vector<llm::TokenId> &h = s.tokens;  // (TokenId is int32_t)
+        const size_t w = std::min(h.size(), (size_t)SAMPLER_WINDOW);
+        ids[i] = llm_sample_exact(s.last_logits.data(), (int)s.last_logits.size(), h.data() + (h.size() - w), (int)w, params, &rngs[i]);
+        if (ids[i] < 0) return false;
+    }
+    return true;
+}
+
+extern "C" {
+
+// test hook: which = 0 the dispatching version, 1 the scalar loop
+int llm_argmax_first(const float *l, int n, int which) { return (int)(which ? argmax_first_scalar(l, (size_t)n) : argmax_first(l, (size_t)n)); }
+
+int32_t llm_infer_next_token_greedy(llm_model *m, llm_session *s) {
+    // inference_session.rs:381-424 with the sampler chain replaced by argmax over last_logits
+    require_room(m, s, 1, "llm_infer_next_token");
+    const double t0 = llm::InferenceSession::now_ns();
+    const llm::TokenId next = (llm::TokenId)argmax_of(s);
+    s->s->tokens.push_back(next);
+    llm::OutputRequest req;
+    const double t1 = llm::InferenceSession::now_ns();
+    req.greedy_next = true;  // the call after this one evaluates the first maximum of this one's logits: the backend may run it ahead
+    model_evaluate(m, s, std::vector<llm::TokenId>{next}, req);
+    llm::InferenceSession::host_ns_add(5, t1 - t0);                                // argmax
+    llm::InferenceSession::host_ns_add(6, llm::InferenceSession::now_ns() - t1);  // evaluate, all of it
+    return next;
+}
+// The reference's token step with the SHAPE of its default sampler (crates/llm-base/src/samplers.rs:97-188: repetition penalty
+// 1.30 over the last 64 tokens, top-k 40, [tail-free, typical, top-p: act on the <= 40 survivors], temperature 0.80) instead of
+// greedy argmax: what a caller that samples gets from the unchanged sequence sample -> evaluate (inference_session.rs:381-424).
+//   device_topk = 0: as the reference does it — all n_vocab logits are read back by the evaluation (model/common.rs:6-19), the
+//                    candidates are found on the host (std::partial_sort);
+//   device_topk = 1: the evaluation leaves the logits in HBM (OutputRequest::logits_on_device) and the k best + the raw logits of
+//                    the penalty window come from llm_session_topk: k + 64 pairs instead of 128 KB per token.
+// Same candidates, same arithmetic, same generator: both settings draw the same tokens (tests/test_device_tools_gpu.py).
+// `rng`: the caller's xorshift64* state.  Not llm-samplers' chain itself — a measurement of what the read-back costs a sampler.
+int32_t llm_infer_next_token_topk(llm_model *m, llm_session *s, int k, float temperature, uint64_t *rng, int device_topk) {
+    require_room(m, s, 1, "llm_infer_next_token_topk");
+    const size_t V = s->s->last_logits.size();
+    if (k < 1 || (size_t)k > V || !rng) return -1;
+    const std::vector<llm::TokenId> &hist = s->s->tokens;
+    std::vector<int32_t> window;  // the last 64 tokens, each once
+    for (size_t i = hist.size() > 64 ? hist.size() - 64 : 0; i < hist.size(); i++)
+        if (std::find(window.begin(), window.end(), (int32_t)hist[i]) == window.end()) window.push_back((int32_t)hist[i]);
+    std::vector<float> vals(k + window.size());
+    std::vector<int32_t> ids(k + window.size());
+    if (device_topk) {
+        if (llm_session_topk(s, k, window.empty() ? nullptr : window.data(), (int)window.size(), vals.data(), ids.data()) != 0) return -1;
+    } else {
+        const std::vector<float> &l = s->s->last_logits;
+        std::vector<int32_t> order(V);
+        for (size_t i = 0; i < V; i++) order[i] = (int32_t)i;
+        std::partial_sort(order.begin(), order.begin() + k, order.end(),
+                          [&](int32_t a, int32_t b) { return l[a] > l[b] || (l[a] == l[b] && a < b); });
+        for (int i = 0; i < k; i++) { ids[i] = order[i]; vals[i] = l[order[i]]; }
+        for (size_t i = 0; i < window.size(); i++) { ids[k + i] = window[i]; vals[k + i] = l[window[i]]; }
+    }
+    // candidates = top-k and the window's tokens (each once), penalised, the k best of them kept
+    struct Cand { float v; int32_t id; };
+    std::vector<Cand> c;
+    for (size_t i = 0; i < ids.size(); i++) {
+        bool dup = false;
+        for (auto &x : c) dup = dup || x.id == ids[i];
+        if (dup) continue;
+        float v = vals[i];
+        if (std::find(window.begin(), window.end(), ids[i]) != window.end()) v = v > 0.0f ? v / 1.30f : v * 1.30f;
+        c.push_back({v, ids[i]});
+    }
+    std::sort(c.begin(), c.end(), [](const Cand &a, const Cand &b) { return a.v > b.v || (a.v == b.v && a.id < b.id); });
+    if (c.size() > (size_t)k) c.resize(k);
+    double sum = 0.0;
+    std::vector<double> pr(c.size());
+    for (size_t i = 0; i < c.size(); i++) sum += (pr[i] = std::exp((double)(c[i].v - c[0].v) / (double)temperature));
+    uint64_t x = *rng;  // xorshift64*
+    x ^= x >> 12; x ^= x << 25; x ^= x >> 27;
+    *rng = x;
+    const double u = (double)((x * 0x2545F4914F6CDD1Dull) >> 11) / 9007199254740992.0 * sum;
+    double acc = 0.0;
+    llm::TokenId next = (llm::TokenId)c.back().id;
+    for (size_t i = 0; i < c.size(); i++) {
+        acc += pr[i];
+        if (u < acc) { next = (llm::TokenId)c[i].id; break; }
+    }
+    s->s->tokens.push_back(next);
+    llm::OutputRequest req;
+    req.logits_on_device = device_topk != 0;
+    model_evaluate(m, s, std::vector<llm::TokenId>{next}, req);
+    return next;
+}
+// n greedy tokens with the sampler on the device (ggml_hip_decode_greedy_chain): the same ids and the
+// same final logits as n calls of llm_infer_next_token_greedy, without a logits read-back and host sync per token.
+// Falls back to that loop when the backend cannot chain (last evaluation not a single-token fused-plan run, layer
+// split stage, ...).  Returns the number of tokens written to out (n).
+int llm_infer_tokens_greedy_device(llm_model *m, llm_session *s, int n, int32_t *out) {
+    if (n < 1) return 0;
+    require_room(m, s, (size_t)n, "llm_infer_tokens_greedy_device");
+    int done = 0;
+    // the chain continues a single-token fused-plan run; after a prompt chunk (or a fresh session) one normal step arms it
+    for (int attempt = 0; attempt < 2 && done < n; attempt++) {
+        if (m->stages.empty() && s->s->last_graph &&
+            ggml_hip_decode_greedy_chain(s->s->last_graph, n - done, out + done, s->s->last_logits.data()) == 0) {
+            s->s->advance_device_chain((const llm::TokenId *)(out + done), (size_t)(n - done));
+            return n;
+        }
+        out[done++] = llm_infer_next_token_greedy(m, s);
+    }
+    for (; done < n; done++) out[done] = llm_infer_next_token_greedy(m, s);
+    return n;
+}
+// One decode step of B sessions of one model (batched multi-session decode): every session's single-token graph is built exactly as
+// llm_evaluate builds it and the B graphs go to the backend together (`entry` = ggml_hip_decode_batch: one pass over the weights for
+// all of them).  If the backend declines (-1: nothing was executed) the sessions are evaluated one after the other — the same
+// results, B passes.  The entry is a parameter because this file also links against backends that have none (the sanitizer jobs'
+// host stand-in); host/llm_batch.cpp binds the real one.  Returns 1 = ran batched, 0 = ran one by one, -1 = bad arguments, nothing
+// evaluated: a session listed twice, of another model or on another device slot than the calling thread's, a split model, a
+// token outside the vocabulary, a session whose context is full.  Like llm_evaluate it leaves the token history to the caller.
+int llm_evaluate_batch_via(llm_batch_entry entry, llm_model *m, llm_session *const *sessions, const int32_t *tokens, int B, float *logits) {
+    if (!tokens || !batch_sessions_ok(m, sessions, B, 1)) return -1;
+    const size_t V = m->llama->hyperparameters.n_vocab;
+    for (int i = 0; i < B; i++)
+        if (tokens[i] < 0 || (size_t)tokens[i] >= V) return -1;
+    int batched = 0;
+    if (entry && B >= 2) {
+        Staged st(m, sessions, tokens, B);
+        if (entry(st.graphs.data(), B) == 0) {
+            for (int i = 0; i < B; i++) st.finish(i);
+            batched = 1;
+        }
+    }
+    if (!batched)
+        for (int i = 0; i < B; i++) {
+            llm::OutputRequest req;
+            model_evaluate(m, sessions[i], std::vector<llm::TokenId>{(llm::TokenId)tokens[i]}, req);
+        }
+    if (logits)
+        for (int i = 0; i < B; i++) memcpy(logits + (size_t)i * V, sessions[i]->s->last_logits.data(), V * sizeof(float));
+    return batched;
+}
+// llm_infer_next_token_greedy for B sessions in one step: the first maximum of every session's last_logits, then the step above
+int llm_infer_next_tokens_greedy_batch_via(llm_batch_entry entry, llm_model *m, llm_session *const *sessions, int B, int32_t *out_ids) {
+    if (!m || !sessions || !out_ids || B < 1) return -1;
+    std::vector<int32_t> next((size_t)B);
+    for (int i = 0; i < B; i++) {
+        if (!sessions[i] || !sessions[i]->s) return -1;
+        next[(size_t)i] = argmax_of(sessions[i]);
+    }
+    const int r = llm_evaluate_batch_via(entry, m, sessions, next.data(), B, nullptr);
+    if (r >= 0) commit_step(sessions, B, next.data(), out_ids);
+    return r;
+}
+// n greedy tokens for each of B sessions with the sampler on the device (`chain` = ggml_hip_decode_batch_greedy): row 0 of out_ids
+// [n][B] is the first maximum of every session's last_logits, as above; the sessions' graphs for those tokens go to the backend once,
+// which evaluates them and n - 1 more steps on the tokens it samples itself (rows 1 .. n - 1, written straight into out_ids).  Every
+// session ends as after n calls of llm_infer_next_tokens_greedy_batch_via — n_past, token history, last_logits, K/V — and that loop is
+// what runs, through `step`, when there is no chain entry or it declines.  Returns 1 = ran chained, 0 = ran as that loop, -1 = nothing
+// evaluated, no session moved: the bad arguments of llm_evaluate_batch_via, n < 1, a session without room for n tokens.
+int llm_infer_tokens_greedy_batch_via(llm_batch_entry step, llm_batch_chain_entry chain, llm_model *m, llm_session *const *sessions, int B,
+                                      int n, int32_t *out_ids) {
+    if (!out_ids || n < 1 || !batch_sessions_ok(m, sessions, B, (size_t)n)) return -1;
+    if (chain && B >= 2) {
+        for (int i = 0; i < B; i++) out_ids[i] = argmax_of(sessions[i]);
+        Staged st(m, sessions, out_ids, B);
+        if (chain(st.graphs.data(), B, n, out_ids + B) == 0) {
+            commit_chain(st, B, n, out_ids);
+            return 1;
+        }
+    }
+    for (int k = 0; k < n; k++)
+        if (llm_infer_next_tokens_greedy_batch_via(step, m, sessions, B, out_ids + (size_t)k * B) < 0) return -1;
+    return 0;
+}
+// One draw by the written spec: the k largest raw logits and the window's tokens (the last 64 of `window`, each id once) as
+// candidates, the window's penalised, the k best kept; top-p; temperature; one xorshift64* step of *rng.  -1 on bad arguments
+// (k outside 1 .. V, a non-positive temperature / top_p / penalty, a window token outside the vocabulary); *rng unmoved then.
+int32_t llm_sample_exact(const float *logits, int V, const int32_t *window, int n_window, const llm_sampler_params *params, uint64_t *rng) {
+    if (!logits || V < 1 || n_window < 0 || (n_window > 0 && !window) || !rng || !sampler_params_ok(params, (size_t)V)) return -1;
+    if (n_window > SAMPLER_WINDOW) {
+        window += n_window - SAMPLER_WINDOW;
+        n_window = SAMPLER_WINDOW;
+    }
+    const int k = params->k;
+    struct Cand { float v; int32_t id; };
+    std::vector<Cand> c;
+    c.reserve((size_t)k + (size_t)n_window);
+    for (int i = 0; i < n_window; i++) {
+        const int32_t id = window[i];
+        if (id < 0 || id >= V) return -1;
+        bool dup = false;
+        for (const Cand &x : c) dup = dup || x.id == id;
+        if (!dup) c.push_back({sampler_penalise(logits[id], params->penalty), id});
+    }
+    const size_t n_win = c.size();
+    std::vector<int32_t> order((size_t)V);
+    for (int i = 0; i < V; i++) order[(size_t)i] = i;
+    std::partial_sort(order.begin(), order.begin() + k, order.end(),
+                      [&](int32_t a, int32_t b) { return logits[a] > logits[b] || (logits[a] == logits[b] && a < b); });
+    for (int i = 0; i < k; i++) {
+        bool in_window = false;
+        for (size_t j = 0; j < n_win; j++) in_window = in_window || c[j].id == order[(size_t)i];
+        if (!in_window) c.push_back({logits[order[(size_t)i]], order[(size_t)i]});
+    }
+    std::sort(c.begin(), c.end(), [](const Cand &a, const Cand &b) { return a.v > b.v || (a.v == b.v && a.id < b.id); });
+    c.resize((size_t)k);  // (the raw top-k alone are k candidates)
+    std::vector<float> q((size_t)k), p((size_t)k);
+    for (int i = 0; i < k; i++) {
+        q[(size_t)i] = sampler_q(c[(size_t)i].v, c[0].v);
+        p[(size_t)i] = sampler_p(c[(size_t)i].v, c[0].v, params->temperature);
+    }
+    return c[(size_t)sampler_pick(q.data(), p.data(), k, params->top_p, rng)].id;
+}
+// llm_infer_next_tokens_greedy_batch_via with that sampler: every session draws from its own generator (rngs[i]), the id is appended
+// to its history and evaluated in one batched step.  -1: nothing evaluated, no session and no generator moved.
+int llm_infer_next_tokens_sampled_batch_via(llm_batch_entry entry, llm_model *m, llm_session *const *sessions, int B,
+                                            const llm_sampler_params *params, uint64_t *rngs, int32_t *out_ids) {
+    if (!out_ids || !rngs || !batch_sessions_ok(m, sessions, B, 1) || !sampler_params_ok(params, m->llama->hyperparameters.n_vocab)) return -1;
+    std::vector<int32_t> next((size_t)B);
+    std::vector<uint64_t> r(rngs, rngs + B);
+    if (!sample_sessions(sessions, B, params, r.data(), next.data())) return -1;
+    const int rc = llm_evaluate_batch_via(entry, m, sessions, next.data(), B, nullptr);
+    if (rc < 0) return -1;
+    commit_step(sessions, B, next.data(), out_ids);
+    std::copy(r.begin(), r.end(), rngs);
+    return rc;
+}
+// llm_infer_tokens_greedy_batch_via with that sampler (`chain` = ggml_hip_decode_batch_sampled): the host draws row 0 of out_ids
+// [n][B] as above, the device rows 1 .. n - 1 — each column's window moves on over the ids the device draws, and the generator states
+// come back advanced by n draws in all.  Every session and generator ends as after n calls of the stepped form, which is what runs
+// when there is no chain entry or it declines.  Returns 1 / 0 / -1 as the greedy form.
+int llm_infer_tokens_sampled_batch_via(llm_batch_entry step, llm_batch_sample_entry chain, llm_model *m, llm_session *const *sessions, int B,
+                                       int n, const llm_sampler_params *params, uint64_t *rngs, int32_t *out_ids) {
+    if (!out_ids || !rngs || n < 1 || !batch_sessions_ok(m, sessions, B, (size_t)n)) return -1;
+    if (!sampler_params_ok(params, m->llama->hyperparameters.n_vocab)) return -1;
+    if (chain && B >= 2) {
+        std::vector<uint64_t> r(rngs, rngs + B);
+        std::vector<int32_t> first((size_t)B), windows((size_t)B * SAMPLER_WINDOW, 0), window_n((size_t)B);
+        if (!sample_sessions(sessions, B, params, r.data(), first.data())) return -1;
+        Staged st(m, sessions, first.data(), B);
+        for (int i = 0; i < B; i++) {
+            // the window the device starts from: the session's history with this token at its end
+            const std::vector<llm::TokenId> &h = sessions[i]->s->tokens;
+            const size_t keep = std::min(h.size(), (size_t)SAMPLER_WINDOW - 1);
+            int32_t *w = windows.data() + (size_t)i * SAMPLER_WINDOW;
+            for (size_t j = 0; j < keep; j++) w[j] = (int32_t)h[h.size() - keep + j];
+            w[keep] = first[(size_t)i];
+            window_n[(size_t)i] = (int32_t)keep + 1;
+        }
+        // (a buffer of the chain's own, never empty: a declining entry's scribbles, and at n = 1 its address, stay away from out_ids)
+        std::vector<int32_t> rest((size_t)(n - 1) * (size_t)B + 1);
+        if (chain(st.graphs.data(), B, n, params, windows.data(), window_n.data(), r.data(), rest.data()) == 0) {
+            std::copy(first.begin(), first.end(), out_ids);
+            std::copy(rest.begin(), rest.end() - 1, out_ids + B);
+            commit_chain(st, B, n, out_ids);
+            std::copy(r.begin(), r.end(), rngs);
+            return 1;
+        }
+    }
+    for (int k = 0; k < n; k++)
+        if (llm_infer_next_tokens_sampled_batch_via(step, m, sessions, B, params, rngs, out_ids + (size_t)k * B) < 0) return -1;
+    return 0;
+}
+
+}  // extern "C"

@@ -1,6 +1,7 @@
 // llm_perplexity.cpp — InferenceSession::perplexity of the reference (crates/llm-base/src/inference_session.rs:519-589, the
-// `llm perplexity` command) over the C entry points of llm_host.cpp.  A translation unit of its own: it is the only host code
-// that calls ggml_hip_row_probs, and llm_host.cpp must keep linking against backends that do not have that hook.
+// `llm perplexity` command) over the C entry points of llm_host.h (llm_state.cpp defines the ones written for it).  A translation
+// unit of its own: it is the only host code that calls ggml_hip_row_probs, and the rest must keep linking against backends
+// that do not have that hook.
 //
 // on_device = 1 keeps every batch's [n_vocab, N] logits in HBM (OutputRequest::logits_on_device) and asks the device for
 // util::softmax(row)[target] of the counted rows only (kernels/nll.h): N floats cross the bus where the reference reads

@@ -1,5 +1,5 @@
 // sampler_math.h — the arithmetic of the sampled batched chain (top-k / repetition penalty / top-p / temperature / draw), written
-// ONCE for the device (k_batch_sample_next, kernels/sample.h) and the host mirror (llm_sample_exact, host/llm_host.cpp).  The chain's
+// ONCE for the device (k_batch_sample_next, kernels/sample.h) and the host mirror (llm_sample_exact, host/llm_infer.cpp). The chain's
 // contract is equality with the stepped loop, ids byte for byte, so nothing here calls a library transcendental: only IEEE f32 / f64
 // multiply, add, subtract, divide, rintf and integer construction of a power of two, which round identically on both sides when
 // neither contracts a multiply and an add (-ffp-contract=off, as the whole library is built).  Plain C++ where __HIPCC__ is absent.

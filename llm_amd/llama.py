@@ -1,4 +1,4 @@
-"""ctypes handle on the host mirror (llm_amd/csrc/host/llm_host.cpp): the call sequence of
+"""ctypes handle on the host mirror (llm_amd/csrc/host/llm_host.h): the call sequence of
 crates/llm-base (Model::start_session, InferenceSession::feed_prompt / infer_next_token,
 Model::evaluate) as a rustformers/llm user drives it."""
 import ctypes as C

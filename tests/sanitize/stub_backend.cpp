@@ -1,6 +1,6 @@
 // stub_backend.cpp — a HOST stand-in for hip_backend.hip, used ONLY by the sanitizer job (tests/test_sanitize.py): the two
 // host translation units of the product (llm_amd/csrc/ggml_core.cpp = the ggml C API: arenas, tensor builders, views, graph
-// build / plan, quantizers; llm_amd/csrc/host/llm_host.cpp = the mirror of InferenceSession + models/llama, the GGML/GGMF/GGJT
+// build / plan, quantizers; llm_amd/csrc/host/llm_*.cpp = the mirror of InferenceSession + models/llama, the GGML/GGMF/GGJT
 // reader, snapshots, the greedy sampler) are compiled with -fsanitize=address,undefined and linked against THIS file instead
 // of the device backend, so that every pointer computation, arena offset, view stride and container parse they do runs under
 // ASan + UBSan on a machine without a GPU (the reference relies on Rust's checks there; C++ gets none).

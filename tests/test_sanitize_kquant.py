@@ -6,28 +6,18 @@ tests/sanitize/kquant_encode_driver.cpp, which encodes every type into heap buff
 LeakSanitizer report fails the test.  Runs on the CPU (no GPU, no HIP); nothing is loaded into python."""
 import os
 import shutil
-import subprocess
+import sys
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import sanitize_job  # noqa: E402
 
 
 @pytest.mark.skipif(shutil.which("g++") is None, reason="g++ not installed")
 def test_k_encoders_under_asan_and_ubsan(tmp_path):
-    exe = tmp_path / "kquant_encode_driver"
-    srcs = ["llm_amd/csrc/ggml_core.cpp", "tests/sanitize/stub_backend.cpp", "tests/sanitize/kquant_encode_driver.cpp"]
-    cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-           "-fno-omit-frame-pointer", "-Iinclude", "-Illm_amd/csrc", "-pthread"] + srcs + ["-o", str(exe)]
-    r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-3000:]
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0:halt_on_error=1", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
-    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=600, env=env)
-    tail = (r.stdout + r.stderr)[-4000:]
-    if r.returncode != 0 and "LeakSanitizer has encountered a fatal error" in tail:  # ptrace-restricted sandbox: leaks unchecked
-        env["ASAN_OPTIONS"] = "detect_leaks=0:halt_on_error=1"
-        r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=600, env=env)
-        tail = (r.stdout + r.stderr)[-4000:]
+    sanitize_job.build(tmp_path / "kquant_encode_driver", ["tests/sanitize/kquant_encode_driver.cpp"], host_srcs=[sanitize_job.GGML_CORE])
+    r, tail = sanitize_job.run(tmp_path / "kquant_encode_driver")
     assert r.returncode == 0, tail
     assert "kquant encode driver OK" in r.stdout
     assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr and "LeakSanitizer" not in r.stderr, tail
