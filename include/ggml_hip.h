@@ -636,6 +636,21 @@ typedef struct {
 } ggml_hip_sampler;
 GGML_API int ggml_hip_decode_batch_sampled(struct ggml_cgraph *const *graphs, int n_graphs, int n_steps, const ggml_hip_sampler *params,
                                            const int32_t *windows, const int32_t *window_n, uint64_t *rng, int32_t *out_ids);
+/* ggml_hip_decode_greedy_chain for ONE session that samples: n more tokens, each drawn on the device by that sampler (k_sample_next,
+ * the arithmetic of sampler_math.h) from the logits the previous token left, between two replays of the single-token plan — no
+ * logits read-back and no host round trip per token.  `last` as for the greedy chain: the cgraph of the most recent
+ * ggml_graph_compute, a single-token whole-model LLaMA evaluation that ran as a fused plan (block-format, K-quant or F16 weights).
+ * window: the session's last window_n (0 .. 64) tokens, oldest first, INCLUDING the token `last` evaluated; *rng: its generator
+ * state, advanced by n draws on return.  out_tokens[n] receives the ids, last_logits (V floats, may be NULL) the logits after the
+ * n-th.  The K/V memory advances by n positions; the caller adds n to its n_past.  Ids, logits and K/V memory are bit for bit what a
+ * caller gets that draws each token with llm_sample_exact and evaluates it.  Returns 0, or -1 with nothing executed and *rng
+ * unmoved: whatever ggml_hip_decode_greedy_chain declines (n_past + 1 + n beyond the context among it), k < 1, k > 256 or
+ * k > n_vocab, temperature <= 0, top_p <= 0, penalty <= 0, window_n outside 0 .. 64, a window entry outside the vocabulary, option
+ * plan_sample_chain off.  Option chain_k does not apply.  Counters: sample_chain_steps and sample_chain_tokens (n each), and what
+ * the greedy chain moves — plan_tokens, fused_tokens, fused_heads_tokens, graph_replays; nothing of batch_* and none of the token
+ * tail's (tail_tokens, spec_*). */
+GGML_API int ggml_hip_decode_sampled_chain(struct ggml_cgraph *last, int n, const ggml_hip_sampler *params, const int32_t *window,
+                                           int window_n, uint64_t *rng, int32_t *out_tokens, float *last_logits);
 /* Top-k prefilter of a logits row on the device: the k (<= 1024, <= ne0) largest entries of row `row` of
  * the f32 tensor `t` — a node of the caller's most recent ggml_graph_compute, normally the logits — as (value, id) pairs,
  * value descending, lower id first among equal values, followed by the entries of `extra_ids` (n_extra ids, e.g. the
@@ -726,6 +741,13 @@ GGML_API int ggml_hip_debug_batch_tail(const float *logits, int B, int V, const 
 GGML_API int ggml_hip_debug_batch_sample(const float *logits, int B, int V, const ggml_hip_sampler *params, const int32_t *pos_in,
                                          const int32_t *tokens_in, int32_t *hist, int32_t *hist_n, uint64_t *rng, int n_draws,
                                          int32_t *ids_out, int32_t *prm_out, int32_t *pos_out);
+/* Test hook: k_sample_next (the kernel between two replays of ggml_hip_decode_sampled_chain) alone, n_draws (1 .. 4096) launches on
+ * one row logits [V], in the form the chain picks for that V.  n_past_in / tokens_in[32]: the DecParams before the first launch
+ * (token = tokens_in[0]); hist[64], *hist_n and *rng: the ring, its count and the generator state, in / out.  Out: ids_out[n_draws],
+ * prm_out[34] = n_past, token, tokens[0..32).  0, or -1 for arguments it cannot take (what the chain declines among them). */
+GGML_API int ggml_hip_debug_sample_next(const float *logits, int V, const ggml_hip_sampler *params, int n_past_in,
+                                        const int32_t *tokens_in, int32_t *hist, int32_t *hist_n, uint64_t *rng, int n_draws,
+                                        int32_t *ids_out, int32_t *prm_out);
 /* Test hook: w (quantized 2-D weight with a device copy) times N = 2..8 host rows x [N][K] through k_mmq_cols as the
  * multi-token plan launches it; out [N][M].  0, or -1 when that plan would not run this shape on k_mmq_cols. */
 GGML_API int ggml_hip_debug_mul_mat_cols(const struct ggml_tensor *w, const float *x, float *out, int N);

@@ -86,7 +86,7 @@ struct Backend {
     size_t ws_off = 0;  // offset in the last chunk
     Timing timing;
     int opt_fuse = 1, opt_plan = 1, opt_plan_k = 1, opt_plan_multi = 1, opt_plan_prompt = 1, opt_graph = 1, opt_big = 1, opt_kbig = 1;
-    int opt_chain_k = 0, opt_prepare = 1, opt_plan_batch = 1, opt_plan_f16 = 1, opt_plan_batch_chain = 1, opt_plan_batch_sample = 1;
+    int opt_chain_k = 0, opt_prepare = 1, opt_plan_batch = 1, opt_plan_f16 = 1, opt_plan_batch_chain = 1, opt_plan_batch_sample = 1, opt_plan_sample_chain = 1;
     int opt_fuse_attn = 1, opt_fuse_wo = 1, opt_warm_mb = 24, opt_affine = 1;
     int opt_act_quant = 0, opt_mmq_i8 = 0;
     int opt_mmq_min = 32, opt_k_prompt_min = 12, opt_mmq_fuse = 3, opt_mmq_cols = 1, opt_mmq_t256 = 1, opt_attn_fused = 1;
@@ -103,6 +103,7 @@ struct Backend {
     uint64_t stat_alibi_fused = 0;
     uint64_t stat_batch_tokens = 0, stat_batch_steps = 0, stat_batch_chain_steps = 0, stat_batch_chain_tokens = 0;
     uint64_t stat_batch_sample_steps = 0, stat_batch_sample_tokens = 0;
+    uint64_t stat_sample_chain_steps = 0, stat_sample_chain_tokens = 0;
     uint64_t stat_flash_attn_nodes = 0;
     // prompt-GEMM launches by kernel (ggml_hip_get_stat("mmq_launches_<name>")): bench.py labels its MFMA roofline with the
     // kernels that actually ran
@@ -197,6 +198,9 @@ static const OptRow g_options[] = {
     // ggml_hip_decode_batch_sampled: the same chain with the top-k / top-p / temperature sampler on the device (0: it answers -1, the
     // caller samples on the host and takes single steps).  It shapes no plan either.
     {"plan_batch_sample", &Backend::opt_plan_batch_sample, OPT_ENV},
+    // ggml_hip_decode_sampled_chain: n tokens of ONE session with that sampler on the device between two replays of its single-token
+    // plan (0: it answers -1, the caller samples on the host and evaluates token by token).  It shapes no plan.
+    {"plan_sample_chain", &Backend::opt_plan_sample_chain, OPT_ENV},
     {"graph", &Backend::opt_graph, OPT_ENV},                          // replay the plan from a captured hipGraph
     {"big", &Backend::opt_big, OPT_ENV | OPT_DROPS},                  // decode mat-vec as one wave of 1024-thread workgroups (kernels/decode_big.h)
     // K plan: its decode mat-vecs as one wave of 1024-thread workgroups that stage the activation themselves (kernels/kquant_big.h)
@@ -307,6 +311,8 @@ static const StatRow g_counters[] = {
     {"batch_chain_tokens", &Backend::stat_batch_chain_tokens},    // ... and their tokens
     {"batch_sample_steps", &Backend::stat_batch_sample_steps},    // batched steps that ran on tokens the device SAMPLED (ggml_hip_decode_batch_sampled: all but a call's first; not in batch_chain_*)
     {"batch_sample_tokens", &Backend::stat_batch_sample_tokens},  // ... and their tokens
+    {"sample_chain_steps", &Backend::stat_sample_chain_steps},    // replays of a single-token plan on a token the device SAMPLED (ggml_hip_decode_sampled_chain: every token of a call); counted in plan_tokens too
+    {"sample_chain_tokens", &Backend::stat_sample_chain_tokens},  // ... and their tokens (one session a step: the same number, kept beside batch_sample_*)
     {"cols_warm_launches", &Backend::stat_cols_warm_launches},    // chunk-plan norm launches that carried warming workgroups (ColsWarm), counted when enqueued or captured
     {"fused_rearms", &Backend::stat_fused_rearms},                // times the fused forms came back after a clean stretch behind a give-up
     {"spec_hits", &Backend::stat_spec_hits},                      // evaluations that found their results already running (option speculate_next)

@@ -854,6 +854,82 @@ int ggml_hip_debug_batch_sample(const float *logits, int B, int V, const ggml_hi
     return 0;
 }
 
+int ggml_hip_decode_sampled_chain(struct ggml_cgraph *last, int n, const ggml_hip_sampler *params, const int32_t *window, int window_n,
+                                  uint64_t *rng, int32_t *out_tokens, float *last_logits) {
+    if (!last || n < 1 || !params || !rng || !out_tokens || window_n < 0 || window_n > SAMPLER_WINDOW || (window_n > 0 && !window))
+        return -1;  // (before any device is touched)
+    SlotLock lk;
+    const BatchSample smp = {params, window, &window_n, rng};
+    return decode_chain(last, n, out_tokens, last_logits, &smp);
+}
+
+// ---- test hook: k_sample_next alone (tests/test_sample_chain_gpu.py) ----
+// One row of logits [V]; n_past_in and tokens_in[32] go to the device as DecParams (token = tokens_in[0]), hist[64] / hist_n / rng as
+// the session's ring, count and generator state (in / out); n_draws launches on the same row, the form the chain would pick for V.
+// Out: ids_out[n_draws], prm_out[34] = n_past, token, tokens[0..32).  0, or -1 for arguments it cannot take.
+int ggml_hip_debug_sample_next(const float *logits, int V, const ggml_hip_sampler *params, int n_past_in, const int32_t *tokens_in,
+                               int32_t *hist, int32_t *hist_n, uint64_t *rng, int n_draws, int32_t *ids_out, int32_t *prm_out) {
+    if (!logits || V < 1 || !params || !tokens_in || !hist || !hist_n || !rng || !ids_out || !prm_out || n_draws < 1 ||
+        n_draws > BATCH_CHAIN_MAX_STEPS)
+        return -1;
+    {
+        const int32_t wn = std::min(*hist_n, SAMPLER_WINDOW);  // (a count beyond 64: the ring is full)
+        if (*hist_n < 0) return -1;
+        const BatchSample smp = {params, hist, &wn, rng};
+        if (!batch_sample_ok(smp, 1, V)) return -1;
+    }
+    SlotLock lk;
+    ensure_init();
+    finish_pending();
+    const size_t lb = ((size_t)V * 4 + 255) & ~(size_t)255, sb = (sizeof(SampleOne) + 255) & ~(size_t)255;
+    const size_t ib = ((size_t)n_draws * 4 + 255) & ~(size_t)255;
+    char *d = nullptr;
+    dev_malloc((void **)&d, lb + 512 + sb + ib, "debug sample next");
+    DecParams *dp = (DecParams *)(d + lb);
+    unsigned long long *dr = (unsigned long long *)(d + lb + 256);
+    SampleOne *ds = (SampleOne *)(d + lb + 512);
+    int *dids = (int *)(d + lb + 512 + sb);
+    static_assert(sizeof(DecParams) <= 256, "debug sample next: layout");
+    DecParams hp;
+    SampleOne hs;
+    memset(&hp, 0, sizeof(hp));
+    memset(&hs, 0, sizeof(hs));
+    for (int i = 0; i < 32; i++) hp.tokens[i] = tokens_in[i];
+    hp.n_past = n_past_in;
+    hp.token = tokens_in[0];
+    memcpy(hs.hist, hist, sizeof(hs.hist));
+    hs.hist_n = *hist_n;
+    hs.k = params->k;
+    hs.top_p = params->top_p;
+    hs.temperature = params->temperature;
+    hs.penalty = params->penalty;
+    HIP_CHECK(hipStreamSynchronize(g.stream));
+    HIP_CHECK(hipMemcpy(d, logits, (size_t)V * 4, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(dp, &hp, sizeof(hp), hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(ds, &hs, sizeof(hs), hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(dr, rng, 8, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemset(dids, 0xff, (size_t)n_draws * 4));
+    for (int i = 0; i < n_draws; i++) {
+        if (V <= SELECT_CAP)
+            hipLaunchKernelGGL(k_sample_next<true>, dim3(1), dim3(1024), 0, g.stream, (const float *)d, V, dp, ds, dr, dids + i);
+        else
+            hipLaunchKernelGGL(k_sample_next<false>, dim3(1), dim3(1024), 0, g.stream, (const float *)d, V, dp, ds, dr, dids + i);
+    }
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipStreamSynchronize(g.stream));
+    HIP_CHECK(hipMemcpy(ids_out, dids, (size_t)n_draws * 4, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(&hp, dp, sizeof(hp), hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(&hs, ds, sizeof(hs), hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(rng, dr, 8, hipMemcpyDeviceToHost));
+    prm_out[0] = hp.n_past;
+    prm_out[1] = hp.token;
+    for (int i = 0; i < 32; i++) prm_out[2 + i] = hp.tokens[i];
+    memcpy(hist, hs.hist, sizeof(hs.hist));
+    *hist_n = hs.hist_n;
+    HIP_CHECK(hipFree(d));
+    return 0;
+}
+
 int64_t ggml_hip_get_stat(const char *key) {
     SlotLock lk;
     for (const StatRow &c : g_counters)  // the plain counters (backend_state.inc); the rest is computed here

@@ -1,6 +1,7 @@
 // llm_batch.cpp — the batched multi-session decode step of the session mirror bound to this library's backend: llm_evaluate_batch and
 // llm_infer_next_tokens_greedy_batch are llm_infer.cpp's llm_*_batch_via with ggml_hip_decode_batch as the entry, and
-// llm_infer_tokens_greedy_batch_device the chained one with ggml_hip_decode_batch_greedy beside it.  A file of its own so that
+// llm_infer_tokens_greedy_batch_device the chained one with ggml_hip_decode_batch_greedy beside it; the sampled chains likewise, the
+// single session's (llm_infer_tokens_sampled_device, ggml_hip_decode_sampled_chain) among them.  A file of its own so that
 // llm_infer.cpp keeps linking against backends that have no such entries.
 #include "ggml_hip.h"
 #include "llm_host.h"
@@ -22,5 +23,8 @@ int llm_infer_next_tokens_sampled_batch(llm_model *m, llm_session *const *sessio
 int llm_infer_tokens_sampled_batch_device(llm_model *m, llm_session *const *sessions, int B, int n, const llm_sampler_params *params,
                                           uint64_t *rngs, int32_t *out_ids) {
     return llm_infer_tokens_sampled_batch_via(ggml_hip_decode_batch, ggml_hip_decode_batch_sampled, m, sessions, B, n, params, rngs, out_ids);
+}
+int llm_infer_tokens_sampled_device(llm_model *m, llm_session *s, int n, const llm_sampler_params *params, uint64_t *rng, int32_t *out) {
+    return llm_infer_tokens_sampled_via(ggml_hip_decode_sampled_chain, m, s, n, params, rng, out);
 }
 }

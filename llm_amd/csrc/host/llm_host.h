@@ -176,6 +176,23 @@ GGML_API int llm_infer_next_tokens_sampled_batch_via(llm_batch_entry entry, llm_
 GGML_API int llm_infer_tokens_sampled_batch_via(llm_batch_entry step, llm_batch_sample_entry chain, llm_model *m,
                                                 llm_session *const *sessions, int B, int n, const llm_sampler_params *params,
                                                 uint64_t *rngs, int32_t *out_ids);
+/* llm_infer_next_token_greedy for a caller that samples: one draw by llm_sample_exact from last_logits and the last 64 tokens of the
+ * history, appended and evaluated.  Steps *rng once.  -1 with nothing moved (and *rng unmoved) on llm_sample_exact's bad arguments.
+ * Never arms the backend's run-ahead (that is the greedy caller's). */
+GGML_API int32_t llm_infer_next_token_sampled(llm_model *m, llm_session *s, const llm_sampler_params *params, uint64_t *rng);
+/* n such tokens drawn on the device (ggml_hip_decode_sampled_chain: k_sample_next between two replays of the session's single-token
+ * plan; block-format, K-quant and F16 models alike).  out[n].  The session ends exactly as after n calls of
+ * llm_infer_next_token_sampled — tokens, n_past, last_logits, K/V — and so does *rng.  Returns the number of tokens the DEVICE drew:
+ * n behind a single-token step, n - 1 behind a prompt chunk or on a fresh session (one stepped token arms the chain), 0 when the
+ * backend declines throughout and the stepped loop ran (same results); -1 with nothing moved: bad arguments (those of
+ * llm_sample_exact, n < 1) or no room for n tokens. */
+GGML_API int llm_infer_tokens_sampled_device(llm_model *m, llm_session *s, int n, const llm_sampler_params *params, uint64_t *rng,
+                                             int32_t *out);
+/* ... with the backend's entry as a parameter (NULL: always the stepped loop), as the batched _via entries */
+typedef int (*llm_sample_chain_entry)(struct ggml_cgraph *last, int n, const ggml_hip_sampler *params, const int32_t *window,
+                                      int window_n, uint64_t *rng, int32_t *out_tokens, float *last_logits);
+GGML_API int llm_infer_tokens_sampled_via(llm_sample_chain_entry entry, llm_model *m, llm_session *s, int n,
+                                          const llm_sampler_params *params, uint64_t *rng, int32_t *out);
 GGML_API size_t llm_session_read_node_host(const llm_session *s, int from_end, void *dst, size_t max_bytes);
 GGML_API int llm_session_rewind(llm_session *s, int num);
 /* host nanoseconds per phase of the decode loop, accumulated: [0] adopt/build graph, [1] token write + plan,

@@ -230,6 +230,54 @@ int llm_infer_tokens_greedy_device(llm_model *m, llm_session *s, int n, int32_t 
     for (; done < n; done++) out[done] = llm_infer_next_token_greedy(m, s);
     return n;
 }
+// The token step of a caller that samples with the reference's default chain, in the exact arithmetic of kernels/sampler_math.h:
+// llm_sample_exact on last_logits and the last 64 tokens of the history, the id appended and evaluated.  greedy_next stays false: the
+// backend never runs ahead of a sampling caller.  -1 with nothing moved on llm_sample_exact's bad arguments.
+int32_t llm_infer_next_token_sampled(llm_model *m, llm_session *s, const llm_sampler_params *params, uint64_t *rng) {
+    if (!m || !s || !s->s || !rng) return -1;
+    require_room(m, s, 1, "llm_infer_next_token_sampled");
+    uint64_t r = *rng;
+    llm_session *one[1] = {s};
+    int32_t next = -1;
+    if (!sample_sessions(one, 1, params, &r, &next)) return -1;
+    *rng = r;
+    s->s->tokens.push_back((llm::TokenId)next);
+    llm::OutputRequest req;
+    model_evaluate(m, s, std::vector<llm::TokenId>{(llm::TokenId)next}, req);
+    return next;
+}
+// n such tokens with the sampler on the device (`entry` = ggml_hip_decode_sampled_chain; a parameter for the reason the batched
+// entries are).  llm_infer_tokens_greedy_device's two attempts: the chain continues a single-token fused-plan run, so after a
+// prompt chunk (or on a fresh session) one stepped token arms it; an entry that still declines leaves the rest to the stepped loop.
+// The session and *rng end exactly as after n calls of llm_infer_next_token_sampled.  Returns the number of tokens the DEVICE drew
+// (n, n - 1 or 0); -1 with nothing moved on bad arguments or without room for n tokens.
+int llm_infer_tokens_sampled_via(llm_sample_chain_entry entry, llm_model *m, llm_session *s, int n, const llm_sampler_params *params,
+                                 uint64_t *rng, int32_t *out) {
+    if (!m || !s || !s->s || !rng || !out || n < 1) return -1;
+    if (s->s->n_past + (size_t)n >= m->llama->params.context_size) return -1;
+    if (!sampler_params_ok(params, s->s->last_logits.size())) return -1;
+    int done = 0;
+    for (int attempt = 0; attempt < 2 && done < n; attempt++) {
+        if (entry && m->stages.empty() && s->s->last_graph) {
+            const std::vector<llm::TokenId> &h = s->s->tokens;
+            const size_t w = std::min(h.size(), (size_t)SAMPLER_WINDOW);
+            uint64_t r = *rng;
+            // (a buffer of the chain's own: a declining entry's scribbles stay away from out)
+            std::vector<int32_t> ids((size_t)(n - done));
+            if (entry(s->s->last_graph, n - done, params, h.data() + (h.size() - w), (int)w, &r, ids.data(), s->s->last_logits.data()) == 0) {
+                std::copy(ids.begin(), ids.end(), out + done);
+                s->s->advance_device_chain((const llm::TokenId *)ids.data(), ids.size());
+                *rng = r;
+                return n - done;
+            }
+        }
+        const int32_t id = llm_infer_next_token_sampled(m, s, params, rng);
+        if (id < 0) return -1;  // (only the first: the parameters held for it, and hold for every later one)
+        out[done++] = id;
+    }
+    for (; done < n; done++) out[done] = llm_infer_next_token_sampled(m, s, params, rng);
+    return 0;
+}
 // One decode step of B sessions of one model (batched multi-session decode): every session's single-token graph is built exactly as
 // llm_evaluate builds it and the B graphs go to the backend together (`entry` = ggml_hip_decode_batch: one pass over the weights for
 // all of them).  If the backend declines (-1: nothing was executed) the sessions are evaluated one after the other — the same

@@ -1,4 +1,6 @@
-// sample.h — k_batch_sample_next: the tail of a SAMPLED batched decode step (ggml_hip_decode_batch_sampled, plan_run.inc).  What
+// sample.h — the device samplers of the sampled chains: k_batch_sample_next (2 .. 8 sessions, below) and k_sample_next (one session,
+// further down, with the on-chip selection sample_select).
+// k_batch_sample_next: the tail of a SAMPLED batched decode step (ggml_hip_decode_batch_sampled, plan_run.inc).  What
 // k_batch_argmax_next (decode.h) is to the greedy chain, with the sampler of kernels/sampler_math.h in place of the first maximum:
 // repetition penalty over the column's last 64 tokens, top-k, top-p, temperature, one xorshift64* draw.  The arithmetic is that
 // header's, which the host mirror (llm_sample_exact) compiles too: the chain draws the ids the stepped loop draws.
@@ -99,5 +101,244 @@ __global__ void __launch_bounds__(1024) k_batch_sample_next(const float *__restr
         }
         sc->hist[c][(unsigned)hn % SAMPLER_WINDOW] = id;
         sc->hist_n[c] = hn + 1;
+    }
+}
+
+// ---- one session: k_sample_next, the tail of a step of ggml_hip_decode_sampled_chain (plan_run.inc).  What k_argmax_next (decode.h)
+// is to the greedy chain of the single-token plan, with the same sampler as above.
+//
+// The new part is the selection.  k_batch_sample_next reads its row nine times from L2 (eight radix passes of one dependent load
+// per thread and iteration, then the gather); beside a 1.1 ms token that is most of the distance to the stepped loop.  Here the row
+// is fetched ONCE, eight independent 16-byte loads in flight per thread, and stays on chip for every pass and for the gather.
+// On chip means REGISTERS, 32 values per thread (thread t: ids 32 t .. 32 t + 31), V <= SELECT_CAP = 32768: a 32000-float row in
+// LDS would be 125 KB of the CU's 160 KB — no room beside k_topk's tables for a wider vocabulary than the registers take anyway,
+// every pass would read it back through the LDS pipe the histogram's atomics already queue at, and __launch_bounds__(1024) leaves
+// 128 VGPRs of which the row takes 32.  Wider rows (template argument ONCHIP = false; the host picks by V) take topk_kth_key over
+// global memory, as the batched kernel does.
+//
+// sample_select: which of this thread's values belong to the k largest keys of the row (topk_key order), as a bit mask.
+//   value bits  four radix passes of 8 bits over the order-preserving image of the VALUE (the high word of topk_key), histogram in
+//               LDS.  The first digit is the sign and seven exponent bits: a row of logits lands in three or four bins, and 64 lanes
+//               of one atomic instruction on one word are served one after the other — with one 256-bin table the kernel took
+//               72 us, with the copies 48.  Tables per WAVE would not help (the lanes that collide are lanes of one wave; the
+//               instructions of 16 waves queue at one LDS pipe whichever table they name), so the table is replicated per LANE:
+//               SELECT_COPIES = 32 copies, bin d of copy c at word d * 32 + c, lane l adds to copy l & 31 — the 32 lanes the pipe
+//               serves together sit in 32 banks whatever their digits.  32 KB of LDS for a kernel that has the CU to itself.
+//               Thread d < 256 sums bin d's copies (starting at copy d & 31, again one bank per lane); suffix sums by shuffles.
+//   id bits     no passes.  Equal values differ in the low word only, ~id, and a thread's ids are consecutive and ascending with
+//               its thread index: the r lowest ids among the keys equal to the k-th value are the first r in (thread, register)
+//               order — one workgroup prefix sum of the threads' counts.  (All-equal rows, where every value pass keeps every key,
+//               end here like any other row.)
+constexpr int SELECT_PER_THREAD = 32;
+constexpr int SELECT_CAP = 1024 * SELECT_PER_THREAD;
+constexpr int SELECT_COPIES = 32;  // of the 256-bin histogram: one per lane of a half-wave
+
+// the order-preserving image of a value: topk_key's high word
+__device__ __forceinline__ uint32_t select_value_bits(float v) { return (uint32_t)(topk_key(v, 0) >> 32); }
+
+// thread t's 32 values of x[0 .. V), V <= SELECT_CAP; entries from V on are never looked at (sample_select masks them by id)
+__device__ __forceinline__ void sample_select_load(const float *__restrict__ x, int V, float (&v)[SELECT_PER_THREAD]) {
+    const int base = (int)threadIdx.x * SELECT_PER_THREAD;
+    const bool vec = (reinterpret_cast<uintptr_t>(x) & 15) == 0;  // (base is a multiple of 32 floats)
+#pragma unroll
+    for (int j = 0; j < SELECT_PER_THREAD / 4; j++) {
+        const int i = base + 4 * j;
+        float4 f = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        if (vec && i + 4 <= V) {
+            f = *reinterpret_cast<const float4 *>(x + i);
+        } else {
+            if (i + 0 < V) f.x = x[i + 0];
+            if (i + 1 < V) f.y = x[i + 1];
+            if (i + 2 < V) f.z = x[i + 2];
+            if (i + 3 < V) f.w = x[i + 3];
+        }
+        v[4 * j + 0] = f.x;
+        v[4 * j + 1] = f.y;
+        v[4 * j + 2] = f.z;
+        v[4 * j + 3] = f.w;
+    }
+}
+// bit i set: v[i] (id 32 t + i) is one of the k largest keys of the row, 1 <= k <= V <= SELECT_CAP.  One 1024-thread workgroup.
+__device__ __forceinline__ uint32_t sample_select(const float (&v)[SELECT_PER_THREAD], int V, int k) {
+    __shared__ unsigned int s_hist[256 * SELECT_COPIES];
+    __shared__ unsigned int s_prefix, s_remaining, s_digits[4];
+    __shared__ int s_wave[16];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int base = tid * SELECT_PER_THREAD;
+    __syncthreads();  // (a caller's earlier use of these words is over)
+    if (tid == 0) {
+        s_prefix = 0;
+        s_remaining = (unsigned int)k;
+    }
+    uint32_t mask = 0;
+    for (int pass = 0; pass < 4; pass++) {
+        const int shift = 24 - 8 * pass;
+        for (int i = tid; i < 256 * SELECT_COPIES; i += 1024) s_hist[i] = 0;
+        __syncthreads();
+        const uint32_t prefix = s_prefix;
+        unsigned int *copy = s_hist + (lane & (SELECT_COPIES - 1));
+#pragma unroll
+        for (int i = 0; i < SELECT_PER_THREAD; i++) {
+            const uint32_t o = select_value_bits(v[i]);
+            if (base + i < V && (o & mask) == prefix) atomicAdd(&copy[((o >> shift) & 255u) * SELECT_COPIES], 1u);
+        }
+        __syncthreads();
+        // threads 0 .. 255 = waves 0 .. 3: `mine` = the keys of digit tid, `above` = those of the digits above it
+        unsigned int above = 0, mine = 0;
+        if (tid < 256) {
+#pragma unroll
+            for (int c = 0; c < SELECT_COPIES; c++) mine += s_hist[tid * SELECT_COPIES + ((c + tid) & (SELECT_COPIES - 1))];
+            unsigned int inc = mine;  // inclusive suffix sum inside the wave
+#pragma unroll
+            for (int off = 1; off < 64; off <<= 1) {
+                const unsigned int down = __shfl_down(inc, off);
+                if (lane + off < 64) inc += down;
+            }
+            if (lane == 0) s_digits[wave] = inc;
+            above = inc - mine;
+        }
+        const unsigned int rem = s_remaining;
+        __syncthreads();  // everyone has read s_remaining and the histogram
+        if (tid < 256)
+            for (int w = wave + 1; w < 4; w++) above += s_digits[w];
+        if (tid < 256 && above < rem && rem <= above + mine) {  // exactly one digit
+            s_prefix = prefix | ((uint32_t)tid << shift);
+            s_remaining = rem - above;
+        }
+        mask |= 0xFFu << shift;
+        __syncthreads();
+    }
+    const uint32_t kth = s_prefix;      // the k-th largest value; every key above it is in
+    const int r = (int)s_remaining;     // ... and the r lowest ids of the keys that equal it, 1 <= r <= their number
+    uint32_t gt = 0, eq = 0;
+#pragma unroll
+    for (int i = 0; i < SELECT_PER_THREAD; i++) {
+        const uint32_t o = select_value_bits(v[i]);
+        if (base + i < V) {
+            gt |= (o > kth ? 1u : 0u) << i;
+            eq |= (o == kth ? 1u : 0u) << i;
+        }
+    }
+    // exclusive prefix sum of the threads' counts of equal keys, in thread order = id order
+    const int cnt = __popc(eq);
+    int inc = cnt;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const int up = __shfl_up(inc, off);
+        if (lane >= off) inc += up;
+    }
+    if (lane == 63) s_wave[wave] = inc;
+    __syncthreads();
+    int before = inc - cnt;
+    for (int w = 0; w < wave; w++) before += s_wave[w];
+    int room = r - before;  // how many of this thread's equal keys are in, lowest register first
+#pragma unroll
+    for (int i = 0; i < SELECT_PER_THREAD; i++) {
+        if (((eq >> i) & 1u) && room > 0) {
+            gt |= 1u << i;
+            room--;
+        }
+    }
+    return gt;
+}
+
+// One session's sampler state on the device, uploaded once per call: column 0 of SampleCols in a struct of its own.
+struct SampleOne {
+    int hist[SAMPLER_WINDOW];
+    int hist_n;
+    int k;
+    float top_p, temperature, penalty;
+};
+
+// One workgroup of 1024 threads.  The steps are k_batch_sample_next's for one row; only the selection differs (above).  Thread 0
+// writes prm->token, prm->tokens[0], prm->n_past + 1, out[0], the ring slot hist_n % 64, hist_n + 1 and the advanced generator
+// state, and nothing else is written; nothing at all for k outside 1 .. min(SAMPLER_K_MAX, V) (the host declines those).
+template <bool ONCHIP>
+__global__ void __launch_bounds__(1024) k_sample_next(const float *__restrict__ logits, int V, DecParams *prm, SampleOne *st,
+                                                      unsigned long long *rng, int *__restrict__ out) {
+    constexpr int PMAX = 512;  // power of two >= SAMPLER_K_MAX + SAMPLER_WINDOW
+    static_assert(PMAX >= SAMPLER_K_MAX + SAMPLER_WINDOW, "k_sample_next: LDS keys");
+    __shared__ unsigned long long s_keys[PMAX];
+    __shared__ float s_v[SAMPLER_K_MAX], s_q[SAMPLER_K_MAX], s_p[SAMPLER_K_MAX];
+    __shared__ int s_id[SAMPLER_K_MAX], s_h[SAMPLER_WINDOW], s_win[SAMPLER_WINDOW];
+    __shared__ int s_cnt, s_wn;
+    const int tid = threadIdx.x;
+    const int k = st->k;
+    if (k < 1 || k > SAMPLER_K_MAX || k > V || (ONCHIP && V > SELECT_CAP)) return;
+    const float *x = logits;
+    float v[SELECT_PER_THREAD];
+    if (ONCHIP) sample_select_load(x, V, v);  // (in flight while the window is set up)
+    const float penalty = st->penalty, temperature = st->temperature;
+    const int hn = st->hist_n;
+    const int nw = hn < SAMPLER_WINDOW ? (hn < 0 ? 0 : hn) : SAMPLER_WINDOW;
+    int P = 1;
+    while (P < k + nw) P <<= 1;
+    for (int i = tid; i < P; i += 1024) s_keys[i] = 0;  // (below every key of a row without NaN)
+    if (tid < SAMPLER_WINDOW) s_h[tid] = tid < nw ? st->hist[tid] : -1;
+    if (tid == 0) {
+        s_cnt = 0;
+        s_wn = 0;
+    }
+    __syncthreads();
+    if (tid < nw) {  // the window's tokens, each id once, with their penalised values
+        const int id = s_h[tid];
+        bool take = id >= 0 && id < V;
+        for (int j = 0; j < tid; j++) take = take && s_h[j] != id;
+        if (take) {
+            s_win[atomicAdd(&s_wn, 1)] = id;
+            s_keys[atomicAdd(&s_cnt, 1)] = topk_key(sampler_penalise(x[id], penalty), id);
+        }
+    }
+    // the raw top-k, without the window's tokens (both selections open with a barrier: s_win / s_wn are complete behind it)
+    if (ONCHIP) {
+        const uint32_t in = sample_select(v, V, k);
+        const int wn = s_wn;
+#pragma unroll
+        for (int i = 0; i < SELECT_PER_THREAD; i++) {
+            if ((in >> i) & 1u) {
+                const int id = tid * SELECT_PER_THREAD + i;
+                bool in_window = false;
+                for (int j = 0; j < wn; j++) in_window = in_window || s_win[j] == id;
+                if (!in_window) s_keys[atomicAdd(&s_cnt, 1)] = topk_key(v[i], id);
+            }
+        }
+    } else {
+        const unsigned long long kth = topk_kth_key(x, V, k);
+        const int wn = s_wn;
+        for (int i = tid; i < V; i += 1024) {
+            const unsigned long long key = topk_key(x[i], i);
+            if (key >= kth) {
+                bool in_window = false;
+                for (int j = 0; j < wn; j++) in_window = in_window || s_win[j] == i;
+                if (!in_window) s_keys[atomicAdd(&s_cnt, 1)] = key;
+            }
+        }
+    }
+    __syncthreads();
+    topk_bitonic_desc(s_keys, P);
+    if (tid < k) {  // at least k keys went in
+        const unsigned long long key = s_keys[tid];
+        const uint32_t o = (uint32_t)(key >> 32);
+        const uint32_t u = (o & 0x80000000u) ? (o ^ 0x80000000u) : ~o;
+        s_v[tid] = __builtin_bit_cast(float, u);
+        s_id[tid] = (int)(0xFFFFFFFFu - (uint32_t)(key & 0xFFFFFFFFull));
+    }
+    __syncthreads();
+    if (tid < k) {
+        const float v0 = s_v[0];
+        s_q[tid] = sampler_q(s_v[tid], v0);
+        s_p[tid] = sampler_p(s_v[tid], v0, temperature);
+    }
+    __syncthreads();
+    if (tid == 0) {
+        uint64_t state = rng[0];
+        const int id = s_id[sampler_pick(s_q, s_p, k, st->top_p, &state)];
+        rng[0] = state;
+        prm->token = id;
+        prm->tokens[0] = id;
+        prm->n_past = prm->n_past + 1;
+        out[0] = id;
+        st->hist[(unsigned)hn % SAMPLER_WINDOW] = id;
+        st->hist_n = hn + 1;
     }
 }

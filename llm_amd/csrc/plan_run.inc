@@ -1,5 +1,5 @@
 // plan_run.inc — running a plan: capture and replay of its hipGraphs, the results' way to the host, the speculative next token,
-// the re-run of a token whose in-launch hand-off gave up, the greedy chain, the batched step.
+// the re-run of a token whose in-launch hand-off gave up, the greedy and the sampled chain of one session, the batched step.
 // An evaluation (try_decode_plan) is the sequence of its steps, each a function of its own in front of it: resolve_plan (the graph's
 // match and plan), settle_ahead (was the run ahead of the caller this evaluation?), host_dec_params (the parameters the host uploads;
 // also the re-run's and the chain's), run_prompt_plan, plan_sync_dev_gen, launch_tail (a greedy token's graph; result set and
@@ -473,18 +473,48 @@ static bool try_decode_plan(ggml_cgraph *gr, bool defer_wait = false) {
     return true;
 }
 
+// ---- what the device-sampled chains share: their caps, a sampled chain's arguments and what its tail can take ----
+constexpr int BATCH_CHAIN_MAX_STEPS = 4096;
+constexpr int SAMPLE_RNG_WORDS = BATCH_COLS_MAX * 2;  // chain_out of a sampled chain: BATCH_COLS_MAX 64-bit generator states, then the ids
+struct BatchSample {
+    const ggml_hip_sampler *prm;
+    const int32_t *windows;   // [B][64]: column c's last window_n[c] tokens, oldest first
+    const int32_t *window_n;  // [B], 0 .. 64
+    uint64_t *rng;            // [B], in / out
+};
+// what the sampled chain's tail can take (checked before anything runs)
+static bool batch_sample_ok(const BatchSample &s, int B, int64_t V) {
+    const ggml_hip_sampler &q = *s.prm;
+    if (q.k < 1 || q.k > SAMPLER_K_MAX || q.k > V) return false;
+    if (!(q.temperature > 0.0f) || !(q.top_p > 0.0f) || !(q.penalty > 0.0f)) return false;
+    for (int c = 0; c < B; c++) {
+        if (s.window_n[c] < 0 || s.window_n[c] > SAMPLER_WINDOW) return false;
+        for (int i = 0; i < s.window_n[c]; i++)
+            if (s.windows[c * SAMPLER_WINDOW + i] < 0 || s.windows[c * SAMPLER_WINDOW + i] >= V) return false;
+    }
+    return true;
+}
+
 // SURVEY section 8f N3: n greedy tokens back to back without a host round trip per token.  `last` must be the cgraph
 // of the caller's most recent ggml_graph_compute (a single-token LLaMA evaluation that ran as the fused plan, whole
 // model on this device); the plan's decode parameters still hold that token and position on the device, and its
 // logits are in HBM.  Per token: k_argmax_next (argmax -> parameters of the next replay) + one replay of the plan.
 // Returns 0 and fills out_tokens[n] (and last_logits[V] with the logits after the n-th token, if not NULL); -1 if
 // the precondition does not hold (the caller then decodes token by token).
-static int decode_greedy_chain(ggml_cgraph *last, int n, int32_t *out_tokens, float *last_logits) {
+//
+// ggml_hip_decode_sampled_chain is the same chain with k_sample_next (kernels/sample.h) between two replays (`smp`, one column of a
+// BatchSample): the session's history ring and the four parameters go up once per call (DecodePlan::chain_sone), the generator state
+// sits in front of the ids in chain_out and comes back with them in one copy.  Every plan the greedy chain runs is run: block-format,
+// K-quant, F16.  Option chain_k does not apply: the K-token graph stays greedy-only.  Counted in sample_chain_steps /
+// sample_chain_tokens and, as the greedy chain, in plan_tokens, fused_tokens, fused_heads_tokens and graph_replays.
+constexpr int SAMPLE_ONE_RNG_WORDS = 2;  // chain_out of a sampled chain of one session: the 64-bit generator state, then the ids
+static int decode_chain(ggml_cgraph *last, int n, int32_t *out_tokens, float *last_logits, const BatchSample *smp = nullptr) {
     finish_pending();
     DecodePlan *p = live_plan(g.chain_plan);
     if (!p || g.chain_graph != last || n < 1) return -1;
     const LlamaMatch &m = p->m;
     if (m.N != 1 || !m.logits || !m.wte || m.n_past + 1 + n > m.C) return -1;
+    if (smp && (!g.opt_plan_sample_chain || !batch_sample_ok(*smp, 1, m.V))) return -1;
     if (p->prm_ahead) {  // a token tail has moved the parameters on (and a run ahead of the caller may be in flight): back to the last evaluated token
         if (!m.embd) return -1;
         const DecParams hp = host_dec_params(m);
@@ -495,14 +525,40 @@ static int decode_greedy_chain(ggml_cgraph *last, int n, int32_t *out_tokens, fl
     // the first argmax reads the set the last evaluated token sits in; every replay below writes set 0
     const float *first_logits = (const float *)plan_cur_logits(p);
     g.res_plan = nullptr;
-    chain_out_reserve(p, n);
+    const int ids_off = smp ? SAMPLE_ONE_RNG_WORDS : 0;
+    chain_out_reserve(p, ids_off + n);
+    int *ids = p->chain_out + ids_off;
     if (!p->chain_ring) HIP_CHECK(hipMalloc((void **)&p->chain_ring, 64 * 4));
+    if (smp) {  // the ring, the parameters, the generator state: once per call
+        if (!p->chain_sone) HIP_CHECK(hipMalloc((void **)&p->chain_sone, sizeof(SampleOne)));
+        SampleOne hs;
+        memset(&hs, 0, sizeof(hs));
+        hs.hist_n = smp->window_n[0];
+        for (int i = 0; i < smp->window_n[0]; i++) hs.hist[i] = smp->windows[i];
+        hs.k = smp->prm->k;
+        hs.top_p = smp->prm->top_p;
+        hs.temperature = smp->prm->temperature;
+        hs.penalty = smp->prm->penalty;
+        h2d_small((char *)p->chain_sone, &hs, sizeof(hs));
+        h2d_small((char *)p->chain_out, smp->rng, 8);
+    }
+    // the kernel between two replays: the next token from `logits`, into the parameters of the next replay and ids[i]
+    const auto sample_next = [&](const float *logits, int i) {
+        if (!smp)
+            hipLaunchKernelGGL(k_argmax_next, dim3(1), dim3(1024), 0, g.stream, logits, (int)m.V, p->prm, ids + i);
+        else if (m.V <= SELECT_CAP)
+            hipLaunchKernelGGL(k_sample_next<true>, dim3(1), dim3(1024), 0, g.stream, logits, (int)m.V, p->prm, p->chain_sone,
+                               (unsigned long long *)p->chain_out, ids + i);
+        else
+            hipLaunchKernelGGL(k_sample_next<false>, dim3(1), dim3(1024), 0, g.stream, logits, (int)m.V, p->prm, p->chain_sone,
+                               (unsigned long long *)p->chain_out, ids + i);
+    };
     const bool use_graph = g.opt_graph && !g.timing.on && p->any_captured();
     int i0 = 0;
     // option chain_k = K (> 1): K tokens per graph launch — every kernel of the plan reads its token and position from the
     // DecParams that k_argmax_next advances on the device, so the launches of consecutive tokens are the same launches.  Only
     // while the whole group stays on the short-context attention variant; the graph's sampled ids land in chain_out[i0 ..].
-    if (use_graph && g.opt_chain_k > 1) {
+    if (use_graph && g.opt_chain_k > 1 && !smp) {
         const int K = g.opt_chain_k;
         if ((const char *)first_logits != p->logits_out) {  // the K-token graph's first argmax is captured on set 0
             HIP_CHECK(hipMemcpyAsync(p->logits_out, first_logits, (size_t)m.V * 4, hipMemcpyDeviceToDevice, g.stream));
@@ -529,8 +585,7 @@ static int decode_greedy_chain(ggml_cgraph *last, int n, int32_t *out_tokens, fl
         }
     }
     for (int i = i0; i < n; i++) {
-        hipLaunchKernelGGL(k_argmax_next, dim3(1), dim3(1024), 0, g.stream, i == 0 ? first_logits : (const float *)p->logits_out, (int)m.V,
-                           p->prm, p->chain_out + i);
+        sample_next(i == 0 ? first_logits : (const float *)p->logits_out, i);
         // the token of step i sits at position n_past + 1 + i; same rule as try_decode_plan for the attention variant
         const int av = attn_variant(m, p, m.n_past + 1 + i + 1);
         // (the chain's books are not count_token_forms': no fused_wo_tokens, fused_affine_tokens or split_tokens — values tests read; left as they are)
@@ -545,16 +600,29 @@ static int decode_greedy_chain(ggml_cgraph *last, int n, int32_t *out_tokens, fl
         }
     }
     HIP_CHECK(hipGetLastError());
-    d2h_queue(out_tokens, (const char *)p->chain_out, (size_t)n * 4);
+    std::vector<int32_t> sample_back;  // a sampled chain's read-back: the generator state, then the ids
+    if (smp) {
+        sample_back.resize((size_t)(ids_off + n));
+        d2h_queue(sample_back.data(), (const char *)p->chain_out, sample_back.size() * 4);
+    } else {
+        d2h_queue(out_tokens, (const char *)p->chain_out, (size_t)n * 4);
+    }
     if (last_logits) d2h_queue(last_logits, p->logits_out, (size_t)m.V * 4);
     token_results_queue(p);
     token_finish(false);  // a hand-off that gave up inside the chain has already fed the sampler garbage: abort
+    if (smp) {
+        memcpy(smp->rng, sample_back.data(), 8);
+        memcpy(out_tokens, sample_back.data() + ids_off, (size_t)n * 4);
+        g.stat_sample_chain_steps += (uint64_t)n;
+        g.stat_sample_chain_tokens += (uint64_t)n;
+    }
     p->m.n_past += n;
     p->replays += use_graph ? (uint64_t)n : 0;
     g.stat_plan_tokens += (uint64_t)n;
     g.chain_plan = nullptr;  // the caller's next evaluation re-arms it
     return 0;
 }
+static int decode_greedy_chain(ggml_cgraph *last, int n, int32_t *out_tokens, float *last_logits) { return decode_chain(last, n, out_tokens, last_logits); }
 
 // ggml_hip_decode_batch: one decode step of B = 2..8 single-token LLaMA graphs of ONE model, each the reference's unchanged graph for
 // its own session (own memory_k / memory_v, own n_past, own token), as ONE pass over the weights: the chunk plan's launches
@@ -574,26 +642,6 @@ static int decode_greedy_chain(ggml_cgraph *last, int n, int32_t *out_tokens, fl
 // column's last 64 tokens, top-k, top-p, temperature and one xorshift64* draw, in the arithmetic of kernels/sampler_math.h, which
 // the host mirror compiles too.  The columns' history rings and the four parameters go up once per call (DecodePlan::scols); the
 // generator states sit in front of the sampled ids in chain_out and come back with them in one copy.
-constexpr int BATCH_CHAIN_MAX_STEPS = 4096;
-constexpr int SAMPLE_RNG_WORDS = BATCH_COLS_MAX * 2;  // chain_out of a sampled chain: BATCH_COLS_MAX 64-bit generator states, then the ids
-struct BatchSample {
-    const ggml_hip_sampler *prm;
-    const int32_t *windows;   // [B][64]: column c's last window_n[c] tokens, oldest first
-    const int32_t *window_n;  // [B], 0 .. 64
-    uint64_t *rng;            // [B], in / out
-};
-// what the sampled chain's tail can take (checked before anything runs)
-static bool batch_sample_ok(const BatchSample &s, int B, int64_t V) {
-    const ggml_hip_sampler &q = *s.prm;
-    if (q.k < 1 || q.k > SAMPLER_K_MAX || q.k > V) return false;
-    if (!(q.temperature > 0.0f) || !(q.top_p > 0.0f) || !(q.penalty > 0.0f)) return false;
-    for (int c = 0; c < B; c++) {
-        if (s.window_n[c] < 0 || s.window_n[c] > SAMPLER_WINDOW) return false;
-        for (int i = 0; i < s.window_n[c]; i++)
-            if (s.windows[c * SAMPLER_WINDOW + i] < 0 || s.windows[c * SAMPLER_WINDOW + i] >= V) return false;
-    }
-    return true;
-}
 static void sample_cols_fill(SampleCols &hs, const BatchSample &s, int B) {
     memset(&hs, 0, sizeof(hs));
     for (int c = 0; c < B; c++) {

@@ -111,6 +111,10 @@ def _lib():
         L.llm_infer_tokens_sampled_batch_device.restype = C.c_int
         L.llm_infer_tokens_sampled_batch_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                                             C.c_void_p]
+        L.llm_infer_next_token_sampled.restype = C.c_int32
+        L.llm_infer_next_token_sampled.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.llm_infer_tokens_sampled_device.restype = C.c_int
+        L.llm_infer_tokens_sampled_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         _bound = True
     return L
 
@@ -396,6 +400,30 @@ class Session:
         out = np.zeros(n, np.int32)
         _lib().llm_infer_tokens_greedy_device(self.model.ptr, self.ptr, n, out.ctypes.data)
         return out
+
+    def infer_next_token_sampled(self, rng, k=40, top_p=0.95, temperature=0.8, penalty=1.30):
+        """One token step of a caller that samples (llm_infer_next_token_sampled): sample_exact on last_logits and the last 64 tokens
+        of the history, the id appended and evaluated.  rng: a uint64 array of one element, stepped in place.  ValueError, with
+        nothing moved, on sample_exact's bad arguments."""
+        rng = Llama._rngs(rng, 1)
+        prm = SamplerParams(int(k), float(top_p), float(temperature), float(penalty))
+        rc = _lib().llm_infer_next_token_sampled(self.model.ptr, self.ptr, C.addressof(prm), rng.ctypes.data)
+        if rc < 0:
+            raise ValueError("llm_infer_next_token_sampled: bad arguments (nothing was evaluated)")
+        return int(rc)
+
+    def infer_tokens_sampled_device(self, n, rng, k=40, top_p=0.95, temperature=0.8, penalty=1.30):
+        """n such tokens drawn on the device where the backend can (llm_infer_tokens_sampled_device: no logits read-back and no host
+        round trip per token; k <= 256); anything else runs as infer_next_token_sampled, with the same ids, session and generator
+        state.  Returns (n_on_device, ids): n behind a single-token step, n - 1 behind a prompt, 0 when the backend declined.
+        ValueError as above, and for n < 1 or a session without room for n tokens."""
+        rng = Llama._rngs(rng, 1)
+        prm = SamplerParams(int(k), float(top_p), float(temperature), float(penalty))
+        out = np.zeros(max(int(n), 0), np.int32)
+        rc = _lib().llm_infer_tokens_sampled_device(self.model.ptr, self.ptr, int(n), C.addressof(prm), rng.ctypes.data, out.ctypes.data)
+        if rc < 0:
+            raise ValueError("llm_infer_tokens_sampled_device: bad arguments (nothing was evaluated)")
+        return int(rc), out
 
     @staticmethod
     def host_timing(reset=False):
