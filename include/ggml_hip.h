@@ -604,7 +604,8 @@ GGML_API int ggml_hip_decode_greedy_chain(struct ggml_cgraph *last, int n, int32
 /* One decode step of B single-token LLaMA graphs of ONE model on this slot, each the reference's unchanged graph for its own
  * session (own memory_k / memory_v, own n_past, own token), as one pass over the weights.  Same results as ggml_graph_compute
  * on each graph in turn (host-visible nodes filled: logits, embeddings).  Returns 0, or -1 with nothing executed.
- * -1 unless: 2 <= B <= 8; every graph is a whole-model single-token graph of a block-format (not K-quant) model; all share the
+ * -1 unless: 2 <= B <= 8; every graph is a whole-model single-token graph of a block-format or F16 model, or of a K-quant model
+ * (Q2_K ... Q6_K, uniform or mixed) with options plan_batch_k (default 0) and plan_k on; all share the
  * weights, dimensions, context size and RoPE parameters; f16 K/V, all distinct; every n_past below the context size, which fits
  * the attention kernel's LDS; options plan and plan_batch on.  NULL or a B out of range is refused before any device is touched. */
 GGML_API int ggml_hip_decode_batch(struct ggml_cgraph *const *graphs, int n_graphs);

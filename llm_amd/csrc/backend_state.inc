@@ -86,7 +86,7 @@ struct Backend {
     size_t ws_off = 0;  // offset in the last chunk
     Timing timing;
     int opt_fuse = 1, opt_plan = 1, opt_plan_k = 1, opt_plan_multi = 1, opt_plan_prompt = 1, opt_graph = 1, opt_big = 1, opt_kbig = 1;
-    int opt_chain_k = 0, opt_prepare = 1, opt_plan_batch = 1, opt_plan_f16 = 1, opt_plan_batch_chain = 1, opt_plan_batch_sample = 1, opt_plan_sample_chain = 1;
+    int opt_chain_k = 0, opt_prepare = 1, opt_plan_batch = 1, opt_plan_f16 = 1, opt_plan_batch_chain = 1, opt_plan_batch_sample = 1, opt_plan_sample_chain = 1, opt_plan_batch_k = 0;
     int opt_fuse_attn = 1, opt_fuse_wo = 1, opt_warm_mb = 24, opt_affine = 1;
     int opt_act_quant = 0, opt_mmq_i8 = 0;
     int opt_mmq_min = 32, opt_k_prompt_min = 12, opt_mmq_fuse = 3, opt_mmq_cols = 1, opt_mmq_t256 = 1, opt_attn_fused = 1;
@@ -102,7 +102,7 @@ struct Backend {
     uint64_t stat_plan_tokens = 0, stat_generic_graphs = 0, stat_split_tokens = 0, stat_prompt_plan_tokens = 0, stat_fused_tokens = 0, stat_kplan_tokens = 0, stat_fused_heads_tokens = 0, stat_fused_wo_tokens = 0, stat_fused_affine_tokens = 0, stat_prepared_tokens = 0;
     uint64_t stat_alibi_fused = 0;
     uint64_t stat_batch_tokens = 0, stat_batch_steps = 0, stat_batch_chain_steps = 0, stat_batch_chain_tokens = 0;
-    uint64_t stat_batch_sample_steps = 0, stat_batch_sample_tokens = 0;
+    uint64_t stat_batch_sample_steps = 0, stat_batch_sample_tokens = 0, stat_batch_k_steps = 0;
     uint64_t stat_sample_chain_steps = 0, stat_sample_chain_tokens = 0;
     uint64_t stat_flash_attn_nodes = 0;
     // prompt-GEMM launches by kernel (ggml_hip_get_stat("mmq_launches_<name>")): bench.py labels its MFMA roofline with the
@@ -192,6 +192,11 @@ static const OptRow g_options[] = {
     {"plan_prompt", &Backend::opt_plan_prompt, OPT_ENV | OPT_DROPS},  // fused plan for prompt batches of >= mmq_min tokens (kernels/prompt.h)
     // ggml_hip_decode_batch: one decode step of 2..8 sessions of one model as one pass over the weights (0: it answers -1, the caller steps them one by one)
     {"plan_batch", &Backend::opt_plan_batch, OPT_ENV | OPT_DROPS},
+    // ... and of a K-quant model, on the K plan's chunk form (plan_launch_k; needs plan_k and plan_batch on).  The default is 0 ONLY
+    // because three GPU tests written before it pin "a Q4_K model at default options is declined and runs one by one" (the q4_k cases
+    // of tests/test_batch_decode_gpu.py, test_batch_chain_gpu.py and test_batch_sample_gpu.py): at 0 nothing behaves differently from
+    // before the option existed.  Making it 1 is a change to those three cases and to this initialiser, nothing else.
+    {"plan_batch_k", &Backend::opt_plan_batch_k, OPT_ENV | OPT_DROPS},
     // ggml_hip_decode_batch_greedy: n greedy steps of those sessions with the argmax on the device, the step's graph replayed (0: it
     // answers -1, the caller takes n single steps).  It shapes no plan: the chain replays the graph of ggml_hip_decode_batch.
     {"plan_batch_chain", &Backend::opt_plan_batch_chain, OPT_ENV},
@@ -290,6 +295,16 @@ inline int opt_value(const OptRow &o, int v) {
     if (o.fx == FX_ACT_QUANT) return v ? 1 : 0;
     return o.lo <= o.hi ? std::min(o.hi, std::max(o.lo, v)) : v;
 }
+// what the environment says for a row (GGML_HIP_<KEY IN CAPITALS>), stored into *out; false: the row has no variable or it is not set
+inline bool opt_env_value(const OptRow &o, int *out) {
+    if (!(o.flags & OPT_ENV)) return false;
+    std::string name = "GGML_HIP_";
+    for (const char *c = o.key; *c; c++) name += (char)toupper((unsigned char)*c);
+    const char *v = getenv(name.c_str());
+    if (!v) return false;
+    *out = o.fx == FX_ACT_QUANT ? (!strcmp(v, "scalar") || atoi(v) == 1) : opt_value(o, atoi(v));
+    return true;
+}
 // The plain counters of ggml_hip_get_stat (the computed ones are in that function): the row says what the counter counts.
 struct StatRow {
     const char *key;
@@ -307,6 +322,7 @@ static const StatRow g_counters[] = {
     {"prompt_plan_tokens", &Backend::stat_prompt_plan_tokens},    // tokens executed by the fused prompt plan
     {"batch_decode_tokens", &Backend::stat_batch_tokens},         // decode tokens that ran as columns of a batched step (ggml_hip_decode_batch); counted in plan_tokens too
     {"batch_decode_steps", &Backend::stat_batch_steps},           // ... and the steps
+    {"batch_k_steps", &Backend::stat_batch_k_steps},              // ... those of them that ran on a K plan (a K-quant model under option plan_batch_k); their tokens count in kplan_tokens too
     {"batch_chain_steps", &Backend::stat_batch_chain_steps},      // ... those of them that ran on device-sampled tokens (ggml_hip_decode_batch_greedy: all but a call's first)
     {"batch_chain_tokens", &Backend::stat_batch_chain_tokens},    // ... and their tokens
     {"batch_sample_steps", &Backend::stat_batch_sample_steps},    // batched steps that ran on tokens the device SAMPLED (ggml_hip_decode_batch_sampled: all but a call's first; not in batch_chain_*)
@@ -574,10 +590,8 @@ void ensure_init() {
     tl_device = g.device;
     HIP_CHECK(hipStreamCreateWithFlags(&g.stream, hipStreamNonBlocking));
     for (const OptRow &o : g_options) {  // the environment: stored straight into the field; the option log below wins over it
-        if (!(o.flags & OPT_ENV)) continue;
-        std::string name = "GGML_HIP_";
-        for (const char *c = o.key; *c; c++) name += (char)toupper((unsigned char)*c);
-        if (const char *v = getenv(name.c_str())) g.*o.field = o.fx == FX_ACT_QUANT ? (!strcmp(v, "scalar") || atoi(v) == 1) : opt_value(o, atoi(v));
+        int v = 0;
+        if (opt_env_value(o, &v)) g.*o.field = v;
     }
     {
         hipDeviceProp_t prop;

@@ -882,10 +882,12 @@ int ggml_hip_get_option(const char *key) {
     const OptRow &o = opt_row(key, "ggml_hip_get_option");
     SlotLock lk;
     if (o.flags & OPT_ACTION) return -1;
-    if (!g.inited) {  // what the slot will hold once it exists: the logged value, else the default
+    if (!g.inited) {  // what the slot will hold once it exists: the logged value, else the environment's, else the default
         std::lock_guard<std::recursive_mutex> lk2(g_mu);
         auto it = g_opt_log.find(key);
         if (it != g_opt_log.end()) return it->second;
+        int v = 0;
+        if (o.field && opt_env_value(o, &v)) return v;
     }
     if (o.fx == FX_TIMELINE) return g.timeline ? g.timeline_wgs : 0;
     if (o.fx == FX_SERIAL_STAGE_SLOTS) return g_dev_serial_stages[g.device & 63].load();

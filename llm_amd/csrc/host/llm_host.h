@@ -119,7 +119,8 @@ GGML_API int32_t llm_infer_next_token_topk(llm_model *m, llm_session *s, int k, 
  * of llm_infer_next_token_greedy, no per-token logits read-back; falls back to that loop when chaining is impossible */
 GGML_API int llm_infer_tokens_greedy_device(llm_model *m, llm_session *s, int n, int32_t *out);
 /* One decode step of B sessions of ONE model, token tokens[i] for sessions[i], as one pass over the weights where the backend can
- * (ggml_hip_decode_batch: 2..8 sessions of a block-format model, f16 K/V): each session's single-token graph is built exactly as
+ * (ggml_hip_decode_batch: 2..8 sessions of a block-format or F16 model, or of a K-quant model under backend option plan_batch_k,
+ * f16 K/V; nothing on the host asks for the weights' type: the backend decides): each session's single-token graph is built exactly as
  * llm_evaluate builds it, and each session ends as after llm_evaluate(m, sessions[i], &tokens[i], 1, ...) — n_past, last_logits; the
  * token history stays the caller's, as there.  logits (nullable): B * n_vocab floats, row i = session i's.
  * Returns 1 if the step ran batched, 0 if the sessions were evaluated one after the other (the backend declined: same results),

@@ -1,7 +1,9 @@
 // kquant_plan.h — the helper launches of the K plan (llama_plan.inc plan_launch_k): a LLaMA whose matrices are Q2_K … Q6_K
 // (file types crates/llm-base/src/loader.rs:80-93, block structs crates/ggml/sys/src/lib.rs:2977-3303) decodes — and takes prompt
-// chunks of up to 8 tokens, the reference's default n_batch — as 10-13 launches per layer from a captured hipGraph instead of ~34
-// eager ones on the node-by-node executor.
+// chunks of up to 31 tokens (up to k_prompt_min - 1 by default), and, under option plan_batch_k, one token each of 2..8 sessions as
+// one batched step — as 10-13 launches per layer from a captured hipGraph instead of ~34 eager ones on the node-by-node executor.
+// A batched step is the chunk's launches; k_k_rope_store<true> is the one kernel here that places a column in a cache, and it reads
+// the per-column table (BatchCols) instead of "position n_past + n of one cache".
 //
 // Every kernel here performs the executor's floating-point operations in the executor's order on the same values — the
 // rms_norm of k_rms_norm<true> (thread t adds elements t, t + 256, … in f64, waves by DPP, (s0 + s1) + (s2 + s3)), the Q8_K
@@ -103,20 +105,28 @@ __global__ void __launch_bounds__(256) k_k_silu_mul_quant(const float *__restric
 
 // RoPE (mode 0, adjacent pairs, the token's (cos, sin) table of k_rope_table) on Q in place and on K; K -> f16 run at the
 // token's position, V -> f16 scatter into the transposed cache (crates/models/llama/src/lib.rs:191-244).
+// Where row n goes is the only thing the two forms differ in: a chunk's row n sits at position n_past + n of ONE session's caches
+// (mem_k / mem_v, the layer's offset applied); a batched step's column n (BATCH) sits at bc->pos[n] of ITS session's caches
+// bc->mem_k[n] / bc->mem_v[n] + kv_off (k_rope_table_batch made table n for that position).  The rotation and the stores are one text.
 struct KRopeStoreArgs {
     float *q;               // [N][E] rotated in place
     const float *k, *v;     // [N][Egqa] each
-    const float *rope;      // per token (blockIdx.y): D/2 (cos, sin) pairs, 128 floats apart (k_rope_table)
-    const DecParams *prm;
-    __half *mem_k, *mem_v;  // + layer offset
+    const float *rope;      // per token (blockIdx.y): D/2 (cos, sin) pairs, 128 floats apart (k_rope_table / k_rope_table_batch)
+    const DecParams *prm;   // chunk form
+    __half *mem_k, *mem_v;  // ... + layer offset
+    const BatchCols *bc;    // BATCH form: the per-column table (prm / mem_k / mem_v are not read)
+    int64_t kv_off;         // ... the layer's offset into every session's memory_k / memory_v (elements)
     int64_t E, Egqa, C;
     int D;
 };
+template <bool BATCH>
 __global__ void __launch_bounds__(256) k_k_rope_store(const KRopeStoreArgs a) {
     const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
     const int64_t nq = a.E >> 1, nk = a.Egqa >> 1;
-    const int64_t n = blockIdx.y;  // token of the chunk: position n_past + n, row n of q / k / v, table n
-    const int p = a.prm->n_past + (int)n;
+    const int64_t n = blockIdx.y;  // token of the chunk / column of the step: row n of q / k / v, table n
+    const int p = BATCH ? a.bc->pos[n] : a.prm->n_past + (int)n;
+    __half *const mem_k = BATCH ? a.bc->mem_k[n] + a.kv_off : a.mem_k;
+    __half *const mem_v = BATCH ? a.bc->mem_v[n] + a.kv_off : a.mem_v;
     float *const q = a.q + n * a.E;
     const float *const kr = a.k + n * a.Egqa, *const vr = a.v + n * a.Egqa, *const rope = a.rope + n * 128;
     if (t < nq + nk) {
@@ -128,14 +138,14 @@ __global__ void __launch_bounds__(256) k_k_rope_store(const KRopeStoreArgs a) {
         const float v0 = src[m0], v1 = src[m0 + 1];
         const float r0 = v0 * c - v1 * s, r1 = v0 * s + v1 * c;
         if (is_k) {
-            a.mem_k[(int64_t)p * a.Egqa + m0] = __float2half_rn(r0);
-            a.mem_k[(int64_t)p * a.Egqa + m0 + 1] = __float2half_rn(r1);
+            mem_k[(int64_t)p * a.Egqa + m0] = __float2half_rn(r0);
+            mem_k[(int64_t)p * a.Egqa + m0 + 1] = __float2half_rn(r1);
         } else {
             q[m0] = r0;
             q[m0 + 1] = r1;
         }
     } else if (t < nq + nk + a.Egqa) {
         const int64_t m = t - nq - nk;
-        a.mem_v[m * a.C + p] = __float2half_rn(vr[m]);
+        mem_v[m * a.C + p] = __float2half_rn(vr[m]);
     }
 }

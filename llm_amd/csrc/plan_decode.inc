@@ -418,7 +418,8 @@ static void plan_launch_all(DecodePlan *p, int av, LaunchCtx cx) {
 // *_K_S / *_K_M file types of crates/llm-base/src/loader.rs:80-93 mix them).  10-13 launches per layer (kernels/kquant_plan.h):
 //   norm+Q8_K | wq|wk|wv | rope + K/V store | attention | Q8_K | wo+residual | norm+Q8_K | w1|w3 | silu·mul+Q8_K | w2+residual
 // (matrices that share an activation row go out as ONE launch per run of equal types: 10 launches per layer for a uniform
-// model, up to 13 for a mixed one)
+// model, up to 13 for a mixed one); chunks of 2..31 tokens and batched steps of 2..8 sessions (option plan_batch_k) are the same launches
+// with N rows, the mat-vecs in passes of 8 / 4 / 2 / 1 columns
 // the mat-vecs are the node-by-node executor's k_mmvq_k / k_mmvq_k2 (same row sums), the attention is k_attn_decode over the
 // whole context.  Same `mask` / `kind_mask` protocol as plan_launch_all for the roofline leg (kinds: 0 wq+wk+wv, 1 wo,
 // 2 w1+w3, 3 w2, 4 lm_head).
@@ -524,9 +525,12 @@ static void launch_kbig(int nseg, const KWeight *const *ws, float *const *dsts, 
         with_kt(w.kt, [&](auto KT) { launch_kbig_x<CT(KT)>(ka, src.xsrc, lds, epi); });
     HIP_CHECK(hipGetLastError());
 }
-static void plan_launch_k(DecodePlan *p, int av, LaunchCtx cx) {
+// batch: a batched step (plan_launch_batch) — the chunk's helper-launch form with column c at its own session's position and cache
+// (BatchCols): the RoPE tables, the rope/store and the attention are the three launches that read the table; AV_SHORT always
+static void plan_launch_k(DecodePlan *p, int av, LaunchCtx cx, bool batch = false) {
     const bool long_ctx = av == AV_SPLIT;
     const bool kbig = kbig_ok(p);
+    if (batch && (kbig || long_ctx || !p->bcols)) die("K plan: a batched step runs on the helper-launch form at AV_SHORT (N %d)", p->m.N);
     const LlamaMatch &m = p->m;
     const int64_t E = m.E, F = m.F, nsbE = E / 256, nsbF = F / 256;
     const int N = m.N;  // 1 = decode; 2..8 = a prompt chunk (rows of every activation buffer, columns of every mat-vec)
@@ -562,11 +566,11 @@ static void plan_launch_k(DecodePlan *p, int av, LaunchCtx cx) {
             hipLaunchKernelGGL(k_k_norm_quant, dim3((unsigned)nsbE, (unsigned)N), dim3(256), 0, g.stream, x, w, m.eps, (int)E, y, p->k_q8, p->k_d8, p->k_bs);
         });
     };
-    plan_open_rows(p, cx, false, 4.6, [&] { dequant_k_rows(p->k_wte, (const int *)p->prm->tokens, N, p->xa, E); });
+    plan_open_rows(p, cx, batch, 4.6, [&] { dequant_k_rows(p->k_wte, (const int *)p->prm->tokens, N, p->xa, E); });
     for (int il = 0; il < m.L; il++) {
         const DecodePlan::KLW &w = p->klw[il];
         const DecodePlan::LayerNorms &nw = p->ln[il];
-        __half *mk = p->mem_k_at(il), *mv = p->mem_v_at(il);
+        __half *mk = batch ? nullptr : p->mem_k_at(il), *mv = batch ? nullptr : p->mem_v_at(il);
         norm_quant(p->xa, nw.attn_norm, nullptr);
         // big-workgroup form: RoPE and the K/V store ride in the epilogue of the wq / wk / wv launches (a unit = two adjacent rows of a
         // matrix, k_k_rope_store's expressions); one launch per run of equal types, as below
@@ -598,12 +602,15 @@ static void plan_launch_k(DecodePlan *p, int av, LaunchCtx cx) {
             mmvq(0, {&w.wq, &w.wk, &w.wv}, {p->q, p->k_kf, p->k_vf}, nullptr, attn_normed);
             cx.other((double)N * (E + 2 * m.Egqa) * 6.0, [&] {
                 KRopeStoreArgs ra;
+                memset(&ra, 0, sizeof(ra));
                 ra.q = p->q; ra.k = p->k_kf; ra.v = p->k_vf; ra.rope = p->rope; ra.prm = p->prm; ra.mem_k = mk; ra.mem_v = mv;
+                if (batch) { ra.bc = p->bcols; ra.kv_off = p->kv_off(il); }
                 ra.E = E; ra.Egqa = m.Egqa; ra.C = m.C; ra.D = (int)m.D;
-                hipLaunchKernelGGL(k_k_rope_store, dim3(grid1(E / 2 + m.Egqa / 2 + m.Egqa).x, (unsigned)N), dim3(256), 0, g.stream, ra);
+                const dim3 grid(grid1(E / 2 + m.Egqa / 2 + m.Egqa).x, (unsigned)N);
+                with_bool(batch, [&](auto BATCH) { hipLaunchKernelGGL(k_k_rope_store<CT(BATCH)>, grid, dim3(256), 0, g.stream, ra); });
             });
         }
-        if (!kfused) plan_attn_f32(p, cx, il, long_ctx, false);
+        if (!kfused) plan_attn_f32(p, cx, il, long_ctx, batch);
         if (!kbig) cx.other((double)N * E * 5.3, [&] { hipLaunchKernelGGL(k_k_quant, dim3((unsigned)nsbE, (unsigned)N), dim3(256), 0, g.stream, (const float *)p->k_att, p->k_q8, p->k_d8, p->k_bs); });
         mmvq(1, {&w.wo}, {p->xb}, p->xa, RowSrc{KX_F32, p->k_att, nullptr, 0.0f, nullptr});
         norm_quant(p->xb, nw.ffn_norm, nullptr);

@@ -239,6 +239,8 @@ static void plan_launch_multi(DecodePlan *p) { plan_launch_chunk(p, false); }
 static void plan_launch_batch(DecodePlan *p) {
     if (p->m.f16w)
         plan_launch_f16(p, AV_SHORT, LaunchCtx{}, true);
+    else if (p->m.kquant)
+        plan_launch_k(p, AV_SHORT, LaunchCtx{}, true);
     else
         plan_launch_chunk(p, true);
 }

@@ -626,7 +626,8 @@ static int decode_greedy_chain(ggml_cgraph *last, int n, int32_t *out_tokens, fl
 
 // ggml_hip_decode_batch: one decode step of B = 2..8 single-token LLaMA graphs of ONE model, each the reference's unchanged graph for
 // its own session (own memory_k / memory_v, own n_past, own token), as ONE pass over the weights: the chunk plan's launches
-// (plan_launch_batch) with column c placed by the per-column table instead of "position n_past + c of one cache".  One plan per
+// (plan_launch_batch) with column c placed by the per-column table instead of "position n_past + c of one cache".  Block-format and
+// F16 models; K-quant models (the K plan's chunk form) under option plan_batch_k.  One plan per
 // (B, model, context) and one hipGraph of it; a step uploads DecParams (the token ids) and BatchCols (positions, caches) and replays.
 // -1 with nothing executed when the graphs are not that; the caller then computes them one by one.
 //
@@ -668,16 +669,18 @@ static int decode_batch_steps(ggml_cgraph *const *graphs, int B, int n_steps, in
     for (int c = 0; c < B; c++) {
         LlamaMatch &m = ms[(size_t)c];
         if (!match_llama_decode(graphs[c], m)) return -1;
-        if (m.N != 1 || m.prompt || m.kquant || !m.wte || !m.output || !m.embd || !m.logits || !m.embedding) return -1;
-        if (m.n_past + n_steps > m.C || (qt_of(m.wtype) < 0 && !m.f16w)) return -1;  // (f16 K/V, D, E, F: the matcher's own preconditions)
+        if (m.kquant && !(g.opt_plan_batch_k && g.opt_plan_k)) return -1;  // a K-quant model: under option plan_batch_k, on the K plan
+        if (m.N != 1 || m.prompt || !m.wte || !m.output || !m.embd || !m.logits || !m.embedding) return -1;
+        if (m.n_past + n_steps > m.C || (qt_of(m.wtype) < 0 && !m.f16w && !m.kquant)) return -1;  // (f16 K/V, D, E, F: the matcher's own preconditions)
         for (const ggml_tensor *t : {m.memory_k, m.memory_v}) {  // a session of another slot keeps its cache to itself (extra_of would abort)
             const DevTensor *e = (const DevTensor *)t->extra;
             if (e && e->magic == 0x48495054 && e->slot != g_cur_slot()) return -1;
         }
     }
     // the whole context in k_attn_decode's LDS arrays (a column may sit anywhere in it), 8 Q8 columns of the widest row in k_mmvq_big8's
-    // (an F16 model: k_mmvq_f16 stages as many columns per pass as its LDS holds)
-    if (attn_decode_lds(ms[0].C, ms[0].D) > ATTN_DECODE_LDS_MAX || (!ms[0].f16w && !multi_shape_ok(ms[0], B))) return -1;
+    // (an F16 model: k_mmvq_f16 stages as many columns per pass as its LDS holds; a K-quant model: so does launch_mmvq_kn, and what a
+    // column of the K plan needs the matcher has checked for every graph)
+    if (attn_decode_lds(ms[0].C, ms[0].D) > ATTN_DECODE_LDS_MAX || (!ms[0].f16w && !ms[0].kquant && !multi_shape_ok(ms[0], B))) return -1;
     if (smp && !batch_sample_ok(*smp, B, ms[0].V)) return -1;
     ws_reset();
     for (int c = 0; c < B; c++) {
@@ -776,6 +779,10 @@ static int decode_batch_steps(ggml_cgraph *const *graphs, int B, int n_steps, in
     g.stat_plan_tokens += (uint64_t)B * (uint64_t)n_steps;
     g.stat_batch_tokens += (uint64_t)B * (uint64_t)n_steps;
     g.stat_batch_steps += (uint64_t)n_steps;
+    if (ms[0].kquant) {
+        g.stat_kplan_tokens += (uint64_t)B * (uint64_t)n_steps;
+        g.stat_batch_k_steps += (uint64_t)n_steps;
+    }
     if (smp) {  // (a sampled step is not a greedy one: batch_chain_* count ggml_hip_decode_batch_greedy's alone)
         g.stat_batch_sample_steps += (uint64_t)(n_steps - 1);
         g.stat_batch_sample_tokens += (uint64_t)(n_steps - 1) * (uint64_t)B;

@@ -2,7 +2,8 @@
 // get_rows + final norm/mul/lm_head, rebuilt by the caller for EVERY evaluation: crates/llm-base/src/inference_session.rs:230)
 // is recognised as a whole and executed as one of five launch sequences over the same cached DecodePlan:
 //   single-token decode, block formats (plan_launch_all): 3 launches per layer with wq|wk|wv + attention + wo fused, 5 without;
-//   single-token decode and chunks of up to 31 tokens, K-quants (plan_launch_k): 10-13 launches per layer;
+//   K-quants (plan_launch_k): single-token decode, 4-6 launches per layer on the big workgroups; chunks of up to 31 tokens and —
+//   option plan_batch_k — batched steps, 10-13 launches per layer on the helper-launch form;
 //   single-token decode, chunks of up to 31 tokens and batched steps, F16 weights (plan_launch_f16): 5 launches per layer;
 //   a chunk of 2..31 tokens, block formats (plan_launch_multi): 8 launches per layer and pass of 8 columns;
 //   a prompt batch (plan_launch_prompt): 13 launches per layer around the matrix-core GEMMs, launched eagerly;
@@ -57,7 +58,7 @@ struct LlamaMatch {
     int n_past = 0, n_dims = 0;
     int N = 1;  // tokens in this evaluation: 1 = decode, 2..31 below mmq_min = a prompt chunk (multi-token plan), >= mmq_min = prompt plan
     bool prompt = false;  // the prompt plan takes it
-    bool kquant = false;  // every matrix is a K-quant (any mix of Q2_K … Q6_K): the K plan (plan_launch_k), single-token decode only
+    bool kquant = false;  // every matrix is a K-quant (any mix of Q2_K … Q6_K): the K plan (plan_launch_k): decode, chunks of up to 31 tokens below k_prompt_min, batched steps (option plan_batch_k)
     bool f16w = false;    // every matrix is F16 (file type 1): the F16 plan (plan_launch_f16), decode, chunks and batched steps
     float eps = 0, freq_base = 0, freq_scale = 0, kq_scale = 0;
     ggml_type wtype = GGML_TYPE_F32;

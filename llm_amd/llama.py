@@ -264,8 +264,9 @@ class Llama:
 
     def evaluate_batch(self, sessions, tokens):
         """One decode step of several sessions of this model, tokens[i] for sessions[i], as ONE pass over the weights where the
-        backend can (llm_evaluate_batch: 2..8 sessions of a block-format model with f16 K/V; anything else is evaluated one
-        session after the other, with the same results).  Returns (ran_batched, logits [B, n_vocab]); every session ends as
+        backend can (llm_evaluate_batch: 2..8 sessions with f16 K/V of a block-format or F16 model, or of a K-quant model — Q2_K …
+        Q6_K, uniform or a *_K_M / *_K_S mix — once ggml.set_option("plan_batch_k", 1) is set (default 0); anything else is
+        evaluated one session after the other, with the same results).  Returns (ran_batched, logits [B, n_vocab]); every session ends as
         after evaluate([token]).  ValueError, with nothing evaluated: a session listed twice, of another model or device slot,
         a token outside the vocabulary, a session whose context is full."""
         tokens = np.ascontiguousarray(tokens, dtype=np.int32)
@@ -290,8 +291,9 @@ class Llama:
 
     def infer_tokens_batch(self, sessions, n):
         """n greedy tokens for each of several sessions of this model, sampled on the device where the backend can
-        (llm_infer_tokens_greedy_batch_device: every step one pass over the weights, no host round trip between steps; anything
-        else runs as n steps of infer_next_tokens_batch, with the same results).  Returns (ran_chained, ids [n, B]).  ValueError,
+        (llm_infer_tokens_greedy_batch_device: every step one pass over the weights, no host round trip between steps; the models
+        evaluate_batch takes batched, K-quant models under option plan_batch_k included; anything else runs as n steps of
+        infer_next_tokens_batch, with the same results).  Returns (ran_chained, ids [n, B]).  ValueError,
         with nothing evaluated: the bad arguments of evaluate_batch, n < 1, a session without room for n tokens."""
         ptrs = (C.c_void_p * len(sessions))(*[s.ptr for s in sessions])
         out = np.zeros((max(int(n), 0), len(sessions)), np.int32)
@@ -323,7 +325,8 @@ class Llama:
 
     def infer_tokens_sampled_batch(self, sessions, n, rngs, k=40, top_p=0.95, temperature=0.8, penalty=1.30):
         """n such tokens for each session, all but the first drawn on the device where the backend can
-        (llm_infer_tokens_sampled_batch_device: no host round trip between steps; k <= 256); anything else runs as n steps of
+        (llm_infer_tokens_sampled_batch_device: no host round trip between steps; k <= 256; the models evaluate_batch takes
+        batched, K-quant models under option plan_batch_k included); anything else runs as n steps of
         infer_next_tokens_sampled_batch, with the same ids, sessions and generator states.  Returns (ran_chained, ids [n, B]).
         ValueError as above, and for n < 1 or a session without room for n tokens."""
         ptrs = (C.c_void_p * len(sessions))(*[s.ptr for s in sessions])
