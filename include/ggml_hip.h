@@ -729,12 +729,12 @@ GGML_API int ggml_hip_debug_token_tail_prepare(const float *logits, int V, const
                                                int half_d, int32_t *id_out, int32_t *prm_out, float *row, float *table,
                                                uint32_t *epoch_out, uint16_t *save, float *row_ref, float *table_ref,
                                                uint32_t *epoch_ref, uint16_t *save_ref);
-/* Test hook: k_batch_argmax_next (the kernel between two steps of ggml_hip_decode_batch_greedy) alone.  logits [B][V], B = 1..8;
+/* Test hook: k_argmax_next with a BatchCols (the kernel between two steps of ggml_hip_decode_batch_greedy) alone.  logits [B][V], B = 1..8;
  * pos_in[8] and tokens_in[32] are the positions and token ids a step's parameters hold before it.  Out: ids_out[B] the sampled ids,
  * prm_out[34] = n_past, token, tokens[0..32) and pos_out[8] as the kernel left them.  0, or -1 for arguments it cannot take. */
 GGML_API int ggml_hip_debug_batch_tail(const float *logits, int B, int V, const int32_t *pos_in, const int32_t *tokens_in,
                                        int32_t *ids_out, int32_t *prm_out, int32_t *pos_out);
-/* Test hook: k_batch_sample_next (the kernel between two steps of ggml_hip_decode_batch_sampled) alone, n_draws (1 .. 4096) launches
+/* Test hook: k_sample_next with a BatchCols (the kernel between two steps of ggml_hip_decode_batch_sampled) alone, n_draws (1 .. 4096) launches
  * on the same rows.  logits [B][V], B = 1..8; pos_in[8] / tokens_in[32] as above; hist [8][64] and hist_n[8] are the columns'
  * history rings (hist_n[c] tokens pushed so far: min(hist_n, 64) entries hold, the next goes to slot hist_n % 64), rng[8] the
  * generator states: all three in / out, all 8 entries.  Out: ids_out [n_draws][B], prm_out[34], pos_out[8] as above.  0, or -1

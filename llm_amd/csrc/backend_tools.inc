@@ -585,7 +585,7 @@ int ggml_hip_debug_token_tail(const float *logits, int V, const float *emb, int 
     if (emb) HIP_CHECK(hipMemcpy(de, emb, (size_t)E * 4, hipMemcpyHostToDevice));
     HIP_CHECK(hipMemcpy(pa, &hp, sizeof(hp), hipMemcpyHostToDevice));
     HIP_CHECK(hipMemcpy(pb, &hp, sizeof(hp), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_argmax_next, dim3(1), dim3(1024), 0, g.stream, (const float *)dl, V, pa, ida);
+    hipLaunchKernelGGL(k_argmax_next, dim3(1), dim3(1024), 0, g.stream, (const float *)dl, V, pa, (BatchCols *)nullptr, ida);
     hipLaunchKernelGGL(k_token_tail, dim3(TOKEN_TAIL_WGS), dim3(1024), 0, g.stream, (const float *)dl, V, emb ? (const float *)de : (const float *)nullptr,
                        E, pb, slot, (int)emb_off, (int)id_off, TailPrep{});
     HIP_CHECK(hipGetLastError());
@@ -666,7 +666,7 @@ int ggml_hip_debug_token_tail_prepare(const float *logits, int V, const void *wt
     }
     hipLaunchKernelGGL(k_token_tail, dim3(token_tail_grid(!zeroed, (long)L * Egqa)), dim3(1024), 0, g.stream, (const float *)dl, V,
                        (const float *)nullptr, 0, prm[0], slot, (int)id_off, (int)id_off, tp);
-    hipLaunchKernelGGL(k_argmax_next, dim3(1), dim3(1024), 0, g.stream, (const float *)dl, V, prm[1], ida);
+    hipLaunchKernelGGL(k_argmax_next, dim3(1), dim3(1024), 0, g.stream, (const float *)dl, V, prm[1], (BatchCols *)nullptr, ida);
     hipLaunchKernelGGL(k_kv_row_save, dim3((unsigned)std::min<int64_t>(256, ((int64_t)L * Egqa + 255) / 256)), dim3(256), 0, g.stream,
                        (const DecParams *)prm[1], (const __half *)dk, (const __half *)dv, (__half *)dsave[1], L, C, Egqa);
     hipLaunchKernelGGL(k_get_rows_q, dim3((unsigned)((nb + 255) / 256), 1), dim3(256), 0, g.stream, w, (const int *)&prm[1]->token,
@@ -738,122 +738,6 @@ int ggml_hip_decode_batch_sampled(struct ggml_cgraph *const *graphs, int n_graph
     return r;
 }
 
-// ---- test hook: k_batch_argmax_next alone (tests/test_batch_chain_gpu.py) ----
-// logits [B][V], pos_in[8] and tokens_in[32] go to the device as a step's BatchCols::pos and DecParams::tokens (n_past = pos_in[0],
-// token = tokens_in[0]); the kernel runs once on B workgroups.  Out: ids_out[B], prm_out[34] = n_past, token, tokens[0..32),
-// pos_out[8].  0, or -1 for arguments it cannot take.
-int ggml_hip_debug_batch_tail(const float *logits, int B, int V, const int32_t *pos_in, const int32_t *tokens_in, int32_t *ids_out,
-                              int32_t *prm_out, int32_t *pos_out) {
-    if (!logits || B < 1 || B > BATCH_COLS_MAX || V < 1 || !pos_in || !tokens_in || !ids_out || !prm_out || !pos_out) return -1;
-    SlotLock lk;
-    ensure_init();
-    finish_pending();
-    const size_t lb = ((size_t)B * V * 4 + 255) & ~(size_t)255;
-    char *d = nullptr;
-    dev_malloc((void **)&d, lb + 1024, "debug batch tail");
-    DecParams *dp = (DecParams *)(d + lb);
-    BatchCols *db = (BatchCols *)(d + lb + 256);
-    int *dids = (int *)(d + lb + 768);
-    static_assert(sizeof(DecParams) <= 256 && sizeof(BatchCols) <= 512 && BATCH_COLS_MAX * 4 <= 256, "debug batch tail: layout");
-    DecParams hp;
-    BatchCols hb;
-    memset(&hp, 0, sizeof(hp));
-    memset(&hb, 0, sizeof(hb));
-    for (int i = 0; i < 32; i++) hp.tokens[i] = tokens_in[i];
-    for (int i = 0; i < BATCH_COLS_MAX; i++) hb.pos[i] = pos_in[i];
-    hp.n_past = pos_in[0];
-    hp.token = tokens_in[0];
-    HIP_CHECK(hipStreamSynchronize(g.stream));
-    HIP_CHECK(hipMemcpy(d, logits, (size_t)B * V * 4, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(dp, &hp, sizeof(hp), hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(db, &hb, sizeof(hb), hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemset(dids, 0xff, BATCH_COLS_MAX * 4));
-    hipLaunchKernelGGL(k_batch_argmax_next, dim3((unsigned)B), dim3(1024), 0, g.stream, (const float *)d, V, dp, db, dids);
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipStreamSynchronize(g.stream));
-    HIP_CHECK(hipMemcpy(ids_out, dids, (size_t)B * 4, hipMemcpyDeviceToHost));
-    HIP_CHECK(hipMemcpy(&hp, dp, sizeof(hp), hipMemcpyDeviceToHost));
-    HIP_CHECK(hipMemcpy(&hb, db, sizeof(hb), hipMemcpyDeviceToHost));
-    prm_out[0] = hp.n_past;
-    prm_out[1] = hp.token;
-    for (int i = 0; i < 32; i++) prm_out[2 + i] = hp.tokens[i];
-    for (int i = 0; i < BATCH_COLS_MAX; i++) pos_out[i] = hb.pos[i];
-    HIP_CHECK(hipFree(d));
-    return 0;
-}
-
-// ---- test hook: k_batch_sample_next alone (tests/test_batch_sample_gpu.py) ----
-// As above, with the columns' rings, counts and generator states (8 entries each, in / out) and n_draws launches on the same rows.
-int ggml_hip_debug_batch_sample(const float *logits, int B, int V, const ggml_hip_sampler *params, const int32_t *pos_in,
-                                const int32_t *tokens_in, int32_t *hist, int32_t *hist_n, uint64_t *rng, int n_draws, int32_t *ids_out,
-                                int32_t *prm_out, int32_t *pos_out) {
-    if (!logits || B < 1 || B > BATCH_COLS_MAX || V < 1 || !params || !pos_in || !tokens_in || !hist || !hist_n || !rng || !ids_out ||
-        !prm_out || !pos_out || n_draws < 1 || n_draws > BATCH_CHAIN_MAX_STEPS)
-        return -1;
-    if (params->k < 1 || params->k > SAMPLER_K_MAX || params->k > V || !(params->temperature > 0.0f) || !(params->top_p > 0.0f) ||
-        !(params->penalty > 0.0f))
-        return -1;
-    for (int c = 0; c < BATCH_COLS_MAX; c++) {
-        if (hist_n[c] < 0) return -1;
-        for (int i = 0; i < std::min(hist_n[c], SAMPLER_WINDOW); i++)
-            if (c < B && (hist[c * SAMPLER_WINDOW + i] < 0 || hist[c * SAMPLER_WINDOW + i] >= V)) return -1;
-    }
-    SlotLock lk;
-    ensure_init();
-    finish_pending();
-    const size_t lb = ((size_t)B * V * 4 + 255) & ~(size_t)255, sb = (sizeof(SampleCols) + 255) & ~(size_t)255;
-    const size_t ib = ((size_t)n_draws * B * 4 + 255) & ~(size_t)255;
-    char *d = nullptr;
-    dev_malloc((void **)&d, lb + 1024 + sb + ib, "debug batch sample");
-    DecParams *dp = (DecParams *)(d + lb);
-    BatchCols *db = (BatchCols *)(d + lb + 256);
-    unsigned long long *dr = (unsigned long long *)(d + lb + 768);
-    SampleCols *ds = (SampleCols *)(d + lb + 1024);
-    int *dids = (int *)(d + lb + 1024 + sb);
-    static_assert(sizeof(DecParams) <= 256 && sizeof(BatchCols) <= 512 && BATCH_COLS_MAX * 8 <= 256, "debug batch sample: layout");
-    DecParams hp;
-    BatchCols hb;
-    SampleCols hs;
-    memset(&hp, 0, sizeof(hp));
-    memset(&hb, 0, sizeof(hb));
-    memset(&hs, 0, sizeof(hs));
-    for (int i = 0; i < 32; i++) hp.tokens[i] = tokens_in[i];
-    for (int i = 0; i < BATCH_COLS_MAX; i++) hb.pos[i] = pos_in[i];
-    hp.n_past = pos_in[0];
-    hp.token = tokens_in[0];
-    memcpy(hs.hist, hist, sizeof(hs.hist));
-    memcpy(hs.hist_n, hist_n, sizeof(hs.hist_n));
-    hs.k = params->k;
-    hs.top_p = params->top_p;
-    hs.temperature = params->temperature;
-    hs.penalty = params->penalty;
-    HIP_CHECK(hipStreamSynchronize(g.stream));
-    HIP_CHECK(hipMemcpy(d, logits, (size_t)B * V * 4, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(dp, &hp, sizeof(hp), hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(db, &hb, sizeof(hb), hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(ds, &hs, sizeof(hs), hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(dr, rng, BATCH_COLS_MAX * 8, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemset(dids, 0xff, (size_t)n_draws * B * 4));
-    for (int i = 0; i < n_draws; i++)
-        hipLaunchKernelGGL(k_batch_sample_next, dim3((unsigned)B), dim3(1024), 0, g.stream, (const float *)d, V, dp, db, ds, dr,
-                           dids + (size_t)i * B);
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipStreamSynchronize(g.stream));
-    HIP_CHECK(hipMemcpy(ids_out, dids, (size_t)n_draws * B * 4, hipMemcpyDeviceToHost));
-    HIP_CHECK(hipMemcpy(&hp, dp, sizeof(hp), hipMemcpyDeviceToHost));
-    HIP_CHECK(hipMemcpy(&hb, db, sizeof(hb), hipMemcpyDeviceToHost));
-    HIP_CHECK(hipMemcpy(&hs, ds, sizeof(hs), hipMemcpyDeviceToHost));
-    HIP_CHECK(hipMemcpy(rng, dr, BATCH_COLS_MAX * 8, hipMemcpyDeviceToHost));
-    prm_out[0] = hp.n_past;
-    prm_out[1] = hp.token;
-    for (int i = 0; i < 32; i++) prm_out[2 + i] = hp.tokens[i];
-    for (int i = 0; i < BATCH_COLS_MAX; i++) pos_out[i] = hb.pos[i];
-    memcpy(hist, hs.hist, sizeof(hs.hist));
-    memcpy(hist_n, hs.hist_n, sizeof(hs.hist_n));
-    HIP_CHECK(hipFree(d));
-    return 0;
-}
-
 int ggml_hip_decode_sampled_chain(struct ggml_cgraph *last, int n, const ggml_hip_sampler *params, const int32_t *window, int window_n,
                                   uint64_t *rng, int32_t *out_tokens, float *last_logits) {
     if (!last || n < 1 || !params || !rng || !out_tokens || window_n < 0 || window_n > SAMPLER_WINDOW || (window_n > 0 && !window))
@@ -863,71 +747,100 @@ int ggml_hip_decode_sampled_chain(struct ggml_cgraph *last, int n, const ggml_hi
     return decode_chain(last, n, out_tokens, last_logits, &smp);
 }
 
-// ---- test hook: k_sample_next alone (tests/test_sample_chain_gpu.py) ----
-// One row of logits [V]; n_past_in and tokens_in[32] go to the device as DecParams (token = tokens_in[0]), hist[64] / hist_n / rng as
-// the session's ring, count and generator state (in / out); n_draws launches on the same row, the form the chain would pick for V.
-// Out: ids_out[n_draws], prm_out[34] = n_past, token, tokens[0..32).  0, or -1 for arguments it cannot take.
-int ggml_hip_debug_sample_next(const float *logits, int V, const ggml_hip_sampler *params, int n_past_in, const int32_t *tokens_in,
-                               int32_t *hist, int32_t *hist_n, uint64_t *rng, int n_draws, int32_t *ids_out, int32_t *prm_out) {
-    if (!logits || V < 1 || !params || !tokens_in || !hist || !hist_n || !rng || !ids_out || !prm_out || n_draws < 1 ||
+// ---- test hooks: the kernel between two steps of a chain, alone.  One body of the three hooks below. ----
+// logits [B][V]; tokens_in[32] go to the device as DecParams::tokens (token = tokens_in[0]) at n_past, pos_in[8] as a step's
+// BatchCols::pos (null: no BatchCols, one session at n_past).  Without params: k_argmax_next on B workgroups.  With params: the sampler,
+// in the form a chain picks for V, on the caller's rings, counts and generator states — T entries each, in / out, T = 8 with a BatchCols
+// and 1 without; a count beyond 64 is a full ring; entries from B on are not checked and make the round trip untouched.  n_draws
+// launches on the same rows.  Out: ids_out[n_draws][B], prm_out[34] = n_past, token, tokens[0..32), pos_out[8] (with a BatchCols).
+// 0, or -1 for arguments the hook or the chain cannot take.
+static int debug_next_token(const float *logits, int B, int V, const ggml_hip_sampler *params, int n_past, const int32_t *pos_in,
+                            const int32_t *tokens_in, int32_t *hist, int32_t *hist_n, uint64_t *rng, int n_draws, int32_t *ids_out,
+                            int32_t *prm_out, int32_t *pos_out) {
+    const int T = pos_in ? BATCH_COLS_MAX : 1;
+    if (!logits || B < 1 || B > T || V < 1 || !tokens_in || !ids_out || !prm_out || (pos_in && !pos_out) || n_draws < 1 ||
         n_draws > BATCH_CHAIN_MAX_STEPS)
         return -1;
-    {
-        const int32_t wn = std::min(*hist_n, SAMPLER_WINDOW);  // (a count beyond 64: the ring is full)
-        if (*hist_n < 0) return -1;
-        const BatchSample smp = {params, hist, &wn, rng};
-        if (!batch_sample_ok(smp, 1, V)) return -1;
+    if (params) {
+        if (!hist || !hist_n || !rng) return -1;
+        int32_t wn[BATCH_COLS_MAX];
+        for (int c = 0; c < B; c++) {
+            if (hist_n[c] < 0) return -1;
+            wn[c] = std::min(hist_n[c], SAMPLER_WINDOW);
+        }
+        const BatchSample smp = {params, hist, wn, rng};
+        if (!batch_sample_ok(smp, B, V)) return -1;
     }
     SlotLock lk;
     ensure_init();
     finish_pending();
-    const size_t lb = ((size_t)V * 4 + 255) & ~(size_t)255, sb = (sizeof(SampleOne) + 255) & ~(size_t)255;
-    const size_t ib = ((size_t)n_draws * 4 + 255) & ~(size_t)255;
-    char *d = nullptr;
-    dev_malloc((void **)&d, lb + 512 + sb + ib, "debug sample next");
-    DecParams *dp = (DecParams *)(d + lb);
-    unsigned long long *dr = (unsigned long long *)(d + lb + 256);
-    SampleOne *ds = (SampleOne *)(d + lb + 512);
-    int *dids = (int *)(d + lb + 512 + sb);
-    static_assert(sizeof(DecParams) <= 256, "debug sample next: layout");
     DecParams hp;
-    SampleOne hs;
+    BatchCols hb;
+    SampleCols hs;
     memset(&hp, 0, sizeof(hp));
+    memset(&hb, 0, sizeof(hb));
     memset(&hs, 0, sizeof(hs));
     for (int i = 0; i < 32; i++) hp.tokens[i] = tokens_in[i];
-    hp.n_past = n_past_in;
+    hp.n_past = n_past;
     hp.token = tokens_in[0];
-    memcpy(hs.hist, hist, sizeof(hs.hist));
-    hs.hist_n = *hist_n;
-    hs.k = params->k;
-    hs.top_p = params->top_p;
-    hs.temperature = params->temperature;
-    hs.penalty = params->penalty;
-    HIP_CHECK(hipStreamSynchronize(g.stream));
-    HIP_CHECK(hipMemcpy(d, logits, (size_t)V * 4, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(dp, &hp, sizeof(hp), hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(ds, &hs, sizeof(hs), hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(dr, rng, 8, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemset(dids, 0xff, (size_t)n_draws * 4));
+    for (int i = 0; pos_in && i < BATCH_COLS_MAX; i++) hb.pos[i] = pos_in[i];
+    if (params) {
+        memcpy(hs.hist, hist, (size_t)T * SAMPLER_WINDOW * 4);
+        memcpy(hs.hist_n, hist_n, (size_t)T * 4);
+        hs.k = params->k;
+        hs.top_p = params->top_p;
+        hs.temperature = params->temperature;
+        hs.penalty = params->penalty;
+    }
+    std::vector<char *> owned;
+    const float *dl = (const float *)debug_buf((size_t)B * V * 4, logits, owned);
+    DecParams *dp = (DecParams *)debug_buf(sizeof(hp), &hp, owned);
+    BatchCols *db = pos_in ? (BatchCols *)debug_buf(sizeof(hb), &hb, owned) : nullptr;
+    SampleCols *ds = (SampleCols *)debug_buf(sizeof(hs), &hs, owned);
+    unsigned long long *dr = (unsigned long long *)debug_buf((size_t)T * 8, params ? rng : nullptr, owned);
+    int *dids = (int *)debug_buf((size_t)n_draws * B * 4, nullptr, owned);
     for (int i = 0; i < n_draws; i++) {
-        if (V <= SELECT_CAP)
-            hipLaunchKernelGGL(k_sample_next<true>, dim3(1), dim3(1024), 0, g.stream, (const float *)d, V, dp, ds, dr, dids + i);
-        else
-            hipLaunchKernelGGL(k_sample_next<false>, dim3(1), dim3(1024), 0, g.stream, (const float *)d, V, dp, ds, dr, dids + i);
+        if (params) launch_sample_next(g.stream, B, dl, V, dp, db, ds, dr, dids + (size_t)i * B);
+        else hipLaunchKernelGGL(k_argmax_next, dim3((unsigned)B), dim3(1024), 0, g.stream, dl, V, dp, db, dids + (size_t)i * B);
     }
     HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipStreamSynchronize(g.stream));
-    HIP_CHECK(hipMemcpy(ids_out, dids, (size_t)n_draws * 4, hipMemcpyDeviceToHost));
-    HIP_CHECK(hipMemcpy(&hp, dp, sizeof(hp), hipMemcpyDeviceToHost));
-    HIP_CHECK(hipMemcpy(&hs, ds, sizeof(hs), hipMemcpyDeviceToHost));
-    HIP_CHECK(hipMemcpy(rng, dr, 8, hipMemcpyDeviceToHost));
+    d2h_queue(ids_out, (const char *)dids, (size_t)n_draws * B * 4);
+    d2h_queue(&hp, (const char *)dp, sizeof(hp));
+    if (db) d2h_queue(&hb, (const char *)db, sizeof(hb));
+    if (params) {
+        d2h_queue(&hs, (const char *)ds, sizeof(hs));
+        d2h_queue(rng, (const char *)dr, (size_t)T * 8);
+    }
+    d2h_finish();
     prm_out[0] = hp.n_past;
     prm_out[1] = hp.token;
     for (int i = 0; i < 32; i++) prm_out[2 + i] = hp.tokens[i];
-    memcpy(hist, hs.hist, sizeof(hs.hist));
-    *hist_n = hs.hist_n;
-    HIP_CHECK(hipFree(d));
+    for (int i = 0; pos_in && i < BATCH_COLS_MAX; i++) pos_out[i] = hb.pos[i];
+    if (params) {
+        memcpy(hist, hs.hist, (size_t)T * SAMPLER_WINDOW * 4);
+        memcpy(hist_n, hs.hist_n, (size_t)T * 4);
+    }
+    for (char *b : owned) HIP_CHECK(hipFree(b));
     return 0;
+}
+// k_argmax_next with a BatchCols, once (tests/test_batch_chain_gpu.py): n_past = pos_in[0]
+int ggml_hip_debug_batch_tail(const float *logits, int B, int V, const int32_t *pos_in, const int32_t *tokens_in, int32_t *ids_out,
+                              int32_t *prm_out, int32_t *pos_out) {
+    if (!pos_in) return -1;
+    return debug_next_token(logits, B, V, nullptr, pos_in[0], pos_in, tokens_in, nullptr, nullptr, nullptr, 1, ids_out, prm_out, pos_out);
+}
+// k_sample_next with a BatchCols (tests/test_batch_sample_gpu.py): hist [8][64], hist_n[8], rng[8]
+int ggml_hip_debug_batch_sample(const float *logits, int B, int V, const ggml_hip_sampler *params, const int32_t *pos_in,
+                                const int32_t *tokens_in, int32_t *hist, int32_t *hist_n, uint64_t *rng, int n_draws, int32_t *ids_out,
+                                int32_t *prm_out, int32_t *pos_out) {
+    if (!params || !pos_in) return -1;
+    return debug_next_token(logits, B, V, params, pos_in[0], pos_in, tokens_in, hist, hist_n, rng, n_draws, ids_out, prm_out, pos_out);
+}
+// k_sample_next for one session at n_past_in (tests/test_sample_chain_gpu.py): one row, hist[64], *hist_n, *rng
+int ggml_hip_debug_sample_next(const float *logits, int V, const ggml_hip_sampler *params, int n_past_in, const int32_t *tokens_in,
+                               int32_t *hist, int32_t *hist_n, uint64_t *rng, int n_draws, int32_t *ids_out, int32_t *prm_out) {
+    if (!params) return -1;
+    return debug_next_token(logits, 1, V, params, n_past_in, nullptr, tokens_in, hist, hist_n, rng, n_draws, ids_out, prm_out, nullptr);
 }
 
 int64_t ggml_hip_get_stat(const char *key) {

@@ -110,7 +110,7 @@ void commit_step(llm_session *const *sessions, int B, const int32_t *next, int32
 }
 }  // namespace
 
-// ---- the sampled batched chain's host side.  The sampler is kernels/sampler_math.h — the header k_batch_sample_next compiles — so
+// ---- the sampled batched chain's host side.  The sampler is kernels/sampler_math.h — the header k_sample_next compiles — so
 // the ids drawn here and on the device are the same ids.
 static bool sampler_params_ok(const llm_sampler_params *p, size_t V) {
     return p && p->k >= 1 && (size_t)p->k <= V && p->temperature > 0.0f && p->top_p > 0.0f && p->penalty > 0.0f;

@@ -86,38 +86,32 @@ __device__ __forceinline__ int argmax_first_block(const float *__restrict__ logi
     }
     return bi;
 }
+// The next replay's parameters, by thread 0 of the workgroup that sampled `id` for column c: the column's token id and its position
+// + 1.  bc is the table of a batched step (plan_launch_batch), or null for one session at DecParams::n_past.  Column 0 also keeps the
+// two fields a step uploads for it (token, n_past) in line.  Returns the new position.
+__device__ __forceinline__ int write_next_token(DecParams *prm, BatchCols *bc, int c, int id) {
+    const int pos = bc ? bc->pos[c] + 1 : prm->n_past + 1;
+    prm->tokens[c] = id;
+    if (bc) bc->pos[c] = pos;
+    if (c == 0) {
+        prm->token = id;
+        prm->n_past = pos;
+    }
+    return pos;
+}
 // Greedy sampling on the device: token = first index of the maximum logit — what a host loop
 // `if (l[i] > l[best]) best = i` returns — written straight into the decode parameters of the NEXT replay of the plan
-// (token id, position + 1) and into out[0], so that a chain of greedy tokens needs neither the 128 KB logits
-// read-back nor a host round trip per token.  One 1024-thread workgroup.
-__global__ void __launch_bounds__(1024) k_argmax_next(const float *__restrict__ logits, int V, DecParams *prm,
+// (write_next_token) and into out[c], so that a chain of greedy tokens needs neither the 128 KB logits read-back nor a host round
+// trip per token.  Grid = the number of columns, 1024 threads each: workgroup c samples row c of logits [B][V], on its own row and
+// its own entries — nothing is handed between workgroups, and entries from the grid's size on are not touched.
+__global__ void __launch_bounds__(1024) k_argmax_next(const float *__restrict__ logits, int V, DecParams *prm, BatchCols *bc,
                                                       int *__restrict__ out) {
-    const int bi = argmax_first_block(logits, V);
-    if (threadIdx.x == 0) {
-        prm->token = bi;
-        prm->tokens[0] = bi;
-        prm->n_past = prm->n_past + 1;
-        out[0] = bi;
-    }
-}
-// The same for a batched step (plan_launch_batch): workgroup c samples column c's row of logits [B][V] and writes the parameters the
-// step's next replay reads for that column — its token id, its position + 1 — and out[c].  Workgroup 0 also keeps the two fields a
-// step uploads for column 0 (token, n_past) in line.  Grid = B workgroups, each on its own row and its own entries: nothing is
-// handed between workgroups, and entries from B on are not touched.
-__global__ void __launch_bounds__(1024) k_batch_argmax_next(const float *__restrict__ logits, int V, DecParams *prm, BatchCols *bc,
-                                                            int *__restrict__ out) {
     const int c = blockIdx.x;
     if (c >= BATCH_COLS_MAX) return;
     const int bi = argmax_first_block(logits + (size_t)c * V, V);
     if (threadIdx.x == 0) {
-        const int pos = bc->pos[c] + 1;
-        prm->tokens[c] = bi;
-        bc->pos[c] = pos;
+        write_next_token(prm, bc, c, bi);
         out[c] = bi;
-        if (c == 0) {
-            prm->token = bi;
-            prm->n_past = pos;
-        }
     }
 }
 // The K row and the V column of position prm->n_past, every layer, saved before a greedy token's graph writes them (its first kernel
@@ -266,10 +260,7 @@ __global__ void __launch_bounds__(1024) k_token_tail(const float *__restrict__ l
         if (bi >= 0 && bi < tp.wte.M) tail_embed_row(tp.wte, bi, tp.xnext);
     }
     if (threadIdx.x == 0) {
-        const int bi = bi0, pos = prm->n_past + 1;
-        prm->token = bi;
-        prm->tokens[0] = bi;
-        prm->n_past = pos;
+        const int bi = bi0, pos = write_next_token(prm, nullptr, 0, bi);
         if (prep) *tp.pos_out = pos;
         *(int *)(slot + id_off) = bi;
     }

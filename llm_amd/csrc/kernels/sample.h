@@ -1,17 +1,17 @@
-// sample.h — the device samplers of the sampled chains: k_batch_sample_next (2 .. 8 sessions, below) and k_sample_next (one session,
-// further down, with the on-chip selection sample_select).
-// k_batch_sample_next: the tail of a SAMPLED batched decode step (ggml_hip_decode_batch_sampled, plan_run.inc).  What
-// k_batch_argmax_next (decode.h) is to the greedy chain, with the sampler of kernels/sampler_math.h in place of the first maximum:
-// repetition penalty over the column's last 64 tokens, top-k, top-p, temperature, one xorshift64* draw.  The arithmetic is that
-// header's, which the host mirror (llm_sample_exact) compiles too: the chain draws the ids the stepped loop draws.
+// sample.h — the device sampler of the sampled chains, 1 .. 8 sessions: k_sample_next, the kernel between two steps of
+// ggml_hip_decode_sampled_chain (one session) and of ggml_hip_decode_batch_sampled (2 .. 8 sessions; plan_run.inc).  What k_argmax_next
+// (decode.h) is to the greedy chains, with the sampler of kernels/sampler_math.h in place of the first maximum: repetition penalty
+// over the column's last 64 tokens, top-k, top-p, temperature, one xorshift64* draw.  The arithmetic is that header's, which the host
+// mirror (llm_sample_exact) compiles too: the chain draws the ids the stepped loop draws.
 #pragma once
 #include "common.h"
 #include "decode.h"
 #include "sampler_math.h"
 #include "topk.h"
 
-// Per-column sampler state of a batched plan, uploaded once per call: the history ring of each column (min(hist_n, 64) entries hold;
-// the next token goes to slot hist_n % 64) and the chain's four parameters.  The generator states travel beside the sampled ids.
+// Per-column sampler state of a plan (one session: column 0), uploaded once per call: the history ring of each column (min(hist_n, 64)
+// entries hold; the next token goes to slot hist_n % 64) and the chain's four parameters.  The generator states travel beside the
+// sampled ids.
 struct SampleCols {
     int hist[BATCH_COLS_MAX][SAMPLER_WINDOW];
     int hist_n[BATCH_COLS_MAX];
@@ -19,102 +19,15 @@ struct SampleCols {
     float top_p, temperature, penalty;
 };
 
-// Grid = B workgroups of 1024 threads; workgroup c works on row c of logits [B][V] and on entry c of every table — nothing is handed
-// between workgroups, and entries from B on are not touched.
-//   selection   topk_kth_key (k_topk's radix passes) finds the k-th largest raw key; the window's tokens (each id once) enter with
-//               their penalised values, the raw top-k without the window's tokens beside them: <= k + 64 keys, bitonic-sorted in LDS
-//               by (value descending, id ascending) — topk_key's order;
-//   q, p        one thread per candidate (f32: sampler_q / sampler_p);
-//   serial tail thread 0: sampler_pick, then the next replay's parameters (DecParams::tokens[c], BatchCols::pos[c] + 1, workgroup 0
-//               also token / n_past), out[c], the id into the column's ring, the advanced generator state.
-// k is 1 .. min(SAMPLER_K_MAX, V) (the host declines anything else; the kernel writes nothing then).
-__global__ void __launch_bounds__(1024) k_batch_sample_next(const float *__restrict__ logits, int V, DecParams *prm, BatchCols *bc,
-                                                            SampleCols *sc, unsigned long long *rng, int *__restrict__ out) {
-    constexpr int PMAX = 512;  // power of two >= SAMPLER_K_MAX + SAMPLER_WINDOW
-    static_assert(PMAX >= SAMPLER_K_MAX + SAMPLER_WINDOW, "k_batch_sample_next: LDS keys");
-    __shared__ unsigned long long s_keys[PMAX];
-    __shared__ float s_v[SAMPLER_K_MAX], s_q[SAMPLER_K_MAX], s_p[SAMPLER_K_MAX];
-    __shared__ int s_id[SAMPLER_K_MAX], s_h[SAMPLER_WINDOW], s_win[SAMPLER_WINDOW];
-    __shared__ int s_cnt, s_wn;
-    const int c = blockIdx.x, tid = threadIdx.x;
-    const int k = sc->k;
-    if (c >= BATCH_COLS_MAX || k < 1 || k > SAMPLER_K_MAX || k > V) return;
-    const float *x = logits + (size_t)c * V;
-    const float penalty = sc->penalty, temperature = sc->temperature;
-    const int hn = sc->hist_n[c];
-    const int nw = hn < SAMPLER_WINDOW ? (hn < 0 ? 0 : hn) : SAMPLER_WINDOW;
-    int P = 1;
-    while (P < k + nw) P <<= 1;
-    for (int i = tid; i < P; i += 1024) s_keys[i] = 0;  // (below every key of a row without NaN)
-    if (tid < SAMPLER_WINDOW) s_h[tid] = tid < nw ? sc->hist[c][tid] : -1;
-    if (tid == 0) {
-        s_cnt = 0;
-        s_wn = 0;
-    }
-    __syncthreads();
-    if (tid < nw) {  // the window's tokens, each id once, with their penalised values
-        const int id = s_h[tid];
-        bool take = id >= 0 && id < V;
-        for (int j = 0; j < tid; j++) take = take && s_h[j] != id;
-        if (take) {
-            s_win[atomicAdd(&s_wn, 1)] = id;
-            s_keys[atomicAdd(&s_cnt, 1)] = topk_key(sampler_penalise(x[id], penalty), id);
-        }
-    }
-    const unsigned long long kth = topk_kth_key(x, V, k);  // (opens with a barrier: s_win / s_wn are complete behind it)
-    const int wn = s_wn;
-    for (int i = tid; i < V; i += 1024) {  // the raw top-k, without the window's tokens
-        const unsigned long long key = topk_key(x[i], i);
-        if (key >= kth) {
-            bool in_window = false;
-            for (int j = 0; j < wn; j++) in_window = in_window || s_win[j] == i;
-            if (!in_window) s_keys[atomicAdd(&s_cnt, 1)] = key;
-        }
-    }
-    __syncthreads();
-    topk_bitonic_desc(s_keys, P);
-    if (tid < k) {  // at least k keys went in
-        const unsigned long long key = s_keys[tid];
-        const uint32_t o = (uint32_t)(key >> 32);
-        const uint32_t u = (o & 0x80000000u) ? (o ^ 0x80000000u) : ~o;
-        s_v[tid] = __builtin_bit_cast(float, u);
-        s_id[tid] = (int)(0xFFFFFFFFu - (uint32_t)(key & 0xFFFFFFFFull));
-    }
-    __syncthreads();
-    if (tid < k) {
-        const float v0 = s_v[0];
-        s_q[tid] = sampler_q(s_v[tid], v0);
-        s_p[tid] = sampler_p(s_v[tid], v0, temperature);
-    }
-    __syncthreads();
-    if (tid == 0) {
-        uint64_t state = rng[c];
-        const int id = s_id[sampler_pick(s_q, s_p, k, sc->top_p, &state)];
-        rng[c] = state;
-        const int pos = bc->pos[c] + 1;
-        prm->tokens[c] = id;
-        bc->pos[c] = pos;
-        out[c] = id;
-        if (c == 0) {
-            prm->token = id;
-            prm->n_past = pos;
-        }
-        sc->hist[c][(unsigned)hn % SAMPLER_WINDOW] = id;
-        sc->hist_n[c] = hn + 1;
-    }
-}
-
-// ---- one session: k_sample_next, the tail of a step of ggml_hip_decode_sampled_chain (plan_run.inc).  What k_argmax_next (decode.h)
-// is to the greedy chain of the single-token plan, with the same sampler as above.
-//
-// The new part is the selection.  k_batch_sample_next reads its row nine times from L2 (eight radix passes of one dependent load
-// per thread and iteration, then the gather); beside a 1.1 ms token that is most of the distance to the stepped loop.  Here the row
-// is fetched ONCE, eight independent 16-byte loads in flight per thread, and stays on chip for every pass and for the gather.
+// ---- the selection: which keys of the row are its k largest.  Over global memory (topk_kth_key, k_topk's radix passes) the row is
+// read nine times from L2 (eight passes of one dependent load per thread and iteration, then the gather); beside a 1.1 ms token that
+// is most of the distance to the stepped loop.  On chip the row is fetched ONCE, eight independent 16-byte loads in flight per
+// thread, and stays there for every pass and for the gather.
 // On chip means REGISTERS, 32 values per thread (thread t: ids 32 t .. 32 t + 31), V <= SELECT_CAP = 32768: a 32000-float row in
 // LDS would be 125 KB of the CU's 160 KB — no room beside k_topk's tables for a wider vocabulary than the registers take anyway,
 // every pass would read it back through the LDS pipe the histogram's atomics already queue at, and __launch_bounds__(1024) leaves
-// 128 VGPRs of which the row takes 32.  Wider rows (template argument ONCHIP = false; the host picks by V) take topk_kth_key over
-// global memory, as the batched kernel does.
+// 128 VGPRs of which the row takes 32.  Wider rows (template argument ONCHIP = false; launch_sample_next picks by V alone, for every
+// number of columns) take topk_kth_key over global memory.
 //
 // sample_select: which of this thread's values belong to the k largest keys of the row (topk_key order), as a bit mask.
 //   value bits  four radix passes of 8 bits over the order-preserving image of the VALUE (the high word of topk_key), histogram in
@@ -242,39 +155,39 @@ __device__ __forceinline__ uint32_t sample_select(const float (&v)[SELECT_PER_TH
     return gt;
 }
 
-// One session's sampler state on the device, uploaded once per call: column 0 of SampleCols in a struct of its own.
-struct SampleOne {
-    int hist[SAMPLER_WINDOW];
-    int hist_n;
-    int k;
-    float top_p, temperature, penalty;
-};
-
-// One workgroup of 1024 threads.  The steps are k_batch_sample_next's for one row; only the selection differs (above).  Thread 0
-// writes prm->token, prm->tokens[0], prm->n_past + 1, out[0], the ring slot hist_n % 64, hist_n + 1 and the advanced generator
-// state, and nothing else is written; nothing at all for k outside 1 .. min(SAMPLER_K_MAX, V) (the host declines those).
+// Grid = B workgroups of 1024 threads; workgroup c works on row c of logits [B][V] and on entry c of every table (sc->hist[c],
+// sc->hist_n[c], rng[c], out[c]) — nothing is handed between workgroups, no workgroup waits for another, and entries from B on are
+// not touched.  bc is the table of a batched step, or null for one session at DecParams::n_past (write_next_token, decode.h).
+//   selection   the k largest raw keys of the row: sample_select over the row in registers (ONCHIP), or topk_kth_key over global
+//               memory and a scan of the row against the k-th key.  The window's tokens (each id once) enter with their penalised
+//               values, the raw top-k without the window's tokens beside them: <= k + 64 keys, bitonic-sorted in LDS by (value
+//               descending, id ascending) — topk_key's order.  Both selections yield the same set of keys, so the same sorted keys;
+//   q, p        one thread per candidate (f32: sampler_q / sampler_p);
+//   serial tail thread 0: sampler_pick, then the next replay's parameters (write_next_token), out[c], the id into the column's ring
+//               slot hist_n % 64, hist_n + 1, the advanced generator state.
+// k is 1 .. min(SAMPLER_K_MAX, V), and V <= SELECT_CAP on chip (the host declines / picks so; the kernel writes nothing otherwise).
 template <bool ONCHIP>
-__global__ void __launch_bounds__(1024) k_sample_next(const float *__restrict__ logits, int V, DecParams *prm, SampleOne *st,
-                                                      unsigned long long *rng, int *__restrict__ out) {
+__global__ void __launch_bounds__(1024) k_sample_next(const float *__restrict__ logits, int V, DecParams *prm, BatchCols *bc,
+                                                      SampleCols *sc, unsigned long long *rng, int *__restrict__ out) {
     constexpr int PMAX = 512;  // power of two >= SAMPLER_K_MAX + SAMPLER_WINDOW
     static_assert(PMAX >= SAMPLER_K_MAX + SAMPLER_WINDOW, "k_sample_next: LDS keys");
     __shared__ unsigned long long s_keys[PMAX];
     __shared__ float s_v[SAMPLER_K_MAX], s_q[SAMPLER_K_MAX], s_p[SAMPLER_K_MAX];
     __shared__ int s_id[SAMPLER_K_MAX], s_h[SAMPLER_WINDOW], s_win[SAMPLER_WINDOW];
     __shared__ int s_cnt, s_wn;
-    const int tid = threadIdx.x;
-    const int k = st->k;
-    if (k < 1 || k > SAMPLER_K_MAX || k > V || (ONCHIP && V > SELECT_CAP)) return;
-    const float *x = logits;
-    float v[SELECT_PER_THREAD];
-    if (ONCHIP) sample_select_load(x, V, v);  // (in flight while the window is set up)
-    const float penalty = st->penalty, temperature = st->temperature;
-    const int hn = st->hist_n;
+    const int c = blockIdx.x, tid = threadIdx.x;
+    const int k = sc->k;
+    if (c >= BATCH_COLS_MAX || k < 1 || k > SAMPLER_K_MAX || k > V || (ONCHIP && V > SELECT_CAP)) return;
+    const float *x = logits + (size_t)c * V;
+    [[maybe_unused]] float v[ONCHIP ? SELECT_PER_THREAD : 1];
+    if constexpr (ONCHIP) sample_select_load(x, V, v);  // (in flight while the window is set up)
+    const float penalty = sc->penalty, temperature = sc->temperature;
+    const int hn = sc->hist_n[c];
     const int nw = hn < SAMPLER_WINDOW ? (hn < 0 ? 0 : hn) : SAMPLER_WINDOW;
     int P = 1;
     while (P < k + nw) P <<= 1;
     for (int i = tid; i < P; i += 1024) s_keys[i] = 0;  // (below every key of a row without NaN)
-    if (tid < SAMPLER_WINDOW) s_h[tid] = tid < nw ? st->hist[tid] : -1;
+    if (tid < SAMPLER_WINDOW) s_h[tid] = tid < nw ? sc->hist[c][tid] : -1;
     if (tid == 0) {
         s_cnt = 0;
         s_wn = 0;
@@ -290,28 +203,23 @@ __global__ void __launch_bounds__(1024) k_sample_next(const float *__restrict__ 
         }
     }
     // the raw top-k, without the window's tokens (both selections open with a barrier: s_win / s_wn are complete behind it)
-    if (ONCHIP) {
+    const auto gather = [&](unsigned long long key, int id, int wn) {
+        bool in_window = false;
+        for (int j = 0; j < wn; j++) in_window = in_window || s_win[j] == id;
+        if (!in_window) s_keys[atomicAdd(&s_cnt, 1)] = key;
+    };
+    if constexpr (ONCHIP) {
         const uint32_t in = sample_select(v, V, k);
         const int wn = s_wn;
 #pragma unroll
-        for (int i = 0; i < SELECT_PER_THREAD; i++) {
-            if ((in >> i) & 1u) {
-                const int id = tid * SELECT_PER_THREAD + i;
-                bool in_window = false;
-                for (int j = 0; j < wn; j++) in_window = in_window || s_win[j] == id;
-                if (!in_window) s_keys[atomicAdd(&s_cnt, 1)] = topk_key(v[i], id);
-            }
-        }
+        for (int i = 0; i < SELECT_PER_THREAD; i++)
+            if ((in >> i) & 1u) gather(topk_key(v[i], tid * SELECT_PER_THREAD + i), tid * SELECT_PER_THREAD + i, wn);
     } else {
         const unsigned long long kth = topk_kth_key(x, V, k);
         const int wn = s_wn;
         for (int i = tid; i < V; i += 1024) {
             const unsigned long long key = topk_key(x[i], i);
-            if (key >= kth) {
-                bool in_window = false;
-                for (int j = 0; j < wn; j++) in_window = in_window || s_win[j] == i;
-                if (!in_window) s_keys[atomicAdd(&s_cnt, 1)] = key;
-            }
+            if (key >= kth) gather(key, i, wn);
         }
     }
     __syncthreads();
@@ -331,14 +239,20 @@ __global__ void __launch_bounds__(1024) k_sample_next(const float *__restrict__ 
     }
     __syncthreads();
     if (tid == 0) {
-        uint64_t state = rng[0];
-        const int id = s_id[sampler_pick(s_q, s_p, k, st->top_p, &state)];
-        rng[0] = state;
-        prm->token = id;
-        prm->tokens[0] = id;
-        prm->n_past = prm->n_past + 1;
-        out[0] = id;
-        st->hist[(unsigned)hn % SAMPLER_WINDOW] = id;
-        st->hist_n = hn + 1;
+        uint64_t state = rng[c];
+        const int id = s_id[sampler_pick(s_q, s_p, k, sc->top_p, &state)];
+        rng[c] = state;
+        write_next_token(prm, bc, c, id);
+        out[c] = id;
+        sc->hist[c][(unsigned)hn % SAMPLER_WINDOW] = id;
+        sc->hist_n[c] = hn + 1;
     }
+}
+// The one launch of the sampler, for the chain, the batched chain and the test hook: B columns, the selection picked from V alone.
+static inline void launch_sample_next(hipStream_t stream, int B, const float *logits, int V, DecParams *prm, BatchCols *bc, SampleCols *sc,
+                                      unsigned long long *rng, int *out) {
+    if (V <= SELECT_CAP)
+        hipLaunchKernelGGL(k_sample_next<true>, dim3((unsigned)B), dim3(1024), 0, stream, logits, V, prm, bc, sc, rng, out);
+    else
+        hipLaunchKernelGGL(k_sample_next<false>, dim3((unsigned)B), dim3(1024), 0, stream, logits, V, prm, bc, sc, rng, out);
 }

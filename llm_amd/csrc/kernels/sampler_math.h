@@ -1,5 +1,5 @@
-// sampler_math.h — the arithmetic of the sampled batched chain (top-k / repetition penalty / top-p / temperature / draw), written
-// ONCE for the device (k_batch_sample_next, kernels/sample.h) and the host mirror (llm_sample_exact, host/llm_infer.cpp). The chain's
+// sampler_math.h — the arithmetic of the sampled chains (top-k / repetition penalty / top-p / temperature / draw), written
+// ONCE for the device (k_sample_next, kernels/sample.h) and the host mirror (llm_sample_exact, host/llm_infer.cpp). The chain's
 // contract is equality with the stepped loop, ids byte for byte, so nothing here calls a library transcendental: only IEEE f32 / f64
 // multiply, add, subtract, divide, rintf and integer construction of a power of two, which round identically on both sides when
 // neither contracts a multiply and an add (-ffp-contract=off, as the whole library is built).  Plain C++ where __HIPCC__ is absent.
@@ -22,7 +22,7 @@
 #define SAMPLER_FN inline
 #endif
 
-constexpr int SAMPLER_K_MAX = 256;   // k_batch_sample_next's LDS budget
+constexpr int SAMPLER_K_MAX = 256;   // k_sample_next's LDS budget
 constexpr int SAMPLER_WINDOW = 64;   // tokens of history the repetition penalty looks at
 
 // e^x for x <= 0, Cephes' expf scheme in separate f32 operations: exactly 0 below -80 (and for NaN), exactly 1 at 0; relative error

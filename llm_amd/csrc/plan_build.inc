@@ -200,7 +200,7 @@ static void plan_pool_layout(DecodePlan *p, PoolCarver &c) {
     c.take(p->ogran, one ? (size_t)m.L * (size_t)(m.E / 32) * OGRAN * 8 : 0);  // the heads' outputs as granules (WO form)
     // a batched step's per-column table and its results, one row per column: the other plans' logits_out / emb_out are graph nodes (build_plan)
     c.take(p->bcols, p->batch ? sizeof(BatchCols) : 0);
-    c.take(p->scols, p->batch ? sizeof(SampleCols) : 0);
+    c.take(p->scols, p->batch || (spec && m.wte) ? sizeof(SampleCols) : 0);  // (a single-token whole-model plan: ggml_hip_decode_sampled_chain's one column)
     c.take(p->logits_out, p->batch ? R * m.V * 4 : 0);
     c.take(p->emb_out, p->batch ? R * E * 4 : 0);
     c.take(p->prm, sizeof(DecParams));

@@ -494,6 +494,38 @@ static bool batch_sample_ok(const BatchSample &s, int B, int64_t V) {
     }
     return true;
 }
+// A sampled chain's state goes up, once per call: the B columns' history rings and the four parameters into the plan's SampleCols,
+// the B generator states to the front of chain_out, which gets room for n_ids ids behind them.  Returns where the ids start.
+static int sample_cols_fill(DecodePlan *p, const BatchSample &s, int B, int n_ids) {
+    chain_out_reserve(p, SAMPLE_RNG_WORDS + n_ids);
+    SampleCols hs;
+    memset(&hs, 0, sizeof(hs));
+    for (int c = 0; c < B; c++) {
+        hs.hist_n[c] = s.window_n[c];
+        for (int i = 0; i < s.window_n[c]; i++) hs.hist[c][i] = s.windows[c * SAMPLER_WINDOW + i];
+    }
+    hs.k = s.prm->k;
+    hs.top_p = s.prm->top_p;
+    hs.temperature = s.prm->temperature;
+    hs.penalty = s.prm->penalty;
+    h2d_small((char *)p->scols, &hs, sizeof(hs));
+    h2d_small((char *)p->chain_out, s.rng, (size_t)B * 8);
+    return SAMPLE_RNG_WORDS;
+}
+// ... and comes back out of the chain's read-back of chain_out (the generator states, then the ids); out_ids may be null
+static void sample_cols_back(const std::vector<int32_t> &sample_back, const BatchSample &s, int B, int32_t *out_ids) {
+    memcpy(s.rng, sample_back.data(), (size_t)B * 8);
+    if (out_ids) memcpy(out_ids, sample_back.data() + SAMPLE_RNG_WORDS, (sample_back.size() - SAMPLE_RNG_WORDS) * 4);
+}
+// The kernel between two steps of a chain: every column's next token from its row of `logits`, into the parameters of the step's next
+// replay and out[c] — the first maximum, or (sampled) a draw of the sampler whose state sample_cols_fill has uploaded.  p->bcols is
+// null on a single-token plan: one session at DecParams::n_past.
+static void launch_next_token(DecodePlan *p, int B, const float *logits, bool sampled, int *out) {
+    if (sampled)
+        launch_sample_next(g.stream, B, logits, (int)p->m.V, p->prm, p->bcols, p->scols, (unsigned long long *)p->chain_out, out);
+    else
+        hipLaunchKernelGGL(k_argmax_next, dim3((unsigned)B), dim3(1024), 0, g.stream, logits, (int)p->m.V, p->prm, p->bcols, out);
+}
 
 // SURVEY section 8f N3: n greedy tokens back to back without a host round trip per token.  `last` must be the cgraph
 // of the caller's most recent ggml_graph_compute (a single-token LLaMA evaluation that ran as the fused plan, whole
@@ -503,11 +535,11 @@ static bool batch_sample_ok(const BatchSample &s, int B, int64_t V) {
 // the precondition does not hold (the caller then decodes token by token).
 //
 // ggml_hip_decode_sampled_chain is the same chain with k_sample_next (kernels/sample.h) between two replays (`smp`, one column of a
-// BatchSample): the session's history ring and the four parameters go up once per call (DecodePlan::chain_sone), the generator state
-// sits in front of the ids in chain_out and comes back with them in one copy.  Every plan the greedy chain runs is run: block-format,
-// K-quant, F16.  Option chain_k does not apply: the K-token graph stays greedy-only.  Counted in sample_chain_steps /
-// sample_chain_tokens and, as the greedy chain, in plan_tokens, fused_tokens, fused_heads_tokens and graph_replays.
-constexpr int SAMPLE_ONE_RNG_WORDS = 2;  // chain_out of a sampled chain of one session: the 64-bit generator state, then the ids
+// BatchSample): the session's history ring and the four parameters go up once per call (column 0 of DecodePlan::scols), the generator
+// state sits in front of the ids in chain_out and comes back with them in one copy (sample_cols_fill / sample_cols_back, as for the
+// batched chain).  Every plan the greedy chain runs is run: block-format, K-quant, F16.  Option chain_k does not apply: the K-token
+// graph stays greedy-only.  Counted in sample_chain_steps / sample_chain_tokens and, as the greedy chain, in plan_tokens,
+// fused_tokens, fused_heads_tokens and graph_replays.
 static int decode_chain(ggml_cgraph *last, int n, int32_t *out_tokens, float *last_logits, const BatchSample *smp = nullptr) {
     finish_pending();
     DecodePlan *p = live_plan(g.chain_plan);
@@ -525,34 +557,11 @@ static int decode_chain(ggml_cgraph *last, int n, int32_t *out_tokens, float *la
     // the first argmax reads the set the last evaluated token sits in; every replay below writes set 0
     const float *first_logits = (const float *)plan_cur_logits(p);
     g.res_plan = nullptr;
-    const int ids_off = smp ? SAMPLE_ONE_RNG_WORDS : 0;
-    chain_out_reserve(p, ids_off + n);
-    int *ids = p->chain_out + ids_off;
     if (!p->chain_ring) HIP_CHECK(hipMalloc((void **)&p->chain_ring, 64 * 4));
-    if (smp) {  // the ring, the parameters, the generator state: once per call
-        if (!p->chain_sone) HIP_CHECK(hipMalloc((void **)&p->chain_sone, sizeof(SampleOne)));
-        SampleOne hs;
-        memset(&hs, 0, sizeof(hs));
-        hs.hist_n = smp->window_n[0];
-        for (int i = 0; i < smp->window_n[0]; i++) hs.hist[i] = smp->windows[i];
-        hs.k = smp->prm->k;
-        hs.top_p = smp->prm->top_p;
-        hs.temperature = smp->prm->temperature;
-        hs.penalty = smp->prm->penalty;
-        h2d_small((char *)p->chain_sone, &hs, sizeof(hs));
-        h2d_small((char *)p->chain_out, smp->rng, 8);
-    }
-    // the kernel between two replays: the next token from `logits`, into the parameters of the next replay and ids[i]
-    const auto sample_next = [&](const float *logits, int i) {
-        if (!smp)
-            hipLaunchKernelGGL(k_argmax_next, dim3(1), dim3(1024), 0, g.stream, logits, (int)m.V, p->prm, ids + i);
-        else if (m.V <= SELECT_CAP)
-            hipLaunchKernelGGL(k_sample_next<true>, dim3(1), dim3(1024), 0, g.stream, logits, (int)m.V, p->prm, p->chain_sone,
-                               (unsigned long long *)p->chain_out, ids + i);
-        else
-            hipLaunchKernelGGL(k_sample_next<false>, dim3(1), dim3(1024), 0, g.stream, logits, (int)m.V, p->prm, p->chain_sone,
-                               (unsigned long long *)p->chain_out, ids + i);
-    };
+    int ids_off = 0;
+    if (smp) ids_off = sample_cols_fill(p, *smp, 1, n);  // the ring, the parameters, the generator state: once per call
+    else chain_out_reserve(p, n);
+    int *ids = p->chain_out + ids_off;
     const bool use_graph = g.opt_graph && !g.timing.on && p->any_captured();
     int i0 = 0;
     // option chain_k = K (> 1): K tokens per graph launch — every kernel of the plan reads its token and position from the
@@ -571,8 +580,7 @@ static int decode_chain(ggml_cgraph *last, int n, int32_t *out_tokens, float *la
                 if (p->graph_chain) (void)hipGraphDestroy(p->graph_chain);
                 capture_into(&p->graph_chain, &p->exec_chain, [&] {
                     for (int k = 0; k < K; k++) {
-                        hipLaunchKernelGGL(k_argmax_next, dim3(1), dim3(1024), 0, g.stream, (const float *)p->logits_out, (int)m.V, p->prm,
-                                           p->chain_ring + k);
+                        launch_next_token(p, 1, (const float *)p->logits_out, false, p->chain_ring + k);
                         plan_launch_decode(p, AV_SHORT);
                     }
                 });
@@ -585,7 +593,7 @@ static int decode_chain(ggml_cgraph *last, int n, int32_t *out_tokens, float *la
         }
     }
     for (int i = i0; i < n; i++) {
-        sample_next(i == 0 ? first_logits : (const float *)p->logits_out, i);
+        launch_next_token(p, 1, i == 0 ? first_logits : (const float *)p->logits_out, smp != nullptr, ids + i);
         // the token of step i sits at position n_past + 1 + i; same rule as try_decode_plan for the attention variant
         const int av = attn_variant(m, p, m.n_past + 1 + i + 1);
         // (the chain's books are not count_token_forms': no fused_wo_tokens, fused_affine_tokens or split_tokens — values tests read; left as they are)
@@ -611,8 +619,7 @@ static int decode_chain(ggml_cgraph *last, int n, int32_t *out_tokens, float *la
     token_results_queue(p);
     token_finish(false);  // a hand-off that gave up inside the chain has already fed the sampler garbage: abort
     if (smp) {
-        memcpy(smp->rng, sample_back.data(), 8);
-        memcpy(out_tokens, sample_back.data() + ids_off, (size_t)n * 4);
+        sample_cols_back(sample_back, *smp, 1, out_tokens);
         g.stat_sample_chain_steps += (uint64_t)n;
         g.stat_sample_chain_tokens += (uint64_t)n;
     }
@@ -632,28 +639,17 @@ static int decode_greedy_chain(ggml_cgraph *last, int n, int32_t *out_tokens, fl
 // -1 with nothing executed when the graphs are not that; the caller then computes them one by one.
 //
 // ggml_hip_decode_batch_greedy: the same step, then n_steps - 1 more of the same B sessions, each on the first maximum of its
-// column's logits, without a host round trip between them: k_batch_argmax_next (kernels/decode.h) samples every column on the device
-// and writes the parameters the step's kernels read (DecParams::tokens[c], BatchCols::pos[c]), and the SAME graph is replayed — the
+// column's logits, without a host round trip between them: k_argmax_next (kernels/decode.h) on B workgroups samples every column and
+// writes the parameters the step's kernels read (DecParams::tokens[c], BatchCols::pos[c]), and the SAME graph is replayed — the
 // launches n batched steps of a greedy caller make, on the same inputs, so the same bits.  The tail kernel is an ordinary launch
 // between two graph launches; the step's graph is the one ggml_hip_decode_batch captured.  The sampled ids [n_steps - 1][B] collect
 // on the device and come back with the results of the last step, which go where a single step leaves them.  Nothing of this
 // outlives the call: the next step of any kind uploads its own parameters.
 //
-// ggml_hip_decode_batch_sampled: the same chain with k_batch_sample_next (kernels/sample.h) as the tail — repetition penalty over the
-// column's last 64 tokens, top-k, top-p, temperature and one xorshift64* draw, in the arithmetic of kernels/sampler_math.h, which
-// the host mirror compiles too.  The columns' history rings and the four parameters go up once per call (DecodePlan::scols); the
+// ggml_hip_decode_batch_sampled: the same chain with k_sample_next (kernels/sample.h), B workgroups, as the tail — repetition penalty
+// over the column's last 64 tokens, top-k, top-p, temperature and one xorshift64* draw, in the arithmetic of kernels/sampler_math.h,
+// which the host mirror compiles too.  The columns' history rings and the four parameters go up once per call (DecodePlan::scols); the
 // generator states sit in front of the sampled ids in chain_out and come back with them in one copy.
-static void sample_cols_fill(SampleCols &hs, const BatchSample &s, int B) {
-    memset(&hs, 0, sizeof(hs));
-    for (int c = 0; c < B; c++) {
-        hs.hist_n[c] = s.window_n[c];
-        for (int i = 0; i < s.window_n[c]; i++) hs.hist[c][i] = s.windows[c * SAMPLER_WINDOW + i];
-    }
-    hs.k = s.prm->k;
-    hs.top_p = s.prm->top_p;
-    hs.temperature = s.prm->temperature;
-    hs.penalty = s.prm->penalty;
-}
 static int decode_batch_steps(ggml_cgraph *const *graphs, int B, int n_steps, int32_t *out_ids, bool chain, const BatchSample *smp = nullptr) {
     ensure_init();
     finish_pending();
@@ -737,28 +733,17 @@ static int decode_batch_steps(ggml_cgraph *const *graphs, int B, int n_steps, in
     step();
     if (n_steps > 1) {  // the device samples every column and moves the step's parameters on; ids of step i at chain_out[(i - 1) * B ..]
         const int n_ids = (n_steps - 1) * B;
-        chain_out_reserve(p, n_ids + (smp ? SAMPLE_RNG_WORDS : 0));
-        int *ids = p->chain_out + (smp ? SAMPLE_RNG_WORDS : 0);
-        if (smp) {
-            SampleCols hs;
-            sample_cols_fill(hs, *smp, B);
-            uint64_t hr[BATCH_COLS_MAX] = {0};
-            for (int c = 0; c < B; c++) hr[c] = smp->rng[c];
-            h2d_small((char *)p->scols, &hs, sizeof(hs));
-            h2d_small((char *)p->chain_out, hr, sizeof(hr));
-        }
+        int ids_off = 0;
+        if (smp) ids_off = sample_cols_fill(p, *smp, B, n_ids);
+        else chain_out_reserve(p, n_ids);
+        int *ids = p->chain_out + ids_off;
         for (int i = 1; i < n_steps; i++) {
-            if (smp)
-                hipLaunchKernelGGL(k_batch_sample_next, dim3((unsigned)B), dim3(1024), 0, g.stream, (const float *)p->logits_out, (int)ms[0].V,
-                                   p->prm, p->bcols, p->scols, (unsigned long long *)p->chain_out, ids + (size_t)(i - 1) * B);
-            else
-                hipLaunchKernelGGL(k_batch_argmax_next, dim3((unsigned)B), dim3(1024), 0, g.stream, (const float *)p->logits_out, (int)ms[0].V,
-                                   p->prm, p->bcols, ids + (size_t)(i - 1) * B);
+            launch_next_token(p, B, (const float *)p->logits_out, smp != nullptr, ids + (size_t)(i - 1) * B);
             step();
         }
         HIP_CHECK(hipGetLastError());
         if (smp) {  // the generator states and the ids: one copy
-            sample_back.resize((size_t)(SAMPLE_RNG_WORDS + n_ids));
+            sample_back.resize((size_t)(ids_off + n_ids));
             d2h_queue(sample_back.data(), (const char *)p->chain_out, sample_back.size() * 4);
         } else if (out_ids) {
             d2h_queue(out_ids, (const char *)p->chain_out, (size_t)n_ids * 4);
@@ -791,10 +776,7 @@ static int decode_batch_steps(ggml_cgraph *const *graphs, int B, int n_steps, in
         g.stat_batch_chain_tokens += (uint64_t)(n_steps - 1) * (uint64_t)B;
     }
     d2h_finish();
-    if (!sample_back.empty()) {
-        memcpy(smp->rng, sample_back.data(), (size_t)B * 8);
-        if (out_ids) memcpy(out_ids, sample_back.data() + SAMPLE_RNG_WORDS, (sample_back.size() - SAMPLE_RNG_WORDS) * 4);
-    }
+    if (!sample_back.empty()) sample_cols_back(sample_back, *smp, B, out_ids);
     g.ns_match += t1 - t0;
     g.ns_launch += t2 - t1;
     g.ns_wait += now_ns() - t2;

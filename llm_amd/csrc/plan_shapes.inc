@@ -132,7 +132,9 @@ struct DecodePlan {
     // uploaded with prm for every step.  Its logits_out / emb_out are rows of the pool (one per column), not a graph's nodes; mem_k / mem_v are unused.
     bool batch = false;
     BatchCols *bcols = nullptr;
-    SampleCols *scols = nullptr;  // ggml_hip_decode_batch_sampled: the columns' history rings and the sampler's parameters (k_batch_sample_next)
+    // the sampled chains (ggml_hip_decode_batch_sampled; ggml_hip_decode_sampled_chain on a single-token whole-model plan, column 0):
+    // the columns' history rings and the sampler's parameters (k_sample_next)
+    SampleCols *scols = nullptr;
     // persistent activations
     char *pool = nullptr;
     DecParams *prm = nullptr;
@@ -180,7 +182,6 @@ struct DecodePlan {
     int *chain_out = nullptr;   // ggml_hip_decode_greedy_chain / ggml_hip_decode_batch_greedy: sampled ids (device)
     int *chain_ring = nullptr;  // ... of one K-token graph launch (option chain_k), copied into chain_out behind it
     int chain_cap = 0;
-    SampleOne *chain_sone = nullptr;  // ggml_hip_decode_sampled_chain: the session's history ring and the sampler's parameters (k_sample_next), made at the first such chain
     VariantGraphs graphs[AV_COUNT];  // per attention variant; a batched step's plan has the one of AV_SHORT
     bool any_captured() const {
         for (const VariantGraphs &v : graphs)
@@ -222,7 +223,6 @@ void drop_plan_graphs(DecodePlan *p) {
 void destroy_plan(DecodePlan *p) {
     drop_plan_graphs(p);
     if (p->chain_ring) (void)hipFree(p->chain_ring);
-    if (p->chain_sone) (void)hipFree(p->chain_sone);
     if (p->chain_out) (void)hipFree(p->chain_out);
     if (p->pool) (void)hipFree(p->pool);
     for (int q = 0; q < 2; q++) {

@@ -9,6 +9,9 @@ One step, from a row of logits (free of NaN), a window of token ids and {k, top_
   3. p_i = exp_((v_i - v_0) / temperature), S = sum_{i<m} p_i in f64; xorshift64*; u = ((x * 0x2545F4914F6CDD1D) >> 11) / 2^53 * S;
      the first i with u < acc_i, else candidate m - 1.
 exp_ is sampler_exp: Cephes' expf scheme in separate f32 operations, exactly 0 below -80."""
+import os
+import re
+
 import numpy as np
 
 F = np.float32
@@ -130,3 +133,22 @@ def window_for(row, k, n, seed=0):
     for i in range(n):
         picks.append(int(top[g.integers(0, top.size)]) if i % 2 == 0 else int(g.integers(0, V)))
     return np.array(picks, dtype=np.int32)
+
+
+# ---- the cases of "the kernel alone", for one session (tests/test_sample_chain_gpu.py) and for B columns (tests/test_batch_sample_gpu.py)
+def _cap():
+    """Rows up to this many entries take the on-chip selection, longer ones topk_kth_key over global memory (kernels/sample.h)."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    src = open(os.path.join(root, "llm_amd", "csrc", "kernels", "sample.h")).read()
+    per_thread = int(re.search(r"constexpr int SELECT_PER_THREAD = (\d+);", src).group(1))
+    assert "constexpr int SELECT_CAP = 1024 * SELECT_PER_THREAD;" in src
+    return 1024 * per_thread
+
+
+CAP = _cap()
+# (V, k, n_draws, top_p, temperature): k = min(40, V) and k = 256 at V = 1000; 70 draws on a small V fill the ring and wrap it; V =
+# 32000 and 32001, where the vector loads' tail appears; then the last row of the on-chip selection and the first of the selection
+# over global memory, each with k = 40 and k = 256
+ALONE = [(1, 1, 3, 0.95, 0.8), (3, 3, 3, 1.0, 1.0), (41, 40, 70, 0.95, 0.8), (1000, 40, 3, 1e-6, 0.1), (1000, 256, 3, 0.95, 1.0),
+         (32000, 40, 3, 0.95, 0.8), (32001, 40, 2, 0.95, 0.8),
+         (CAP, 40, 3, 0.95, 0.8), (CAP, 256, 3, 0.95, 0.8), (CAP + 1, 40, 3, 0.95, 0.8), (CAP + 1, 256, 3, 0.95, 0.8)]

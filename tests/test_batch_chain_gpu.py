@@ -1,6 +1,6 @@
 """The batched greedy chain (ggml_hip_decode_batch_greedy / llm_infer_tokens_greedy_batch_device / Llama.infer_tokens_batch):
 n greedy tokens for each of B sessions of one model, every step one pass over the weights, the argmax and the next step's
-parameters on the device (k_batch_argmax_next) and the step's captured graph replayed — no host round trip between steps.
+parameters on the device (k_argmax_next, one workgroup per column) and the step's captured graph replayed — no host round trip between steps.
 
 The chain makes the launches n calls of infer_next_tokens_batch make, on the same inputs: every comparison with that loop below
 is equality (ids, and Session.snapshot() — n_past, token history, last_logits, K/V — byte for byte), with no tolerance.  Only
@@ -84,7 +84,7 @@ def _rows(B, V):
     return rows
 
 
-@pytest.mark.parametrize("B", [2, 8])
+@pytest.mark.parametrize("B", [1, 2, 8])
 @pytest.mark.parametrize("V", [1, 3, 1000, 32000, 32001])
 def test_k_batch_argmax_next_alone(G, V, B):
     rows = _rows(B, V)

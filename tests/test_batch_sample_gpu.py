@@ -1,7 +1,7 @@
 """The sampled batched chain (ggml_hip_decode_batch_sampled / llm_infer_tokens_sampled_batch_device /
 Llama.infer_tokens_sampled_batch): n tokens for each of B sessions of one model, every step one pass over the weights, the
 sampler — repetition penalty over the last 64 tokens, top-k, top-p, temperature, a xorshift64* draw — and the next step's
-parameters on the device (k_batch_sample_next), the step's captured graph replayed.
+parameters on the device (k_sample_next, one workgroup per column), the step's captured graph replayed.
 
 The sampler is specified on IEEE basic operations only and written once for host and device (kernels/sampler_math.h), so every
 comparison below is equality: the kernel alone against tests/sampler_ref.py (a numpy restatement of the specification), the chain
@@ -80,17 +80,14 @@ def _free(*things):
 
 
 # ---- the kernel alone ----
-# (V, k, n_draws, top_p, temperature): k = min(40, V) and k = 256 at V = 1000; 70 draws on a small V fill the ring and wrap it
-ALONE = [(1, 1, 3, 0.95, 0.8), (3, 3, 3, 1.0, 1.0), (41, 40, 70, 0.95, 0.8), (1000, 40, 3, 1e-6, 0.1), (1000, 256, 3, 0.95, 1.0),
-         (32000, 40, 3, 0.95, 0.8), (32001, 40, 2, 0.95, 0.8)]
-
-
-@pytest.mark.parametrize("B", [2, 8])
-@pytest.mark.parametrize("V,k,n_draws,top_p,temperature", ALONE)
+# sampler_ref.ALONE, the cases tests/test_sample_chain_gpu.py runs on one row: both selections (on chip up to V = sampler_ref.CAP, over
+# global memory beyond) in batched form, and B = 1 with a BatchCols
+@pytest.mark.parametrize("B", [1, 2, 8])
+@pytest.mark.parametrize("V,k,n_draws,top_p,temperature", R.ALONE)
 def test_k_batch_sample_next_alone(G, V, k, n_draws, top_p, temperature, B):
-    """Column c carries row family c mod 4 (sampler_ref.rows) and starts from a ring of 0 / 5 / 64 / 30 tokens taken from inside and
-    outside its raw top-k.  Ids, rings, counts, generator states, positions and DecParams equal the restatement's after n_draws
-    launches; entries from B on are untouched."""
+    """k_sample_next on B columns.  Column c carries row family c mod 4 (sampler_ref.rows) and starts from a ring of 0 / 5 / 64 / 30
+    tokens taken from inside and outside its raw top-k.  Ids, rings, counts, generator states, positions and DecParams equal the
+    restatement's after n_draws launches; entries from B on are untouched."""
     from llm_amd import llama
     rows = R.rows(B, V, seed=3)
     pos_in = (np.arange(8, dtype=np.int32) * 7 + 3) % 40

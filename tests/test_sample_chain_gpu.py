@@ -8,7 +8,6 @@ comparison below is equality: the kernel alone against tests/sampler_ref.py (a n
 against the stepped loop (ids, generator state, and Session.snapshot() byte for byte).  Contexts are 64 unless said otherwise."""
 import ctypes as C
 import os
-import re
 import sys
 
 import numpy as np
@@ -19,7 +18,6 @@ import sampler_ref as R  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GQA2 = dict(n_vocab=512, n_embd=1024, n_head=8, n_head_kv=4, n_layer=2, n_rot=128, n_ff=2816, n_mult=32)
 CTX = 64
 N = 6
@@ -27,17 +25,6 @@ F16 = 1  # ggml's type number of F16 weights
 COUNTERS = ("sample_chain_steps", "sample_chain_tokens", "batch_sample_steps", "batch_sample_tokens", "batch_chain_steps",
             "batch_chain_tokens", "batch_decode_steps", "batch_decode_tokens", "tail_tokens", "plan_tokens")
 DEFAULT = dict(k=40, top_p=0.95, temperature=0.8, penalty=1.30)
-
-
-def _cap():
-    """Rows up to this many entries take the on-chip selection, longer ones topk_kth_key over global memory (kernels/sample.h)."""
-    src = open(os.path.join(ROOT, "llm_amd", "csrc", "kernels", "sample.h")).read()
-    per_thread = int(re.search(r"constexpr int SELECT_PER_THREAD = (\d+);", src).group(1))
-    assert "constexpr int SELECT_CAP = 1024 * SELECT_PER_THREAD;" in src
-    return 1024 * per_thread
-
-
-CAP = _cap()
 
 
 def _stat(G, key):
@@ -102,11 +89,7 @@ def _free(*things):
 
 
 # ---- the kernel alone ----
-# (V, k, n_draws, top_p, temperature): tests/test_batch_sample_gpu.py's ALONE, then the last row of the on-chip selection and the
-# first of the selection over global memory, each with k = 40 and k = 256
-ALONE = [(1, 1, 3, 0.95, 0.8), (3, 3, 3, 1.0, 1.0), (41, 40, 70, 0.95, 0.8), (1000, 40, 3, 1e-6, 0.1), (1000, 256, 3, 0.95, 1.0),
-         (32000, 40, 3, 0.95, 0.8), (32001, 40, 2, 0.95, 0.8),
-         (CAP, 40, 3, 0.95, 0.8), (CAP, 256, 3, 0.95, 0.8), (CAP + 1, 40, 3, 0.95, 0.8), (CAP + 1, 256, 3, 0.95, 0.8)]
+# sampler_ref.ALONE: the cases tests/test_batch_sample_gpu.py runs on B columns (CAP = sampler_ref.CAP, the last row of the on-chip selection)
 _rows = {}
 
 
@@ -123,7 +106,7 @@ def _hook(G, row, V, prm_s, n_past_in, tokens_in, hist, hist_n, rng, n_draws, id
 
 
 @pytest.mark.parametrize("f", [0, 1, 2, 3])
-@pytest.mark.parametrize("V,k,n_draws,top_p,temperature", ALONE)
+@pytest.mark.parametrize("V,k,n_draws,top_p,temperature", R.ALONE)
 def test_k_sample_next_alone(G, V, k, n_draws, top_p, temperature, f):
     """Row family f (sampler_ref.rows: ties between neighbours and -inf; equal maxima first and last; zeros of both signs with the
     maximum last; all equal — at V = CAP the row on which every pass over the value bits keeps every key) from a ring of
