@@ -652,6 +652,33 @@ GGML_API int ggml_hip_decode_batch_sampled(struct ggml_cgraph *const *graphs, in
  * tail's (tail_tokens, spec_*). */
 GGML_API int ggml_hip_decode_sampled_chain(struct ggml_cgraph *last, int n, const ggml_hip_sampler *params, const int32_t *window,
                                            int window_n, uint64_t *rng, int32_t *out_tokens, float *last_logits);
+/* The whole sampler: the four parameters above and the reference's other samplers (crates/llm-base/src/samplers.rs:97-188 and the
+ * flat bias of build_sampler, :308-345) — token bias, frequency / presence penalty over the same 64-token window, tail-free, locally
+ * typical, min-p, Mirostat 2 — as specified at the head of llm_amd/csrc/kernels/sampler_math.h, which k_sample_next and the host's
+ * llm_sample_chain both compile.  Neutral values: freq 0, presence 0, tail_free_z 1, typical_p 1, min_p 0, n_bias 0, mirostat 0, and ANY tau > 0 and eta >= 0,
+ * such as 5 and 0.1: they are checked whatever mirostat is, so a zeroed struct with only the listed values set is declined —
+ * with them every _ex entry below computes what its four-parameter sibling computes, bit for bit (the siblings forward to them).
+ * mirostat is 0 or 2; with 2 the truncating samplers must be neutral (top_p >= 1 too; k is not read) and tau > 0, eta >= 0.
+ * bias_id / bias: n_bias (0 .. 64) pairs, every id once; -inf bans a token.  Not representable: Mirostat 1, top-a, sequence
+ * repetition, a window other than 64. */
+typedef struct {
+    ggml_hip_sampler base;
+    float freq, presence, tail_free_z, typical_p, min_p;
+    int32_t mirostat;
+    float tau, eta;
+    int32_t n_bias;
+    int32_t bias_id[64];
+    float bias[64];
+} ggml_hip_sampler_chain;
+/* ggml_hip_decode_sampled_chain / ggml_hip_decode_batch_sampled with that sampler.  mu: the sessions' Mirostat states (one / B floats,
+ * in / out beside rng; a caller starts them at 2 * tau; may be NULL when mirostat == 0).  -1 with nothing executed and no state moved
+ * for whatever the siblings decline and for: NaN in a parameter, tail_free_z <= 0, typical_p <= 0, min_p outside [0, 1], n_bias
+ * outside 0 .. 64, a bias id outside the vocabulary or listed twice, a NaN or +inf bias, mirostat not 0 or 2, Mirostat 2 beside a
+ * truncating sampler, tau <= 0, eta < 0, a NaN mu, Mirostat 2 on more than 32768 vocabulary entries.  Same options, same counters. */
+GGML_API int ggml_hip_decode_sampled_chain_ex(struct ggml_cgraph *last, int n, const ggml_hip_sampler_chain *chain, const int32_t *window,
+                                              int window_n, uint64_t *rng, float *mu, int32_t *out_tokens, float *last_logits);
+GGML_API int ggml_hip_decode_batch_sampled_ex(struct ggml_cgraph *const *graphs, int n_graphs, int n_steps, const ggml_hip_sampler_chain *chain,
+                                              const int32_t *windows, const int32_t *window_n, uint64_t *rng, float *mu, int32_t *out_ids);
 /* Top-k prefilter of a logits row on the device: the k (<= 1024, <= ne0) largest entries of row `row` of
  * the f32 tensor `t` — a node of the caller's most recent ggml_graph_compute, normally the logits — as (value, id) pairs,
  * value descending, lower id first among equal values, followed by the entries of `extra_ids` (n_extra ids, e.g. the
@@ -749,6 +776,12 @@ GGML_API int ggml_hip_debug_batch_sample(const float *logits, int B, int V, cons
 GGML_API int ggml_hip_debug_sample_next(const float *logits, int V, const ggml_hip_sampler *params, int n_past_in,
                                         const int32_t *tokens_in, int32_t *hist, int32_t *hist_n, uint64_t *rng, int n_draws,
                                         int32_t *ids_out, int32_t *prm_out);
+/* Test hook: the two hooks above with the whole sampler (one body): pos_in == NULL is ggml_hip_debug_sample_next's form (B = 1,
+ * n_past_in, hist[64], one count, one rng, one mu), otherwise ggml_hip_debug_batch_sample's (n_past_in ignored; hist [8][64], hist_n[8],
+ * rng[8], mu[8], all 8 entries in / out).  mu may be NULL when chain->mirostat == 0. */
+GGML_API int ggml_hip_debug_next_token_ex(const float *logits, int B, int V, const ggml_hip_sampler_chain *chain, int n_past_in,
+                                          const int32_t *pos_in, const int32_t *tokens_in, int32_t *hist, int32_t *hist_n, uint64_t *rng,
+                                          float *mu, int n_draws, int32_t *ids_out, int32_t *prm_out, int32_t *pos_out);
 /* Test hook: w (quantized 2-D weight with a device copy) times N = 2..8 host rows x [N][K] through k_mmq_cols as the
  * multi-token plan launches it; out [N][M].  0, or -1 when that plan would not run this shape on k_mmq_cols. */
 GGML_API int ggml_hip_debug_mul_mat_cols(const struct ggml_tensor *w, const float *x, float *out, int N);

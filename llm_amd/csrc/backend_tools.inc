@@ -724,40 +724,54 @@ int ggml_hip_decode_batch_greedy(struct ggml_cgraph *const *graphs, int n_graphs
     return r;
 }
 
-int ggml_hip_decode_batch_sampled(struct ggml_cgraph *const *graphs, int n_graphs, int n_steps, const ggml_hip_sampler *params,
-                                  const int32_t *windows, const int32_t *window_n, uint64_t *rng, int32_t *out_ids) {
+int ggml_hip_decode_batch_sampled_ex(struct ggml_cgraph *const *graphs, int n_graphs, int n_steps, const ggml_hip_sampler_chain *chain,
+                                     const int32_t *windows, const int32_t *window_n, uint64_t *rng, float *mu, int32_t *out_ids) {
     if (!graphs || n_graphs < 2 || n_graphs > BATCH_COLS_MAX || n_steps < 1 || n_steps > BATCH_CHAIN_MAX_STEPS) return -1;  // (before any device is touched)
-    if (!params || !windows || !window_n || !rng || (n_steps > 1 && !out_ids)) return -1;
+    if (!chain || !windows || !window_n || !rng || (n_steps > 1 && !out_ids)) return -1;
     for (int i = 0; i < n_graphs; i++)
         if (!graphs[i]) return -1;
     SlotLock lk;
     const uint64_t t0 = now_ns();
-    const BatchSample smp = {params, windows, window_n, rng};
+    const BatchSample smp = {chain, windows, window_n, rng, mu};
     const int r = decode_batch_steps(graphs, n_graphs, n_steps, out_ids, true, &smp);
     g.ns_compute += now_ns() - t0;
     return r;
 }
+int ggml_hip_decode_batch_sampled(struct ggml_cgraph *const *graphs, int n_graphs, int n_steps, const ggml_hip_sampler *params,
+                                  const int32_t *windows, const int32_t *window_n, uint64_t *rng, int32_t *out_ids) {
+    if (!params) return -1;
+    const ggml_hip_sampler_chain chain = sample_neutral(params);
+    return ggml_hip_decode_batch_sampled_ex(graphs, n_graphs, n_steps, &chain, windows, window_n, rng, nullptr, out_ids);
+}
 
-int ggml_hip_decode_sampled_chain(struct ggml_cgraph *last, int n, const ggml_hip_sampler *params, const int32_t *window, int window_n,
-                                  uint64_t *rng, int32_t *out_tokens, float *last_logits) {
-    if (!last || n < 1 || !params || !rng || !out_tokens || window_n < 0 || window_n > SAMPLER_WINDOW || (window_n > 0 && !window))
+int ggml_hip_decode_sampled_chain_ex(struct ggml_cgraph *last, int n, const ggml_hip_sampler_chain *chain, const int32_t *window, int window_n,
+                                     uint64_t *rng, float *mu, int32_t *out_tokens, float *last_logits) {
+    if (!last || n < 1 || !chain || !rng || !out_tokens || window_n < 0 || window_n > SAMPLER_WINDOW || (window_n > 0 && !window))
         return -1;  // (before any device is touched)
     SlotLock lk;
-    const BatchSample smp = {params, window, &window_n, rng};
+    const BatchSample smp = {chain, window, &window_n, rng, mu};
     return decode_chain(last, n, out_tokens, last_logits, &smp);
+}
+int ggml_hip_decode_sampled_chain(struct ggml_cgraph *last, int n, const ggml_hip_sampler *params, const int32_t *window, int window_n,
+                                  uint64_t *rng, int32_t *out_tokens, float *last_logits) {
+    if (!params) return -1;
+    const ggml_hip_sampler_chain chain = sample_neutral(params);
+    return ggml_hip_decode_sampled_chain_ex(last, n, &chain, window, window_n, rng, nullptr, out_tokens, last_logits);
 }
 
 // ---- test hooks: the kernel between two steps of a chain, alone.  One body of the three hooks below. ----
 // logits [B][V]; tokens_in[32] go to the device as DecParams::tokens (token = tokens_in[0]) at n_past, pos_in[8] as a step's
 // BatchCols::pos (null: no BatchCols, one session at n_past).  Without params: k_argmax_next on B workgroups.  With params: the sampler,
 // in the form a chain picks for V, on the caller's rings, counts and generator states — T entries each, in / out, T = 8 with a BatchCols
-// and 1 without; a count beyond 64 is a full ring; entries from B on are not checked and make the round trip untouched.  n_draws
+// and 1 without (mu likewise; may be null without Mirostat); a count beyond 64 is a full ring; entries from B on are not checked and
+// make the round trip untouched.  n_draws
 // launches on the same rows.  Out: ids_out[n_draws][B], prm_out[34] = n_past, token, tokens[0..32), pos_out[8] (with a BatchCols).
 // 0, or -1 for arguments the hook or the chain cannot take.
-static int debug_next_token(const float *logits, int B, int V, const ggml_hip_sampler *params, int n_past, const int32_t *pos_in,
-                            const int32_t *tokens_in, int32_t *hist, int32_t *hist_n, uint64_t *rng, int n_draws, int32_t *ids_out,
-                            int32_t *prm_out, int32_t *pos_out) {
+static int debug_next_token(const float *logits, int B, int V, const ggml_hip_sampler_chain *params, int n_past, const int32_t *pos_in,
+                            const int32_t *tokens_in, int32_t *hist, int32_t *hist_n, uint64_t *rng, float *mu, int n_draws,
+                            int32_t *ids_out, int32_t *prm_out, int32_t *pos_out) {
     const int T = pos_in ? BATCH_COLS_MAX : 1;
+    int stages = SAMPLE_DEFAULT;
     if (!logits || B < 1 || B > T || V < 1 || !tokens_in || !ids_out || !prm_out || (pos_in && !pos_out) || n_draws < 1 ||
         n_draws > BATCH_CHAIN_MAX_STEPS)
         return -1;
@@ -768,8 +782,9 @@ static int debug_next_token(const float *logits, int B, int V, const ggml_hip_sa
             if (hist_n[c] < 0) return -1;
             wn[c] = std::min(hist_n[c], SAMPLER_WINDOW);
         }
-        const BatchSample smp = {params, hist, wn, rng};
+        const BatchSample smp = {params, hist, wn, rng, mu};
         if (!batch_sample_ok(smp, B, V)) return -1;
+        stages = smp.stages();
     }
     SlotLock lk;
     ensure_init();
@@ -777,9 +792,12 @@ static int debug_next_token(const float *logits, int B, int V, const ggml_hip_sa
     DecParams hp;
     BatchCols hb;
     SampleCols hs;
+    SampleHead hh;
+    SampleState &hst = hh.state;
     memset(&hp, 0, sizeof(hp));
     memset(&hb, 0, sizeof(hb));
     memset(&hs, 0, sizeof(hs));
+    memset(&hh, 0, sizeof(hh));
     for (int i = 0; i < 32; i++) hp.tokens[i] = tokens_in[i];
     hp.n_past = n_past;
     hp.token = tokens_in[0];
@@ -787,20 +805,22 @@ static int debug_next_token(const float *logits, int B, int V, const ggml_hip_sa
     if (params) {
         memcpy(hs.hist, hist, (size_t)T * SAMPLER_WINDOW * 4);
         memcpy(hs.hist_n, hist_n, (size_t)T * 4);
-        hs.k = params->k;
-        hs.top_p = params->top_p;
-        hs.temperature = params->temperature;
-        hs.penalty = params->penalty;
+        sample_cols_params(hs, *params);
+        sample_head_bias(hh, *params);
+        for (int i = 0; i < T; i++) {
+            hst.rng[i] = rng[i];
+            if (mu) hst.mu[i] = mu[i];
+        }
     }
     std::vector<char *> owned;
     const float *dl = (const float *)debug_buf((size_t)B * V * 4, logits, owned);
     DecParams *dp = (DecParams *)debug_buf(sizeof(hp), &hp, owned);
     BatchCols *db = pos_in ? (BatchCols *)debug_buf(sizeof(hb), &hb, owned) : nullptr;
     SampleCols *ds = (SampleCols *)debug_buf(sizeof(hs), &hs, owned);
-    unsigned long long *dr = (unsigned long long *)debug_buf((size_t)T * 8, params ? rng : nullptr, owned);
+    unsigned long long *dr = (unsigned long long *)(debug_buf(sizeof(hh), &hh, owned) + sizeof(SampleBias));
     int *dids = (int *)debug_buf((size_t)n_draws * B * 4, nullptr, owned);
     for (int i = 0; i < n_draws; i++) {
-        if (params) launch_sample_next(g.stream, B, dl, V, dp, db, ds, dr, dids + (size_t)i * B);
+        if (params) launch_sample_next(g.stream, B, dl, V, dp, db, ds, dr, dids + (size_t)i * B, stages);
         else hipLaunchKernelGGL(k_argmax_next, dim3((unsigned)B), dim3(1024), 0, g.stream, dl, V, dp, db, dids + (size_t)i * B);
     }
     HIP_CHECK(hipGetLastError());
@@ -809,7 +829,7 @@ static int debug_next_token(const float *logits, int B, int V, const ggml_hip_sa
     if (db) d2h_queue(&hb, (const char *)db, sizeof(hb));
     if (params) {
         d2h_queue(&hs, (const char *)ds, sizeof(hs));
-        d2h_queue(rng, (const char *)dr, (size_t)T * 8);
+        d2h_queue(&hst, (const char *)dr, sizeof(hst));
     }
     d2h_finish();
     prm_out[0] = hp.n_past;
@@ -819,6 +839,10 @@ static int debug_next_token(const float *logits, int B, int V, const ggml_hip_sa
     if (params) {
         memcpy(hist, hs.hist, (size_t)T * SAMPLER_WINDOW * 4);
         memcpy(hist_n, hs.hist_n, (size_t)T * 4);
+        for (int i = 0; i < T; i++) {
+            rng[i] = hst.rng[i];
+            if (mu) mu[i] = hst.mu[i];
+        }
     }
     for (char *b : owned) HIP_CHECK(hipFree(b));
     return 0;
@@ -827,20 +851,30 @@ static int debug_next_token(const float *logits, int B, int V, const ggml_hip_sa
 int ggml_hip_debug_batch_tail(const float *logits, int B, int V, const int32_t *pos_in, const int32_t *tokens_in, int32_t *ids_out,
                               int32_t *prm_out, int32_t *pos_out) {
     if (!pos_in) return -1;
-    return debug_next_token(logits, B, V, nullptr, pos_in[0], pos_in, tokens_in, nullptr, nullptr, nullptr, 1, ids_out, prm_out, pos_out);
+    return debug_next_token(logits, B, V, nullptr, pos_in[0], pos_in, tokens_in, nullptr, nullptr, nullptr, nullptr, 1, ids_out, prm_out, pos_out);
 }
 // k_sample_next with a BatchCols (tests/test_batch_sample_gpu.py): hist [8][64], hist_n[8], rng[8]
 int ggml_hip_debug_batch_sample(const float *logits, int B, int V, const ggml_hip_sampler *params, const int32_t *pos_in,
                                 const int32_t *tokens_in, int32_t *hist, int32_t *hist_n, uint64_t *rng, int n_draws, int32_t *ids_out,
                                 int32_t *prm_out, int32_t *pos_out) {
     if (!params || !pos_in) return -1;
-    return debug_next_token(logits, B, V, params, pos_in[0], pos_in, tokens_in, hist, hist_n, rng, n_draws, ids_out, prm_out, pos_out);
+    const ggml_hip_sampler_chain chain = sample_neutral(params);
+    return debug_next_token(logits, B, V, &chain, pos_in[0], pos_in, tokens_in, hist, hist_n, rng, nullptr, n_draws, ids_out, prm_out, pos_out);
 }
 // k_sample_next for one session at n_past_in (tests/test_sample_chain_gpu.py): one row, hist[64], *hist_n, *rng
 int ggml_hip_debug_sample_next(const float *logits, int V, const ggml_hip_sampler *params, int n_past_in, const int32_t *tokens_in,
                                int32_t *hist, int32_t *hist_n, uint64_t *rng, int n_draws, int32_t *ids_out, int32_t *prm_out) {
     if (!params) return -1;
-    return debug_next_token(logits, 1, V, params, n_past_in, nullptr, tokens_in, hist, hist_n, rng, n_draws, ids_out, prm_out, nullptr);
+    const ggml_hip_sampler_chain chain = sample_neutral(params);
+    return debug_next_token(logits, 1, V, &chain, n_past_in, nullptr, tokens_in, hist, hist_n, rng, nullptr, n_draws, ids_out, prm_out, nullptr);
+}
+// ... and both with the whole sampler: pos_in null = one session at n_past_in, else the batched form at pos_in[0]
+int ggml_hip_debug_next_token_ex(const float *logits, int B, int V, const ggml_hip_sampler_chain *chain, int n_past_in, const int32_t *pos_in,
+                                 const int32_t *tokens_in, int32_t *hist, int32_t *hist_n, uint64_t *rng, float *mu, int n_draws,
+                                 int32_t *ids_out, int32_t *prm_out, int32_t *pos_out) {
+    if (!chain) return -1;
+    return debug_next_token(logits, B, V, chain, pos_in ? pos_in[0] : n_past_in, pos_in, tokens_in, hist, hist_n, rng, mu, n_draws, ids_out,
+                            prm_out, pos_out);
 }
 
 int64_t ggml_hip_get_stat(const char *key) {

@@ -27,4 +27,18 @@ int llm_infer_tokens_sampled_batch_device(llm_model *m, llm_session *const *sess
 int llm_infer_tokens_sampled_device(llm_model *m, llm_session *s, int n, const llm_sampler_params *params, uint64_t *rng, int32_t *out) {
     return llm_infer_tokens_sampled_via(ggml_hip_decode_sampled_chain, m, s, n, params, rng, out);
 }
+// ... and with the whole sampler (llm_sampler_chain): the _ex entries
+int llm_infer_next_tokens_sampled_chain_batch(llm_model *m, llm_session *const *sessions, int B, const llm_sampler_chain *chain, uint64_t *rngs,
+                                              float *mus, int32_t *out_ids) {
+    return llm_infer_next_tokens_sampled_chain_batch_via(ggml_hip_decode_batch, m, sessions, B, chain, rngs, mus, out_ids);
+}
+int llm_infer_tokens_sampled_chain_batch_device(llm_model *m, llm_session *const *sessions, int B, int n, const llm_sampler_chain *chain,
+                                                uint64_t *rngs, float *mus, int32_t *out_ids) {
+    return llm_infer_tokens_sampled_chain_batch_via(ggml_hip_decode_batch, ggml_hip_decode_batch_sampled_ex, m, sessions, B, n, chain, rngs, mus,
+                                                    out_ids);
+}
+int llm_infer_tokens_sampled_chain_device(llm_model *m, llm_session *s, int n, const llm_sampler_chain *chain, uint64_t *rng, float *mu,
+                                          int32_t *out) {
+    return llm_infer_tokens_sampled_chain_via(ggml_hip_decode_sampled_chain_ex, m, s, n, chain, rng, mu, out);
+}
 }

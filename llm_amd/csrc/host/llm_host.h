@@ -194,6 +194,35 @@ typedef int (*llm_sample_chain_entry)(struct ggml_cgraph *last, int n, const ggm
                                       int window_n, uint64_t *rng, int32_t *out_tokens, float *last_logits);
 GGML_API int llm_infer_tokens_sampled_via(llm_sample_chain_entry entry, llm_model *m, llm_session *s, int n,
                                           const llm_sampler_params *params, uint64_t *rng, int32_t *out);
+/* ---- the whole sampler (ggml_hip_sampler_chain: the four parameters and flat bias, frequency / presence penalty, tail-free, locally
+ * typical, min-p, Mirostat 2; specified at the head of llm_amd/csrc/kernels/sampler_math.h).  Every entry above that takes an
+ * llm_sampler_params forwards to its _chain sibling below with neutral extras: same ids, same states. ---- */
+typedef ggml_hip_sampler_chain llm_sampler_chain;
+/* llm_sample_exact with that sampler, on the host, for any V: returns the id, steps *rng once and (mirostat == 2) moves *mu; -1 with
+ * *rng and *mu unmoved for what the specification declines.  mu may be NULL when mirostat == 0.  Needs no device. */
+GGML_API int32_t llm_sample_chain(const float *logits, int V, const int32_t *window, int n_window, const llm_sampler_chain *chain,
+                                  uint64_t *rng, float *mu);
+/* test hook: sampler_log2 of sampler_math.h, n values */
+GGML_API void llm_sampler_log2(const double *r, int n, float *out);
+GGML_API int32_t llm_infer_next_token_sampled_chain(llm_model *m, llm_session *s, const llm_sampler_chain *chain, uint64_t *rng, float *mu);
+GGML_API int llm_infer_tokens_sampled_chain_device(llm_model *m, llm_session *s, int n, const llm_sampler_chain *chain, uint64_t *rng,
+                                                   float *mu, int32_t *out);
+GGML_API int llm_infer_next_tokens_sampled_chain_batch(llm_model *m, llm_session *const *sessions, int B, const llm_sampler_chain *chain,
+                                                       uint64_t *rngs, float *mus, int32_t *out_ids);
+GGML_API int llm_infer_tokens_sampled_chain_batch_device(llm_model *m, llm_session *const *sessions, int B, int n,
+                                                         const llm_sampler_chain *chain, uint64_t *rngs, float *mus, int32_t *out_ids);
+/* ... with the backend's entries as parameters (any may be NULL), as the _via entries above */
+typedef int (*llm_sample_chain_ex_entry)(struct ggml_cgraph *last, int n, const ggml_hip_sampler_chain *chain, const int32_t *window,
+                                         int window_n, uint64_t *rng, float *mu, int32_t *out_tokens, float *last_logits);
+typedef int (*llm_batch_sample_ex_entry)(struct ggml_cgraph *const *graphs, int n_graphs, int n_steps, const ggml_hip_sampler_chain *chain,
+                                         const int32_t *windows, const int32_t *window_n, uint64_t *rng, float *mu, int32_t *out_ids);
+GGML_API int llm_infer_tokens_sampled_chain_via(llm_sample_chain_ex_entry entry, llm_model *m, llm_session *s, int n,
+                                                const llm_sampler_chain *chain, uint64_t *rng, float *mu, int32_t *out);
+GGML_API int llm_infer_next_tokens_sampled_chain_batch_via(llm_batch_entry entry, llm_model *m, llm_session *const *sessions, int B,
+                                                           const llm_sampler_chain *chain, uint64_t *rngs, float *mus, int32_t *out_ids);
+GGML_API int llm_infer_tokens_sampled_chain_batch_via(llm_batch_entry step, llm_batch_sample_ex_entry chain_entry, llm_model *m,
+                                                      llm_session *const *sessions, int B, int n, const llm_sampler_chain *chain,
+                                                      uint64_t *rngs, float *mus, int32_t *out_ids);
 GGML_API size_t llm_session_read_node_host(const llm_session *s, int from_end, void *dst, size_t max_bytes);
 GGML_API int llm_session_rewind(llm_session *s, int num);
 /* host nanoseconds per phase of the decode loop, accumulated: [0] adopt/build graph, [1] token write + plan,

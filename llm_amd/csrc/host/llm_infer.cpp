@@ -112,21 +112,112 @@ void commit_step(llm_session *const *sessions, int B, const int32_t *next, int32
 
 // ---- the sampled batched chain's host side.  The sampler is kernels/sampler_math.h — the header k_sample_next compiles — so
 // the ids drawn here and on the device are the same ids.
-static bool sampler_params_ok(const llm_sampler_params *p, size_t V) {
-    return p && p->k >= 1 && (size_t)p->k <= V && p->temperature > 0.0f && p->top_p > 0.0f && p->penalty > 0.0f;
+static llm_sampler_chain neutral_chain(const llm_sampler_params *p) {
+    static const llm_sampler_params none = {0, 0.0f, 0.0f, 0.0f};  // (declined by every check)
+    return sampler_chain_neutral<llm_sampler_chain>(p ? *p : none);
 }
-// the draw for each of B sessions: from its last_logits and the last 64 tokens of its history, with its own generator.  All B ids
-// are drawn before anything is staged, so a draw that fails (false) leaves every session and — the caller hands in copies —
-// every generator unmoved
-static bool sample_sessions(llm_session *const *sessions, int B, const llm_sampler_params *params, uint64_t *rngs, int32_t *ids) {
+static bool chain_ok(const llm_sampler_chain *c, size_t V, const float *mus, int B) {
+    if (!c || !sampler_chain_ok(*c, (int64_t)V, (int64_t)V)) return false;
+    if (c->mirostat == 2) {
+        if (!mus) return false;
+        for (int i = 0; i < B; i++)
+            if (mus[i] != mus[i]) return false;
+    }
+    return true;
+}
+// the draw for each of B sessions: from its last_logits and the last 64 tokens of its history, with its own generator (and Mirostat
+// state; mus may be null without Mirostat).  All B ids are drawn before anything is staged, so a draw that fails (false) leaves every
+// session and — the caller hands in copies — every state unmoved
+static bool sample_sessions(llm_session *const *sessions, int B, const llm_sampler_chain *chain, uint64_t *rngs, float *mus, int32_t *ids) {
     for (int i = 0; i < B; i++) {
         const llm::InferenceSession &s = *sessions[i]->s;
         const std::vector<llm::TokenId> &h = s.tokens;  // (TokenId is int32_t)
         const size_t w = std::min(h.size(), (size_t)SAMPLER_WINDOW);
-        ids[i] = llm_sample_exact(s.last_logits.data(), (int)s.last_logits.size(), h.data() + (h.size() - w), (int)w, params, &rngs[i]);
+        ids[i] = llm_sample_chain(s.last_logits.data(), (int)s.last_logits.size(), h.data() + (h.size() - w), (int)w, chain, &rngs[i],
+                                  mus ? &mus[i] : nullptr);
         if (ids[i] < 0) return false;
     }
     return true;
+}
+// copies of B Mirostat states to work on (empty: the caller has none)
+static std::vector<float> mu_copy(const float *mus, int B) { return mus ? std::vector<float>(mus, mus + B) : std::vector<float>(); }
+static float *mu_ptr(std::vector<float> &v) { return v.empty() ? nullptr : v.data(); }
+
+// n sampled tokens of one session with the sampler on the device: `entry` (graph, n, window, window_n, rng, mu, ids, logits) is
+// ggml_hip_decode_sampled_chain_ex, or its four-parameter sibling behind a neutral chain; null: always the stepped loop.
+// llm_infer_tokens_greedy_device's two attempts: the chain continues a single-token fused-plan run, so after a prompt chunk (or on a
+// fresh session) one stepped token arms it; an entry that still declines leaves the rest to the stepped loop.  The session, *rng and
+// *mu end exactly as after n calls of llm_infer_next_token_sampled_chain.  Returns the number of tokens the DEVICE drew (n, n - 1 or
+// 0); -1 with nothing moved on bad arguments or without room for n tokens.
+template <class Entry>
+static int tokens_sampled(const Entry *entry, llm_model *m, llm_session *s, int n, const llm_sampler_chain *chain, uint64_t *rng, float *mu,
+                          int32_t *out) {
+    if (!m || !s || !s->s || !rng || !out || n < 1) return -1;
+    if (s->s->n_past + (size_t)n >= m->llama->params.context_size) return -1;
+    if (!chain_ok(chain, s->s->last_logits.size(), mu, 1)) return -1;
+    int done = 0;
+    for (int attempt = 0; attempt < 2 && done < n; attempt++) {
+        if (entry && m->stages.empty() && s->s->last_graph) {
+            const std::vector<llm::TokenId> &h = s->s->tokens;
+            const size_t w = std::min(h.size(), (size_t)SAMPLER_WINDOW);
+            uint64_t r = *rng;
+            float u = mu ? *mu : 0.0f;
+            // (a buffer of the chain's own: a declining entry's scribbles stay away from out)
+            std::vector<int32_t> ids((size_t)(n - done));
+            if ((*entry)(s->s->last_graph, n - done, h.data() + (h.size() - w), (int)w, &r, mu ? &u : nullptr, ids.data(),
+                         s->s->last_logits.data()) == 0) {
+                std::copy(ids.begin(), ids.end(), out + done);
+                s->s->advance_device_chain((const llm::TokenId *)ids.data(), ids.size());
+                *rng = r;
+                if (mu) *mu = u;
+                return n - done;
+            }
+        }
+        const int32_t id = llm_infer_next_token_sampled_chain(m, s, chain, rng, mu);
+        if (id < 0) return -1;  // (only the first: the parameters held for it, and hold for every later one)
+        out[done++] = id;
+    }
+    for (; done < n; done++) out[done] = llm_infer_next_token_sampled_chain(m, s, chain, rng, mu);
+    return 0;
+}
+// n sampled tokens for each of B sessions (`entry` (graphs, B, n, windows, window_n, rngs, mus, ids): ggml_hip_decode_batch_sampled_ex or
+// its sibling behind a neutral chain): the host draws row 0 of out_ids [n][B], the device rows 1 .. n - 1 — each column's window moves
+// on over the ids the device draws, and the states come back advanced by n draws in all.  Every session and state ends as after n
+// calls of the stepped form, which is what runs when there is no entry or it declines.  Returns 1 / 0 / -1 as the greedy form.
+template <class Entry>
+static int tokens_sampled_batch(llm_batch_entry step, const Entry *entry, llm_model *m, llm_session *const *sessions, int B, int n,
+                                const llm_sampler_chain *chain, uint64_t *rngs, float *mus, int32_t *out_ids) {
+    if (!out_ids || !rngs || n < 1 || !batch_sessions_ok(m, sessions, B, (size_t)n)) return -1;
+    if (!chain_ok(chain, m->llama->hyperparameters.n_vocab, mus, B)) return -1;
+    if (entry && B >= 2) {
+        std::vector<uint64_t> r(rngs, rngs + B);
+        std::vector<float> u = mu_copy(mus, B);
+        std::vector<int32_t> first((size_t)B), windows((size_t)B * SAMPLER_WINDOW, 0), window_n((size_t)B);
+        if (!sample_sessions(sessions, B, chain, r.data(), mu_ptr(u), first.data())) return -1;
+        Staged st(m, sessions, first.data(), B);
+        for (int i = 0; i < B; i++) {
+            // the window the device starts from: the session's history with this token at its end
+            const std::vector<llm::TokenId> &h = sessions[i]->s->tokens;
+            const size_t keep = std::min(h.size(), (size_t)SAMPLER_WINDOW - 1);
+            int32_t *w = windows.data() + (size_t)i * SAMPLER_WINDOW;
+            for (size_t j = 0; j < keep; j++) w[j] = (int32_t)h[h.size() - keep + j];
+            w[keep] = first[(size_t)i];
+            window_n[(size_t)i] = (int32_t)keep + 1;
+        }
+        // (a buffer of the chain's own, never empty: a declining entry's scribbles, and at n = 1 its address, stay away from out_ids)
+        std::vector<int32_t> rest((size_t)(n - 1) * (size_t)B + 1);
+        if ((*entry)(st.graphs.data(), B, n, windows.data(), window_n.data(), r.data(), mu_ptr(u), rest.data()) == 0) {
+            std::copy(first.begin(), first.end(), out_ids);
+            std::copy(rest.begin(), rest.end() - 1, out_ids + B);
+            commit_chain(st, B, n, out_ids);
+            std::copy(r.begin(), r.end(), rngs);
+            std::copy(u.begin(), u.end(), mus);
+            return 1;
+        }
+    }
+    for (int k = 0; k < n; k++)
+        if (llm_infer_next_tokens_sampled_chain_batch_via(step, m, sessions, B, chain, rngs, mus, out_ids + (size_t)k * B) < 0) return -1;
+    return 0;
 }
 
 extern "C" {
@@ -230,53 +321,44 @@ int llm_infer_tokens_greedy_device(llm_model *m, llm_session *s, int n, int32_t 
     for (; done < n; done++) out[done] = llm_infer_next_token_greedy(m, s);
     return n;
 }
-// The token step of a caller that samples with the reference's default chain, in the exact arithmetic of kernels/sampler_math.h:
-// llm_sample_exact on last_logits and the last 64 tokens of the history, the id appended and evaluated.  greedy_next stays false: the
-// backend never runs ahead of a sampling caller.  -1 with nothing moved on llm_sample_exact's bad arguments.
-int32_t llm_infer_next_token_sampled(llm_model *m, llm_session *s, const llm_sampler_params *params, uint64_t *rng) {
+// The token step of a caller that samples, in the exact arithmetic of kernels/sampler_math.h: llm_sample_chain on last_logits and the
+// last 64 tokens of the history, the id appended and evaluated.  greedy_next stays false: the backend never runs ahead of a sampling
+// caller.  -1 with nothing moved on llm_sample_chain's bad arguments.
+int32_t llm_infer_next_token_sampled_chain(llm_model *m, llm_session *s, const llm_sampler_chain *chain, uint64_t *rng, float *mu) {
     if (!m || !s || !s->s || !rng) return -1;
     require_room(m, s, 1, "llm_infer_next_token_sampled");
     uint64_t r = *rng;
+    float u = mu ? *mu : 0.0f;
     llm_session *one[1] = {s};
     int32_t next = -1;
-    if (!sample_sessions(one, 1, params, &r, &next)) return -1;
+    if (!sample_sessions(one, 1, chain, &r, mu ? &u : nullptr, &next)) return -1;
     *rng = r;
+    if (mu) *mu = u;
     s->s->tokens.push_back((llm::TokenId)next);
     llm::OutputRequest req;
     model_evaluate(m, s, std::vector<llm::TokenId>{(llm::TokenId)next}, req);
     return next;
 }
-// n such tokens with the sampler on the device (`entry` = ggml_hip_decode_sampled_chain; a parameter for the reason the batched
-// entries are).  llm_infer_tokens_greedy_device's two attempts: the chain continues a single-token fused-plan run, so after a
-// prompt chunk (or on a fresh session) one stepped token arms it; an entry that still declines leaves the rest to the stepped loop.
-// The session and *rng end exactly as after n calls of llm_infer_next_token_sampled.  Returns the number of tokens the DEVICE drew
-// (n, n - 1 or 0); -1 with nothing moved on bad arguments or without room for n tokens.
+int32_t llm_infer_next_token_sampled(llm_model *m, llm_session *s, const llm_sampler_params *params, uint64_t *rng) {
+    const llm_sampler_chain c = neutral_chain(params);
+    return llm_infer_next_token_sampled_chain(m, s, &c, rng, nullptr);
+}
+// n such tokens with the sampler on the device (tokens_sampled above): `entry` = ggml_hip_decode_sampled_chain_ex, or — the
+// four-parameter form — ggml_hip_decode_sampled_chain behind a neutral chain; a parameter for the reason the batched entries are.
+int llm_infer_tokens_sampled_chain_via(llm_sample_chain_ex_entry entry, llm_model *m, llm_session *s, int n, const llm_sampler_chain *chain,
+                                       uint64_t *rng, float *mu, int32_t *out) {
+    const auto call = [&](ggml_cgraph *g, int k, const int32_t *w, int wn, uint64_t *r, float *u, int32_t *ids, float *logits) {
+        return entry(g, k, chain, w, wn, r, u, ids, logits);
+    };
+    return tokens_sampled(entry ? &call : nullptr, m, s, n, chain, rng, mu, out);
+}
 int llm_infer_tokens_sampled_via(llm_sample_chain_entry entry, llm_model *m, llm_session *s, int n, const llm_sampler_params *params,
                                  uint64_t *rng, int32_t *out) {
-    if (!m || !s || !s->s || !rng || !out || n < 1) return -1;
-    if (s->s->n_past + (size_t)n >= m->llama->params.context_size) return -1;
-    if (!sampler_params_ok(params, s->s->last_logits.size())) return -1;
-    int done = 0;
-    for (int attempt = 0; attempt < 2 && done < n; attempt++) {
-        if (entry && m->stages.empty() && s->s->last_graph) {
-            const std::vector<llm::TokenId> &h = s->s->tokens;
-            const size_t w = std::min(h.size(), (size_t)SAMPLER_WINDOW);
-            uint64_t r = *rng;
-            // (a buffer of the chain's own: a declining entry's scribbles stay away from out)
-            std::vector<int32_t> ids((size_t)(n - done));
-            if (entry(s->s->last_graph, n - done, params, h.data() + (h.size() - w), (int)w, &r, ids.data(), s->s->last_logits.data()) == 0) {
-                std::copy(ids.begin(), ids.end(), out + done);
-                s->s->advance_device_chain((const llm::TokenId *)ids.data(), ids.size());
-                *rng = r;
-                return n - done;
-            }
-        }
-        const int32_t id = llm_infer_next_token_sampled(m, s, params, rng);
-        if (id < 0) return -1;  // (only the first: the parameters held for it, and hold for every later one)
-        out[done++] = id;
-    }
-    for (; done < n; done++) out[done] = llm_infer_next_token_sampled(m, s, params, rng);
-    return 0;
+    const llm_sampler_chain c = neutral_chain(params);
+    const auto call = [&](ggml_cgraph *g, int k, const int32_t *w, int wn, uint64_t *r, float *, int32_t *ids, float *logits) {
+        return entry(g, k, params, w, wn, r, ids, logits);
+    };
+    return tokens_sampled(entry ? &call : nullptr, m, s, n, &c, rng, nullptr, out);
 }
 // One decode step of B sessions of one model (batched multi-session decode): every session's single-token graph is built exactly as
 // llm_evaluate builds it and the B graphs go to the backend together (`entry` = ggml_hip_decode_batch: one pass over the weights for
@@ -340,94 +422,174 @@ int llm_infer_tokens_greedy_batch_via(llm_batch_entry step, llm_batch_chain_entr
         if (llm_infer_next_tokens_greedy_batch_via(step, m, sessions, B, out_ids + (size_t)k * B) < 0) return -1;
     return 0;
 }
-// One draw by the written spec: the k largest raw logits and the window's tokens (the last 64 of `window`, each id once) as
-// candidates, the window's penalised, the k best kept; top-p; temperature; one xorshift64* step of *rng.  -1 on bad arguments
-// (k outside 1 .. V, a non-positive temperature / top_p / penalty, a window token outside the vocabulary); *rng unmoved then.
-int32_t llm_sample_exact(const float *logits, int V, const int32_t *window, int n_window, const llm_sampler_params *params, uint64_t *rng) {
-    if (!logits || V < 1 || n_window < 0 || (n_window > 0 && !window) || !rng || !sampler_params_ok(params, (size_t)V)) return -1;
+// One draw by the written specification (kernels/sampler_math.h, A - E), for any V.  -1 on what it declines; *rng and *mu unmoved then.
+int32_t llm_sample_chain(const float *logits, int V, const int32_t *window, int n_window, const llm_sampler_chain *chain, uint64_t *rng,
+                         float *mu) {
+    if (!logits || V < 1 || n_window < 0 || (n_window > 0 && !window) || !rng || !chain_ok(chain, (size_t)V, mu, 1)) return -1;
     if (n_window > SAMPLER_WINDOW) {
         window += n_window - SAMPLER_WINDOW;
         n_window = SAMPLER_WINDOW;
     }
-    const int k = params->k;
+    const llm_sampler_params *params = &chain->base;
     struct Cand { float v; int32_t id; };
+    // A: M with its adjusted values — the window's distinct ids, then the bias ids that are not in it
     std::vector<Cand> c;
-    c.reserve((size_t)k + (size_t)n_window);
+    c.reserve((size_t)SAMPLER_K_MAX + SAMPLER_M_MAX);
     for (int i = 0; i < n_window; i++) {
         const int32_t id = window[i];
         if (id < 0 || id >= V) return -1;
         bool dup = false;
         for (const Cand &x : c) dup = dup || x.id == id;
-        if (!dup) c.push_back({sampler_penalise(logits[id], params->penalty), id});
+        if (dup) continue;
+        int count = 0, at = -1;
+        for (int j = 0; j < n_window; j++) count += window[j] == id;
+        for (int j = 0; j < chain->n_bias; j++)
+            if (chain->bias_id[j] == id) at = j;
+        c.push_back({sampler_adjust(logits[id], at >= 0, at >= 0 ? chain->bias[at] : 0.0f, count, params->penalty, chain->freq, chain->presence), id});
     }
-    const size_t n_win = c.size();
+    for (int j = 0; j < chain->n_bias; j++) {
+        bool in_window = false;
+        for (const Cand &x : c) in_window = in_window || x.id == chain->bias_id[j];
+        if (!in_window) c.push_back({sampler_adjust(logits[chain->bias_id[j]], true, chain->bias[j], 0, params->penalty, chain->freq, chain->presence), chain->bias_id[j]});
+    }
+    const size_t n_m = c.size();
+    if (chain->mirostat == 2) {  // E
+        std::vector<float> e(logits, logits + V);
+        for (size_t j = 0; j < n_m; j++) e[(size_t)c[j].id] = c[j].v;
+        float amax = e[0];
+        int first = 0;
+        for (int i = 1; i < V; i++)
+            if (e[(size_t)i] > amax) {
+                amax = e[(size_t)i];
+                first = i;
+            }
+        for (int i = 0; i < V; i++) e[(size_t)i] = sampler_mirostat_e(e[(size_t)i], amax, params->temperature);
+        const int nb = (V + SAMPLER_BLOCK - 1) / SAMPLER_BLOCK;
+        std::vector<double> sums((size_t)nb);
+        std::vector<char> keep((size_t)V, 1);
+        const auto total = [&] {  // the block sums over the kept entries, then their sum
+            double S = 0.0;
+            for (int b = 0; b < nb; b++) {
+                double sb = 0.0;
+                for (int i = b * SAMPLER_BLOCK; i < std::min(V, (b + 1) * SAMPLER_BLOCK); i++)
+                    if (keep[(size_t)i]) sb += (double)e[(size_t)i];
+                sums[(size_t)b] = sb;
+            }
+            for (int b = 0; b < nb; b++) S += sums[(size_t)b];
+            return S;
+        };
+        const double S = total();
+        if (*mu < 0.0f) {
+            std::fill(keep.begin(), keep.end(), 0);
+        } else {
+            const double least = sampler_mirostat_least(S, *mu);
+            for (int i = 0; i < V; i++) keep[(size_t)i] = (double)e[(size_t)i] >= least;
+        }
+        keep[(size_t)first] = 1;
+        const double S_R = total();
+        const uint64_t x = sampler_rng_step(*rng);
+        const double u = sampler_rng_unit(x) * S_R;
+        int sel = -1;
+        double run = 0.0;
+        for (int b = 0; b < nb && sel < 0; b++) {
+            const double before = run;
+            run += sums[(size_t)b];
+            if (!(run > u)) continue;
+            double acc = 0.0;
+            for (int i = b * SAMPLER_BLOCK; i < std::min(V, (b + 1) * SAMPLER_BLOCK); i++) {
+                if (!keep[(size_t)i]) continue;
+                sel = i;  // (the block's last retained id, unless the walk stops before it)
+                acc += (double)e[(size_t)i];
+                if (u - before < acc) break;
+            }
+        }
+        for (int i = V - 1; i >= 0 && sel < 0; i--)
+            if (keep[(size_t)i]) sel = i;
+        *rng = x;
+        *mu = sampler_mirostat_mu(*mu, e[(size_t)sel], S_R, chain->tau, chain->eta);
+        return sel;
+    }
+    // B: the raw top-k beside M, the k best kept
+    const int k = params->k;
     std::vector<int32_t> order((size_t)V);
     for (int i = 0; i < V; i++) order[(size_t)i] = i;
     std::partial_sort(order.begin(), order.begin() + k, order.end(),
                       [&](int32_t a, int32_t b) { return logits[a] > logits[b] || (logits[a] == logits[b] && a < b); });
     for (int i = 0; i < k; i++) {
-        bool in_window = false;
-        for (size_t j = 0; j < n_win; j++) in_window = in_window || c[j].id == order[(size_t)i];
-        if (!in_window) c.push_back({logits[order[(size_t)i]], order[(size_t)i]});
+        bool in_m = false;
+        for (size_t j = 0; j < n_m; j++) in_m = in_m || c[j].id == order[(size_t)i];
+        if (!in_m) c.push_back({logits[order[(size_t)i]], order[(size_t)i]});
     }
     std::sort(c.begin(), c.end(), [](const Cand &a, const Cand &b) { return a.v > b.v || (a.v == b.v && a.id < b.id); });
     c.resize((size_t)k);  // (the raw top-k alone are k candidates)
-    std::vector<float> q((size_t)k), p((size_t)k);
+    std::vector<float> v((size_t)k), q((size_t)k), p((size_t)k);
     for (int i = 0; i < k; i++) {
+        v[(size_t)i] = c[(size_t)i].v;
         q[(size_t)i] = sampler_q(c[(size_t)i].v, c[0].v);
         p[(size_t)i] = sampler_p(c[(size_t)i].v, c[0].v, params->temperature);
     }
-    return c[(size_t)sampler_pick(q.data(), p.data(), k, params->top_p, rng)].id;
+    // C, D
+    const int n = sampler_tail_free(q.data(), k, chain->tail_free_z);
+    std::vector<int> ord, idx((size_t)n);
+    double Q = 0.0;
+    if (chain->typical_p < 1.0f) {
+        const double mean = sampler_typical_mean(v.data(), q.data(), n, &Q);
+        std::vector<double> t((size_t)n);
+        ord.resize((size_t)n);
+        for (int i = 0; i < n; i++) {
+            t[(size_t)i] = sampler_typical_key(v[0], v[(size_t)i], q[(size_t)i], mean);
+            ord[(size_t)i] = i;
+        }
+        std::sort(ord.begin(), ord.end(), [&](int a, int b) { return t[(size_t)a] < t[(size_t)b] || (t[(size_t)a] == t[(size_t)b] && a < b); });
+    }
+    return c[(size_t)sampler_pick_chain(q.data(), p.data(), n, ord.empty() ? nullptr : ord.data(), Q, chain->typical_p, params->top_p,
+                                        chain->min_p, idx.data(), rng)].id;
 }
-// llm_infer_next_tokens_greedy_batch_via with that sampler: every session draws from its own generator (rngs[i]), the id is appended
-// to its history and evaluated in one batched step.  -1: nothing evaluated, no session and no generator moved.
-int llm_infer_next_tokens_sampled_batch_via(llm_batch_entry entry, llm_model *m, llm_session *const *sessions, int B,
-                                            const llm_sampler_params *params, uint64_t *rngs, int32_t *out_ids) {
-    if (!out_ids || !rngs || !batch_sessions_ok(m, sessions, B, 1) || !sampler_params_ok(params, m->llama->hyperparameters.n_vocab)) return -1;
+int32_t llm_sample_exact(const float *logits, int V, const int32_t *window, int n_window, const llm_sampler_params *params, uint64_t *rng) {
+    const llm_sampler_chain c = neutral_chain(params);
+    return llm_sample_chain(logits, V, window, n_window, &c, rng, nullptr);
+}
+void llm_sampler_log2(const double *r, int n, float *out) {
+    for (int i = 0; i < n; i++) out[i] = sampler_log2(r[i]);
+}
+// llm_infer_next_tokens_greedy_batch_via with that sampler: every session draws from its own generator (rngs[i]; Mirostat state
+// mus[i]), the id is appended to its history and evaluated in one batched step.  -1: nothing evaluated, no session and no state moved.
+int llm_infer_next_tokens_sampled_chain_batch_via(llm_batch_entry entry, llm_model *m, llm_session *const *sessions, int B,
+                                                  const llm_sampler_chain *chain, uint64_t *rngs, float *mus, int32_t *out_ids) {
+    if (!out_ids || !rngs || !batch_sessions_ok(m, sessions, B, 1) || !chain_ok(chain, m->llama->hyperparameters.n_vocab, mus, B)) return -1;
     std::vector<int32_t> next((size_t)B);
     std::vector<uint64_t> r(rngs, rngs + B);
-    if (!sample_sessions(sessions, B, params, r.data(), next.data())) return -1;
+    std::vector<float> u = mu_copy(mus, B);
+    if (!sample_sessions(sessions, B, chain, r.data(), mu_ptr(u), next.data())) return -1;
     const int rc = llm_evaluate_batch_via(entry, m, sessions, next.data(), B, nullptr);
     if (rc < 0) return -1;
     commit_step(sessions, B, next.data(), out_ids);
     std::copy(r.begin(), r.end(), rngs);
+    std::copy(u.begin(), u.end(), mus);
     return rc;
 }
-// llm_infer_tokens_greedy_batch_via with that sampler (`chain` = ggml_hip_decode_batch_sampled): the host draws row 0 of out_ids
-// [n][B] as above, the device rows 1 .. n - 1 — each column's window moves on over the ids the device draws, and the generator states
-// come back advanced by n draws in all.  Every session and generator ends as after n calls of the stepped form, which is what runs
-// when there is no chain entry or it declines.  Returns 1 / 0 / -1 as the greedy form.
+int llm_infer_next_tokens_sampled_batch_via(llm_batch_entry entry, llm_model *m, llm_session *const *sessions, int B,
+                                            const llm_sampler_params *params, uint64_t *rngs, int32_t *out_ids) {
+    const llm_sampler_chain c = neutral_chain(params);
+    return llm_infer_next_tokens_sampled_chain_batch_via(entry, m, sessions, B, &c, rngs, nullptr, out_ids);
+}
+// llm_infer_tokens_greedy_batch_via with that sampler (tokens_sampled_batch above): `chain_entry` = ggml_hip_decode_batch_sampled_ex, or
+// — the four-parameter form — ggml_hip_decode_batch_sampled behind a neutral chain.
+int llm_infer_tokens_sampled_chain_batch_via(llm_batch_entry step, llm_batch_sample_ex_entry chain_entry, llm_model *m,
+                                             llm_session *const *sessions, int B, int n, const llm_sampler_chain *chain, uint64_t *rngs,
+                                             float *mus, int32_t *out_ids) {
+    const auto call = [&](ggml_cgraph *const *graphs, int nb, int k, const int32_t *w, const int32_t *wn, uint64_t *r, float *u, int32_t *ids) {
+        return chain_entry(graphs, nb, k, chain, w, wn, r, u, ids);
+    };
+    return tokens_sampled_batch(step, chain_entry ? &call : nullptr, m, sessions, B, n, chain, rngs, mus, out_ids);
+}
 int llm_infer_tokens_sampled_batch_via(llm_batch_entry step, llm_batch_sample_entry chain, llm_model *m, llm_session *const *sessions, int B,
                                        int n, const llm_sampler_params *params, uint64_t *rngs, int32_t *out_ids) {
-    if (!out_ids || !rngs || n < 1 || !batch_sessions_ok(m, sessions, B, (size_t)n)) return -1;
-    if (!sampler_params_ok(params, m->llama->hyperparameters.n_vocab)) return -1;
-    if (chain && B >= 2) {
-        std::vector<uint64_t> r(rngs, rngs + B);
-        std::vector<int32_t> first((size_t)B), windows((size_t)B * SAMPLER_WINDOW, 0), window_n((size_t)B);
-        if (!sample_sessions(sessions, B, params, r.data(), first.data())) return -1;
-        Staged st(m, sessions, first.data(), B);
-        for (int i = 0; i < B; i++) {
-            // the window the device starts from: the session's history with this token at its end
-            const std::vector<llm::TokenId> &h = sessions[i]->s->tokens;
-            const size_t keep = std::min(h.size(), (size_t)SAMPLER_WINDOW - 1);
-            int32_t *w = windows.data() + (size_t)i * SAMPLER_WINDOW;
-            for (size_t j = 0; j < keep; j++) w[j] = (int32_t)h[h.size() - keep + j];
-            w[keep] = first[(size_t)i];
-            window_n[(size_t)i] = (int32_t)keep + 1;
-        }
-        // (a buffer of the chain's own, never empty: a declining entry's scribbles, and at n = 1 its address, stay away from out_ids)
-        std::vector<int32_t> rest((size_t)(n - 1) * (size_t)B + 1);
-        if (chain(st.graphs.data(), B, n, params, windows.data(), window_n.data(), r.data(), rest.data()) == 0) {
-            std::copy(first.begin(), first.end(), out_ids);
-            std::copy(rest.begin(), rest.end() - 1, out_ids + B);
-            commit_chain(st, B, n, out_ids);
-            std::copy(r.begin(), r.end(), rngs);
-            return 1;
-        }
-    }
-    for (int k = 0; k < n; k++)
-        if (llm_infer_next_tokens_sampled_batch_via(step, m, sessions, B, params, rngs, out_ids + (size_t)k * B) < 0) return -1;
-    return 0;
+    const llm_sampler_chain c = neutral_chain(params);
+    const auto call = [&](ggml_cgraph *const *graphs, int nb, int k, const int32_t *w, const int32_t *wn, uint64_t *r, float *, int32_t *ids) {
+        return chain(graphs, nb, k, params, w, wn, r, ids);
+    };
+    return tokens_sampled_batch(step, chain ? &call : nullptr, m, sessions, B, n, &c, rngs, nullptr, out_ids);
 }
 
 }  // extern "C"

@@ -1,8 +1,9 @@
 // sample.h — the device sampler of the sampled chains, 1 .. 8 sessions: k_sample_next, the kernel between two steps of
 // ggml_hip_decode_sampled_chain (one session) and of ggml_hip_decode_batch_sampled (2 .. 8 sessions; plan_run.inc).  What k_argmax_next
 // (decode.h) is to the greedy chains, with the sampler of kernels/sampler_math.h in place of the first maximum: repetition penalty
-// over the column's last 64 tokens, top-k, top-p, temperature, one xorshift64* draw.  The arithmetic is that header's, which the host
-// mirror (llm_sample_exact) compiles too: the chain draws the ids the stepped loop draws.
+// over the column's last 64 tokens, top-k, top-p, temperature, one xorshift64* draw — and, as instantiations of their own, the rest of
+// the reference's chain: flat bias, frequency / presence penalty, tail-free, locally typical, min-p, or Mirostat 2.  The arithmetic is
+// that header's, which the host mirror (llm_sample_chain) compiles too: the chain draws the ids the stepped loop draws.
 #pragma once
 #include "common.h"
 #include "decode.h"
@@ -10,14 +11,42 @@
 #include "topk.h"
 
 // Per-column sampler state of a plan (one session: column 0), uploaded once per call: the history ring of each column (min(hist_n, 64)
-// entries hold; the next token goes to slot hist_n % 64) and the chain's four parameters.  The generator states travel beside the
-// sampled ids.
+// entries hold; the next token goes to slot hist_n % 64), the chain's four parameters and the extras of the whole sampler
+// (ggml_hip_sampler_chain; the default instantiations read none of them).  What comes back per column — SampleState: the generator
+// states, then Mirostat's mu — travels in front of the sampled ids, and the bias table (SampleBias) lies in front of that, where the
+// read-back does not reach: SampleCols keeps the 2304 bytes it has always had in a plan's pool, so that no buffer of a plan moves.
 struct SampleCols {
     int hist[BATCH_COLS_MAX][SAMPLER_WINDOW];
     int hist_n[BATCH_COLS_MAX];
     int k;
     float top_p, temperature, penalty;
+    float freq, presence, tail_free_z, typical_p, min_p;
+    int mirostat;
+    float tau, eta;
+    int n_bias;
 };
+static_assert(sizeof(SampleCols) <= 2304, "SampleCols: its slot in the plan's pool");
+struct SampleState {
+    unsigned long long rng[BATCH_COLS_MAX];
+    float mu[BATCH_COLS_MAX];
+};
+struct SampleBias {
+    int id[SAMPLER_BIAS_MAX];
+    float b[SAMPLER_BIAS_MAX];
+};
+// what heads a sampled chain's chain_out; k_sample_next's `rng` argument points at `state` (the default instantiations know no more)
+struct SampleHead {
+    SampleBias bias;
+    SampleState state;
+};
+static_assert(sizeof(SampleHead) == sizeof(SampleBias) + sizeof(SampleState), "SampleHead: the bias table ends where the state begins");
+// which stages an instantiation of k_sample_next carries: the default chain (the four parameters: today's kernel, registers and all),
+// the whole truncating chain (specification A - D), Mirostat 2 (A, E; on chip only)
+enum { SAMPLE_DEFAULT = 0, SAMPLE_FULL = 1, SAMPLE_MIROSTAT = 2 };
+__device__ __forceinline__ int sample_n_bias(const SampleCols *sc) {  // (0 .. 64 whatever the table says)
+    const int n = sc->n_bias;
+    return n < 0 ? 0 : (n > SAMPLER_BIAS_MAX ? SAMPLER_BIAS_MAX : n);
+}
 
 // ---- the selection: which keys of the row are its k largest.  Over global memory (topk_kth_key, k_topk's radix passes) the row is
 // read nine times from L2 (eight passes of one dependent load per thread and iteration, then the gather); beside a 1.1 ms token that
@@ -156,28 +185,44 @@ __device__ __forceinline__ uint32_t sample_select(const float (&v)[SELECT_PER_TH
 }
 
 // Grid = B workgroups of 1024 threads; workgroup c works on row c of logits [B][V] and on entry c of every table (sc->hist[c],
-// sc->hist_n[c], rng[c], out[c]) — nothing is handed between workgroups, no workgroup waits for another, and entries from B on are
-// not touched.  bc is the table of a batched step, or null for one session at DecParams::n_past (write_next_token, decode.h).
+// sc->hist_n[c], st->rng[c], st->mu[c], out[c]) — nothing is handed between workgroups, no workgroup waits for another, and entries
+// from B on are not touched.  bc is the table of a batched step, or null for one session at DecParams::n_past (write_next_token, decode.h).
+//   M           (SAMPLE_FULL / SAMPLE_MIROSTAT) the ids whose value the step adjusts, <= 128: threads 0 .. 63 take the window's tokens
+//               (each id once, with its count and its bias), threads 64 .. 127 the bias entries that are not in the window;
+//               sampler_adjust.  SAMPLE_DEFAULT: the window's tokens, sampler_penalise.
 //   selection   the k largest raw keys of the row: sample_select over the row in registers (ONCHIP), or topk_kth_key over global
-//               memory and a scan of the row against the k-th key.  The window's tokens (each id once) enter with their penalised
-//               values, the raw top-k without the window's tokens beside them: <= k + 64 keys, bitonic-sorted in LDS by (value
-//               descending, id ascending) — topk_key's order.  Both selections yield the same set of keys, so the same sorted keys;
+//               memory and a scan of the row against the k-th key.  M's tokens enter with their adjusted values, the raw top-k
+//               without M's tokens beside them: <= k + 128 keys, bitonic-sorted in LDS by (value descending, id ascending) —
+//               topk_key's order.  Both selections yield the same set of keys, so the same sorted keys;
 //   q, p        one thread per candidate (f32: sampler_q / sampler_p);
-//   serial tail thread 0: sampler_pick, then the next replay's parameters (write_next_token), out[c], the id into the column's ring
-//               slot hist_n % 64, hist_n + 1, the advanced generator state.
-// k is 1 .. min(SAMPLER_K_MAX, V), and V <= SELECT_CAP on chip (the host declines / picks so; the kernel writes nothing otherwise).
-template <bool ONCHIP>
+//   filters     (SAMPLE_FULL) thread 0: tail-free and locally typical's mean (f64 sums in list order); one thread per entry: its
+//               key, then its rank among the keys by (key, index) — 256 comparisons each, the order any sort would give; thread 0
+//               again: sampler_pick_chain (the visit, top-p, min-p, the draw);
+//   serial tail thread 0: sampler_pick (SAMPLE_DEFAULT) / sampler_pick_chain, then the next replay's parameters (write_next_token),
+//               out[c], the id into the column's ring slot hist_n % 64, hist_n + 1, the advanced generator state.
+//   Mirostat 2  (SAMPLE_MIROSTAT, ONCHIP only: no selection, no sort) the row stays in registers, 32 ids per thread = one block of
+//               the specification: M's values patched in, a workgroup maximum with its lowest id, 32 exponentials per thread, the
+//               thread's f64 block sum to LDS, thread 0 over the blocks in order (S), the retain mask per thread, block sums
+//               again (S_R), thread 0 draws and walks the blocks; the thread that owns the block walks its registers and is the
+//               tail: mu, the generator, the parameters, the ring.
+// k is 1 .. min(SAMPLER_K_MAX, V) (not read by Mirostat 2), and V <= SELECT_CAP on chip (the host declines / picks so; the kernel
+// writes nothing otherwise).
+template <bool ONCHIP, int CHAIN = SAMPLE_DEFAULT>
 __global__ void __launch_bounds__(1024) k_sample_next(const float *__restrict__ logits, int V, DecParams *prm, BatchCols *bc,
                                                       SampleCols *sc, unsigned long long *rng, int *__restrict__ out) {
-    constexpr int PMAX = 512;  // power of two >= SAMPLER_K_MAX + SAMPLER_WINDOW
-    static_assert(PMAX >= SAMPLER_K_MAX + SAMPLER_WINDOW, "k_sample_next: LDS keys");
+    constexpr int PMAX = 512;  // power of two >= SAMPLER_K_MAX + SAMPLER_M_MAX
+    constexpr int NM = CHAIN == SAMPLE_DEFAULT ? SAMPLER_WINDOW : SAMPLER_M_MAX;
+    static_assert(PMAX >= SAMPLER_K_MAX + SAMPLER_M_MAX, "k_sample_next: LDS keys");
+    static_assert(CHAIN != SAMPLE_MIROSTAT || ONCHIP, "k_sample_next: Mirostat 2 works on the row in registers");
+    static_assert(SAMPLER_BLOCK == SELECT_PER_THREAD, "k_sample_next: one thread, one block of Mirostat's sums");
     __shared__ unsigned long long s_keys[PMAX];
     __shared__ float s_v[SAMPLER_K_MAX], s_q[SAMPLER_K_MAX], s_p[SAMPLER_K_MAX];
-    __shared__ int s_id[SAMPLER_K_MAX], s_h[SAMPLER_WINDOW], s_win[SAMPLER_WINDOW];
+    __shared__ int s_id[SAMPLER_K_MAX], s_h[SAMPLER_WINDOW], s_win[NM];
     __shared__ int s_cnt, s_wn;
     const int c = blockIdx.x, tid = threadIdx.x;
     const int k = sc->k;
-    if (c >= BATCH_COLS_MAX || k < 1 || k > SAMPLER_K_MAX || k > V || (ONCHIP && V > SELECT_CAP)) return;
+    if (c >= BATCH_COLS_MAX || (ONCHIP && V > SELECT_CAP)) return;
+    if (CHAIN != SAMPLE_MIROSTAT && (k < 1 || k > SAMPLER_K_MAX || k > V)) return;
     const float *x = logits + (size_t)c * V;
     [[maybe_unused]] float v[ONCHIP ? SELECT_PER_THREAD : 1];
     if constexpr (ONCHIP) sample_select_load(x, V, v);  // (in flight while the window is set up)
@@ -185,24 +230,198 @@ __global__ void __launch_bounds__(1024) k_sample_next(const float *__restrict__ 
     const int hn = sc->hist_n[c];
     const int nw = hn < SAMPLER_WINDOW ? (hn < 0 ? 0 : hn) : SAMPLER_WINDOW;
     int P = 1;
-    while (P < k + nw) P <<= 1;
-    for (int i = tid; i < P; i += 1024) s_keys[i] = 0;  // (below every key of a row without NaN)
+    if constexpr (CHAIN != SAMPLE_MIROSTAT) {
+        while (P < k + nw + (CHAIN == SAMPLE_DEFAULT ? 0 : sample_n_bias(sc))) P <<= 1;
+        for (int i = tid; i < P; i += 1024) s_keys[i] = 0;  // (below every key of a row without NaN)
+    }
     if (tid < SAMPLER_WINDOW) s_h[tid] = tid < nw ? sc->hist[c][tid] : -1;
     if (tid == 0) {
         s_cnt = 0;
         s_wn = 0;
     }
-    __syncthreads();
-    if (tid < nw) {  // the window's tokens, each id once, with their penalised values
-        const int id = s_h[tid];
-        bool take = id >= 0 && id < V;
-        for (int j = 0; j < tid; j++) take = take && s_h[j] != id;
-        if (take) {
-            s_win[atomicAdd(&s_wn, 1)] = id;
-            s_keys[atomicAdd(&s_cnt, 1)] = topk_key(sampler_penalise(x[id], penalty), id);
+    if constexpr (CHAIN == SAMPLE_DEFAULT) {
+        __syncthreads();
+        if (tid < nw) {  // the window's tokens, each id once, with their penalised values
+            const int id = s_h[tid];
+            bool take = id >= 0 && id < V;
+            for (int j = 0; j < tid; j++) take = take && s_h[j] != id;
+            if (take) {
+                s_win[atomicAdd(&s_wn, 1)] = id;
+                s_keys[atomicAdd(&s_cnt, 1)] = topk_key(sampler_penalise(x[id], penalty), id);
+            }
+        }
+    } else {
+        __shared__ int s_bid[SAMPLER_BIAS_MAX];
+        __shared__ float s_bv[SAMPLER_BIAS_MAX], s_adj[SAMPLER_M_MAX];
+        const int nb = sample_n_bias(sc);
+        const float freq = sc->freq, presence = sc->presence;
+        if (tid < SAMPLER_BIAS_MAX) {
+            const SampleBias *sb = reinterpret_cast<const SampleBias *>(rng) - 1;  // (SampleHead)
+            s_bid[tid] = tid < nb ? sb->id[tid] : -1;
+            s_bv[tid] = tid < nb ? sb->b[tid] : 0.0f;
+        }
+        __syncthreads();
+        // M: thread t < 64 the window's token t (its first occurrence), thread 64 + j bias entry j unless the window holds its id
+        int id = -1, count = 0, at = -1;
+        if (tid < nw) {
+            id = s_h[tid];
+            for (int j = 0; j < tid; j++)
+                if (s_h[j] == id) id = -1;
+            for (int j = 0; j < nw; j++) count += s_h[j] == id;
+            for (int j = 0; j < nb; j++)
+                if (s_bid[j] == id) at = j;
+        } else if (tid >= SAMPLER_WINDOW && tid < SAMPLER_WINDOW + nb) {
+            at = tid - SAMPLER_WINDOW;
+            id = s_bid[at];
+            for (int j = 0; j < nw; j++)
+                if (s_h[j] == id) id = -1;
+        }
+        if (id >= 0 && id < V) {
+            const float val = sampler_adjust(x[id], at >= 0, at >= 0 ? s_bv[at] : 0.0f, count, penalty, freq, presence);
+            const int slot = atomicAdd(&s_wn, 1);
+            s_win[slot] = id;
+            if constexpr (CHAIN == SAMPLE_MIROSTAT) s_adj[slot] = val;
+            else s_keys[atomicAdd(&s_cnt, 1)] = topk_key(val, id);
+        }
+        if constexpr (CHAIN == SAMPLE_MIROSTAT) {
+            __shared__ double s_blk[1024];
+            __shared__ unsigned int s_mask[1024];
+            __shared__ float s_wmax[16];
+            __shared__ int s_wat[16], s_selb, s_walk;
+            __shared__ double s_S, s_SR, s_urel;
+            __shared__ unsigned long long s_x;
+            SampleState *st = reinterpret_cast<SampleState *>(rng);
+            const int base = tid * SELECT_PER_THREAD, lane = tid & 63, wave = tid >> 6;
+            const int nblk = (V + SELECT_PER_THREAD - 1) / SELECT_PER_THREAD;
+            __syncthreads();
+            const int wn = s_wn;
+            for (int j = 0; j < wn; j++) {  // a_i: M's values into the registers that hold their ids
+                const int mid = s_win[j];
+                if ((mid >> 5) == tid) {
+                    const float val = s_adj[j];
+#pragma unroll
+                    for (int i = 0; i < SELECT_PER_THREAD; i++)
+                        if (i == (mid & 31)) v[i] = val;
+                }
+            }
+            // amax and the lowest id that holds it
+            float mx = 0.0f;
+            int first = 0x7FFFFFFF;
+#pragma unroll
+            for (int i = 0; i < SELECT_PER_THREAD; i++)
+                if (base + i < V && (first == 0x7FFFFFFF || v[i] > mx)) {
+                    mx = v[i];
+                    first = base + i;
+                }
+            const auto better = [](float om, int oa, float m, int a) { return oa != 0x7FFFFFFF && (a == 0x7FFFFFFF || om > m || (om == m && oa < a)); };
+#pragma unroll
+            for (int off = 1; off < 64; off <<= 1) {
+                const float om = __shfl_xor(mx, off);
+                const int oa = __shfl_xor(first, off);
+                if (better(om, oa, mx, first)) {
+                    mx = om;
+                    first = oa;
+                }
+            }
+            if (lane == 0) {
+                s_wmax[wave] = mx;
+                s_wat[wave] = first;
+            }
+            __syncthreads();
+            mx = s_wmax[0];
+            first = s_wat[0];
+            for (int w = 1; w < 16; w++)
+                if (better(s_wmax[w], s_wat[w], mx, first)) {
+                    mx = s_wmax[w];
+                    first = s_wat[w];
+                }
+            // e_i in place of a_i; the block's f64 sum in id order
+            double sum = 0.0;
+#pragma unroll
+            for (int i = 0; i < SELECT_PER_THREAD; i++) {
+                v[i] = base + i < V ? sampler_mirostat_e(v[i], mx, temperature) : 0.0f;
+                if (base + i < V) sum += (double)v[i];
+                __builtin_amdgcn_sched_barrier(0);  // (one exponential at a time: 32 interleaved would not fit beside the row)
+            }
+            s_blk[tid] = sum;
+            __syncthreads();
+            if (tid == 0) {
+                double S = 0.0;
+                for (int b = 0; b < nblk; b++) S += s_blk[b];
+                s_S = S;
+            }
+            __syncthreads();
+            const float mu = st->mu[c];
+            uint32_t keep = 0;
+            if (!(mu < 0.0f)) {
+                const double least = sampler_mirostat_least(s_S, mu);
+#pragma unroll
+                for (int i = 0; i < SELECT_PER_THREAD; i++) {
+                    keep |= (base + i < V && (double)v[i] >= least ? 1u : 0u) << i;
+                    __builtin_amdgcn_sched_barrier(0);  // (one conversion at a time, as above)
+                }
+            }
+            if ((first >> 5) == tid) keep |= 1u << (first & 31);
+            sum = 0.0;
+#pragma unroll
+            for (int i = 0; i < SELECT_PER_THREAD; i++)
+                if ((keep >> i) & 1u) {
+                    sum += (double)v[i];
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            s_blk[tid] = sum;
+            s_mask[tid] = keep;
+            __syncthreads();
+            if (tid == 0) {  // S_R, the draw, the block it falls into (or, past them all, the last block that retains an id)
+                double SR = 0.0;
+                for (int b = 0; b < nblk; b++) SR += s_blk[b];
+                const uint64_t xs = sampler_rng_step(st->rng[c]);
+                const double u = sampler_rng_unit(xs) * SR;
+                double run = 0.0, before = 0.0;
+                int selb = -1;
+                for (int b = 0; b < nblk; b++) {
+                    before = run;
+                    run += s_blk[b];
+                    if (run > u) {
+                        selb = b;
+                        break;
+                    }
+                }
+                s_walk = selb >= 0;
+                for (int b = nblk - 1; b >= 0 && selb < 0; b--)
+                    if (s_mask[b]) selb = b;
+                s_selb = selb;
+                s_urel = u - before;
+                s_SR = SR;
+                s_x = xs;
+            }
+            __syncthreads();
+            if (tid == s_selb) {  // the block's owner walks its retained ids, and is the tail
+                const double urel = s_urel;
+                const bool walk = s_walk != 0;
+                int sel = first;
+                float e_sel = 0.0f;
+                double acc = 0.0;
+                bool done = false;
+#pragma unroll
+                for (int i = 0; i < SELECT_PER_THREAD; i++)
+                    if (((keep >> i) & 1u) && !done) {
+                        sel = base + i;  // (the block's last retained id, unless the walk stops before it)
+                        e_sel = v[i];
+                        acc += (double)v[i];
+                        done = walk && urel < acc;
+                    }
+                st->mu[c] = sampler_mirostat_mu(mu, e_sel, s_SR, sc->tau, sc->eta);
+                st->rng[c] = s_x;
+                write_next_token(prm, bc, c, sel);
+                out[c] = sel;
+                sc->hist[c][(unsigned)hn % SAMPLER_WINDOW] = sel;
+                sc->hist_n[c] = hn + 1;
+            }
+            return;
         }
     }
-    // the raw top-k, without the window's tokens (both selections open with a barrier: s_win / s_wn are complete behind it)
+    // the raw top-k, without M's tokens (both selections open with a barrier: s_win / s_wn are complete behind it)
     const auto gather = [&](unsigned long long key, int id, int wn) {
         bool in_window = false;
         for (int j = 0; j < wn; j++) in_window = in_window || s_win[j] == id;
@@ -238,6 +457,45 @@ __global__ void __launch_bounds__(1024) k_sample_next(const float *__restrict__ 
         s_p[tid] = sampler_p(s_v[tid], v0, temperature);
     }
     __syncthreads();
+    if constexpr (CHAIN == SAMPLE_FULL) {
+        __shared__ double s_t[SAMPLER_K_MAX], s_mean, s_Q;
+        __shared__ int s_ord[SAMPLER_K_MAX], s_idx[SAMPLER_K_MAX], s_n1;
+        const float typical_p = sc->typical_p;
+        const bool typ = typical_p < 1.0f;  // (the same for every thread: the barriers below are taken by all or none)
+        if (tid == 0) {
+            const int n1 = sampler_tail_free(s_q, k, sc->tail_free_z);
+            double Q = 0.0;
+            if (typ) s_mean = sampler_typical_mean(s_v, s_q, n1, &Q);
+            s_Q = Q;
+            s_n1 = n1;
+        }
+        __syncthreads();
+        const int n1 = s_n1;
+        if (typ) {
+            if (tid < n1) s_t[tid] = sampler_typical_key(s_v[0], s_v[tid], s_q[tid], s_mean);
+            __syncthreads();
+            if (tid < n1) {  // the entry's place in the order by (key ascending, index ascending): the keys below it, counted
+                const double t = s_t[tid];
+                int rank = 0;
+                for (int j = 0; j < n1; j++) {
+                    const double tj = s_t[j];
+                    rank += (tj < t || (tj == t && j < tid)) ? 1 : 0;
+                }
+                s_ord[rank] = tid;
+            }
+            __syncthreads();
+        }
+        if (tid == 0) {
+            uint64_t state = rng[c];
+            const int id = s_id[sampler_pick_chain(s_q, s_p, n1, typ ? s_ord : nullptr, s_Q, typical_p, sc->top_p, sc->min_p, s_idx, &state)];
+            rng[c] = state;
+            write_next_token(prm, bc, c, id);
+            out[c] = id;
+            sc->hist[c][(unsigned)hn % SAMPLER_WINDOW] = id;
+            sc->hist_n[c] = hn + 1;
+        }
+        return;
+    }
     if (tid == 0) {
         uint64_t state = rng[c];
         const int id = s_id[sampler_pick(s_q, s_p, k, sc->top_p, &state)];
@@ -248,11 +506,19 @@ __global__ void __launch_bounds__(1024) k_sample_next(const float *__restrict__ 
         sc->hist_n[c] = hn + 1;
     }
 }
-// The one launch of the sampler, for the chain, the batched chain and the test hook: B columns, the selection picked from V alone.
+// The one launch of the sampler, for the chain, the batched chain and the test hook: B columns, the selection picked from V alone, the
+// stages from the chain's parameters (`stages`: SAMPLE_DEFAULT for neutral extras — today's kernel).  rng is a SampleHead's state.
+// The SAMPLE_FULL and SAMPLE_MIROSTAT instantiations are compiled into an object of their own (sample_ext.hip, which defines
+// launch_sample_next_ext): the code object that holds every other kernel of the library keeps its contents and its addresses.
+#ifndef SAMPLE_EXT_OBJECT
+void launch_sample_next_ext(hipStream_t stream, int B, const float *logits, int V, void *prm, void *bc, void *sc, void *state, int *out, int stages);
 static inline void launch_sample_next(hipStream_t stream, int B, const float *logits, int V, DecParams *prm, BatchCols *bc, SampleCols *sc,
-                                      unsigned long long *rng, int *out) {
-    if (V <= SELECT_CAP)
-        hipLaunchKernelGGL(k_sample_next<true>, dim3((unsigned)B), dim3(1024), 0, stream, logits, V, prm, bc, sc, rng, out);
+                                      unsigned long long *rng, int *out, int stages = SAMPLE_DEFAULT) {
+    if (stages != SAMPLE_DEFAULT)
+        launch_sample_next_ext(stream, B, logits, V, prm, bc, sc, rng, out, stages);
+    else if (V <= SELECT_CAP)
+        hipLaunchKernelGGL((k_sample_next<true, SAMPLE_DEFAULT>), dim3((unsigned)B), dim3(1024), 0, stream, logits, V, prm, bc, sc, rng, out);
     else
-        hipLaunchKernelGGL(k_sample_next<false>, dim3((unsigned)B), dim3(1024), 0, stream, logits, V, prm, bc, sc, rng, out);
+        hipLaunchKernelGGL((k_sample_next<false, SAMPLE_DEFAULT>), dim3((unsigned)B), dim3(1024), 0, stream, logits, V, prm, bc, sc, rng, out);
 }
+#endif

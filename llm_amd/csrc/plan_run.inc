@@ -475,18 +475,27 @@ static bool try_decode_plan(ggml_cgraph *gr, bool defer_wait = false) {
 
 // ---- what the device-sampled chains share: their caps, a sampled chain's arguments and what its tail can take ----
 constexpr int BATCH_CHAIN_MAX_STEPS = 4096;
-constexpr int SAMPLE_RNG_WORDS = BATCH_COLS_MAX * 2;  // chain_out of a sampled chain: BATCH_COLS_MAX 64-bit generator states, then the ids
+// chain_out of a sampled chain: a SampleHead — the bias table, which only goes up, then the SampleState (generator states, Mirostat's mu) —
+// then the ids; the read-back begins at the state
+constexpr int SAMPLE_BIAS_WORDS = (int)(sizeof(SampleBias) / 4), SAMPLE_RNG_WORDS = (int)(sizeof(SampleState) / 4);
 struct BatchSample {
-    const ggml_hip_sampler *prm;
+    const ggml_hip_sampler_chain *prm;
     const int32_t *windows;   // [B][64]: column c's last window_n[c] tokens, oldest first
     const int32_t *window_n;  // [B], 0 .. 64
     uint64_t *rng;            // [B], in / out
+    float *mu;                // [B], in / out; may be null without Mirostat
+    int stages() const { return prm->mirostat == 2 ? SAMPLE_MIROSTAT : (sampler_chain_is_default(*prm) ? SAMPLE_DEFAULT : SAMPLE_FULL); }
 };
+// the four-parameter entries' chain: neutral extras
+static ggml_hip_sampler_chain sample_neutral(const ggml_hip_sampler *params) { return sampler_chain_neutral<ggml_hip_sampler_chain>(*params); }
 // what the sampled chain's tail can take (checked before anything runs)
 static bool batch_sample_ok(const BatchSample &s, int B, int64_t V) {
-    const ggml_hip_sampler &q = *s.prm;
-    if (q.k < 1 || q.k > SAMPLER_K_MAX || q.k > V) return false;
-    if (!(q.temperature > 0.0f) || !(q.top_p > 0.0f) || !(q.penalty > 0.0f)) return false;
+    if (!sampler_chain_ok(*s.prm, V, SAMPLER_K_MAX)) return false;
+    if (s.prm->mirostat == 2) {  // on the row in registers only; every column's state a number
+        if (V > SELECT_CAP || !s.mu) return false;
+        for (int c = 0; c < B; c++)
+            if (s.mu[c] != s.mu[c]) return false;
+    }
     for (int c = 0; c < B; c++) {
         if (s.window_n[c] < 0 || s.window_n[c] > SAMPLER_WINDOW) return false;
         for (int i = 0; i < s.window_n[c]; i++)
@@ -494,35 +503,68 @@ static bool batch_sample_ok(const BatchSample &s, int B, int64_t V) {
     }
     return true;
 }
-// A sampled chain's state goes up, once per call: the B columns' history rings and the four parameters into the plan's SampleCols,
-// the B generator states to the front of chain_out, which gets room for n_ids ids behind them.  Returns where the ids start.
+// the parameters of a chain into a SampleCols (the rings are the caller's)
+static void sample_cols_params(SampleCols &hs, const ggml_hip_sampler_chain &q) {
+    hs.k = q.base.k;
+    hs.top_p = q.base.top_p;
+    hs.temperature = q.base.temperature;
+    hs.penalty = q.base.penalty;
+    hs.freq = q.freq;
+    hs.presence = q.presence;
+    hs.tail_free_z = q.tail_free_z;
+    hs.typical_p = q.typical_p;
+    hs.min_p = q.min_p;
+    hs.mirostat = q.mirostat;
+    hs.tau = q.tau;
+    hs.eta = q.eta;
+    hs.n_bias = q.n_bias;
+}
+// ... and its bias table into the SampleHead that heads chain_out
+static void sample_head_bias(SampleHead &h, const ggml_hip_sampler_chain &q) {
+    for (int i = 0; i < q.n_bias; i++) {
+        h.bias.id[i] = q.bias_id[i];
+        h.bias.b[i] = q.bias[i];
+    }
+}
+// A sampled chain's state goes up, once per call: the B columns' history rings and the parameters into the plan's SampleCols, the B
+// generator states and Mirostat states (a SampleState) to the front of chain_out, which gets room for n_ids ids behind them.  Returns
+// where the ids start.
 static int sample_cols_fill(DecodePlan *p, const BatchSample &s, int B, int n_ids) {
-    chain_out_reserve(p, SAMPLE_RNG_WORDS + n_ids);
+    chain_out_reserve(p, SAMPLE_BIAS_WORDS + SAMPLE_RNG_WORDS + n_ids);
     SampleCols hs;
     memset(&hs, 0, sizeof(hs));
     for (int c = 0; c < B; c++) {
         hs.hist_n[c] = s.window_n[c];
         for (int i = 0; i < s.window_n[c]; i++) hs.hist[c][i] = s.windows[c * SAMPLER_WINDOW + i];
     }
-    hs.k = s.prm->k;
-    hs.top_p = s.prm->top_p;
-    hs.temperature = s.prm->temperature;
-    hs.penalty = s.prm->penalty;
+    sample_cols_params(hs, *s.prm);
     h2d_small((char *)p->scols, &hs, sizeof(hs));
-    h2d_small((char *)p->chain_out, s.rng, (size_t)B * 8);
-    return SAMPLE_RNG_WORDS;
+    SampleHead h;
+    memset(&h, 0, sizeof(h));
+    for (int c = 0; c < B; c++) {
+        h.state.rng[c] = s.rng[c];
+        if (s.mu) h.state.mu[c] = s.mu[c];
+    }
+    sample_head_bias(h, *s.prm);
+    h2d_small((char *)p->chain_out, &h, sizeof(h));
+    return SAMPLE_BIAS_WORDS + SAMPLE_RNG_WORDS;
 }
-// ... and comes back out of the chain's read-back of chain_out (the generator states, then the ids); out_ids may be null
+// ... and comes back out of the chain's read-back of chain_out (the SampleState, then the ids); out_ids may be null
 static void sample_cols_back(const std::vector<int32_t> &sample_back, const BatchSample &s, int B, int32_t *out_ids) {
-    memcpy(s.rng, sample_back.data(), (size_t)B * 8);
+    SampleState st;
+    memcpy(&st, sample_back.data(), sizeof(st));
+    for (int c = 0; c < B; c++) {
+        s.rng[c] = st.rng[c];
+        if (s.mu && s.prm->mirostat == 2) s.mu[c] = st.mu[c];
+    }
     if (out_ids) memcpy(out_ids, sample_back.data() + SAMPLE_RNG_WORDS, (sample_back.size() - SAMPLE_RNG_WORDS) * 4);
 }
 // The kernel between two steps of a chain: every column's next token from its row of `logits`, into the parameters of the step's next
 // replay and out[c] — the first maximum, or (sampled) a draw of the sampler whose state sample_cols_fill has uploaded.  p->bcols is
 // null on a single-token plan: one session at DecParams::n_past.
-static void launch_next_token(DecodePlan *p, int B, const float *logits, bool sampled, int *out) {
-    if (sampled)
-        launch_sample_next(g.stream, B, logits, (int)p->m.V, p->prm, p->bcols, p->scols, (unsigned long long *)p->chain_out, out);
+static void launch_next_token(DecodePlan *p, int B, const float *logits, const BatchSample *smp, int *out) {
+    if (smp)
+        launch_sample_next(g.stream, B, logits, (int)p->m.V, p->prm, p->bcols, p->scols, (unsigned long long *)(p->chain_out + SAMPLE_BIAS_WORDS), out, smp->stages());
     else
         hipLaunchKernelGGL(k_argmax_next, dim3((unsigned)B), dim3(1024), 0, g.stream, logits, (int)p->m.V, p->prm, p->bcols, out);
 }
@@ -580,7 +622,7 @@ static int decode_chain(ggml_cgraph *last, int n, int32_t *out_tokens, float *la
                 if (p->graph_chain) (void)hipGraphDestroy(p->graph_chain);
                 capture_into(&p->graph_chain, &p->exec_chain, [&] {
                     for (int k = 0; k < K; k++) {
-                        launch_next_token(p, 1, (const float *)p->logits_out, false, p->chain_ring + k);
+                        launch_next_token(p, 1, (const float *)p->logits_out, nullptr, p->chain_ring + k);
                         plan_launch_decode(p, AV_SHORT);
                     }
                 });
@@ -593,7 +635,7 @@ static int decode_chain(ggml_cgraph *last, int n, int32_t *out_tokens, float *la
         }
     }
     for (int i = i0; i < n; i++) {
-        launch_next_token(p, 1, i == 0 ? first_logits : (const float *)p->logits_out, smp != nullptr, ids + i);
+        launch_next_token(p, 1, i == 0 ? first_logits : (const float *)p->logits_out, smp, ids + i);
         // the token of step i sits at position n_past + 1 + i; same rule as try_decode_plan for the attention variant
         const int av = attn_variant(m, p, m.n_past + 1 + i + 1);
         // (the chain's books are not count_token_forms': no fused_wo_tokens, fused_affine_tokens or split_tokens — values tests read; left as they are)
@@ -610,8 +652,8 @@ static int decode_chain(ggml_cgraph *last, int n, int32_t *out_tokens, float *la
     HIP_CHECK(hipGetLastError());
     std::vector<int32_t> sample_back;  // a sampled chain's read-back: the generator state, then the ids
     if (smp) {
-        sample_back.resize((size_t)(ids_off + n));
-        d2h_queue(sample_back.data(), (const char *)p->chain_out, sample_back.size() * 4);
+        sample_back.resize((size_t)(SAMPLE_RNG_WORDS + n));
+        d2h_queue(sample_back.data(), (const char *)(p->chain_out + SAMPLE_BIAS_WORDS), sample_back.size() * 4);
     } else {
         d2h_queue(out_tokens, (const char *)p->chain_out, (size_t)n * 4);
     }
@@ -738,13 +780,13 @@ static int decode_batch_steps(ggml_cgraph *const *graphs, int B, int n_steps, in
         else chain_out_reserve(p, n_ids);
         int *ids = p->chain_out + ids_off;
         for (int i = 1; i < n_steps; i++) {
-            launch_next_token(p, B, (const float *)p->logits_out, smp != nullptr, ids + (size_t)(i - 1) * B);
+            launch_next_token(p, B, (const float *)p->logits_out, smp, ids + (size_t)(i - 1) * B);
             step();
         }
         HIP_CHECK(hipGetLastError());
         if (smp) {  // the generator states and the ids: one copy
-            sample_back.resize((size_t)(ids_off + n_ids));
-            d2h_queue(sample_back.data(), (const char *)p->chain_out, sample_back.size() * 4);
+            sample_back.resize((size_t)(SAMPLE_RNG_WORDS + n_ids));
+            d2h_queue(sample_back.data(), (const char *)(p->chain_out + SAMPLE_BIAS_WORDS), sample_back.size() * 4);
         } else if (out_ids) {
             d2h_queue(out_ids, (const char *)p->chain_out, (size_t)n_ids * 4);
         }

@@ -115,6 +115,20 @@ def _lib():
         L.llm_infer_next_token_sampled.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.llm_infer_tokens_sampled_device.restype = C.c_int
         L.llm_infer_tokens_sampled_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.llm_sample_chain.restype = C.c_int32
+        L.llm_sample_chain.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.llm_sampler_log2.restype = None
+        L.llm_sampler_log2.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        L.llm_infer_next_token_sampled_chain.restype = C.c_int32
+        L.llm_infer_next_token_sampled_chain.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.llm_infer_tokens_sampled_chain_device.restype = C.c_int
+        L.llm_infer_tokens_sampled_chain_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.llm_infer_next_tokens_sampled_chain_batch.restype = C.c_int
+        L.llm_infer_next_tokens_sampled_chain_batch.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                                C.c_void_p]
+        L.llm_infer_tokens_sampled_chain_batch_device.restype = C.c_int
+        L.llm_infer_tokens_sampled_chain_batch_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                                                  C.c_void_p, C.c_void_p]
         _bound = True
     return L
 
@@ -122,6 +136,57 @@ def _lib():
 class SamplerParams(C.Structure):
     """llm_sampler_params / ggml_hip_sampler: the sampled batched chain's {k, top_p, temperature, penalty}."""
     _fields_ = [("k", C.c_int32), ("top_p", C.c_float), ("temperature", C.c_float), ("penalty", C.c_float)]
+
+
+class SamplerChain(C.Structure):
+    """llm_sampler_chain / ggml_hip_sampler_chain: the four parameters and the reference's other samplers (flat bias, frequency /
+    presence penalty, tail-free, locally typical, min-p, Mirostat 2)."""
+    _fields_ = [("base", SamplerParams), ("freq", C.c_float), ("presence", C.c_float), ("tail_free_z", C.c_float), ("typical_p", C.c_float),
+                ("min_p", C.c_float), ("mirostat", C.c_int32), ("tau", C.c_float), ("eta", C.c_float), ("n_bias", C.c_int32),
+                ("bias_id", C.c_int32 * 64), ("bias", C.c_float * 64)]
+
+
+def sampler_chain(k=40, top_p=0.95, temperature=0.8, penalty=1.30, freq=0.0, presence=0.0, tail_free_z=1.0, typical_p=1.0, min_p=0.0,
+                  bias=(), mirostat=0, tau=5.0, eta=0.1):
+    """A SamplerChain from keywords; the defaults of everything behind `penalty` are neutral (the default chain).  bias: [(id, b), ...],
+    at most 64 pairs, every id once (b = -inf bans a token); mirostat: 0 or 2 (with 2: tau, eta, and no truncating sampler — top_p 1
+    too).  ValueError for more than 64 bias pairs; everything else is checked by the library."""
+    bias = list(bias)
+    if len(bias) > 64:
+        raise ValueError("sampler_chain: at most 64 bias pairs")
+    c = SamplerChain(SamplerParams(int(k), float(top_p), float(temperature), float(penalty)), float(freq), float(presence),
+                     float(tail_free_z), float(typical_p), float(min_p), int(mirostat), float(tau), float(eta), len(bias))
+    for i, (t, b) in enumerate(bias):
+        c.bias_id[i] = int(t)
+        c.bias[i] = float(b)
+    return c
+
+
+def _mu(mu, B, chain):
+    """The Mirostat states: a contiguous float32 array of B elements, advanced in place (None without Mirostat)."""
+    if mu is None:
+        if chain.mirostat != 0:
+            raise ValueError("mu: Mirostat needs its state, a float32 array with one element per session (start it at 2 * tau)")
+        return None
+    if not (isinstance(mu, np.ndarray) and mu.dtype == np.float32 and mu.size == B and mu.flags.c_contiguous):
+        raise ValueError("mu: a contiguous float32 array with one Mirostat state per session (updated in place)")
+    return mu.ctypes.data
+
+
+def sample_chain(logits, window, rng, mu=None, **chain):
+    """llm_sample_chain: one draw from a row of logits by the whole sampler (sampler_chain's keywords; no device needed).  rng: a
+    uint64 array of one element, mu: a float32 array of one element (Mirostat 2's state; None otherwise), both stepped in place.
+    Returns the id; ValueError, with nothing moved, on what the specification declines."""
+    logits = np.ascontiguousarray(logits, dtype=np.float32)
+    window = np.ascontiguousarray(window, dtype=np.int32)
+    if not (isinstance(rng, np.ndarray) and rng.dtype == np.uint64 and rng.size == 1 and rng.flags.c_contiguous):
+        raise ValueError("sample_chain: rng is a uint64 array of one element")
+    c = sampler_chain(**chain)
+    rc = _lib().llm_sample_chain(logits.ctypes.data, logits.size, window.ctypes.data if window.size else None, window.size,
+                                 C.addressof(c), rng.ctypes.data, _mu(mu, 1, c))
+    if rc < 0:
+        raise ValueError("llm_sample_chain: bad arguments")
+    return int(rc)
 
 
 def sample_exact(logits, window, rng, k=40, top_p=0.95, temperature=0.8, penalty=1.30):
@@ -308,33 +373,36 @@ class Llama:
             raise ValueError("rngs: a contiguous uint64 array with one generator state per session (updated in place)")
         return rngs
 
-    def infer_next_tokens_sampled_batch(self, sessions, rngs, k=40, top_p=0.95, temperature=0.8, penalty=1.30):
+    def infer_next_tokens_sampled_batch(self, sessions, rngs, k=40, top_p=0.95, temperature=0.8, penalty=1.30, mu=None, **extras):
         """infer_next_tokens_batch with the shape of the reference's default sampler instead of the first maximum
         (llm_infer_next_tokens_sampled_batch): repetition penalty over each session's last 64 tokens, top-k, top-p, temperature, one
         xorshift64* draw from rngs[i] (a uint64 array, updated in place).  Returns (ran_batched, ids).  ValueError, with nothing
         evaluated and no generator moved: the bad arguments of evaluate_batch, k outside 1 .. n_vocab, a non-positive top_p,
-        temperature or penalty."""
+        temperature or penalty.  extras: sampler_chain's further keywords (freq, presence, tail_free_z, typical_p, min_p, bias,
+        mirostat, tau, eta; neutral by default); mu: the sessions' Mirostat states, a float32 array advanced in place like rngs."""
         ptrs = (C.c_void_p * len(sessions))(*[s.ptr for s in sessions])
         rngs = self._rngs(rngs, len(sessions))
-        prm = SamplerParams(int(k), float(top_p), float(temperature), float(penalty))
+        prm = sampler_chain(k, top_p, temperature, penalty, **extras)
         out = np.zeros(len(sessions), np.int32)
-        rc = _lib().llm_infer_next_tokens_sampled_batch(self.ptr, ptrs, len(sessions), C.addressof(prm), rngs.ctypes.data, out.ctypes.data)
+        rc = _lib().llm_infer_next_tokens_sampled_chain_batch(self.ptr, ptrs, len(sessions), C.addressof(prm), rngs.ctypes.data,
+                                                              _mu(mu, len(sessions), prm), out.ctypes.data)
         if rc < 0:
             raise ValueError("llm_infer_next_tokens_sampled_batch: bad arguments (nothing was evaluated)")
         return bool(rc), out
 
-    def infer_tokens_sampled_batch(self, sessions, n, rngs, k=40, top_p=0.95, temperature=0.8, penalty=1.30):
+    def infer_tokens_sampled_batch(self, sessions, n, rngs, k=40, top_p=0.95, temperature=0.8, penalty=1.30, mu=None, **extras):
         """n such tokens for each session, all but the first drawn on the device where the backend can
         (llm_infer_tokens_sampled_batch_device: no host round trip between steps; k <= 256; the models evaluate_batch takes
         batched, K-quant models under option plan_batch_k included); anything else runs as n steps of
         infer_next_tokens_sampled_batch, with the same ids, sessions and generator states.  Returns (ran_chained, ids [n, B]).
-        ValueError as above, and for n < 1 or a session without room for n tokens."""
+        ValueError as above, and for n < 1 or a session without room for n tokens.  extras and mu as above (Mirostat 2 on the
+        device: n_vocab <= 32768)."""
         ptrs = (C.c_void_p * len(sessions))(*[s.ptr for s in sessions])
         rngs = self._rngs(rngs, len(sessions))
-        prm = SamplerParams(int(k), float(top_p), float(temperature), float(penalty))
+        prm = sampler_chain(k, top_p, temperature, penalty, **extras)
         out = np.zeros((max(int(n), 0), len(sessions)), np.int32)
-        rc = _lib().llm_infer_tokens_sampled_batch_device(self.ptr, ptrs, len(sessions), int(n), C.addressof(prm), rngs.ctypes.data,
-                                                          out.ctypes.data)
+        rc = _lib().llm_infer_tokens_sampled_chain_batch_device(self.ptr, ptrs, len(sessions), int(n), C.addressof(prm), rngs.ctypes.data,
+                                                                _mu(mu, len(sessions), prm), out.ctypes.data)
         if rc < 0:
             raise ValueError("llm_infer_tokens_sampled_batch_device: bad arguments (nothing was evaluated)")
         return bool(rc), out
@@ -404,26 +472,30 @@ class Session:
         _lib().llm_infer_tokens_greedy_device(self.model.ptr, self.ptr, n, out.ctypes.data)
         return out
 
-    def infer_next_token_sampled(self, rng, k=40, top_p=0.95, temperature=0.8, penalty=1.30):
+    def infer_next_token_sampled(self, rng, k=40, top_p=0.95, temperature=0.8, penalty=1.30, mu=None, **extras):
         """One token step of a caller that samples (llm_infer_next_token_sampled): sample_exact on last_logits and the last 64 tokens
         of the history, the id appended and evaluated.  rng: a uint64 array of one element, stepped in place.  ValueError, with
-        nothing moved, on sample_exact's bad arguments."""
+        nothing moved, on sample_exact's bad arguments.  extras: sampler_chain's further keywords (freq, presence, tail_free_z,
+        typical_p, min_p, bias, mirostat, tau, eta; neutral by default — sample_chain draws); mu: Mirostat 2's state, a float32 array
+        of one element advanced in place like rng."""
         rng = Llama._rngs(rng, 1)
-        prm = SamplerParams(int(k), float(top_p), float(temperature), float(penalty))
-        rc = _lib().llm_infer_next_token_sampled(self.model.ptr, self.ptr, C.addressof(prm), rng.ctypes.data)
+        prm = sampler_chain(k, top_p, temperature, penalty, **extras)
+        rc = _lib().llm_infer_next_token_sampled_chain(self.model.ptr, self.ptr, C.addressof(prm), rng.ctypes.data, _mu(mu, 1, prm))
         if rc < 0:
             raise ValueError("llm_infer_next_token_sampled: bad arguments (nothing was evaluated)")
         return int(rc)
 
-    def infer_tokens_sampled_device(self, n, rng, k=40, top_p=0.95, temperature=0.8, penalty=1.30):
+    def infer_tokens_sampled_device(self, n, rng, k=40, top_p=0.95, temperature=0.8, penalty=1.30, mu=None, **extras):
         """n such tokens drawn on the device where the backend can (llm_infer_tokens_sampled_device: no logits read-back and no host
         round trip per token; k <= 256); anything else runs as infer_next_token_sampled, with the same ids, session and generator
         state.  Returns (n_on_device, ids): n behind a single-token step, n - 1 behind a prompt, 0 when the backend declined.
-        ValueError as above, and for n < 1 or a session without room for n tokens."""
+        ValueError as above, and for n < 1 or a session without room for n tokens.  extras and mu as above (Mirostat 2 on the
+        device: n_vocab <= 32768)."""
         rng = Llama._rngs(rng, 1)
-        prm = SamplerParams(int(k), float(top_p), float(temperature), float(penalty))
+        prm = sampler_chain(k, top_p, temperature, penalty, **extras)
         out = np.zeros(max(int(n), 0), np.int32)
-        rc = _lib().llm_infer_tokens_sampled_device(self.model.ptr, self.ptr, int(n), C.addressof(prm), rng.ctypes.data, out.ctypes.data)
+        rc = _lib().llm_infer_tokens_sampled_chain_device(self.model.ptr, self.ptr, int(n), C.addressof(prm), rng.ctypes.data,
+                                                          _mu(mu, 1, prm), out.ctypes.data)
         if rc < 0:
             raise ValueError("llm_infer_tokens_sampled_device: bad arguments (nothing was evaluated)")
         return int(rc), out
