@@ -679,6 +679,41 @@ GGML_API int ggml_hip_decode_sampled_chain_ex(struct ggml_cgraph *last, int n, c
                                               int window_n, uint64_t *rng, float *mu, int32_t *out_tokens, float *last_logits);
 GGML_API int ggml_hip_decode_batch_sampled_ex(struct ggml_cgraph *const *graphs, int n_graphs, int n_steps, const ggml_hip_sampler_chain *chain,
                                               const int32_t *windows, const int32_t *window_n, uint64_t *rng, float *mu, int32_t *out_ids);
+/* Chains that stop: every column carries its own request — its own sampler (a NULL chain: the first maximum), up to 8 stop ids and
+ * its own budget — and ends on its own: with the draw of one of its stop ids, which the next step still evaluates as the reference's
+ * loop does (inference_session.rs:404-408: evaluate, then EndOfText), or when its budget is used up.  A column that has ended is
+ * frozen while the others go on: the kernel between two steps leaves its token, position, ring, generator and mu alone, so every
+ * further step evaluates the same token at the same position again and rewrites the same K/V rows and logits with the same bits.
+ * The call ends as soon as no column is live: the steps are enqueued in groups of option chain_group, the columns' live flags come
+ * back behind each group, and nothing more is launched once every column was found ended.  Each session is left exactly where its
+ * own last evaluation left it: logits, K/V, generator, mu.
+ * ended_by: 1 = the budget, 2 = a stop id.  Rows of the ids that belong to steps a column sat out frozen, or that were never
+ * launched, hold -1. */
+typedef struct {
+    int32_t budget, n_stop, stop_id[8];
+} ggml_hip_chain_end;
+#define GGML_HIP_CHAIN_END_BUDGET 1
+#define GGML_HIP_CHAIN_END_STOP 2
+/* One session, as ggml_hip_decode_sampled_chain_ex (chain != NULL) or ggml_hip_decode_greedy_chain (chain == NULL; window, rng and mu
+ * may then be NULL): at most end->budget (1 .. n) draws.  out_tokens[n]: the ids drawn, then -1; *n_drawn their number (every one
+ * of them was evaluated: the caller adds it to its n_past); last_logits (V floats, may be NULL): the logits after the last of them.
+ * Returns 0, or -1 with nothing executed and no state moved: whatever the sibling declines, with n_past + 1 + end->budget against the
+ * context; n_stop outside 0 .. 8; a stop id outside the vocabulary; a budget outside 1 .. n.  Option chain_k does not apply.
+ * Counters as the sibling's, for the steps that were launched; chain_stopped_columns, chain_frozen_steps, chain_steps_cut. */
+GGML_API int ggml_hip_decode_chain_requests(struct ggml_cgraph *last, int n, const ggml_hip_sampler_chain *chain, const ggml_hip_chain_end *end,
+                                            const int32_t *window, int window_n, uint64_t *rng, float *mu, int32_t *out_tokens,
+                                            int32_t *n_drawn, int32_t *ended_by, float *last_logits);
+/* B = 2 .. 8 sessions, as ggml_hip_decode_batch_sampled_ex / ggml_hip_decode_batch_greedy: chains [B] (entries may be NULL: that
+ * column takes the first maximum), ends [B].  A column's budget is the number of evaluations it takes, counting step 0: 1 .. n_steps;
+ * 1 = frozen from the first draw on (a session whose host-drawn first token was already its stop id).  n_evaluated [B]: the
+ * evaluations each column took (the caller adds them to the session's n_past).  windows, window_n, rng may be NULL when every column
+ * is greedy; mu when none runs Mirostat 2.  -1 with nothing executed and no state moved: whatever the siblings decline, checked per
+ * column, with n_past + budget against the context; n_stop outside 0 .. 8; a stop id outside the vocabulary; a budget outside
+ * 1 .. n_steps.  NULL pointers and counts out of range are refused before any device is touched. */
+GGML_API int ggml_hip_decode_batch_requests(struct ggml_cgraph *const *graphs, int n_graphs, int n_steps,
+                                            const ggml_hip_sampler_chain *const *chains, const ggml_hip_chain_end *ends, const int32_t *windows,
+                                            const int32_t *window_n, uint64_t *rng, float *mu, int32_t *out_ids, int32_t *n_evaluated,
+                                            int32_t *ended_by);
 /* Top-k prefilter of a logits row on the device: the k (<= 1024, <= ne0) largest entries of row `row` of
  * the f32 tensor `t` — a node of the caller's most recent ggml_graph_compute, normally the logits — as (value, id) pairs,
  * value descending, lower id first among equal values, followed by the entries of `extra_ids` (n_extra ids, e.g. the
@@ -782,6 +817,14 @@ GGML_API int ggml_hip_debug_sample_next(const float *logits, int V, const ggml_h
 GGML_API int ggml_hip_debug_next_token_ex(const float *logits, int B, int V, const ggml_hip_sampler_chain *chain, int n_past_in,
                                           const int32_t *pos_in, const int32_t *tokens_in, int32_t *hist, int32_t *hist_n, uint64_t *rng,
                                           float *mu, int n_draws, int32_t *ids_out, int32_t *prm_out, int32_t *pos_out);
+/* Test hook: the kernel(s) between two steps of the chains that stop, alone, n_draws rounds on the same rows: the hook above with a
+ * request per column — chains [B] (NULL entries: the first maximum) and ends [B], whose budget is here the number of DRAWS the
+ * column may make (0 .. n_draws; 0 = frozen from the start).  Out besides the hook's: n_drawn [B] and ended_by [B]; a frozen column's
+ * entries of ids_out are -1. */
+GGML_API int ggml_hip_debug_next_token_req(const float *logits, int B, int V, const ggml_hip_sampler_chain *const *chains,
+                                           const ggml_hip_chain_end *ends, int n_past_in, const int32_t *pos_in, const int32_t *tokens_in,
+                                           int32_t *hist, int32_t *hist_n, uint64_t *rng, float *mu, int n_draws, int32_t *ids_out,
+                                           int32_t *prm_out, int32_t *pos_out, int32_t *n_drawn, int32_t *ended_by);
 /* Test hook: w (quantized 2-D weight with a device copy) times N = 2..8 host rows x [N][K] through k_mmq_cols as the
  * multi-token plan launches it; out [N][M].  0, or -1 when that plan would not run this shape on k_mmq_cols. */
 GGML_API int ggml_hip_debug_mul_mat_cols(const struct ggml_tensor *w, const float *x, float *out, int N);

@@ -104,6 +104,12 @@ struct Backend {
     uint64_t stat_batch_tokens = 0, stat_batch_steps = 0, stat_batch_chain_steps = 0, stat_batch_chain_tokens = 0;
     uint64_t stat_batch_sample_steps = 0, stat_batch_sample_tokens = 0, stat_batch_k_steps = 0;
     uint64_t stat_sample_chain_steps = 0, stat_sample_chain_tokens = 0;
+    // the chains that stop (plan_run.inc chain_req_run): steps per group behind which the host looks at the columns' live flags, the
+    // pinned words the flags are copied into (two sets: the host reads one while the next group's copy is in flight) and their events
+    int opt_chain_group = 8;
+    int *chain_live_pin = nullptr;
+    hipEvent_t chain_live_ev[2] = {nullptr, nullptr};
+    uint64_t stat_chain_stopped_columns = 0, stat_chain_frozen_steps = 0, stat_chain_steps_cut = 0;
     uint64_t stat_flash_attn_nodes = 0;
     // prompt-GEMM launches by kernel (ggml_hip_get_stat("mmq_launches_<name>")): bench.py labels its MFMA roofline with the
     // kernels that actually ran
@@ -211,6 +217,10 @@ static const OptRow g_options[] = {
     // K plan: its decode mat-vecs as one wave of 1024-thread workgroups that stage the activation themselves (kernels/kquant_big.h)
     {"kbig", &Backend::opt_kbig, OPT_ENV | OPT_DROPS},
     {"chain_k", &Backend::opt_chain_k, OPT_ENV, FX_NONE, 0, 64},  // greedy chain: tokens per hipGraph launch (0 / 1 = one token per launch)
+    // the chains that stop (ggml_hip_decode_chain_requests / ggml_hip_decode_batch_requests): steps enqueued between two looks at the
+    // columns' live flags; a call whose columns cannot end early never looks.  8: the smallest group whose median lay inside the
+    // no-stop run's own spread (DESIGN section 3 item 5; 8 .. 64 all did, one session and B = 8)
+    {"chain_group", &Backend::opt_chain_group, OPT_ENV, FX_NONE, 1, 4096},
     // ggml_hip_graph_prepare remembers its match (0: it answers 0 and every begin() matches its graph itself)
     {"prepare", &Backend::opt_prepare, OPT_ENV},
     // 1 = run the greedy next token ahead behind every single-token plan run, whoever the caller is (Backend::spec, plan_run.inc)
@@ -328,6 +338,9 @@ static const StatRow g_counters[] = {
     {"batch_sample_steps", &Backend::stat_batch_sample_steps},    // batched steps that ran on tokens the device SAMPLED (ggml_hip_decode_batch_sampled: all but a call's first; not in batch_chain_*)
     {"batch_sample_tokens", &Backend::stat_batch_sample_tokens},  // ... and their tokens
     {"sample_chain_steps", &Backend::stat_sample_chain_steps},    // replays of a single-token plan on a token the device SAMPLED (ggml_hip_decode_sampled_chain: every token of a call); counted in plan_tokens too
+    {"chain_stopped_columns", &Backend::stat_chain_stopped_columns},  // columns of the chains that stop that ended on one of their stop ids
+    {"chain_frozen_steps", &Backend::stat_chain_frozen_steps},        // column-steps such a chain replayed for a column that had ended (the same token at the same position again)
+    {"chain_steps_cut", &Backend::stat_chain_steps_cut},              // steps of such calls that were never launched: every column had ended
     {"sample_chain_tokens", &Backend::stat_sample_chain_tokens},  // ... and their tokens (one session a step: the same number, kept beside batch_sample_*)
     {"cols_warm_launches", &Backend::stat_cols_warm_launches},    // chunk-plan norm launches that carried warming workgroups (ColsWarm), counted when enqueued or captured
     {"fused_rearms", &Backend::stat_fused_rearms},                // times the fused forms came back after a clean stretch behind a give-up

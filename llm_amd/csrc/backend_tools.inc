@@ -759,6 +759,131 @@ int ggml_hip_decode_sampled_chain(struct ggml_cgraph *last, int n, const ggml_hi
     return ggml_hip_decode_sampled_chain_ex(last, n, &chain, window, window_n, rng, nullptr, out_tokens, last_logits);
 }
 
+// ---- the chains that stop: a request per column (plan_run.inc ChainRequests) ----
+int ggml_hip_decode_chain_requests(struct ggml_cgraph *last, int n, const ggml_hip_sampler_chain *chain, const ggml_hip_chain_end *end,
+                                   const int32_t *window, int window_n, uint64_t *rng, float *mu, int32_t *out_tokens, int32_t *n_drawn,
+                                   int32_t *ended_by, float *last_logits) {
+    if (!last || n < 1 || n > BATCH_CHAIN_MAX_STEPS || !end || !out_tokens || !n_drawn || !ended_by) return -1;  // (before any device is touched)
+    if (window_n < 0 || window_n > SAMPLER_WINDOW || (window_n > 0 && !window) || (chain && !rng)) return -1;
+    if (end->budget < 1 || end->budget > n || end->n_stop < 0 || end->n_stop > CHAIN_STOP_MAX) return -1;
+    SlotLock lk;
+    const int32_t none[1] = {0};
+    uint64_t r = rng ? *rng : 0;  // (copies: nothing moves unless the chain ran)
+    float u = mu ? *mu : 0.0f;
+    int32_t count = 0, why = 0;
+    ChainRequests req = {&chain, end, window ? window : none, &window_n, &r, mu ? &u : nullptr, &count, &why, 0, {0, 0, 0, 0}};
+    std::vector<int32_t> ids((size_t)end->budget);
+    if (decode_chain(last, end->budget, ids.data(), last_logits, nullptr, &req) != 0) return -1;
+    for (int i = 0; i < n; i++) out_tokens[i] = i < end->budget ? ids[(size_t)i] : -1;
+    if (rng) *rng = r;
+    if (mu) *mu = u;
+    *n_drawn = count;
+    *ended_by = why;
+    return 0;
+}
+int ggml_hip_decode_batch_requests(struct ggml_cgraph *const *graphs, int n_graphs, int n_steps, const ggml_hip_sampler_chain *const *chains,
+                                   const ggml_hip_chain_end *ends, const int32_t *windows, const int32_t *window_n, uint64_t *rng, float *mu,
+                                   int32_t *out_ids, int32_t *n_evaluated, int32_t *ended_by) {
+    if (!graphs || n_graphs < 2 || n_graphs > BATCH_COLS_MAX || n_steps < 1 || n_steps > BATCH_CHAIN_MAX_STEPS) return -1;  // (before any device is touched)
+    if (!chains || !ends || !n_evaluated || !ended_by || (n_steps > 1 && !out_ids)) return -1;
+    for (int i = 0; i < n_graphs; i++) {
+        if (!graphs[i] || (chains[i] && (!windows || !window_n || !rng))) return -1;
+        if (ends[i].budget < 1 || ends[i].budget > n_steps || ends[i].n_stop < 0 || ends[i].n_stop > CHAIN_STOP_MAX) return -1;
+    }
+    SlotLock lk;
+    const uint64_t t0 = now_ns();
+    std::vector<uint64_t> r((size_t)n_graphs, 0);  // (copies: nothing moves unless the chain ran)
+    std::vector<float> u((size_t)n_graphs, 0.0f);
+    std::vector<int32_t> count((size_t)n_graphs), why((size_t)n_graphs);
+    for (int i = 0; i < n_graphs; i++) {
+        if (rng) r[(size_t)i] = rng[i];
+        if (mu) u[(size_t)i] = mu[i];
+    }
+    ChainRequests req = {chains, ends, windows, window_n, r.data(), mu ? u.data() : nullptr, count.data(), why.data(), 1, {0, 0, 0, 0}};
+    const int rc = decode_batch_steps(graphs, n_graphs, n_steps, out_ids, true, nullptr, &req);
+    g.ns_compute += now_ns() - t0;
+    if (rc != 0) return -1;
+    for (int i = 0; i < n_graphs; i++) {
+        if (rng && chains[i]) rng[i] = r[(size_t)i];
+        if (mu && chains[i]) mu[i] = u[(size_t)i];
+        n_evaluated[i] = count[(size_t)i];
+        ended_by[i] = why[(size_t)i];
+    }
+    return 0;
+}
+
+// ---- test hook: the kernels between two steps of the chains that stop, alone (tests/test_chain_requests_gpu.py).  debug_next_token's
+// shape with a request per column; a budget here is the number of draws, 0 .. n_draws. ----
+int ggml_hip_debug_next_token_req(const float *logits, int B, int V, const ggml_hip_sampler_chain *const *chains, const ggml_hip_chain_end *ends,
+                                  int n_past_in, const int32_t *pos_in, const int32_t *tokens_in, int32_t *hist, int32_t *hist_n, uint64_t *rng,
+                                  float *mu, int n_draws, int32_t *ids_out, int32_t *prm_out, int32_t *pos_out, int32_t *n_drawn,
+                                  int32_t *ended_by) {
+    const int T = pos_in ? BATCH_COLS_MAX : 1;
+    if (!logits || B < 1 || B > T || V < 1 || !chains || !ends || !tokens_in || !hist || !hist_n || !rng || !ids_out || !prm_out ||
+        (pos_in && !pos_out) || !n_drawn || !ended_by || n_draws < 1 || n_draws > BATCH_CHAIN_MAX_STEPS)
+        return -1;
+    int32_t wn[BATCH_COLS_MAX];
+    for (int c = 0; c < B; c++) {
+        if (hist_n[c] < 0) return -1;
+        wn[c] = std::min(hist_n[c], SAMPLER_WINDOW);
+    }
+    std::vector<int32_t> count((size_t)B), why((size_t)B);
+    ChainRequests req = {chains, ends, hist, wn, rng, mu, count.data(), why.data(), 0, {0, 0, 0, 0}};
+    if (!chain_requests_ok(req, B, V, 0, n_draws)) return -1;
+    SlotLock lk;
+    ensure_init();
+    finish_pending();
+    DecParams hp;
+    BatchCols hb;
+    SampleCols hs;
+    SampleReqs ht;
+    memset(&hp, 0, sizeof(hp));
+    memset(&hb, 0, sizeof(hb));
+    memset(&hs, 0, sizeof(hs));
+    for (int i = 0; i < 32; i++) hp.tokens[i] = tokens_in[i];
+    hp.n_past = pos_in ? pos_in[0] : n_past_in;
+    hp.token = tokens_in[0];
+    for (int i = 0; pos_in && i < BATCH_COLS_MAX; i++) hb.pos[i] = pos_in[i];
+    memcpy(hs.hist, hist, (size_t)T * SAMPLER_WINDOW * 4);
+    memcpy(hs.hist_n, hist_n, (size_t)T * 4);
+    chain_req_table(ht, req, B);
+    for (int i = 0; i < T; i++) {  // (entries from B on make the round trip untouched)
+        ht.back.state.rng[i] = rng[i];
+        if (mu) ht.back.state.mu[i] = mu[i];
+    }
+    std::vector<char *> owned;
+    const float *dl = (const float *)debug_buf((size_t)B * V * 4, logits, owned);
+    DecParams *dp = (DecParams *)debug_buf(sizeof(hp), &hp, owned);
+    BatchCols *db = pos_in ? (BatchCols *)debug_buf(sizeof(hb), &hb, owned) : nullptr;
+    SampleCols *ds = (SampleCols *)debug_buf(sizeof(hs), &hs, owned);
+    char *dt = debug_buf(sizeof(ht), &ht, owned);
+    int *dids = (int *)debug_buf((size_t)n_draws * B * 4, nullptr, owned);
+    for (int i = 0; i < n_draws; i++) launch_next_token_req(g.stream, req.n_class, dl, V, dp, db, ds, dt, dids + (size_t)i * B);
+    HIP_CHECK(hipGetLastError());
+    d2h_queue(ids_out, (const char *)dids, (size_t)n_draws * B * 4);
+    d2h_queue(&hp, (const char *)dp, sizeof(hp));
+    if (db) d2h_queue(&hb, (const char *)db, sizeof(hb));
+    d2h_queue(&hs, (const char *)ds, sizeof(hs));
+    d2h_queue(&ht.back, (const char *)dt, sizeof(ht.back));
+    d2h_finish();
+    prm_out[0] = hp.n_past;
+    prm_out[1] = hp.token;
+    for (int i = 0; i < 32; i++) prm_out[2 + i] = hp.tokens[i];
+    for (int i = 0; pos_in && i < BATCH_COLS_MAX; i++) pos_out[i] = hb.pos[i];
+    memcpy(hist, hs.hist, (size_t)T * SAMPLER_WINDOW * 4);
+    memcpy(hist_n, hs.hist_n, (size_t)T * 4);
+    for (int i = 0; i < T; i++) {
+        rng[i] = ht.back.state.rng[i];
+        if (mu) mu[i] = ht.back.state.mu[i];
+    }
+    for (int c = 0; c < B; c++) {
+        n_drawn[c] = ht.back.n_drawn[c];
+        ended_by[c] = ht.back.ended_by[c];
+    }
+    for (char *b : owned) HIP_CHECK(hipFree(b));
+    return 0;
+}
+
 // ---- test hooks: the kernel between two steps of a chain, alone.  One body of the three hooks below. ----
 // logits [B][V]; tokens_in[32] go to the device as DecParams::tokens (token = tokens_in[0]) at n_past, pos_in[8] as a step's
 // BatchCols::pos (null: no BatchCols, one session at n_past).  Without params: k_argmax_next on B workgroups.  With params: the sampler,

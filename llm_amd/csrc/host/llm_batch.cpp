@@ -41,4 +41,14 @@ int llm_infer_tokens_sampled_chain_device(llm_model *m, llm_session *s, int n, c
                                           int32_t *out) {
     return llm_infer_tokens_sampled_chain_via(ggml_hip_decode_sampled_chain_ex, m, s, n, chain, rng, mu, out);
 }
+// ... and the generation that stops: the chains with a request per session
+int llm_infer_until(llm_model *m, llm_session *s, const llm_until_request *req, uint64_t *rng, float *mu, int32_t *out, int32_t *n_out,
+                    int32_t *ended_by) {
+    return llm_infer_until_via(ggml_hip_decode_chain_requests, m, s, req, rng, mu, out, n_out, ended_by);
+}
+int llm_infer_until_batch(llm_model *m, llm_session *const *sessions, int B, const llm_until_request *reqs, uint64_t *rngs, float *mus,
+                          int32_t *out_ids, int32_t *n_out, int32_t *ended_by) {
+    return llm_infer_until_batch_via(ggml_hip_decode_batch, ggml_hip_decode_batch_requests, m, sessions, B, reqs, rngs, mus, out_ids, n_out,
+                                     ended_by);
+}
 }

@@ -142,8 +142,8 @@ GGML_API int llm_infer_next_tokens_greedy_batch_via(llm_batch_entry entry, llm_m
  * the first maximum of each session's current last_logits.  Every session ends exactly as after n calls of
  * llm_infer_next_tokens_greedy_batch: n_past, token history, last_logits (after the n-th token), K/V.  Returns 1 if the chain
  * ran, 0 if the backend declined and that loop ran instead (same results), -1 with nothing evaluated and no session moved: the
- * bad arguments of llm_evaluate_batch, n < 1, a session with n_past + n beyond the context size.  No stop tokens: the caller
- * trims. */
+ * bad arguments of llm_evaluate_batch, n < 1, a session with n_past + n beyond the context size.  (Stop ids and
+ * budgets per session: llm_infer_until_batch.) */
 GGML_API int llm_infer_tokens_greedy_batch_device(llm_model *m, llm_session *const *sessions, int B, int n, int32_t *out_ids);
 /* ... with the backend's single step and its chain as parameters (either may be NULL), as the two _via entries above */
 typedef int (*llm_batch_chain_entry)(struct ggml_cgraph *const *graphs, int n_graphs, int n_steps, int32_t *out_ids);
@@ -223,6 +223,46 @@ GGML_API int llm_infer_next_tokens_sampled_chain_batch_via(llm_batch_entry entry
 GGML_API int llm_infer_tokens_sampled_chain_batch_via(llm_batch_entry step, llm_batch_sample_ex_entry chain_entry, llm_model *m,
                                                       llm_session *const *sessions, int B, int n, const llm_sampler_chain *chain,
                                                       uint64_t *rngs, float *mus, int32_t *out_ids);
+/* ---- generation that stops, as InferenceSession::infer does (inference_session.rs:381-424, :487-507): draw, evaluate, and end when
+ * the token is one of the request's stop ids (it is still evaluated first, :404-408), when max_tokens were drawn, or where the
+ * reference's loop would return ContextFull (:388: n_past + 1 reaches the context size).  A request per session: its own sampler
+ * (chain == NULL: the first maximum), its own budget, up to 8 stop ids (every one inside the vocabulary). ---- */
+typedef struct {
+    const llm_sampler_chain *chain;
+    int32_t max_tokens, n_stop, stop_id[8];
+} llm_until_request;
+enum { LLM_ENDED_BY_BUDGET = 1, LLM_ENDED_BY_STOP = 2, LLM_ENDED_BY_CONTEXT = 3 };
+/* One session.  out[max_tokens]: the ids drawn, then -1; *n_out their number; *ended_by one of the above.  On the device where the
+ * backend can (ggml_hip_decode_chain_requests: the chain ends by itself at the stop id and leaves the session where the stop token's
+ * evaluation left it), after one stepped token behind a prompt chunk as llm_infer_tokens_sampled_chain_device; the stepped loop with
+ * the same rule runs when it declines.  Tokens, n_past, last_logits, K/V, *rng and *mu end as the stepped loop leaves them.  Returns 1
+ * if the device chain ran, 0 if the stepped loop did it all, -1 with nothing moved on bad arguments (those of llm_sample_chain,
+ * max_tokens < 1, n_stop outside 0 .. 8, a stop id outside the vocabulary).  rng may be NULL for a greedy request. */
+GGML_API int llm_infer_until(llm_model *m, llm_session *s, const llm_until_request *req, uint64_t *rng, float *mu, int32_t *out,
+                             int32_t *n_out, int32_t *ended_by);
+/* B sessions of one model, requests [B], rngs [B] / mus [B] (either may be NULL when no request needs it).  out_ids [n][B] with n the
+ * largest max_tokens: column i holds session i's ids, then -1; n_out [B], ended_by [B].  One call of ggml_hip_decode_batch_requests
+ * where the backend can (the host draws row 0; a session whose first token is already a stop id enters with a budget of one
+ * evaluation), otherwise steps of the sessions that are still going.  Returns 1 / 0 / -1 as llm_infer_tokens_sampled_chain_batch_device. */
+GGML_API int llm_infer_until_batch(llm_model *m, llm_session *const *sessions, int B, const llm_until_request *reqs, uint64_t *rngs,
+                                   float *mus, int32_t *out_ids, int32_t *n_out, int32_t *ended_by);
+/* ... with the backend's entries as parameters (any may be NULL), as the _via entries above */
+typedef int (*llm_chain_requests_entry)(struct ggml_cgraph *last, int n, const ggml_hip_sampler_chain *chain, const ggml_hip_chain_end *end,
+                                        const int32_t *window, int window_n, uint64_t *rng, float *mu, int32_t *out_tokens, int32_t *n_drawn,
+                                        int32_t *ended_by, float *last_logits);
+typedef int (*llm_batch_requests_entry)(struct ggml_cgraph *const *graphs, int n_graphs, int n_steps, const ggml_hip_sampler_chain *const *chains,
+                                        const ggml_hip_chain_end *ends, const int32_t *windows, const int32_t *window_n, uint64_t *rng,
+                                        float *mu, int32_t *out_ids, int32_t *n_evaluated, int32_t *ended_by);
+GGML_API int llm_infer_until_via(llm_chain_requests_entry entry, llm_model *m, llm_session *s, const llm_until_request *req, uint64_t *rng,
+                                 float *mu, int32_t *out, int32_t *n_out, int32_t *ended_by);
+GGML_API int llm_infer_until_batch_via(llm_batch_entry step, llm_batch_requests_entry entry, llm_model *m, llm_session *const *sessions, int B,
+                                       const llm_until_request *reqs, uint64_t *rngs, float *mus, int32_t *out_ids, int32_t *n_out,
+                                       int32_t *ended_by);
+/* test hook: the end rule alone, on recorded logits rows [n_rows][V] (row t stands for the logits the t-th draw sees; the window is
+ * `window` followed by the ids drawn so far; n_past counts up from n_past0 with every draw against context_size).  Draws with
+ * llm_sample_chain (or the first maximum) until the rule ends the run or the rows run out (*ended_by = 0 then).  Needs no device. */
+GGML_API int llm_until_rule(const float *rows, int n_rows, int V, const llm_until_request *req, const int32_t *window, int n_window,
+                            int n_past0, int context_size, uint64_t *rng, float *mu, int32_t *out, int32_t *n_out, int32_t *ended_by);
 GGML_API size_t llm_session_read_node_host(const llm_session *s, int from_end, void *dst, size_t max_bytes);
 GGML_API int llm_session_rewind(llm_session *s, int num);
 /* host nanoseconds per phase of the decode loop, accumulated: [0] adopt/build graph, [1] token write + plan,

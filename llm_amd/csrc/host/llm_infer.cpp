@@ -220,6 +220,55 @@ static int tokens_sampled_batch(llm_batch_entry step, const Entry *entry, llm_mo
     return 0;
 }
 
+// ---- generation that stops (llm_infer_until, llm_infer_until_batch): the end rule of InferenceSession::infer, once, for the stepped
+// loops, for what the device chains are asked to do and for the test hook.  A session at n_past may draw while n_past + 1 is below
+// the context size (inference_session.rs:388); the budget is max_tokens or that room, whichever is less, and a run that uses up a
+// budget the room cut short ended on the context.
+struct UntilRule {
+    const llm_until_request *q;
+    int budget;
+    bool cut;
+    UntilRule(const llm_until_request *q, size_t n_past, size_t context) : q(q) {
+        const size_t room = n_past + 1 < context ? context - 1 - n_past : 0;
+        budget = (int)std::min((size_t)q->max_tokens, room);
+        cut = budget < q->max_tokens;
+    }
+    bool is_stop(int32_t id) const {
+        for (int j = 0; j < q->n_stop; j++)
+            if (q->stop_id[j] == id) return true;
+        return false;
+    }
+    int out_of_budget() const { return cut ? LLM_ENDED_BY_CONTEXT : LLM_ENDED_BY_BUDGET; }
+    // 0: go on; otherwise why the run ends behind its drawn-th draw, which was `id` (the stop id wins: it is what the reference reports)
+    int after(int drawn, int32_t id) const { return is_stop(id) ? LLM_ENDED_BY_STOP : (drawn >= budget ? out_of_budget() : 0); }
+};
+static bool until_request_ok(const llm_until_request *q, size_t V, const uint64_t *rng, const float *mu) {
+    if (!q || q->max_tokens < 1 || q->n_stop < 0 || q->n_stop > 8) return false;
+    for (int j = 0; j < q->n_stop; j++)
+        if (q->stop_id[j] < 0 || (size_t)q->stop_id[j] >= V) return false;
+    return !q->chain || (rng && chain_ok(q->chain, V, mu, 1));
+}
+static ggml_hip_chain_end until_end(const llm_until_request *q, int budget) {
+    ggml_hip_chain_end e;
+    memset(&e, 0, sizeof(e));
+    e.budget = budget;
+    e.n_stop = q->n_stop;
+    for (int j = 0; j < q->n_stop; j++) e.stop_id[j] = q->stop_id[j];
+    return e;
+}
+// one draw of a request from a logits row and a window (oldest first, the last 64 count): its sampler, or the first maximum
+static int32_t until_draw(const llm_until_request *q, const float *logits, size_t V, const int32_t *hist, size_t n_hist, uint64_t *rng, float *mu) {
+    if (!q->chain) return (int32_t)argmax_first(logits, V);
+    const size_t w = std::min(n_hist, (size_t)SAMPLER_WINDOW);
+    return llm_sample_chain(logits, (int)V, hist + (n_hist - w), (int)w, q->chain, rng, mu);
+}
+// ... of a session, appended and evaluated (a greedy request steps as llm_infer_next_token_greedy does, a sampling one as
+// llm_infer_next_token_sampled_chain); -1 with nothing moved if the sampler declines
+static int32_t until_step(llm_model *m, llm_session *s, const llm_until_request *q, uint64_t *rng, float *mu) {
+    if (!q->chain) return llm_infer_next_token_greedy(m, s);
+    return llm_infer_next_token_sampled_chain(m, s, q->chain, rng, mu);
+}
+
 extern "C" {
 
 // test hook: which = 0 the dispatching version, 1 the scalar loop
@@ -590,6 +639,178 @@ int llm_infer_tokens_sampled_batch_via(llm_batch_entry step, llm_batch_sample_en
         return chain(graphs, nb, k, params, w, wn, r, ids);
     };
     return tokens_sampled_batch(step, chain ? &call : nullptr, m, sessions, B, n, &c, rngs, nullptr, out_ids);
+}
+
+// ---- generation that stops ----
+// One session (`entry` = ggml_hip_decode_chain_requests, or NULL: always the stepped loop).  tokens_sampled's two attempts: the chain
+// continues a single-token fused-plan run, so behind a prompt chunk one stepped token arms it.  The entry is asked for what is left of
+// the budget and ends by itself; whatever it declines is left to the stepped loop under the same rule.
+int llm_infer_until_via(llm_chain_requests_entry entry, llm_model *m, llm_session *s, const llm_until_request *req, uint64_t *rng, float *mu,
+                        int32_t *out, int32_t *n_out, int32_t *ended_by) {
+    if (!m || !s || !s->s || !out || !n_out || !ended_by) return -1;
+    if (!until_request_ok(req, s->s->last_logits.size(), rng, mu)) return -1;
+    const UntilRule rule(req, s->s->n_past, m->llama->params.context_size);
+    int done = 0, why = rule.budget == 0 ? LLM_ENDED_BY_CONTEXT : 0, ran = 0;
+    for (int attempt = 0; attempt < 2 && !why; attempt++) {
+        if (entry && m->stages.empty() && s->s->last_graph) {
+            const std::vector<llm::TokenId> &h = s->s->tokens;
+            const size_t w = std::min(h.size(), (size_t)SAMPLER_WINDOW);
+            const int left = rule.budget - done;
+            const ggml_hip_chain_end end = until_end(req, left);
+            uint64_t r = rng ? *rng : 0;
+            float u = mu ? *mu : 0.0f;
+            int32_t drawn = 0, dev_why = 0;
+            std::vector<int32_t> ids((size_t)left);  // (a buffer of the chain's own: a declining entry's scribbles stay away from out)
+            if (entry(s->s->last_graph, left, req->chain, &end, h.data() + (h.size() - w), (int)w, rng ? &r : nullptr, mu ? &u : nullptr, ids.data(),
+                      &drawn, &dev_why, s->s->last_logits.data()) == 0) {
+                std::copy(ids.begin(), ids.begin() + drawn, out + done);
+                s->s->advance_device_chain((const llm::TokenId *)ids.data(), (size_t)drawn);
+                if (rng) *rng = r;
+                if (mu) *mu = u;
+                done += drawn;
+                why = dev_why == GGML_HIP_CHAIN_END_STOP ? LLM_ENDED_BY_STOP : rule.out_of_budget();
+                ran = 1;
+                break;
+            }
+        }
+        const int32_t id = until_step(m, s, req, rng, mu);
+        if (id < 0) return -1;  // (only the first: the parameters held for it, and hold for every later one)
+        out[done++] = id;
+        why = rule.after(done, id);
+    }
+    while (!why) {
+        const int32_t id = until_step(m, s, req, rng, mu);
+        out[done++] = id;
+        why = rule.after(done, id);
+    }
+    for (int i = done; i < req->max_tokens; i++) out[i] = -1;
+    *n_out = done;
+    *ended_by = why;
+    return ran;
+}
+// B sessions (`entry` = ggml_hip_decode_batch_requests; `step` = ggml_hip_decode_batch for the stepped form; either may be NULL).
+// The host draws row 0 for every session — a session whose first token is a stop id enters the chain with a budget of one evaluation —
+// and the chain runs for the largest budget.  Without an entry, or when it declines, or when a session has no room at all: steps over
+// the sessions that are still going, each drawn from its own request.
+int llm_infer_until_batch_via(llm_batch_entry step, llm_batch_requests_entry entry, llm_model *m, llm_session *const *sessions, int B,
+                              const llm_until_request *reqs, uint64_t *rngs, float *mus, int32_t *out_ids, int32_t *n_out, int32_t *ended_by) {
+    if (!reqs || !out_ids || !n_out || !ended_by || !batch_sessions_ok(m, sessions, B, 0)) return -1;
+    const size_t V = m->llama->hyperparameters.n_vocab;
+    int n = 0;
+    bool room_for_all = true;
+    std::vector<UntilRule> rules;
+    for (int i = 0; i < B; i++) {
+        if (!until_request_ok(&reqs[i], V, rngs ? &rngs[i] : nullptr, mus ? &mus[i] : nullptr)) return -1;
+        rules.emplace_back(&reqs[i], sessions[i]->s->n_past, m->llama->params.context_size);
+        n = std::max(n, (int)reqs[i].max_tokens);
+        room_for_all = room_for_all && rules.back().budget > 0;
+    }
+    std::vector<int> done((size_t)B, 0), why((size_t)B, 0);
+    std::fill(out_ids, out_ids + (size_t)n * B, -1);
+    const auto history = [&](int i) -> const std::vector<llm::TokenId> & { return sessions[i]->s->tokens; };
+    if (entry && B >= 2 && room_for_all) {
+        std::vector<uint64_t> r((size_t)B, 0);
+        std::vector<float> u((size_t)B, 0.0f);
+        if (rngs) std::copy(rngs, rngs + B, r.begin());
+        if (mus) std::copy(mus, mus + B, u.begin());
+        std::vector<int32_t> first((size_t)B), windows((size_t)B * SAMPLER_WINDOW, 0), window_n((size_t)B);
+        std::vector<const ggml_hip_sampler_chain *> chains((size_t)B);
+        std::vector<ggml_hip_chain_end> ends((size_t)B);
+        int n_steps = 1;
+        bool drew = true;
+        for (int i = 0; i < B && drew; i++) {
+            const llm::InferenceSession &s = *sessions[i]->s;
+            first[(size_t)i] = until_draw(&reqs[i], s.last_logits.data(), V, history(i).data(), history(i).size(), &r[(size_t)i], mus ? &u[(size_t)i] : nullptr);
+            drew = first[(size_t)i] >= 0;
+            chains[(size_t)i] = reqs[i].chain;
+            ends[(size_t)i] = until_end(&reqs[i], rules[(size_t)i].is_stop(first[(size_t)i]) ? 1 : rules[(size_t)i].budget);
+            n_steps = std::max(n_steps, (int)ends[(size_t)i].budget);
+        }
+        if (!drew) return -1;
+        Staged st(m, sessions, first.data(), B);
+        for (int i = 0; i < B; i++) {  // the window the device starts from: the session's history with this token at its end
+            const std::vector<llm::TokenId> &h = history(i);
+            const size_t keep = std::min(h.size(), (size_t)SAMPLER_WINDOW - 1);
+            int32_t *w = windows.data() + (size_t)i * SAMPLER_WINDOW;
+            for (size_t j = 0; j < keep; j++) w[j] = (int32_t)h[h.size() - keep + j];
+            w[keep] = first[(size_t)i];
+            window_n[(size_t)i] = (int32_t)keep + 1;
+        }
+        std::vector<int32_t> rest((size_t)(n_steps - 1) * (size_t)B + 1), evaluated((size_t)B), dev_why((size_t)B);
+        if (entry(st.graphs.data(), B, n_steps, chains.data(), ends.data(), windows.data(), window_n.data(), r.data(), mus ? u.data() : nullptr,
+                  rest.data(), evaluated.data(), dev_why.data()) == 0) {
+            std::vector<llm::TokenId> col;
+            for (int i = 0; i < B; i++) {
+                llm::InferenceSession &s = *sessions[i]->s;
+                const int e = evaluated[(size_t)i];
+                st.finish(i);
+                s.tokens.push_back((llm::TokenId)first[(size_t)i]);
+                out_ids[i] = first[(size_t)i];
+                col.clear();
+                for (int k = 1; k < e; k++) col.push_back((llm::TokenId)(out_ids[(size_t)k * B + i] = rest[(size_t)(k - 1) * B + i]));
+                if (!col.empty()) s.advance_device_chain(col.data(), col.size());
+                n_out[i] = e;
+                ended_by[i] = (dev_why[(size_t)i] == GGML_HIP_CHAIN_END_STOP || rules[(size_t)i].is_stop(first[(size_t)i])) ? LLM_ENDED_BY_STOP
+                                                                                                                         : rules[(size_t)i].out_of_budget();
+            }
+            if (rngs) std::copy(r.begin(), r.end(), rngs);
+            if (mus) std::copy(u.begin(), u.end(), mus);
+            return 1;
+        }
+    }
+    for (int i = 0; i < B; i++) why[(size_t)i] = rules[(size_t)i].budget == 0 ? LLM_ENDED_BY_CONTEXT : 0;
+    for (;;) {
+        std::vector<llm_session *> going;
+        std::vector<int> who;
+        std::vector<int32_t> next;
+        for (int i = 0; i < B; i++)
+            if (!why[(size_t)i]) {
+                const llm::InferenceSession &s = *sessions[i]->s;
+                uint64_t r = rngs ? rngs[i] : 0;
+                float u = mus ? mus[i] : 0.0f;
+                const int32_t id = until_draw(&reqs[i], s.last_logits.data(), V, history(i).data(), history(i).size(), &r, mus ? &u : nullptr);
+                if (id < 0) return -1;  // (only in the first round, before anything moved: the parameters hold for every later draw)
+                if (rngs) rngs[i] = r;
+                if (mus) mus[i] = u;
+                going.push_back(sessions[i]);
+                who.push_back(i);
+                next.push_back(id);
+            }
+        if (going.empty()) break;
+        if (llm_evaluate_batch_via(step, m, going.data(), next.data(), (int)going.size(), nullptr) < 0) return -1;
+        for (size_t j = 0; j < going.size(); j++) {
+            const int i = who[j];
+            going[j]->s->tokens.push_back((llm::TokenId)next[j]);
+            out_ids[(size_t)done[(size_t)i] * B + i] = next[j];
+            done[(size_t)i]++;
+            why[(size_t)i] = rules[(size_t)i].after(done[(size_t)i], next[j]);
+        }
+    }
+    for (int i = 0; i < B; i++) {
+        n_out[i] = done[(size_t)i];
+        ended_by[i] = why[(size_t)i];
+    }
+    return 0;
+}
+// the end rule alone, on recorded rows (test hook): the same UntilRule, the same draw, no session
+int llm_until_rule(const float *rows, int n_rows, int V, const llm_until_request *req, const int32_t *window, int n_window, int n_past0,
+                   int context_size, uint64_t *rng, float *mu, int32_t *out, int32_t *n_out, int32_t *ended_by) {
+    if (!rows || n_rows < 0 || V < 1 || !out || !n_out || !ended_by || n_window < 0 || (n_window > 0 && !window) || n_past0 < 0 || context_size < 1)
+        return -1;
+    if (!until_request_ok(req, (size_t)V, rng, mu)) return -1;
+    const UntilRule rule(req, (size_t)n_past0, (size_t)context_size);
+    std::vector<int32_t> hist(window, window + n_window);
+    int done = 0, why = rule.budget == 0 ? LLM_ENDED_BY_CONTEXT : 0;
+    while (!why && done < n_rows) {
+        const int32_t id = until_draw(req, rows + (size_t)done * V, (size_t)V, hist.data(), hist.size(), rng, mu);
+        if (id < 0) return -1;
+        hist.push_back(id);
+        out[done++] = id;
+        why = rule.after(done, id);
+    }
+    *n_out = done;
+    *ended_by = why;
+    return 0;
 }
 
 }  // extern "C"

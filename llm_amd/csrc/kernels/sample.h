@@ -43,9 +43,61 @@ static_assert(sizeof(SampleHead) == sizeof(SampleBias) + sizeof(SampleState), "S
 // which stages an instantiation of k_sample_next carries: the default chain (the four parameters: today's kernel, registers and all),
 // the whole truncating chain (specification A - D), Mirostat 2 (A, E; on chip only)
 enum { SAMPLE_DEFAULT = 0, SAMPLE_FULL = 1, SAMPLE_MIROSTAT = 2 };
-__device__ __forceinline__ int sample_n_bias(const SampleCols *sc) {  // (0 .. 64 whatever the table says)
+template <class Params>
+__device__ __forceinline__ int sample_n_bias(const Params *sc) {  // (0 .. 64 whatever the table says)
     const int n = sc->n_bias;
     return n < 0 ? 0 : (n > SAMPLER_BIAS_MAX ? SAMPLER_BIAS_MAX : n);
+}
+
+// ---- chains that stop (ggml_hip_decode_chain_requests / ggml_hip_decode_batch_requests): every column carries its own request — its own
+// sampler or the first maximum, its own stop ids, its own budget of draws.  SampleCols keeps the rings and nothing else of such a chain;
+// the parameters it holds once are here per column, beside a bias table per column, and the table lies in a buffer of its own
+// (DecodePlan::chain_req, allocated on first use).  What comes back with the ids is the head of the table, SampleReqBack: the generator
+// states and Mirostat states where k_sample_next looks for them (its `rng` argument points at the table), the draws each column
+// made, why it ended, and whether it is still live.  A column's entries are written by that column's own workgroup alone.
+constexpr int CHAIN_STOP_MAX = 8;
+enum { CHAIN_END_NONE = 0, CHAIN_END_BUDGET = 1, CHAIN_END_STOP = 2, CHAIN_END_CONTEXT = 3 };  // (the last: the host loop's alone)
+enum { SAMPLE_GREEDY = 3, SAMPLE_CLASSES = 4 };  // the instantiation a column needs: SAMPLE_DEFAULT .. SAMPLE_MIROSTAT, or the first maximum
+struct SampleReqParams {  // (SampleCols' parameters, by the same names)
+    int k;
+    float top_p, temperature, penalty;
+    float freq, presence, tail_free_z, typical_p, min_p;
+    int mirostat;
+    float tau, eta;
+    int n_bias;
+};
+struct SampleReqBack {
+    SampleState state;
+    int n_drawn[BATCH_COLS_MAX], ended_by[BATCH_COLS_MAX], live[BATCH_COLS_MAX];
+};
+struct SampleReqs {
+    SampleReqBack back;                             // first: the table's address is its SampleState's
+    int max_draws[BATCH_COLS_MAX];                  // the column ends with its max_draws-th draw (0: it never draws)
+    int n_stop[BATCH_COLS_MAX];                     // ... or with a draw of one of its stop ids
+    int stop_id[BATCH_COLS_MAX][CHAIN_STOP_MAX];
+    int n_list[SAMPLE_CLASSES];                     // the columns of each class, compacted: the grid of class s is n_list[s] workgroups,
+    int list[SAMPLE_CLASSES][BATCH_COLS_MAX];       // workgroup w of it works on column list[s][w].  Fixed for the whole call.
+    SampleReqParams prm[BATCH_COLS_MAX];
+    SampleBias bias[BATCH_COLS_MAX];
+};
+// whose parameters an instantiation reads: the one set of a SampleCols, or column c's request
+template <bool REQ>
+__device__ __forceinline__ auto sample_params_of(const SampleCols *sc, const void *table, int c) {
+    if constexpr (REQ) return &static_cast<const SampleReqs *>(table)->prm[c];
+    else return sc;
+}
+// the end of a live column's tail (one thread): the draw is counted, and the column stops being live if the id is one of its stop ids
+// or its budget is used up.  The stop id wins: it is what the reference's loop would report (EndOfText, inference_session.rs:404-408).
+__device__ __forceinline__ void chain_req_drawn(SampleReqs *rq, int c, int id) {
+    const int n = rq->back.n_drawn[c] + 1;
+    rq->back.n_drawn[c] = n;
+    const int ns = rq->n_stop[c] < CHAIN_STOP_MAX ? rq->n_stop[c] : CHAIN_STOP_MAX;
+    bool stop = false;
+    for (int j = 0; j < ns; j++) stop = stop || rq->stop_id[c][j] == id;
+    if (stop || n >= rq->max_draws[c]) {
+        rq->back.ended_by[c] = stop ? CHAIN_END_STOP : CHAIN_END_BUDGET;
+        rq->back.live[c] = 0;
+    }
 }
 
 // ---- the selection: which keys of the row are its k largest.  Over global memory (topk_kth_key, k_topk's radix passes) the row is
@@ -207,7 +259,12 @@ __device__ __forceinline__ uint32_t sample_select(const float (&v)[SELECT_PER_TH
 //               tail: mu, the generator, the parameters, the ring.
 // k is 1 .. min(SAMPLER_K_MAX, V) (not read by Mirostat 2), and V <= SELECT_CAP on chip (the host declines / picks so; the kernel
 // writes nothing otherwise).
-template <bool ONCHIP, int CHAIN = SAMPLE_DEFAULT>
+//
+// REQ (the chains that stop): `rng` is the call's SampleReqs.  Workgroup w works on column list[CHAIN][w] with that column's own
+// parameters, bias table and end rule; sc holds the rings alone.  A column that is not live touches nothing but out[c] = -1 — the test
+// is uniform over the workgroup and comes before any barrier and before the row is loaded — so the step behind this launch evaluates
+// the same token at the same position again.  A live column's tail also counts the draw and applies the end rule (chain_req_drawn).
+template <bool ONCHIP, int CHAIN = SAMPLE_DEFAULT, bool REQ = false>
 __global__ void __launch_bounds__(1024) k_sample_next(const float *__restrict__ logits, int V, DecParams *prm, BatchCols *bc,
                                                       SampleCols *sc, unsigned long long *rng, int *__restrict__ out) {
     constexpr int PMAX = 512;  // power of two >= SAMPLER_K_MAX + SAMPLER_M_MAX
@@ -219,19 +276,32 @@ __global__ void __launch_bounds__(1024) k_sample_next(const float *__restrict__ 
     __shared__ float s_v[SAMPLER_K_MAX], s_q[SAMPLER_K_MAX], s_p[SAMPLER_K_MAX];
     __shared__ int s_id[SAMPLER_K_MAX], s_h[SAMPLER_WINDOW], s_win[NM];
     __shared__ int s_cnt, s_wn;
-    const int c = blockIdx.x, tid = threadIdx.x;
-    const int k = sc->k;
+    int c = blockIdx.x;
+    const int tid = threadIdx.x;
+    [[maybe_unused]] SampleReqs *rq = nullptr;
+    if constexpr (REQ) {
+        rq = reinterpret_cast<SampleReqs *>(rng);
+        if (c >= BATCH_COLS_MAX || c >= rq->n_list[CHAIN]) return;
+        c = rq->list[CHAIN][c];
+        if (c < 0 || c >= BATCH_COLS_MAX) return;
+        if (!rq->back.live[c]) {
+            if (tid == 0) out[c] = -1;
+            return;
+        }
+    }
+    const auto *pp = sample_params_of<REQ>(sc, rng, c);
+    const int k = pp->k;
     if (c >= BATCH_COLS_MAX || (ONCHIP && V > SELECT_CAP)) return;
     if (CHAIN != SAMPLE_MIROSTAT && (k < 1 || k > SAMPLER_K_MAX || k > V)) return;
     const float *x = logits + (size_t)c * V;
     [[maybe_unused]] float v[ONCHIP ? SELECT_PER_THREAD : 1];
     if constexpr (ONCHIP) sample_select_load(x, V, v);  // (in flight while the window is set up)
-    const float penalty = sc->penalty, temperature = sc->temperature;
+    const float penalty = pp->penalty, temperature = pp->temperature;
     const int hn = sc->hist_n[c];
     const int nw = hn < SAMPLER_WINDOW ? (hn < 0 ? 0 : hn) : SAMPLER_WINDOW;
     int P = 1;
     if constexpr (CHAIN != SAMPLE_MIROSTAT) {
-        while (P < k + nw + (CHAIN == SAMPLE_DEFAULT ? 0 : sample_n_bias(sc))) P <<= 1;
+        while (P < k + nw + (CHAIN == SAMPLE_DEFAULT ? 0 : sample_n_bias(pp))) P <<= 1;
         for (int i = tid; i < P; i += 1024) s_keys[i] = 0;  // (below every key of a row without NaN)
     }
     if (tid < SAMPLER_WINDOW) s_h[tid] = tid < nw ? sc->hist[c][tid] : -1;
@@ -253,10 +323,11 @@ __global__ void __launch_bounds__(1024) k_sample_next(const float *__restrict__ 
     } else {
         __shared__ int s_bid[SAMPLER_BIAS_MAX];
         __shared__ float s_bv[SAMPLER_BIAS_MAX], s_adj[SAMPLER_M_MAX];
-        const int nb = sample_n_bias(sc);
-        const float freq = sc->freq, presence = sc->presence;
+        const int nb = sample_n_bias(pp);
+        const float freq = pp->freq, presence = pp->presence;
         if (tid < SAMPLER_BIAS_MAX) {
             const SampleBias *sb = reinterpret_cast<const SampleBias *>(rng) - 1;  // (SampleHead)
+            if constexpr (REQ) sb = &rq->bias[c];
             s_bid[tid] = tid < nb ? sb->id[tid] : -1;
             s_bv[tid] = tid < nb ? sb->b[tid] : 0.0f;
         }
@@ -411,12 +482,13 @@ __global__ void __launch_bounds__(1024) k_sample_next(const float *__restrict__ 
                         acc += (double)v[i];
                         done = walk && urel < acc;
                     }
-                st->mu[c] = sampler_mirostat_mu(mu, e_sel, s_SR, sc->tau, sc->eta);
+                st->mu[c] = sampler_mirostat_mu(mu, e_sel, s_SR, pp->tau, pp->eta);
                 st->rng[c] = s_x;
                 write_next_token(prm, bc, c, sel);
                 out[c] = sel;
                 sc->hist[c][(unsigned)hn % SAMPLER_WINDOW] = sel;
                 sc->hist_n[c] = hn + 1;
+                if constexpr (REQ) chain_req_drawn(rq, c, sel);
             }
             return;
         }
@@ -460,10 +532,10 @@ __global__ void __launch_bounds__(1024) k_sample_next(const float *__restrict__ 
     if constexpr (CHAIN == SAMPLE_FULL) {
         __shared__ double s_t[SAMPLER_K_MAX], s_mean, s_Q;
         __shared__ int s_ord[SAMPLER_K_MAX], s_idx[SAMPLER_K_MAX], s_n1;
-        const float typical_p = sc->typical_p;
+        const float typical_p = pp->typical_p;
         const bool typ = typical_p < 1.0f;  // (the same for every thread: the barriers below are taken by all or none)
         if (tid == 0) {
-            const int n1 = sampler_tail_free(s_q, k, sc->tail_free_z);
+            const int n1 = sampler_tail_free(s_q, k, pp->tail_free_z);
             double Q = 0.0;
             if (typ) s_mean = sampler_typical_mean(s_v, s_q, n1, &Q);
             s_Q = Q;
@@ -487,30 +559,59 @@ __global__ void __launch_bounds__(1024) k_sample_next(const float *__restrict__ 
         }
         if (tid == 0) {
             uint64_t state = rng[c];
-            const int id = s_id[sampler_pick_chain(s_q, s_p, n1, typ ? s_ord : nullptr, s_Q, typical_p, sc->top_p, sc->min_p, s_idx, &state)];
+            const int id = s_id[sampler_pick_chain(s_q, s_p, n1, typ ? s_ord : nullptr, s_Q, typical_p, pp->top_p, pp->min_p, s_idx, &state)];
             rng[c] = state;
             write_next_token(prm, bc, c, id);
             out[c] = id;
             sc->hist[c][(unsigned)hn % SAMPLER_WINDOW] = id;
             sc->hist_n[c] = hn + 1;
+            if constexpr (REQ) chain_req_drawn(rq, c, id);
         }
         return;
     }
     if (tid == 0) {
         uint64_t state = rng[c];
-        const int id = s_id[sampler_pick(s_q, s_p, k, sc->top_p, &state)];
+        const int id = s_id[sampler_pick(s_q, s_p, k, pp->top_p, &state)];
         rng[c] = state;
         write_next_token(prm, bc, c, id);
         out[c] = id;
         sc->hist[c][(unsigned)hn % SAMPLER_WINDOW] = id;
         sc->hist_n[c] = hn + 1;
+        if constexpr (REQ) chain_req_drawn(rq, c, id);
     }
 }
+#ifdef SAMPLE_REQ_OBJECT
+// k_argmax_next for the chains that stop: the columns whose request is "greedy", through the same table — the same live test in the same
+// place, the first maximum, the same tail (the id goes to the column's ring too: one history whatever the column's class).
+__global__ void __launch_bounds__(1024) k_argmax_next_req(const float *__restrict__ logits, int V, DecParams *prm, BatchCols *bc, SampleCols *sc,
+                                                          SampleReqs *rq, int *__restrict__ out) {
+    int c = blockIdx.x;
+    if (c >= BATCH_COLS_MAX || c >= rq->n_list[SAMPLE_GREEDY]) return;
+    c = rq->list[SAMPLE_GREEDY][c];
+    if (c < 0 || c >= BATCH_COLS_MAX) return;
+    if (!rq->back.live[c]) {
+        if (threadIdx.x == 0) out[c] = -1;
+        return;
+    }
+    const int bi = argmax_first_block(logits + (size_t)c * V, V);
+    if (threadIdx.x == 0) {
+        const int hn = sc->hist_n[c];
+        write_next_token(prm, bc, c, bi);
+        out[c] = bi;
+        sc->hist[c][(unsigned)hn % SAMPLER_WINDOW] = bi;
+        sc->hist_n[c] = hn + 1;
+        chain_req_drawn(rq, c, bi);
+    }
+}
+#endif
 // The one launch of the sampler, for the chain, the batched chain and the test hook: B columns, the selection picked from V alone, the
 // stages from the chain's parameters (`stages`: SAMPLE_DEFAULT for neutral extras — today's kernel).  rng is a SampleHead's state.
 // The SAMPLE_FULL and SAMPLE_MIROSTAT instantiations are compiled into an object of their own (sample_ext.hip, which defines
 // launch_sample_next_ext): the code object that holds every other kernel of the library keeps its contents and its addresses.
+// The chains that stop launch through launch_next_token_req (sample_req.hip, a third object for the same reason): every class of
+// columns that is present once, n_class[s] workgroups each, over the lists of the SampleReqs `reqs`.
 #ifndef SAMPLE_EXT_OBJECT
+void launch_next_token_req(hipStream_t stream, const int *n_class, const float *logits, int V, void *prm, void *bc, void *sc, void *reqs, int *out);
 void launch_sample_next_ext(hipStream_t stream, int B, const float *logits, int V, void *prm, void *bc, void *sc, void *state, int *out, int stages);
 static inline void launch_sample_next(hipStream_t stream, int B, const float *logits, int V, DecParams *prm, BatchCols *bc, SampleCols *sc,
                                       unsigned long long *rng, int *out, int stages = SAMPLE_DEFAULT) {

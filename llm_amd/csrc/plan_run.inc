@@ -569,6 +569,170 @@ static void launch_next_token(DecodePlan *p, int B, const float *logits, const B
         hipLaunchKernelGGL(k_argmax_next, dim3((unsigned)B), dim3(1024), 0, g.stream, logits, (int)p->m.V, p->prm, p->bcols, out);
 }
 
+// ---- the chains that stop (ggml_hip_decode_chain_requests, ggml_hip_decode_batch_requests): a request per column ----
+struct ChainRequests {
+    const ggml_hip_sampler_chain *const *chains;  // [B]; a null entry: the first maximum
+    const ggml_hip_chain_end *ends;               // [B]
+    const int32_t *windows, *window_n;            // [B][64], [B]: as a BatchSample's; may be null when every column is greedy
+    uint64_t *rng;                                // [B], in / out (likewise)
+    float *mu;                                    // [B], in / out; may be null without Mirostat
+    int32_t *n_count, *ended_by;                  // [B], out: draws (one session) / evaluations (batched); CHAIN_END_*
+    int draws_off;                                // a column may draw budget - draws_off times: 0 for one session, 1 batched (step 0 is an evaluation, not a draw)
+    int n_class[SAMPLE_CLASSES];                  // (chain_req_fill) how many columns need each instantiation
+    bool any_sampled(int B) const {
+        for (int c = 0; c < B; c++)
+            if (chains[c]) return true;
+        return false;
+    }
+    // whether some column can end before the call's last step: otherwise the call enqueues what its siblings enqueue, nothing polled
+    bool can_end_early(int B, int steps) const {
+        for (int c = 0; c < B; c++)
+            if (ends[c].n_stop > 0 || ends[c].budget != steps) return true;
+        return false;
+    }
+};
+static int chain_req_class(const ggml_hip_sampler_chain *q) {
+    return !q ? SAMPLE_GREEDY : (q->mirostat == 2 ? SAMPLE_MIROSTAT : (sampler_chain_is_default(*q) ? SAMPLE_DEFAULT : SAMPLE_FULL));
+}
+// what the request table can take, per column (checked before anything runs): the sampler as batch_sample_ok, the end rule; a budget
+// in lo .. hi
+static bool chain_requests_ok(const ChainRequests &r, int B, int64_t V, int lo, int hi) {
+    for (int c = 0; c < B; c++) {
+        const ggml_hip_chain_end &e = r.ends[c];
+        if (e.n_stop < 0 || e.n_stop > CHAIN_STOP_MAX || e.budget < lo || e.budget > hi) return false;
+        for (int j = 0; j < e.n_stop; j++)
+            if (e.stop_id[j] < 0 || e.stop_id[j] >= V) return false;
+        if (r.chains[c]) {
+            if (!r.windows || !r.window_n || !r.rng) return false;
+            const BatchSample one = {r.chains[c], r.windows + (size_t)c * SAMPLER_WINDOW, r.window_n + c, r.rng + c, r.mu ? r.mu + c : nullptr};
+            if (!batch_sample_ok(one, 1, V)) return false;
+        } else if (r.windows && r.window_n) {
+            if (r.window_n[c] < 0 || r.window_n[c] > SAMPLER_WINDOW) return false;
+            for (int i = 0; i < r.window_n[c]; i++)
+                if (r.windows[c * SAMPLER_WINDOW + i] < 0 || r.windows[c * SAMPLER_WINDOW + i] >= V) return false;
+        }
+    }
+    return true;
+}
+// the rings of the B columns into a SampleCols (its parameters stay zero: the requests carry them)
+static void chain_req_rings(SampleCols &hs, const ChainRequests &r, int B) {
+    memset(&hs, 0, sizeof(hs));
+    for (int c = 0; c < B && r.windows && r.window_n; c++) {
+        hs.hist_n[c] = r.window_n[c];
+        for (int i = 0; i < r.window_n[c]; i++) hs.hist[c][i] = r.windows[c * SAMPLER_WINDOW + i];
+    }
+}
+// the request table of a call: every column's parameters, bias table, end rule and state, and the compacted column list of every class
+static void chain_req_table(SampleReqs &t, ChainRequests &r, int B) {
+    memset(&t, 0, sizeof(t));
+    for (int c = 0; c < B; c++) {
+        const ggml_hip_sampler_chain *q = r.chains[c];
+        const int cls = chain_req_class(q);
+        t.list[cls][t.n_list[cls]++] = c;
+        if (q) {
+            SampleCols one;  // (the one place that knows the parameters' names: sample_cols_params)
+            memset(&one, 0, sizeof(one));
+            sample_cols_params(one, *q);
+            SampleReqParams &d = t.prm[c];
+            d.k = one.k; d.top_p = one.top_p; d.temperature = one.temperature; d.penalty = one.penalty;
+            d.freq = one.freq; d.presence = one.presence; d.tail_free_z = one.tail_free_z; d.typical_p = one.typical_p; d.min_p = one.min_p;
+            d.mirostat = one.mirostat; d.tau = one.tau; d.eta = one.eta; d.n_bias = one.n_bias;
+            for (int i = 0; i < q->n_bias; i++) {
+                t.bias[c].id[i] = q->bias_id[i];
+                t.bias[c].b[i] = q->bias[i];
+            }
+            t.back.state.rng[c] = r.rng[c];
+            if (r.mu) t.back.state.mu[c] = r.mu[c];
+        }
+        const ggml_hip_chain_end &e = r.ends[c];
+        t.max_draws[c] = e.budget - r.draws_off;
+        t.n_stop[c] = e.n_stop;
+        for (int j = 0; j < e.n_stop; j++) t.stop_id[c][j] = e.stop_id[j];
+        t.back.live[c] = t.max_draws[c] > 0;
+        t.back.ended_by[c] = t.back.live[c] ? CHAIN_END_NONE : CHAIN_END_BUDGET;
+    }
+    for (int s = 0; s < SAMPLE_CLASSES; s++) r.n_class[s] = t.n_list[s];
+}
+// ... goes up, once per call: the rings into the plan's SampleCols, the table into DecodePlan::chain_req (a buffer of its own, made
+// at the first such call: no buffer of the plan moves), chain_out gets room for n_ids ids (which start at its front)
+static void chain_req_fill(DecodePlan *p, ChainRequests &r, int B, int n_ids) {
+    chain_out_reserve(p, n_ids);
+    if (!p->chain_req) HIP_CHECK(hipMalloc((void **)&p->chain_req, sizeof(SampleReqs)));
+    SampleCols hs;
+    chain_req_rings(hs, r, B);
+    h2d_small((char *)p->scols, &hs, sizeof(hs));
+    SampleReqs t;
+    chain_req_table(t, r, B);
+    h2d_small((char *)p->chain_req, &t, sizeof(t));
+}
+// ... and what comes back of it with the ids (SampleReqBack): states, counts, reasons
+static void chain_req_back(const SampleReqBack &b, const ChainRequests &r, int B) {
+    for (int c = 0; c < B; c++) {
+        if (r.chains[c]) {
+            r.rng[c] = b.state.rng[c];
+            if (r.mu && r.chains[c]->mirostat == 2) r.mu[c] = b.state.mu[c];
+        }
+        r.n_count[c] = b.n_drawn[c] + r.draws_off;
+        r.ended_by[c] = b.ended_by[c];
+        if (b.ended_by[c] == CHAIN_END_STOP) g.stat_chain_stopped_columns++;
+    }
+}
+static void launch_next_token_requests(DecodePlan *p, const ChainRequests &r, const float *logits, int *out) {
+    launch_next_token_req(g.stream, r.n_class, logits, (int)p->m.V, p->prm, p->bcols, p->scols, p->chain_req, out);
+}
+// The columns' live flags behind a group of steps: a small copy into pinned memory of parity q and an event behind it.  The host
+// waits on that event (never on memory), and only once the NEXT group is enqueued, so the device never idles.
+static void chain_live_queue(DecodePlan *p, int q) {
+    if (!g.chain_live_pin) {
+        HIP_CHECK(hipHostMalloc((void **)&g.chain_live_pin, 2 * BATCH_COLS_MAX * 4, hipHostMallocDefault));
+        for (int i = 0; i < 2; i++) HIP_CHECK(hipEventCreateWithFlags(&g.chain_live_ev[i], hipEventDisableTiming));
+    }
+    HIP_CHECK(hipMemcpyAsync(g.chain_live_pin + q * BATCH_COLS_MAX, (const char *)p->chain_req + offsetof(SampleReqBack, live), BATCH_COLS_MAX * 4,
+                             hipMemcpyDeviceToHost, g.stream));
+    HIP_CHECK(hipEventRecord(g.chain_live_ev[q], g.stream));
+}
+static bool chain_live_any(int q, int B) {
+    HIP_CHECK(hipEventSynchronize(g.chain_live_ev[q]));
+    for (int c = 0; c < B; c++)
+        if (g.chain_live_pin[q * BATCH_COLS_MAX + c]) return true;
+    return false;
+}
+// Enqueues steps first .. last - 1 of a chain that stops — enqueue(i) is step i's launches, the kernel between two steps and the
+// replay — and returns the step behind the last one enqueued.  When no column can end early that is the plain loop.  Otherwise the
+// steps go in groups of option chain_group: behind each group the live flags are read back, waited for once the next group is
+// enqueued, and nothing more is launched once no column was found live.  variant(i) (one session) is the attention variant the host
+// picks for step i from the position it EXPECTS; a frozen session sits at a lower one, and two variants are not known to agree bit
+// for bit at one position — so a group never spans a variant boundary, and a group of another variant is enqueued only after the
+// previous group's flags have been read and the session is still live.  (The batched step has one variant.)
+template <class Enqueue, class Variant>
+static int chain_req_run(DecodePlan *p, const ChainRequests &r, int B, int first, int last, bool early, Enqueue &&enqueue, Variant &&variant) {
+    int i = first;
+    if (!early) {
+        for (; i < last; i++) enqueue(i);
+        return i;
+    }
+    const int G = std::max(1, g.opt_chain_group);
+    int pending = -1, q = 0, av_prev = 0;
+    bool live = false;
+    for (int c = 0; c < B; c++) live = live || r.ends[c].budget - r.draws_off > 0;
+    while (i < last && live) {
+        const int av = variant(i);
+        if (pending >= 0 && av != av_prev) {  // across a variant boundary only behind a look at the flags
+            live = chain_live_any(pending, B);
+            pending = -1;
+            if (!live) break;
+        }
+        // (groups are counted from step 0, which a batched call has run before its first tail: its first group is one step shorter)
+        for (const int e = std::min(last, (i / G + 1) * G); i < e && variant(i) == av; i++) enqueue(i);
+        chain_live_queue(p, q);
+        if (pending >= 0) live = chain_live_any(pending, B);
+        pending = q;
+        q ^= 1;
+        av_prev = av;
+    }
+    return i;
+}
+
 // SURVEY section 8f N3: n greedy tokens back to back without a host round trip per token.  `last` must be the cgraph
 // of the caller's most recent ggml_graph_compute (a single-token LLaMA evaluation that ran as the fused plan, whole
 // model on this device); the plan's decode parameters still hold that token and position on the device, and its
@@ -582,13 +746,19 @@ static void launch_next_token(DecodePlan *p, int B, const float *logits, const B
 // batched chain).  Every plan the greedy chain runs is run: block-format, K-quant, F16.  Option chain_k does not apply: the K-token
 // graph stays greedy-only.  Counted in sample_chain_steps / sample_chain_tokens and, as the greedy chain, in plan_tokens,
 // fused_tokens, fused_heads_tokens and graph_replays.
-static int decode_chain(ggml_cgraph *last, int n, int32_t *out_tokens, float *last_logits, const BatchSample *smp = nullptr) {
+//
+// ggml_hip_decode_chain_requests is the chain with a request (`req`, one column: sampler or first maximum, stop ids, a budget of n
+// draws) and the kernels of sample_req.hip between two replays; it may end before its n-th step (chain_req_run), and the session's
+// position moves by the draws that were made.
+static int decode_chain(ggml_cgraph *last, int n, int32_t *out_tokens, float *last_logits, const BatchSample *smp = nullptr,
+                        ChainRequests *req = nullptr) {
     finish_pending();
     DecodePlan *p = live_plan(g.chain_plan);
     if (!p || g.chain_graph != last || n < 1) return -1;
     const LlamaMatch &m = p->m;
     if (m.N != 1 || !m.logits || !m.wte || m.n_past + 1 + n > m.C) return -1;
     if (smp && (!g.opt_plan_sample_chain || !batch_sample_ok(*smp, 1, m.V))) return -1;
+    if (req && ((req->chains[0] && !g.opt_plan_sample_chain) || !p->scols || !chain_requests_ok(*req, 1, m.V, n, n))) return -1;
     if (p->prm_ahead) {  // a token tail has moved the parameters on (and a run ahead of the caller may be in flight): back to the last evaluated token
         if (!m.embd) return -1;
         const DecParams hp = host_dec_params(m);
@@ -601,7 +771,8 @@ static int decode_chain(ggml_cgraph *last, int n, int32_t *out_tokens, float *la
     g.res_plan = nullptr;
     if (!p->chain_ring) HIP_CHECK(hipMalloc((void **)&p->chain_ring, 64 * 4));
     int ids_off = 0;
-    if (smp) ids_off = sample_cols_fill(p, *smp, 1, n);  // the ring, the parameters, the generator state: once per call
+    if (req) chain_req_fill(p, *req, 1, n);
+    else if (smp) ids_off = sample_cols_fill(p, *smp, 1, n);  // the ring, the parameters, the generator state: once per call
     else chain_out_reserve(p, n);
     int *ids = p->chain_out + ids_off;
     const bool use_graph = g.opt_graph && !g.timing.on && p->any_captured();
@@ -609,7 +780,7 @@ static int decode_chain(ggml_cgraph *last, int n, int32_t *out_tokens, float *la
     // option chain_k = K (> 1): K tokens per graph launch — every kernel of the plan reads its token and position from the
     // DecParams that k_argmax_next advances on the device, so the launches of consecutive tokens are the same launches.  Only
     // while the whole group stays on the short-context attention variant; the graph's sampled ids land in chain_out[i0 ..].
-    if (use_graph && g.opt_chain_k > 1 && !smp) {
+    if (use_graph && g.opt_chain_k > 1 && !smp && !req) {
         const int K = g.opt_chain_k;
         if ((const char *)first_logits != p->logits_out) {  // the K-token graph's first argmax is captured on set 0
             HIP_CHECK(hipMemcpyAsync(p->logits_out, first_logits, (size_t)m.V * 4, hipMemcpyDeviceToDevice, g.stream));
@@ -634,10 +805,12 @@ static int decode_chain(ggml_cgraph *last, int n, int32_t *out_tokens, float *la
             i0 += K;
         }
     }
-    for (int i = i0; i < n; i++) {
-        launch_next_token(p, 1, i == 0 ? first_logits : (const float *)p->logits_out, smp, ids + i);
-        // the token of step i sits at position n_past + 1 + i; same rule as try_decode_plan for the attention variant
-        const int av = attn_variant(m, p, m.n_past + 1 + i + 1);
+    // the token of step i sits at position n_past + 1 + i; same rule as try_decode_plan for the attention variant
+    const auto variant = [&](int i) { return attn_variant(m, p, m.n_past + 1 + i + 1); };
+    const auto enqueue = [&](int i) {
+        if (req) launch_next_token_requests(p, *req, i == 0 ? first_logits : (const float *)p->logits_out, ids + i);
+        else launch_next_token(p, 1, i == 0 ? first_logits : (const float *)p->logits_out, smp, ids + i);
+        const int av = variant(i);
         // (the chain's books are not count_token_forms': no fused_wo_tokens, fused_affine_tokens or split_tokens — values tests read; left as they are)
         if (av != AV_SPLIT && fused_qkv_shape(m, av_heads_split(av)).ok) g.stat_fused_tokens++;
         if (av >= AV_FUSED2) g.stat_fused_heads_tokens++;
@@ -648,10 +821,18 @@ static int decode_chain(ggml_cgraph *last, int n, int32_t *out_tokens, float *la
         } else {
             plan_launch_decode(p, av);
         }
-    }
+    };
+    int launched = n;  // steps enqueued: all of them, unless a request ended the chain early
+    if (req) launched = chain_req_run(p, *req, 1, i0, n, req->can_end_early(1, n), enqueue, variant);
+    else
+        for (int i = i0; i < n; i++) enqueue(i);
     HIP_CHECK(hipGetLastError());
     std::vector<int32_t> sample_back;  // a sampled chain's read-back: the generator state, then the ids
-    if (smp) {
+    SampleReqBack req_back;
+    if (req) {
+        d2h_queue(&req_back, (const char *)p->chain_req, sizeof(req_back));
+        if (launched) d2h_queue(out_tokens, (const char *)p->chain_out, (size_t)launched * 4);
+    } else if (smp) {
         sample_back.resize((size_t)(SAMPLE_RNG_WORDS + n));
         d2h_queue(sample_back.data(), (const char *)(p->chain_out + SAMPLE_BIAS_WORDS), sample_back.size() * 4);
     } else {
@@ -665,7 +846,20 @@ static int decode_chain(ggml_cgraph *last, int n, int32_t *out_tokens, float *la
         g.stat_sample_chain_steps += (uint64_t)n;
         g.stat_sample_chain_tokens += (uint64_t)n;
     }
-    p->m.n_past += n;
+    int moved = n;  // positions the session moved by
+    if (req) {  // the draws that were made; the steps behind them replayed the last one's evaluation, the rest was never launched
+        chain_req_back(req_back, *req, 1);
+        moved = req_back.n_drawn[0];
+        for (int i = launched; i < n; i++) out_tokens[i] = -1;
+        g.stat_chain_frozen_steps += (uint64_t)(launched - moved);
+        g.stat_chain_steps_cut += (uint64_t)(n - launched);
+        if (req->chains[0]) {
+            g.stat_sample_chain_steps += (uint64_t)launched;
+            g.stat_sample_chain_tokens += (uint64_t)launched;
+        }
+        n = launched;
+    }
+    p->m.n_past += moved;
     p->replays += use_graph ? (uint64_t)n : 0;
     g.stat_plan_tokens += (uint64_t)n;
     g.chain_plan = nullptr;  // the caller's next evaluation re-arms it
@@ -692,7 +886,11 @@ static int decode_greedy_chain(ggml_cgraph *last, int n, int32_t *out_tokens, fl
 // over the column's last 64 tokens, top-k, top-p, temperature and one xorshift64* draw, in the arithmetic of kernels/sampler_math.h,
 // which the host mirror compiles too.  The columns' history rings and the four parameters go up once per call (DecodePlan::scols); the
 // generator states sit in front of the sampled ids in chain_out and come back with them in one copy.
-static int decode_batch_steps(ggml_cgraph *const *graphs, int B, int n_steps, int32_t *out_ids, bool chain, const BatchSample *smp = nullptr) {
+//
+// ggml_hip_decode_batch_requests: the same chain with a request per column (`req`) and the kernels of sample_req.hip as the tail: a
+// column that ends is frozen while the others go on, and the call ends once no column is live (chain_req_run).
+static int decode_batch_steps(ggml_cgraph *const *graphs, int B, int n_steps, int32_t *out_ids, bool chain, const BatchSample *smp = nullptr,
+                              ChainRequests *req = nullptr) {
     ensure_init();
     finish_pending();
     spec_cancel();
@@ -700,6 +898,7 @@ static int decode_batch_steps(ggml_cgraph *const *graphs, int B, int n_steps, in
     res_settle();  // (every column's results go to its graph's own nodes: result set 0)
     if (g.prep) g.prep->gr = nullptr;
     if (!g.opt_plan || !g.opt_plan_batch || (chain && !g.opt_plan_batch_chain) || (smp && !g.opt_plan_batch_sample)) return -1;
+    if (req && req->any_sampled(B) && !g.opt_plan_batch_sample) return -1;
     if (n_steps < 1 || n_steps > BATCH_CHAIN_MAX_STEPS) return -1;
     const uint64_t t0 = now_ns();
     std::vector<LlamaMatch> ms((size_t)B);
@@ -709,7 +908,8 @@ static int decode_batch_steps(ggml_cgraph *const *graphs, int B, int n_steps, in
         if (!match_llama_decode(graphs[c], m)) return -1;
         if (m.kquant && !(g.opt_plan_batch_k && g.opt_plan_k)) return -1;  // a K-quant model: under option plan_batch_k, on the K plan
         if (m.N != 1 || m.prompt || !m.wte || !m.output || !m.embd || !m.logits || !m.embedding) return -1;
-        if (m.n_past + n_steps > m.C || (qt_of(m.wtype) < 0 && !m.f16w && !m.kquant)) return -1;  // (f16 K/V, D, E, F: the matcher's own preconditions)
+        const int room = req ? std::max(1, std::min(n_steps, (int)req->ends[c].budget)) : n_steps;  // (a budget out of range is declined below)
+        if (m.n_past + room > m.C || (qt_of(m.wtype) < 0 && !m.f16w && !m.kquant)) return -1;  // (f16 K/V, D, E, F: the matcher's own preconditions)
         for (const ggml_tensor *t : {m.memory_k, m.memory_v}) {  // a session of another slot keeps its cache to itself (extra_of would abort)
             const DevTensor *e = (const DevTensor *)t->extra;
             if (e && e->magic == 0x48495054 && e->slot != g_cur_slot()) return -1;
@@ -720,6 +920,7 @@ static int decode_batch_steps(ggml_cgraph *const *graphs, int B, int n_steps, in
     // column of the K plan needs the matcher has checked for every graph)
     if (attn_decode_lds(ms[0].C, ms[0].D) > ATTN_DECODE_LDS_MAX || (!ms[0].f16w && !ms[0].kquant && !multi_shape_ok(ms[0], B))) return -1;
     if (smp && !batch_sample_ok(*smp, B, ms[0].V)) return -1;
+    if (req && !chain_requests_ok(*req, B, ms[0].V, 1, n_steps)) return -1;
     ws_reset();
     for (int c = 0; c < B; c++) {
         const LlamaMatch &m = ms[(size_t)c];
@@ -773,7 +974,24 @@ static int decode_batch_steps(ggml_cgraph *const *graphs, int B, int n_steps, in
         }
     };
     step();
-    if (n_steps > 1) {  // the device samples every column and moves the step's parameters on; ids of step i at chain_out[(i - 1) * B ..]
+    int launched = n_steps;  // steps enqueued: all of them, unless every request ended early
+    SampleReqBack req_back;
+    if (req) {  // ids of step i at chain_out[(i - 1) * B ..], -1 where the column sat the step out
+        chain_req_fill(p, *req, B, std::max(1, (n_steps - 1) * B));
+        launched = chain_req_run(p, *req, B, 1, n_steps, req->can_end_early(B, n_steps),
+                                 [&](int i) {
+                                     launch_next_token_requests(p, *req, (const float *)p->logits_out, p->chain_out + (size_t)(i - 1) * B);
+                                     step();
+                                 },
+                                 [](int) { return AV_SHORT; });
+        HIP_CHECK(hipGetLastError());
+        d2h_queue(&req_back, (const char *)p->chain_req, sizeof(req_back));
+        if (launched > 1) d2h_queue(out_ids, (const char *)p->chain_out, (size_t)(launched - 1) * B * 4);
+        p->m.n_past = mb.n_past + launched - 1;
+        for (size_t i = (size_t)(launched - 1) * B; i < (size_t)(n_steps - 1) * B; i++) out_ids[i] = -1;  // rows never launched
+        g.stat_chain_steps_cut += (uint64_t)(n_steps - launched);
+        n_steps = launched;  // (the books below count the device's work)
+    } else if (n_steps > 1) {  // the device samples every column and moves the step's parameters on; ids of step i at chain_out[(i - 1) * B ..]
         const int n_ids = (n_steps - 1) * B;
         int ids_off = 0;
         if (smp) ids_off = sample_cols_fill(p, *smp, B, n_ids);
@@ -810,7 +1028,7 @@ static int decode_batch_steps(ggml_cgraph *const *graphs, int B, int n_steps, in
         g.stat_kplan_tokens += (uint64_t)B * (uint64_t)n_steps;
         g.stat_batch_k_steps += (uint64_t)n_steps;
     }
-    if (smp) {  // (a sampled step is not a greedy one: batch_chain_* count ggml_hip_decode_batch_greedy's alone)
+    if (smp || (req && req->any_sampled(B))) {  // (a sampled step is not a greedy one: batch_chain_* count ggml_hip_decode_batch_greedy's alone)
         g.stat_batch_sample_steps += (uint64_t)(n_steps - 1);
         g.stat_batch_sample_tokens += (uint64_t)(n_steps - 1) * (uint64_t)B;
     } else {
@@ -819,6 +1037,10 @@ static int decode_batch_steps(ggml_cgraph *const *graphs, int B, int n_steps, in
     }
     d2h_finish();
     if (!sample_back.empty()) sample_cols_back(sample_back, *smp, B, out_ids);
+    if (req) {
+        chain_req_back(req_back, *req, B);
+        for (int c = 0; c < B; c++) g.stat_chain_frozen_steps += (uint64_t)(launched - req->n_count[c]);
+    }
     g.ns_match += t1 - t0;
     g.ns_launch += t2 - t1;
     g.ns_wait += now_ns() - t2;

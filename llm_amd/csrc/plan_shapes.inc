@@ -182,6 +182,7 @@ struct DecodePlan {
     int *chain_out = nullptr;   // ggml_hip_decode_greedy_chain / ggml_hip_decode_batch_greedy: sampled ids (device)
     int *chain_ring = nullptr;  // ... of one K-token graph launch (option chain_k), copied into chain_out behind it
     int chain_cap = 0;
+    char *chain_req = nullptr;  // the chains that stop: the call's request table (a SampleReqs, kernels/sample.h), made at the first such call
     VariantGraphs graphs[AV_COUNT];  // per attention variant; a batched step's plan has the one of AV_SHORT
     bool any_captured() const {
         for (const VariantGraphs &v : graphs)
@@ -224,6 +225,7 @@ void destroy_plan(DecodePlan *p) {
     drop_plan_graphs(p);
     if (p->chain_ring) (void)hipFree(p->chain_ring);
     if (p->chain_out) (void)hipFree(p->chain_out);
+    if (p->chain_req) (void)hipFree(p->chain_req);
     if (p->pool) (void)hipFree(p->pool);
     for (int q = 0; q < 2; q++) {
         if (p->slot[q]) (void)hipHostFree(p->slot[q]);

@@ -129,6 +129,14 @@ def _lib():
         L.llm_infer_tokens_sampled_chain_batch_device.restype = C.c_int
         L.llm_infer_tokens_sampled_chain_batch_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                                                   C.c_void_p, C.c_void_p]
+        L.llm_infer_until.restype = C.c_int
+        L.llm_infer_until.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.llm_infer_until_batch.restype = C.c_int
+        L.llm_infer_until_batch.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_void_p]
+        L.llm_until_rule.restype = C.c_int
+        L.llm_until_rule.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_void_p]
         _bound = True
     return L
 
@@ -160,6 +168,43 @@ def sampler_chain(k=40, top_p=0.95, temperature=0.8, penalty=1.30, freq=0.0, pre
         c.bias_id[i] = int(t)
         c.bias[i] = float(b)
     return c
+
+
+class UntilRequest(C.Structure):
+    """llm_until_request: one session's request of a generation that stops — its sampler (NULL: the first maximum), its budget, up to
+    8 stop ids."""
+    _fields_ = [("chain", C.c_void_p), ("max_tokens", C.c_int32), ("n_stop", C.c_int32), ("stop_id", C.c_int32 * 8)]
+
+
+class ChainEnd(C.Structure):
+    """ggml_hip_chain_end: a column's end rule for ggml_hip_decode_chain_requests / ggml_hip_decode_batch_requests."""
+    _fields_ = [("budget", C.c_int32), ("n_stop", C.c_int32), ("stop_id", C.c_int32 * 8)]
+
+
+def chain_end(budget, stop=()):
+    stop = [int(t) for t in stop]
+    if len(stop) > 8:
+        raise ValueError("chain_end: at most 8 stop ids")
+    e = ChainEnd(int(budget), len(stop))
+    for i, t in enumerate(stop):
+        e.stop_id[i] = t
+    return e
+
+
+ENDED_BY = {1: "budget", 2: "stop", 3: "context"}
+
+
+def until_request(max_tokens, stop=(), sampler=None):
+    """(UntilRequest, the SamplerChain it points at or None — keep it alive beside the request).  sampler: sampler_chain's keywords
+    as a dict, or None for the first maximum.  ValueError for more than 8 stop ids."""
+    stop = [int(t) for t in stop]
+    if len(stop) > 8:
+        raise ValueError("until_request: at most 8 stop ids")
+    chain = None if sampler is None else sampler_chain(**sampler)
+    r = UntilRequest(None if chain is None else C.addressof(chain), int(max_tokens), len(stop))
+    for i, t in enumerate(stop):
+        r.stop_id[i] = t
+    return r, chain
 
 
 def _mu(mu, B, chain):
@@ -407,6 +452,36 @@ class Llama:
             raise ValueError("llm_infer_tokens_sampled_batch_device: bad arguments (nothing was evaluated)")
         return bool(rc), out
 
+    def infer_until_batch(self, sessions, requests, rngs, mu=None):
+        """Generation that stops, for several sessions at once (llm_infer_until_batch): requests[i] is a dict for sessions[i] with
+        max_tokens, stop (up to 8 ids, optional) and sampler (sampler_chain's keywords as a dict; None or absent: the first maximum).
+        Every session draws and evaluates until it draws one of its stop ids (still evaluated, as the reference does), has drawn
+        max_tokens, or its context is full; one device chain where the backend can (a session that has ended is frozen while the
+        others go on, and the call ends when none is left), steps of the sessions still going otherwise — the same results.
+        rngs: a uint64 array with one state per session (None when every request is greedy), mu: the Mirostat states (None without
+        Mirostat 2); both advanced in place.  Returns (ids [n, B] with -1 behind a session's last token, counts [B], reasons [B] of
+        "budget" / "stop" / "context", ran_chained).  ValueError with nothing moved on bad arguments."""
+        B = len(sessions)
+        if len(requests) != B:
+            raise ValueError("infer_until_batch: one request per session")
+        ptrs = (C.c_void_p * B)(*[s.ptr for s in sessions])
+        built = [until_request(r["max_tokens"], r.get("stop", ()), r.get("sampler")) for r in requests]
+        reqs = (UntilRequest * B)(*[b[0] for b in built])
+        sampled = [b[1] for b in built if b[1] is not None]
+        if sampled:
+            rngs = self._rngs(rngs, B)
+        if any(c.mirostat != 0 for c in sampled) or mu is not None:
+            if not (isinstance(mu, np.ndarray) and mu.dtype == np.float32 and mu.size == B and mu.flags.c_contiguous):
+                raise ValueError("mu: a contiguous float32 array with one Mirostat state per session (updated in place)")
+        n = max([int(r["max_tokens"]) for r in requests] + [0])
+        out = np.full((max(n, 0), B), -1, np.int32)
+        counts, why = np.zeros(B, np.int32), np.zeros(B, np.int32)
+        rc = _lib().llm_infer_until_batch(self.ptr, ptrs, B, C.addressof(reqs), None if rngs is None else rngs.ctypes.data,
+                                          None if mu is None else mu.ctypes.data, out.ctypes.data, counts.ctypes.data, why.ctypes.data)
+        if rc < 0:
+            raise ValueError("llm_infer_until_batch: bad arguments (nothing was evaluated)")
+        return out, counts, [ENDED_BY[int(w)] for w in why], bool(rc)
+
     def free(self):
         if self.ptr:
             _lib().llm_model_free(self.ptr)
@@ -499,6 +574,26 @@ class Session:
         if rc < 0:
             raise ValueError("llm_infer_tokens_sampled_device: bad arguments (nothing was evaluated)")
         return int(rc), out
+
+    def infer_until(self, max_tokens, rng, stop=(), mu=None, **sampler):
+        """Generation that stops, as InferenceSession::infer (llm_infer_until): draw and evaluate until the token is one of `stop` (up
+        to 8 ids; it is still evaluated), max_tokens were drawn or the context is full.  sampler: sampler_chain's keywords; with
+        rng None (and no keywords) the first maximum is taken.  On the device where the backend can — the chain ends by itself and
+        leaves the session where the stop token's evaluation left it — otherwise the stepped loop with the same rule: same ids,
+        session, generator state and mu.  Returns (ids, count, reason, ran_chained) with reason "budget", "stop" or "context".
+        ValueError with nothing moved on bad arguments."""
+        if rng is None and sampler:
+            raise ValueError("infer_until: a sampler needs rng, a uint64 array of one element")
+        req, chain = until_request(max_tokens, stop, None if rng is None else sampler)
+        if rng is not None:
+            rng = Llama._rngs(rng, 1)
+        out = np.full(max(int(max_tokens), 0), -1, np.int32)
+        count, why = C.c_int32(0), C.c_int32(0)
+        rc = _lib().llm_infer_until(self.model.ptr, self.ptr, C.addressof(req), None if rng is None else rng.ctypes.data,
+                                    None if chain is None else _mu(mu, 1, chain), out.ctypes.data, C.addressof(count), C.addressof(why))
+        if rc < 0:
+            raise ValueError("llm_infer_until: bad arguments (nothing was evaluated)")
+        return out[:count.value], int(count.value), ENDED_BY[int(why.value)], bool(rc)
 
     @staticmethod
     def host_timing(reset=False):
