@@ -714,6 +714,27 @@ GGML_API int ggml_hip_decode_batch_requests(struct ggml_cgraph *const *graphs, i
                                             const ggml_hip_sampler_chain *const *chains, const ggml_hip_chain_end *ends, const int32_t *windows,
                                             const int32_t *window_n, uint64_t *rng, float *mu, int32_t *out_ids, int32_t *n_evaluated,
                                             int32_t *ended_by);
+/* A POOL of n_pool = n_cols .. 64 requests over n_cols = 2 .. 8 columns: ggml_hip_decode_batch_requests where a column whose request
+ * has ended is not frozen for the rest of the call but takes the next waiting request, on the device, between two replays of the
+ * same captured graph.  graphs, chains, ends, windows, window_n, rng, mu: [n_pool], as the sibling's per column; graphs[r] is request
+ * r's staged single-token graph (its first token, its session's caches and position).  Entries 0 .. n_cols - 1 start in columns
+ * 0 .. n_cols - 1, the rest wait in order.  The admission rule (kernels/pool_rule.h): after step s and its tail a column is free when
+ * its request is not live and was already not live before step s ran (its last drawn token, a stop id included, has been evaluated);
+ * a request born ended (a budget of one evaluation) is free after its first step; free columns in ascending index take the waiting
+ * requests in ascending pool index, and the admitted request's first token is evaluated at step s + 1.
+ * Out: col [n_pool], first_step [n_pool]: request r ran in column col[r] from step first_step[r] (-1, 0: it never left the queue and
+ * is untouched); n_evaluated [n_pool], ended_by [n_pool] (0: n_steps ran out with the request still live; its states are where its
+ * last evaluation left them); out_ids [n_steps - 1][n_cols]: request r's k-th id (k = 1 .. n_evaluated - 1) is
+ * out_ids[(first_step + k - 1) * n_cols + col]; *steps_run: the largest first_step + n_evaluated.  Every request that ran finds its
+ * logits and embedding row at its graph's result nodes.  A budget is 1 .. n_steps and is checked, with the request's own position,
+ * against the context.  -1 with nothing executed and no state moved: whatever the sibling declines for any request of the pool
+ * (all checked up front), a session twice in the pool, option plan_batch_pool = 0.  NULL pointers and counts out of range are
+ * refused before any device is touched.  Counters: the sibling's, and pool_calls, pool_admitted, pool_steps. */
+#define GGML_HIP_POOL_MAX 64
+GGML_API int ggml_hip_decode_pool_requests(struct ggml_cgraph *const *graphs, int n_pool, int n_cols, int n_steps,
+                                           const ggml_hip_sampler_chain *const *chains, const ggml_hip_chain_end *ends, const int32_t *windows,
+                                           const int32_t *window_n, uint64_t *rng, float *mu, int32_t *out_ids, int32_t *col,
+                                           int32_t *first_step, int32_t *n_evaluated, int32_t *ended_by, int32_t *steps_run);
 /* Top-k prefilter of a logits row on the device: the k (<= 1024, <= ne0) largest entries of row `row` of
  * the f32 tensor `t` — a node of the caller's most recent ggml_graph_compute, normally the logits — as (value, id) pairs,
  * value descending, lower id first among equal values, followed by the entries of `extra_ids` (n_extra ids, e.g. the
@@ -825,6 +846,15 @@ GGML_API int ggml_hip_debug_next_token_req(const float *logits, int B, int V, co
                                            const ggml_hip_chain_end *ends, int n_past_in, const int32_t *pos_in, const int32_t *tokens_in,
                                            int32_t *hist, int32_t *hist_n, uint64_t *rng, float *mu, int n_draws, int32_t *ids_out,
                                            int32_t *prm_out, int32_t *pos_out, int32_t *n_drawn, int32_t *ended_by);
+/* Test hook: ONE launch of k_pool_admit (kernels/pool_admit.h) on the caller's tables, every table read back in place.  The tables
+ * are the device structures byte for byte: table (PoolTable), reqs (SampleReqs), scols (SampleCols), prm (DecParams), bcols
+ * (BatchCols; its pointers are copied, never followed); sizes [5] their sizes in that order, which must be the library's own
+ * (ggml_hip_debug_pool_admit_sizes fills them in).  logits [n_cols][V], emb [n_cols][E]; slot_logits [n_pool][V] and slot_emb
+ * [n_pool][E] go up and come back.  -1 before any device is touched: NULLs, wrong sizes, n_cols outside 2 .. 8, n_pool outside
+ * n_cols .. 64, V or E < 1, a table whose head disagrees with n_cols / n_pool or whose cursor, owners or classes are out of range. */
+GGML_API void ggml_hip_debug_pool_admit_sizes(int64_t *sizes);
+GGML_API int ggml_hip_debug_pool_admit(void *table, void *reqs, void *scols, void *prm, void *bcols, const int64_t *sizes, int n_cols, int n_pool,
+                                       const float *logits, const float *emb, int V, int E, float *slot_logits, float *slot_emb);
 /* Test hook: w (quantized 2-D weight with a device copy) times N = 2..8 host rows x [N][K] through k_mmq_cols as the
  * multi-token plan launches it; out [N][M].  0, or -1 when that plan would not run this shape on k_mmq_cols. */
 GGML_API int ggml_hip_debug_mul_mat_cols(const struct ggml_tensor *w, const float *x, float *out, int N);

@@ -145,6 +145,7 @@ void invalidate_xf16_if_overwritten_impl(const ggml_tensor *n) {
 #include "plan_decode.inc"
 #include "plan_prompt.inc"
 #include "plan_run.inc"
+#include "plan_pool.inc"
 
 void execute_graph(ggml_cgraph *gr) {
     ensure_init();

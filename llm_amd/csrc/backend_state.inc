@@ -110,6 +110,12 @@ struct Backend {
     int *chain_live_pin = nullptr;
     hipEvent_t chain_live_ev[2] = {nullptr, nullptr};
     uint64_t stat_chain_stopped_columns = 0, stat_chain_frozen_steps = 0, stat_chain_steps_cut = 0;
+    // the request pools (plan_pool.inc): the pinned words the pool's head is copied into behind a group of steps (two sets, as the
+    // live flags above) and their events
+    int opt_plan_batch_pool = 1;
+    PoolHead *pool_pin = nullptr;
+    hipEvent_t pool_ev[2] = {nullptr, nullptr};
+    uint64_t stat_pool_calls = 0, stat_pool_admitted = 0, stat_pool_steps = 0;
     uint64_t stat_flash_attn_nodes = 0;
     // prompt-GEMM launches by kernel (ggml_hip_get_stat("mmq_launches_<name>")): bench.py labels its MFMA roofline with the
     // kernels that actually ran
@@ -209,6 +215,8 @@ static const OptRow g_options[] = {
     // ggml_hip_decode_batch_sampled: the same chain with the top-k / top-p / temperature sampler on the device (0: it answers -1, the
     // caller samples on the host and takes single steps).  It shapes no plan either.
     {"plan_batch_sample", &Backend::opt_plan_batch_sample, OPT_ENV},
+    // ggml_hip_decode_pool_requests: ended columns take waiting requests on the device (0: the entry declines, callers step)
+    {"plan_batch_pool", &Backend::opt_plan_batch_pool, OPT_ENV},
     // ggml_hip_decode_sampled_chain: n tokens of ONE session with that sampler on the device between two replays of its single-token
     // plan (0: it answers -1, the caller samples on the host and evaluates token by token).  It shapes no plan.
     {"plan_sample_chain", &Backend::opt_plan_sample_chain, OPT_ENV},
@@ -341,6 +349,9 @@ static const StatRow g_counters[] = {
     {"chain_stopped_columns", &Backend::stat_chain_stopped_columns},  // columns of the chains that stop that ended on one of their stop ids
     {"chain_frozen_steps", &Backend::stat_chain_frozen_steps},        // column-steps such a chain replayed for a column that had ended (the same token at the same position again)
     {"chain_steps_cut", &Backend::stat_chain_steps_cut},              // steps of such calls that were never launched: every column had ended
+    {"pool_calls", &Backend::stat_pool_calls},                        // calls of ggml_hip_decode_pool_requests that ran
+    {"pool_admitted", &Backend::stat_pool_admitted},                  // requests k_pool_admit moved from the queue into a column
+    {"pool_steps", &Backend::stat_pool_steps},                        // their steps_run: steps up to the last evaluation any request took (what was launched counts in batch_decode_steps)
     {"sample_chain_tokens", &Backend::stat_sample_chain_tokens},  // ... and their tokens (one session a step: the same number, kept beside batch_sample_*)
     {"cols_warm_launches", &Backend::stat_cols_warm_launches},    // chunk-plan norm launches that carried warming workgroups (ColsWarm), counted when enqueued or captured
     {"fused_rearms", &Backend::stat_fused_rearms},                // times the fused forms came back after a clean stretch behind a give-up

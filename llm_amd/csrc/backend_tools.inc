@@ -812,6 +812,96 @@ int ggml_hip_decode_batch_requests(struct ggml_cgraph *const *graphs, int n_grap
     return 0;
 }
 
+// ---- the request pool: more requests than columns (plan_pool.inc) ----
+int ggml_hip_decode_pool_requests(struct ggml_cgraph *const *graphs, int n_pool, int n_cols, int n_steps, const ggml_hip_sampler_chain *const *chains,
+                                  const ggml_hip_chain_end *ends, const int32_t *windows, const int32_t *window_n, uint64_t *rng, float *mu,
+                                  int32_t *out_ids, int32_t *col, int32_t *first_step, int32_t *n_evaluated, int32_t *ended_by, int32_t *steps_run) {
+    if (!graphs || n_cols < 2 || n_cols > BATCH_COLS_MAX || n_pool < n_cols || n_pool > POOL_REQUESTS_MAX) return -1;  // (before any device is touched)
+    if (n_steps < 1 || n_steps > BATCH_CHAIN_MAX_STEPS) return -1;
+    if (!chains || !ends || !col || !first_step || !n_evaluated || !ended_by || !steps_run || (n_steps > 1 && !out_ids)) return -1;
+    for (int i = 0; i < n_pool; i++) {
+        if (!graphs[i] || (chains[i] && (!windows || !window_n || !rng))) return -1;
+        if (ends[i].budget < 1 || ends[i].budget > n_steps || ends[i].n_stop < 0 || ends[i].n_stop > CHAIN_STOP_MAX) return -1;
+    }
+    SlotLock lk;
+    const uint64_t t0 = now_ns();
+    std::vector<uint64_t> r((size_t)n_pool, 0);  // (copies: nothing moves unless the pool ran)
+    std::vector<float> u((size_t)n_pool, 0.0f);
+    std::vector<int32_t> c((size_t)n_pool), f((size_t)n_pool), count((size_t)n_pool), why((size_t)n_pool);
+    for (int i = 0; i < n_pool; i++) {
+        if (rng) r[(size_t)i] = rng[i];
+        if (mu) u[(size_t)i] = mu[i];
+    }
+    int32_t steps = 0;
+    ChainRequests req = {chains, ends, windows, window_n, r.data(), mu ? u.data() : nullptr, count.data(), why.data(), 1, {0, 0, 0, 0}};
+    const PoolResults res = {c.data(), f.data(), count.data(), why.data(), &steps};
+    const int rc = decode_pool_requests(graphs, n_pool, n_cols, n_steps, out_ids, req, res);
+    g.ns_compute += now_ns() - t0;
+    if (rc != 0) return -1;
+    for (int i = 0; i < n_pool; i++) {
+        if (rng && chains[i]) rng[i] = r[(size_t)i];
+        if (mu && chains[i]) mu[i] = u[(size_t)i];
+        col[i] = c[(size_t)i];
+        first_step[i] = f[(size_t)i];
+        n_evaluated[i] = count[(size_t)i];
+        ended_by[i] = why[(size_t)i];
+    }
+    *steps_run = steps;
+    return 0;
+}
+
+// ---- test hook: one launch of k_pool_admit on the caller's tables (tests/test_pool_requests_gpu.py) ----
+void ggml_hip_debug_pool_admit_sizes(int64_t *sizes) {
+    if (!sizes) return;
+    sizes[0] = (int64_t)sizeof(PoolTable);
+    sizes[1] = (int64_t)sizeof(SampleReqs);
+    sizes[2] = (int64_t)sizeof(SampleCols);
+    sizes[3] = (int64_t)sizeof(DecParams);
+    sizes[4] = (int64_t)sizeof(BatchCols);
+}
+int ggml_hip_debug_pool_admit(void *table, void *reqs, void *scols, void *prm, void *bcols, const int64_t *sizes, int n_cols, int n_pool,
+                              const float *logits, const float *emb, int V, int E, float *slot_logits, float *slot_emb) {
+    if (!table || !reqs || !scols || !prm || !bcols || !sizes || !logits || !emb || !slot_logits || !slot_emb) return -1;
+    if (n_cols < 2 || n_cols > BATCH_COLS_MAX || n_pool < n_cols || n_pool > POOL_REQUESTS_MAX || V < 1 || E < 1) return -1;
+    int64_t own[5];
+    ggml_hip_debug_pool_admit_sizes(own);
+    for (int i = 0; i < 5; i++)
+        if (sizes[i] != own[i]) return -1;
+    {  // the kernel clamps and checks every index it reads; the hook refuses what a call would never stage all the same
+        const PoolTable *t = (const PoolTable *)table;
+        if (t->head.n_cols != n_cols || t->head.n_pool != n_pool || t->head.cursor < 0 || t->head.cursor > n_pool) return -1;
+        for (int c = 0; c < n_cols; c++)
+            if (t->head.owner[c] < -1 || t->head.owner[c] >= n_pool) return -1;
+        for (int r = 0; r < n_pool; r++)
+            if (t->in[r].cls < 0 || t->in[r].cls >= SAMPLE_CLASSES) return -1;
+    }
+    SlotLock lk;
+    ensure_init();
+    finish_pending();
+    std::vector<char *> owned;
+    char *dt = debug_buf(sizeof(PoolTable), table, owned);
+    char *dr = debug_buf(sizeof(SampleReqs), reqs, owned);
+    char *ds = debug_buf(sizeof(SampleCols), scols, owned);
+    char *dp = debug_buf(sizeof(DecParams), prm, owned);
+    char *db = debug_buf(sizeof(BatchCols), bcols, owned);
+    const float *dl = (const float *)debug_buf((size_t)n_cols * V * 4, logits, owned);
+    const float *de = (const float *)debug_buf((size_t)n_cols * E * 4, emb, owned);
+    float *sl = (float *)debug_buf((size_t)n_pool * V * 4, slot_logits, owned);
+    float *se = (float *)debug_buf((size_t)n_pool * E * 4, slot_emb, owned);
+    launch_pool_admit(g.stream, dt, dr, ds, dp, db, dl, de, V, E, sl, se);
+    HIP_CHECK(hipGetLastError());
+    d2h_queue(table, dt, sizeof(PoolTable));
+    d2h_queue(reqs, dr, sizeof(SampleReqs));
+    d2h_queue(scols, ds, sizeof(SampleCols));
+    d2h_queue(prm, dp, sizeof(DecParams));
+    d2h_queue(bcols, db, sizeof(BatchCols));
+    d2h_queue(slot_logits, (const char *)sl, (size_t)n_pool * V * 4);
+    d2h_queue(slot_emb, (const char *)se, (size_t)n_pool * E * 4);
+    d2h_finish();
+    for (char *b : owned) HIP_CHECK(hipFree(b));
+    return 0;
+}
+
 // ---- test hook: the kernels between two steps of the chains that stop, alone (tests/test_chain_requests_gpu.py).  debug_next_token's
 // shape with a request per column; a budget here is the number of draws, 0 .. n_draws. ----
 int ggml_hip_debug_next_token_req(const float *logits, int B, int V, const ggml_hip_sampler_chain *const *chains, const ggml_hip_chain_end *ends,

@@ -50,6 +50,7 @@
 #include "kernels/ops.h"
 #include "kernels/decode.h"
 #include "kernels/sample.h"
+#include "kernels/pool_admit.h"
 #include "kernels/decode_big.h"
 #include "kernels/decode_fused.h"
 #include "kernels/decode_big8.h"

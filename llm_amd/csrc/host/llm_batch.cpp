@@ -51,4 +51,10 @@ int llm_infer_until_batch(llm_model *m, llm_session *const *sessions, int B, con
     return llm_infer_until_batch_via(ggml_hip_decode_batch, ggml_hip_decode_batch_requests, m, sessions, B, reqs, rngs, mus, out_ids, n_out,
                                      ended_by);
 }
+// ... and the request pool
+int llm_infer_until_pool(llm_model *m, llm_session *const *sessions, int N, const llm_until_request *reqs, uint64_t *rngs, float *mus, int max_cols,
+                         int32_t *out_ids, int32_t *n_out, int32_t *ended_by) {
+    return llm_infer_until_pool_via(ggml_hip_decode_batch, ggml_hip_decode_chain_requests, ggml_hip_decode_pool_requests, m, sessions, N, reqs, rngs,
+                                    mus, max_cols, out_ids, n_out, ended_by);
+}
 }

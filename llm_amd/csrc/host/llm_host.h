@@ -258,6 +258,29 @@ GGML_API int llm_infer_until_via(llm_chain_requests_entry entry, llm_model *m, l
 GGML_API int llm_infer_until_batch_via(llm_batch_entry step, llm_batch_requests_entry entry, llm_model *m, llm_session *const *sessions, int B,
                                        const llm_until_request *reqs, uint64_t *rngs, float *mus, int32_t *out_ids, int32_t *n_out,
                                        int32_t *ended_by);
+/* ---- the request pool: N >= 1 fed sessions of one model, a request each, over at most max_cols (1 .. 8) columns.  A column whose
+ * request has ended takes the next waiting session — on the device through ggml_hip_decode_pool_requests, which is called again for
+ * whatever it left unfinished or unstarted (more than 64 requests; the step cap); a lone remainder goes through llm_infer_until; the
+ * stepped loop under the same admission rule (kernels/pool_rule.h) runs when the backend has no such entry or declines.  A session
+ * with no room reports LLM_ENDED_BY_CONTEXT and never enters the pool.  out_ids [N][n] with n the largest max_tokens: ROW i holds
+ * session i's ids, then -1; n_out [N], ended_by [N].  Every session ends as llm_infer_until leaves it alone.  Returns 1 if the device
+ * ran requests, 0 if the stepped loop did it all, -1 with nothing moved (generator states included) on bad arguments: those of
+ * llm_infer_until_batch, max_cols outside 1 .. 8. ---- */
+GGML_API int llm_infer_until_pool(llm_model *m, llm_session *const *sessions, int N, const llm_until_request *reqs, uint64_t *rngs, float *mus,
+                                  int max_cols, int32_t *out_ids, int32_t *n_out, int32_t *ended_by);
+typedef int (*llm_pool_requests_entry)(struct ggml_cgraph *const *graphs, int n_pool, int n_cols, int n_steps,
+                                       const ggml_hip_sampler_chain *const *chains, const ggml_hip_chain_end *ends, const int32_t *windows,
+                                       const int32_t *window_n, uint64_t *rng, float *mu, int32_t *out_ids, int32_t *col, int32_t *first_step,
+                                       int32_t *n_evaluated, int32_t *ended_by, int32_t *steps_run);
+GGML_API int llm_infer_until_pool_via(llm_batch_entry step, llm_chain_requests_entry single, llm_pool_requests_entry entry, llm_model *m,
+                                      llm_session *const *sessions, int N, const llm_until_request *reqs, uint64_t *rngs, float *mus, int max_cols,
+                                      int32_t *out_ids, int32_t *n_out, int32_t *ended_by);
+/* The admission rule alone: n requests of evals[i] >= 1 evaluations over n_cols (1 .. 8, <= n) columns; col_out [n], first_step_out [n]
+ * (either may be NULL): request i runs in column col_out[i] from step first_step_out[i].  Returns the number of steps, -1 on bad
+ * arguments.  Needs no device. */
+GGML_API int llm_pool_schedule(const int32_t *evals, int n, int n_cols, int32_t *col_out, int32_t *first_step_out);
+/* test hook: the most steps llm_infer_until_pool asks of one call of the entry (1 .. 4096, the default); returns the previous cap */
+GGML_API int llm_pool_step_cap(int cap);
 /* test hook: the end rule alone, on recorded logits rows [n_rows][V] (row t stands for the logits the t-th draw sees; the window is
  * `window` followed by the ids drawn so far; n_past counts up from n_past0 with every draw against context_size).  Draws with
  * llm_sample_chain (or the first maximum) until the rule ends the run or the rows run out (*ended_by = 0 then).  Needs no device. */

@@ -6,6 +6,7 @@
 #endif
 #include "llm_session.hpp"
 #include "kernels/sampler_math.h"
+#include "kernels/pool_rule.h"
 
 using namespace llm_host;
 
@@ -811,6 +812,210 @@ int llm_until_rule(const float *rows, int n_rows, int V, const llm_until_request
     *n_out = done;
     *ended_by = why;
     return 0;
+}
+
+// ---- the request pool: N sessions' requests over at most max_cols columns (kernels/pool_rule.h) ----
+int llm_pool_schedule(const int32_t *evals, int n, int n_cols, int32_t *col_out, int32_t *first_step_out) {
+    if (!evals || n_cols < 1 || n_cols > POOL_COLS_MAX || n < n_cols) return -1;
+    for (int i = 0; i < n; i++)
+        if (evals[i] < 1) return -1;
+    return pool_schedule(evals, n, n_cols, col_out, first_step_out);
+}
+static int g_pool_step_cap = 4096;  // (BATCH_CHAIN_MAX_STEPS)
+int llm_pool_step_cap(int cap) {
+    const int was = g_pool_step_cap;
+    if (cap >= 1 && cap <= 4096) g_pool_step_cap = cap;
+    return was;
+}
+// `entry` = ggml_hip_decode_pool_requests, `single` = ggml_hip_decode_chain_requests (a lone remainder: llm_infer_until_via), `step` =
+// ggml_hip_decode_batch for the stepped form; any may be NULL.  The host draws every request's first token; the entry gets the first
+// 64 unfinished requests and is called again for whatever it left unfinished or unstarted (more than 64, the step cap); a request
+// whose budget the cap cut comes back "ended by its budget" with budget left, and simply goes on in the next call.  When the entry
+// declines, everything left runs as steps under the same admission rule.
+int llm_infer_until_pool_via(llm_batch_entry step, llm_chain_requests_entry single, llm_pool_requests_entry entry, llm_model *m,
+                             llm_session *const *sessions, int N, const llm_until_request *reqs, uint64_t *rngs, float *mus, int max_cols,
+                             int32_t *out_ids, int32_t *n_out, int32_t *ended_by) {
+    if (!reqs || !out_ids || !n_out || !ended_by || max_cols < 1 || max_cols > POOL_COLS_MAX || !batch_sessions_ok(m, sessions, N, 0)) return -1;
+    const size_t V = m->llama->hyperparameters.n_vocab;
+    int n = 0;
+    std::vector<UntilRule> rules;
+    for (int i = 0; i < N; i++) {
+        if (!until_request_ok(&reqs[i], V, rngs ? &rngs[i] : nullptr, mus ? &mus[i] : nullptr)) return -1;
+        rules.emplace_back(&reqs[i], sessions[i]->s->n_past, m->llama->params.context_size);
+        n = std::max(n, (int)reqs[i].max_tokens);
+    }
+    std::vector<int> done((size_t)N, 0), why((size_t)N, 0);
+    std::fill(out_ids, out_ids + (size_t)n * N, -1);
+    for (int i = 0; i < N; i++) why[(size_t)i] = rules[(size_t)i].budget == 0 ? LLM_ENDED_BY_CONTEXT : 0;  // (it never enters the pool)
+    const auto history = [&](int i) -> const std::vector<llm::TokenId> & { return sessions[i]->s->tokens; };
+    const auto draw = [&](int i, uint64_t *r, float *u) {
+        const llm::InferenceSession &s = *sessions[i]->s;
+        return until_draw(&reqs[i], s.last_logits.data(), V, history(i).data(), history(i).size(), r, u);
+    };
+    const auto finish = [&](int ran) {
+        for (int i = 0; i < N; i++) {
+            n_out[i] = done[(size_t)i];
+            ended_by[i] = why[(size_t)i];
+        }
+        return ran;
+    };
+    int ran = 0;
+    bool moved = false;  // (a draw can fail only before anything moved: the parameters then hold for every later draw)
+    for (;;) {
+        std::vector<int> todo;
+        for (int i = 0; i < N; i++)
+            if (!why[(size_t)i]) todo.push_back(i);
+        if (todo.empty()) return finish(ran);
+        if (todo.size() == 1 || max_cols == 1) {  // a lone remainder (or one column): the one-session form, one after the other
+            for (const int i : todo) {
+                llm_until_request q = reqs[i];
+                q.max_tokens = rules[(size_t)i].budget - done[(size_t)i];
+                std::vector<int32_t> ids((size_t)q.max_tokens);
+                int32_t cnt = 0, w = 0;
+                const int rc = llm_infer_until_via(single, m, sessions[i], &q, rngs ? &rngs[i] : nullptr, mus ? &mus[i] : nullptr, ids.data(), &cnt, &w);
+                if (rc < 0) return -1;
+                moved = true;
+                std::copy(ids.begin(), ids.begin() + cnt, out_ids + (size_t)i * n + done[(size_t)i]);
+                done[(size_t)i] += cnt;
+                why[(size_t)i] = w == LLM_ENDED_BY_STOP ? w : rules[(size_t)i].out_of_budget();
+                ran = ran || rc;
+            }
+            return finish(ran);
+        }
+        if (!entry) break;
+        const int P = (int)std::min(todo.size(), (size_t)POOL_REQUESTS_MAX), B = std::min(max_cols, P);
+        std::vector<uint64_t> r((size_t)P, 0);
+        std::vector<float> u((size_t)P, 0.0f);
+        std::vector<int32_t> first((size_t)P), windows((size_t)P * SAMPLER_WINDOW, 0), window_n((size_t)P), budgets((size_t)P);
+        std::vector<const ggml_hip_sampler_chain *> chains((size_t)P);
+        std::vector<ggml_hip_chain_end> ends((size_t)P);
+        std::vector<llm_session *> who((size_t)P);
+        for (int j = 0; j < P; j++) {
+            const int i = todo[(size_t)j];
+            if (rngs) r[(size_t)j] = rngs[i];
+            if (mus) u[(size_t)j] = mus[i];
+            first[(size_t)j] = draw(i, &r[(size_t)j], mus ? &u[(size_t)j] : nullptr);
+            if (first[(size_t)j] < 0) {
+                if (!moved) return -1;
+                abort();  // (cannot happen: see `moved`)
+            }
+            who[(size_t)j] = sessions[i];
+            chains[(size_t)j] = reqs[i].chain;
+            budgets[(size_t)j] = rules[(size_t)i].is_stop(first[(size_t)j]) ? 1 : rules[(size_t)i].budget - done[(size_t)i];
+        }
+        const int n_steps = std::min(pool_schedule(budgets.data(), P, B, nullptr, nullptr), g_pool_step_cap);
+        for (int j = 0; j < P; j++) {
+            const int i = todo[(size_t)j];
+            ends[(size_t)j] = until_end(&reqs[i], std::min((int)budgets[(size_t)j], n_steps));
+            const std::vector<llm::TokenId> &h = history(i);  // the window the device starts from: the history with this token at its end
+            const size_t keep = std::min(h.size(), (size_t)SAMPLER_WINDOW - 1);
+            int32_t *w = windows.data() + (size_t)j * SAMPLER_WINDOW;
+            for (size_t k = 0; k < keep; k++) w[k] = (int32_t)h[h.size() - keep + k];
+            w[keep] = first[(size_t)j];
+            window_n[(size_t)j] = (int32_t)keep + 1;
+        }
+        Staged st(m, who.data(), first.data(), P);
+        std::vector<int32_t> rest((size_t)(n_steps - 1) * (size_t)B + 1), col((size_t)P), first_step((size_t)P), evaluated((size_t)P), dev_why((size_t)P);
+        int32_t steps_run = 0;
+        if (entry(st.graphs.data(), P, B, n_steps, chains.data(), ends.data(), windows.data(), window_n.data(), r.data(), mus ? u.data() : nullptr,
+                  rest.data(), col.data(), first_step.data(), evaluated.data(), dev_why.data(), &steps_run) != 0)
+            break;
+        ran = 1;
+        moved = true;
+        std::vector<llm::TokenId> ids;
+        for (int j = 0; j < P; j++) {
+            const int i = todo[(size_t)j], c = col[(size_t)j], e = evaluated[(size_t)j], f = first_step[(size_t)j];
+            if (c < 0 || e < 1) continue;  // it never left the queue: untouched, its draw forgotten
+            llm::InferenceSession &s = *sessions[i]->s;
+            st.finish(j);
+            s.tokens.push_back((llm::TokenId)first[(size_t)j]);
+            int32_t *o = out_ids + (size_t)i * n + done[(size_t)i];
+            o[0] = first[(size_t)j];
+            ids.clear();
+            for (int k = 1; k < e; k++) ids.push_back((llm::TokenId)(o[k] = rest[(size_t)(f + k - 1) * B + c]));
+            if (!ids.empty()) s.advance_device_chain(ids.data(), ids.size());
+            done[(size_t)i] += e;
+            if (rngs) rngs[i] = r[(size_t)j];
+            if (mus) mus[i] = u[(size_t)j];
+            const UntilRule &rule = rules[(size_t)i];
+            if (dev_why[(size_t)j] == GGML_HIP_CHAIN_END_STOP || rule.is_stop(first[(size_t)j])) why[(size_t)i] = LLM_ENDED_BY_STOP;
+            else if (done[(size_t)i] >= rule.budget) why[(size_t)i] = rule.out_of_budget();
+        }
+    }
+    // The stepped form under the same admission rule: columns, a tail that draws, an admission, a step of the columns that have a
+    // token to evaluate.  (A session's results do not depend on its column or its step; the rule decides who waits.)
+    std::vector<int> todo;
+    for (int i = 0; i < N; i++)
+        if (!why[(size_t)i]) todo.push_back(i);
+    const int P = (int)todo.size(), B = std::min(max_cols, P);
+    int owner[POOL_COLS_MAX], live[POOL_COLS_MAX], was_live[POOL_COLS_MAX], take[POOL_COLS_MAX], cursor = B;
+    int32_t next[POOL_COLS_MAX];
+    bool has[POOL_COLS_MAX];
+    // a draw for the request in column c: the token waits for the next step; the request stays live while more draws will follow
+    const auto draw_col = [&](int c) -> bool {
+        const int i = owner[c];
+        uint64_t r = rngs ? rngs[i] : 0;
+        float u = mus ? mus[i] : 0.0f;
+        const int32_t id = draw(i, &r, mus ? &u : nullptr);
+        if (id < 0) return false;
+        if (rngs) rngs[i] = r;
+        if (mus) mus[i] = u;
+        next[c] = id;
+        has[c] = true;
+        why[(size_t)i] = rules[(size_t)i].after(done[(size_t)i] + 1, id);
+        live[c] = !why[(size_t)i];
+        return true;
+    };
+    for (int c = 0; c < B; c++) {
+        owner[c] = todo[(size_t)c];
+        has[c] = false;
+    }
+    {  // every first draw before anything moves, on copies
+        std::vector<uint64_t> r0;
+        std::vector<float> u0;
+        if (rngs) r0.assign(rngs, rngs + N);
+        if (mus) u0.assign(mus, mus + N);
+        bool ok = true;
+        for (int c = 0; c < B && ok; c++) ok = draw_col(c);
+        if (!ok) {
+            if (rngs) std::copy(r0.begin(), r0.end(), rngs);
+            if (mus) std::copy(u0.begin(), u0.end(), mus);
+            if (!moved) return -1;
+            abort();
+        }
+    }
+    for (int c = 0; c < B; c++) was_live[c] = live[c];
+    for (;;) {
+        std::vector<llm_session *> going;
+        std::vector<int32_t> ids;
+        std::vector<int> cols;
+        for (int c = 0; c < B; c++)
+            if (has[c]) {
+                going.push_back(sessions[owner[c]]);
+                ids.push_back(next[c]);
+                cols.push_back(c);
+            }
+        if (going.empty()) break;
+        if (llm_evaluate_batch_via(step, m, going.data(), ids.data(), (int)going.size(), nullptr) < 0) return -1;
+        for (size_t j = 0; j < going.size(); j++) {  // the step's commit
+            const int c = cols[j], i = owner[c];
+            going[j]->s->tokens.push_back((llm::TokenId)ids[j]);
+            out_ids[(size_t)i * n + done[(size_t)i]] = ids[j];
+            done[(size_t)i]++;
+            has[c] = false;
+        }
+        for (int c = 0; c < B; c++)  // the tail
+            if (live[c] && !draw_col(c)) abort();
+        cursor = pool_assign(live, was_live, B, cursor, P, take);  // the admission
+        for (int c = 0; c < B; c++) {
+            if (take[c] >= 0) {
+                owner[c] = todo[(size_t)take[c]];
+                if (!draw_col(c)) abort();
+            }
+            was_live[c] = live[c];
+        }
+    }
+    return finish(ran);
 }
 
 }  // extern "C"

@@ -183,6 +183,9 @@ struct DecodePlan {
     int *chain_ring = nullptr;  // ... of one K-token graph launch (option chain_k), copied into chain_out behind it
     int chain_cap = 0;
     char *chain_req = nullptr;  // the chains that stop: the call's request table (a SampleReqs, kernels/sample.h), made at the first such call
+    char *pool_tab = nullptr;   // the request pools (plan_pool.inc): the call's PoolTable (kernels/pool_admit.h) and the retire slots
+    float *pool_rows = nullptr;  // ... logits [n_pool][V], then embedding rows [n_pool][E]; both made at the first such call
+    size_t pool_rows_cap = 0;
     VariantGraphs graphs[AV_COUNT];  // per attention variant; a batched step's plan has the one of AV_SHORT
     bool any_captured() const {
         for (const VariantGraphs &v : graphs)
@@ -226,6 +229,8 @@ void destroy_plan(DecodePlan *p) {
     if (p->chain_ring) (void)hipFree(p->chain_ring);
     if (p->chain_out) (void)hipFree(p->chain_out);
     if (p->chain_req) (void)hipFree(p->chain_req);
+    if (p->pool_tab) (void)hipFree(p->pool_tab);
+    if (p->pool_rows) (void)hipFree(p->pool_rows);
     if (p->pool) (void)hipFree(p->pool);
     for (int q = 0; q < 2; q++) {
         if (p->slot[q]) (void)hipHostFree(p->slot[q]);

@@ -134,6 +134,13 @@ def _lib():
         L.llm_infer_until_batch.restype = C.c_int
         L.llm_infer_until_batch.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.c_void_p, C.c_void_p]
+        L.llm_infer_until_pool.restype = C.c_int
+        L.llm_infer_until_pool.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                           C.c_void_p, C.c_void_p]
+        L.llm_pool_schedule.restype = C.c_int
+        L.llm_pool_schedule.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        L.llm_pool_step_cap.restype = C.c_int
+        L.llm_pool_step_cap.argtypes = [C.c_int]
         L.llm_until_rule.restype = C.c_int
         L.llm_until_rule.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_void_p, C.c_void_p]
@@ -481,6 +488,36 @@ class Llama:
         if rc < 0:
             raise ValueError("llm_infer_until_batch: bad arguments (nothing was evaluated)")
         return out, counts, [ENDED_BY[int(w)] for w in why], bool(rc)
+
+    def infer_until_pool(self, sessions, requests, rngs, mu=None, max_cols=8):
+        """Generation that stops for MORE sessions than a batched step has columns (llm_infer_until_pool): infer_until_batch's
+        requests, one per session, any number of them, over at most max_cols (1 .. 8) columns.  A column whose request has ended
+        takes the next waiting session on the device, between two replays of the same step, so the columns stay busy; every session
+        ends exactly as Session.infer_until leaves it alone.  Without the backend's pool (option plan_batch_pool = 0, a model it
+        declines) the stepped loop runs under the same admission rule — the same results.  rngs, mu: as infer_until_batch, one entry
+        per session.  Returns (ids: a list with one int32 array per request, counts [N], reasons [N], ran_chained).  ValueError with
+        nothing moved on bad arguments."""
+        N = len(sessions)
+        if len(requests) != N or N < 1:
+            raise ValueError("infer_until_pool: one request per session, at least one")
+        ptrs = (C.c_void_p * N)(*[s.ptr for s in sessions])
+        built = [until_request(r["max_tokens"], r.get("stop", ()), r.get("sampler")) for r in requests]
+        reqs = (UntilRequest * N)(*[b[0] for b in built])
+        sampled = [b[1] for b in built if b[1] is not None]
+        if sampled:
+            rngs = self._rngs(rngs, N)
+        if any(c.mirostat != 0 for c in sampled) or mu is not None:
+            if not (isinstance(mu, np.ndarray) and mu.dtype == np.float32 and mu.size == N and mu.flags.c_contiguous):
+                raise ValueError("mu: a contiguous float32 array with one Mirostat state per session (updated in place)")
+        n = max([int(r["max_tokens"]) for r in requests] + [0])
+        out = np.full((N, max(n, 0)), -1, np.int32)
+        counts, why = np.zeros(N, np.int32), np.zeros(N, np.int32)
+        rc = _lib().llm_infer_until_pool(self.ptr, ptrs, N, C.addressof(reqs), None if rngs is None else rngs.ctypes.data,
+                                         None if mu is None else mu.ctypes.data, int(max_cols), out.ctypes.data, counts.ctypes.data,
+                                         why.ctypes.data)
+        if rc < 0:
+            raise ValueError("llm_infer_until_pool: bad arguments (nothing was evaluated)")
+        return [out[i, :counts[i]].copy() for i in range(N)], counts, [ENDED_BY[int(w)] for w in why], bool(rc)
 
     def free(self):
         if self.ptr:
