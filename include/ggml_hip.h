@@ -880,6 +880,22 @@ GGML_API int ggml_hip_debug_mat_vec_f16(const struct ggml_tensor *w0, const stru
                                         int xsrc, int epi, const float *x, const float *xw, float eps, const float *res, float *out,
                                         float *y_out, int n_past, int D, float freq_base, float freq_scale, int64_t C,
                                         uint16_t *mem_k, uint16_t *mem_v, int ncols);
+/* Test hook: ONE launch of an activation quantizer kernel (Q8_0 / Q8_1 planar rows, the int8 and f16 GEMM operands, Q8_K) on host
+ * arrays, with the launch geometry of its call sites.  a [rows][K] f32 (the strided kinds: [rows][stride], stride >= K floats), b the
+ * second input (SiLU kinds: w3 x; P_NORM_QUANT: the second K-split partial, nullable), r the residual (P_NORM_QUANT's ADD form,
+ * nullable), w [K] and eps the norm's; part != 0 (P_SILU_MUL_QUANT): second partials `part` floats on in a and b; zp: the zero point
+ * of QUANT_ACT_I8 (8, 16 or 0).  flags: 1 = d after its f16 round trip (the Q8_0 kind), 2 = with the [block][8] tables dT / sT, 4 = the
+ * Q8_K round trip form of the P_* kinds.  outs: the kind's output buffers in the order listed at the definition
+ * (llm_amd/csrc/backend_tools.inc), each holding its elements and 256 bytes more, which come back as the device holds them (0xFF
+ * before the launch).  0, or -1 for what no call site launches. */
+enum ggml_hip_act_quant_kind {
+    GGML_HIP_AQ_QUANTIZE_ACT = 0, GGML_HIP_AQ_QUANT_ROW, GGML_HIP_AQ_RMSNORM_QUANT, GGML_HIP_AQ_RMSNORM_QUANT_WARM,
+    GGML_HIP_AQ_QUANT_ACT_I8, GGML_HIP_AQ_QUANT_ACT_F16, GGML_HIP_AQ_P_QUANT4, GGML_HIP_AQ_P_SILU_MUL_QUANT, GGML_HIP_AQ_P_NORM_QUANT,
+    GGML_HIP_AQ_QUANT_ACT_F16_K, GGML_HIP_AQ_F32_TO_W16, GGML_HIP_AQ_QUANT_Q8K, GGML_HIP_AQ_K_NORM_QUANT, GGML_HIP_AQ_K_QUANT,
+    GGML_HIP_AQ_K_SILU_MUL_QUANT
+};
+GGML_API int ggml_hip_debug_act_quant(int kind, int flags, int64_t rows, int64_t K, int64_t stride, const float *a, const float *b,
+                                      const float *r, const float *w, float eps, int64_t part, int zp, void *const *outs);
 /* Extension (layer split inside one process): slot `slot` enqueues on slot `with_slot`'s stream (with_slot < 0: on its own again).
  * Only for slots of ONE physical GPU whose work never overlaps — the stages of one split session: a wait on another queue's event
  * costs tens of microseconds per stage boundary on this runtime, the same wait inside one queue nothing.  1 = now shared, 0 = not

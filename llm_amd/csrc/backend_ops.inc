@@ -5,6 +5,88 @@
 // ---------------------------------------------------------------------------------------------------
 bool is_contig_f32(const ggml_tensor *t) { return t->type == GGML_TYPE_F32 && ggml_is_contiguous(t); }
 
+// ---- the activation quantizers' launches: grid, block and dynamic LDS of each kernel, one text for the executor, the plans and
+// the test hook ggml_hip_debug_act_quant (backend_tools.inc).  Accounting (Timed / cx) stays with the callers.
+// 32 lanes per block, rows of nb_row bytes
+void launch_quantize_act(bool f16_d, const char *x, int64_t nb_row, int64_t nb, int64_t N, int8_t *lo, int8_t *hi, float *d, int *s) {
+    with_bool(f16_d, [&](auto F16D) {
+        hipLaunchKernelGGL(k_quantize_act<CT(F16D)>, grid1(nb * N * 32), dim3(256), 0, g.stream, x, nb_row, nb, N, lo, hi, d, s);
+    });
+}
+void launch_quant_act_f16(bool f16_d, const char *x, int64_t nb_row, int64_t nb, int64_t N, _Float16 *out) {
+    with_bool(f16_d, [&](auto F16D) {
+        hipLaunchKernelGGL(k_quant_act_f16<CT(F16D)>, grid1(nb * N * 32), dim3(256), 0, g.stream, x, nb_row, nb, N, out);
+    });
+}
+void launch_quant_act_i8(bool f16_d, const char *x, int64_t nb_row, int64_t nb, int64_t N, float zp, int8_t *q8, float *dq, float *xs) {
+    with_bool(f16_d, [&](auto F16D) {
+        hipLaunchKernelGGL(k_quant_act_i8<CT(F16D)>, grid1(nb * N * 32), dim3(256), 0, g.stream, x, nb_row, nb, N, zp, q8, dq, xs);
+    });
+}
+// one workgroup per (super-block, row)
+void launch_quant_q8k(const char *x, int64_t nb_row, int64_t nsb, int64_t N, int8_t *q8, float *d8, int16_t *bs) {
+    hipLaunchKernelGGL(k_quant_q8k, dim3((unsigned)nsb, (unsigned)N), dim3(256), 0, g.stream, x, nb_row, nsb, q8, d8, bs);
+}
+void launch_quant_act_f16_k(const char *x, int64_t nb_row, int64_t nsb, int64_t N, _Float16 *out) {
+    hipLaunchKernelGGL(k_quant_act_f16_k, dim3((unsigned)nsb, (unsigned)N), dim3(256), 0, g.stream, x, nb_row, nsb, out);
+}
+void launch_f32_to_w16(const float *src, int64_t n /* elements, a multiple of 32 */, _Float16 *out) {
+    hipLaunchKernelGGL(k_f32_to_w16, grid1(n), dim3(256), 0, g.stream, src, n / 32, out);
+}
+// the plans' planar Q8 rows: blockIdx.y = row; dT / sT (nullable): the [block][8] tables, rows 8p .. 8p + 7 in table p
+void launch_quant_row(bool f16_d, const float *x, int64_t nb, int64_t N, int8_t *lo, int8_t *hi, float *d, int *s, float *dT, int *sT) {
+    const dim3 grid(grid1(nb * 32).x, (unsigned)N);
+    with_bool(f16_d, [&](auto F16D) { hipLaunchKernelGGL(k_quant_row<CT(F16D)>, grid, dim3(256), 0, g.stream, x, (int)nb, lo, hi, d, s, dT, sT); });
+}
+// one 1024-thread workgroup per row; cw (nullable): the launch on every CU whose other workgroups warm the next launch's rows
+void launch_rmsnorm_quant(bool f16_d, const float *x, const float *w, float eps, int64_t E, int64_t N, float *y, int8_t *lo, int8_t *hi,
+                          float *d, int *s, float *dT, int *sT, const ColsWarm *cw) {
+    with_bool(f16_d, [&](auto F16D) {
+        if (cw)
+            hipLaunchKernelGGL(k_rmsnorm_quant_warm<CT(F16D)>, dim3((unsigned)g.num_cus), dim3(1024), (size_t)E * 4, g.stream, x, w, eps, (int)E, y,
+                               lo, hi, d, s, dT, sT, (int)N, *cw);
+        else
+            hipLaunchKernelGGL(k_rmsnorm_quant<CT(F16D)>, dim3((unsigned)N), dim3(1024), (size_t)E * 4, g.stream, x, w, eps, (int)E, y, lo, hi, d, s,
+                               dT, sT);
+    });
+}
+// the K plan's helpers: Q8_K rows [N][nsb * 256]
+void launch_k_norm_quant(const float *x, const float *w, float eps, int64_t E, int64_t N, float *y, int8_t *q8, float *d8, int16_t *bs) {
+    hipLaunchKernelGGL(k_k_norm_quant, dim3((unsigned)(E / 256), (unsigned)N), dim3(256), 0, g.stream, x, w, eps, (int)E, y, q8, d8, bs);
+}
+void launch_k_quant(const float *x, int64_t nsb, int64_t N, int8_t *q8, float *d8, int16_t *bs) {
+    hipLaunchKernelGGL(k_k_quant, dim3((unsigned)nsb, (unsigned)N), dim3(256), 0, g.stream, x, q8, d8, bs);
+}
+void launch_k_silu_mul_quant(const float *g1, const float *g3, int64_t nsb, int64_t N, int8_t *q8, float *d8, int16_t *bs) {
+    hipLaunchKernelGGL(k_k_silu_mul_quant, dim3((unsigned)nsb, (unsigned)N), dim3(256), 0, g.stream, g1, g3, q8, d8, bs);
+}
+// the prompt plan's f16 operands; kq: the Q8_K round trip (a K-quant weight's GEMM), else Q8_0 / Q8_1 by f16_d
+void launch_p_norm_quant(bool kq, bool f16_d, const float *x, const float *x2, const float *r, float *xsum, const float *w, float eps,
+                         int64_t E, int64_t N, float *y_f32, _Float16 *out) {
+    with_bool(r != nullptr, [&](auto RES) {
+        if (kq)
+            hipLaunchKernelGGL((k_p_norm_quant<false, CT(RES), true>), dim3((unsigned)N), dim3(256), (size_t)E * 4, g.stream, x, x2, r, xsum, w, eps, (int)E, y_f32, out);
+        else
+            with_bool(f16_d, [&](auto F16D) {
+                hipLaunchKernelGGL((k_p_norm_quant<CT(F16D), CT(RES)>), dim3((unsigned)N), dim3(256), (size_t)E * 4, g.stream, x, x2, r, xsum, w, eps, (int)E, y_f32, out);
+            });
+    });
+}
+void launch_p_quant4(bool kq, bool f16_d, const f32x4 *a, int64_t n4, _Float16 *out) {
+    const dim3 grid((unsigned)((n4 + 255) / 256));
+    if (kq)
+        hipLaunchKernelGGL((k_p_quant4<false, true>), grid, dim3(256), 0, g.stream, a, n4, out);
+    else
+        with_bool(f16_d, [&](auto F16D) { hipLaunchKernelGGL(k_p_quant4<CT(F16D)>, grid, dim3(256), 0, g.stream, a, n4, out); });
+}
+void launch_p_silu_mul_quant(bool kq, bool f16_d, const f32x4 *a, const f32x4 *b, int64_t n4, int64_t part4, _Float16 *out) {
+    const dim3 grid((unsigned)((n4 + 255) / 256));
+    if (kq)
+        hipLaunchKernelGGL((k_p_silu_mul_quant<false, true>), grid, dim3(256), 0, g.stream, a, b, n4, part4, out);
+    else
+        with_bool(f16_d, [&](auto F16D) { hipLaunchKernelGGL(k_p_silu_mul_quant<CT(F16D)>, grid, dim3(256), 0, g.stream, a, b, n4, part4, out); });
+}
+
 QAct quantize_activation(const ggml_tensor *src1, bool f16_d) {
     BK_ASSERT(src1->type == GGML_TYPE_F32 && src1->nb[0] == 4 && src1->ne[2] == 1 && src1->ne[3] == 1);
     const int64_t K = src1->ne[0], N = src1->ne[1], nb = K / 32;
@@ -15,11 +97,7 @@ QAct quantize_activation(const ggml_tensor *src1, bool f16_d) {
     char *lo = blk, *hi = blk + nblk * 16, *d = blk + nblk * 32, *s = blk + nblk * 36;
     const char *x = dev_ptr(src1);
     Timed tm(GGML_HIP_KCLASS_OTHER, (double)(K * N * 4 + nblk * 40));
-    const int64_t threads = (int64_t)nblk * 32;
-    with_bool(f16_d, [&](auto F16D) {
-        hipLaunchKernelGGL(k_quantize_act<CT(F16D)>, grid1(threads), dim3(256), 0, g.stream, x, (int64_t)src1->nb[1], nb, N,
-                           (int8_t *)lo, (int8_t *)hi, (float *)d, (int *)s);
-    });
+    launch_quantize_act(f16_d, x, (int64_t)src1->nb[1], nb, N, (int8_t *)lo, (int8_t *)hi, (float *)d, (int *)s);
     HIP_CHECK(hipGetLastError());
     g_qact.valid = true;
     g_qact.src_data = src1->data;
@@ -63,11 +141,7 @@ const _Float16 *quantize_activation_f16(const ggml_tensor *src1, bool f16_d) {
         return g_xf16.x;
     _Float16 *out = (_Float16 *)ws_alloc((size_t)N * K * 2);
     Timed tm(GGML_HIP_KCLASS_OTHER, (double)(K * N * 6));
-    const int64_t threads = nb * N * 32;
-    with_bool(f16_d, [&](auto F16D) {
-        hipLaunchKernelGGL(k_quant_act_f16<CT(F16D)>, grid1(threads), dim3(256), 0, g.stream, dev_ptr(src1),
-                           (int64_t)src1->nb[1], nb, N, out);
-    });
+    launch_quant_act_f16(f16_d, dev_ptr(src1), (int64_t)src1->nb[1], nb, N, out);
     HIP_CHECK(hipGetLastError());
     g_xf16.valid = true;
     g_xf16.src_data = src1->data;
@@ -101,11 +175,7 @@ void quantize_activation_i8(const ggml_tensor *src1, int qt, const int8_t **q8, 
         float *od = (float *)ws_alloc((size_t)N * nb * 4);
         float *os = (float *)ws_alloc((size_t)N * nb * 4);
         Timed tm(GGML_HIP_KCLASS_OTHER, (double)(K * N * 5));
-        const int64_t threads = nb * N * 32;
-        with_bool(f16_d, [&](auto F16D) {
-            hipLaunchKernelGGL(k_quant_act_i8<CT(F16D)>, grid1(threads), dim3(256), 0, g.stream, dev_ptr(src1), (int64_t)src1->nb[1], nb,
-                               N, zp, o8, od, os);
-        });
+        launch_quant_act_i8(f16_d, dev_ptr(src1), (int64_t)src1->nb[1], nb, N, zp, o8, od, os);
         HIP_CHECK(hipGetLastError());
         g_xi8.valid = true;
         g_xi8.src_data = src1->data;
@@ -147,8 +217,7 @@ KAct quantize_activation_k(const ggml_tensor *src1) {
         float *d8 = (float *)ws_alloc((size_t)N * nsb * 4);
         int16_t *bs = (int16_t *)ws_alloc((size_t)N * nsb * 32);
         Timed tm(GGML_HIP_KCLASS_OTHER, (double)(K * N * 5));
-        hipLaunchKernelGGL(k_quant_q8k, dim3((unsigned)nsb, (unsigned)N), dim3(256), 0, g.stream, dev_ptr(src1),
-                           (int64_t)src1->nb[1], nsb, q8, d8, bs);
+        launch_quant_q8k(dev_ptr(src1), (int64_t)src1->nb[1], nsb, N, q8, d8, bs);
         HIP_CHECK(hipGetLastError());
         g_xk.valid = true;
         g_xk.src_data = src1->data;
@@ -304,7 +373,7 @@ bool ensure_w16_k(DevTensor *e) {
     for (int64_t r0 = 0; r0 < M; r0 += chunk) {
         const int64_t n = std::min(chunk, M - r0);
         dequant_k_rows(kw_rows(e->kw, r0, n), nullptr, n, tmp, K);
-        hipLaunchKernelGGL(k_f32_to_w16, grid1(n * K), dim3(256), 0, g.stream, tmp, n * K / 32, (_Float16 *)w16 + r0 * K);
+        launch_f32_to_w16(tmp, n * K, (_Float16 *)w16 + r0 * K);
         HIP_CHECK(hipGetLastError());
     }
     HIP_CHECK(hipStreamSynchronize(g.stream));
@@ -505,8 +574,7 @@ bool mul_mat_k_gemm(const ggml_tensor *src0, const ggml_tensor *src1, ggml_tenso
     _Float16 *x16 = (_Float16 *)ws_alloc((size_t)N * K * 2);
     {
         Timed tm(GGML_HIP_KCLASS_OTHER, (double)(K * N * 6));
-        hipLaunchKernelGGL(k_quant_act_f16_k, dim3((unsigned)nsb, (unsigned)N), dim3(256), 0, g.stream, dev_ptr(src1),
-                           (int64_t)src1->nb[1], nsb, x16);
+        launch_quant_act_f16_k(dev_ptr(src1), (int64_t)src1->nb[1], nsb, N, x16);
         HIP_CHECK(hipGetLastError());
     }
     QWeight w;

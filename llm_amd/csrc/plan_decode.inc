@@ -230,10 +230,7 @@ static void plan_launch_all(DecodePlan *p, int av, LaunchCtx cx) {
     // rms_norm + weight + Q8 of the E-wide residual row (separate launch)
     auto rmsq = [&](const float *x, const float *w, float *y) {
         cx.other((double)E * 9.25, [&] {
-            with_bool(f16d, [&](auto F16D) {
-                hipLaunchKernelGGL(k_rmsnorm_quant<CT(F16D)>, dim3(1), dim3(1024), (size_t)E * 4, g.stream, x, w, m.eps, (int)E, y,
-                                   p->e_lo, p->e_hi, p->e_d, p->e_s);
-            });
+            launch_rmsnorm_quant(f16d, x, w, m.eps, E, 1, y, p->e_lo, p->e_hi, p->e_d, p->e_s, nullptr, nullptr, nullptr);
         });
     };
     // one mat-vec launch: k_mmvq_big with the staging XSRC, or (option big = 0) k_mmvq_dec on nwg workgroups — behind the separate
@@ -389,10 +386,7 @@ static void plan_launch_all(DecodePlan *p, int av, LaunchCtx cx) {
         // ---- re-quantize the gate, w2 + residual → next layer's input ----
         if (!fuse_x)
             cx.other((double)F * 5.25, [&] {
-                with_bool(f16d, [&](auto F16D) {
-                    hipLaunchKernelGGL(k_quant_row<CT(F16D)>, grid1(nbF * 32), dim3(256), 0, g.stream, (const float *)p->gate,
-                                       (int)nbF, p->f_lo, p->f_hi, p->f_d, p->f_s);
-                });
+                launch_quant_row(f16d, (const float *)p->gate, nbF, 1, p->f_lo, p->f_hi, p->f_d, p->f_s, nullptr, nullptr);
             });
         {
             DecMmvqArgs a;
@@ -563,7 +557,7 @@ static void plan_launch_k(DecodePlan *p, int av, LaunchCtx cx, bool batch = fals
     auto norm_quant = [&](const float *x, const float *w, float *y) {
         if (kbig) return;  // staged by the mat-vec that follows
         cx.other((double)N * E * 9.3, [&] {
-            hipLaunchKernelGGL(k_k_norm_quant, dim3((unsigned)nsbE, (unsigned)N), dim3(256), 0, g.stream, x, w, m.eps, (int)E, y, p->k_q8, p->k_d8, p->k_bs);
+            launch_k_norm_quant(x, w, m.eps, E, N, y, p->k_q8, p->k_d8, p->k_bs);
         });
     };
     plan_open_rows(p, cx, batch, 4.6, [&] { dequant_k_rows(p->k_wte, (const int *)p->prm->tokens, N, p->xa, E); });
@@ -611,7 +605,7 @@ static void plan_launch_k(DecodePlan *p, int av, LaunchCtx cx, bool batch = fals
             });
         }
         if (!kfused) plan_attn_f32(p, cx, il, long_ctx, batch);
-        if (!kbig) cx.other((double)N * E * 5.3, [&] { hipLaunchKernelGGL(k_k_quant, dim3((unsigned)nsbE, (unsigned)N), dim3(256), 0, g.stream, (const float *)p->k_att, p->k_q8, p->k_d8, p->k_bs); });
+        if (!kbig) cx.other((double)N * E * 5.3, [&] { launch_k_quant((const float *)p->k_att, nsbE, N, p->k_q8, p->k_d8, p->k_bs); });
         mmvq(1, {&w.wo}, {p->xb}, p->xa, RowSrc{KX_F32, p->k_att, nullptr, 0.0f, nullptr});
         norm_quant(p->xb, nw.ffn_norm, nullptr);
         // w1 and w3 of one type: one launch whose epilogue is silu(w1 x) * (w3 x) (the product lands in p->gate, w2 stages it as a
@@ -627,8 +621,7 @@ static void plan_launch_k(DecodePlan *p, int av, LaunchCtx cx, bool batch = fals
             mmvq(2, {&w.w1, &w.w3}, {p->gate, p->k_g3}, nullptr, ffn_normed);
         }
         if (!kbig) cx.other((double)N * F * 9.3, [&] {
-            hipLaunchKernelGGL(k_k_silu_mul_quant, dim3((unsigned)nsbF, (unsigned)N), dim3(256), 0, g.stream, (const float *)p->gate, (const float *)p->k_g3,
-                               p->k_q8, p->k_d8, p->k_bs);
+            launch_k_silu_mul_quant((const float *)p->gate, (const float *)p->k_g3, nsbF, N, p->k_q8, p->k_d8, p->k_bs);
         });
         mmvq(3, {&w.w2}, {p->xa}, p->xb, kgate ? RowSrc{KX_F32, p->gate, nullptr, 0.0f, nullptr} : RowSrc{KX_SILU_MUL, p->gate, p->k_g3, 0.0f, nullptr});
     }

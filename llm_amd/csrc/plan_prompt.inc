@@ -91,15 +91,8 @@ static void plan_launch_chunk(DecodePlan *p, const bool batch) {
     };
     auto rmsq = [&](const float *x, const float *w, float *y, const ColsWarm &cw) {
         cx.other((double)N * E * 9.25, [&] {
-            with_bool(f16d, [&](auto F16D) {
-                if (cw.n > 0) {  // N norm workgroups + one warming workgroup on every other CU
-                    g.stat_cols_warm_launches++;
-                    hipLaunchKernelGGL(k_rmsnorm_quant_warm<CT(F16D)>, dim3((unsigned)g.num_cus), dim3(1024), (size_t)E * 4, g.stream, x, w, m.eps, (int)E, y,
-                                       p->e_lo, p->e_hi, p->e_d, p->e_s, p->e_dT, p->e_sT, N, cw);
-                } else
-                    hipLaunchKernelGGL(k_rmsnorm_quant<CT(F16D)>, dim3(N), dim3(1024), (size_t)E * 4, g.stream, x, w, m.eps, (int)E, y,
-                                       p->e_lo, p->e_hi, p->e_d, p->e_s, p->e_dT, p->e_sT);
-            });
+            if (cw.n > 0) g.stat_cols_warm_launches++;  // N norm workgroups + one warming workgroup on every other CU
+            launch_rmsnorm_quant(f16d, x, w, m.eps, E, N, y, p->e_lo, p->e_hi, p->e_d, p->e_s, p->e_dT, p->e_sT, cw.n > 0 ? &cw : nullptr);
         });
     };
     const double bb = (double)blk_bytes(qt);
@@ -206,11 +199,7 @@ static void plan_launch_chunk(DecodePlan *p, const bool batch) {
             block(2, std::integral_constant<int, EPI_GATE>{}, cols.gate, a, (int)(2 * F), p->e_dT, p->e_sT);
         }
         cx.other((double)N * F * 5.25, [&] {
-            const dim3 grid((unsigned)((nbF * 32 + 255) / 256), (unsigned)N);
-            with_bool(f16d, [&](auto F16D) {
-                hipLaunchKernelGGL(k_quant_row<CT(F16D)>, grid, dim3(256), 0, g.stream, (const float *)p->gate, (int)nbF, p->f_lo,
-                                   p->f_hi, p->f_d, p->f_s, p->f_dT, p->f_sT);
-            });
+            launch_quant_row(f16d, (const float *)p->gate, nbF, N, p->f_lo, p->f_hi, p->f_d, p->f_s, p->f_dT, p->f_sT);
         });
         {
             Big8Args a;
@@ -375,14 +364,7 @@ static void plan_launch_prompt(DecodePlan *p) {
     auto norm_quant = [&](const float *x, const float *x2, const float *r, float *xsum, const float *w, float *y_f32) {
         Timed tm(GGML_HIP_KCLASS_OTHER, (double)N * E * (r ? 18.0 : 6.0));
         if (E > 8192) die("prompt plan: rows of %lld elements (k_p_norm_quant holds a row of up to 8192 in registers)", (long long)E);
-        with_bool(r != nullptr, [&](auto RES) {
-            if (kq)
-                hipLaunchKernelGGL((k_p_norm_quant<false, CT(RES), true>), dim3(N), dim3(256), (size_t)E * 4, g.stream, x, x2, r, xsum, w, m.eps, (int)E, y_f32, p->p_x16);
-            else
-                with_bool(f16d, [&](auto F16D) {
-                    hipLaunchKernelGGL((k_p_norm_quant<CT(F16D), CT(RES)>), dim3(N), dim3(256), (size_t)E * 4, g.stream, x, x2, r, xsum, w, m.eps, (int)E, y_f32, p->p_x16);
-                });
-        });
+        launch_p_norm_quant(kq, f16d, x, x2, r, xsum, w, m.eps, E, N, y_f32, p->p_x16);
         HIP_CHECK(hipGetLastError());
     };
     // A GEMM whose tile count leaves CUs idle splits K in two (mmq_auto_splits, as in the node-by-node executor).  There
@@ -471,12 +453,7 @@ static void plan_launch_prompt(DecodePlan *p) {
         if (!fused_attn || kq) {
             Timed tm(GGML_HIP_KCLASS_OTHER, (double)N * E * 6.0);
             const int64_t n4 = (int64_t)N * E / 4;
-            if (kq)
-                hipLaunchKernelGGL((k_p_quant4<false, true>), dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, g.stream, (const f32x4 *)p->p_mg, n4, p->p_x16);
-            else
-                with_bool(f16d, [&](auto F16D) {
-                    hipLaunchKernelGGL(k_p_quant4<CT(F16D)>, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, g.stream, (const f32x4 *)p->p_mg, n4, p->p_x16);
-                });
+            launch_p_quant4(kq, f16d, (const f32x4 *)p->p_mg, n4, p->p_x16);
             HIP_CHECK(hipGetLastError());
         }
         const int sp_wo = gemm(w.wo, p->p_te, nbE, te_stride);
@@ -489,12 +466,7 @@ static void plan_launch_prompt(DecodePlan *p) {
         {
             const int64_t n4 = (int64_t)N * F / 4;
             Timed tm(GGML_HIP_KCLASS_OTHER, (double)n4 * 40.0);
-            if (kq)
-                hipLaunchKernelGGL((k_p_silu_mul_quant<false, true>), dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, g.stream, (const f32x4 *)p->p_g1, (const f32x4 *)p->p_g3, n4, sp_13 > 1 ? g13_stride / 4 : 0, p->p_x16);
-            else
-                with_bool(f16d, [&](auto F16D) {
-                    hipLaunchKernelGGL(k_p_silu_mul_quant<CT(F16D)>, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, g.stream, (const f32x4 *)p->p_g1, (const f32x4 *)p->p_g3, n4, sp_13 > 1 ? g13_stride / 4 : 0, p->p_x16);
-                });
+            launch_p_silu_mul_quant(kq, f16d, (const f32x4 *)p->p_g1, (const f32x4 *)p->p_g3, n4, sp_13 > 1 ? g13_stride / 4 : 0, p->p_x16);
             HIP_CHECK(hipGetLastError());
         }
         sp_w2 = gemm(w.w2, p->p_te, nbF, te_stride);

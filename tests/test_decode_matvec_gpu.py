@@ -12,6 +12,8 @@ bound is small against an f16 step and the edges are few."""
 import numpy as np
 import pytest
 
+import act_quant_ref as R
+
 pytestmark = pytest.mark.gpu
 
 GUARD = 256  # bytes behind every output buffer of the hooks (include/ggml_hip.h)
@@ -450,3 +452,176 @@ def test_kbig_hook_refuses_what_the_plan_cannot_stage(G, O, kt):
     assert _run(G, O, True, [kt], [64], 16384 + 256, KF32, KROW, one(16640))[0] == -1  # nsb 65
     assert _run(G, O, True, [kt], [64], 22016, KF32, KROW, one(22016))[0] == -1  # 65B w2: the K plan's helper-launch form
     assert _run(G, O, True, [kt], [64], 8192 + 256, KNORM, KROW, one(8448), one(8448))[0] == -1  # the norm: 8192 at most
+
+
+# ---- the quantizers inside the launches: selector weights make every output row reveal one quant (or one pair of bsums) exactly.
+# The bound above lets one flipped quant pass from K of about 1200 on; here the weights are one-hot, the oracle's product on the
+# same selector is the expected value and the comparison is ==, on rounding ties, two-signed extremes and the clamp
+# (tests/act_quant_ref.py), under both branches of the Q8 quantizer for k_mmvq_big.
+def _selector_q8_0(K):
+    """Q8_0 [K][K]: row m has d = 1 everywhere and q = 1 at column m only: out[m] = q_x[m] * d_x."""
+    nb = K // 32
+    raw = np.zeros((K, nb, 34), np.uint8)
+    raw[:, :, :2] = np.array([1.0], np.float16).view(np.uint8)
+    m = np.arange(K)
+    raw[m, m // 32, 2 + m % 32] = 1
+    return raw.reshape(-1)
+
+
+def _selector_q6_k(K):
+    """Q6_K [K][K]: row m has d = 1, scale 1 for the 16 columns around m only, code 33 at column m and 32 elsewhere: the weight is
+    1 at column m, 0 elsewhere, and out[m] = q8[m] * d8."""
+    nsb = K // 256
+    raw = np.zeros((K, nsb, 210), np.uint8)
+    raw[:, :, 128:192] = 0xAA  # qh: the two high bits of every code = 2 (code 32)
+    raw[:, :, 208:210] = np.array([1.0], np.float16).view(np.uint8)
+    for m in range(K):
+        sb, c = divmod(m, 256)
+        n, r = divmod(c, 128)
+        quarter, l = divmod(r, 32)
+        raw[m, sb, 64 * n + l + (32 if quarter & 1 else 0)] = 1 if quarter < 2 else 0x10  # the low four bits of the code at column m
+        raw[m, sb, 192 + c // 16] = 1
+    return raw.reshape(-1)
+
+
+def _selector_q4_k(K):
+    """Q4_K [K / 32][K]: d = 0, dmin = 1, row m has min 1 for sub-block m (32 columns) only: the weight is -1 there, 0 elsewhere, and
+    out[m] = -d8 * (bsums[2 j] + bsums[2 j + 1]) of that sub-block."""
+    nsb = K // 256
+    M = K // 32
+    raw = np.zeros((M, nsb, 144), np.uint8)
+    raw[:, :, 2:4] = np.array([1.0], np.float16).view(np.uint8)
+    for m in range(M):
+        sb, j = divmod(m, 8)
+        raw[m, sb, 4 + j + 4] = 1 if j < 4 else 0x10  # get_scale_min_k4: the six-bit min of sub-block j
+    return raw.reshape(-1)
+
+
+def _selector_launch(G, k_hook, wptr, xsrc, epi, K, M, x, xw=None, res=None, y=False):
+    ob, out = _buf(M)
+    yb, yv = _buf(K) if y else (None, None)
+    x = np.ascontiguousarray(x, np.float32)
+    xw = None if xw is None else np.ascontiguousarray(xw, np.float32)
+    res = None if res is None else np.ascontiguousarray(res, np.float32)
+    f = G.lib().ggml_hip_debug_mat_vec_kbig if k_hook else G.lib().ggml_hip_debug_mat_vec_big
+    rc = f(wptr, None, None, xsrc, epi, _ptr(x), _ptr(xw), EPS, _ptr(res), _ptr(ob), _ptr(yb), 0, 0, 10000.0, 1.0, 0, None, None)
+    assert rc == 0
+    assert not np.any(np.isnan(out))
+    _guard_ok(ob, M * 4, "out")
+    if y:
+        assert not np.any(np.isnan(yv))
+        _guard_ok(yb, K * 4, "y_out")
+    return out.copy(), None if yv is None else yv.copy()
+
+
+def _rows_of(pool, fam, names, per):
+    """The blocks of the named families, as rows of `per` blocks (the last one filled up from the start)."""
+    sel = pool[np.isin(np.array(fam), names)]
+    return list(R.launches(sel, 1, per))
+
+
+def _norm_rows3(K, seed):
+    return R.norm_rows_input(3, K, seed), np.random.default_rng([seed, K]).uniform(0.5, 1.5, K).astype(np.float32)
+
+
+def test_selector_weights_are_one_hot(O):
+    for K in (32, 288):
+        assert np.array_equal(O.dequantize(8, _selector_q8_0(K), K * K).reshape(K, K), np.eye(K, dtype=np.float32))
+    assert np.array_equal(O.dequantize(14, _selector_q6_k(768), 768 * 768).reshape(768, 768), np.eye(768, dtype=np.float32))
+    w = O.dequantize(12, _selector_q4_k(768), 24 * 768).reshape(24, 768)
+    assert np.array_equal(w, -np.repeat(np.eye(24, dtype=np.float32), 32, axis=1))
+
+
+@pytest.mark.parametrize("K", [32, 288])
+def test_big_matvec_staging_quantizer_reveals_every_quant(G, O, K):
+    """k_mmvq_big's staging quantizer (XSRC_F32 + EPI_ADD with res = 0) through a Q8_0 selector: K = 32 is the smallest the hook
+    takes, 288 puts nine blocks in a row (which block meets which weight).  Every family of the Q8 set, act_quant 0 and 1: each
+    result == the oracle's product of its branch, and the two differ exactly where the oracle's do."""
+    pool, fam = R.q8_pool()
+    rows = list(R.launches(pool, 1, K // 32)) if K > 32 else _rows_of(pool, fam, ("tie", "edge", "zero", "negzero", "single", "d_tie"), 1)
+    raw = _selector_q8_0(K)
+    zero = np.zeros(K, np.float32)
+    got, want = {}, {}
+    with G.Context(raw.nbytes + (1 << 20)) as ctx:
+        w = ctx.tensor_from(raw, 8, (K, K)).set_name("selector")
+        w.transfer_to_gpu()
+        try:
+            for aq in (0, 1):
+                G.set_option("act_quant", aq)
+                got[aq] = [_selector_launch(G, False, w.ptr, XF32, EADD, K, K, x[0], res=zero)[0] for x in rows]
+                want[aq] = [O.mul_mat(8, raw, K, K, x, mode=O.ref_mode() if aq == 0 else O.MODE_SCALAR)[0] for x in rows]
+        finally:
+            G.set_option("act_quant", 0)
+    ndiff = 0
+    for aq in (0, 1):
+        for i, (g, e) in enumerate(zip(got[aq], want[aq])):
+            bad = np.flatnonzero(g != e)
+            assert bad.size == 0, f"K {K} act_quant {aq} row {i}: {bad.size} outputs differ, first {bad[:8]}: got {g[bad[:4]]} want {e[bad[:4]]}"
+    for g0, g1, e0, e1 in zip(got[0], got[1], want[0], want[1]):
+        assert np.array_equal(g0 != g1, e0 != e1)
+        ndiff += int(np.count_nonzero(g0 != g1))
+    print(f"K {K}: {len(rows)} rows, the branches differ on {ndiff} outputs")
+    assert ndiff > 0
+    if K > 32:  # the whole set once: the count of tests/test_act_quant_ref.py
+        assert ndiff == R.branch_diff_count(pool)
+
+
+def test_big_matvec_norm_staging_reveals_every_quant(G, O):
+    """XSRC_NORM (+ EPI_STORE): ties cannot be placed behind the launch's own norm; the revealed quants are compared exactly with
+    the oracle's quantization of the tapped y_out, on rows of three magnitudes, act_quant 0 and 1."""
+    K = 288
+    raw = _selector_q8_0(K)
+    xs, nw = _norm_rows3(K, 21)
+    with G.Context(raw.nbytes + (1 << 20)) as ctx:
+        w = ctx.tensor_from(raw, 8, (K, K)).set_name("selector")
+        w.transfer_to_gpu()
+        try:
+            for aq in (0, 1):
+                G.set_option("act_quant", aq)
+                for i, x in enumerate(xs):
+                    out, y = _selector_launch(G, False, w.ptr, XNORM, ESTORE, K, K, x, xw=nw, y=True)
+                    assert np.array_equal(y.view(np.uint32), R.norm_rows(x[None], nw, EPS)[0].view(np.uint32)), f"row {i}: the normed row"
+                    e = O.mul_mat(8, raw, K, K, y[None], mode=O.ref_mode() if aq == 0 else O.MODE_SCALAR)[0]
+                    q, d, _ = R.q8(y, aq, True)
+                    assert np.array_equal(e, (q.astype(np.float32) * d[:, None]).reshape(-1))
+                    bad = np.flatnonzero(out != e)
+                    assert bad.size == 0, f"act_quant {aq} row {i}: {bad.size} outputs differ, first {bad[:8]}"
+        finally:
+            G.set_option("act_quant", 0)
+
+
+def test_kbig_matvec_staging_quantizer_reveals_quants_and_bsums(G, O):
+    """k_mmvq_kbig's staging quantizer (KX_F32 + KE_ROW) through a Q6_K selector (q8 * d8 of every column) and a Q4_K matrix of
+    one-hot mins (every pair of bsums), on the whole Q8_K set: ties, +max and -max at every reduction boundary, the clamp."""
+    K = 768
+    pool, _ = R.q8k_pool()
+    rows = list(R.launches(pool, 1, K // 256))
+    for t, raw, M in ((14, _selector_q6_k(K), K), (12, _selector_q4_k(K), K // 32)):
+        with G.Context(raw.nbytes + (1 << 20)) as ctx:
+            w = ctx.tensor_from(raw, t, (K, M)).set_name("selector")
+            w.transfer_to_gpu()
+            for i, x in enumerate(rows):
+                out, _ = _selector_launch(G, True, w.ptr, KF32, KROW, K, M, x[0])
+                e = O.mul_mat(t, raw, M, K, x, mode=O.ref_mode())[0]
+                q, d, bs = R.q8k(x)
+                mine = (d[:, None] * q.astype(np.float32)).reshape(-1) if t == 14 else \
+                    -(d[:, None] * bs.astype(np.int32).reshape(-1, 8, 2).sum(axis=2).astype(np.float32)).reshape(-1)
+                assert np.array_equal(e, mine.astype(np.float32)), f"type {t} row {i}: the oracle's product is not the revealed quantity"
+                bad = np.flatnonzero(out != e)
+                assert bad.size == 0, f"type {t} row {i}: {bad.size} outputs differ, first {bad[:8]}: got {out[bad[:4]]} want {e[bad[:4]]}"
+
+
+def test_kbig_matvec_norm_staging_reveals_quants_and_bsums(G, O):
+    """KX_NORM (+ KE_ROW): the revealed quants and bsums against the oracle's quantization of the tapped y_out, three magnitudes."""
+    K = 768
+    xs, nw = _norm_rows3(K, 22)
+    for t, raw, M in ((14, _selector_q6_k(K), K), (12, _selector_q4_k(K), K // 32)):
+        with G.Context(raw.nbytes + (1 << 20)) as ctx:
+            w = ctx.tensor_from(raw, t, (K, M)).set_name("selector")
+            w.transfer_to_gpu()
+            for i, x in enumerate(xs):
+                out, y = _selector_launch(G, True, w.ptr, KNORM, KROW, K, M, x, xw=nw, y=True)
+                assert np.array_equal(y.view(np.uint32), R.norm_rows(x[None], nw, EPS)[0].view(np.uint32)), f"row {i}: the normed row"
+                e = O.mul_mat(t, raw, M, K, y[None], mode=O.ref_mode())[0]
+                bad = np.flatnonzero(out != e)
+                assert bad.size == 0, f"type {t} row {i}: {bad.size} outputs differ, first {bad[:8]}: got {out[bad[:4]]} want {e[bad[:4]]}"
