@@ -735,6 +735,20 @@ GGML_API int ggml_hip_decode_pool_requests(struct ggml_cgraph *const *graphs, in
                                            const ggml_hip_sampler_chain *const *chains, const ggml_hip_chain_end *ends, const int32_t *windows,
                                            const int32_t *window_n, uint64_t *rng, float *mu, int32_t *out_ids, int32_t *col,
                                            int32_t *first_step, int32_t *n_evaluated, int32_t *ended_by, int32_t *steps_run);
+/* The PROMPTS of 1 .. 64 sessions of one model as one packed prompt batch: graphs[i] is the reference's unchanged N_i-token
+ * Llama::evaluate graph of its own session (own memory_k / memory_v, own n_past, N_i >= 1), built and not computed.  The R = sum N_i
+ * rows run as ONE pass of the prompt plan (f16-MFMA GEMMs over all R rows, the K split chosen at R rows); segment i is rows
+ * [row0_i, row0_i + N_i) in graph order, and the three launches that place a row in a sequence — RoPE table, K/V store, fused
+ * attention — read every row's position and cache from tables of the call (kernels/prompt_pack.h).  Results go where an evaluation of
+ * graph i alone leaves them: its logits and embedding rows at its result nodes, K/V rows n_past_i .. n_past_i + N_i - 1 of its caches.
+ * 0, or -1 with nothing executed and nothing written: option plan, plan_prompt or plan_prompt_pack (default 1, GGML_HIP_PLAN_PROMPT_PACK)
+ * = 0, a graph that is not a whole-model LLaMA graph, a K-quant or F16 model (block formats Q4_0 .. Q8_0 only), K/V not f16, graphs of
+ * different models, the same cache twice, a cache of another device slot, option attn_fused = 0 or a segment whose n_past_i + N_i does
+ * not take the 32-query form of the fused attention, n_past_i + N_i beyond the context, R > 4096, rows of more than 8192 elements, a
+ * token id outside the vocabulary.  NULL pointers and n_graphs outside 1 .. 64 are refused before any device is touched.  Counters:
+ * prompt_pack_calls, prompt_pack_segments, prompt_pack_tokens; the rows count in prompt_plan_tokens too. */
+#define GGML_HIP_PACK_MAX 64
+GGML_API int ggml_hip_prompt_pack(struct ggml_cgraph *const *graphs, int n_graphs);
 /* Top-k prefilter of a logits row on the device: the k (<= 1024, <= ne0) largest entries of row `row` of
  * the f32 tensor `t` — a node of the caller's most recent ggml_graph_compute, normally the logits — as (value, id) pairs,
  * value descending, lower id first among equal values, followed by the entries of `extra_ids` (n_extra ids, e.g. the

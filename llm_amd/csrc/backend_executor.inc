@@ -146,6 +146,7 @@ void invalidate_xf16_if_overwritten_impl(const ggml_tensor *n) {
 #include "plan_prompt.inc"
 #include "plan_run.inc"
 #include "plan_pool.inc"
+#include "plan_pack.inc"
 
 void execute_graph(ggml_cgraph *gr) {
     ensure_init();

@@ -116,6 +116,9 @@ struct Backend {
     PoolHead *pool_pin = nullptr;
     hipEvent_t pool_ev[2] = {nullptr, nullptr};
     uint64_t stat_pool_calls = 0, stat_pool_admitted = 0, stat_pool_steps = 0;
+    // the packed prompt batch (plan_pack.inc)
+    int opt_plan_prompt_pack = 1;
+    uint64_t stat_prompt_pack_calls = 0, stat_prompt_pack_segments = 0, stat_prompt_pack_tokens = 0;
     uint64_t stat_flash_attn_nodes = 0;
     // prompt-GEMM launches by kernel (ggml_hip_get_stat("mmq_launches_<name>")): bench.py labels its MFMA roofline with the
     // kernels that actually ran
@@ -217,6 +220,8 @@ static const OptRow g_options[] = {
     {"plan_batch_sample", &Backend::opt_plan_batch_sample, OPT_ENV},
     // ggml_hip_decode_pool_requests: ended columns take waiting requests on the device (0: the entry declines, callers step)
     {"plan_batch_pool", &Backend::opt_plan_batch_pool, OPT_ENV},
+    // ggml_hip_prompt_pack: the prompt rows of up to 64 sessions as one pass of the prompt plan (0: the entry declines, callers feed one by one)
+    {"plan_prompt_pack", &Backend::opt_plan_prompt_pack, OPT_ENV},
     // ggml_hip_decode_sampled_chain: n tokens of ONE session with that sampler on the device between two replays of its single-token
     // plan (0: it answers -1, the caller samples on the host and evaluates token by token).  It shapes no plan.
     {"plan_sample_chain", &Backend::opt_plan_sample_chain, OPT_ENV},
@@ -352,6 +357,9 @@ static const StatRow g_counters[] = {
     {"pool_calls", &Backend::stat_pool_calls},                        // calls of ggml_hip_decode_pool_requests that ran
     {"pool_admitted", &Backend::stat_pool_admitted},                  // requests k_pool_admit moved from the queue into a column
     {"pool_steps", &Backend::stat_pool_steps},                        // their steps_run: steps up to the last evaluation any request took (what was launched counts in batch_decode_steps)
+    {"prompt_pack_calls", &Backend::stat_prompt_pack_calls},          // calls of ggml_hip_prompt_pack that ran
+    {"prompt_pack_segments", &Backend::stat_prompt_pack_segments},    // their graphs (one segment each)
+    {"prompt_pack_tokens", &Backend::stat_prompt_pack_tokens},        // their rows (counted in prompt_plan_tokens too)
     {"sample_chain_tokens", &Backend::stat_sample_chain_tokens},  // ... and their tokens (one session a step: the same number, kept beside batch_sample_*)
     {"cols_warm_launches", &Backend::stat_cols_warm_launches},    // chunk-plan norm launches that carried warming workgroups (ColsWarm), counted when enqueued or captured
     {"fused_rearms", &Backend::stat_fused_rearms},                // times the fused forms came back after a clean stretch behind a give-up

@@ -987,6 +987,18 @@ int ggml_hip_decode_pool_requests(struct ggml_cgraph *const *graphs, int n_pool,
     return 0;
 }
 
+// ---- the packed prompt batch: the prompt rows of several sessions as one pass of the prompt plan (plan_pack.inc) ----
+int ggml_hip_prompt_pack(struct ggml_cgraph *const *graphs, int n_graphs) {
+    if (!graphs || n_graphs < 1 || n_graphs > PACK_SEGS_MAX) return -1;  // (before any device is touched)
+    for (int i = 0; i < n_graphs; i++)
+        if (!graphs[i]) return -1;
+    SlotLock lk;
+    const uint64_t t0 = now_ns();
+    const int r = prompt_pack(graphs, n_graphs);
+    g.ns_compute += now_ns() - t0;
+    return r;
+}
+
 // ---- test hook: one launch of k_pool_admit on the caller's tables (tests/test_pool_requests_gpu.py) ----
 void ggml_hip_debug_pool_admit_sizes(int64_t *sizes) {
     if (!sizes) return;

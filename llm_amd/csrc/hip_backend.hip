@@ -61,6 +61,7 @@
 #include "kernels/decode_f16.h"
 #include "kernels/prompt.h"
 #include "kernels/prompt_attn.h"
+#include "kernels/prompt_pack.h"
 #include "kernels/flash_attn.h"
 
 // Last words of the library: stderr, and (GGML_HIP_FATAL_LOG=path) a file — a test runner that captures file descriptor 2

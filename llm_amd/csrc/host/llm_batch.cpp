@@ -57,4 +57,12 @@ int llm_infer_until_pool(llm_model *m, llm_session *const *sessions, int N, cons
     return llm_infer_until_pool_via(ggml_hip_decode_batch, ggml_hip_decode_chain_requests, ggml_hip_decode_pool_requests, m, sessions, N, reqs, rngs,
                                     mus, max_cols, out_ids, n_out, ended_by);
 }
+// ... and the packed prompt batch (llm_pack.cpp)
+int llm_feed_prompt_batch(llm_model *m, llm_session *const *sessions, int B, const int32_t *tokens, const int32_t *counts, int max_rows) {
+    return llm_feed_prompt_batch_via(ggml_hip_prompt_pack, m, sessions, B, tokens, counts, max_rows);
+}
+int llm_prompt_pack(llm_model *m, llm_session *const *sessions, int B, const int32_t *tokens, const int32_t *counts, float *all_logits,
+                    float *embeddings) {
+    return llm_prompt_pack_via(ggml_hip_prompt_pack, m, sessions, B, tokens, counts, all_logits, embeddings);
+}
 }

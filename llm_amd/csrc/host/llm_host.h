@@ -279,6 +279,36 @@ GGML_API int llm_infer_until_pool_via(llm_batch_entry step, llm_chain_requests_e
  * (either may be NULL): request i runs in column col_out[i] from step first_step_out[i].  Returns the number of steps, -1 on bad
  * arguments.  Needs no device. */
 GGML_API int llm_pool_schedule(const int32_t *evals, int n, int n_cols, int32_t *col_out, int32_t *first_step_out);
+/* ---- feeding the prompts of B >= 1 sessions of one model as packed prompt batches (ggml_hip_prompt_pack): `tokens` is the prompts back
+ * to back, counts [B] (all >= 1) their lengths, max_rows 1 .. 4096 the rows of one evaluation (0 means 512).  Rounds follow ONE rule
+ * (llm_pack_schedule): in every round the sessions are visited in index order and a session with tokens left takes min(left, room)
+ * rows, room being what is left of max_rows; the round goes to the backend as those sessions' graphs, one per session, built as
+ * llm_evaluate builds them and not computed (more than 64 sessions in a round: pieces of 64 in index order); repeat until nothing is
+ * left.  The sessions' own n_batch is NOT consulted: the round is the unit.  Afterwards every session has its tokens appended, n_past
+ * advanced and last_logits equal to its last row's logits, as llm_feed_prompt leaves it.  If the backend declines a round, that
+ * round's sessions and all later rounds are fed one by one through llm_feed_prompt (each session's remaining tokens as one call, so a
+ * call that never packs leaves exactly what llm_feed_prompt alone leaves).  Returns 1 if every round ran packed, 0 if any was
+ * stepped, -1 with nothing moved on bad arguments: B < 1, a NULL session, the same session twice, a session of another model, of a
+ * layer-split model or on another device slot than the calling thread's, a count < 1, a token outside the vocabulary, max_rows out
+ * of range, a session for which llm_feed_prompt would report ContextFull. ---- */
+GGML_API int llm_feed_prompt_batch(llm_model *m, llm_session *const *sessions, int B, const int32_t *tokens, const int32_t *counts,
+                                   int max_rows);
+typedef int (*llm_pack_entry)(struct ggml_cgraph *const *graphs, int n_graphs);
+GGML_API int llm_feed_prompt_batch_via(llm_pack_entry entry, llm_model *m, llm_session *const *sessions, int B, const int32_t *tokens,
+                                       const int32_t *counts, int max_rows);
+/* ONE evaluation of ggml_hip_prompt_pack over all B <= 64 sessions' tokens: no rounds, no fallback (tests and tools).  all_logits
+ * (nullable): [sum counts][n_vocab], every row's logits in order; embeddings (nullable): [B][n_embd], each session's last row.
+ * 0 = it ran and every session moved as above; -1 = bad arguments or the backend declined, nothing moved. */
+GGML_API int llm_prompt_pack(llm_model *m, llm_session *const *sessions, int B, const int32_t *tokens, const int32_t *counts,
+                             float *all_logits, float *embeddings);
+GGML_API int llm_prompt_pack_via(llm_pack_entry entry, llm_model *m, llm_session *const *sessions, int B, const int32_t *tokens,
+                                 const int32_t *counts, float *all_logits, float *embeddings);
+/* test hook: the session's graph for these n tokens at its n_past, built as llm_evaluate builds it and not computed (for
+ * ggml_hip_prompt_pack); the session does not move.  NULL on bad arguments. */
+GGML_API struct ggml_cgraph *llm_session_stage_rows(llm_model *m, llm_session *s, const int32_t *tokens, int n);
+/* The rule for rounds alone: take_out (nullable) [rounds][B], row r = the rows each session takes in round r.  Returns the number of
+ * rounds, -1 on bad arguments (NULL counts, B < 1, a count < 1, max_rows outside 0 .. 4096).  Needs no device. */
+GGML_API int llm_pack_schedule(const int32_t *counts, int B, int max_rows, int32_t *take_out);
 /* test hook: the most steps llm_infer_until_pool asks of one call of the entry (1 .. 4096, the default); returns the previous cap */
 GGML_API int llm_pool_step_cap(int cap);
 /* test hook: the end rule alone, on recorded logits rows [n_rows][V] (row t stands for the logits the t-th draw sees; the window is

@@ -233,6 +233,24 @@ class InferenceSession {
         n_past += 1;
     }
 
+    // The packed prompt batch (llm_feed_prompt_batch): the session's graph for `n` tokens at n_past, built as compute() builds it and its
+    // tokens written, but not computed; commit_rows is compute()'s bookkeeping once a backend entry has run it.
+    ggml_cgraph *stage_rows(const TokenId *toks, size_t n, const Builder &builder, GraphOutputs &out) {
+        pre_.valid = false;
+        cur_ ^= 1;
+        Built built = build_into(cur_, n, builder);
+        built.embd.write_data(toks, n * sizeof(TokenId));
+        out = GraphOutputs{built.out.result.share(), built.out.embedding_result.share()};
+        return built.gf.raw();
+    }
+    void commit_rows(ggml_cgraph *gr, size_t n) {
+        last_n_nodes = gr->n_nodes;
+        last_n_leafs = gr->n_leafs;
+        last_graph = gr;
+        if (mem_per_token == 0) mem_per_token = ctx0_[cur_].used_mem() / n_embd_;
+        n_past += n;
+    }
+
     void drop_prebuilt() {  // a speculatively built next-token graph no longer describes the session's next call
         pre_.valid = false;
         last_graph = nullptr;
@@ -558,6 +576,16 @@ class Llama {
     void finish_single(InferenceSession &session, ggml_cgraph *gr, const GraphOutputs &out) {
         session.commit_single(gr);
         common::read_last_token(session, out.result, hyperparameters.n_vocab, 1);
+    }
+
+    // ... and evaluate() of n tokens the same way (llm_feed_prompt_batch): the graph evaluate builds for a default OutputRequest — the
+    // logits of more than one token stay on the device — then n_past, and last_logits from the last row
+    ggml_cgraph *stage_rows(InferenceSession &session, const TokenId *toks, size_t n, GraphOutputs &out) {
+        return session.stage_rows(toks, n, make_builder(&session, n, session.n_past, n > 1), out);
+    }
+    void finish_rows(InferenceSession &session, ggml_cgraph *gr, size_t n, const GraphOutputs &out, bool last_piece) {
+        session.commit_rows(gr, n);
+        if (last_piece) common::read_last_token(session, out.result, hyperparameters.n_vocab, n);  // (as feed_prompt: only the last chunk's logits can be observed)
     }
 
     Hyperparameters hyperparameters;

@@ -56,6 +56,8 @@ static inline bool perm_0213(const ggml_tensor *t) {
 
 // set while try_decode_plan re-matches a K-quant batch whose f16 copies have no room: the K plan's multi-token form instead
 static thread_local bool tl_k_prompt_off = false;
+// set while prompt_pack (plan_pack.inc) matches its graphs: each is a segment of a prompt-plan evaluation whatever its own token count
+static thread_local bool tl_match_pack = false;
 #define MATCH(cond)       \
     do {                  \
         if (!(cond)) return false; \
@@ -339,6 +341,7 @@ static bool match_llama_decode(ggml_cgraph *gr, LlamaMatch &m) {
     const bool k_early = m.kquant && g.opt_mmq_w16 && g.opt_plan_prompt && !g.opt_mmq_i8;  // (the early switch only where that plan can run)
     m.prompt = m.N > 8 && g.opt_mmq_min > 0 && m.N >= (k_early ? std::min(g.opt_mmq_min, std::max(9, g.opt_k_prompt_min)) : g.opt_mmq_min);
     if (m.kquant && tl_k_prompt_off && m.N <= MULTI_MAX_N) m.prompt = false;
+    if (tl_match_pack) m.prompt = true;  // (one token or many: the pack's rows run on the prompt plan, so its conditions are the ones that count)
     if (!m.prompt) MATCH(attn_decode_lds(attn_decode_rows(m.C, m.N, m.H), m.D) <= ATTN_DECODE_LDS_MAX);
     if (m.prompt) {  // prompt plan (plan_launch_prompt): the default f16 GEMM path only, score buffer bounded
         MATCH(g.opt_plan_prompt && !g.opt_mmq_i8);

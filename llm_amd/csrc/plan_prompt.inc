@@ -324,12 +324,30 @@ static void prompt_attention(bool fused, const float *q, const __half *mk, const
         HIP_CHECK(hipGetLastError());
     }
 }
-static void plan_launch_prompt(DecodePlan *p) {
+// the fused attention of a packed batch: k_p_attn_seg over the call's attention tiles (the table is in dealing order), LDS for
+// the longest segment; wo's re-quantized f16 operand out, Q rotated while it is loaded, as the one-session plan's fused launch
+static void prompt_attention_pack(const PackLaunch &pk, int il, const float *q, _Float16 *x16_out, int64_t E, int64_t Egqa, int64_t H, int64_t Hkv,
+                                  int64_t D, int64_t C, float scale, bool f16d, const float *rope, int64_t q_part) {
+    PAttnArgs pa;
+    pa.q = q; pa.mem_k = nullptr; pa.mem_v = nullptr; pa.out = nullptr;
+    pa.N = 0; pa.E = (int)E; pa.Egqa = (int)Egqa; pa.H = (int)H; pa.r = (int)(H / Hkv); pa.n_past = 0;
+    pa.C = C; pa.scale = scale; pa.row_bytes = prompt_attn_row_bytes(pk.T_max);
+    pa.x16 = x16_out; pa.f16d = f16d ? 1 : 0;
+    pa.rope = rope; pa.q_part = q_part;
+    pa.r1 = 0; pa.ts = nullptr;
+    const size_t lds = (size_t)PATTN_Q * std::max<size_t>(pa.row_bytes, 2 * D + 16);
+    Timed tm(GGML_HIP_KCLASS_ATTN, (double)pk.T_max * Egqa * 4.0 * pk.n_segs + (double)pk.n_atiles * PATTN_Q * E * 8.0);
+    if (launch_p_attn_seg(g.stream, (int)D, &pa, pk.segs + (size_t)il * pk.n_segs, pk.atiles, pk.n_atiles, lds)) die("prompt pack: the fused attention's LDS opt-in failed");
+    HIP_CHECK(hipGetLastError());
+}
+// pk: a packed batch (plan_pack.inc) — the N rows are segments of several sessions; the three launches that place a row in a sequence
+// (RoPE table, K/V store, attention) run in their segment forms (kernels/prompt_pack.h), everything else is the same launch over N rows
+static void plan_launch_prompt(DecodePlan *p, const PackLaunch *pk = nullptr) {
     const LlamaMatch &m = p->m;
     const bool kq = m.kquant;  // K-quant model: the GEMMs' token operand is the Q8_K round trip, the weights their f16 copies (k_prompt_weights)
     const int N = m.N, qt = kq ? QT_Q8_0 : qt_of(m.wtype);
     const bool f16d = !kq && qt_f16d(qt);
-    const int64_t E = m.E, F = m.F, nbE = E / 32, nbF = F / 32, T = (int64_t)m.n_past + N;
+    const int64_t E = m.E, F = m.F, nbE = E / 32, nbF = F / 32, T = pk ? pk->T_max : (int64_t)m.n_past + N;
     const int64_t Tp = (T + 7) & ~(int64_t)7;  // row length of the f16 probabilities (16-byte aligned rows)
     const float theta_scale = powf(m.freq_base, -2.0f / m.n_dims);
     const bool fused_attn = g.opt_attn_fused && prompt_attn_fits(m.D, T);
@@ -416,13 +434,16 @@ static void plan_launch_prompt(DecodePlan *p) {
                            (const int *)p->p_tok, p->xa, E);
         HIP_CHECK(hipGetLastError());
     }
-    hipLaunchKernelGGL(k_rope_table, dim3((unsigned)N), dim3(128), 0, g.stream, (const DecParams *)p->prm, theta_scale,
-                       m.freq_scale, (int)(m.D >> 1), p->rope);
+    if (pk)
+        launch_rope_table_rows(g.stream, N, pk->pos, theta_scale, m.freq_scale, (int)(m.D >> 1), p->rope);
+    else
+        hipLaunchKernelGGL(k_rope_table, dim3((unsigned)N), dim3(128), 0, g.stream, (const DecParams *)p->prm, theta_scale,
+                           m.freq_scale, (int)(m.D >> 1), p->rope);
     HIP_CHECK(hipGetLastError());
     for (int il = 0; il < m.L; il++) {
         const DecodePlan::LW &w = p->lw[il];
         const DecodePlan::LayerNorms &ln = p->ln[il];
-        __half *mk = p->mem_k_at(il), *mv = p->mem_v_at(il);
+        __half *mk = pk ? nullptr : p->mem_k_at(il), *mv = pk ? nullptr : p->mem_v_at(il);
         // inpSA (xa) = the previous layer's inpFF + its w2 output; cur = rms_norm(inpSA) * attn_norm
         if (il == 0)
             norm_quant(p->xa, nullptr, nullptr, nullptr, ln.attn_norm, nullptr);
@@ -433,7 +454,20 @@ static void plan_launch_prompt(DecodePlan *p) {
             float *ds[3] = {p->p_qf, p->p_kf, p->p_vf};
             sp_qkv = gemm_multi(3, ws, ds, nbE, qkv_stride);
         }
-        {
+        if (pk) {
+            PQkvPostSeg a;
+            a.q = p->p_qf; a.kf = p->p_kf; a.vf = p->p_vf; a.tab = p->rope;
+            a.segs = pk->segs + (size_t)il * pk->n_segs; a.row_seg = pk->row_seg; a.vtiles = pk->vtiles;
+            a.R = N; a.E = (int)E; a.Egqa = (int)m.Egqa; a.D = (int)m.D; a.C = m.C;
+            a.skip_q = 1;  // (a pack runs the fused attention only)
+            a.nb_rope = (int)(((int64_t)N * (m.Egqa / 4) + 255) / 256);
+            a.part = sp_qkv > 1 ? qkv_stride : 0;
+            a.vt_n = pk->n_vtiles;
+            a.vt_m = (int)((m.Egqa + 63) / 64);
+            Timed tm(GGML_HIP_KCLASS_OTHER, (double)N * (E * 8.0 + m.Egqa * 12.0));
+            launch_p_qkv_post_seg(g.stream, &a);
+            HIP_CHECK(hipGetLastError());
+        } else {
             PQkvPost a;
             a.q = p->p_qf; a.kf = p->p_kf; a.vf = p->p_vf; a.tab = p->rope; a.mem_k = mk; a.mem_v = mv;
             a.N = N; a.E = (int)E; a.Egqa = (int)m.Egqa; a.D = (int)m.D; a.n_past = m.n_past; a.C = m.C;
@@ -448,8 +482,11 @@ static void plan_launch_prompt(DecodePlan *p) {
         }
         // the fused attention kernel hands wo its GEMM operand directly (k_p_quant4's arithmetic in its epilogue)
         // (K-quant model: a Q8_K super-block spans two heads, so the attention writes f32 and k_p_quant4 makes the operand)
-        prompt_attention(fused_attn, p->p_qf, mk, mv, p->p_mg, p->p_sc, p->p_p16, N, E, m.Egqa, m.H, m.Hkv, m.D, m.n_past, m.C, m.kq_scale,
-                         fused_attn && !kq ? p->p_x16 : nullptr, f16d, fused_attn ? p->rope : nullptr, fused_attn && sp_qkv > 1 ? qkv_stride : 0);
+        if (pk)
+            prompt_attention_pack(*pk, il, p->p_qf, p->p_x16, E, m.Egqa, m.H, m.Hkv, m.D, m.C, m.kq_scale, f16d, p->rope, sp_qkv > 1 ? qkv_stride : 0);
+        else
+            prompt_attention(fused_attn, p->p_qf, mk, mv, p->p_mg, p->p_sc, p->p_p16, N, E, m.Egqa, m.H, m.Hkv, m.D, m.n_past, m.C, m.kq_scale,
+                             fused_attn && !kq ? p->p_x16 : nullptr, f16d, fused_attn ? p->rope : nullptr, fused_attn && sp_qkv > 1 ? qkv_stride : 0);
         if (!fused_attn || kq) {
             Timed tm(GGML_HIP_KCLASS_OTHER, (double)N * E * 6.0);
             const int64_t n4 = (int64_t)N * E / 4;

@@ -24,6 +24,8 @@
 //   plan_prompt.inc  plan_launch_multi, plan_launch_batch, prompt_attention, plan_launch_prompt
 //   plan_run.inc     capture and replay, an evaluation as its steps (try_decode_plan), speculation, the fused-timeout re-run, the
 //                    greedy chain, the batched step
+//   plan_pool.inc    the request pool (ggml_hip_decode_pool_requests)
+//   plan_pack.inc    the packed prompt batch (ggml_hip_prompt_pack): plan_launch_prompt over the rows of several sessions
 //
 // The matcher is structural (it follows src[] pointers from the logits back to get_rows and checks every view's
 // shape/stride/offset against the KV-cache layout), so any graph that is not exactly the reference's LLaMA
@@ -529,6 +531,17 @@ static inline int prompt_attn_queries(int64_t D, int64_t T) {
     return 0;
 }
 static inline bool prompt_attn_fits(int64_t D, int64_t T) { return prompt_attn_queries(D, T) != 0; }
+// ---- a packed prompt batch (plan_pack.inc, kernels/prompt_pack.h): what plan_launch_prompt's three placing launches read instead of
+// "rows n_past .. of one cache" — the tables of the call, on the device ----
+struct PackLaunch {
+    const int *pos;            // [R] the position of row r
+    const int *row_seg;        // [R] its segment
+    const PackSeg *segs;       // [L][n_segs]: layer il's table at segs + il * n_segs
+    const PackTile *vtiles;    // [n_vtiles] 64-token V tiles
+    const int *atiles;         // [n_atiles][2] attention tiles in dealing order
+    int n_segs, n_vtiles, n_atiles;
+    int64_t T_max;             // the longest n_past + N of the pack: the score rows' LDS
+};
 // ---- GGML_OP_FLASH_ATTN (kernels/flash_attn.h): queries per workgroup of the MFMA kernel k_flash_attn_tile — 32, 16 (long rows) —
 // or 0: one row per workgroup (k_flash_attn_row).  The tile kernel takes f16 K/V of head size 32 / 64 / 128, at least two query
 // rows, rows of at most FLASH_ATTN_MAX_KEYS_TILE keys (its score rows have k_p_attn's size) and reads K rows and V rows 16 bytes

@@ -284,6 +284,7 @@ PROTOTYPES.update({
     "ggml_hip_decode_pool_requests": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                 C.c_void_p]),
+    "ggml_hip_prompt_pack": (C.c_int, [C.c_void_p, C.c_int]),
     "ggml_hip_debug_pool_admit_sizes": (None, [C.c_void_p]),
     "ggml_hip_debug_pool_admit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                             C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
@@ -584,6 +585,12 @@ def timing_query(kclass):
     ms, n, b = C.c_double(0), C.c_int64(0), C.c_double(0)
     lib().ggml_hip_timing_query(kclass, C.byref(ms), C.byref(n), C.byref(b))
     return ms.value, n.value, b.value
+
+
+def prompt_pack(graphs):
+    """ggml_hip_prompt_pack on staged graphs (pointers, e.g. from llama.Session.stage_rows): 0, or -1 = declined, nothing executed."""
+    arr = (C.c_void_p * max(len(graphs), 1))(*graphs)
+    return int(lib().ggml_hip_prompt_pack(arr, len(graphs)))
 
 
 def get_stat(key):

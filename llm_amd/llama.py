@@ -139,6 +139,14 @@ def _lib():
                                            C.c_void_p, C.c_void_p]
         L.llm_pool_schedule.restype = C.c_int
         L.llm_pool_schedule.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        L.llm_feed_prompt_batch.restype = C.c_int
+        L.llm_feed_prompt_batch.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_void_p, C.c_int]
+        L.llm_prompt_pack.restype = C.c_int
+        L.llm_prompt_pack.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.llm_session_stage_rows.restype = C.c_void_p
+        L.llm_session_stage_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+        L.llm_pack_schedule.restype = C.c_int
+        L.llm_pack_schedule.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         L.llm_pool_step_cap.restype = C.c_int
         L.llm_pool_step_cap.argtypes = [C.c_int]
         L.llm_until_rule.restype = C.c_int
@@ -519,6 +527,44 @@ class Llama:
             raise ValueError("llm_infer_until_pool: bad arguments (nothing was evaluated)")
         return [out[i, :counts[i]].copy() for i in range(N)], counts, [ENDED_BY[int(w)] for w in why], bool(rc)
 
+    @staticmethod
+    def _packed(sessions, prompts):
+        if len(prompts) != len(sessions) or len(sessions) < 1:
+            raise ValueError("one prompt per session, at least one")
+        prompts = [np.ascontiguousarray(p, dtype=np.int32).ravel() for p in prompts]
+        counts = np.array([p.size for p in prompts], np.int32)
+        tokens = np.ascontiguousarray(np.concatenate(prompts) if counts.sum() else np.zeros(1, np.int32), dtype=np.int32)
+        return (C.c_void_p * len(sessions))(*[s.ptr for s in sessions]), tokens, counts
+
+    def feed_prompt_batch(self, sessions, prompts, max_rows=512):
+        """Session.feed_prompt for several sessions of this model at once (llm_feed_prompt_batch): prompts[i] goes to sessions[i], and
+        the rows of all of them run as packed prompt batches of at most max_rows (1 .. 4096) rows — one pass over the weights per
+        round instead of one per session and chunk (ggml_hip_prompt_pack: block-format models, f16 K/V).  Rounds: sessions in index
+        order, each takes min(tokens left, room left in the round); the sessions' own n_batch is not consulted.  Every session ends
+        as feed_prompt leaves it (tokens, n_past, last_logits of its last token).  Returns 1 if every round ran packed, 0 if the
+        backend declined one: that round's and all later tokens were then fed one session after the other through feed_prompt.
+        ValueError with nothing moved on bad arguments (a session twice, an empty prompt, a token outside the vocabulary, a prompt
+        that does not fit its session's context)."""
+        ptrs, tokens, counts = self._packed(sessions, prompts)
+        rc = _lib().llm_feed_prompt_batch(self.ptr, ptrs, len(sessions), tokens.ctypes.data, counts.ctypes.data, int(max_rows))
+        if rc < 0:
+            raise ValueError("llm_feed_prompt_batch: bad arguments (nothing was evaluated)")
+        return int(rc)
+
+    def prompt_pack(self, sessions, prompts):
+        """Test hook: ONE call of ggml_hip_prompt_pack over all the prompts (llm_prompt_pack; at most 64 sessions), no rounds and no
+        fallback.  Returns (rc, logits, embeddings): rc 0 = it ran — logits[i] is [len(prompts[i]), n_vocab], embeddings[i] the
+        final-norm row of session i's last token — or -1 = bad arguments or the backend declined: nothing moved, the rest is None."""
+        ptrs, tokens, counts = self._packed(sessions, prompts)
+        V, E = self.hp["n_vocab"], self.hp["n_embd"]
+        logits = np.zeros((int(counts.sum()), V), np.float32)
+        emb = np.zeros((len(sessions), E), np.float32)
+        rc = _lib().llm_prompt_pack(self.ptr, ptrs, len(sessions), tokens.ctypes.data, counts.ctypes.data, logits.ctypes.data, emb.ctypes.data)
+        if rc != 0:
+            return -1, None, None
+        ends = np.cumsum(counts)
+        return 0, [logits[e - c:e] for c, e in zip(counts, ends)], [emb[i] for i in range(len(sessions))]
+
     def free(self):
         if self.ptr:
             _lib().llm_model_free(self.ptr)
@@ -563,6 +609,12 @@ class Session:
     def feed_prompt(self, tokens):
         tokens = np.ascontiguousarray(tokens, dtype=np.int32)
         _lib().llm_feed_prompt(self.model.ptr, self.ptr, tokens.ctypes.data, tokens.size)
+
+    def stage_rows(self, tokens):
+        """Test hook: this session's graph for `tokens` at its n_past, built as evaluate builds it and NOT computed (llm_session_stage_rows);
+        returns the ggml_cgraph pointer for ggml.prompt_pack.  The session does not move."""
+        tokens = np.ascontiguousarray(tokens, dtype=np.int32)
+        return _lib().llm_session_stage_rows(self.model.ptr, self.ptr, tokens.ctypes.data, tokens.size)
 
     def infer_next_token(self):
         return int(_lib().llm_infer_next_token_greedy(self.model.ptr, self.ptr))
