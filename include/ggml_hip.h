@@ -900,7 +900,7 @@ GGML_API int ggml_hip_debug_mat_vec_f16(const struct ggml_tensor *w0, const stru
  * nullable), w [K] and eps the norm's; part != 0 (P_SILU_MUL_QUANT): second partials `part` floats on in a and b; zp: the zero point
  * of QUANT_ACT_I8 (8, 16 or 0).  flags: 1 = d after its f16 round trip (the Q8_0 kind), 2 = with the [block][8] tables dT / sT, 4 = the
  * Q8_K round trip form of the P_* kinds.  outs: the kind's output buffers in the order listed at the definition
- * (llm_amd/csrc/backend_tools.inc), each holding its elements and 256 bytes more, which come back as the device holds them (0xFF
+ * (llm_amd/csrc/debug_quant_attn.inc), each holding its elements and 256 bytes more, which come back as the device holds them (0xFF
  * before the launch).  0, or -1 for what no call site launches. */
 enum ggml_hip_act_quant_kind {
     GGML_HIP_AQ_QUANTIZE_ACT = 0, GGML_HIP_AQ_QUANT_ROW, GGML_HIP_AQ_RMSNORM_QUANT, GGML_HIP_AQ_RMSNORM_QUANT_WARM,

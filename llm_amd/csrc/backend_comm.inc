@@ -143,11 +143,4 @@ void ggml_hip_comm_sendrecv(const void *dev_src, int send_peer, void *dev_dst, i
     RCCL_CHECK(rccl.GroupEnd());
 }
 
-// Launch-floor probe (tests/tools/launch_probe.py): a linear hipGraph of `n_launch` launches of a kernel that does
-// nothing but stamp the 100 MHz wall clock — at its very first instruction, again once its LAST kernel argument has
-// arrived, and at its end — with the launch shape of the decode mat-vecs (threads per workgroup, dynamic LDS, size
-// of the kernarg segment).  Separates what a kernel boundary costs by itself, and how long the kernel arguments
-// take to arrive, from what the mat-vec kernels add.  out[0] = us per launch (HIP events around `replays` replays),
-// out[1] = us from one launch's end stamp to the next launch's first instruction, out[2] = us first instruction ->
-// last kernel argument usable (workgroup 0 of each launch).
 }  // extern "C"

@@ -6,7 +6,7 @@
 bool is_contig_f32(const ggml_tensor *t) { return t->type == GGML_TYPE_F32 && ggml_is_contiguous(t); }
 
 // ---- the activation quantizers' launches: grid, block and dynamic LDS of each kernel, one text for the executor, the plans and
-// the test hook ggml_hip_debug_act_quant (backend_tools.inc).  Accounting (Timed / cx) stays with the callers.
+// the test hook ggml_hip_debug_act_quant (debug_quant_attn.inc).  Accounting (Timed / cx) stays with the callers.
 // 32 lanes per block, rows of nb_row bytes
 void launch_quantize_act(bool f16_d, const char *x, int64_t nb_row, int64_t nb, int64_t N, int8_t *lo, int8_t *hi, float *d, int *s) {
     with_bool(f16_d, [&](auto F16D) {

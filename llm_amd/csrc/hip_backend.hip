@@ -962,4 +962,9 @@ int ggml_hip_bench_plan_class(int kclass, int replays, double *ms_total, int64_t
 }
 
 #include "backend_comm.inc"
+#include "backend_api.inc"
 #include "backend_tools.inc"
+#include "debug_run.inc"
+#include "debug_matvec.inc"
+#include "debug_quant_attn.inc"
+#include "debug_token.inc"

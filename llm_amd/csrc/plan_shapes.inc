@@ -16,7 +16,7 @@
 //   plan_shapes.inc  LlamaMatch, DecodePlan (the layers' matrices as LayerMats<format>, the captured graphs as one VariantGraphs
 //                    per attention variant), live_plan (what a remembered plan pointer still names) and every "which kernel, which
 //                    grid for which shape" decision (plain host functions the matcher, the launchers, the run loop and the test
-//                    hooks of backend_tools.inc all call)
+//                    hooks of the debug_*.inc files all call)
 //   plan_match.inc   the structural graph matcher
 //   plan_build.inc   weights, signature and activation pool of a plan (plan_pool_layout: every buffer declared once)
 //   plan_decode.inc  the single-token launchers: plan_launch_all, plan_launch_k, plan_launch_f16, and what the last two share
