@@ -49,10 +49,20 @@ struct FusedAttnArgs {
     // WO form (k_qkv_attn<.., WO = true>): the heads' re-quantized outputs are PUBLISHED to the mat-vec workgroups of the same
     // launch instead of stored for a following wo launch: this layer's E/32 x OGRAN granules (publish_head_q8 below)
     unsigned long long *ogran;
+    // Eight unused bytes, for where the next field lands in the KERNARG segment.  Every workgroup of k_qkv_attn_wo opens with two
+    // dependent round trips of scalar loads of its arguments, on the launch's critical path.  `ogran` is the last word of a 64-byte
+    // line of the segment (BigArgs = 448 bytes, ogran at 184); with out_f32 directly behind it hipcc fetched the two as ONE 16-byte
+    // load across the line boundary, in the second round trip — the only load there to touch a line the first round trip had not
+    // brought in.  With the pad it loads ogran alone.  Measured, this field and nothing else: the mat-vec workgroups finish wq|wk|wv
+    // 0.3 us and the next launch enters 0.5-0.9 us earlier, +1.25 % tokens/s at 7B (DESIGN.md section 4.2 "kernarg lines",
+    // profiles/r12_kernarg_line_headline.txt); that the straddling load is a scalar-cache miss is read from the ISA, not measured.
+    unsigned long long kernarg_line_pad;
     // K plan (k_qkv_attn_k, kernels/kquant_big.h): the merged heads as f32 [n_head * D] instead of Q8_0 blocks (wo stages its own
     // Q8_K row from them); nullptr = the Q8_0 forms above
     float *out_f32;
 };
+// (whoever moves a field of BigArgs or FusedAttnArgs: look at the kernel's first s_load instructions again, tests/tools/disasm.py)
+static_assert((sizeof(BigArgs) + offsetof(FusedAttnArgs, kernarg_line_pad)) % 64 == 0, "FusedAttnArgs::ogran no longer ends a 64-byte line of the kernarg segment of k_qkv_attn_wo");
 
 // ---------------------------------------------------------------------------------------------------
 // wo under the attention's tail.  After its last wq|wk|wv row pair (about 7 us into a 7B launch) a mat-vec workgroup is idle
