@@ -58,6 +58,8 @@ static std::vector<uint64_t> plan_signature(const LlamaMatch &m, bool session = 
                        (uint64_t)m.V, (uint64_t)m.C, (uint64_t)m.n_dims, (uint64_t)m.wtype, f2u(m.eps),
                        f2u(m.freq_base), f2u(m.freq_scale), f2u(m.kq_scale)})
         s.push_back(v);
+    // a K output under block-format layers: its own word (the output's record, next, differs from a pure twin's too)
+    s.push_back((uint64_t)m.out_k);
     for (const ggml_tensor *t : {m.wte, m.norm, m.output, m.stage_in, m.stage_out}) s.push_back(t ? rec_id(t) : 0);
     if (session)
         for (const ggml_tensor *t : {m.memory_k, m.memory_v}) s.push_back(rec_id(t));
@@ -139,6 +141,25 @@ static bool k_prompt_weights(const LlamaMatch &m, DecodePlan *p) {
     p->w16_gen = g.w16_gen;
     return true;
 }
+// The prompt plan of an out_k model (block-format layers, K output): its lm_head GEMM has no operand but the resident f16 copy of the
+// output matrix, as every GEMM of a K-quant model (k_prompt_weights).  Made here if it is not there; p: also its QWeight face into
+// p->output.  false = no room for the copy: nothing has been launched, the node-by-node executor runs the batch.
+static bool out_k_prompt_weight(const LlamaMatch &m, DecodePlan *p) {
+    DevTensor *e = plan_rec(m.output);
+    if (!e || !e->ksoa || (uintptr_t)m.output->data != e->host) return false;
+    if (!e->w16) {
+        size_t free_b = 0, total_b = 0;
+        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || free_b < w16_need({m.output}) + w16_headroom()) return false;
+        if (!ensure_w16_k(e)) return false;
+    }
+    if (!p) return true;
+    memset(&p->output, 0, sizeof(p->output));
+    p->output.M = e->kw.M;
+    p->output.nb = e->kw.nsb * 8;
+    p->output.qt = QT_Q8_0;  // never read: every kernel that takes a resident copy reads only w16 (as in mul_mat_k_gemm)
+    p->output.w16 = e->w16;
+    return true;
+}
 // Does blockIdx mod 8 name the XCD of a one-workgroup-per-CU launch on this device?  (The dispatcher deals workgroups round robin over
 // the XCDs; HW_REG_XCC_ID says where each one landed.)  Looked at once per slot, outside any capture (build_plan).
 static void xcd_labels_probe() {
@@ -178,6 +199,7 @@ static void plan_pool_layout(DecodePlan *p, PoolCarver &c) {
     const size_t R = (size_t)m.N;  // activation rows: 1 for decode, 2..31 for a prompt chunk, the columns of a batched step, more for the prompt plan
     const size_t E = (size_t)m.E, F = (size_t)m.F, S = (size_t)p->att_S;
     const bool one = m.N == 1, spec = one && m.logits, multi = m.N >= 2 && !m.prompt, kq = m.kquant;
+    const bool okq = m.out_k && !m.prompt;  // the Q8_K rows of the final norm for an out_k model's lm_head (plan_lm_head_k): R rows of E
     // scratch of the split attention, and the hand-off granules of the in-launch attention exchanges: one set per LAYER for a single token (the tag is the token's epoch alone)
     const size_t Lg = one ? (size_t)m.L : 1;
     c.take(p->att_sc, (size_t)m.H * m.C * 4);
@@ -222,14 +244,14 @@ static void plan_pool_layout(DecodePlan *p, PoolCarver &c) {
     c.take(p->e_sT, multi ? passes * E / 32 * 32 : 0);
     c.take(p->f_dT, multi ? passes * F / 32 * 32 : 0);
     c.take(p->f_sT, multi ? passes * F / 32 * 32 : 0);
-    const size_t kW = std::max(E, F);
+    const size_t kW = okq ? E : std::max(E, F);
     c.take(p->k_kf, kq ? R * m.Egqa * 4 : 0);
     c.take(p->k_vf, kq ? R * m.Egqa * 4 : 0);
     c.take(p->k_att, kq || m.f16w ? R * E * 4 : 0);  // (the F16 plan's attention output too: the f32 row wo stages)
     c.take(p->k_g3, kq ? R * F * 4 : 0);
-    c.take(p->k_q8, kq ? R * kW : 0);
-    c.take(p->k_d8, kq ? R * kW / 256 * 4 : 0);
-    c.take(p->k_bs, kq ? R * kW / 256 * 32 : 0);
+    c.take(p->k_q8, kq || okq ? R * kW : 0);
+    c.take(p->k_d8, kq || okq ? R * kW / 256 * 4 : 0);
+    c.take(p->k_bs, kq || okq ? R * kW / 256 * 32 : 0);
     // (the prompt plan's other buffers live only during one evaluation: shared workspace, plan_launch_prompt)
     c.take(p->p_tok, m.prompt ? R * 4 : 0);
 }
@@ -240,7 +262,8 @@ static DecodePlan *build_plan(const LlamaMatch &m, std::vector<uint64_t> sig, bo
         size_t free_b = 0, total_b = 0;
         const bool room = hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b >= w16_need(ws) + w16_headroom();
         if (room)
-            for (auto *w : ws) ensure_w16(plan_rec(w));
+            for (auto *w : ws)
+                if (w != m.output || !m.out_k) ensure_w16(plan_rec(w));  // (an out_k model's output: resolve_plan / prompt_pack have made its copy, out_k_prompt_weight)
     }
     xcd_labels_probe();
     if (!g.hot_line) {  // (here, not at the first launch: launches may be inside a stream capture)
@@ -253,9 +276,10 @@ static DecodePlan *build_plan(const LlamaMatch &m, std::vector<uint64_t> sig, bo
     if (m.wte) (m.f16w ? (void)(p->f_wte = plan_f16w(m.wte)) : m.kquant ? (void)(p->k_wte = plan_kw(m.wte)) : (void)(p->wte = plan_qw(m.wte)));
     if (m.output) {
         if (m.f16w) p->f_output = plan_f16w(m.output);
-        else if (m.kquant) p->k_output = plan_kw(m.output);
+        else if (m.kquant || m.out_k) p->k_output = plan_kw(m.output);  // (out_k: the one K matrix of a block-format plan)
         else p->output = plan_qw(m.output);
         p->norm = (const float *)dev_ptr(m.norm);
+        if (m.out_k && m.prompt && !out_k_prompt_weight(m, p)) die("prompt plan: no room for the f16 copy of the K-quant output matrix (set GGML_HIP_PLAN_OUT_K=0 to run the node-by-node executor)");
     }
     if (m.stage_in) p->stage_in = (float *)dev_ptr(m.stage_in);
     if (m.stage_out) p->stage_out = (float *)dev_ptr(m.stage_out);

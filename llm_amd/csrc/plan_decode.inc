@@ -160,6 +160,7 @@ struct ResultDst {
     char *logits;
 };
 static ResultDst plan_result_dst(const DecodePlan *p, const LaunchCtx &cx) { return ResultDst{p->res_emb(cx.out_set), p->res_logits(cx.out_set)}; }
+static void plan_lm_head_k(DecodePlan *p, LaunchCtx &cx, const ResultDst &dst);  // (behind launch_kbig below)
 // ---- what the K plan and the F16 plan share: everything around their mat-vecs ----
 // The opening: the residual rows from the hand-off buffer, or the embedding rows of the N token ids (`embed`: the plan's own get_rows
 // launch, embed_bytes per element its books); then one (cos, sin) table per column, 128 floats apart (batch: each at its own session's position)
@@ -397,6 +398,7 @@ static void plan_launch_all(DecodePlan *p, int av, LaunchCtx cx) {
     }
     if (!m.output) return;  // not the last stage: the last layer's w2 launch has written the residual into the outgoing hand-off buffer
     const ResultDst dst = plan_result_dst(p, cx);
+    if (m.out_k) return plan_lm_head_k(p, cx, dst);  // a K output under these layers: the K plan's tail (its own norm staging or norm launch)
     if (!big) rmsq(p->xa, p->norm, dst.emb);  // final norm: f32 copy for OutputRequest.embeddings + Q8 for lm_head
     {
         DecMmvqArgs a;
@@ -518,6 +520,23 @@ static void launch_kbig(int nseg, const KWeight *const *ws, float *const *dsts, 
     } else
         with_kt(w.kt, [&](auto KT) { launch_kbig_x<CT(KT)>(ka, src.xsrc, lds, epi); });
     HIP_CHECK(hipGetLastError());
+}
+// The lm_head of an out_k plan (block-format layers under a K output matrix: plan_launch_all, plan_launch_chunk) over the N rows of
+// p->xa — the K plan's tail, nothing new.  A single token whose matrix k_mmvq_kbig takes (out_k_big): that one launch, which stages the
+// final norm itself and taps the embedding row.  Otherwise k_k_norm_quant over the N rows (f32 copy into dst.emb, Q8_K into the plan's
+// k_* rows) and k_mmvq_k in passes of 8 / 4 / 2 / 1 columns.  Both repeat the node-by-node executor's Q8_K quantizer and row sums.
+static void plan_lm_head_k(DecodePlan *p, LaunchCtx &cx, const ResultDst &dst) {
+    const LlamaMatch &m = p->m;
+    const int N = m.N;
+    const KWeight *const ws[1] = {&p->k_output};
+    float *const ds[1] = {(float *)dst.logits};
+    const double bytes = (double)N * ws[0]->nsb * 292.0 + (double)ws[0]->M * ws[0]->nsb * k_block_bytes(ws[0]->kt) + (double)N * ws[0]->M * 4.0;
+    if (out_k_big(m)) {
+        cx.mmvq(4, bytes, [&] { launch_kbig(1, ws, ds, RowSrc{KX_NORM, p->xa, p->norm, m.eps, dst.emb}, nullptr); });
+        return;
+    }
+    cx.other((double)N * m.E * 9.3, [&] { launch_k_norm_quant(p->xa, p->norm, m.eps, m.E, N, dst.emb, p->k_q8, p->k_d8, p->k_bs); });
+    cx.mmvq(4, bytes, [&] { launch_mmvq_kn(1, ws, ds, KAct{p->k_q8, p->k_d8, p->k_bs}, N, nullptr); });
 }
 // batch: a batched step (plan_launch_batch) — the chunk's helper-launch form with column c at its own session's position and cache
 // (BatchCols): the RoPE tables, the rope/store and the attention are the three launches that read the table; AV_SHORT always

@@ -256,6 +256,16 @@ static bool match_llama_decode(ggml_cgraph *gr, LlamaMatch &m) {
         MATCH(match_norm(cur, c, nx1, lw.attn_norm, m) && nx1 == inpSA);
         x = inpSA;
     }
+    // The output matrix disagrees with the layers: the model is what its layers are.  Block-format layers under a K output — what
+    // llama.cpp's quantizer writes for every block-format file type whose output has dimensions in multiples of 256 — are a block-format
+    // model whose lm_head alone runs as the K plan's launches (out_k; option plan_out_k, 0 = the node-by-node executor as before the
+    // option existed).  Every other disagreement fails the per-matrix type check below.
+    if (m.output && m.kquant && qt_of(m.layers[0].wq->type) >= 0) {
+        MATCH(g.opt_plan_out_k);
+        m.wtype = m.layers[0].wq->type;
+        m.kquant = false;
+        m.out_k = true;
+    }
     // the residual stream starts at get_rows(wte, embd) — or, for a later stage of a layer split, at the residual
     // received into the stage's hand-off buffer: reshape_2d(view_1d(stage_in))
     if (is_op(x, GGML_OP_GET_ROWS)) {
@@ -352,7 +362,7 @@ static bool match_llama_decode(ggml_cgraph *gr, LlamaMatch &m) {
         MATCH(g.opt_plan_multi && g.opt_big && m.N <= MULTI_MAX_N && m.n_past + m.N <= m.C && qt_of(m.wtype) >= 0);
         MATCH(m.E % 32 == 0 && m.F % 32 == 0);
         const MultiCols mc = multi_cols(m);
-        MATCH(mc.qkv && mc.wo && mc.gate && mc.w2 && (mc.out || !m.output));
+        MATCH(mc.qkv && mc.wo && mc.gate && mc.w2 && (mc.out || !m.output || m.out_k));  // (out_k: the lm_head does not run on k_mmq_cols)
     } else if (m.N > 1) {  // multi-token plan (kernels/decode_big8.h): 8 Q8 columns of the widest row must fit LDS
         MATCH(g.opt_plan_multi && g.opt_big && multi_shape_ok(m, m.N));
         MATCH(m.n_past + m.N <= m.C);
@@ -362,6 +372,12 @@ static bool match_llama_decode(ggml_cgraph *gr, LlamaMatch &m) {
             const ggml_tensor *w = lw.at(i);
             MATCH(is_leaf(w) && (m.kquant ? kt_of(w->type) >= 0 : w->type == m.wtype));
         }
+    if (m.out_k) {  // the lm_head's own conditions: super-blocks of 256; a prompt batch multiplies by the resident f16 copy of the output (no other
+                    // operand); decode, chunks and batched steps (whose columns are matched here one by one, at N = 1) need a column of the
+                    // helper launches in LDS — the weaker condition for every E k_mmvq_kbig takes (out_k_big: E <= 8192), so it is asked always
+        MATCH(m.E % 256 == 0 && (!m.prompt || g.opt_mmq_w16));
+        MATCH(m.prompt || (size_t)m.E + (size_t)(m.E / 256) * 68 <= 150 * 1024);
+    }
     if (m.kquant && m.prompt) {  // prompt plan on the resident f16 copies of the K weights (mul_mat_k_gemm's operands: k_prompt_weights below)
         MATCH(g.opt_plan_k && g.opt_mmq_w16 && m.E % 256 == 0 && m.F % 256 == 0);
     } else if (m.kquant) {  // K plan: decode and chunks of up to 31 tokens (every helper kernel has the row as a grid dimension, the mat-vecs take

@@ -29,7 +29,7 @@ static int prompt_pack(ggml_cgraph *const *graphs, int B) {
         tl_match_pack = false;
         if (!matched) PACK_DECLINE();
         if (!m.wte || !m.output || !m.embd || !m.logits || !m.embedding) PACK_DECLINE();  // (a stage of a layer split)
-        if (m.kquant || m.f16w || qt_of(m.wtype) < 0) PACK_DECLINE();                     // block formats only
+        if (m.kquant || m.f16w || qt_of(m.wtype) < 0) PACK_DECLINE();                     // block formats only (a K output under block-format layers included: out_k)
         if (m.N < 1 || m.n_past + m.N > m.C || m.E > 8192) PACK_DECLINE();                // (f16 K/V, D, E, F: the matcher's own preconditions)
         if (prompt_attn_queries(m.D, (int64_t)m.n_past + m.N) != PATTN_Q) PACK_DECLINE();
         for (const ggml_tensor *t : {m.memory_k, m.memory_v}) {  // a session of another slot keeps its cache to itself (extra_of would abort)
@@ -56,6 +56,7 @@ static int prompt_pack(ggml_cgraph *const *graphs, int B) {
         if (i == 0) sig = std::move(s);
         else if (s != sig) PACK_DECLINE();
     }
+    if (ms[0].out_k && !out_k_prompt_weight(ms[0], nullptr)) PACK_DECLINE();  // a K output under block-format layers: no room for its f16 copy
     std::vector<__half *> mk((size_t)B), mv((size_t)B);
     for (int i = 0; i < B; i++) {
         mk[(size_t)i] = (__half *)dev_ptr(ms[(size_t)i].memory_k);
@@ -159,6 +160,7 @@ static int prompt_pack(ggml_cgraph *const *graphs, int B) {
     g.stat_prompt_pack_calls++;
     g.stat_prompt_pack_segments += (uint64_t)B;
     g.stat_prompt_pack_tokens += (uint64_t)R;
+    if (m0.out_k) g.stat_out_k_tokens += (uint64_t)R;
     d2h_finish();
     g.ns_match += t1 - t0;
     g.ns_launch += t2 - t1;

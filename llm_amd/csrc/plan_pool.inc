@@ -245,6 +245,7 @@ static int decode_pool_requests(ggml_cgraph *const *graphs, int n_pool, int B, i
         g.stat_kplan_tokens += (uint64_t)B * n;
         g.stat_batch_k_steps += n;
     }
+    if (ms[0].out_k) g.stat_out_k_tokens += (uint64_t)B * n;
     if (req.any_sampled(n_pool)) {
         g.stat_batch_sample_steps += n - 1;
         g.stat_batch_sample_tokens += (n - 1) * (uint64_t)B;

@@ -213,6 +213,7 @@ static void plan_launch_chunk(DecodePlan *p, const bool batch) {
         HIP_CHECK(hipMemcpyAsync(p->stage_out, p->xa, (size_t)N * E * 4, hipMemcpyDeviceToDevice, g.stream));
         return;
     }
+    if (m.out_k) return plan_lm_head_k(p, cx, ResultDst{p->emb_out, p->logits_out});  // a K output under these layers: the K plan's tail over the N rows
     // final norm of all N rows: f32 copy (embedding_result node) + Q8
     rmsq(p->xa, p->norm, p->emb_out, cols_warm_of(cols.out, {&p->output}, 1, nbE));
     {
@@ -372,17 +373,22 @@ static void plan_launch_prompt(DecodePlan *p, const PackLaunch *pk = nullptr) {
     if (kq && p->w16_gen != g.w16_gen && !k_prompt_weights(m, p))
         die("prompt plan: no room for the f16 copies of the K-quant weights any more (set GGML_HIP_PLAN_K=0 to run the node-by-node executor)");
     if (!kq && p->w16_gen != g.w16_gen) {
+        // out_k: the lm_head GEMM has no operand but the f16 copy of the K output (plan_build.inc out_k_prompt_weight) — made, if it has
+        // to be, before any pointer below is read again
+        if (m.out_k && !out_k_prompt_weight(m, p))
+            die("prompt plan: no room for the f16 copy of the K-quant output matrix any more (set GGML_HIP_PLAN_OUT_K=0 to run the node-by-node executor)");
         auto w16_of = [](const ggml_tensor *t) { DevTensor *e = plan_rec(t); return e ? e->qw.w16 : nullptr; };
         for (int il = 0; il < m.L; il++)
             for (int i = 0; i < LAYER_MATS; i++) p->lw[il].at(i).w16 = w16_of(m.layers[il].at(i));
-        if (m.output) p->output.w16 = w16_of(m.output);
+        if (m.output && !m.out_k) p->output.w16 = w16_of(m.output);
         p->w16_gen = g.w16_gen;
     }
     // [x + r ->] rms_norm * w -> Q8 -> f16 operand of the next GEMM
-    auto norm_quant = [&](const float *x, const float *x2, const float *r, float *xsum, const float *w, float *y_f32) {
+    // k_row: the operand of a GEMM on the f16 copy of a K matrix under block-format layers (out_k's lm_head): the Q8_K round trip
+    auto norm_quant = [&](const float *x, const float *x2, const float *r, float *xsum, const float *w, float *y_f32, bool k_row = false) {
         Timed tm(GGML_HIP_KCLASS_OTHER, (double)N * E * (r ? 18.0 : 6.0));
         if (E > 8192) die("prompt plan: rows of %lld elements (k_p_norm_quant holds a row of up to 8192 in registers)", (long long)E);
-        launch_p_norm_quant(kq, f16d, x, x2, r, xsum, w, m.eps, E, N, y_f32, p->p_x16);
+        launch_p_norm_quant(kq || k_row, f16d, x, x2, r, xsum, w, m.eps, E, N, y_f32, p->p_x16);
         HIP_CHECK(hipGetLastError());
     };
     // A GEMM whose tile count leaves CUs idle splits K in two (mmq_auto_splits, as in the node-by-node executor).  There
@@ -521,6 +527,6 @@ static void plan_launch_prompt(DecodePlan *p, const PackLaunch *pk = nullptr) {
         HIP_CHECK(hipGetLastError());
         return;
     }
-    norm_quant(p->p_te, sp_w2 > 1 ? p->p_te + te_stride : nullptr, p->xb, p->xa, p->norm, p->emb_out);
-    mmq_f16_launch(qt, p->output, p->p_x16, (float *)p->logits_out, m.V, N, nbE, true);
+    norm_quant(p->p_te, sp_w2 > 1 ? p->p_te + te_stride : nullptr, p->xb, p->xa, p->norm, p->emb_out, m.out_k);
+    mmq_f16_launch(m.out_k ? QT_Q8_0 : qt, p->output, p->p_x16, (float *)p->logits_out, m.V, N, nbE, true);
 }

@@ -265,6 +265,7 @@ static DecodePlan *resolve_plan(ggml_cgraph *gr, LlamaMatch &m) {
         if (!ok) return nullptr;
         m = m2;
     }
+    if (m.prompt && m.out_k && !out_k_prompt_weight(m, nullptr)) return nullptr;  // (likewise: no room for the f16 copy of the K output, the node-by-node executor)
     return find_or_build_plan(m, plan_signature(m));
 }
 // One token ahead: is this evaluation the one the device is already running?  Returns the parity of the ahead run on a hit, -1
@@ -310,6 +311,7 @@ static void run_prompt_plan(DecodePlan *p, const LlamaMatch &m, bool defer_wait,
     g.ns_match += t1 - t0;
     g.ns_launch += t2 - t1;
     g.stat_prompt_plan_tokens += (uint64_t)m.N;
+    if (m.out_k) g.stat_out_k_tokens += (uint64_t)m.N;
     if (defer_wait) {
         g.pending_wait = true;
         g.pending_light = true;
@@ -371,6 +373,7 @@ static void count_token_forms(const LlamaMatch &m, int av) {
     }
     if (av >= AV_FUSED2) g.stat_fused_heads_tokens++;
     if (m.kquant) g.stat_kplan_tokens += (uint64_t)m.N;
+    if (m.out_k) g.stat_out_k_tokens += (uint64_t)m.N;
 }
 static bool try_decode_plan(ggml_cgraph *gr, bool defer_wait = false) {
     g.chain_plan = nullptr;  // any new graph ends the chainable state; a single-token plan run re-arms it below
@@ -862,6 +865,7 @@ static int decode_chain(ggml_cgraph *last, int n, int32_t *out_tokens, float *la
     p->m.n_past += moved;
     p->replays += use_graph ? (uint64_t)n : 0;
     g.stat_plan_tokens += (uint64_t)n;
+    if (m.out_k) g.stat_out_k_tokens += (uint64_t)n;
     g.chain_plan = nullptr;  // the caller's next evaluation re-arms it
     return 0;
 }
@@ -1028,6 +1032,7 @@ static int decode_batch_steps(ggml_cgraph *const *graphs, int B, int n_steps, in
         g.stat_kplan_tokens += (uint64_t)B * (uint64_t)n_steps;
         g.stat_batch_k_steps += (uint64_t)n_steps;
     }
+    if (ms[0].out_k) g.stat_out_k_tokens += (uint64_t)B * (uint64_t)n_steps;
     if (smp || (req && req->any_sampled(B))) {  // (a sampled step is not a greedy one: batch_chain_* count ggml_hip_decode_batch_greedy's alone)
         g.stat_batch_sample_steps += (uint64_t)(n_steps - 1);
         g.stat_batch_sample_tokens += (uint64_t)(n_steps - 1) * (uint64_t)B;

@@ -9,6 +9,8 @@
 //   a prompt batch (plan_launch_prompt): 13 launches per layer around the matrix-core GEMMs, launched eagerly;
 //   one token each of 2..8 sessions of one model (plan_launch_batch; ggml_hip_decode_batch hands over their graphs together): the
 //   chunk's launches with a per-column position and cache.
+// A block-format model whose output matrix alone is a K-quant (LlamaMatch::out_k: llama.cpp's "mostly Q4_0 ... Q8_0" files) takes the block
+// formats' sequences with the K plan's tail as its lm_head (plan_decode.inc plan_lm_head_k).
 // The first three and the last are captured once in a hipGraph per attention variant and replayed for the following tokens with only
 // {n_past, token} changing in a device-side parameter block.  One file per concern, included in this order from
 // backend_executor.inc inside hip_backend.hip's anonymous namespace; the only forward declarations are DecodePlan and PrepMatch in
@@ -62,6 +64,8 @@ struct LlamaMatch {
     bool prompt = false;  // the prompt plan takes it
     bool kquant = false;  // every matrix is a K-quant (any mix of Q2_K … Q6_K): the K plan (plan_launch_k): decode, chunks of up to 31 tokens below k_prompt_min, batched steps (option plan_batch_k)
     bool f16w = false;    // every matrix is F16 (file type 1): the F16 plan (plan_launch_f16), decode, chunks and batched steps
+    bool out_k = false;   // a block-format model (wtype = the layers' type, kquant = false) whose output matrix alone is a K-quant, as llama.cpp's quantizer writes
+                          // every block-format file: every plan of the block formats, the lm_head as the K plan's launches (plan_lm_head_k; option plan_out_k)
     float eps = 0, freq_base = 0, freq_scale = 0, kq_scale = 0;
     ggml_type wtype = GGML_TYPE_F32;
     const ggml_tensor *wte = nullptr, *norm = nullptr, *output = nullptr, *embd = nullptr, *memory_k = nullptr,
@@ -455,6 +459,11 @@ static bool kfused_ok(const DecodePlan *p, int av) {
 static bool kbig_weight_ok(int kt, int64_t nsb, int64_t M, int64_t norm_width) {
     return kt >= 0 && kt <= KT_Q5_K && nsb <= 64 && norm_width <= 8192 &&  // all five K types; staging limits of k_mmvq_kbig (KBIG_SBW, KBIG_SQ)
            (M + (int64_t)g.num_cus * 16 - 1) / ((int64_t)g.num_cus * 16) <= 21;  // (three matrices per launch: 63 rows per wave)
+}
+// the lm_head of an out_k model as ONE k_mmvq_kbig launch that stages the final norm itself: a single token whose output matrix that
+// kernel takes; every other evaluation runs it as k_k_norm_quant + k_mmvq_k (plan_lm_head_k)
+static bool out_k_big(const LlamaMatch &m) {
+    return m.out_k && g.opt_kbig && m.N == 1 && kbig_weight_ok(kt_of(m.output->type), m.E / 256, m.V, m.E);
 }
 static bool kbig_ok(const DecodePlan *p) {  // K matrices whose rows of a wave fit its 64 epilogue lanes and whose activation row fits the staging
     if (!g.opt_kbig || p->m.N != 1) return false;
