@@ -910,6 +910,15 @@ enum ggml_hip_act_quant_kind {
 };
 GGML_API int ggml_hip_debug_act_quant(int kind, int flags, int64_t rows, int64_t K, int64_t stride, const float *a, const float *b,
                                       const float *r, const float *w, float eps, int64_t part, int zp, void *const *outs);
+/* Test hook of the MPT decode plan's two kernels with arithmetic of their own (option plan_mpt; llm_amd/csrc/kernels/mpt_plan.h), on
+ * host arrays.  op 0: the LayerNorm staging of its mat-vecs — x [K], the gain w [K], eps; out[0..3] = the planar Q8 blocks one workgroup
+ * stages: lo, hi [K/2] int8, d [K/32] f32 (flag 1: after its f16 round trip), sum [K/32] i32.  op 1: the ALiBi decode attention over
+ * token-major caches — x = q [H*D], w = the slopes [H], mem_k / mem_v [C][H*D] f16, the token at n_past, scale; out[0] [H*D] f32.
+ * op 2 (test-only state): flag != 0 = MPT plans built from now on carry a slope table with every head on the first sequence; cached
+ * plans are dropped.  op 3: x = a ggml_cgraph *: 1 if the MPT matcher takes it under the current options, 0 if not; nothing is executed.
+ * Every output is followed by 256 guard bytes (0xFF before the launch).  0, or -1 for what no call site launches. */
+GGML_API int ggml_hip_debug_mpt(int op, int flag, const float *x, const float *w, float eps, int64_t K, const uint16_t *mem_k,
+                                const uint16_t *mem_v, int H, int D, int n_past, int64_t C, float scale, void *const *out);
 /* Extension (layer split inside one process): slot `slot` enqueues on slot `with_slot`'s stream (with_slot < 0: on its own again).
  * Only for slots of ONE physical GPU whose work never overlaps — the stages of one split session: a wait on another queue's event
  * costs tens of microseconds per stage boundary on this runtime, the same wait inside one queue nothing.  1 = now shared, 0 = not

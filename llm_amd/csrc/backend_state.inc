@@ -86,7 +86,7 @@ struct Backend {
     size_t ws_off = 0;  // offset in the last chunk
     Timing timing;
     int opt_fuse = 1, opt_plan = 1, opt_plan_k = 1, opt_plan_multi = 1, opt_plan_prompt = 1, opt_graph = 1, opt_big = 1, opt_kbig = 1;
-    int opt_chain_k = 0, opt_prepare = 1, opt_plan_batch = 1, opt_plan_f16 = 1, opt_plan_batch_chain = 1, opt_plan_batch_sample = 1, opt_plan_sample_chain = 1, opt_plan_batch_k = 0, opt_plan_out_k = 1;
+    int opt_chain_k = 0, opt_prepare = 1, opt_plan_batch = 1, opt_plan_f16 = 1, opt_plan_batch_chain = 1, opt_plan_batch_sample = 1, opt_plan_sample_chain = 1, opt_plan_batch_k = 0, opt_plan_out_k = 1, opt_plan_mpt = 0;
     int opt_fuse_attn = 1, opt_fuse_wo = 1, opt_warm_mb = 24, opt_affine = 1;
     int opt_act_quant = 0, opt_mmq_i8 = 0;
     int opt_mmq_min = 32, opt_k_prompt_min = 12, opt_mmq_fuse = 3, opt_mmq_cols = 1, opt_mmq_t256 = 1, opt_attn_fused = 1;
@@ -102,7 +102,7 @@ struct Backend {
     uint64_t stat_plan_tokens = 0, stat_generic_graphs = 0, stat_split_tokens = 0, stat_prompt_plan_tokens = 0, stat_fused_tokens = 0, stat_kplan_tokens = 0, stat_fused_heads_tokens = 0, stat_fused_wo_tokens = 0, stat_fused_affine_tokens = 0, stat_prepared_tokens = 0;
     uint64_t stat_alibi_fused = 0;
     uint64_t stat_batch_tokens = 0, stat_batch_steps = 0, stat_batch_chain_steps = 0, stat_batch_chain_tokens = 0;
-    uint64_t stat_batch_sample_steps = 0, stat_batch_sample_tokens = 0, stat_batch_k_steps = 0, stat_out_k_tokens = 0;
+    uint64_t stat_batch_sample_steps = 0, stat_batch_sample_tokens = 0, stat_batch_k_steps = 0, stat_out_k_tokens = 0, stat_mpt_plan_tokens = 0;
     uint64_t stat_sample_chain_steps = 0, stat_sample_chain_tokens = 0;
     // the chains that stop (plan_run.inc chain_req_run): steps per group behind which the host looks at the columns' live flags, the
     // pinned words the flags are copied into (two sets: the host reads one while the next group's copy is in flight) and their events
@@ -206,6 +206,12 @@ static const OptRow g_options[] = {
     // ... and the block formats' plans for a block-format model whose output matrix alone is a K-quant (what llama.cpp's quantizer writes:
     // LlamaMatch::out_k, the lm_head as the K plan's launches); 0 = such a model runs node by node
     {"plan_out_k", &Backend::opt_plan_out_k, OPT_ENV | OPT_DROPS},
+    // ... and the MPT plan for the single-token graph of an MPT model with block-format weights (plan_match.inc match_mpt_decode,
+    // plan_decode.inc plan_launch_mpt: five launches per layer).  The default is 0 ONLY because tests/test_alibi_families_gpu.py, written
+    // before it, pins "single-token MPT steps run on the executor" (generic_graphs + 3, plan_tokens unchanged, alibi_fused per chunk and
+    // layer): at 0 nothing behaves differently from before the option existed — the plan_batch_k precedent.  Making it 1 is a change to
+    // those pins and to this initialiser, nothing else.
+    {"plan_mpt", &Backend::opt_plan_mpt, OPT_ENV | OPT_DROPS},
     {"plan_multi", &Backend::opt_plan_multi, OPT_ENV | OPT_DROPS},    // fused plan for prompt chunks of 2..8 tokens (kernels/decode_big8.h)
     {"plan_prompt", &Backend::opt_plan_prompt, OPT_ENV | OPT_DROPS},  // fused plan for prompt batches of >= mmq_min tokens (kernels/prompt.h)
     // ggml_hip_decode_batch: one decode step of 2..8 sessions of one model as one pass over the weights (0: it answers -1, the caller steps them one by one)
@@ -344,6 +350,7 @@ static const StatRow g_counters[] = {
     {"fused_affine_tokens", &Backend::stat_fused_affine_tokens},  // ... whose wq|wk|wv rows were dealt XCD-affine and handed over through the XCD's L2
     {"attn_split_tokens", &Backend::stat_split_tokens},           // tokens whose attention ran split over positions
     {"kplan_tokens", &Backend::stat_kplan_tokens},                // decode tokens of K-quant models that ran as the K plan
+    {"mpt_plan_tokens", &Backend::stat_mpt_plan_tokens},          // decode tokens of MPT models that ran as the MPT plan (option plan_mpt), evaluations and greedy chains; counted in plan_tokens too, never in generic_graphs
     {"out_k_tokens", &Backend::stat_out_k_tokens},                // tokens whose lm_head ran as the K launch inside a block-format plan (LlamaMatch::out_k); counted in plan_tokens / prompt_plan_tokens too
     {"prepared_tokens", &Backend::stat_prepared_tokens},          // decode tokens whose graph had been matched ahead of time (ggml_hip_graph_prepare)
     {"prompt_plan_tokens", &Backend::stat_prompt_plan_tokens},    // tokens executed by the fused prompt plan
@@ -609,6 +616,7 @@ void apply_act_quant() {
     HIP_CHECK(hipStreamSynchronize(g.stream));
     const int v = g.opt_act_quant;
     HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(c_act_quant_scalar), &v, sizeof(v)));
+    if (mpt_plan_set_act_quant(v)) die("option act_quant: the MPT plan's code object did not take it");  // (its own copy of the constant: mpt_plan.hip)
 }
 void ensure_init() {
     if (g.inited) {

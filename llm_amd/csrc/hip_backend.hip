@@ -63,6 +63,7 @@
 #include "kernels/prompt_attn.h"
 #include "kernels/prompt_pack.h"
 #include "kernels/flash_attn.h"
+#include "kernels/mpt_plan.h"
 
 // Last words of the library: stderr, and (GGML_HIP_FATAL_LOG=path) a file — a test runner that captures file descriptor 2
 // swallows the message of an abort together with the process.
@@ -968,3 +969,4 @@ int ggml_hip_bench_plan_class(int kclass, int replays, double *ms_total, int64_t
 #include "debug_matvec.inc"
 #include "debug_quant_attn.inc"
 #include "debug_token.inc"
+#include "debug_mpt.inc"

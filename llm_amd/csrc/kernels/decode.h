@@ -483,7 +483,9 @@ __global__ void __launch_bounds__(256) k_quant_row(const float *__restrict__ x, 
 // decode mat-vec with fused epilogues.  One wave = one PAIR of consecutive rows (m0, m0+1) of each
 // weight matrix it serves; 4 waves per workgroup; x staged in LDS exactly like k_mmvq.
 // ---------------------------------------------------------------------------------------------------
-enum { EPI_STORE = 0, EPI_ADD = 1, EPI_GATE = 2, EPI_QKV = 3 };
+// (the last two: k_mmvq_big alone, the MPT plan's code object mpt_plan.hip — EPI_QKV_TM: ONE matrix of [Q | K | V] rows, Q to f32, K and V
+//  as f16 into token-major caches, no RoPE; EPI_GELU: gelu_table of the row sum)
+enum { EPI_STORE = 0, EPI_ADD = 1, EPI_GATE = 2, EPI_QKV = 3, EPI_QKV_TM = 4, EPI_GELU = 5 };
 
 struct DecMmvqArgs {
     QWeight w[3];        // STORE/ADD: w[0]; GATE: w[0]=w1, w[1]=w3; QKV: wq, wk, wv
@@ -511,7 +513,9 @@ struct DecMmvqArgs {
 //               but it removes the separate norm+quantize launch (≈6.5 µs + a kernel boundary per use, twice
 //               per layer) from the serial decode chain.
 //   XSRC_F32  : plain f32 row → Q8 (the FFN gate feeding w2), same idea.
-enum { XSRC_Q8 = 0, XSRC_NORM = 1, XSRC_F32 = 2 };
+//   XSRC_LNORM: as XSRC_NORM with ggml's `norm` (LayerNorm without bias: mean, then the variance of the centred values, f64 sums as
+//               k_norm) in front of the gain; k_mmvq_big alone, instantiated in mpt_plan.hip only.
+enum { XSRC_Q8 = 0, XSRC_NORM = 1, XSRC_F32 = 2, XSRC_LNORM = 3 };
 
 // thread t of the 256 owns elements 4i..4i+3 with i = it*256 + t; a Q8 block = 8 consecutive threads
 template <bool F16_D, bool SC>

@@ -149,6 +149,74 @@ struct BigX<XSRC_NORM> {
     }
 };
 
+// ggml's `norm` and the gain (MPT's LayerNorm: no bias): the same loads, the same 1024 staging threads, a second statistic
+template <>
+struct BigX<XSRC_LNORM> : BigX<XSRC_NORM> {};
+// the row of xr.v as norm(x) * w, quantized into LDS.  k_norm's arithmetic (kernels/ops.h): mean = (float)(sum of x in f64 / n), then
+// variance = (float)(sum of the f32 squares of the f32 differences x - mean, in f64, / n), scale = 1 / sqrtf(variance + eps),
+// y = ((x - mean) * scale) * w — the two f64 sums in another order than k_norm's 256 threads take them (f64 sums of f32 terms: the
+// f32 they round to is the same but for ties of the f64 sum itself).  Three barriers: s_part is written twice.
+template <bool F16_D, bool YOUT>
+__device__ __forceinline__ void big_stage_lnorm(const BigArgs &a, const BigX<XSRC_LNORM> &xr, int nb, int tid, i32x4 *s_lo, i32x4 *s_hi,
+                                                float *s_d, int *s_sum, double *s_part, f32x4 *y_keep) {
+    constexpr int MAXIT = BigX<XSRC_NORM>::MAXIT, NT = BigX<XSRC_NORM>::NT;  // T == NT (launcher)
+    const int n4 = nb * 8, n_el = nb * 32;
+    const bool pow2 = (n_el & (n_el - 1)) == 0;  // uniform: the division is then an exact scaling (see the RMS form below)
+    auto mean_of = [&](double tot) {
+        return pow2 ? (float)__builtin_ldexp(tot, -(31 - __builtin_clz((unsigned)n_el))) : (float)(tot / (double)n_el);
+    };
+    auto total = [&](double v) {
+        v = wave_sum_f64(v);
+        if ((tid & 63) == 0) s_part[tid >> 6] = v;
+        __syncthreads();
+        double tot = 0.0;
+#pragma unroll
+        for (int i = 0; i < NT / 64; i++) tot += s_part[i];
+        return tot;
+    };
+    double s = 0.0;
+#pragma unroll
+    for (int it = 0; it < MAXIT; it++) {
+        const int i4 = it * NT + tid;
+        if (i4 < n4) {
+            s += (double)xr.v[it][0];
+            s += (double)xr.v[it][1];
+            s += (double)xr.v[it][2];
+            s += (double)xr.v[it][3];
+        }
+    }
+    const float mean = mean_of(total(s));
+    __syncthreads();  // every wave has read the first set of partial sums
+    f32x4 c[MAXIT];
+    double s2 = 0.0;
+#pragma unroll
+    for (int it = 0; it < MAXIT; it++) {
+        const int i4 = it * NT + tid;
+        c[it] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+        if (i4 < n4) {
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                c[it][k] = xr.v[it][k] - mean;
+                s2 += (double)(c[it][k] * c[it][k]);
+            }
+        }
+    }
+    const float variance = mean_of(total(s2));
+    const float scale = 1.0f / sqrtf(variance + a.d.eps);
+#pragma unroll
+    for (int it = 0; it < MAXIT; it++) {
+        const int i4 = it * NT + tid;
+        if (it * NT >= n4) break;  // uniform
+        f32x4 y = {0.0f, 0.0f, 0.0f, 0.0f};
+        if (i4 < n4) {
+#pragma unroll
+            for (int k = 0; k < 4; k++) y[k] = (c[it][k] * scale) * xr.w[it][k];
+            if constexpr (YOUT) y_keep[it] = y;
+        }
+        quant4_to_lds<F16_D>(y, i4, nb, tid, s_lo, s_hi, s_d, s_sum);
+    }
+}
+
 // registers -> LDS as padded planar Q8 (nbp = nbl*64 blocks; blocks >= nb are zero so tail steps contribute 0)
 template <bool F16_D, int XSRC, bool YOUT = false>
 __device__ __forceinline__ void big_stage_x(const BigArgs &a, const BigX<XSRC> &xr, int nb, int nbp, int tid, int T,
@@ -177,6 +245,8 @@ __device__ __forceinline__ void big_stage_x(const BigArgs &a, const BigX<XSRC> &
             const f32x4 v = i4 < n4 ? xr.v[it] : f32x4{0.0f, 0.0f, 0.0f, 0.0f};
             quant4_to_lds<F16_D>(v, i4, nb, tid, s_lo, s_hi, s_d, s_sum);
         }
+    } else if constexpr (XSRC == XSRC_LNORM) {
+        big_stage_lnorm<F16_D, YOUT>(a, xr, nb, tid, s_lo, s_hi, s_d, s_sum, s_part, y_keep);
     } else {
         constexpr int MAXIT = BigX<XSRC_NORM>::MAXIT, NT = BigX<XSRC_NORM>::NT;  // T == NT (launcher)
         {
@@ -270,6 +340,10 @@ __device__ __forceinline__ void big_body(const BigArgs &ba, const int bid, const
         n_past = a.prm->n_past;
         store_at = a.prm->store_at;
         if (ba.gran) epoch = *ba.epoch;
+    }
+    if constexpr (EPI == EPI_QKV_TM) {
+        n_past = a.prm->n_past;
+        store_at = a.prm->store_at;
     }
     BigX<XSRC> xr;
     xr.load(ba, nb, tid, T);
@@ -422,8 +496,9 @@ __device__ __forceinline__ void big_body(const BigArgs &ba, const int bid, const
             s_rope[2 * kk + 1] = rope_pre[1];
         }
     }
-    f32x4 y_keep[XSRC == XSRC_NORM && EPI == EPI_STORE ? BigX<XSRC_NORM>::MAXIT : 1];  // the normed row for the embedding tap (stored in the epilogue)
-    big_stage_x<F16_D, XSRC, XSRC == XSRC_NORM && EPI == EPI_STORE>(ba, xr, nb, nbp, tid, T, s_lo, s_hi, s_d, s_sum, s_part, y_keep);
+    constexpr bool YTAP = (XSRC == XSRC_NORM || XSRC == XSRC_LNORM) && EPI == EPI_STORE;
+    f32x4 y_keep[YTAP ? BigX<XSRC_NORM>::MAXIT : 1];  // the normed row for the embedding tap (stored in the epilogue)
+    big_stage_x<F16_D, XSRC, YTAP>(ba, xr, nb, nbp, tid, T, s_lo, s_hi, s_d, s_sum, s_part, y_keep);
     const long long t_staged = ts ? big_now() : 0;
     // ---- 2b. the rest of the ring
 #pragma unroll
@@ -506,6 +581,17 @@ __device__ __forceinline__ void big_body(const BigArgs &ba, const int bid, const
             a.dst[m0] = myv[0] + res_pre;
         } else if constexpr (EPI == EPI_GATE) {
             a.dst[m0] = silu_table(myv[0]) * myv[1];
+        } else if constexpr (EPI == EPI_GELU) {
+            a.dst[m0] = gelu_table(myv[0]);
+        } else if constexpr (EPI == EPI_QKV_TM) {  // row m0 of [Q | K | V], Egqa rows each: Q as f32, K and V as f16 (RNE, ggml's cpy) at position n_past
+            const int Eq = (int)a.Egqa;
+            const int p = store_at ? store_at : n_past;  // (store_at: a roofline replay parks its rows, see DecParams)
+            if (m0 < Eq)
+                a.dst[m0] = myv[0];
+            else if (m0 < 2 * Eq)
+                a.mem_k[(int64_t)p * Eq + (m0 - Eq)] = __float2half_rn(myv[0]);
+            else
+                a.mem_v[(int64_t)p * Eq + (m0 - 2 * Eq)] = __float2half_rn(myv[0]);
         } else {  // EPI_QKV, see k_mmvq_dec
             const int p = store_at ? store_at : n_past;
             __half h0, h1;  // the pair as f16: what the K/V cache holds, and what ggml's F16 mat-mul makes of Q (src1 -> f16)
@@ -540,7 +626,7 @@ __device__ __forceinline__ void big_body(const BigArgs &ba, const int bid, const
             }
         }
     }
-    if constexpr (XSRC == XSRC_NORM && EPI == EPI_STORE) {  // the embedding tap: workgroup 0's copy of the normed row
+    if constexpr (YTAP) {  // the embedding tap: workgroup 0's copy of the normed row
         if (ba.y_out && bid == 0) {
 #pragma unroll
             for (int it = 0; it < BigX<XSRC_NORM>::MAXIT; it++) {

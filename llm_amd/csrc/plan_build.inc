@@ -60,6 +60,10 @@ static std::vector<uint64_t> plan_signature(const LlamaMatch &m, bool session = 
         s.push_back(v);
     // a K output under block-format layers: its own word (the output's record, next, differs from a pure twin's too)
     s.push_back((uint64_t)m.out_k);
+    if (m.mpt) {  // another family's plan altogether: its own words (a LLaMA signature never has 0x6d7074 here: the next word is a record)
+        s.push_back(0x6d7074ull);
+        s.push_back(f2u(m.alibi_bias_max));
+    }
     for (const ggml_tensor *t : {m.wte, m.norm, m.output, m.stage_in, m.stage_out}) s.push_back(t ? rec_id(t) : 0);
     if (session)
         for (const ggml_tensor *t : {m.memory_k, m.memory_v}) s.push_back(rec_id(t));
@@ -79,7 +83,7 @@ static std::vector<uint64_t> plan_signature(const LlamaMatch &m, bool session = 
         for (auto &l : m.layers)
             for (int i = 0; i < LAYER_MATS; i++) rec(l.at(i));
     }
-    if (!session) return s;
+    if (!session || m.mpt) return s;  // (an MPT plan's results are rows of its pool: whichever arena the caller's graph of this token lives in)
     s.push_back(m.logits ? (uint64_t)(uintptr_t)dev_ptr(m.logits) : 0);
     s.push_back(m.embedding ? (uint64_t)(uintptr_t)dev_ptr(m.embedding) : 0);
     return s;
@@ -214,7 +218,7 @@ static void plan_pool_layout(DecodePlan *p, PoolCarver &c) {
     c.take(p->emb_alt, spec ? E * 4 : 0);
     c.take(p->kv_save[0], spec ? (size_t)m.L * m.Egqa * 4 : 0);
     c.take(p->kv_save[1], spec ? (size_t)m.L * m.Egqa * 4 : 0);
-    c.take(p->xnext, spec && m.wte && !kq && !m.f16w ? E * 4 : 0);
+    c.take(p->xnext, spec && m.wte && !kq && !m.f16w && !m.mpt ? E * 4 : 0);
     c.take(p->epoch, 256);
     const size_t units = (size_t)((m.E + 2 * m.Egqa) / 2);  // granules of a layer's wq|wk|wv rows
     c.take(p->gran, one ? (size_t)m.L * units * 8 : 0);
@@ -223,8 +227,9 @@ static void plan_pool_layout(DecodePlan *p, PoolCarver &c) {
     // a batched step's per-column table and its results, one row per column: the other plans' logits_out / emb_out are graph nodes (build_plan)
     c.take(p->bcols, p->batch ? sizeof(BatchCols) : 0);
     c.take(p->scols, p->batch || (spec && m.wte) ? sizeof(SampleCols) : 0);  // (a single-token whole-model plan: ggml_hip_decode_sampled_chain's one column)
-    c.take(p->logits_out, p->batch ? R * m.V * 4 : 0);
-    c.take(p->emb_out, p->batch ? R * E * 4 : 0);
+    c.take(p->logits_out, p->batch || m.mpt ? R * m.V * 4 : 0);  // (an MPT plan's too: its caller builds every token's graph in a fresh arena)
+    c.take(p->emb_out, p->batch || m.mpt ? R * E * 4 : 0);
+    c.take(p->alibi, m.mpt ? 256 * 4 : 0);
     c.take(p->prm, sizeof(DecParams));
     c.take(p->rope, std::max<size_t>(8, R) * 128 * 4);
     c.take(p->xa, R * E * 4);
@@ -247,7 +252,7 @@ static void plan_pool_layout(DecodePlan *p, PoolCarver &c) {
     const size_t kW = okq ? E : std::max(E, F);
     c.take(p->k_kf, kq ? R * m.Egqa * 4 : 0);
     c.take(p->k_vf, kq ? R * m.Egqa * 4 : 0);
-    c.take(p->k_att, kq || m.f16w ? R * E * 4 : 0);  // (the F16 plan's attention output too: the f32 row wo stages)
+    c.take(p->k_att, kq || m.f16w || m.mpt ? R * E * 4 : 0);  // (the F16 plan's attention output too: the f32 row wo stages)
     c.take(p->k_g3, kq ? R * F * 4 : 0);
     c.take(p->k_q8, kq || okq ? R * kW : 0);
     c.take(p->k_d8, kq || okq ? R * kW / 256 * 4 : 0);
@@ -256,6 +261,9 @@ static void plan_pool_layout(DecodePlan *p, PoolCarver &c) {
     c.take(p->p_tok, m.prompt ? R * 4 : 0);
 }
 // batch: the plan of a batched step (m: its first graph's match with N = the columns)
+// Test-only: MPT plans built while it is set get a WRONG slope table.  Nothing but ggml_hip_debug_mpt (op 2, debug_mpt.inc) may set it, and
+// whoever sets it clears it again (tests/test_mpt_plan_gpu.py does so in a finally); no option, no environment variable reaches it.
+static int g_mpt_slope_mutant = 0;
 static DecodePlan *build_plan(const LlamaMatch &m, std::vector<uint64_t> sig, bool batch = false) {
     if (m.prompt && !m.kquant) {  // prompt plan: resident f16 copies of the GEMM weights, all or none (a model either fits twice or not)
         const std::vector<const ggml_tensor *> ws = plan_matrices(m);
@@ -293,8 +301,8 @@ static DecodePlan *build_plan(const LlamaMatch &m, std::vector<uint64_t> sig, bo
     else p->lw = plan_layer_weights<QWeight>(m, plan_qw);
     for (auto &l : m.layers) p->ln.push_back({(const float *)dev_ptr(l.attn_norm), (const float *)dev_ptr(l.ffn_norm)});
     // the results of every plan but a batched step's are the graph's own nodes; a batched step's are rows of the pool (plan_pool_layout)
-    if (m.embedding && !batch) p->emb_out = (float *)dev_ptr(m.embedding);
-    if (m.logits && !batch) p->logits_out = dev_ptr(m.logits);
+    if (m.embedding && !batch && !m.mpt) p->emb_out = (float *)dev_ptr(m.embedding);
+    if (m.logits && !batch && !m.mpt) p->logits_out = dev_ptr(m.logits);
     p->att_S = plan_att_S(m.H);
     PoolCarver sizes{nullptr};
     plan_pool_layout(p, sizes);
@@ -307,5 +315,18 @@ static DecodePlan *build_plan(const LlamaMatch &m, std::vector<uint64_t> sig, bo
         *g.ferr_pin = 0;
     }
     p->ferr = g.ferr_pin;  // device-visible address of the slot's pinned word
+    if (m.mpt) {  // the slope table: the executor's host routine on the graph's alibi parameters
+        ggml_tensor al;
+        memset(&al, 0, sizeof(al));
+        al.op_params[1] = (int32_t)m.H;
+        memcpy(al.op_params + 2, &m.alibi_bias_max, 4);
+        AlibiSlopes sl = alibi_slopes(&al);
+        if (g_mpt_slope_mutant) {  // test hook (ggml_hip_debug_mpt): every head on the first sequence
+            const int n_floor = 1 << (int)floor(log2((double)m.H));
+            const float m0 = powf(2.0f, -(m.alibi_bias_max) / n_floor);
+            for (int k = 0; k < (int)m.H; k++) sl.m[k] = powf(m0, k + 1);
+        }
+        h2d_bulk((char *)p->alibi, &sl, sizeof(sl));
+    }
     return p;
 }

@@ -1,5 +1,6 @@
 // plan_decode.inc — the single-token launch sequences of a DecodePlan: plan_launch_all (block formats), plan_launch_k
-// (K-quants, which also takes chunks of up to 31 tokens) and plan_launch_f16 (F16 weights: decode, chunks and batched steps), and the launchers they share with plan_prompt.inc and the test hooks.
+// (K-quants, which also takes chunks of up to 31 tokens), plan_launch_f16 (F16 weights: decode, chunks and batched steps) and plan_launch_mpt (an MPT graph,
+// block formats), and the launchers they share with plan_prompt.inc and the test hooks.
 // per-class launch/byte accounting of one token (filled by the launch sequences when given)
 struct PlanStats {
     double bytes[GGML_HIP_KCLASS_COUNT] = {0, 0, 0, 0};
@@ -786,9 +787,81 @@ static void plan_launch_f16(DecodePlan *p, int av, LaunchCtx cx, bool batch = fa
     cx.mmvq(4, mv_bytes({&p->f_output}, E, 4.0),
             [&] { launch_f16(1, &p->f_output, d1, E, RowSrc{KX_NORM, p->xa, p->norm, m.eps, dst.emb}, nullptr, N); });
 }
+// ---------------------------------------------------------------------------------------------------
+// The MPT plan: single-token decode of an MPT graph (LlamaMatch::mpt), block-format weights.  Five launches per layer, every
+// dependency a kernel boundary, one stream:
+//   LayerNorm + Wqkv + K/V store | ALiBi attention | out_proj + residual | LayerNorm + up_proj + GELU | down_proj + residual
+// then LayerNorm + the tied lm_head, which taps the embedding row.  The first, the fourth and the last are k_mmvq_big with the LayerNorm
+// staging (XSRC_LNORM) out of the plan's own code object (mpt_plan.hip, with the attention); the two residual launches are the LLaMA
+// plan's own wo / w2 instantiations (EPI_ADD over a plain f32 row).  The reference's per-token copy of the layer's whole V cache is not
+// made: the attention reads memory_v's rows.  Same `mask` / `kind_mask` protocol as the other plans (kinds: 0 Wqkv, 1 out_proj,
+// 2 up_proj, 3 down_proj, 4 lm_head).
+// ---------------------------------------------------------------------------------------------------
+static void launch_big_lnorm(int qt, int epi, const BigArgs &a) {
+    const BigShape sh = big_shape(XSRC_LNORM, epi, a.d.nb, a.d.w[0].M);
+    if (!sh.ok) die("MPT plan: a launch the matcher's preconditions exclude (%lld rows)", (long long)a.d.w[0].M);
+    BigArgs b = a;
+    b.wdeal = sh.W;  // all 16 waves stage the norm, W of them take rows (as launch_big does for XSRC_NORM)
+    if (launch_mpt_big(g.stream, qt, epi, &b, sh.G, sh.lds)) die("MPT plan: no k_mmvq_big instantiation for type %d, epilogue %d", qt, epi);
+}
+static void plan_launch_mpt(DecodePlan *p, LaunchCtx cx) {
+    const LlamaMatch &m = p->m;
+    const int qt = qt_of(m.wtype);
+    const int64_t E = m.E, F = m.F, nbE = E / 32, nbF = F / 32;
+    const double bb = (double)blk_bytes(qt);
+    const int64_t Clds = (m.C + 7) & ~(int64_t)7;
+    auto big_args = [&](const DecMmvqArgs &a, float *y_out) {
+        return BigArgs{a, y_out, nullptr, 0, nullptr, 0, nullptr, nullptr, 0, p->hot};  // (no timeline, no probe: the production instantiations)
+    };
+    auto residual = [&](int kind, const QWeight &w, const float *xf, int64_t nb, const float *res, float *dst) {
+        DecMmvqArgs a;
+        memset(&a, 0, sizeof(a));
+        a.w[0] = w; a.xf = xf; a.nb = nb; a.dst = dst; a.res = res;
+        cx.mmvq(kind, (double)E * nb * bb + nb * 40.0 + E * 8.0, [&] { with_qt(qt, [&](auto QT) { launch_big<CT(QT), EPI_ADD, XSRC_F32>(big_args(a, nullptr)); }); });
+    };
+    cx.other((double)E * 4.6, [&] {
+        hipLaunchKernelGGL(k_get_rows_q, dim3((unsigned)((nbE + 255) / 256), 1), dim3(256), 0, g.stream, p->wte, (const int *)&p->prm->token, p->xa, E);
+    });
+    for (int il = 0; il < m.L; il++) {
+        const DecodePlan::LW &w = p->lw[il];
+        const DecodePlan::LayerNorms &ln = p->ln[il];
+        {   // LayerNorm + Wqkv; q as f32, the K and V rows as f16 at position n_past of the layer's caches
+            DecMmvqArgs a;
+            memset(&a, 0, sizeof(a));
+            a.w[0] = w.wq; a.xf = p->xa; a.xw = ln.attn_norm; a.eps = m.eps; a.nb = nbE; a.dst = p->q; a.prm = p->prm;
+            a.mem_k = p->mem_k_at(il); a.mem_v = p->mem_v_at(il); a.Egqa = E; a.C = m.C; a.D = (int)m.D;
+            cx.mmvq(0, 3.0 * E * nbE * bb + nbE * 40.0 + E * 8.0, [&] { launch_big_lnorm(qt, EPI_QKV_TM, big_args(a, nullptr)); });
+        }
+        {
+            const double bytes = (double)(m.n_past + 1) * E * 4.0 + E * 8.0;
+            if (cx.want(GGML_HIP_KCLASS_ATTN, bytes)) {
+                Timed tm(GGML_HIP_KCLASS_ATTN, bytes);
+                if (launch_mpt_attn(g.stream, (int)m.H, p->q, p->mem_k_at(il), p->mem_v_at(il), p->prm, m.kq_scale, p->alibi, (int)m.D, E, p->k_att,
+                                    Clds, attn_decode_lds(Clds, m.D)))
+                    die("MPT plan: the attention's LDS opt-in failed");
+                HIP_CHECK(hipGetLastError());
+            }
+        }
+        residual(1, w.wo, p->k_att, nbE, p->xa, p->xb);
+        {   // LayerNorm + up_proj + GELU
+            DecMmvqArgs a;
+            memset(&a, 0, sizeof(a));
+            a.w[0] = w.w1; a.xf = p->xb; a.xw = ln.ffn_norm; a.eps = m.eps; a.nb = nbE; a.dst = p->gate;
+            cx.mmvq(2, (double)F * nbE * bb + nbE * 40.0 + F * 4.0, [&] { launch_big_lnorm(qt, EPI_GELU, big_args(a, nullptr)); });
+        }
+        residual(3, w.w2, p->gate, nbF, p->xb, p->xa);
+    }
+    const ResultDst dst = plan_result_dst(p, cx);
+    DecMmvqArgs a;
+    memset(&a, 0, sizeof(a));
+    a.w[0] = p->output; a.xf = p->xa; a.xw = p->norm; a.eps = m.eps; a.nb = nbE; a.dst = (float *)dst.logits;
+    cx.mmvq(4, (double)m.V * nbE * bb + nbE * 40.0 + m.V * 4.0, [&] { launch_big_lnorm(qt, EPI_STORE, big_args(a, dst.emb)); });
+}
 // the decode launches of a plan, whichever kind it is
 static void plan_launch_decode(DecodePlan *p, int av = AV_SHORT, LaunchCtx cx = {}) {
-    if (p->m.f16w)
+    if (p->m.mpt)
+        plan_launch_mpt(p, cx);
+    else if (p->m.f16w)
         plan_launch_f16(p, av, cx);
     else if (p->m.kquant)
         plan_launch_k(p, av, cx);

@@ -388,4 +388,201 @@ static bool match_llama_decode(ggml_cgraph *gr, LlamaMatch &m) {
     }
     return true;
 }
+
+// ---------------------------------------------------------------------------------------------------
+// MPT (crates/models/mpt/src/lib.rs:93-259 as llm_amd/mpt.py builds it with every node offloaded): the single-token graph, for the MPT
+// plan (plan_decode.inc plan_launch_mpt; option plan_mpt).  Per layer, from the residual x:
+//   cur = mul(norm(x), norm_1) -> qkv = mul_mat(Wqkv, cur) -> views at 0, E, 2E -> cpy(K view, memory_k row) | cpy(V view, memory_v row)
+//   q = permute(cpy(Q view, [D, H, 1])) ; k = permute(reshape_3d(view_1d(memory_k)))            -> kq = mul_mat(k, q)
+//   soft_max(diag_mask_inf(alibi(scale(kq))))  ; vt = cpy(permute(reshape_3d(view_1d(memory_v)), 1, 2, 0, 3), [T, D, H] f16)
+//   cpy(permute(mul_mat(vt, p)), [E, 1]) -> x = add(x, mul_mat(out_proj, .))
+//   x = add(x, mul_mat(down_proj, gelu(mul_mat(up_proj, mul(norm(x), norm_2)))))
+// then mul(norm(x), norm_f) and mul_mat(wte, .) with the leaf get_rows read: 35 nodes per layer + 4. The vt copy is matched and never
+// executed: its destination has the one reader, which the plan's attention replaces.  No node but the logits may be mirrored to the
+// host (the reference's own form never offloads, every node is mirrored: the executor's).
+// ---------------------------------------------------------------------------------------------------
+static bool match_mpt_norm(const ggml_tensor *mul, Claims &c, const ggml_tensor *&x, const ggml_tensor *&gain, const LlamaMatch &m) {
+    MATCH(is_op(mul, GGML_OP_MUL) && mul->type == GGML_TYPE_F32 && !mirrored_to_host(mul));
+    const ggml_tensor *nr = mul->src[0];
+    MATCH(is_op(nr, GGML_OP_NORM) && !mirrored_to_host(nr) && nr->ne[0] == m.E && nr->ne[1] == 1 && ggml_nelements(nr) == m.E);
+    gain = mul->src[1];
+    MATCH(is_leaf(gain) && gain->type == GGML_TYPE_F32 && ggml_nelements(gain) == m.E && gain->ne[0] == m.E);
+    x = nr->src[0];
+    MATCH(x && x->type == GGML_TYPE_F32 && ggml_is_contiguous(x));
+    c.take(mul);
+    c.take(nr);
+    return true;
+}
+static bool match_mpt_decode(ggml_cgraph *gr, LlamaMatch &m) {
+    const int n = gr->n_nodes;
+    MATCH(g.opt_plan_mpt && g.opt_big && n >= 39);
+    Claims c;
+    c.index(gr);
+    auto dev_op = [&](const ggml_tensor *t, ggml_op op) { return is_op(t, op) && !mirrored_to_host(t); };
+    m.mpt = true;
+    m.N = 1;
+    m.eps = 1e-5f;  // ggml_norm's (op_norm)
+    ggml_tensor *last = gr->nodes[n - 1];
+    MATCH(is_op(last, GGML_OP_MUL_MAT) && last->type == GGML_TYPE_F32 && last->ne[1] == 1 && last->ne[2] == 1 && last->ne[3] == 1);
+    MATCH(last->backend == GGML_BACKEND_CPU && last->data && ggml_is_contiguous(last));  // the results go to the node's host data
+    m.output = last->src[0];
+    MATCH(is_leaf(m.output) && qt_of(m.output->type) >= 0);
+    m.wtype = m.output->type;
+    m.E = m.output->ne[0];
+    m.V = m.output->ne[1];
+    m.logits = last;
+    c.take(last);
+    ggml_tensor *fin = last->src[1];
+    const ggml_tensor *x = nullptr;
+    MATCH(match_mpt_norm(fin, c, x, m.norm, m));
+    m.embedding = fin;
+    {   // number of layers = length of the residual chain add(add(x, ..), ..) below the tail
+        int cnt = 0;
+        const ggml_tensor *y = x;
+        while (is_op(y, GGML_OP_ADD) && is_op(y->src[0], GGML_OP_ADD) && cnt < 4096) {
+            y = y->src[0]->src[0];
+            cnt++;
+        }
+        MATCH(cnt >= 1);
+        m.L = cnt;
+    }
+    m.F = 4 * m.E;
+    m.layers.resize(m.L);
+    for (int il = m.L - 1; il >= 0; il--) {
+        LayerW &lw = m.layers[il];
+        // x = add(inpFF, mul_mat(down_proj, gelu(mul_mat(up_proj, mul(norm(inpFF), norm_2)))))
+        MATCH(dev_op(x, GGML_OP_ADD) && ggml_nelements(x) == m.E);
+        const ggml_tensor *inpFF = x->src[0], *dn = x->src[1];
+        MATCH(dev_op(dn, GGML_OP_MUL_MAT));
+        lw.w2 = dn->src[0];
+        const ggml_tensor *ge = dn->src[1];
+        MATCH(dev_op(ge, GGML_OP_UNARY) && ge->op_params[0] == GGML_UNARY_OP_GELU);
+        const ggml_tensor *up = ge->src[0];
+        MATCH(dev_op(up, GGML_OP_MUL_MAT));
+        lw.w1 = lw.w3 = up->src[0];
+        MATCH(is_leaf(lw.w1) && is_leaf(lw.w2) && lw.w1->ne[0] == m.E && lw.w1->ne[1] == m.F && lw.w2->ne[0] == m.F && lw.w2->ne[1] == m.E);
+        c.take(x); c.take(dn); c.take(ge); c.take(up);
+        const ggml_tensor *nx = nullptr;
+        MATCH(match_mpt_norm(up->src[1], c, nx, lw.ffn_norm, m) && nx == inpFF);
+        // inpFF = add(inpSA, mul_mat(out_proj, merged))
+        MATCH(dev_op(inpFF, GGML_OP_ADD));
+        const ggml_tensor *inpSA = inpFF->src[0], *mo = inpFF->src[1];
+        MATCH(dev_op(mo, GGML_OP_MUL_MAT));
+        lw.wo = mo->src[0];
+        MATCH(is_leaf(lw.wo) && lw.wo->ne[0] == m.E && lw.wo->ne[1] == m.E);
+        const ggml_tensor *merged = mo->src[1];
+        MATCH(is_op(merged, GGML_OP_CPY) && merged->type == GGML_TYPE_F32 && merged->ne[0] == m.E && merged->ne[1] == 1 && ggml_nelements(merged) == m.E &&
+              ggml_is_contiguous(merged) && is_leaf(merged->src[1]));
+        const ggml_tensor *perm = merged->src[0];
+        MATCH(is_op(perm, GGML_OP_PERMUTE) && perm_0213(perm));
+        const ggml_tensor *kqv = perm->src[0];
+        MATCH(dev_op(kqv, GGML_OP_MUL_MAT));
+        c.take(inpFF); c.take(mo); c.take(merged); c.take(perm); c.take(kqv);
+        // V re-laid per token (never executed) and the probabilities
+        const ggml_tensor *vt = kqv->src[0], *probs = kqv->src[1];
+        MATCH(is_op(vt, GGML_OP_CPY) && vt->type == GGML_TYPE_F16 && is_leaf(vt->src[1]) && ggml_is_contiguous(vt));
+        const ggml_tensor *vp = vt->src[0];
+        MATCH(is_op(vp, GGML_OP_PERMUTE) && vp->op_params[0] == 1 && vp->op_params[1] == 2 && vp->op_params[2] == 0 && vp->op_params[3] == 3);
+        const ggml_tensor *vr = vp->src[0];
+        MATCH(is_op(vr, GGML_OP_RESHAPE));
+        const ggml_tensor *vv1 = vr->src[0];
+        MATCH(is_op(vv1, GGML_OP_VIEW) && is_leaf(vv1->src[0]) && vv1->type == GGML_TYPE_F16);
+        if (!m.memory_v) m.memory_v = vv1->src[0];
+        MATCH(vv1->src[0] == m.memory_v);
+        MATCH(dev_op(probs, GGML_OP_SOFT_MAX));
+        const ggml_tensor *mask = probs->src[0];
+        MATCH(dev_op(mask, GGML_OP_DIAG_MASK_INF));
+        const ggml_tensor *al = mask->src[0];
+        MATCH(dev_op(al, GGML_OP_ALIBI));
+        const ggml_tensor *sc = al->src[0];
+        MATCH(dev_op(sc, GGML_OP_SCALE));
+        const ggml_tensor *kq = sc->src[0], *kqs = sc->src[1];
+        MATCH(dev_op(kq, GGML_OP_MUL_MAT) && is_leaf(kqs) && kqs->type == GGML_TYPE_F32 && kqs->data && ggml_nelements(kqs) == 1);
+        const float kqsv = *(const float *)kqs->data;
+        float bias_max;
+        memcpy(&bias_max, al->op_params + 2, 4);
+        if (il == m.L - 1) {
+            m.kq_scale = kqsv;
+            m.n_past = al->op_params[0];
+            m.H = al->op_params[1];
+            m.alibi_bias_max = bias_max;
+            MATCH(m.H >= 1 && m.H <= 256 && m.E % m.H == 0 && m.n_past >= 0);
+            m.Hkv = m.H;
+            m.D = m.E / m.H;
+            m.Egqa = m.E;
+        }
+        MATCH(kqsv == m.kq_scale && al->op_params[0] == m.n_past && al->op_params[1] == m.H && bias_max == m.alibi_bias_max &&
+              mask->op_params[0] == m.n_past);
+        c.take(vt); c.take(vp); c.take(vr); c.take(vv1); c.take(probs); c.take(mask); c.take(al); c.take(sc); c.take(kq);
+        const int P = m.n_past, T = P + 1;
+        MATCH(kq->ne[0] == T && kq->ne[1] == 1 && kq->ne[2] == m.H && kq->ne[3] == 1);
+        // K = permute(reshape_3d(view_1d(memory_k)))   Q = permute(cpy(view of qkv at 0, [D, H, 1]))
+        const ggml_tensor *kp = kq->src[0], *qp = kq->src[1];
+        MATCH(is_op(kp, GGML_OP_PERMUTE) && perm_0213(kp) && is_op(qp, GGML_OP_PERMUTE) && perm_0213(qp));
+        const ggml_tensor *kr = kp->src[0];
+        MATCH(is_op(kr, GGML_OP_RESHAPE));
+        const ggml_tensor *kv1 = kr->src[0];
+        MATCH(is_op(kv1, GGML_OP_VIEW) && is_leaf(kv1->src[0]) && kv1->type == GGML_TYPE_F16);
+        if (!m.memory_k) m.memory_k = kv1->src[0];
+        MATCH(kv1->src[0] == m.memory_k && m.memory_k != m.memory_v);
+        if (m.C == 0) {  // the context: what the caches hold per layer
+            MATCH(m.L > 0 && ggml_nelements(m.memory_k) % ((int64_t)m.L * m.E) == 0 && ggml_nelements(m.memory_k) == ggml_nelements(m.memory_v));
+            m.C = ggml_nelements(m.memory_k) / ((int64_t)m.L * m.E);
+        }
+        MATCH(T <= m.C);
+        for (const ggml_tensor *r3 : {kr, vr}) MATCH(r3->ne[0] == m.D && r3->ne[1] == m.H && r3->ne[2] == T && r3->ne[3] == 1);
+        for (const ggml_tensor *v1 : {kv1, vv1}) MATCH(v1->ne[0] == (int64_t)T * m.E && ggml_nelements(v1) == (int64_t)T * m.E && v1->nb[0] == 2);
+        MATCH(view_offset(kv1, m.memory_k) == (size_t)il * m.C * m.E * 2 && view_offset(vv1, m.memory_v) == (size_t)il * m.C * m.E * 2);
+        MATCH(vt->ne[0] == T && vt->ne[1] == m.D && vt->ne[2] == m.H);
+        const ggml_tensor *qcp = qp->src[0];
+        MATCH(is_op(qcp, GGML_OP_CPY) && qcp->type == GGML_TYPE_F32 && is_leaf(qcp->src[1]) && ggml_is_contiguous(qcp) && qcp->ne[0] == m.D &&
+              qcp->ne[1] == m.H && ggml_nelements(qcp) == m.E);
+        const ggml_tensor *qv = qcp->src[0];
+        MATCH(is_op(qv, GGML_OP_VIEW) && qv->type == GGML_TYPE_F32 && ggml_nelements(qv) == m.E && qv->ne[0] == m.E && qv->nb[0] == 4);
+        const ggml_tensor *qkv = qv->src[0];
+        MATCH(dev_op(qkv, GGML_OP_MUL_MAT) && qkv->ne[0] == 3 * m.E && ggml_nelements(qkv) == 3 * m.E && view_offset(qv, qkv) == 0);
+        lw.wq = lw.wk = lw.wv = qkv->src[0];
+        MATCH(is_leaf(lw.wq) && lw.wq->ne[0] == m.E && lw.wq->ne[1] == 3 * m.E);
+        c.take(kp); c.take(qp); c.take(kr); c.take(kv1); c.take(qcp); c.take(qv); c.take(qkv);
+        const ggml_tensor *nx1 = nullptr;
+        MATCH(match_mpt_norm(qkv->src[1], c, nx1, lw.attn_norm, m) && nx1 == inpSA);
+        lw.cur = qkv;
+        x = inpSA;
+    }
+    MATCH(dev_op(x, GGML_OP_GET_ROWS));
+    m.wte = x->src[0];
+    m.embd = x->src[1];
+    MATCH(m.wte == m.output && is_leaf(m.embd) && m.embd->type == GGML_TYPE_I32 && m.embd->ne[0] == 1 && ggml_nelements(m.embd) == 1 && m.embd->data);
+    c.take(x);
+    // the K/V stores: cpy(view of qkv at E | 2E, view_1d(memory_k | memory_v) at position n_past of the layer)
+    for (int i = 0; i < n; i++) {
+        const ggml_tensor *t = gr->nodes[i];
+        if (c.claimed[i] || t->op != GGML_OP_CPY) continue;
+        const ggml_tensor *dst = t->src[1], *src = t->src[0];
+        MATCH(is_op(dst, GGML_OP_VIEW) && dst->type == GGML_TYPE_F16 && is_op(src, GGML_OP_VIEW) && src->type == GGML_TYPE_F32);
+        const bool isk = dst->src[0] == m.memory_k;
+        MATCH(isk || dst->src[0] == m.memory_v);
+        int il = -1;
+        for (int j = 0; j < m.L; j++)
+            if (m.layers[j].cur == src->src[0]) il = j;
+        MATCH(il >= 0 && !(isk ? m.layers[il].k_store : m.layers[il].v_store));
+        MATCH(ggml_nelements(src) == m.E && src->ne[0] == m.E && src->nb[0] == 4 && view_offset(src, src->src[0]) == (size_t)(isk ? 1 : 2) * m.E * 4);
+        MATCH(dst->ne[0] == m.E && ggml_nelements(dst) == m.E && dst->nb[0] == 2);
+        MATCH(view_offset(dst, dst->src[0]) == ((size_t)il * m.C + m.n_past) * m.E * 2);
+        (isk ? m.layers[il].k_store : m.layers[il].v_store) = true;
+        c.take(t); c.take(dst); c.take(src);
+    }
+    for (auto &lw : m.layers) MATCH(lw.k_store && lw.v_store);
+    MATCH(c.n == n);  // every node of the graph is accounted for
+    // the plan's kernels' own preconditions
+    MATCH(m.D % 32 == 0 && m.D <= 128 && m.E % 32 == 0 && m.E <= 8192);
+    MATCH(m.memory_k->type == GGML_TYPE_F16 && m.memory_v->type == GGML_TYPE_F16);
+    MATCH(attn_decode_lds((m.C + 7) & ~(int64_t)7, m.D) <= ATTN_DECODE_LDS_MAX);  // (k_attn_decode_alibi's arrays hold the context rounded up to 8)
+    for (auto &lw : m.layers)
+        for (int i = 0; i < LAYER_MATS; i++) MATCH(lw.at(i)->type == m.wtype && lw.at(i)->ne[2] == 1 && lw.at(i)->ne[3] == 1);
+    MATCH(big_shape(XSRC_LNORM, EPI_QKV_TM, m.E / 32, 3 * m.E).ok && big_shape(XSRC_LNORM, EPI_GELU, m.E / 32, m.F).ok &&
+          big_shape(XSRC_LNORM, EPI_STORE, m.E / 32, m.V).ok && big_shape(XSRC_F32, EPI_ADD, m.E / 32, m.E).ok &&
+          big_shape(XSRC_F32, EPI_ADD, m.F / 32, m.E).ok && m.F <= 24 * BIG_T);
+    return true;
+}
 #undef MATCH

@@ -213,7 +213,7 @@ static void tail_slots(DecodePlan *p) {
 // model.  K-quant plans, F16 plans, option big = 0 and the stages of a split keep their prologue launches.
 static bool tail_prepares(const DecodePlan *p) {
     const LlamaMatch &m = p->m;
-    return g.opt_tail_prepare && g.opt_big && !m.kquant && !m.f16w && m.N == 1 && m.wte && m.output && qt_of(m.wtype) >= 0 && p->xnext && p->kv_save[0] && p->mem_k &&
+    return g.opt_tail_prepare && g.opt_big && !m.kquant && !m.f16w && !m.mpt && m.N == 1 && m.wte && m.output && qt_of(m.wtype) >= 0 && p->xnext && p->kv_save[0] && p->mem_k &&
            p->mem_v && m.D / 2 <= 64 && m.E % 32 == 0;
 }
 // what the tail of the graph of parity q prepares: the next token's row, its table and epoch, and the cache rows the graph of parity
@@ -249,7 +249,10 @@ static DecodePlan *resolve_plan(ggml_cgraph *gr, LlamaMatch &m) {
             return p;
         }
     }
-    if (!match_llama_decode(gr, m)) return nullptr;
+    if (!match_llama_decode(gr, m)) {  // not LLaMA's graph: MPT's (option plan_mpt), or nothing for the plans
+        m = LlamaMatch{};
+        if (!match_mpt_decode(gr, m)) return nullptr;
+    }
     if (!plan_weights_resident(m)) {
         // first evaluation of a model: tok_embeddings is a leaf the caller never offloads (models/llama lib.rs:52);
         // upload the graph's leaves the way the generic executor would, then look again
@@ -374,6 +377,7 @@ static void count_token_forms(const LlamaMatch &m, int av) {
     if (av >= AV_FUSED2) g.stat_fused_heads_tokens++;
     if (m.kquant) g.stat_kplan_tokens += (uint64_t)m.N;
     if (m.out_k) g.stat_out_k_tokens += (uint64_t)m.N;
+    if (m.mpt) g.stat_mpt_plan_tokens += (uint64_t)m.N;
 }
 static bool try_decode_plan(ggml_cgraph *gr, bool defer_wait = false) {
     g.chain_plan = nullptr;  // any new graph ends the chainable state; a single-token plan run re-arms it below
@@ -420,7 +424,7 @@ static bool try_decode_plan(ggml_cgraph *gr, bool defer_wait = false) {
     // graph goes right behind it.  After a miss the guessing pauses; the last positions of the context have no next token. ----
     if (g.spec.cooldown > 0) g.spec.cooldown--;
     const bool tail = g.opt_token_tail && (g.opt_speculate_next || greedy_next) && g.spec.cooldown == 0 && use_graph && m.N == 1 && m.logits && m.wte &&
-                      m.output && m.embd && p->logits_alt && m.n_past + 2 < m.C;
+                      m.output && m.embd && p->logits_alt && m.n_past + 2 < m.C && !m.mpt;  // (an MPT plan: no token runs ahead — k_kv_row_save knows LLaMA's V layout alone)
     int tail_q = -1;  // the slot this token's results come through, if any
     if (spec_hit) {
         tail_q = hit_q;  // already enqueued behind the previous token (same plan, position, token and attention variant): only the host's part is missing
@@ -760,6 +764,7 @@ static int decode_chain(ggml_cgraph *last, int n, int32_t *out_tokens, float *la
     if (!p || g.chain_graph != last || n < 1) return -1;
     const LlamaMatch &m = p->m;
     if (m.N != 1 || !m.logits || !m.wte || m.n_past + 1 + n > m.C) return -1;
+    if (m.mpt && (smp || req)) return -1;  // an MPT plan: the greedy chain alone
     if (smp && (!g.opt_plan_sample_chain || !batch_sample_ok(*smp, 1, m.V))) return -1;
     if (req && ((req->chains[0] && !g.opt_plan_sample_chain) || !p->scols || !chain_requests_ok(*req, 1, m.V, n, n))) return -1;
     if (p->prm_ahead) {  // a token tail has moved the parameters on (and a run ahead of the caller may be in flight): back to the last evaluated token
@@ -866,6 +871,7 @@ static int decode_chain(ggml_cgraph *last, int n, int32_t *out_tokens, float *la
     p->replays += use_graph ? (uint64_t)n : 0;
     g.stat_plan_tokens += (uint64_t)n;
     if (m.out_k) g.stat_out_k_tokens += (uint64_t)n;
+    if (m.mpt) g.stat_mpt_plan_tokens += (uint64_t)n;
     g.chain_plan = nullptr;  // the caller's next evaluation re-arms it
     return 0;
 }

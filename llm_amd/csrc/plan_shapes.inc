@@ -9,6 +9,8 @@
 //   a prompt batch (plan_launch_prompt): 13 launches per layer around the matrix-core GEMMs, launched eagerly;
 //   one token each of 2..8 sessions of one model (plan_launch_batch; ggml_hip_decode_batch hands over their graphs together): the
 //   chunk's launches with a per-column position and cache.
+// One more family has a plan over the same DecodePlan and run path: MPT's single-token graph (LlamaMatch::mpt, match_mpt_decode, plan_launch_mpt:
+// five launches per layer; option plan_mpt) — decode and the greedy chain alone, everything else of it runs on the generic executor.
 // A block-format model whose output matrix alone is a K-quant (LlamaMatch::out_k: llama.cpp's "mostly Q4_0 ... Q8_0" files) takes the block
 // formats' sequences with the K plan's tail as its lm_head (plan_decode.inc plan_lm_head_k).
 // The first three and the last are captured once in a hipGraph per attention variant and replayed for the following tokens with only
@@ -66,6 +68,11 @@ struct LlamaMatch {
     bool f16w = false;    // every matrix is F16 (file type 1): the F16 plan (plan_launch_f16), decode, chunks and batched steps
     bool out_k = false;   // a block-format model (wtype = the layers' type, kquant = false) whose output matrix alone is a K-quant, as llama.cpp's quantizer writes
                           // every block-format file: every plan of the block formats, the lm_head as the K plan's launches (plan_lm_head_k; option plan_out_k)
+    // an MPT graph (plan_match.inc match_mpt_decode; option plan_mpt): the MPT plan (plan_launch_mpt), single-token decode alone.  Its four
+    // matrices per layer sit in the LLaMA names — wq = Wqkv (3 E rows), wo = out_proj, w1 = up_proj, w2 = down_proj; wk, wv and w3 name
+    // wq and w1 again so that "for each matrix" needs no second form — F = 4 E, Hkv = H, eps is ggml_norm's, and K AND V are token-major
+    bool mpt = false;
+    float alibi_bias_max = 0;
     float eps = 0, freq_base = 0, freq_scale = 0, kq_scale = 0;
     ggml_type wtype = GGML_TYPE_F32;
     const ggml_tensor *wte = nullptr, *norm = nullptr, *output = nullptr, *embd = nullptr, *memory_k = nullptr,
@@ -145,6 +152,7 @@ struct DecodePlan {
     char *pool = nullptr;
     DecParams *prm = nullptr;
     float *rope = nullptr;      // this token's RoPE (cos, sin) table, D/2 pairs (k_rope_table)
+    float *alibi = nullptr;     // MPT plan: the 256 ALiBi slopes (alibi_slopes' values, uploaded when the plan is built)
     unsigned *epoch = nullptr;  // k_qkv_attn (kernels/decode_fused.h): the token's granule tag, bumped by k_rope_table
     const void *hot = nullptr;  // 256 zero bytes that every dummy ring step of k_mmvq_big reads (BigArgs::hot)
     unsigned *ferr = nullptr;   // ... raised when an attention workgroup gave up waiting for its rows
@@ -363,7 +371,7 @@ struct FusedShape {
 };
 static FusedShape fused_qkv_shape(const LlamaMatch &m, int S = 1) {
     FusedShape s;
-    if (!g.opt_fuse_attn || !g.opt_big || m.kquant || m.f16w || m.N != 1 || m.D > 128 || m.D % 32 != 0) return s;
+    if (!g.opt_fuse_attn || !g.opt_big || m.kquant || m.f16w || m.mpt || m.N != 1 || m.D > 128 || m.D % 32 != 0) return s;
     const int H = (int)m.H * S;  // attention workgroups
     const int64_t units = (m.E + 2 * m.Egqa) / 2;
     if (H + 1 > g.num_cus) return s;
@@ -432,7 +440,7 @@ static bool attn_one_ok(const LlamaMatch &m, int att_S) {
 // fuse_heads (default 1): contexts beyond k_qkv_attn's 512-position register window get 2 / 4 attention workgroups per head inside
 // the wq|wk|wv launch instead of the separate split attention, where the chip has room for them.
 static int attn_variant(const LlamaMatch &m, const DecodePlan *p, int64_t T) {
-    if (m.N != 1) return AV_SHORT;
+    if (m.N != 1 || m.mpt) return AV_SHORT;  // (the MPT plan has the one attention: k_attn_decode_alibi over the whole context)
     const bool split_ok = (!(m.kquant || m.f16w) || attn_one_ok(m, p->att_S)) && attn_split_from_min(m.H);
     if (g.opt_fuse_heads && g.opt_attn_split == 1 && split_ok && T > FUSE_HEADS_MIN && fused_qkv_shape(m).ok) {
         const int S = (int)((T + 511) / 512);  // workgroups per head: 512 positions each

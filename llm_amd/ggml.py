@@ -257,6 +257,8 @@ PROTOTYPES.update({
                                              C.c_void_p, C.c_void_p, C.c_int]),
     "ggml_hip_debug_act_quant": (C.c_int, [C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.c_float, C.c_int64, C.c_int, C.c_void_p]),
+    "ggml_hip_debug_mpt": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_int64, C.c_void_p, C.c_void_p, C.c_int,
+                                     C.c_int, C.c_int, C.c_int64, C.c_float, C.c_void_p]),
     "ggml_hip_debug_exp_le0": (C.c_int, [C.c_void_p, C.c_void_p]),
     "ggml_hip_decode_greedy_chain": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "ggml_hip_decode_batch": (C.c_int, [C.c_void_p, C.c_int]),
