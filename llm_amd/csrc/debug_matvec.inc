@@ -109,7 +109,7 @@ int ggml_hip_debug_mat_vec_big(const struct ggml_tensor *w0, const struct ggml_t
         a.freq_scale = freq_scale;
     }
     // the launcher plan_launch_all uses (no timeline, no probe, no granules; the dealing is launch_big's)
-    const BigArgs ba{a, epi == EPI_STORE ? (float *)dy : nullptr, nullptr, 0, kv.rope, 0, nullptr, nullptr, 0, g.hot_line};
+    const BigArgs ba = big_pack(a, epi == EPI_STORE ? (float *)dy : nullptr, nullptr, 0, kv.rope, 0, nullptr, nullptr, 0, g.hot_line);
     with_qt(qt, [&](auto QT) {
         switch (epi) {
             case EPI_QKV: launch_big<CT(QT), EPI_QKV, XSRC_NORM>(ba); break;
@@ -127,7 +127,7 @@ int ggml_hip_debug_mat_vec_big(const struct ggml_tensor *w0, const struct ggml_t
         DecMmvqArgs t = a;
         t.w[1] = t.w[2] = QWeight{};
         t.dst = (float *)run.buf((size_t)M0 * 4);
-        with_qt(qt, [&](auto QT) { launch_big<CT(QT), EPI_STORE, XSRC_NORM>(BigArgs{t, (float *)dy, nullptr, 0, nullptr, 0, nullptr, nullptr, 0, g.hot_line}); });
+        with_qt(qt, [&](auto QT) { launch_big<CT(QT), EPI_STORE, XSRC_NORM>(big_pack(t, (float *)dy, nullptr, 0, nullptr, 0, nullptr, nullptr, 0, g.hot_line)); });
     }
     return debug_matvec_finish(run, out, dout, n_out, y_out, dy, (size_t)K * 4, kv);
 }

@@ -33,10 +33,12 @@ int ggml_hip_debug_mpt(int op, int flag, const float *x, const float *w, float e
         const int64_t nb = K / 32;
         BigArgs ba;
         memset(&ba, 0, sizeof(ba));
-        ba.d.xf = (const float *)run.buf((size_t)K * 4, x);
-        ba.d.xw = (const float *)run.buf((size_t)K * 4, w);
-        ba.d.eps = eps;
-        ba.d.nb = nb;
+        ba.xf = (const float *)run.buf((size_t)K * 4, x);
+        ba.xw = (const float *)run.buf((size_t)K * 4, w);
+        ba.eps = eps;
+        ba.nb = (int)nb;
+        ba.T = 1024;
+        ba.G = 1;
         char *lo = run.buf((size_t)K / 2), *hi = run.buf((size_t)K / 2), *d = run.buf((size_t)nb * 4), *sum = run.buf((size_t)nb * 4);
         launch_mpt_stage_dump(g.stream, flag != 0, &ba, lo, hi, (float *)d, (int *)sum, (size_t)((nb + 63) / 64 * 64) * 40);
         run.back(out[0], lo, (size_t)K / 2 + DEBUG_GUARD);

@@ -70,30 +70,104 @@ __device__ __forceinline__ constexpr int big_pf(int NR) {
 // wave exactly 2 of the 6144 row pairs of a 7B wq|wk|wv; with 16 waves half of them get 2 and half 1, and the
 // launch lasts as long as the workgroups with the 2s.
 
+// The launch's arguments AS THE KERNARG SEGMENT HOLDS THEM.  A workgroup cannot ask for its first byte before the scalar loads of its
+// arguments have come back, and a scalar load of a 64-byte line of the segment that no earlier load has touched is a scalar-cache miss:
+// a full dependent round trip on the critical path of every launch (DESIGN.md section 4.2 "Kernarg lines").  So what a production
+// workgroup reads before its first weight request stands together in front — lines 0 and 1 for a Q4_0 / Q4_1 launch of k_mmvq_big,
+// line 2 as well inside the fused launches — big_entry_nb() makes the FIRST batch of loads touch every one of those lines, and
+// neither blockDim nor gridDim is read (the hidden arguments are a line of their own behind the struct): T, G.  Everything cold
+// lies behind.  The host describes a launch as DecMmvqArgs (decode.h, shared with k_mmvq_dec) and packs it with big_pack().
+struct BigMat {
+    const uint8_t *qs;
+    const __half *d;
+};
+struct BigPlanes {  // the planes only some block types have
+    const uint8_t *qs2;
+    const uint32_t *qh;
+    const __half *m;
+};
 struct BigArgs {
-    DecMmvqArgs d;
-    float *y_out;  // XSRC_NORM: optional f32 copy of the normed row (final norm -> OutputRequest.embeddings)
-    long long *ts;  // optional timeline slot (ggml_hip_set_option("timeline", n)): 8 x int64 per sampled workgroup
-    int ts_wgs;     // workgroups that record: 0, G/n, 2G/n, ... (n = 4 for "timeline" = 1, else the option's value)
-    const float *rope;  // EPI_QKV: (cos, sin) of this token's RoPE angle per pair of a head, from k_rope_table
-    int probe;          // measurement only (ggml_hip_set_option("probe", n), tests/tools/launch_probe.py): 1 = return before
-                        // the first weight request, 2 = return once x is staged and the ring requested, 3 = no epilogue stores, 4 = every
-                        // other step's dots skipped, 5 = no wave reductions; 0 = normal
-    // EPI_QKV inside k_qkv_attn (kernels/decode_fused.h): the epilogue also PUBLISHES every row pair to the attention workgroups
-    // of the same launch, as one 8-byte {tag = epoch, two f16} granule per pair (index = the pair's index over wq|wk|wv); Q is
-    // not stored as f32 then (nothing else reads it).  nullptr = plain launch.
-    unsigned long long *gran;
-    const unsigned *epoch;  // device word, bumped once per token by k_rope_table: this token's tag
-    int wdeal;              // waves of a workgroup that take units (0 = all of blockDim); the rest only help staging
+    // ---- line 0: the activation, the dealing
+    const float *xf;  // XSRC_NORM / XSRC_F32 / XSRC_LNORM: the f32 activation row
+    const float *xw;  // the norm weight
+    float *dst;
+    const float *res;  // EPI_ADD: residual
     // 256 bytes that the DUMMY ring steps read (a wave's slots past its last real step): one line for the whole chip, fetched with
     // plain loads, so it sits in every CU's L1 — a dummy step costs its issue slots and nothing else (see `issue`).  nullptr = the
     // first line of the matrix's scales.
     const void *hot;
+    int nb;      // K / 32
+    int T;       // threads of the workgroup (what blockDim.x would say)
+    int G;       // mat-vec workgroups of the launch (k_mmvq_big: the grid; the fused kernels: the grid less n_attn)
+    int wdeal;   // waves of a workgroup that take units (0 = all T / 64); the rest only help staging
+    int n_attn;  // k_qkv_attn / k_qkv_attn_wo: the attention workgroups, dispatched in front of the G mat-vec ones; else 0
+    float eps;
+    // ---- line 1: the matrices.  STORE/ADD: w[0]; GATE: w[0] = w1, w[1] = w3; QKV: wq, wk, wv
+    BigMat w[3];
+    int M[3];  // rows
+    int D;     // QKV: head size (rope row length)
+    // ---- line 2: what the QKV forms read besides
+    const float *rope;  // EPI_QKV: (cos, sin) of this token's RoPE angle per pair of a head, from k_rope_table
+    const DecParams *prm;
+    const unsigned *epoch;  // device word, bumped once per token by k_rope_table: this token's tag
+    // EPI_QKV inside k_qkv_attn (kernels/decode_fused.h): the epilogue also PUBLISHES every row pair to the attention workgroups
+    // of the same launch, as one 8-byte {tag = epoch, two f16} granule per pair (index = the pair's index over wq|wk|wv); Q is
+    // not stored as f32 then (nothing else reads it).  nullptr = plain launch.
+    unsigned long long *gran;
+    __half *mem_k;  // + layer offset: K element (pos p, chan c) at p*Egqa + c
+    __half *mem_v;  // + layer offset: V element (chan c, pos p) at c*C + p
     // EPI_QKV inside k_qkv_attn, XCD-affine dealing (aff_hpl > 0): the row pairs of head h's Q / K / V go to the mat-vec workgroups
     // whose blockIdx mod 8 equals h mod 8 — the XCD head h's attention workgroup (blockIdx h) runs on — and travel through that
     // XCD's L2 (gran_store_l2).  aff_hpl = heads per XCD (n_head / 8), aff_shift = log2(D / 2).  MHA only (wk, wv as tall as wq).
     int aff_hpl, aff_shift;
+    int Egqa, C;  // (the caches' strides: 32-bit here, widened where an element's index is formed)
+    // ---- line 3 (and 8 bytes of line 4): the other block types' planes
+    BigPlanes wx[3];
+    // ---- cold: the epilogues', the measurement builds'
+    QAct x;         // XSRC_Q8: activation already re-quantized (attention output)
+    float *y_out;   // XSRC_NORM: optional f32 copy of the normed row (final norm -> OutputRequest.embeddings)
+    long long *ts;  // optional timeline slot (ggml_hip_set_option("timeline", n)): 8 x int64 per sampled workgroup
+    int ts_wgs;     // workgroups that record: 0, G/n, 2G/n, ... (n = 4 for "timeline" = 1, else the option's value)
+    int probe;      // measurement only (ggml_hip_set_option("probe", n), tests/tools/launch_probe.py): 1 = return before
+                    // the first weight request, 2 = return once x is staged and the ring requested, 3 = no epilogue stores, 4 = every
+                    // other step's dots skipped, 5 = no wave reductions; 0 = normal
+    int64_t line_pad[8];  // to whole lines: the argument behind BigArgs in a fused kernel's segment starts a line
 };
+static_assert(alignof(BigArgs) == 8 && sizeof(BigArgs) == 384, "BigArgs: six 64-byte lines of the kernarg segment");
+static_assert(offsetof(BigArgs, xf) == 0 && offsetof(BigArgs, eps) == 60, "BigArgs: line 0 = activation and dealing");
+static_assert(offsetof(BigArgs, w) == 64 && offsetof(BigArgs, D) == 124, "BigArgs: line 1 = the matrices");
+static_assert(offsetof(BigArgs, rope) == 128 && offsetof(BigArgs, C) == 188, "BigArgs: line 2 = the QKV forms' entry");
+static_assert(offsetof(BigArgs, wx) == 192 && offsetof(BigArgs, x) == 264, "BigArgs: line 3 = the other planes, cold fields behind");
+// the launch described by `a` as the kernels take it; T, G, n_attn are the launcher's (launch_big, launch_qkv_attn*, launch_big_lnorm)
+inline BigArgs big_pack(const DecMmvqArgs &a, float *y_out, long long *ts, int ts_wgs, const float *rope, int probe, unsigned long long *gran,
+                        const unsigned *epoch, int wdeal, const void *hot) {
+    BigArgs b{};
+    b.xf = a.xf; b.xw = a.xw; b.dst = a.dst; b.res = a.res; b.hot = hot; b.nb = (int)a.nb; b.eps = a.eps; b.wdeal = wdeal;
+    for (int i = 0; i < 3; i++) {
+        b.w[i] = BigMat{a.w[i].qs, a.w[i].d};
+        b.wx[i] = BigPlanes{a.w[i].qs2, a.w[i].qh, a.w[i].m};
+        b.M[i] = (int)a.w[i].M;
+    }
+    b.D = a.D; b.rope = rope; b.prm = a.prm; b.epoch = epoch; b.gran = gran; b.mem_k = a.mem_k; b.mem_v = a.mem_v;
+    b.Egqa = (int)a.Egqa; b.C = (int)a.C; b.x = a.x; b.y_out = y_out; b.ts = ts; b.ts_wgs = ts_wgs; b.probe = probe;
+    return b;
+}
+// The first batch of argument loads touches every line the workgroup will read before its first weight request: `nb`, which the
+// activation's loads need, passes through an empty instruction that names a field of each such line (and the matrices' pointers) as
+// inputs, so hipcc has to have them all by then — one round trip.  What later loads still fetch comes from lines the scalar cache
+// already holds.  (Not `asm volatile`: behind one hipcc takes every uniform load from memory — DecParams, the epoch — for clobbered and
+// fetches it with a vector load.)
+template <int QT, int EPI, int XSRC>
+__device__ __forceinline__ int big_entry_nb(const BigArgs &ba) {
+    int nb = ba.nb;
+    asm("" : "+s"(nb) : "s"(ba.hot), "s"(ba.G), "s"(ba.wdeal), "s"(ba.w[0].qs), "s"(ba.w[0].d), "s"(ba.M[0]));
+    if constexpr (EPI == EPI_GATE) asm("" : "+s"(nb) : "s"(ba.w[1].qs), "s"(ba.w[1].d));
+    if constexpr (EPI == EPI_QKV) asm("" : "+s"(nb) : "s"(ba.w[1].qs), "s"(ba.w[1].d), "s"(ba.w[2].qs), "s"(ba.w[2].d), "s"(ba.M[1]), "s"(ba.M[2]));
+    if constexpr (EPI == EPI_QKV || EPI == EPI_QKV_TM) asm("" : "+s"(nb) : "s"(ba.prm));
+    if constexpr (QT != QT_Q4_0) asm("" : "+s"(nb) : "s"(ba.wx[0].qs2));
+    if constexpr (XSRC == XSRC_Q8) asm("" : "+s"(nb) : "s"(ba.x.lo));
+    return nb;
+}
 __device__ __forceinline__ long long big_now() { return (long long)wall_clock64(); }  // 100 MHz, chip-wide
 
 // The activation's global loads, issued as the FIRST memory operations of the kernel: a wave's loads return in
@@ -108,10 +182,10 @@ struct BigX<XSRC_Q8> {
     int sum;
     __device__ __forceinline__ void load(const BigArgs &a, int nb, int tid, int T) {
         const int i = tid < nb ? tid : 0;  // nb <= T (checked by the launcher)
-        lo = a.d.x.lo[i];
-        hi = a.d.x.hi[i];
-        d = a.d.x.d[i];
-        sum = a.d.x.sum[i];
+        lo = a.x.lo[i];
+        hi = a.x.hi[i];
+        d = a.x.d[i];
+        sum = a.x.sum[i];
     }
 };
 template <>
@@ -123,7 +197,7 @@ struct BigX<XSRC_F32> {
 #pragma unroll
         for (int it = 0; it < MAXIT; it++) {
             const int i4 = it * T + tid;
-            v[it] = ((const f32x4 *)a.d.xf)[i4 < n4 ? i4 : 0];
+            v[it] = ((const f32x4 *)a.xf)[i4 < n4 ? i4 : 0];
         }
     }
 };
@@ -143,8 +217,8 @@ struct BigX<XSRC_NORM> {
         for (int it = 0; it < MAXIT; it++) {
             const int i4 = it * NT + tid;
             const int ic = i4 < n4 ? i4 : 0;
-            v[it] = ((const f32x4 *)a.d.xf)[ic];
-            w[it] = ((const f32x4 *)a.d.xw)[ic];
+            v[it] = ((const f32x4 *)a.xf)[ic];
+            w[it] = ((const f32x4 *)a.xw)[ic];
         }
     }
 };
@@ -202,7 +276,7 @@ __device__ __forceinline__ void big_stage_lnorm(const BigArgs &a, const BigX<XSR
         }
     }
     const float variance = mean_of(total(s2));
-    const float scale = 1.0f / sqrtf(variance + a.d.eps);
+    const float scale = 1.0f / sqrtf(variance + a.eps);
 #pragma unroll
     for (int it = 0; it < MAXIT; it++) {
         const int i4 = it * NT + tid;
@@ -221,7 +295,6 @@ __device__ __forceinline__ void big_stage_lnorm(const BigArgs &a, const BigX<XSR
 template <bool F16_D, int XSRC, bool YOUT = false>
 __device__ __forceinline__ void big_stage_x(const BigArgs &a, const BigX<XSRC> &xr, int nb, int nbp, int tid, int T,
                                             i32x4 *s_lo, i32x4 *s_hi, float *s_d, int *s_sum, double *s_part, f32x4 *y_keep = nullptr) {
-    const DecMmvqArgs &d = a.d;
     (void)s_part;
     for (int i = nb + tid; i < nbp; i += T) {
         s_lo[i] = i32x4{0, 0, 0, 0};
@@ -274,7 +347,7 @@ __device__ __forceinline__ void big_stage_x(const BigArgs &a, const BigX<XSRC> &
             const int n_el = nb * 32;
             const bool pow2 = (n_el & (n_el - 1)) == 0;  // uniform
             const float mean = pow2 ? (float)__builtin_ldexp(tot, -(31 - __builtin_clz((unsigned)n_el))) : (float)(tot / (double)n_el);
-            const float scale = 1.0f / sqrtf(mean + d.eps);
+            const float scale = 1.0f / sqrtf(mean + a.eps);
 #pragma unroll
             for (int it = 0; it < MAXIT; it++) {
                 const int i4 = it * NT + tid;
@@ -298,11 +371,10 @@ __device__ __forceinline__ void big_stage_x(const BigArgs &a, const BigX<XSRC> &
 
 // INSTR: the measurement build (BigArgs::probe early exits, BigArgs::ts timeline stamps), launched only while option
 // "probe" or "timeline" is set; the production instantiation (INSTR = false) carries none of those branches.
-// `bid` of `G` workgroups run the launch (blockIdx.x / gridDim.x for k_mmvq_big itself; the producer workgroups of
+// `bid` of `G` workgroups run the launch (blockIdx.x / BigArgs::G for k_mmvq_big itself; the producer workgroups of
 // k_qkv_attn pass their index among the producers).
 template <int QT, int EPI, int XSRC, bool INSTR>
 __device__ __forceinline__ void big_body(const BigArgs &ba, const int bid, const int G) {
-    const DecMmvqArgs &a = ba.d;
     const int probe = INSTR ? ba.probe : 0;
     long long *const ts = INSTR ? ba.ts : nullptr;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -317,7 +389,7 @@ __device__ __forceinline__ void big_body(const BigArgs &ba, const int bid, const
     constexpr int PF0 = PF < BIG_PF0 ? PF : BIG_PF0;  // steps requested before x is staged (see step 2)
     // all index arithmetic is 32-bit (rows <= 2^17, blocks per matrix < 2^27): 64-bit divides and multiplies in
     // the prologue cost ~1 us of VALU time per launch
-    const int nb = (int)a.nb;
+    const int nb = big_entry_nb<QT, EPI, XSRC>(ba);
     const int nbl = (nb + 63) >> 6;
     const int nbp = nbl * 64;
     i32x4 *s_lo = (i32x4 *)smem;
@@ -325,7 +397,7 @@ __device__ __forceinline__ void big_body(const BigArgs &ba, const int bid, const
     float *s_d = (float *)(s_hi + nbp);
     int *s_sum = (int *)(s_d + nbp);
     const int tid = threadIdx.x, lane = tid & 63;
-    const int T = (int)blockDim.x;
+    const int T = ba.T;
     const int W = ba.wdeal > 0 ? ba.wdeal : T >> 6;  // waves per workgroup that take units: chosen per launch (launch_big)
     // wave-uniform values must be uniform FOR THE COMPILER too (scalar registers, scalar selects of the matrix
     // pointers): a kernarg array indexed by a "divergent" segment id is fetched with vector loads, and waiting for
@@ -337,29 +409,29 @@ __device__ __forceinline__ void big_body(const BigArgs &ba, const int bid, const
     int n_past = 0, store_at = 0;
     unsigned epoch = 0;
     if constexpr (EPI == EPI_QKV) {
-        n_past = a.prm->n_past;
-        store_at = a.prm->store_at;
+        n_past = ba.prm->n_past;
+        store_at = ba.prm->store_at;
         if (ba.gran) epoch = *ba.epoch;
     }
     if constexpr (EPI == EPI_QKV_TM) {
-        n_past = a.prm->n_past;
-        store_at = a.prm->store_at;
+        n_past = ba.prm->n_past;
+        store_at = ba.prm->store_at;
     }
     BigX<XSRC> xr;
     xr.load(ba, nb, tid, T);
-    const uint8_t *hotp = ba.hot ? (const uint8_t *)ba.hot : (const uint8_t *)a.w[0].d;
+    const uint8_t *hotp = ba.hot ? (const uint8_t *)ba.hot : (const uint8_t *)ba.w[0].d;
     const unsigned warm_v = *(const unsigned *)hotp;  // every wave touches the dummies' line with a plain load at entry: it stays cached
     // EPI_QKV: the last two waves fetch the token's RoPE table (k_rope_table); every wave issues the load so that all
     // load queues keep one compile-time shape
     f32x2 rope_pre = {0.0f, 0.0f};
     if constexpr (EPI == EPI_QKV) {
         const int kk = tid - (T - 128);
-        rope_pre = ((const f32x2 *)ba.rope)[(kk >= 0 && kk < (a.D >> 1)) ? kk : 0];
+        rope_pre = ((const f32x2 *)ba.rope)[(kk >= 0 && kk < (ba.D >> 1)) ? kk : 0];
     }
 
     // this wave's units: ((i * G + g) * 16 + wave), i < nu — at any moment the G workgroups together stream ONE
     // contiguous window of G*16 units of the matrix.  Lane i of the wave owns unit i's epilogue.
-    const int M0 = (int)a.w[0].M, M1 = EPI == EPI_QKV ? (int)a.w[1].M : 0, M2 = EPI == EPI_QKV ? (int)a.w[2].M : 0;
+    const int M0 = ba.M[0], M1 = EPI == EPI_QKV ? ba.M[1] : 0, M2 = EPI == EPI_QKV ? ba.M[2] : 0;
     const int Utot = (M0 + M1 + M2) / RU;
     // wave-major within a round: the units of the last, partial round go to waves 0..k of EVERY workgroup, so all CUs
     // stream the same number of rows (11008 w1|w3 rows: 43 per CU instead of 45 on 222 CUs and 30 on 34)
@@ -387,7 +459,7 @@ __device__ __forceinline__ void big_body(const BigArgs &ba, const int bid, const
     float res_pre = 0.0f;
     if constexpr (EPI == EPI_ADD) {
         const int m = u_first + u_stride * lane;
-        res_pre = a.res[(lane < nu && m < Utot) ? m : 0];
+        res_pre = ba.res[(lane < nu && m < Utot) ? m : 0];
     }
 
     // unit -> (matrix, first row)
@@ -421,19 +493,19 @@ __device__ __forceinline__ void big_body(const BigArgs &ba, const int bid, const
         resolve(i, sg, m0);
 #pragma unroll
         for (int k = 0; k < NR; k++) {
-            const uint8_t *qs = a.w[0].qs, *qs2 = a.w[0].qs2;
-            const uint32_t *qh = a.w[0].qh;
-            const __half *wd = a.w[0].d, *wm = a.w[0].m;
+            const uint8_t *qs = ba.w[0].qs, *qs2 = ba.wx[0].qs2;
+            const uint32_t *qh = ba.wx[0].qh;
+            const __half *wd = ba.w[0].d, *wm = ba.wx[0].m;
             if constexpr (EPI == EPI_GATE) {
                 if (k == 1) {
-                    qs = a.w[1].qs; qs2 = a.w[1].qs2; qh = a.w[1].qh; wd = a.w[1].d; wm = a.w[1].m;
+                    qs = ba.w[1].qs; qs2 = ba.wx[1].qs2; qh = ba.wx[1].qh; wd = ba.w[1].d; wm = ba.wx[1].m;
                 }
             } else if constexpr (EPI == EPI_QKV) {  // scalar selects (sg is wave-uniform)
-                qs = sg == 0 ? a.w[0].qs : sg == 1 ? a.w[1].qs : a.w[2].qs;
-                qs2 = sg == 0 ? a.w[0].qs2 : sg == 1 ? a.w[1].qs2 : a.w[2].qs2;
-                qh = sg == 0 ? a.w[0].qh : sg == 1 ? a.w[1].qh : a.w[2].qh;
-                wd = sg == 0 ? a.w[0].d : sg == 1 ? a.w[1].d : a.w[2].d;
-                wm = sg == 0 ? a.w[0].m : sg == 1 ? a.w[1].m : a.w[2].m;
+                qs = sg == 0 ? ba.w[0].qs : sg == 1 ? ba.w[1].qs : ba.w[2].qs;
+                qs2 = sg == 0 ? ba.wx[0].qs2 : sg == 1 ? ba.wx[1].qs2 : ba.wx[2].qs2;
+                qh = sg == 0 ? ba.wx[0].qh : sg == 1 ? ba.wx[1].qh : ba.wx[2].qh;
+                wd = sg == 0 ? ba.w[0].d : sg == 1 ? ba.w[1].d : ba.w[2].d;
+                wm = sg == 0 ? ba.wx[0].m : sg == 1 ? ba.wx[1].m : ba.wx[2].m;
             }
             const size_t ro = (size_t)(uint32_t)(m0 + (EPI == EPI_QKV ? k : 0)) * (uint32_t)nb;  // first block of the row
             ub_qs[k] = qs + ro * 16;
@@ -490,7 +562,7 @@ __device__ __forceinline__ void big_body(const BigArgs &ba, const int bid, const
 
     // ---- 3. norm / re-quantization of x into LDS; meanwhile the last two waves (not stagers) park the RoPE table
     if constexpr (EPI == EPI_QKV) {
-        if (tid >= T - 128 && tid - (T - 128) < (a.D >> 1)) {
+        if (tid >= T - 128 && tid - (T - 128) < (ba.D >> 1)) {
             const int kk = tid - (T - 128);
             s_rope[2 * kk] = rope_pre[0];
             s_rope[2 * kk + 1] = rope_pre[1];
@@ -576,44 +648,44 @@ __device__ __forceinline__ void big_body(const BigArgs &ba, const int bid, const
         int sg, m0;
         resolve(lane, sg, m0);
         if constexpr (EPI == EPI_STORE) {
-            a.dst[m0] = myv[0];
+            ba.dst[m0] = myv[0];
         } else if constexpr (EPI == EPI_ADD) {
-            a.dst[m0] = myv[0] + res_pre;
+            ba.dst[m0] = myv[0] + res_pre;
         } else if constexpr (EPI == EPI_GATE) {
-            a.dst[m0] = silu_table(myv[0]) * myv[1];
+            ba.dst[m0] = silu_table(myv[0]) * myv[1];
         } else if constexpr (EPI == EPI_GELU) {
-            a.dst[m0] = gelu_table(myv[0]);
+            ba.dst[m0] = gelu_table(myv[0]);
         } else if constexpr (EPI == EPI_QKV_TM) {  // row m0 of [Q | K | V], Egqa rows each: Q as f32, K and V as f16 (RNE, ggml's cpy) at position n_past
-            const int Eq = (int)a.Egqa;
+            const int Eq = ba.Egqa;
             const int p = store_at ? store_at : n_past;  // (store_at: a roofline replay parks its rows, see DecParams)
             if (m0 < Eq)
-                a.dst[m0] = myv[0];
+                ba.dst[m0] = myv[0];
             else if (m0 < 2 * Eq)
-                a.mem_k[(int64_t)p * Eq + (m0 - Eq)] = __float2half_rn(myv[0]);
+                ba.mem_k[(int64_t)p * Eq + (m0 - Eq)] = __float2half_rn(myv[0]);
             else
-                a.mem_v[(int64_t)p * Eq + (m0 - 2 * Eq)] = __float2half_rn(myv[0]);
+                ba.mem_v[(int64_t)p * Eq + (m0 - 2 * Eq)] = __float2half_rn(myv[0]);
         } else {  // EPI_QKV, see k_mmvq_dec
             const int p = store_at ? store_at : n_past;
             __half h0, h1;  // the pair as f16: what the K/V cache holds, and what ggml's F16 mat-mul makes of Q (src1 -> f16)
             if (sg == 2) {
                 h0 = __float2half_rn(myv[0]);
                 h1 = __float2half_rn(myv[1]);
-                a.mem_v[(int64_t)m0 * a.C + p] = h0;
-                a.mem_v[(int64_t)(m0 + 1) * a.C + p] = h1;
+                ba.mem_v[(int64_t)m0 * ba.C + p] = h0;
+                ba.mem_v[(int64_t)(m0 + 1) * ba.C + p] = h1;
             } else {
-                const int kk = (m0 % a.D) >> 1;
+                const int kk = (m0 % ba.D) >> 1;
                 const float c = s_rope[2 * kk], sn = s_rope[2 * kk + 1];
                 const float r0 = myv[0] * c - myv[1] * sn, r1 = myv[0] * sn + myv[1] * c;
                 h0 = __float2half_rn(r0);
                 h1 = __float2half_rn(r1);
                 if (sg == 0) {
                     if (!ba.gran) {
-                        a.dst[m0] = r0;
-                        a.dst[m0 + 1] = r1;
+                        ba.dst[m0] = r0;
+                        ba.dst[m0 + 1] = r1;
                     }
                 } else {
-                    a.mem_k[(int64_t)p * a.Egqa + m0] = h0;
-                    a.mem_k[(int64_t)p * a.Egqa + m0 + 1] = h1;
+                    ba.mem_k[(int64_t)p * ba.Egqa + m0] = h0;
+                    ba.mem_k[(int64_t)p * ba.Egqa + m0 + 1] = h1;
                 }
             }
             if (ba.gran) {  // one aligned 8-byte agent-scope (write-through) store: the data is the flag
@@ -635,7 +707,7 @@ __device__ __forceinline__ void big_body(const BigArgs &ba, const int bid, const
             }
         }
     }
-    if (warm_v == 0x7fc0dead && nb < 0) a.dst[0] = 0.0f;  // (never: keeps the warm-up load alive; its wait falls here, long after it landed)
+    if (warm_v == 0x7fc0dead && nb < 0) ba.dst[0] = 0.0f;  // (never: keeps the warm-up load alive; its wait falls here, long after it landed)
     if (ts && wave == 0 && lane == 0) {
         const int q = G / ba.ts_wgs;
         if (q > 0 && bid % q == 0 && bid / q < ba.ts_wgs) {
@@ -647,5 +719,5 @@ __device__ __forceinline__ void big_body(const BigArgs &ba, const int bid, const
 }
 template <int QT, int EPI, int XSRC, bool INSTR = false>
 __global__ void __launch_bounds__(BIG_T) k_mmvq_big(const BigArgs ba) {
-    big_body<QT, EPI, XSRC, INSTR>(ba, (int)blockIdx.x, (int)gridDim.x);
+    big_body<QT, EPI, XSRC, INSTR>(ba, (int)blockIdx.x, ba.G);
 }

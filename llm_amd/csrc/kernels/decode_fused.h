@@ -49,19 +49,18 @@ struct FusedAttnArgs {
     // WO form (k_qkv_attn<.., WO = true>): the heads' re-quantized outputs are PUBLISHED to the mat-vec workgroups of the same
     // launch instead of stored for a following wo launch: this layer's E/32 x OGRAN granules (publish_head_q8 below)
     unsigned long long *ogran;
-    // Eight unused bytes, for where the next field lands in the KERNARG segment.  Every workgroup of k_qkv_attn_wo opens with two
-    // dependent round trips of scalar loads of its arguments, on the launch's critical path.  `ogran` is the last word of a 64-byte
-    // line of the segment (BigArgs = 448 bytes, ogran at 184); with out_f32 directly behind it hipcc fetched the two as ONE 16-byte
-    // load across the line boundary, in the second round trip — the only load there to touch a line the first round trip had not
-    // brought in.  With the pad it loads ogran alone.  Measured, this field and nothing else: the mat-vec workgroups finish wq|wk|wv
-    // 0.3 us and the next launch enters 0.5-0.9 us earlier, +1.25 % tokens/s at 7B (DESIGN.md section 4.2 "kernarg lines",
-    // profiles/r12_kernarg_line_headline.txt); that the straddling load is a scalar-cache miss is read from the ISA, not measured.
+    // Eight unused bytes, for where the next field lands in the KERNARG segment (see BigArgs, kernels/decode_big.h, for why lines
+    // matter).  BigArgs is six whole lines (384 bytes), so `ogran` (offset 184 here) is the last word of a 64-byte line of the segment
+    // of k_qkv_attn_wo; with out_f32 directly behind it hipcc fetched the two as ONE 16-byte scalar load across the line boundary.
+    // With the pad it loads ogran alone, in the launch's first batch of loads, next to epoch from the same line.  Measured in round 12,
+    // when that straddling load stood in the second dependent round trip of every workgroup: +1.25 % tokens/s at 7B (DESIGN.md
+    // section 4.2 "kernarg lines", profiles/r12_kernarg_line_headline.txt).
     unsigned long long kernarg_line_pad;
     // K plan (k_qkv_attn_k, kernels/kquant_big.h): the merged heads as f32 [n_head * D] instead of Q8_0 blocks (wo stages its own
     // Q8_K row from them); nullptr = the Q8_0 forms above
     float *out_f32;
 };
-// (whoever moves a field of BigArgs or FusedAttnArgs: look at the kernel's first s_load instructions again, tests/tools/disasm.py)
+// (whoever moves a field of BigArgs or FusedAttnArgs: tests/test_kernarg_entry.py reads the kernels' first s_load instructions again)
 static_assert((sizeof(BigArgs) + offsetof(FusedAttnArgs, kernarg_line_pad)) % 64 == 0, "FusedAttnArgs::ogran no longer ends a 64-byte line of the kernarg segment of k_qkv_attn_wo");
 
 // ---------------------------------------------------------------------------------------------------
@@ -750,31 +749,42 @@ __device__ __forceinline__ void attn_consumer_split(const FusedAttnArgs &f, cons
     publish_head_q8<F16_D>(f, h, v, nblk, l, b, epoch);
 }
 
+// the load that decides attention or mat-vec brings lines 1 and 2 of the entry block along: the mat-vec workgroups' own first batch
+// (big_entry_nb) then finds all three lines in the scalar cache
+__device__ __forceinline__ int fused_entry_attn(const BigArgs &ba) {
+    int A = ba.n_attn;
+    asm("" : "+s"(A) : "s"(ba.M[0]), "s"(ba.prm));
+    return A;
+}
 template <int QT, bool INSTR = false>
 __global__ void __launch_bounds__(1024) k_qkv_attn(const BigArgs ba, const FusedAttnArgs fa) {
     constexpr bool F16_D = QT == QT_Q4_0 || QT == QT_Q5_0 || QT == QT_Q8_0;
-    const int H = fa.n_head, A = H * (fa.S > 1 ? fa.S : 1);  // attention workgroups (dispatched first)
+    // attention workgroups (dispatched first): n_head x S of them, counted by the host (BigArgs::n_attn) so that the branch is decided
+    // from the very line big_body opens with; its first batch of loads touches the rest of the entry block (see BigArgs)
+    const int A = fused_entry_attn(ba);
     if ((int)blockIdx.x < A) {
+        const int H = fa.n_head;
         if (fa.S > 1)
             attn_consumer_split<F16_D>(fa, (int)blockIdx.x % H, (int)blockIdx.x / H);
         else
             attn_consumer<F16_D>(fa, (int)blockIdx.x);
         return;
     }
-    big_body<QT, EPI_QKV, XSRC_NORM, INSTR>(ba, (int)blockIdx.x - A, (int)gridDim.x - A);
+    big_body<QT, EPI_QKV, XSRC_NORM, INSTR>(ba, (int)blockIdx.x - A, ba.G);
 }
 // the WO form: wq|wk|wv + attention + wo + residual in one launch (see wo_tail)
 template <int QT, int NBLT>
 __global__ void __launch_bounds__(1024) k_qkv_attn_wo(const BigArgs ba, const FusedAttnArgs fa, const WoTailArgs wt) {
     constexpr bool F16_D = QT == QT_Q4_0 || QT == QT_Q5_0 || QT == QT_Q8_0;
-    const int H = fa.n_head, A = H * (fa.S > 1 ? fa.S : 1);
+    const int A = fused_entry_attn(ba);  // (as k_qkv_attn)
     if ((int)blockIdx.x < A) {
+        const int H = fa.n_head;
         if (fa.S > 1)
             attn_consumer_split<F16_D>(fa, (int)blockIdx.x % H, (int)blockIdx.x / H);
         else
             attn_consumer<F16_D>(fa, (int)blockIdx.x);
         return;
     }
-    big_body<QT, EPI_QKV, XSRC_NORM, false>(ba, (int)blockIdx.x - A, (int)gridDim.x - A);
-    wo_tail<QT, NBLT>(wt, fa, (int)blockIdx.x - A, (int)gridDim.x - A);
+    big_body<QT, EPI_QKV, XSRC_NORM, false>(ba, (int)blockIdx.x - A, ba.G);
+    wo_tail<QT, NBLT>(wt, fa, (int)blockIdx.x - A, ba.G);
 }

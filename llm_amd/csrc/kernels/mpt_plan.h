@@ -146,7 +146,7 @@ template <bool F16_D>
 __global__ void __launch_bounds__(1024) k_lnorm_stage_dump(const BigArgs ba, i32x4 *lo, i32x4 *hi, float *d, int *sum) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     __shared__ double s_part[16];
-    const int nb = (int)ba.d.nb, nbp = ((nb + 63) >> 6) * 64, tid = threadIdx.x;
+    const int nb = ba.nb, nbp = ((nb + 63) >> 6) * 64, tid = threadIdx.x;
     i32x4 *s_lo = (i32x4 *)smem;
     i32x4 *s_hi = s_lo + nbp;
     float *s_d = (float *)(s_hi + nbp);

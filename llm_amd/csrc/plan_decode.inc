@@ -52,9 +52,9 @@ static void launch_dec(const DecMmvqArgs &a, int nwg) {
 }
 template <int QT, int EPI, int XSRC>
 static void launch_big(const BigArgs &a) {
-    const int64_t Mtot = a.d.w[0].M + (EPI == EPI_QKV ? a.d.w[1].M + a.d.w[2].M : 0);
+    const int64_t Mtot = a.M[0] + (EPI == EPI_QKV ? a.M[1] + a.M[2] : 0);
     const int64_t units = Mtot / (EPI == EPI_QKV ? 2 : 1);
-    const BigShape sh = big_shape(XSRC, EPI, a.d.nb, units);
+    const BigShape sh = big_shape(XSRC, EPI, a.nb, units);
     if (!sh.ok) {
         fprintf(stderr, "ggml-hip: k_mmvq_big: %lld units over %d x %d waves exceed 64 per wave\n", (long long)units, sh.G, sh.W);
         abort();
@@ -66,19 +66,31 @@ static void launch_big(const BigArgs &a) {
         threads = BigX<XSRC_NORM>::NT;
         b.wdeal = sh.W;
     }
+    b.T = threads;  // the kernel reads neither blockDim nor gridDim (BigArgs: the entry block)
+    b.G = sh.G;
     with_bool(a.probe || a.ts, [&](auto INSTR) {  // true: measurement build (tests/tools/launch_probe.py, timeline.py)
         hipLaunchKernelGGL((k_mmvq_big<QT, EPI, XSRC, CT(INSTR)>), dim3(sh.G), dim3(threads), sh.lds, g.stream, b);
     });
 }
+// the mat-vec workgroups' view of a fused launch of sh.G workgroups: the attention workgroups in front (n_head x S), themselves behind
+static BigArgs fused_big_args(const BigArgs &a, const FusedAttnArgs &fa, const FusedShape &sh) {
+    BigArgs b = a;
+    b.T = 1024;
+    b.n_attn = fa.n_head * (fa.S > 1 ? fa.S : 1);
+    b.G = sh.G - b.n_attn;
+    return b;
+}
 template <int QT>
-static void launch_qkv_attn(const BigArgs &ba, const FusedAttnArgs &fa, const FusedShape &sh, size_t lds) {
+static void launch_qkv_attn(const BigArgs &a, const FusedAttnArgs &fa, const FusedShape &sh, size_t lds) {
+    const BigArgs ba = fused_big_args(a, fa, sh);
     with_bool(ba.probe || ba.ts, [&](auto INSTR) {
         lds_opt_in<k_qkv_attn<QT, CT(INSTR)>>(lds, ATTN_DECODE_LDS_MAX);  // (a context whose score rows exceed the default)
         hipLaunchKernelGGL((k_qkv_attn<QT, CT(INSTR)>), dim3(sh.G), dim3(1024), lds, g.stream, ba, fa);
     });
 }
 template <int QT>
-static void launch_qkv_attn_wo(const BigArgs &ba, const FusedAttnArgs &fa, const WoTailArgs &wt, const FusedShape &sh, size_t lds) {
+static void launch_qkv_attn_wo(const BigArgs &a, const FusedAttnArgs &fa, const WoTailArgs &wt, const FusedShape &sh, size_t lds) {
+    const BigArgs ba = fused_big_args(a, fa, sh);
     const bool two = (wt.w.nb + 63) / 64 <= 2;  // blocks of a row per lane: 2 steps up to 4096-wide rows, else up to 4
     with_bool(two, [&](auto TWO) {
         constexpr int STEPS = CT(TWO) ? 2 : 4;
@@ -241,7 +253,7 @@ static void plan_launch_all(DecodePlan *p, int av, LaunchCtx cx) {
         cx.mmvq(kind, bytes, [&] {
             with_qt(qt, [&](auto QT) {
                 if (big)
-                    launch_big<CT(QT), CT(EPI), CT(XSRC)>(BigArgs{a, y_out, cx.next_ts(), g.timeline_wgs, rope, g.opt_probe, nullptr, nullptr, 0, p->hot});
+                    launch_big<CT(QT), CT(EPI), CT(XSRC)>(big_pack(a, y_out, cx.next_ts(), g.timeline_wgs, rope, g.opt_probe, nullptr, nullptr, 0, p->hot));
                 else
                     fuse_x ? launch_dec<CT(QT), CT(EPI), CT(XDEC)>(a, nwg) : launch_dec<CT(QT), CT(EPI), XSRC_Q8>(a, nwg);
             });
@@ -306,7 +318,7 @@ static void plan_launch_all(DecodePlan *p, int av, LaunchCtx cx) {
             if (fsh.ok) {  // the attention workgroups ride in the same launch; no k_attn_decode below
                 const double att_bytes = (double)(m.n_past + 1) * m.Egqa * 4.0 + m.E * 9.0;
                 cx.mmvq(0, qkv_bytes + att_bytes + (fuse_wo ? wo_bytes : 0.0), [&] {
-                    BigArgs ba{a, nullptr, cx.next_ts(), g.timeline_wgs, p->rope, g.opt_probe, p->gran_at(il), p->epoch, fsh.W, p->hot};
+                    BigArgs ba = big_pack(a, nullptr, cx.next_ts(), g.timeline_wgs, p->rope, g.opt_probe, p->gran_at(il), p->epoch, fsh.W, p->hot);
                     FusedAttnArgs fa = fused_attn_args(p, il, fsh.S, attn_decode_rows(m.C, 1, m.H));
                     if (fsh.affine) {
                         ba.aff_hpl = (int)(m.H / 8);
@@ -798,10 +810,12 @@ static void plan_launch_f16(DecodePlan *p, int av, LaunchCtx cx, bool batch = fa
 // 2 up_proj, 3 down_proj, 4 lm_head).
 // ---------------------------------------------------------------------------------------------------
 static void launch_big_lnorm(int qt, int epi, const BigArgs &a) {
-    const BigShape sh = big_shape(XSRC_LNORM, epi, a.d.nb, a.d.w[0].M);
-    if (!sh.ok) die("MPT plan: a launch the matcher's preconditions exclude (%lld rows)", (long long)a.d.w[0].M);
+    const BigShape sh = big_shape(XSRC_LNORM, epi, a.nb, a.M[0]);
+    if (!sh.ok) die("MPT plan: a launch the matcher's preconditions exclude (%lld rows)", (long long)a.M[0]);
     BigArgs b = a;
     b.wdeal = sh.W;  // all 16 waves stage the norm, W of them take rows (as launch_big does for XSRC_NORM)
+    b.T = BigX<XSRC_NORM>::NT;
+    b.G = sh.G;
     if (launch_mpt_big(g.stream, qt, epi, &b, sh.G, sh.lds)) die("MPT plan: no k_mmvq_big instantiation for type %d, epilogue %d", qt, epi);
 }
 static void plan_launch_mpt(DecodePlan *p, LaunchCtx cx) {
@@ -811,7 +825,7 @@ static void plan_launch_mpt(DecodePlan *p, LaunchCtx cx) {
     const double bb = (double)blk_bytes(qt);
     const int64_t Clds = (m.C + 7) & ~(int64_t)7;
     auto big_args = [&](const DecMmvqArgs &a, float *y_out) {
-        return BigArgs{a, y_out, nullptr, 0, nullptr, 0, nullptr, nullptr, 0, p->hot};  // (no timeline, no probe: the production instantiations)
+        return big_pack(a, y_out, nullptr, 0, nullptr, 0, nullptr, nullptr, 0, p->hot);  // (no timeline, no probe: the production instantiations)
     };
     auto residual = [&](int kind, const QWeight &w, const float *xf, int64_t nb, const float *res, float *dst) {
         DecMmvqArgs a;
