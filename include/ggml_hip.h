@@ -919,6 +919,20 @@ GGML_API int ggml_hip_debug_act_quant(int kind, int flags, int64_t rows, int64_t
  * Every output is followed by 256 guard bytes (0xFF before the launch).  0, or -1 for what no call site launches. */
 GGML_API int ggml_hip_debug_mpt(int op, int flag, const float *x, const float *w, float eps, int64_t K, const uint16_t *mem_k,
                                 const uint16_t *mem_v, int H, int D, int n_past, int64_t C, float scale, void *const *out);
+/* The MPT prompt plan (option plan_mpt_prompt, GGML_HIP_PLAN_MPT_PROMPT, default 0; independent of plan_mpt): an evaluation of mmq_min
+ * tokens and more of an MPT graph with block-format weights, f16 caches and head size 32 / 64 / 128, every node offloaded, runs as nine
+ * launches per layer (llm_amd/csrc/plan_mpt_prompt.inc).  Counter mpt_prompt_tokens: its tokens; they count in prompt_plan_tokens too
+ * and never in generic_graphs.  What the matcher declines runs on the node-by-node executor with nothing executed by the plan.
+ * Test hook of its kernels (llm_amd/csrc/kernels/mpt_prompt.h), each alone on host arrays.  what 0: the LayerNorm operand — x [N][K],
+ * x2 (nullable second partial), r (nullable residual: out[1] = x (+ x2) + r, [N][K] f32), the gain w [K], eps; out[0] = the f16 operand
+ * [N][K] in the GEMM's k order; flag 1 = Q8_0's scale (after its f16 round trip), 0 = Q8_1's.  what 1: the GELU operand — x [N][K], x2;
+ * out[0] likewise.  what 2: the ALiBi prompt attention — x = the Wqkv product [N][3*H*D] (x2: its second partial), w = the slopes [H],
+ * mem_k / mem_v [C][H*D] f16 token-major, queries at n_past .. n_past + N - 1, scale; out[0] = the merged heads [N][H*D], f32 (flag 0) or
+ * out_proj's f16 operand (flag 1: Q8_1's scale, 2: Q8_0's).  Every output is followed by 256 guard bytes (0xFF before the launch).  0,
+ * or -1 for what no call site launches (a T = n_past + N behind the attention's LDS fit included). */
+GGML_API int ggml_hip_debug_mpt_prompt(int what, int flag, const float *x, const float *x2, const float *r, const float *w, float eps, int64_t K,
+                                       int N, const uint16_t *mem_k, const uint16_t *mem_v, int H, int D, int n_past, int64_t C, float scale,
+                                       void *const *out);
 /* Extension (layer split inside one process): slot `slot` enqueues on slot `with_slot`'s stream (with_slot < 0: on its own again).
  * Only for slots of ONE physical GPU whose work never overlaps — the stages of one split session: a wait on another queue's event
  * costs tens of microseconds per stage boundary on this runtime, the same wait inside one queue nothing.  1 = now shared, 0 = not

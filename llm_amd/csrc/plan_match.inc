@@ -391,7 +391,8 @@ static bool match_llama_decode(ggml_cgraph *gr, LlamaMatch &m) {
 
 // ---------------------------------------------------------------------------------------------------
 // MPT (crates/models/mpt/src/lib.rs:93-259 as llm_amd/mpt.py builds it with every node offloaded): the single-token graph, for the MPT
-// plan (plan_decode.inc plan_launch_mpt; option plan_mpt).  Per layer, from the residual x:
+// plan (plan_decode.inc plan_launch_mpt; option plan_mpt), and the same walk at N rows for the MPT prompt plan (plan_mpt_prompt.inc
+// plan_launch_mpt_prompt; option plan_mpt_prompt, N >= mmq_min: LlamaMatch::prompt).  Per layer, from the residual x ([E, N]):
 //   cur = mul(norm(x), norm_1) -> qkv = mul_mat(Wqkv, cur) -> views at 0, E, 2E -> cpy(K view, memory_k row) | cpy(V view, memory_v row)
 //   q = permute(cpy(Q view, [D, H, 1])) ; k = permute(reshape_3d(view_1d(memory_k)))            -> kq = mul_mat(k, q)
 //   soft_max(diag_mask_inf(alibi(scale(kq))))  ; vt = cpy(permute(reshape_3d(view_1d(memory_v)), 1, 2, 0, 3), [T, D, H] f16)
@@ -404,7 +405,7 @@ static bool match_llama_decode(ggml_cgraph *gr, LlamaMatch &m) {
 static bool match_mpt_norm(const ggml_tensor *mul, Claims &c, const ggml_tensor *&x, const ggml_tensor *&gain, const LlamaMatch &m) {
     MATCH(is_op(mul, GGML_OP_MUL) && mul->type == GGML_TYPE_F32 && !mirrored_to_host(mul));
     const ggml_tensor *nr = mul->src[0];
-    MATCH(is_op(nr, GGML_OP_NORM) && !mirrored_to_host(nr) && nr->ne[0] == m.E && nr->ne[1] == 1 && ggml_nelements(nr) == m.E);
+    MATCH(is_op(nr, GGML_OP_NORM) && !mirrored_to_host(nr) && nr->ne[0] == m.E && nr->ne[1] == m.N && ggml_nelements(nr) == m.N * m.E);
     gain = mul->src[1];
     MATCH(is_leaf(gain) && gain->type == GGML_TYPE_F32 && ggml_nelements(gain) == m.E && gain->ne[0] == m.E);
     x = nr->src[0];
@@ -415,15 +416,23 @@ static bool match_mpt_norm(const ggml_tensor *mul, Claims &c, const ggml_tensor 
 }
 static bool match_mpt_decode(ggml_cgraph *gr, LlamaMatch &m) {
     const int n = gr->n_nodes;
-    MATCH(g.opt_plan_mpt && g.opt_big && n >= 39);
+    MATCH(n >= 39);
     Claims c;
     c.index(gr);
     auto dev_op = [&](const ggml_tensor *t, ggml_op op) { return is_op(t, op) && !mirrored_to_host(t); };
     m.mpt = true;
-    m.N = 1;
     m.eps = 1e-5f;  // ggml_norm's (op_norm)
     ggml_tensor *last = gr->nodes[n - 1];
-    MATCH(is_op(last, GGML_OP_MUL_MAT) && last->type == GGML_TYPE_F32 && last->ne[1] == 1 && last->ne[2] == 1 && last->ne[3] == 1);
+    MATCH(is_op(last, GGML_OP_MUL_MAT) && last->type == GGML_TYPE_F32 && last->ne[1] >= 1 && last->ne[1] <= PROMPT_PLAN_MAX && last->ne[2] == 1 && last->ne[3] == 1);
+    m.N = (int)last->ne[1];
+    // one token: the MPT plan; a batch of mmq_min tokens and more (the LLaMA prompt plan's rule): the MPT prompt plan, on the default f16
+    // GEMM path only; the chunks between have no plan
+    m.prompt = m.N > 1;
+    if (m.prompt)
+        MATCH(g.opt_plan_mpt_prompt && g.opt_plan_prompt && !g.opt_mmq_i8 && m.N > 8 && g.opt_mmq_min > 0 && m.N >= g.opt_mmq_min);
+    else
+        MATCH(g.opt_plan_mpt && g.opt_big);
+    const int64_t N = m.N;
     MATCH(last->backend == GGML_BACKEND_CPU && last->data && ggml_is_contiguous(last));  // the results go to the node's host data
     m.output = last->src[0];
     MATCH(is_leaf(m.output) && qt_of(m.output->type) >= 0);
@@ -451,7 +460,7 @@ static bool match_mpt_decode(ggml_cgraph *gr, LlamaMatch &m) {
     for (int il = m.L - 1; il >= 0; il--) {
         LayerW &lw = m.layers[il];
         // x = add(inpFF, mul_mat(down_proj, gelu(mul_mat(up_proj, mul(norm(inpFF), norm_2)))))
-        MATCH(dev_op(x, GGML_OP_ADD) && ggml_nelements(x) == m.E);
+        MATCH(dev_op(x, GGML_OP_ADD) && ggml_nelements(x) == N * m.E);
         const ggml_tensor *inpFF = x->src[0], *dn = x->src[1];
         MATCH(dev_op(dn, GGML_OP_MUL_MAT));
         lw.w2 = dn->src[0];
@@ -471,7 +480,7 @@ static bool match_mpt_decode(ggml_cgraph *gr, LlamaMatch &m) {
         lw.wo = mo->src[0];
         MATCH(is_leaf(lw.wo) && lw.wo->ne[0] == m.E && lw.wo->ne[1] == m.E);
         const ggml_tensor *merged = mo->src[1];
-        MATCH(is_op(merged, GGML_OP_CPY) && merged->type == GGML_TYPE_F32 && merged->ne[0] == m.E && merged->ne[1] == 1 && ggml_nelements(merged) == m.E &&
+        MATCH(is_op(merged, GGML_OP_CPY) && merged->type == GGML_TYPE_F32 && merged->ne[0] == m.E && merged->ne[1] == N && ggml_nelements(merged) == N * m.E &&
               ggml_is_contiguous(merged) && is_leaf(merged->src[1]));
         const ggml_tensor *perm = merged->src[0];
         MATCH(is_op(perm, GGML_OP_PERMUTE) && perm_0213(perm));
@@ -514,8 +523,8 @@ static bool match_mpt_decode(ggml_cgraph *gr, LlamaMatch &m) {
         MATCH(kqsv == m.kq_scale && al->op_params[0] == m.n_past && al->op_params[1] == m.H && bias_max == m.alibi_bias_max &&
               mask->op_params[0] == m.n_past);
         c.take(vt); c.take(vp); c.take(vr); c.take(vv1); c.take(probs); c.take(mask); c.take(al); c.take(sc); c.take(kq);
-        const int P = m.n_past, T = P + 1;
-        MATCH(kq->ne[0] == T && kq->ne[1] == 1 && kq->ne[2] == m.H && kq->ne[3] == 1);
+        const int P = m.n_past, T = P + m.N;
+        MATCH(kq->ne[0] == T && kq->ne[1] == N && kq->ne[2] == m.H && kq->ne[3] == 1);
         // K = permute(reshape_3d(view_1d(memory_k)))   Q = permute(cpy(view of qkv at 0, [D, H, 1]))
         const ggml_tensor *kp = kq->src[0], *qp = kq->src[1];
         MATCH(is_op(kp, GGML_OP_PERMUTE) && perm_0213(kp) && is_op(qp, GGML_OP_PERMUTE) && perm_0213(qp));
@@ -536,11 +545,12 @@ static bool match_mpt_decode(ggml_cgraph *gr, LlamaMatch &m) {
         MATCH(vt->ne[0] == T && vt->ne[1] == m.D && vt->ne[2] == m.H);
         const ggml_tensor *qcp = qp->src[0];
         MATCH(is_op(qcp, GGML_OP_CPY) && qcp->type == GGML_TYPE_F32 && is_leaf(qcp->src[1]) && ggml_is_contiguous(qcp) && qcp->ne[0] == m.D &&
-              qcp->ne[1] == m.H && ggml_nelements(qcp) == m.E);
+              qcp->ne[1] == m.H && qcp->ne[2] == N && ggml_nelements(qcp) == N * m.E);
         const ggml_tensor *qv = qcp->src[0];
-        MATCH(is_op(qv, GGML_OP_VIEW) && qv->type == GGML_TYPE_F32 && ggml_nelements(qv) == m.E && qv->ne[0] == m.E && qv->nb[0] == 4);
+        MATCH(is_op(qv, GGML_OP_VIEW) && qv->type == GGML_TYPE_F32 && ggml_nelements(qv) == N * m.E && qv->ne[0] == m.E && qv->ne[1] == N && qv->nb[0] == 4 &&
+              (N == 1 || qv->nb[1] == (size_t)3 * m.E * 4));
         const ggml_tensor *qkv = qv->src[0];
-        MATCH(dev_op(qkv, GGML_OP_MUL_MAT) && qkv->ne[0] == 3 * m.E && ggml_nelements(qkv) == 3 * m.E && view_offset(qv, qkv) == 0);
+        MATCH(dev_op(qkv, GGML_OP_MUL_MAT) && qkv->ne[0] == 3 * m.E && qkv->ne[1] == N && ggml_nelements(qkv) == N * 3 * m.E && ggml_is_contiguous(qkv) && view_offset(qv, qkv) == 0);
         lw.wq = lw.wk = lw.wv = qkv->src[0];
         MATCH(is_leaf(lw.wq) && lw.wq->ne[0] == m.E && lw.wq->ne[1] == 3 * m.E);
         c.take(kp); c.take(qp); c.take(kr); c.take(kv1); c.take(qcp); c.take(qv); c.take(qkv);
@@ -552,7 +562,7 @@ static bool match_mpt_decode(ggml_cgraph *gr, LlamaMatch &m) {
     MATCH(dev_op(x, GGML_OP_GET_ROWS));
     m.wte = x->src[0];
     m.embd = x->src[1];
-    MATCH(m.wte == m.output && is_leaf(m.embd) && m.embd->type == GGML_TYPE_I32 && m.embd->ne[0] == 1 && ggml_nelements(m.embd) == 1 && m.embd->data);
+    MATCH(m.wte == m.output && is_leaf(m.embd) && m.embd->type == GGML_TYPE_I32 && m.embd->ne[0] == N && ggml_nelements(m.embd) == N && m.embd->data);
     c.take(x);
     // the K/V stores: cpy(view of qkv at E | 2E, view_1d(memory_k | memory_v) at position n_past of the layer)
     for (int i = 0; i < n; i++) {
@@ -566,8 +576,9 @@ static bool match_mpt_decode(ggml_cgraph *gr, LlamaMatch &m) {
         for (int j = 0; j < m.L; j++)
             if (m.layers[j].cur == src->src[0]) il = j;
         MATCH(il >= 0 && !(isk ? m.layers[il].k_store : m.layers[il].v_store));
-        MATCH(ggml_nelements(src) == m.E && src->ne[0] == m.E && src->nb[0] == 4 && view_offset(src, src->src[0]) == (size_t)(isk ? 1 : 2) * m.E * 4);
-        MATCH(dst->ne[0] == m.E && ggml_nelements(dst) == m.E && dst->nb[0] == 2);
+        MATCH(ggml_nelements(src) == N * m.E && src->ne[0] == m.E && src->ne[1] == N && src->nb[0] == 4 && (N == 1 || src->nb[1] == (size_t)3 * m.E * 4) &&
+              view_offset(src, src->src[0]) == (size_t)(isk ? 1 : 2) * m.E * 4);
+        MATCH(dst->ne[0] == N * m.E && ggml_nelements(dst) == N * m.E && dst->nb[0] == 2);
         MATCH(view_offset(dst, dst->src[0]) == ((size_t)il * m.C + m.n_past) * m.E * 2);
         (isk ? m.layers[il].k_store : m.layers[il].v_store) = true;
         c.take(t); c.take(dst); c.take(src);
@@ -577,9 +588,13 @@ static bool match_mpt_decode(ggml_cgraph *gr, LlamaMatch &m) {
     // the plan's kernels' own preconditions
     MATCH(m.D % 32 == 0 && m.D <= 128 && m.E % 32 == 0 && m.E <= 8192);
     MATCH(m.memory_k->type == GGML_TYPE_F16 && m.memory_v->type == GGML_TYPE_F16);
-    MATCH(attn_decode_lds((m.C + 7) & ~(int64_t)7, m.D) <= ATTN_DECODE_LDS_MAX);  // (k_attn_decode_alibi's arrays hold the context rounded up to 8)
     for (auto &lw : m.layers)
         for (int i = 0; i < LAYER_MATS; i++) MATCH(lw.at(i)->type == m.wtype && lw.at(i)->ne[2] == 1 && lw.at(i)->ne[3] == 1);
+    if (m.prompt) {  // k_p_attn_alibi keeps a query tile's score rows in LDS: a T behind its fit runs on the executor
+        MATCH(m.n_past + m.N <= m.C && mpt_attn_queries(m.D, (int64_t)m.n_past + m.N) != 0);
+        return true;
+    }
+    MATCH(attn_decode_lds((m.C + 7) & ~(int64_t)7, m.D) <= ATTN_DECODE_LDS_MAX);  // (k_attn_decode_alibi's arrays hold the context rounded up to 8)
     MATCH(big_shape(XSRC_LNORM, EPI_QKV_TM, m.E / 32, 3 * m.E).ok && big_shape(XSRC_LNORM, EPI_GELU, m.E / 32, m.F).ok &&
           big_shape(XSRC_LNORM, EPI_STORE, m.E / 32, m.V).ok && big_shape(XSRC_F32, EPI_ADD, m.E / 32, m.E).ok &&
           big_shape(XSRC_F32, EPI_ADD, m.F / 32, m.E).ok && m.F <= 24 * BIG_T);

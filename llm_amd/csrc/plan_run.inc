@@ -307,7 +307,10 @@ static void run_prompt_plan(DecodePlan *p, const LlamaMatch &m, bool defer_wait,
             if (ids[i] < 0 || ids[i] >= m.wte->ne[1]) die("token id %d out of range", ids[i]);
         h2d_small((char *)p->p_tok, ids, (size_t)m.N * 4);
     }
-    plan_launch_prompt(p);
+    if (m.mpt)
+        plan_launch_mpt_prompt(p);
+    else
+        plan_launch_prompt(p);
     if (m.logits && m.logits->backend == GGML_BACKEND_CPU)  // (the logits alone: the embedding rows of a batch stay on the device, queue_results)
         d2h_queue(m.logits->data, p->logits_out, (size_t)m.V * m.N * 4);
     const uint64_t t2 = now_ns();
@@ -315,6 +318,7 @@ static void run_prompt_plan(DecodePlan *p, const LlamaMatch &m, bool defer_wait,
     g.ns_launch += t2 - t1;
     g.stat_prompt_plan_tokens += (uint64_t)m.N;
     if (m.out_k) g.stat_out_k_tokens += (uint64_t)m.N;
+    if (m.mpt) g.stat_mpt_prompt_tokens += (uint64_t)m.N;
     if (defer_wait) {
         g.pending_wait = true;
         g.pending_light = true;

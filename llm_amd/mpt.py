@@ -1,7 +1,9 @@
 """MPT through the drop-in C ABI: the graph of crates/models/mpt/src/lib.rs:93-259 built node by node with the ctypes
 binding (llm_amd.ggml) and executed by ggml_graph_compute on the MI355X: node by node on the generic executor, or — backend
 option plan_mpt, block-format weights, one token, every node offloaded — on the fused MPT plan (csrc/plan_decode.inc
-plan_launch_mpt: five launches per layer, the captured graph replayed), which Mpt.infer_tokens_device chains on the device.  LayerNorms without bias, no linear biases at all; Wqkv split into [Q | K | V] blocks of n_embd rows (views at 0,
+plan_launch_mpt: five launches per layer, the captured graph replayed), which Mpt.infer_tokens_device chains on the device, or —
+option plan_mpt_prompt, the same model, mmq_min tokens and more — on the MPT prompt plan (csrc/plan_mpt_prompt.inc
+plan_launch_mpt_prompt: nine launches per layer around the f16-MFMA GEMMs), which Mpt.feed_prompt feeds batch by batch.  LayerNorms without bias, no linear biases at all; Wqkv split into [Q | K | V] blocks of n_embd rows (views at 0,
 E and 2E); K and V stored token-major, V re-laid by cpy(permute(.., 1, 2, 0, 3)) at every use; ALiBi attention bias
 with the model's alibi_bias_max, the chain built out of place; lm_head tied to transformer.wte.weight (lib.rs:244).
 clip_kqv is a hyperparameter the reference reads but its graph does not use; so is it here.  The reference's scratch
@@ -58,6 +60,12 @@ class Mpt(Resident):
             return self._evaluate_in(ctx0, tokens)[0]
         finally:
             ctx0.free()
+
+    def feed_prompt(self, tokens, n_batch=512):
+        """The reference's feed_prompt loop: n_batch tokens per evaluation; returns the last row's logits [n_vocab]."""
+        for i in range(0, len(tokens), n_batch):
+            self.evaluate(tokens[i:i + n_batch])
+        return self.last_logits
 
     def infer_tokens_device(self, n):
         """n greedy tokens from the last evaluation's logits on: the pending token (their first maximum) is evaluated as its
