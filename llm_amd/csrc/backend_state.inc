@@ -86,7 +86,7 @@ struct Backend {
     size_t ws_off = 0;  // offset in the last chunk
     Timing timing;
     int opt_fuse = 1, opt_plan = 1, opt_plan_k = 1, opt_plan_multi = 1, opt_plan_prompt = 1, opt_graph = 1, opt_big = 1, opt_kbig = 1;
-    int opt_chain_k = 0, opt_prepare = 1, opt_plan_batch = 1, opt_plan_f16 = 1, opt_plan_batch_chain = 1, opt_plan_batch_sample = 1, opt_plan_sample_chain = 1, opt_plan_batch_k = 0, opt_plan_out_k = 1, opt_plan_mpt = 0, opt_plan_mpt_prompt = 0;
+    int opt_chain_k = 0, opt_prepare = 1, opt_plan_batch = 1, opt_plan_f16 = 1, opt_plan_batch_chain = 1, opt_plan_batch_sample = 1, opt_plan_sample_chain = 1, opt_plan_batch_k = 0, opt_plan_out_k = 1, opt_plan_mpt = 0, opt_plan_mpt_prompt = 0, opt_mpt_attn_stream = 1;
     int opt_fuse_attn = 1, opt_fuse_wo = 1, opt_warm_mb = 24, opt_affine = 1;
     int opt_act_quant = 0, opt_mmq_i8 = 0;
     int opt_mmq_min = 32, opt_k_prompt_min = 12, opt_mmq_fuse = 3, opt_mmq_cols = 1, opt_mmq_t256 = 1, opt_attn_fused = 1;
@@ -102,7 +102,7 @@ struct Backend {
     uint64_t stat_plan_tokens = 0, stat_generic_graphs = 0, stat_split_tokens = 0, stat_prompt_plan_tokens = 0, stat_fused_tokens = 0, stat_kplan_tokens = 0, stat_fused_heads_tokens = 0, stat_fused_wo_tokens = 0, stat_fused_affine_tokens = 0, stat_prepared_tokens = 0;
     uint64_t stat_alibi_fused = 0;
     uint64_t stat_batch_tokens = 0, stat_batch_steps = 0, stat_batch_chain_steps = 0, stat_batch_chain_tokens = 0;
-    uint64_t stat_batch_sample_steps = 0, stat_batch_sample_tokens = 0, stat_batch_k_steps = 0, stat_out_k_tokens = 0, stat_mpt_plan_tokens = 0, stat_mpt_prompt_tokens = 0;
+    uint64_t stat_batch_sample_steps = 0, stat_batch_sample_tokens = 0, stat_batch_k_steps = 0, stat_out_k_tokens = 0, stat_mpt_plan_tokens = 0, stat_mpt_prompt_tokens = 0, stat_mpt_stream_tokens = 0;
     uint64_t stat_sample_chain_steps = 0, stat_sample_chain_tokens = 0;
     // the chains that stop (plan_run.inc chain_req_run): steps per group behind which the host looks at the columns' live flags, the
     // pinned words the flags are copied into (two sets: the host reads one while the next group's copy is in flight) and their events
@@ -216,6 +216,11 @@ static const OptRow g_options[] = {
     // plan_mpt_prompt.inc plan_launch_mpt_prompt: nine launches per layer, launched eagerly).  Independent of plan_mpt; 0 for the same
     // reason: tests/test_mpt_plan_gpu.py counts its prompts as executor graphs.
     {"plan_mpt_prompt", &Backend::opt_plan_mpt_prompt, OPT_ENV | OPT_DROPS},
+    // ... whose attention keeps a query tile's score rows in LDS (k_p_attn_alibi: up to 2240 keys at D = 128, mpt_attn_queries).  Rows behind
+    // that fit: 1 = on the streaming kernel (k_p_attn_alibi_stream: three sweeps, LDS independent of T), 0 = the matcher declines and the
+    // executor runs the graph, 2 = every MPT prompt evaluation streams (tests and tests/tools/mpt_long_prompt.py).  Acts only under
+    // plan_mpt_prompt; read by the matcher and at launch, frozen by no plan.
+    {"mpt_attn_stream", &Backend::opt_mpt_attn_stream, OPT_ENV, FX_NONE, 0, 2},
     {"plan_multi", &Backend::opt_plan_multi, OPT_ENV | OPT_DROPS},    // fused plan for prompt chunks of 2..8 tokens (kernels/decode_big8.h)
     {"plan_prompt", &Backend::opt_plan_prompt, OPT_ENV | OPT_DROPS},  // fused plan for prompt batches of >= mmq_min tokens (kernels/prompt.h)
     // ggml_hip_decode_batch: one decode step of 2..8 sessions of one model as one pass over the weights (0: it answers -1, the caller steps them one by one)
@@ -356,6 +361,7 @@ static const StatRow g_counters[] = {
     {"kplan_tokens", &Backend::stat_kplan_tokens},                // decode tokens of K-quant models that ran as the K plan
     {"mpt_plan_tokens", &Backend::stat_mpt_plan_tokens},          // decode tokens of MPT models that ran as the MPT plan (option plan_mpt), evaluations and greedy chains; counted in plan_tokens too, never in generic_graphs
     {"mpt_prompt_tokens", &Backend::stat_mpt_prompt_tokens},      // prompt tokens of MPT models that ran as the MPT prompt plan (option plan_mpt_prompt); counted in prompt_plan_tokens too, never in generic_graphs
+    {"mpt_stream_tokens", &Backend::stat_mpt_stream_tokens},      // ... those of them whose attention ran on the streaming kernel (option mpt_attn_stream); counted in mpt_prompt_tokens too
     {"out_k_tokens", &Backend::stat_out_k_tokens},                // tokens whose lm_head ran as the K launch inside a block-format plan (LlamaMatch::out_k); counted in plan_tokens / prompt_plan_tokens too
     {"prepared_tokens", &Backend::stat_prepared_tokens},          // decode tokens whose graph had been matched ahead of time (ggml_hip_graph_prepare)
     {"prompt_plan_tokens", &Backend::stat_prompt_plan_tokens},    // tokens executed by the fused prompt plan

@@ -9,6 +9,7 @@ extern "C" {
 //          mem_k / mem_v [C][H D] f16 (token-major, one layer), queries at positions n_past .. n_past + N - 1 <= C - 1; out[0] the merged
 //          heads [N][H D]: flag 0 = f32, 1 / 2 = out_proj's f16 operand with Q8_1's / Q8_0's scale.  D = 32 / 64 / 128, H <= 256, and
 //          n_past + N within the attention's fit (mpt_attn_queries).
+// what 3 — k_p_attn_alibi_stream: what 2's arguments and outputs on the streaming kernel, at any n_past + N <= C.
 // Every output comes back followed by 256 guard bytes of 0xFF.  -1 for what no call site could launch.
 int ggml_hip_debug_mpt_prompt(int what, int flag, const float *x, const float *x2, const float *r, const float *w, float eps, int64_t K, int N,
                               const uint16_t *mem_k, const uint16_t *mem_v, int H, int D, int n_past, int64_t C, float scale, void *const *out) {
@@ -37,9 +38,9 @@ int ggml_hip_debug_mpt_prompt(int what, int flag, const float *x, const float *x
         run.back(out[0], dout, nx / 2 + DEBUG_GUARD);
         return run.finish();
     }
-    if (what != 2) return -1;
+    if (what != 2 && what != 3) return -1;
     if (!w || !mem_k || !mem_v || H < 1 || H > 256 || !(D == 32 || D == 64 || D == 128) || n_past < 0 || (int64_t)n_past + N > C || flag < 0 || flag > 2 ||
-        !mpt_attn_queries(D, (int64_t)n_past + N))
+        (what == 2 && !mpt_attn_queries(D, (int64_t)n_past + N)))
         return -1;
     const int64_t E = (int64_t)H * D;
     DebugRun run;
@@ -52,7 +53,7 @@ int ggml_hip_debug_mpt_prompt(int what, int flag, const float *x, const float *x
     const size_t no = (size_t)N * E * (flag ? 2 : 4);
     char *dout = run.buf(no);
     mpt_prompt_attention((const float *)dq, x2 ? (int64_t)N * 3 * E : 0, dk, dv, dsl, flag ? nullptr : (float *)dout, flag ? (_Float16 *)dout : nullptr, flag == 2, N, E,
-                         H, D, n_past, C, scale);
+                         H, D, n_past, C, scale, what == 3);
     run.back(out[0], dout, no + DEBUG_GUARD);
     return run.finish();
 }

@@ -1,5 +1,5 @@
 // mpt_prompt.hip — the kernels of the MPT prompt plan (kernels/mpt_prompt.h): the LayerNorm and GELU operands, the token-major K/V
-// store and the ALiBi prompt attention, in an object and so a code object of their own, as mpt_plan.hip and prompt_pack.hip are and
+// store and the ALiBi prompt attention (both forms), in an object and so a code object of their own, as mpt_plan.hip and prompt_pack.hip are and
 // for their reason: hip_backend.hip's code object keeps its kernels at their addresses, and every other plan launches exactly what
 // it launched.  The headers are included inside an unnamed namespace (see sample_ext.hip for what that costs and asks); this object's
 // copy of c_act_quant_scalar is set with the others (mpt_prompt_set_act_quant).
@@ -72,6 +72,18 @@ int launch_mpt_attn_alibi(hipStream_t stream, int D, int QR, const void *args, u
         if (D == 32) return attn_launch<32, 16>(stream, a, grid, lds);
     }
     return 1;
+}
+int launch_mpt_attn_alibi_stream(hipStream_t stream, int D, const void *args, unsigned grid) {
+    const MptAttnArgs &a = *(const MptAttnArgs *)args;
+    if (D == 128)
+        hipLaunchKernelGGL(k_p_attn_alibi_stream<128>, dim3(grid), dim3(256), 0, stream, a);
+    else if (D == 64)
+        hipLaunchKernelGGL(k_p_attn_alibi_stream<64>, dim3(grid), dim3(256), 0, stream, a);
+    else if (D == 32)
+        hipLaunchKernelGGL(k_p_attn_alibi_stream<32>, dim3(grid), dim3(256), 0, stream, a);
+    else
+        return 1;
+    return 0;
 }
 int mpt_prompt_set_act_quant(int v) {
     return hipMemcpyToSymbol(HIP_SYMBOL(c_act_quant_scalar), &v, sizeof(v)) == hipSuccess ? 0 : 1;

@@ -590,8 +590,8 @@ static bool match_mpt_decode(ggml_cgraph *gr, LlamaMatch &m) {
     MATCH(m.memory_k->type == GGML_TYPE_F16 && m.memory_v->type == GGML_TYPE_F16);
     for (auto &lw : m.layers)
         for (int i = 0; i < LAYER_MATS; i++) MATCH(lw.at(i)->type == m.wtype && lw.at(i)->ne[2] == 1 && lw.at(i)->ne[3] == 1);
-    if (m.prompt) {  // k_p_attn_alibi keeps a query tile's score rows in LDS: a T behind its fit runs on the executor
-        MATCH(m.n_past + m.N <= m.C && mpt_attn_queries(m.D, (int64_t)m.n_past + m.N) != 0);
+    if (m.prompt) {  // k_p_attn_alibi keeps a query tile's score rows in LDS: a T behind its fit streams (option mpt_attn_stream)
+        MATCH(m.n_past + m.N <= m.C && (mpt_attn_queries(m.D, (int64_t)m.n_past + m.N) != 0 || (g.opt_mpt_attn_stream && (m.D == 32 || m.D == 64 || m.D == 128))));
         return true;
     }
     MATCH(attn_decode_lds((m.C + 7) & ~(int64_t)7, m.D) <= ATTN_DECODE_LDS_MAX);  // (k_attn_decode_alibi's arrays hold the context rounded up to 8)

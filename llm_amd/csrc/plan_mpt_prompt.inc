@@ -2,31 +2,34 @@
 // plan_mpt_prompt) as nine launches per layer, launched eagerly as plan_launch_prompt is:
 //   k_p_lnorm_quant -> Wqkv GEMM -> k_p_qkv_post_tm -> k_p_attn_alibi -> out_proj GEMM -> k_p_lnorm_quant (+ residual) -> up_proj GEMM ->
 //   k_p_gelu_quant -> down_proj GEMM
+// (k_p_attn_alibi_stream in k_p_attn_alibi's place for rows behind its LDS fit: option mpt_attn_stream)
 // then the final LayerNorm and the tied lm_head GEMM over all N rows.  The GEMMs are the executor's (mmq_f16_launch_multi on the resident
 // f16 copies, the K split of mmq_auto_splits per matrix); a split GEMM stores two partials `stride` floats apart and its consumer adds
 // them, as in the LLaMA prompt plan: no memset, no atomics.  Everything between them is kernels/mpt_prompt.h (mpt_prompt.hip).  The
 // reference's re-copy of the V cache (cpy(permute(V, 1, 2, 0, 3))) is matched and never made: the attention reads token-major V.
 
-// the attention launch of one layer; x16 == nullptr: `out` (f32 merged heads) is written instead (the test hook)
+// the attention launch of one layer; x16 == nullptr: `out` (f32 merged heads) is written instead (the test hook); force_stream: the
+// streaming kernel also where the rows fit
 static void mpt_prompt_attention(const float *qkv, int64_t q_part, const void *mk, const void *mv, const float *slopes, float *out, _Float16 *x16,
-                                 bool f16d, int N, int64_t E, int64_t H, int64_t D, int n_past, int64_t C, float scale) {
+                                 bool f16d, int N, int64_t E, int64_t H, int64_t D, int n_past, int64_t C, float scale, bool force_stream) {
     const int64_t T = (int64_t)n_past + N;
-    const int QR = mpt_attn_queries(D, T);
-    if (!QR) die("MPT prompt plan: rows of %lld keys do not fit the attention's LDS", (long long)T);
+    const bool stream = force_stream || !mpt_attn_queries(D, T);
+    const int QR = stream ? 32 : mpt_attn_queries(D, T);
     MptAttnArgs a;
     memset(&a, 0, sizeof(a));
     a.qkv = qkv; a.q_part = q_part; a.mem_k = mk; a.mem_v = mv; a.slopes = slopes; a.out = out; a.x16 = x16;
     a.N = N; a.E = (int)E; a.H = (int)H; a.n_past = n_past; a.f16d = f16d ? 1 : 0;
     a.row_bytes = mpt_attn_row_bytes(T);
     a.C = C; a.scale = scale;
-    const size_t lds = mpt_attn_lds(QR, D, T);
+    const size_t lds = stream ? mpt_attn_stream_lds(D) : mpt_attn_lds(QR, D, T);
     const int ntile = (N + QR - 1) / QR;
     // two workgroups per CU where the LDS allows and there are more workgroups than CUs: the first num_cus take the longest tiles, the
     // rest come shortest first (k_p_attn's dealing, plan_prompt.inc prompt_attention)
     const bool two_per_cu = 2 * (lds + 1024) <= 160 * 1024 && (int64_t)ntile * H > g.num_cus;
     a.r1 = two_per_cu ? std::max(1, std::min(ntile, (int)(g.num_cus / H))) : ntile;
-    Timed tm(GGML_HIP_KCLASS_ATTN, (double)T * E * 4.0 + (double)N * E * 6.0);
-    if (launch_mpt_attn_alibi(g.stream, (int)D, QR, &a, (unsigned)(ntile * H), lds)) die("MPT prompt plan: the attention launch for head size %lld failed", (long long)D);
+    Timed tm(GGML_HIP_KCLASS_ATTN, (double)T * E * (stream ? 8.0 : 4.0) + (double)N * E * 6.0);  // (the streaming kernel reads K three times)
+    if (stream ? launch_mpt_attn_alibi_stream(g.stream, (int)D, &a, (unsigned)(ntile * H)) : launch_mpt_attn_alibi(g.stream, (int)D, QR, &a, (unsigned)(ntile * H), lds))
+        die("MPT prompt plan: the attention launch for head size %lld failed", (long long)D);
     HIP_CHECK(hipGetLastError());
 }
 
@@ -83,7 +86,7 @@ static void plan_launch_mpt_prompt(DecodePlan *p) {
             HIP_CHECK(hipGetLastError());
         }
         mpt_prompt_attention(qkv, sp_qkv > 1 ? qkv_stride : 0, p->mem_k_at(il), p->mem_v_at(il), p->alibi, nullptr, x16, f16d, N, E, m.H, m.D, m.n_past,
-                             m.C, m.kq_scale);
+                             m.C, m.kq_scale, g.opt_mpt_attn_stream == 2);
         const int sp_o = gemm(w.wo, te, nbE, te_stride);
         lnorm_quant(te, sp_o > 1 ? te + te_stride : nullptr, p->xa, p->xb, ln.ffn_norm);  // inpFF (xb) = out_proj output + inpSA
         const int sp_up = gemm(w.w1, up, nbE, up_stride);

@@ -319,6 +319,7 @@ static void run_prompt_plan(DecodePlan *p, const LlamaMatch &m, bool defer_wait,
     g.stat_prompt_plan_tokens += (uint64_t)m.N;
     if (m.out_k) g.stat_out_k_tokens += (uint64_t)m.N;
     if (m.mpt) g.stat_mpt_prompt_tokens += (uint64_t)m.N;
+    if (m.mpt && (g.opt_mpt_attn_stream == 2 || !mpt_attn_queries(m.D, (int64_t)m.n_past + m.N))) g.stat_mpt_stream_tokens += (uint64_t)m.N;
     if (defer_wait) {
         g.pending_wait = true;
         g.pending_light = true;

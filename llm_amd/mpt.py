@@ -3,7 +3,11 @@ binding (llm_amd.ggml) and executed by ggml_graph_compute on the MI355X: node by
 option plan_mpt, block-format weights, one token, every node offloaded — on the fused MPT plan (csrc/plan_decode.inc
 plan_launch_mpt: five launches per layer, the captured graph replayed), which Mpt.infer_tokens_device chains on the device, or —
 option plan_mpt_prompt, the same model, mmq_min tokens and more — on the MPT prompt plan (csrc/plan_mpt_prompt.inc
-plan_launch_mpt_prompt: nine launches per layer around the f16-MFMA GEMMs), which Mpt.feed_prompt feeds batch by batch.  LayerNorms without bias, no linear biases at all; Wqkv split into [Q | K | V] blocks of n_embd rows (views at 0,
+plan_launch_mpt_prompt: nine launches per layer around the f16-MFMA GEMMs), which Mpt.feed_prompt feeds batch by batch.  Its
+attention keeps a query tile's score rows in LDS up to n_past + N = 2240 keys (head size 128); batches behind that stay on the plan,
+on the streaming attention kernel (option mpt_attn_stream, default 1; 0 = such a batch runs on the executor; counter
+mpt_stream_tokens), so a long context is fed on the plan to its end.
+LayerNorms without bias, no linear biases at all; Wqkv split into [Q | K | V] blocks of n_embd rows (views at 0,
 E and 2E); K and V stored token-major, V re-laid by cpy(permute(.., 1, 2, 0, 3)) at every use; ALiBi attention bias
 with the model's alibi_bias_max, the chain built out of place; lm_head tied to transformer.wte.weight (lib.rs:244).
 clip_kqv is a hyperparameter the reference reads but its graph does not use; so is it here.  The reference's scratch
