@@ -916,6 +916,8 @@ GGML_API int ggml_hip_debug_act_quant(int kind, int flags, int64_t rows, int64_t
  * token-major caches — x = q [H*D], w = the slopes [H], mem_k / mem_v [C][H*D] f16, the token at n_past, scale; out[0] [H*D] f32.
  * op 2 (test-only state): flag != 0 = MPT plans built from now on carry a slope table with every head on the first sequence; cached
  * plans are dropped.  op 3: x = a ggml_cgraph *: 1 if the MPT matcher takes it under the current options, 0 if not; nothing is executed.
+ * op 4: op 1's attention split over the positions — the three launches an MPT plan runs from option attn_split's threshold on — with op 1's
+ * arguments and flag = S, the workgroups per head (2 .. 16); no LDS condition on C (op 1 returns -1 above some 25.5k positions).
  * Every output is followed by 256 guard bytes (0xFF before the launch).  0, or -1 for what no call site launches. */
 GGML_API int ggml_hip_debug_mpt(int op, int flag, const float *x, const float *w, float eps, int64_t K, const uint16_t *mem_k,
                                 const uint16_t *mem_v, int H, int D, int n_past, int64_t C, float scale, void *const *out);

@@ -102,7 +102,7 @@ struct Backend {
     uint64_t stat_plan_tokens = 0, stat_generic_graphs = 0, stat_split_tokens = 0, stat_prompt_plan_tokens = 0, stat_fused_tokens = 0, stat_kplan_tokens = 0, stat_fused_heads_tokens = 0, stat_fused_wo_tokens = 0, stat_fused_affine_tokens = 0, stat_prepared_tokens = 0;
     uint64_t stat_alibi_fused = 0;
     uint64_t stat_batch_tokens = 0, stat_batch_steps = 0, stat_batch_chain_steps = 0, stat_batch_chain_tokens = 0;
-    uint64_t stat_batch_sample_steps = 0, stat_batch_sample_tokens = 0, stat_batch_k_steps = 0, stat_out_k_tokens = 0, stat_mpt_plan_tokens = 0, stat_mpt_prompt_tokens = 0, stat_mpt_stream_tokens = 0;
+    uint64_t stat_batch_sample_steps = 0, stat_batch_sample_tokens = 0, stat_batch_k_steps = 0, stat_out_k_tokens = 0, stat_mpt_plan_tokens = 0, stat_mpt_split_tokens = 0, stat_mpt_prompt_tokens = 0, stat_mpt_stream_tokens = 0;
     uint64_t stat_sample_chain_steps = 0, stat_sample_chain_tokens = 0;
     // the chains that stop (plan_run.inc chain_req_run): steps per group behind which the host looks at the columns' live flags, the
     // pinned words the flags are copied into (two sets: the host reads one while the next group's copy is in flight) and their events
@@ -278,7 +278,11 @@ static const OptRow g_options[] = {
     {"affine", &Backend::opt_affine, OPT_ENV | OPT_DROPS},
     // contexts beyond k_qkv_attn's register window: 2 / 4 attention workgroups per head inside the wq|wk|wv launch
     {"fuse_heads", &Backend::opt_fuse_heads, OPT_ENV | OPT_DROPS},
-    {"attn_split", &Backend::opt_attn_split, OPT_ENV | OPT_DROPS},  // long contexts: attention split over positions too (kernels/decode_attn_split.h)
+    // long contexts: attention split over positions too (kernels/decode_attn_split.h; an MPT plan: kernels/mpt_plan.h).  0 = off, 1 = from the
+    // plan's default threshold on (ATTN_SPLIT_MIN, ATTN_SPLIT_MIN_FUSED, ATTN_SPLIT_MIN_MPT), n > 1 = from n positions on.  For an MPT model it also
+    // decides the longest context the MPT plan takes: with the split path k_attn_decode_alibi keeps the rows below the threshold alone in LDS,
+    // without it (0, or fewer than two workgroups per head) the whole context must fit there (about 25.5k positions)
+    {"attn_split", &Backend::opt_attn_split, OPT_ENV | OPT_DROPS},
     {"attn_one", &Backend::opt_attn_one, OPT_ENV | OPT_DROPS},      // ... its three phases as ONE launch (k_attn_split_one) where every workgroup is resident
     // a token whose in-launch hand-off gave up: 1 = re-run it on the kernels that do not wait inside a launch and keep them; 0 = abort
     {"fused_fallback", &Backend::opt_fused_fallback, OPT_ENV},
@@ -360,6 +364,7 @@ static const StatRow g_counters[] = {
     {"attn_split_tokens", &Backend::stat_split_tokens},           // tokens whose attention ran split over positions
     {"kplan_tokens", &Backend::stat_kplan_tokens},                // decode tokens of K-quant models that ran as the K plan
     {"mpt_plan_tokens", &Backend::stat_mpt_plan_tokens},          // decode tokens of MPT models that ran as the MPT plan (option plan_mpt), evaluations and greedy chains; counted in plan_tokens too, never in generic_graphs
+    {"mpt_split_tokens", &Backend::stat_mpt_split_tokens},        // ... those of them whose attention ran split over the positions (option attn_split), evaluations and chain steps; counted in mpt_plan_tokens too
     {"mpt_prompt_tokens", &Backend::stat_mpt_prompt_tokens},      // prompt tokens of MPT models that ran as the MPT prompt plan (option plan_mpt_prompt); counted in prompt_plan_tokens too, never in generic_graphs
     {"mpt_stream_tokens", &Backend::stat_mpt_stream_tokens},      // ... those of them whose attention ran on the streaming kernel (option mpt_attn_stream); counted in mpt_prompt_tokens too
     {"out_k_tokens", &Backend::stat_out_k_tokens},                // tokens whose lm_head ran as the K launch inside a block-format plan (LlamaMatch::out_k); counted in plan_tokens / prompt_plan_tokens too

@@ -10,6 +10,9 @@ extern "C" {
 //        first sequence (the mutant tests/test_mpt_plan_gpu.py must see); flag 0 ends that.  Cached plans are dropped either way.
 // op 3 — the matcher alone: x = a ggml_cgraph *; 1 if match_mpt_decode takes the graph under the slot's options, 0 if it declines.  Nothing of
 //        the graph is executed or uploaded (a test can ask about a graph it must not run: a token behind the context's end).
+// op 4 — the same attention split over the positions (k_attn_split_scores_alibi, _vp_alibi, _merge_alibi: the three launches of an MPT plan's
+//        AV_SPLIT): op 1's arguments with flag = S, the workgroups per head (2 .. 16), on scratch of the call's own; no LDS condition on C but
+//        that a range's probabilities fit (2 bytes a position); out[0] as op 1's.
 // Every output comes back followed by 256 guard bytes of 0xFF.  -1 for what no call site could launch.
 int ggml_hip_debug_mpt(int op, int flag, const float *x, const float *w, float eps, int64_t K, const uint16_t *mem_k, const uint16_t *mem_v,
                        int H, int D, int n_past, int64_t C, float scale, void *const *out) {
@@ -47,11 +50,12 @@ int ggml_hip_debug_mpt(int op, int flag, const float *x, const float *w, float e
         run.back(out[3], sum, (size_t)nb * 4 + DEBUG_GUARD);
         return run.finish();
     }
-    if (op != 1) return -1;
+    if (op != 1 && op != 4) return -1;
     if (!x || !w || !mem_k || !mem_v || !out || !out[0] || H < 1 || H > 256 || D < 32 || D % 32 || D > 128 || n_past < 0 || (int64_t)n_past + 1 > C)
         return -1;
     const int64_t E = (int64_t)H * D, Clds = (C + 7) & ~(int64_t)7;
-    if (attn_decode_lds(Clds, D) > ATTN_DECODE_LDS_MAX) return -1;
+    const int S = flag;
+    if (op == 4 ? S < 2 || S > 16 || attn_split_chunk_max(C, S) * 2 > ATTN_DECODE_LDS_MAX : attn_decode_lds(Clds, D) > ATTN_DECODE_LDS_MAX) return -1;
     DebugRun run;
     DecParams hp;
     memset(&hp, 0, sizeof(hp));
@@ -60,7 +64,14 @@ int ggml_hip_debug_mpt(int op, int flag, const float *x, const float *w, float e
     const float *dq = (const float *)run.buf((size_t)E * 4, x), *dsl = (const float *)run.buf((size_t)H * 4, w);
     const char *dk = run.buf((size_t)C * E * 2, mem_k), *dv = run.buf((size_t)C * E * 2, mem_v);
     char *dout = run.buf((size_t)E * 4);
-    if (launch_mpt_attn(g.stream, H, dq, dk, dv, prm, scale, dsl, D, E, (float *)dout, Clds, attn_decode_lds(Clds, D))) return -1;
+    if (op == 4) {
+        char *sc = run.buf((size_t)H * C * 4), *pmax = run.buf((size_t)H * S * 4), *part = run.buf((size_t)H * S * D * 4);
+        if (launch_mpt_attn_split(g.stream, H, S, dq, dk, dv, prm, scale, dsl, D, E, C, (float *)sc, (float *)pmax, (float *)part, (float *)dout,
+                                  attn_split_chunk_max(C, S) * 2))
+            return -1;
+    } else if (launch_mpt_attn(g.stream, H, dq, dk, dv, prm, scale, dsl, D, E, (float *)dout, Clds, attn_decode_lds(Clds, D))) {
+        return -1;
+    }
     run.back(out[0], dout, (size_t)E * 4 + DEBUG_GUARD);
     return run.finish();
 }

@@ -2,6 +2,7 @@
 // a code object of its own (mpt_plan.hip, MPT_PLAN_OBJECT) so that hip_backend.hip's code object holds what it held:
 //   k_mmvq_big<QT, EPI_QKV_TM | EPI_GELU | EPI_STORE, XSRC_LNORM>   the mat-vecs behind a LayerNorm (kernels/decode_big.h)
 //   k_attn_decode_alibi                                             decode attention over token-major K AND V, with the ALiBi bias
+//   k_attn_split_scores_alibi / _vp_alibi / _merge_alibi            the same attention split over the positions: three launches, long contexts
 //   k_lnorm_stage_dump                                              test hook: the Q8 blocks big_stage_lnorm leaves in LDS
 // hip_backend.hip sees only the launch functions declared at the end of this file.
 #pragma once
@@ -140,6 +141,198 @@ __global__ void __launch_bounds__(1024) k_attn_decode_alibi(const float *__restr
     }
 }
 
+// ---------------------------------------------------------------------------------------------------
+// The same attention split over the positions as well as the heads (AV_SPLIT of an MPT plan): S workgroups per head, each a contiguous
+// range of positions, so a long context's K and V enter through n_head * S CUs instead of n_head.  ggml's soft_max fixes its rounding
+// points (the row maximum first, the f64 sum of the f16-rounded exps, p rounded to f16 before V), so nothing is rescaled online; the
+// split costs three launches, every dependency a kernel boundary — no workgroup waits for another of its own launch:
+//   1. k_attn_split_scores_alibi  x_t of the range (k_attn_decode_alibi's expression: the same bits) -> sc[h][t], the range's maximum -> pmax[h][s]
+//   2. k_attn_split_vp_alibi      every workgroup of a head: mx = the maximum of the S partial maxima, then e_t and the f64 sum over the
+//                                 WHOLE row from sc (T * 4 bytes out of L2 per workgroup; every e is an f16 value in [0, 1], a multiple of
+//                                 2^-24: the sum is exact in any order) — so mx, inv and every p_t are k_attn_decode_alibi's bits; p of the
+//                                 own range as f16 in LDS, then V·P over the range in k_attn_decode_alibi's lane shape -> part[h][s][0..D)
+//   3. k_attn_split_merge_alibi   out[h * D + d] = Σ_s part[h][s][d], s ascending, f32: the merged-heads row out_proj stages
+// The ranges are attn_split_range's (kernels/decode_attn_split.h, restated: this object does not see that header): multiples of 64
+// positions but for the last, derived from prm->n_past on the device — one captured graph serves every T.  A range may be empty (T <= 64 * s):
+// its workgroup of launch 1 writes -INFINITY, its workgroup of launch 2 writes D zeros, so launch 3 adds all S rows whatever T is.
+// Positions at or behind T are never read.  The result is reproducible for a given (T, S); it is not k_attn_decode_alibi's bit for bit:
+// the f32 V·P chain is cut at other places.
+// ---------------------------------------------------------------------------------------------------
+struct MptSplitArgs {
+    const float *q;
+    const __half *mem_k, *mem_v;  // [C][E] f16, token-major, one layer
+    const DecParams *prm;
+    const float *slopes;
+    float scale;
+    int D, S;  // S = workgroups per head
+    int64_t E, C;
+    float *sc;    // [n_head][C] biased scores
+    float *pmax;  // [n_head][S]
+    float *part;  // [n_head][S][D]
+    float *out;   // [n_head * D]
+};
+// the positions [t0, t1) of workgroup s; returns the full range length (the last non-empty range may be shorter, later ones are empty)
+__device__ __forceinline__ int mpt_split_range(int T, int S, int s, int &t0, int &t1) {
+    const int chunk = (((T + S - 1) / S) + 63) & ~63;
+    t0 = s * chunk < T ? s * chunk : T;
+    t1 = t0 + chunk < T ? t0 + chunk : T;
+    return chunk;
+}
+
+__global__ void __launch_bounds__(1024) k_attn_split_scores_alibi(const MptSplitArgs a) {
+    __shared__ float s_red[16];
+    const int h = blockIdx.x, s = blockIdx.y;
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int T = a.prm->n_past + 1;
+    if (T < 1 || T > a.C) return;  // (never: the plan runs positions inside the context only)
+    int t0, t1;
+    mpt_split_range(T, a.S, s, t0, t1);
+    const float slope = a.slopes[h];
+    const int g = tid >> 4, gl = tid & 15, d0 = gl * 8;  // 64 groups of 16 lanes, lane gl owns dims d0 .. d0 + 7
+    const bool act = d0 < a.D;
+    const f16x8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
+    f16x2 qh2[4];
+    {
+        f32x4 q0 = {0.0f, 0.0f, 0.0f, 0.0f}, q1 = q0;
+        if (act) {
+            q0 = *(const f32x4 *)(a.q + (int64_t)h * a.D + d0);
+            q1 = *(const f32x4 *)(a.q + (int64_t)h * a.D + d0 + 4);
+        }
+#pragma unroll
+        for (int j = 0; j < 2; j++) {
+            qh2[j] = f16x2{(_Float16)q0[2 * j], (_Float16)q0[2 * j + 1]};
+            qh2[2 + j] = f16x2{(_Float16)q1[2 * j], (_Float16)q1[2 * j + 1]};
+        }
+    }
+    const __half *kbase = a.mem_k + (int64_t)h * a.D + d0;
+    float *sc = a.sc + (int64_t)h * a.C;
+    float mx = -INFINITY;
+#pragma unroll 1
+    for (int tb = t0 + g; tb < t1; tb += 256) {
+        f16x8 kv[4];
+#pragma unroll
+        for (int u = 0; u < 4; u++) {
+            const int t = tb + 64 * u;
+            kv[u] = zero8;
+            if (act && t < t1) kv[u] = *(const f16x8 *)(kbase + (int64_t)t * a.E);
+        }
+#pragma unroll
+        for (int u = 0; u < 4; u++) {
+            const int t = tb + 64 * u;
+            float v = 0.0f;
+#pragma unroll
+            for (int j = 0; j < 4; j++) v = __builtin_amdgcn_fdot2(f16x2{kv[u][2 * j], kv[u][2 * j + 1]}, qh2[j], v, false);
+            v = g16_sum_f32(v);
+            if (t < t1) {
+                const float x = __fadd_rn(__fmul_rn((float)t, slope), __fmul_rn(v, a.scale));
+                if (gl == 0) sc[t] = x;
+                mx = fmaxf(mx, x);
+            }
+        }
+    }
+    mx = wave_max_f32(mx);
+    if (lane == 0) s_red[wave] = mx;
+    __syncthreads();
+    if (tid == 0) {
+        float m = s_red[0];
+#pragma unroll
+        for (int i = 1; i < 16; i++) m = fmaxf(m, s_red[i]);
+        a.pmax[h * a.S + s] = m;  // (an empty range: -INFINITY)
+    }
+}
+
+// Dynamic LDS: the range's probabilities as f16 — attn_split_chunk_max(C, S) of them, what the launcher asks for.
+__global__ void __launch_bounds__(1024) k_attn_split_vp_alibi(const MptSplitArgs a) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    __shared__ double s_redd[16];
+    __shared__ float s_acc[16][128];
+    _Float16 *s_p = (_Float16 *)smem;
+    const int h = blockIdx.x, s = blockIdx.y;
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int T = a.prm->n_past + 1;
+    if (T < 1 || T > a.C) return;
+    int t0, t1;
+    mpt_split_range(T, a.S, s, t0, t1);
+    float *part = a.part + ((int64_t)h * a.S + s) * a.D;
+    if (t0 >= t1) {  // an empty range (the whole workgroup takes this branch): the zeros launch 3 adds
+        if (tid < a.D) part[tid] = 0.0f;
+        return;
+    }
+    float mx = a.pmax[h * a.S];
+    for (int i = 1; i < a.S; i++) mx = fmaxf(mx, a.pmax[h * a.S + i]);
+    // e and its sum over the whole row; the own range's e stay in LDS (f16 values: stored exactly)
+    const float *sc = a.sc + (int64_t)h * a.C;
+    double sum = 0.0;
+    for (int t = tid; t < T; t += 1024) {
+        const float e = round_f16(expf(round_f16(sc[t] - mx)));
+        sum += (double)e;
+        if (t >= t0 && t < t1) s_p[t - t0] = (_Float16)e;
+    }
+    sum = wave_sum_f64(sum);
+    if (lane == 0) s_redd[wave] = sum;
+    __syncthreads();
+    double tot = 0.0;
+#pragma unroll
+    for (int i = 0; i < 16; i++) tot += s_redd[i];
+    const float inv = (float)(1.0 / tot);
+    const int n = t1 - t0;
+    for (int i = tid; i < n; i += 1024) s_p[i] = (_Float16)((float)s_p[i] * inv);
+    __syncthreads();
+    // ---- V·P over the range ----
+    const int g = tid >> 4, gl = tid & 15, d0 = gl * 8;
+    const bool act = d0 < a.D;
+    const f16x8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
+    float acc[8];
+#pragma unroll
+    for (int j = 0; j < 8; j++) acc[j] = 0.0f;
+    const __half *vbase = a.mem_v + (int64_t)h * a.D + d0;
+#pragma unroll 1
+    for (int tb = t0 + g; tb < t1; tb += 256) {
+        f16x8 vv[4];
+#pragma unroll
+        for (int u = 0; u < 4; u++) {
+            const int t = tb + 64 * u;
+            vv[u] = zero8;
+            if (act && t < t1) vv[u] = *(const f16x8 *)(vbase + (int64_t)t * a.E);
+        }
+#pragma unroll
+        for (int u = 0; u < 4; u++) {
+            const int t = tb + 64 * u;
+            if (t < t1) {
+                const float p = (float)s_p[t - t0];
+#pragma unroll
+                for (int j = 0; j < 8; j++) acc[j] += (float)vv[u][j] * p;  // f16 x f16: exact in f32
+            }
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 8; j++) {  // the wave's four groups (lanes gl, gl + 16, gl + 32, gl + 48)
+        acc[j] += __shfl_xor(acc[j], 16);
+        acc[j] += __shfl_xor(acc[j], 32);
+    }
+    if (lane < 16 && act) {
+#pragma unroll
+        for (int j = 0; j < 8; j++) s_acc[wave][d0 + j] = acc[j];
+    }
+    __syncthreads();
+    if (tid < a.D) {
+        float o = 0.0f;
+#pragma unroll
+        for (int w = 0; w < 16; w++) o += s_acc[w][tid];
+        part[tid] = o;
+    }
+}
+
+__global__ void __launch_bounds__(128) k_attn_split_merge_alibi(const MptSplitArgs a) {
+    const int h = blockIdx.x, d = threadIdx.x;
+    const int T = a.prm->n_past + 1;
+    if (T < 1 || T > a.C || d >= a.D) return;
+    const float *part = a.part + (int64_t)h * a.S * a.D + d;
+    float o = part[0];
+    for (int s = 1; s < a.S; s++) o += part[(int64_t)s * a.D];
+    a.out[(int64_t)h * a.D + d] = o;
+}
+
 // Test hook: one workgroup stages norm(x) * w as k_mmvq_big<.., XSRC_LNORM> stages it (the same BigX loads, the same big_stage_lnorm)
 // and hands out what its LDS holds: the planar Q8 blocks (lo, hi: 16 int8 each), their scales and sums.
 template <bool F16_D>
@@ -171,6 +364,11 @@ int launch_mpt_big(hipStream_t stream, int qt, int epi, const void *big_args, in
 // k_attn_decode_alibi on n_head workgroups; lds = attn_decode_lds(Clds, D).  1: the LDS opt-in failed.
 int launch_mpt_attn(hipStream_t stream, int n_head, const float *q, const void *mem_k, const void *mem_v, const void *prm, float scale,
                     const float *slopes, int D, int64_t E, float *out, int64_t Clds, size_t lds);
+// the position-split form of the same attention (k_attn_split_scores_alibi, k_attn_split_vp_alibi, k_attn_split_merge_alibi) on n_head x S,
+// n_head x S and n_head workgroups; sc [n_head][C], pmax [n_head][S], part [n_head][S][D]; lds = 2 bytes per position of the longest range
+// (attn_split_chunk_max(C, S)).  1: the LDS opt-in failed.
+int launch_mpt_attn_split(hipStream_t stream, int n_head, int S, const float *q, const void *mem_k, const void *mem_v, const void *prm, float scale,
+                          const float *slopes, int D, int64_t E, int64_t C, float *sc, float *pmax, float *part, float *out, size_t lds);
 int launch_mpt_stage_dump(hipStream_t stream, int f16d, const void *big_args, void *lo, void *hi, float *d, int *sum, size_t lds);
 // the quantizer branch of THIS code object's copy of c_act_quant_scalar (kernels/common.h): apply_act_quant sets both
 int mpt_plan_set_act_quant(int v);

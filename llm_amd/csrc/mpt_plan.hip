@@ -1,5 +1,5 @@
 // mpt_plan.hip — the kernels of the MPT decode plan (kernels/mpt_plan.h): k_mmvq_big's LayerNorm-staged instantiations, the ALiBi
-// decode attention over token-major K and V, and the staging dump of the test hook, in an object and so a code object of their own,
+// decode attention over token-major K and V (one workgroup per head, and split over the positions), and the staging dump of the test hook, in an object and so a code object of their own,
 // as sample_ext.hip, sample_req.hip, pool_admit.hip and prompt_pack.hip are and for their reason: hip_backend.hip's code object keeps
 // its kernels at their addresses, and every LLaMA plan launches exactly what it launched.  The headers are included inside an unnamed
 // namespace (see sample_ext.hip for what that costs and asks).  One thing more than there: kernels/common.h's c_act_quant_scalar
@@ -25,14 +25,13 @@ int big_lnorm(hipStream_t stream, int epi, const BigArgs &a, int G, size_t lds) 
         default: return 1;
     }
 }
-// the dynamic LDS of the attention above the 64 KiB default: asked for once per device (two slots asking at once both ask: harmless)
-int attn_opt_in(size_t lds) {
-    static std::atomic<bool> done[64] = {};
-    if (lds <= 64 * 1024) return 0;
+// the dynamic LDS of an attention kernel above `dflt` bytes: asked for once per device and kernel (two slots asking at once both ask: harmless)
+int attn_opt_in(const void *kernel, std::atomic<bool> *done, size_t lds, size_t dflt) {
+    if (lds <= dflt) return 0;
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) return 1;
     if (done[dev & 63].load(std::memory_order_acquire)) return 0;
-    if (hipFuncSetAttribute((const void *)k_attn_decode_alibi, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess) return 1;
+    if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess) return 1;
     done[dev & 63].store(true, std::memory_order_release);
     return 0;
 }
@@ -51,9 +50,23 @@ int launch_mpt_big(hipStream_t stream, int qt, int epi, const void *big_args, in
 }
 int launch_mpt_attn(hipStream_t stream, int n_head, const float *q, const void *mem_k, const void *mem_v, const void *prm, float scale,
                     const float *slopes, int D, int64_t E, float *out, int64_t Clds, size_t lds) {
-    if (attn_opt_in(lds)) return 1;
+    static std::atomic<bool> done[64] = {};
+    if (attn_opt_in((const void *)k_attn_decode_alibi, done, lds, 64 * 1024)) return 1;
     hipLaunchKernelGGL(k_attn_decode_alibi, dim3((unsigned)n_head), dim3(1024), lds, stream, q, (const __half *)mem_k, (const __half *)mem_v,
                        (const DecParams *)prm, scale, slopes, D, E, out, Clds);
+    return 0;
+}
+int launch_mpt_attn_split(hipStream_t stream, int n_head, int S, const float *q, const void *mem_k, const void *mem_v, const void *prm, float scale,
+                          const float *slopes, int D, int64_t E, int64_t C, float *sc, float *pmax, float *part, float *out, size_t lds) {
+    static std::atomic<bool> done[64] = {};  // (k_attn_split_vp_alibi has 8.1 KiB of static arrays beside the range's probabilities)
+    if (attn_opt_in((const void *)k_attn_split_vp_alibi, done, lds, 48 * 1024)) return 1;
+    MptSplitArgs a;
+    a.q = q; a.mem_k = (const __half *)mem_k; a.mem_v = (const __half *)mem_v; a.prm = (const DecParams *)prm; a.slopes = slopes;
+    a.scale = scale; a.D = D; a.S = S; a.E = E; a.C = C; a.sc = sc; a.pmax = pmax; a.part = part; a.out = out;
+    const dim3 grid((unsigned)n_head, (unsigned)S);
+    hipLaunchKernelGGL(k_attn_split_scores_alibi, grid, dim3(1024), 0, stream, a);
+    hipLaunchKernelGGL(k_attn_split_vp_alibi, grid, dim3(1024), lds, stream, a);
+    hipLaunchKernelGGL(k_attn_split_merge_alibi, dim3((unsigned)n_head), dim3(128), 0, stream, a);
     return 0;
 }
 int launch_mpt_stage_dump(hipStream_t stream, int f16d, const void *big_args, void *lo, void *hi, float *d, int *sum, size_t lds) {

@@ -803,6 +803,7 @@ static void plan_launch_f16(DecodePlan *p, int av, LaunchCtx cx, bool batch = fa
 // The MPT plan: single-token decode of an MPT graph (LlamaMatch::mpt), block-format weights.  Five launches per layer, every
 // dependency a kernel boundary, one stream:
 //   LayerNorm + Wqkv + K/V store | ALiBi attention | out_proj + residual | LayerNorm + up_proj + GELU | down_proj + residual
+// (av == AV_SPLIT, a long context: the attention as the three position-split launches of kernels/mpt_plan.h, launch_mpt_attn_split)
 // then LayerNorm + the tied lm_head, which taps the embedding row.  The first, the fourth and the last are k_mmvq_big with the LayerNorm
 // staging (XSRC_LNORM) out of the plan's own code object (mpt_plan.hip, with the attention); the two residual launches are the LLaMA
 // plan's own wo / w2 instantiations (EPI_ADD over a plain f32 row).  The reference's per-token copy of the layer's whole V cache is not
@@ -818,12 +819,12 @@ static void launch_big_lnorm(int qt, int epi, const BigArgs &a) {
     b.G = sh.G;
     if (launch_mpt_big(g.stream, qt, epi, &b, sh.G, sh.lds)) die("MPT plan: no k_mmvq_big instantiation for type %d, epilogue %d", qt, epi);
 }
-static void plan_launch_mpt(DecodePlan *p, LaunchCtx cx) {
+static void plan_launch_mpt(DecodePlan *p, int av, LaunchCtx cx) {
     const LlamaMatch &m = p->m;
     const int qt = qt_of(m.wtype);
     const int64_t E = m.E, F = m.F, nbE = E / 32, nbF = F / 32;
     const double bb = (double)blk_bytes(qt);
-    const int64_t Clds = (m.C + 7) & ~(int64_t)7;
+    const int64_t Clds = mpt_attn_rows(m.C, m.H);
     auto big_args = [&](const DecMmvqArgs &a, float *y_out) {
         return big_pack(a, y_out, nullptr, 0, nullptr, 0, nullptr, nullptr, 0, p->hot);  // (no timeline, no probe: the production instantiations)
     };
@@ -850,9 +851,12 @@ static void plan_launch_mpt(DecodePlan *p, LaunchCtx cx) {
             const double bytes = (double)(m.n_past + 1) * E * 4.0 + E * 8.0;
             if (cx.want(GGML_HIP_KCLASS_ATTN, bytes)) {
                 Timed tm(GGML_HIP_KCLASS_ATTN, bytes);
-                if (launch_mpt_attn(g.stream, (int)m.H, p->q, p->mem_k_at(il), p->mem_v_at(il), p->prm, m.kq_scale, p->alibi, (int)m.D, E, p->k_att,
-                                    Clds, attn_decode_lds(Clds, m.D)))
-                    die("MPT plan: the attention's LDS opt-in failed");
+                const int rc = av == AV_SPLIT  // every CU pulls a piece of the cache: the three launches of kernels/mpt_plan.h
+                                   ? launch_mpt_attn_split(g.stream, (int)m.H, p->att_S, p->q, p->mem_k_at(il), p->mem_v_at(il), p->prm, m.kq_scale, p->alibi,
+                                                           (int)m.D, E, m.C, p->att_sc, p->att_pmax, p->att_part, p->k_att, attn_split_chunk_max(m.C, p->att_S) * 2)
+                                   : launch_mpt_attn(g.stream, (int)m.H, p->q, p->mem_k_at(il), p->mem_v_at(il), p->prm, m.kq_scale, p->alibi, (int)m.D, E,
+                                                     p->k_att, Clds, attn_decode_lds(Clds, m.D));
+                if (rc) die("MPT plan: the attention's LDS opt-in failed");
                 HIP_CHECK(hipGetLastError());
             }
         }
@@ -874,7 +878,7 @@ static void plan_launch_mpt(DecodePlan *p, LaunchCtx cx) {
 // the decode launches of a plan, whichever kind it is
 static void plan_launch_decode(DecodePlan *p, int av = AV_SHORT, LaunchCtx cx = {}) {
     if (p->m.mpt)
-        plan_launch_mpt(p, cx);
+        plan_launch_mpt(p, av, cx);
     else if (p->m.f16w)
         plan_launch_f16(p, av, cx);
     else if (p->m.kquant)

@@ -594,7 +594,9 @@ static bool match_mpt_decode(ggml_cgraph *gr, LlamaMatch &m) {
         MATCH(m.n_past + m.N <= m.C && (mpt_attn_queries(m.D, (int64_t)m.n_past + m.N) != 0 || (g.opt_mpt_attn_stream && (m.D == 32 || m.D == 64 || m.D == 128))));
         return true;
     }
-    MATCH(attn_decode_lds((m.C + 7) & ~(int64_t)7, m.D) <= ATTN_DECODE_LDS_MAX);  // (k_attn_decode_alibi's arrays hold the context rounded up to 8)
+    // k_attn_decode_alibi's arrays hold the context rounded up to 8 — or, where the split attention takes the longer rows (option
+    // attn_split, two workgroups and more per head), the rows up to its threshold: a context of any length whose ranges fit
+    MATCH(attn_decode_lds(mpt_attn_rows(m.C, m.H), m.D) <= ATTN_DECODE_LDS_MAX);
     MATCH(big_shape(XSRC_LNORM, EPI_QKV_TM, m.E / 32, 3 * m.E).ok && big_shape(XSRC_LNORM, EPI_GELU, m.E / 32, m.F).ok &&
           big_shape(XSRC_LNORM, EPI_STORE, m.E / 32, m.V).ok && big_shape(XSRC_F32, EPI_ADD, m.E / 32, m.E).ok &&
           big_shape(XSRC_F32, EPI_ADD, m.F / 32, m.E).ok && m.F <= 24 * BIG_T);

@@ -383,6 +383,7 @@ static void count_token_forms(const LlamaMatch &m, int av) {
     if (m.kquant) g.stat_kplan_tokens += (uint64_t)m.N;
     if (m.out_k) g.stat_out_k_tokens += (uint64_t)m.N;
     if (m.mpt) g.stat_mpt_plan_tokens += (uint64_t)m.N;
+    if (m.mpt && long_ctx) g.stat_mpt_split_tokens++;
 }
 static bool try_decode_plan(ggml_cgraph *gr, bool defer_wait = false) {
     g.chain_plan = nullptr;  // any new graph ends the chainable state; a single-token plan run re-arms it below
@@ -827,6 +828,7 @@ static int decode_chain(ggml_cgraph *last, int n, int32_t *out_tokens, float *la
         // (the chain's books are not count_token_forms': no fused_wo_tokens, fused_affine_tokens or split_tokens — values tests read; left as they are)
         if (av != AV_SPLIT && fused_qkv_shape(m, av_heads_split(av)).ok) g.stat_fused_tokens++;
         if (av >= AV_FUSED2) g.stat_fused_heads_tokens++;
+        if (m.mpt && av == AV_SPLIT) g.stat_mpt_split_tokens++;
         if (use_graph) {
             VariantGraphs &vg = plain_graph(p, av, [&] { plan_launch_decode(p, av); });  // (captured here: the chain crossed into a variant no evaluation has captured yet)
             if (!vg.exec2) HIP_CHECK(hipGraphInstantiate(&vg.exec2, vg.graph, nullptr, nullptr, 0));

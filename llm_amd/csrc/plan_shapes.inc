@@ -83,7 +83,7 @@ struct LlamaMatch {
 };
 // Attention variants of the single-token plan (one hipGraph each, chosen per token by the context length: attn_variant):
 //   AV_SHORT  the attention of a head is ONE workgroup: inside the wq|wk|wv launch (k_qkv_attn) where the shape allows, else k_attn_decode
-//   AV_SPLIT  plain wq|wk|wv launch, then the position-split attention over all CUs (k_attn_split_one / the three launches)
+//   AV_SPLIT  plain wq|wk|wv launch, then the position-split attention over all CUs (k_attn_split_one / the three launches; an MPT plan: its own three)
 //   AV_FUSED2 / 3 / 4  k_qkv_attn with 2 / 3 / 4 attention workgroups per head (512 positions each: up to 1024 / 1536 / 2048)
 enum { AV_SHORT = 0, AV_SPLIT = 1, AV_FUSED2 = 2, AV_FUSED3 = 3, AV_FUSED4 = 4, AV_COUNT = 5 };
 enum { TAIL_FIRST = 0, TAIL_AHEAD = 1 };  // flavours of a greedy token's graph (VariantGraphs::tail_exec)
@@ -439,8 +439,21 @@ static bool attn_one_ok(const LlamaMatch &m, int att_S) {
 // The attention variant of a single-token evaluation whose token sits at position T - 1 (see the enum above).  Option
 // fuse_heads (default 1): contexts beyond k_qkv_attn's 512-position register window get 2 / 4 attention workgroups per head inside
 // the wq|wk|wv launch instead of the separate split attention, where the chip has room for them.
+// The MPT plan's own split attention (kernels/mpt_plan.h: three launches, token-major V, the ALiBi bias): option attn_split as above, its
+// default threshold ATTN_SPLIT_MIN_MPT.  Taken where the chip has two workgroups and more per head and the longest range's probabilities
+// (2 bytes a position) fit in a workgroup's LDS.
+static inline int64_t mpt_split_min() { return g.opt_attn_split > 1 ? g.opt_attn_split : ATTN_SPLIT_MIN_MPT; }
+static inline bool mpt_split_from_min(int64_t H, int64_t C) {
+    return g.opt_attn_split && plan_att_S(H) >= 2 && attn_split_chunk_max(C, plan_att_S(H)) * 2 <= ATTN_DECODE_LDS_MAX;
+}
+// positions k_attn_decode_alibi's LDS arrays must hold at context C (the context rounded up to 8): longer rows run on the split attention
+static inline int64_t mpt_attn_rows(int64_t C, int64_t H) {
+    const int64_t C8 = (C + 7) & ~(int64_t)7;
+    return mpt_split_from_min(H, C) ? std::min<int64_t>(C8, (mpt_split_min() + 7) & ~(int64_t)7) : C8;
+}
 static int attn_variant(const LlamaMatch &m, const DecodePlan *p, int64_t T) {
-    if (m.N != 1 || m.mpt) return AV_SHORT;  // (the MPT plan has the one attention: k_attn_decode_alibi over the whole context)
+    if (m.N != 1) return AV_SHORT;
+    if (m.mpt) return mpt_split_from_min(m.H, m.C) && T >= mpt_split_min() ? AV_SPLIT : AV_SHORT;  // (k_attn_decode_alibi | the three split launches)
     const bool split_ok = (!(m.kquant || m.f16w) || attn_one_ok(m, p->att_S)) && attn_split_from_min(m.H);
     if (g.opt_fuse_heads && g.opt_attn_split == 1 && split_ok && T > FUSE_HEADS_MIN && fused_qkv_shape(m).ok) {
         const int S = (int)((T + 511) / 512);  // workgroups per head: 512 positions each

@@ -1,7 +1,10 @@
 """MPT through the drop-in C ABI: the graph of crates/models/mpt/src/lib.rs:93-259 built node by node with the ctypes
 binding (llm_amd.ggml) and executed by ggml_graph_compute on the MI355X: node by node on the generic executor, or — backend
 option plan_mpt, block-format weights, one token, every node offloaded — on the fused MPT plan (csrc/plan_decode.inc
-plan_launch_mpt: five launches per layer, the captured graph replayed), which Mpt.infer_tokens_device chains on the device, or —
+plan_launch_mpt: five launches per layer, the captured graph replayed; from backend option attn_split's threshold on — 1024 positions
+by default — the attention runs split over the positions, seven launches per layer, counter mpt_split_tokens, and with that path a model
+of a longer n_ctx lands on the plan: Mpt(hp, w, n_ctx=65536) does, where ~25.5k was the cap and still is under attn_split = 0), which
+Mpt.infer_tokens_device chains on the device, or —
 option plan_mpt_prompt, the same model, mmq_min tokens and more — on the MPT prompt plan (csrc/plan_mpt_prompt.inc
 plan_launch_mpt_prompt: nine launches per layer around the f16-MFMA GEMMs), which Mpt.feed_prompt feeds batch by batch.  Its
 attention keeps a query tile's score rows in LDS up to n_past + N = 2240 keys (head size 128); batches behind that stay on the plan,
