@@ -921,6 +921,20 @@ GGML_API int ggml_hip_debug_act_quant(int kind, int flags, int64_t rows, int64_t
  * Every output is followed by 256 guard bytes (0xFF before the launch).  0, or -1 for what no call site launches. */
 GGML_API int ggml_hip_debug_mpt(int op, int flag, const float *x, const float *w, float eps, int64_t K, const uint16_t *mem_k,
                                 const uint16_t *mem_v, int H, int D, int n_past, int64_t C, float scale, void *const *out);
+/* The MPT chunk plan (option plan_mpt_chunk, GGML_HIP_PLAN_MPT_CHUNK, default 0; independent of plan_mpt and plan_mpt_prompt): an evaluation
+ * of 2 .. 31 tokens of such a graph that the prompt plan does not take (N < mmq_min, or plan_mpt_prompt = 0) runs with its mat-vecs on
+ * k_mmq_cols in passes of 8 columns (llm_amd/csrc/plan_mpt_chunk.inc; needs option mmq_cols, n_embd 1024 .. 8192).  Counter
+ * mpt_chunk_tokens: its tokens; they count in plan_tokens too and never in generic_graphs.
+ * Test hook of its device code (llm_amd/csrc/kernels/mpt_chunk.h), each piece alone on host arrays.  op 0: the LayerNorm columns — x [N][K],
+ * gain [K], eps, flag 1 = Q8_0's scale kind; out[0..5] = lo, hi, d, sum, dT, sT (the planar rows and ceil(N/8) tables of [K/32][8]),
+ * out[6] (nullable) the normed rows.  op 1: one residual mat-vec of a chunk in `flag` K slices (0 = the plan's choice) — w [K, M], x [N][K],
+ * res [N][M]; out[0] [N][M].  op 2: one EPI_QKV_TM pass — w [K, 3K], x [N <= 8][K], columns col0 .. of a chunk at n_past, mem_k / mem_v
+ * [C][K] f16 in-out; out[0] the Q rows.  op 3: the position-split chunk attention — x = q [N][H*D], gain = the slopes [H], mem_k / mem_v
+ * [C][H*D], queries at n_past .., scale, flag = S workgroups per head; out[0] the merged heads [N][H*D] f32.  Every output and both caches are followed by 256 guard bytes (0xFF before the launch).  0, or -1
+ * for what no call site launches. */
+GGML_API int ggml_hip_debug_mpt_chunk(int op, int flag, const struct ggml_tensor *w, const float *x, const float *gain, float eps, const float *res,
+                                      int64_t K, int N, int col0, int n_past, int64_t C, uint16_t *mem_k, uint16_t *mem_v, int H, int D, float scale,
+                                      void *const *out);
 /* The MPT prompt plan (option plan_mpt_prompt, GGML_HIP_PLAN_MPT_PROMPT, default 0; independent of plan_mpt): an evaluation of mmq_min
  * tokens and more of an MPT graph with block-format weights, f16 caches and head size 32 / 64 / 128, every node offloaded, runs as nine
  * launches per layer (llm_amd/csrc/plan_mpt_prompt.inc).  Counter mpt_prompt_tokens: its tokens; they count in prompt_plan_tokens too

@@ -65,6 +65,7 @@
 #include "kernels/flash_attn.h"
 #include "kernels/mpt_plan.h"
 #include "kernels/mpt_prompt.h"
+#include "kernels/mpt_chunk.h"
 
 // Last words of the library: stderr, and (GGML_HIP_FATAL_LOG=path) a file — a test runner that captures file descriptor 2
 // swallows the message of an abort together with the process.
@@ -972,3 +973,4 @@ int ggml_hip_bench_plan_class(int kclass, int replays, double *ms_total, int64_t
 #include "debug_token.inc"
 #include "debug_mpt.inc"
 #include "debug_mpt_prompt.inc"
+#include "debug_mpt_chunk.inc"

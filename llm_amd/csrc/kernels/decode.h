@@ -485,7 +485,9 @@ __global__ void __launch_bounds__(256) k_quant_row(const float *__restrict__ x, 
 // ---------------------------------------------------------------------------------------------------
 // (the last two: k_mmvq_big alone, the MPT plan's code object mpt_plan.hip — EPI_QKV_TM: ONE matrix of [Q | K | V] rows, Q to f32, K and V
 //  as f16 into token-major caches, no RoPE; EPI_GELU: gelu_table of the row sum)
-enum { EPI_STORE = 0, EPI_ADD = 1, EPI_GATE = 2, EPI_QKV = 3, EPI_QKV_TM = 4, EPI_GELU = 5 };
+// (EPI_ADD_KS: k_mmq_cols alone, the MPT chunk plan's code object mpt_chunk.hip — EPI_ADD over a K slice of the matrix: the weight rows
+//  are QWeight::nb blocks apart while the launch covers DecMmvqArgs::nb of them)
+enum { EPI_STORE = 0, EPI_ADD = 1, EPI_GATE = 2, EPI_QKV = 3, EPI_QKV_TM = 4, EPI_GELU = 5, EPI_ADD_KS = 6 };
 
 struct DecMmvqArgs {
     QWeight w[3];        // STORE/ADD: w[0]; GATE: w[0]=w1, w[1]=w3; QKV: wq, wk, wv

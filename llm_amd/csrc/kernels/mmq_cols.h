@@ -20,6 +20,9 @@
 // of the workgroup: a unit = (group, matrix) costs every wave the same number of steps, nothing is divided at run time, and
 // the eight partial sums of a row meet in LDS in wave order (deterministic).  Then the epilogues of decode_big8.h run
 // (store / +residual / silu(w1 x) * w3 x / RoPE + K,V store per token).
+// The MPT chunk plan's code object (mpt_chunk.hip) instantiates three epilogues more, which no LLaMA plan launches: EPI_QKV_TM (one
+// matrix of [Q | K | V] rows: Q as f32, K and V as f16 rows n_past + col0 + c of token-major caches, no rotation), EPI_GELU
+// (gelu_table of the row sum) and EPI_ADD_KS (EPI_ADD over a K slice: see decode.h).
 // Staging: the activation planes and the [block][8] scale / sum tables (written in that layout by the producing kernels:
 // ColsArgs::dxT, sxT) go to LDS by LDS-DMA in front of the weight ring; the first barrier waits for them only
 // (s_waitcnt vmcnt(ring loads)), not for the ring (12.5 MB chip-wide: 2.7 us at HBM speed).
@@ -146,8 +149,14 @@ __global__ void __launch_bounds__(COLS_T) k_mmq_cols(const ColsArgs ca) {
         const int nq = ncols * nb;  // 16-byte items of a quant plane (columns >= ncols stay as they are: never stored)
         for (int i0 = wave * 64; i0 < nq; i0 += COLS_T) {  // wave-uniform
             if (i0 + lane < nq) {
-                __builtin_amdgcn_global_load_lds((gptr_t)(a.x.lo + i0 + lane), (lptr_t)(s_lo + i0), 16, 0, 0);
-                __builtin_amdgcn_global_load_lds((gptr_t)(a.x.hi + i0 + lane), (lptr_t)(s_hi + i0), 16, 0, 0);
+                if constexpr (EPI == EPI_ADD_KS) {  // a column's blocks lie a whole row of the activation apart, not nb
+                    const int src = i0 + lane + ((i0 + lane) / nb) * ((int)a.w[0].nb - nb);
+                    __builtin_amdgcn_global_load_lds((gptr_t)(a.x.lo + src), (lptr_t)(s_lo + i0), 16, 0, 0);
+                    __builtin_amdgcn_global_load_lds((gptr_t)(a.x.hi + src), (lptr_t)(s_hi + i0), 16, 0, 0);
+                } else {
+                    __builtin_amdgcn_global_load_lds((gptr_t)(a.x.lo + i0 + lane), (lptr_t)(s_lo + i0), 16, 0, 0);
+                    __builtin_amdgcn_global_load_lds((gptr_t)(a.x.hi + i0 + lane), (lptr_t)(s_hi + i0), 16, 0, 0);
+                }
             }
         }
         const int nt = 2 * nb;  // 16-byte items of a [nb][8] table
@@ -193,7 +202,10 @@ __global__ void __launch_bounds__(COLS_T) k_mmq_cols(const ColsArgs ca) {
             c.wd = sg == 0 ? wdA : wdB;
             if constexpr (QT == QT_Q4_1 || QT == QT_Q5_1) c.wm = sg == 0 ? wmA : wmB;
         }
-        c.row_blk = (uint32_t)(m0 + jrow) * (uint32_t)nb;
+        if constexpr (EPI == EPI_ADD_KS)  // a K slice: the rows stay a whole row's blocks apart
+            c.row_blk = (uint32_t)(m0 + jrow) * (uint32_t)a.w[0].nb;
+        else
+            c.row_blk = (uint32_t)(m0 + jrow) * (uint32_t)nb;
     };
     // A step past the wave's last one is a DUMMY that reads ColsArgs::hot (one line, a cache hit): every ring slot is refilled
     // unconditionally, so the loads in flight are a compile-time constant at every wait (k_mmvq_big's `issue`, decode_big.h).
@@ -371,8 +383,19 @@ __global__ void __launch_bounds__(COLS_T) k_mmq_cols(const ColsArgs ca) {
             const float v = total(lg, 0, row, c);
             if constexpr (EPI == EPI_STORE) {
                 a.dst[(int64_t)c * ca.ldd + m] = v;
-            } else if constexpr (EPI == EPI_ADD) {
+            } else if constexpr (EPI == EPI_ADD || EPI == EPI_ADD_KS) {
                 a.dst[(int64_t)c * ca.ldd + m] = v + a.res[(int64_t)c * ca.ldr + m];
+            } else if constexpr (EPI == EPI_GELU) {
+                a.dst[(int64_t)c * ca.ldd + m] = gelu_table(v);
+            } else if constexpr (EPI == EPI_QKV_TM) {  // one matrix of [Q | K | V] rows (Egqa each): Q as f32, K and V as f16 rows of token-major caches
+                const int E = (int)a.Egqa;
+                const int64_t p = (int64_t)a.prm->n_past + ca.col0 + c;
+                if (m < E)
+                    a.dst[(int64_t)c * ca.ldd + m] = v;
+                else if (m < 2 * E)
+                    a.mem_k[p * E + (m - E)] = __float2half_rn(v);
+                else
+                    a.mem_v[p * E + (m - 2 * E)] = __float2half_rn(v);
             } else {
                 a.dst[(int64_t)c * ca.ldd + m] = silu_table(v) * total(lg, 1, row, c);
             }

@@ -206,9 +206,10 @@ static void plan_pool_layout(DecodePlan *p, PoolCarver &c) {
     const bool okq = m.out_k && !m.prompt;  // the Q8_K rows of the final norm for an out_k model's lm_head (plan_lm_head_k): R rows of E
     // scratch of the split attention, and the hand-off granules of the in-launch attention exchanges: one set per LAYER for a single token (the tag is the token's epoch alone)
     const size_t Lg = one ? (size_t)m.L : 1;
-    c.take(p->att_sc, (size_t)m.H * m.C * 4);
-    c.take(p->att_pmax, (size_t)m.H * S * 4);
-    c.take(p->att_part, (size_t)m.H * S * m.D * 4);
+    const size_t QT = m.mpt && multi ? 32 : 1;  // the MPT chunk plan's split attention keeps a 32-query tile's scores, maxima and partial rows
+    c.take(p->att_sc, QT * m.H * m.C * 4);
+    c.take(p->att_pmax, QT * m.H * S * 4);
+    c.take(p->att_part, QT * m.H * S * m.D * 4);
     c.take(p->att_mxg, Lg * m.H * S * 8);
     c.take(p->att_sumg, Lg * m.H * S * 16);
     c.take(p->att_partg, one ? Lg * m.H * S * m.D * 8 : 0);

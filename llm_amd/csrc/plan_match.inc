@@ -414,6 +414,17 @@ static bool match_mpt_norm(const ggml_tensor *mul, Claims &c, const ggml_tensor 
     c.take(nr);
     return true;
 }
+// what the MPT chunk plan's launches (plan_mpt_chunk.inc) need of the shape: every mat-vec on k_mmq_cols — down_proj, whose K may exceed the
+// LDS staging, as equal K slices (mpt_chunk_slices) —, rows of whole 16-row groups, the LayerNorm's row in registers (E <= 8192; E >= 1024:
+// every wave of k_mmq_cols has a step), and the split attention's fit (32 rows of the longest range's probabilities in LDS: mpt_chunk_attn_lds)
+static bool mpt_chunk_shape_ok(const LlamaMatch &m) {
+    const int nbE = (int)(m.E / 32), nbF = (int)(m.F / 32);
+    const int64_t T = (int64_t)m.n_past + m.N;
+    return m.E >= 1024 && m.E <= 8192 && m.E % 16 == 0 && m.V % 16 == 0 && T <= m.C && (m.D == 32 || m.D == 64 || m.D == 128) &&
+           cols_shape((int)(3 * m.E / 16), 1, nbE).kc > 0 && cols_shape((int)(m.E / 16), 1, nbE).kc > 0 && cols_shape((int)(m.F / 16), 1, nbE).kc > 0 &&
+           cols_shape((int)(m.V / 16), 1, nbE).kc > 0 && mpt_chunk_slices((int)(m.E / 16), nbF) > 0 &&
+           mpt_chunk_attn_lds(attn_split_chunk_max(m.C, plan_att_S(m.H))) <= 150 * 1024;
+}
 static bool match_mpt_decode(ggml_cgraph *gr, LlamaMatch &m) {
     const int n = gr->n_nodes;
     MATCH(n >= 39);
@@ -426,10 +437,14 @@ static bool match_mpt_decode(ggml_cgraph *gr, LlamaMatch &m) {
     MATCH(is_op(last, GGML_OP_MUL_MAT) && last->type == GGML_TYPE_F32 && last->ne[1] >= 1 && last->ne[1] <= PROMPT_PLAN_MAX && last->ne[2] == 1 && last->ne[3] == 1);
     m.N = (int)last->ne[1];
     // one token: the MPT plan; a batch of mmq_min tokens and more (the LLaMA prompt plan's rule): the MPT prompt plan, on the default f16
-    // GEMM path only; the chunks between have no plan
-    m.prompt = m.N > 1;
-    if (m.prompt)
-        MATCH(g.opt_plan_mpt_prompt && g.opt_plan_prompt && !g.opt_mmq_i8 && m.N > 8 && g.opt_mmq_min > 0 && m.N >= g.opt_mmq_min);
+    // GEMM path only; a chunk of 2 .. MULTI_MAX_N tokens that the prompt plan does not take: the MPT chunk plan (option plan_mpt_chunk)
+    const bool prompt_ok = g.opt_plan_mpt_prompt && g.opt_plan_prompt && !g.opt_mmq_i8 && m.N > 8 && g.opt_mmq_min > 0 && m.N >= g.opt_mmq_min;
+    const bool chunk = m.N >= 2 && m.N <= MULTI_MAX_N && !prompt_ok;
+    m.prompt = m.N > 1 && !chunk;
+    if (chunk)
+        MATCH(g.opt_plan_mpt_chunk && g.opt_mmq_cols);
+    else if (m.prompt)
+        MATCH(prompt_ok);
     else
         MATCH(g.opt_plan_mpt && g.opt_big);
     const int64_t N = m.N;
@@ -594,6 +609,7 @@ static bool match_mpt_decode(ggml_cgraph *gr, LlamaMatch &m) {
         MATCH(m.n_past + m.N <= m.C && (mpt_attn_queries(m.D, (int64_t)m.n_past + m.N) != 0 || (g.opt_mpt_attn_stream && (m.D == 32 || m.D == 64 || m.D == 128))));
         return true;
     }
+    if (chunk) return mpt_chunk_shape_ok(m);
     // k_attn_decode_alibi's arrays hold the context rounded up to 8 — or, where the split attention takes the longer rows (option
     // attn_split, two workgroups and more per head), the rows up to its threshold: a context of any length whose ranges fit
     MATCH(attn_decode_lds(mpt_attn_rows(m.C, m.H), m.D) <= ATTN_DECODE_LDS_MAX);

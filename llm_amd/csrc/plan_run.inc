@@ -382,7 +382,8 @@ static void count_token_forms(const LlamaMatch &m, int av) {
     if (av >= AV_FUSED2) g.stat_fused_heads_tokens++;
     if (m.kquant) g.stat_kplan_tokens += (uint64_t)m.N;
     if (m.out_k) g.stat_out_k_tokens += (uint64_t)m.N;
-    if (m.mpt) g.stat_mpt_plan_tokens += (uint64_t)m.N;
+    if (m.mpt && m.N == 1) g.stat_mpt_plan_tokens++;
+    if (m.mpt && m.N > 1) g.stat_mpt_chunk_tokens += (uint64_t)m.N;
     if (m.mpt && long_ctx) g.stat_mpt_split_tokens++;
 }
 static bool try_decode_plan(ggml_cgraph *gr, bool defer_wait = false) {
@@ -421,7 +422,9 @@ static bool try_decode_plan(ggml_cgraph *gr, bool defer_wait = false) {
     // the attention variant for this context length (a graph each of the same plan)
     const int av = attn_variant(m, p, m.n_past + 1);
     auto launch = [&] {
-        if (m.N > 1 && !m.kquant && !m.f16w)
+        if (m.mpt && m.N > 1)
+            plan_launch_mpt_chunk(p);
+        else if (m.N > 1 && !m.kquant && !m.f16w)
             plan_launch_multi(p);
         else
             plan_launch_decode(p, av);

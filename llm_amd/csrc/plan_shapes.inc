@@ -533,6 +533,13 @@ static ColsShape cols_shape(int ngroups, int nsub, int nb) {
     if (s.lds > 150 * 1024) s.G = 0, s.kc = 0;
     return s;
 }
+// K slices of a matrix of nb blocks a row whose staging may not fit: the fewest equal slices, multiples of 4 blocks each, that
+// cols_shape takes (1: the whole row; 0: none) — the MPT chunk plan's down_proj (plan_mpt_chunk.inc: consecutive EPI_ADD_KS launches)
+static int mpt_chunk_slices(int ngroups, int nb) {
+    for (int ns = 1; ns <= 8; ns++)
+        if (nb % (4 * ns) == 0 && cols_shape(ngroups, 1, nb / ns).kc > 0) return ns;
+    return 0;
+}
 // whether a launch of the multi-token plan can run on k_mmq_cols (else k_mmvq_big8)
 static bool cols_ok(int M_total, int nsub, int64_t nb, std::initializer_list<int64_t> Ms) {
     if (!g.opt_mmq_cols) return false;

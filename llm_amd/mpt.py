@@ -9,7 +9,11 @@ option plan_mpt_prompt, the same model, mmq_min tokens and more — on the MPT p
 plan_launch_mpt_prompt: nine launches per layer around the f16-MFMA GEMMs), which Mpt.feed_prompt feeds batch by batch.  Its
 attention keeps a query tile's score rows in LDS up to n_past + N = 2240 keys (head size 128); batches behind that stay on the plan,
 on the streaming attention kernel (option mpt_attn_stream, default 1; 0 = such a batch runs on the executor; counter
-mpt_stream_tokens), so a long context is fed on the plan to its end.
+mpt_stream_tokens), so a long context is fed on the plan to its end; or —
+option plan_mpt_chunk, the same model, 2 .. 31 tokens below mmq_min (what feed_prompt(tokens, n_batch=8), the reference's default, feeds) —
+on the MPT chunk plan (csrc/plan_mpt_chunk.inc plan_launch_mpt_chunk: every mat-vec on k_mmq_cols in passes of 8 columns, down_proj of
+MPT-7B as two K slices; counter mpt_chunk_tokens; MPT-7B Q4_0 at n_batch 8: 412 -> 1083 prompt tok/s against the executor, profiles/mpt_chunk.json).  It declines, with nothing executed, offload=False, K-quant or F16 weights, f32 K/V,
+head size 16, n_embd < 1024 and a chunk that ends behind n_ctx: those run on the executor.
 LayerNorms without bias, no linear biases at all; Wqkv split into [Q | K | V] blocks of n_embd rows (views at 0,
 E and 2E); K and V stored token-major, V re-laid by cpy(permute(.., 1, 2, 0, 3)) at every use; ALiBi attention bias
 with the model's alibi_bias_max, the chain built out of place; lm_head tied to transformer.wte.weight (lib.rs:244).
