@@ -935,6 +935,19 @@ GGML_API int ggml_hip_debug_mpt(int op, int flag, const float *x, const float *w
 GGML_API int ggml_hip_debug_mpt_chunk(int op, int flag, const struct ggml_tensor *w, const float *x, const float *gain, float eps, const float *res,
                                       int64_t K, int N, int col0, int n_past, int64_t C, uint16_t *mem_k, uint16_t *mem_v, int H, int D, float scale,
                                       void *const *out);
+/* The batched MPT step (option plan_mpt_batch, GGML_HIP_PLAN_MPT_BATCH, default 0; independent of the other MPT options): under it
+ * ggml_hip_decode_batch and ggml_hip_decode_batch_greedy take 2 .. 8 single-token graphs of ONE MPT model with block-format weights, f16
+ * caches, head size 32 / 64 / 128 and n_embd 1024 .. 8192, every node offloaded (llm_amd/csrc/plan_mpt_batch.inc; needs options plan_batch
+ * and mmq_cols), instead of answering -1; the sampled, request and pool entries keep declining MPT graphs.  Counter mpt_batch_steps: its
+ * steps; they count in batch_decode_steps, batch_decode_tokens and plan_tokens too and never in generic_graphs.
+ * Test hook of its device code (llm_amd/csrc/kernels/mpt_batch.h), each piece alone on host arrays.  op 0: the batched ALiBi decode
+ * attention — x = q [B][H*D], slopes [H], pos [B], mem_k / mem_v = B pointers to [C][H*D] f16 token-major caches (read only), scale, W
+ * workgroups per head (1 .. 16); out[0] the merged heads [B][H*D] f32.  op 1: one EPI_QKV_TM_BATCH pass — w [K, 3K], x [B][K], the B caches
+ * [C][K] in-out (column c's K and V rows land in row pos[c] of cache c, each cache followed by its guard); out[0] the Q rows [B][K].
+ * Every output is followed by 256 guard bytes (0xFF before the launch).  0, or -1 for what no call site launches. */
+GGML_API int ggml_hip_debug_mpt_batch(int op, int W, const struct ggml_tensor *w, const float *x, const float *slopes, int B, const int32_t *pos,
+                                      int64_t C, uint16_t *const *mem_k, uint16_t *const *mem_v, int64_t K, int H, int D, float scale,
+                                      void *const *out);
 /* The MPT prompt plan (option plan_mpt_prompt, GGML_HIP_PLAN_MPT_PROMPT, default 0; independent of plan_mpt): an evaluation of mmq_min
  * tokens and more of an MPT graph with block-format weights, f16 caches and head size 32 / 64 / 128, every node offloaded, runs as nine
  * launches per layer (llm_amd/csrc/plan_mpt_prompt.inc).  Counter mpt_prompt_tokens: its tokens; they count in prompt_plan_tokens too

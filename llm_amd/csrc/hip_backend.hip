@@ -66,6 +66,7 @@
 #include "kernels/mpt_plan.h"
 #include "kernels/mpt_prompt.h"
 #include "kernels/mpt_chunk.h"
+#include "kernels/mpt_batch.h"
 
 // Last words of the library: stderr, and (GGML_HIP_FATAL_LOG=path) a file — a test runner that captures file descriptor 2
 // swallows the message of an abort together with the process.
@@ -974,3 +975,4 @@ int ggml_hip_bench_plan_class(int kclass, int replays, double *ms_total, int64_t
 #include "debug_mpt.inc"
 #include "debug_mpt_prompt.inc"
 #include "debug_mpt_chunk.inc"
+#include "debug_mpt_batch.inc"

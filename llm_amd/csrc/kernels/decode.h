@@ -487,7 +487,9 @@ __global__ void __launch_bounds__(256) k_quant_row(const float *__restrict__ x, 
 //  as f16 into token-major caches, no RoPE; EPI_GELU: gelu_table of the row sum)
 // (EPI_ADD_KS: k_mmq_cols alone, the MPT chunk plan's code object mpt_chunk.hip — EPI_ADD over a K slice of the matrix: the weight rows
 //  are QWeight::nb blocks apart while the launch covers DecMmvqArgs::nb of them)
-enum { EPI_STORE = 0, EPI_ADD = 1, EPI_GATE = 2, EPI_QKV = 3, EPI_QKV_TM = 4, EPI_GELU = 5, EPI_ADD_KS = 6 };
+// (EPI_QKV_TM_BATCH: k_mmq_cols alone, the batched MPT step's code object mpt_batch.hip — EPI_QKV_TM with column c's K and V rows at
+//  position BatchCols::pos[c] of session c's caches)
+enum { EPI_STORE = 0, EPI_ADD = 1, EPI_GATE = 2, EPI_QKV = 3, EPI_QKV_TM = 4, EPI_GELU = 5, EPI_ADD_KS = 6, EPI_QKV_TM_BATCH = 7 };
 
 struct DecMmvqArgs {
     QWeight w[3];        // STORE/ADD: w[0]; GATE: w[0]=w1, w[1]=w3; QKV: wq, wk, wv

@@ -22,7 +22,8 @@
 // (store / +residual / silu(w1 x) * w3 x / RoPE + K,V store per token).
 // The MPT chunk plan's code object (mpt_chunk.hip) instantiates three epilogues more, which no LLaMA plan launches: EPI_QKV_TM (one
 // matrix of [Q | K | V] rows: Q as f32, K and V as f16 rows n_past + col0 + c of token-major caches, no rotation), EPI_GELU
-// (gelu_table of the row sum) and EPI_ADD_KS (EPI_ADD over a K slice: see decode.h).
+// (gelu_table of the row sum) and EPI_ADD_KS (EPI_ADD over a K slice: see decode.h).  The batched MPT step's (mpt_batch.hip) instantiates
+// EPI_QKV_TM_BATCH: EPI_QKV_TM with column c's K and V rows at BatchCols::pos[c] of session c's caches (ColsArgs::bc, kv_off).
 // Staging: the activation planes and the [block][8] scale / sum tables (written in that layout by the producing kernels:
 // ColsArgs::dxT, sxT) go to LDS by LDS-DMA in front of the weight ring; the first barrier waits for them only
 // (s_waitcnt vmcnt(ring loads)), not for the ring (12.5 MB chip-wide: 2.7 us at HBM speed).
@@ -396,6 +397,15 @@ __global__ void __launch_bounds__(COLS_T) k_mmq_cols(const ColsArgs ca) {
                     a.mem_k[p * E + (m - E)] = __float2half_rn(v);
                 else
                     a.mem_v[p * E + (m - 2 * E)] = __float2half_rn(v);
+            } else if constexpr (EPI == EPI_QKV_TM_BATCH) {  // EPI_QKV_TM of a batched step: column c's K and V rows go to ITS session's caches
+                const int E = (int)a.Egqa;
+                if (m < E) {
+                    a.dst[(int64_t)c * ca.ldd + m] = v;
+                } else {
+                    const int64_t p = ca.bc->pos[ca.col0 + c];
+                    __half *row = (m < 2 * E ? ca.bc->mem_k : ca.bc->mem_v)[ca.col0 + c] + ca.kv_off + p * E;
+                    if (p >= 0 && p < a.C) row[m < 2 * E ? m - E : m - 2 * E] = __float2half_rn(v);  // (always: the entry checks n_past + steps <= C)
+                }
             } else {
                 a.dst[(int64_t)c * ca.ldd + m] = silu_table(v) * total(lg, 1, row, c);
             }

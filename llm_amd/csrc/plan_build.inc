@@ -305,6 +305,7 @@ static DecodePlan *build_plan(const LlamaMatch &m, std::vector<uint64_t> sig, bo
     if (m.embedding && !batch && !m.mpt) p->emb_out = (float *)dev_ptr(m.embedding);
     if (m.logits && !batch && !m.mpt) p->logits_out = dev_ptr(m.logits);
     p->att_S = plan_att_S(m.H);
+    if (batch && m.mpt) p->att_S = mpt_batch_W(g.num_cus, m.H);  // the batched attention's W workgroups a head: the pool holds [H][B <= 8][W] maxima and partial rows
     PoolCarver sizes{nullptr};
     plan_pool_layout(p, sizes);
     dev_malloc((void **)&p->pool, sizes.off, "a decode plan's activation pool");

@@ -425,6 +425,15 @@ static bool mpt_chunk_shape_ok(const LlamaMatch &m) {
            cols_shape((int)(m.V / 16), 1, nbE).kc > 0 && mpt_chunk_slices((int)(m.E / 16), nbF) > 0 &&
            mpt_chunk_attn_lds(attn_split_chunk_max(m.C, plan_att_S(m.H))) <= 150 * 1024;
 }
+// The batched MPT step (plan_run.inc decode_batch_steps; option plan_mpt_batch): while this holds B > 0 the matcher holds a single-token
+// graph to the preconditions of a COLUMN of that step — the chunk plan's at N = B and the batched attention's fit — not to the decode plan's
+static thread_local int tl_mpt_batch_cols = 0;
+// the chunk plan's shape at N = B columns, and a share's p values of the batched attention in LDS (kernels/mpt_batch.h)
+static bool mpt_batch_shape_ok(const LlamaMatch &m, int B) {
+    LlamaMatch mc = m;
+    mc.N = 1;  // (a column ends at n_past + 1)
+    return mpt_chunk_shape_ok(mc) && mpt_batch_attn_lds(m.C, B, mpt_batch_W(g.num_cus, m.H)) <= 150 * 1024;
+}
 static bool match_mpt_decode(ggml_cgraph *gr, LlamaMatch &m) {
     const int n = gr->n_nodes;
     MATCH(n >= 39);
@@ -441,7 +450,10 @@ static bool match_mpt_decode(ggml_cgraph *gr, LlamaMatch &m) {
     const bool prompt_ok = g.opt_plan_mpt_prompt && g.opt_plan_prompt && !g.opt_mmq_i8 && m.N > 8 && g.opt_mmq_min > 0 && m.N >= g.opt_mmq_min;
     const bool chunk = m.N >= 2 && m.N <= MULTI_MAX_N && !prompt_ok;
     m.prompt = m.N > 1 && !chunk;
-    if (chunk)
+    const bool column = tl_mpt_batch_cols > 0;
+    if (column)
+        MATCH(m.N == 1 && g.opt_plan_mpt_batch && g.opt_mmq_cols);
+    else if (chunk)
         MATCH(g.opt_plan_mpt_chunk && g.opt_mmq_cols);
     else if (m.prompt)
         MATCH(prompt_ok);
@@ -610,6 +622,7 @@ static bool match_mpt_decode(ggml_cgraph *gr, LlamaMatch &m) {
         return true;
     }
     if (chunk) return mpt_chunk_shape_ok(m);
+    if (column) return mpt_batch_shape_ok(m, tl_mpt_batch_cols);
     // k_attn_decode_alibi's arrays hold the context rounded up to 8 — or, where the split attention takes the longer rows (option
     // attn_split, two workgroups and more per head), the rows up to its threshold: a context of any length whose ranges fit
     MATCH(attn_decode_lds(mpt_attn_rows(m.C, m.H), m.D) <= ATTN_DECODE_LDS_MAX);

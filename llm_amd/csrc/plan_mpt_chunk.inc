@@ -20,13 +20,14 @@ static void mpt_cols_launch(int qt, int epi, ColsArgs c, int M_total) {
         with_qt(qt, [&](auto QT) { launch_cols<CT(QT), EPI_ADD>(c, M_total); });
     else if (epi == EPI_STORE)
         with_qt(qt, [&](auto QT) { launch_cols<CT(QT), EPI_STORE>(c, M_total); });
-    else if (launch_mpt_cols(g.stream, qt, epi, &c, sh.G, sh.lds))
+    else if (epi == EPI_QKV_TM_BATCH ? launch_mpt_batch_cols(g.stream, qt, &c, sh.G, sh.lds) : launch_mpt_cols(g.stream, qt, epi, &c, sh.G, sh.lds))
         die("MPT chunk plan: no k_mmq_cols instantiation for type %d, epilogue %d", qt, epi);
     HIP_CHECK(hipGetLastError());
 }
 // One mat-vec of the chunk over N columns: passes of 8 columns, `slices` equal K slices each (1 but for EPI_ADD).  a: the whole-chunk
-// arguments (x, dst, res: row 0; nb: blocks of a whole row), dT / sT: the [block][8] tables, one per pass
-static void mpt_cols_block(int qt, int epi, const DecMmvqArgs &a, int N, int64_t ldd, int64_t ldr, int M_total, const float *dT, const int *sT, int slices) {
+// arguments (x, dst, res: row 0; nb: blocks of a whole row), dT / sT: the [block][8] tables, one per pass; bc, kv_off: EPI_QKV_TM_BATCH's
+static void mpt_cols_block(int qt, int epi, const DecMmvqArgs &a, int N, int64_t ldd, int64_t ldr, int M_total, const float *dT, const int *sT, int slices,
+                           const BatchCols *bc = nullptr, int64_t kv_off = 0) {
     const int64_t nb = a.nb, nbs = nb / slices;
     for (int c0 = 0; c0 < N; c0 += 8) {
         for (int s = 0; s < slices; s++) {
@@ -47,6 +48,7 @@ static void mpt_cols_block(int qt, int epi, const DecMmvqArgs &a, int N, int64_t
             c.dxT = dT + ((int64_t)(c0 / 8) * nb + b0) * 8;
             c.sxT = sT + ((int64_t)(c0 / 8) * nb + b0) * 8;
             c.hot = g.hot_line;
+            c.bc = bc; c.kv_off = kv_off;
             if (slices > 1) {  // the slice's first block of every weight row; the rows stay QWeight::nb blocks apart
                 QWeight &w = c.d.w[0];
                 w.qs += b0 * 16;

@@ -925,7 +925,14 @@ static int decode_batch_steps(ggml_cgraph *const *graphs, int B, int n_steps, in
     std::vector<uint64_t> sig;
     for (int c = 0; c < B; c++) {
         LlamaMatch &m = ms[(size_t)c];
-        if (!match_llama_decode(graphs[c], m)) return -1;
+        if (!match_llama_decode(graphs[c], m)) {  // not LLaMA's graph: a column of the batched MPT step (option plan_mpt_batch; the greedy chain alone, as for one session), or nothing
+            if (!g.opt_plan_mpt_batch || smp || req) return -1;
+            m = LlamaMatch{};
+            tl_mpt_batch_cols = B;
+            const bool ok = match_mpt_decode(graphs[c], m);
+            tl_mpt_batch_cols = 0;
+            if (!ok) return -1;
+        }
         if (m.kquant && !(g.opt_plan_batch_k && g.opt_plan_k)) return -1;  // a K-quant model: under option plan_batch_k, on the K plan
         if (m.N != 1 || m.prompt || !m.wte || !m.output || !m.embd || !m.logits || !m.embedding) return -1;
         const int room = req ? std::max(1, std::min(n_steps, (int)req->ends[c].budget)) : n_steps;  // (a budget out of range is declined below)
@@ -938,7 +945,8 @@ static int decode_batch_steps(ggml_cgraph *const *graphs, int B, int n_steps, in
     // the whole context in k_attn_decode's LDS arrays (a column may sit anywhere in it), 8 Q8 columns of the widest row in k_mmvq_big8's
     // (an F16 model: k_mmvq_f16 stages as many columns per pass as its LDS holds; a K-quant model: so does launch_mmvq_kn, and what a
     // column of the K plan needs the matcher has checked for every graph)
-    if (attn_decode_lds(ms[0].C, ms[0].D) > ATTN_DECODE_LDS_MAX || (!ms[0].f16w && !ms[0].kquant && !multi_shape_ok(ms[0], B))) return -1;
+    // (an MPT column: the matcher has held every graph to the batched step's shape, mpt_batch_shape_ok)
+    if (!ms[0].mpt && (attn_decode_lds(ms[0].C, ms[0].D) > ATTN_DECODE_LDS_MAX || (!ms[0].f16w && !ms[0].kquant && !multi_shape_ok(ms[0], B)))) return -1;
     if (smp && !batch_sample_ok(*smp, B, ms[0].V)) return -1;
     if (req && !chain_requests_ok(*req, B, ms[0].V, 1, n_steps)) return -1;
     ws_reset();
@@ -985,12 +993,13 @@ static int decode_batch_steps(ggml_cgraph *const *graphs, int B, int n_steps, in
     h2d_small((char *)p->prm, &hp, sizeof(hp));
     h2d_small((char *)p->bcols, &hb, sizeof(hb));
     std::vector<int32_t> sample_back;  // a sampled chain's read-back: generator states, then ids
+    const auto launch = [&] { mb.mpt ? plan_launch_mpt_batch(p) : plan_launch_batch(p); };
     const auto step = [&] {
         if (g.opt_graph && !g.timing.on) {
-            HIP_CHECK(hipGraphLaunch(plain_graph(p, AV_SHORT, [&] { plan_launch_batch(p); }).exec, g.stream));
+            HIP_CHECK(hipGraphLaunch(plain_graph(p, AV_SHORT, launch).exec, g.stream));
             p->replays++;
         } else {
-            plan_launch_batch(p);
+            launch();
         }
     };
     step();
@@ -1049,6 +1058,7 @@ static int decode_batch_steps(ggml_cgraph *const *graphs, int B, int n_steps, in
         g.stat_batch_k_steps += (uint64_t)n_steps;
     }
     if (ms[0].out_k) g.stat_out_k_tokens += (uint64_t)B * (uint64_t)n_steps;
+    if (ms[0].mpt) g.stat_mpt_batch_steps += (uint64_t)n_steps;
     if (smp || (req && req->any_sampled(B))) {  // (a sampled step is not a greedy one: batch_chain_* count ggml_hip_decode_batch_greedy's alone)
         g.stat_batch_sample_steps += (uint64_t)(n_steps - 1);
         g.stat_batch_sample_tokens += (uint64_t)(n_steps - 1) * (uint64_t)B;

@@ -14,6 +14,9 @@ option plan_mpt_chunk, the same model, 2 .. 31 tokens below mmq_min (what feed_p
 on the MPT chunk plan (csrc/plan_mpt_chunk.inc plan_launch_mpt_chunk: every mat-vec on k_mmq_cols in passes of 8 columns, down_proj of
 MPT-7B as two K slices; counter mpt_chunk_tokens; MPT-7B Q4_0 at n_batch 8: 412 -> 1083 prompt tok/s against the executor, profiles/mpt_chunk.json).  It declines, with nothing executed, offload=False, K-quant or F16 weights, f32 K/V,
 head size 16, n_embd < 1024 and a chunk that ends behind n_ctx: those run on the executor.
+Several sessions of one model (Mpt.new_session) decode one step together through evaluate_batch / infer_tokens_batch: under option
+plan_mpt_batch as ONE pass over the weights (csrc/plan_mpt_batch.inc plan_launch_mpt_batch; counter mpt_batch_steps; rates in
+profiles/mpt_batch.json), one after the other otherwise.
 LayerNorms without bias, no linear biases at all; Wqkv split into [Q | K | V] blocks of n_embd rows (views at 0,
 E and 2E); K and V stored token-major, V re-laid by cpy(permute(.., 1, 2, 0, 3)) at every use; ALiBi attention bias
 with the model's alibi_bias_max, the chain built out of place; lm_head tied to transformer.wte.weight (lib.rs:244).
@@ -110,10 +113,35 @@ class Mpt(Resident):
             self.evaluate([int(ids[i])])
         return ids, self.last_logits
 
+    def new_session(self):
+        """Another session of this model: the model's resident weight tensors, its own f16 K/V memory and n_past (0).  Its free()
+        frees that memory alone; free it before the model."""
+        s = Mpt.__new__(Mpt)
+        s.hp, s.C, s.ctx, s.t, s.offload, s.last_logits, s.n_past = self.hp, self.C, None, self.t, self.offload, None, 0
+        n_kv = self.hp["n_layer"] * self.C * self.hp["n_embd"]
+        s.sctx = G.Context(2 * n_kv * 2 + (1 << 16))
+        s.memory_k = s.sctx.new_tensor(G.TYPE_F16, n_kv).set_name("memory_k").offload_no_scratch()
+        s.memory_v = s.sctx.new_tensor(G.TYPE_F16, n_kv).set_name("memory_v").offload_no_scratch()
+        return s
+
+    def free(self):
+        self.sctx.free()
+        if self.ctx is not None:  # (a session of new_session owns no weights)
+            self.ctx.free()
+
     def _evaluate_in(self, ctx0, tokens):
         """evaluate's graph in ctx0, computed: (logits [N, n_vocab], the graph)."""
+        logits, gf = self._build(ctx0, tokens)
+        gf.compute()
+        self.n_past += len(tokens)
+        out = logits.read_data().reshape(len(tokens), self.hp["n_vocab"]).copy()
+        self.last_logits = out[-1]
+        return out, gf
+
+    def _build(self, ctx0, tokens):
+        """evaluate's graph in ctx0, not computed: (the logits node, the graph)."""
         hp, t = self.hp, self.t
-        E, H, L, V = hp["n_embd"], hp["n_head"], hp["n_layer"], hp["n_vocab"]
+        E, H, L = hp["n_embd"], hp["n_head"], hp["n_layer"]
         D, N, P, C = E // H, len(tokens), self.n_past, self.C
         T = P + N
         off = (lambda x: x.offload()) if self.offload else (lambda x: x)
@@ -155,8 +183,75 @@ class Mpt(Resident):
         x = ln(x, "transformer.norm_f.weight")  # :236-237
         logits = ctx0.op_mul_mat(t["transformer.wte.weight"], x)  # :244, tied to the input embedding
         gf.build_forward_expand(logits)
-        gf.compute()
-        self.n_past = T
-        out = logits.read_data().reshape(N, V).copy()
-        self.last_logits = out[-1]
-        return out, gf
+        return logits, gf
+
+
+def _batch_graphs(sessions, tokens):
+    """every session's unchanged single-token graph at its own position, not computed: ([compute contexts], [(logits node, graph)], the
+    graph pointers as the batched entries take them)"""
+    ctxs, built = [], []
+    for s, tok in zip(sessions, tokens):
+        ctxs.append(s._ctx0(1, kq_copies=4))
+        built.append(s._build(ctxs[-1], [int(tok)]))
+    return ctxs, built, (C.c_void_p * len(built))(*[C.cast(gf.ptr, C.c_void_p).value for _, gf in built])
+
+
+def evaluate_batch(sessions, tokens):
+    """One decode step of several sessions of one model (Mpt and its new_session()s), tokens[i] for sessions[i]: each session's
+    single-token graph is built and the graphs go to ggml_hip_decode_batch together — under backend option plan_mpt_batch (default 0) 2 .. 8
+    sessions of a block-format model run as ONE pass over the weights (csrc/plan_mpt_batch.inc plan_launch_mpt_batch: the chunk plan's
+    mat-vecs at N = B, K/V rows placed and the ALiBi attention run per column; counter mpt_batch_steps).  Where the entry answers -1
+    (the option off, a session listed twice, sessions of two models, K-quant weights, f32 K/V, head size 16, n_embd < 1024) the sessions
+    are evaluated one after the other.  Returns logits [B, n_vocab]; every session ends as after evaluate([token])."""
+    tokens = [int(t) for t in tokens]
+    if len(tokens) != len(sessions):
+        raise ValueError("evaluate_batch: one token per session")
+    ctxs, built, arr = [], [], None
+    try:
+        if 2 <= len(sessions) <= 8:
+            ctxs, built, arr = _batch_graphs(sessions, tokens)
+        if arr is not None and G.lib().ggml_hip_decode_batch(arr, len(sessions)) == 0:
+            out = np.stack([lg.read_data().reshape(-1) for lg, _ in built])
+            for s, row in zip(sessions, out):
+                s.n_past += 1
+                s.last_logits = row
+            return out
+    finally:
+        for c in ctxs:
+            c.free()
+    return np.stack([s.evaluate([t])[0] for s, t in zip(sessions, tokens)])
+
+
+def infer_tokens_batch(sessions, n):
+    """n greedy tokens for each of several sessions, from each session's last logits on: the pending tokens (their first maxima) go
+    through one batched step and, where that ran as the batched MPT step, the n - 1 steps behind it are chained on the device
+    (ggml_hip_decode_batch_greedy: k_argmax_next feeds the next replay of the step's graph).  Where the entry declines (evaluate_batch's
+    cases, a session without room for n tokens) the steps are made one by one: evaluate_batch + argmax each.  Returns (ids [n, B], the
+    logits [B, n_vocab] behind the last of them) — what the stepped loop returns — and leaves every n_past n further."""
+    B = len(sessions)
+    if any(s.last_logits is None for s in sessions):
+        raise ValueError("infer_tokens_batch: a session without an evaluation to continue")
+    ids = np.zeros((max(int(n), 0), B), np.int32)
+    if n < 1:
+        return ids, np.stack([s.last_logits for s in sessions])
+    ids[0] = [int(np.argmax(s.last_logits)) for s in sessions]
+    ctxs = []
+    try:
+        if 2 <= B <= 8:
+            ctxs, built, arr = _batch_graphs(sessions, ids[0])
+            tail = np.zeros((n - 1, B), np.int32)
+            if G.lib().ggml_hip_decode_batch_greedy(arr, B, int(n), tail.ctypes.data) == 0:
+                ids[1:] = tail
+                out = np.stack([lg.read_data().reshape(-1) for lg, _ in built])
+                for s, row in zip(sessions, out):
+                    s.n_past += n
+                    s.last_logits = row
+                return ids, out
+    finally:
+        for c in ctxs:
+            c.free()
+    for i in range(n):
+        if i:
+            ids[i] = [int(np.argmax(s.last_logits)) for s in sessions]
+        out = evaluate_batch(sessions, ids[i])
+    return ids, out
