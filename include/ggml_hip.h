@@ -921,6 +921,20 @@ GGML_API int ggml_hip_debug_act_quant(int kind, int flags, int64_t rows, int64_t
  * Every output is followed by 256 guard bytes (0xFF before the launch).  0, or -1 for what no call site launches. */
 GGML_API int ggml_hip_debug_mpt(int op, int flag, const float *x, const float *w, float eps, int64_t K, const uint16_t *mem_k,
                                 const uint16_t *mem_v, int H, int D, int n_past, int64_t C, float scale, void *const *out);
+/* The BLOOM plan (option plan_bloom, GGML_HIP_PLAN_BLOOM, default 0): the single-token graph of a BLOOM model with Q4_0 .. Q8_0 weights, every
+ * node offloaded, f16 K/V, head size 32 .. 128 runs as one embedding launch, five launches per layer and one lm_head launch, captured and
+ * replayed (llm_amd/csrc/plan_decode.inc plan_launch_bloom); ggml_hip_decode_greedy_chain chains it.  Counter bloom_plan_tokens: its tokens;
+ * they count in plan_tokens too and never in generic_graphs.  Everything else of a BLOOM model runs on the node-by-node executor.
+ * Test hook of its device code (llm_amd/csrc/kernels/bloom_plan.h), each launch alone on host arrays.  op 0: the biased LayerNorm staging —
+ * x, gain, nbias [K], eps; out[0..3] = lo, hi [K/2] int8, d [K/32] f32 (flag 1: after its f16 round trip), sum [K/32] i32.  op 1: one
+ * mat-vec launch of w [K, M] (a block-format tensor with a device copy), flag = the epilogue: 8 (M = 3 K: LayerNorm, + bias [M], out[0] = q
+ * [K], the K and V rows as f16 at position n_past of mem_k / mem_v [C][K], in-out), 9 (LayerNorm, + bias, GELU; out[0] [M]), 10 (x a plain
+ * row, + bias, + res [M]; out[0] [M]; gain and nbias unused) or 0 (LayerNorm, no matrix bias: the lm_head; out[0] [M], out[1] nullable: the
+ * normed row [K]).  op 2: row `token` of w dequantized, then the LayerNorm with gain and nbias; out[0] [K].  K <= 8192 but for flag 10.
+ * Every output is followed by 256 guard bytes (0xFF before the launch).  0, or -1 — before a device is touched — for what no call site launches. */
+GGML_API int ggml_hip_debug_bloom(int op, int flag, const struct ggml_tensor *w, const float *x, const float *gain, const float *nbias, float eps,
+                                  int64_t K, const float *bias, const float *res, int token, int n_past, int64_t C, uint16_t *mem_k,
+                                  uint16_t *mem_v, void *const *out);
 /* The MPT chunk plan (option plan_mpt_chunk, GGML_HIP_PLAN_MPT_CHUNK, default 0; independent of plan_mpt and plan_mpt_prompt): an evaluation
  * of 2 .. 31 tokens of such a graph that the prompt plan does not take (N < mmq_min, or plan_mpt_prompt = 0) runs with its mat-vecs on
  * k_mmq_cols in passes of 8 columns (llm_amd/csrc/plan_mpt_chunk.inc; needs option mmq_cols, n_embd 1024 .. 8192).  Counter

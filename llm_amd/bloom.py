@@ -1,10 +1,17 @@
 """BLOOM through the drop-in C ABI: the graph of crates/models/bloom/src/lib.rs:116-342 built node by node with the
-ctypes binding (llm_amd.ggml) and executed by ggml_graph_compute on the MI355X (generic executor; there is no fused
-plan for it).  A LayerNorm with bias on the embeddings; fused QKV stored as [Q | K | V] blocks of n_embd rows, viewed
+ctypes binding (llm_amd.ggml) and executed by ggml_graph_compute on the MI355X: node by node on the generic executor, or —
+backend option plan_bloom, block-format weights, one token, every node offloaded — on the fused BLOOM plan (csrc/plan_decode.inc
+plan_launch_bloom: one embedding launch with its LayerNorm, five launches per layer with the biases inside the mat-vec launches,
+one lm_head launch, the captured graph replayed; from option attn_split's threshold on the attention runs split over the
+positions), which Bloom.infer_tokens_device chains on the device.  It declines, with nothing executed, more than one token,
+offload=False, K-quant or F16 weights, f32 K/V and head size 16: those run on the executor, as every prompt does.
+A LayerNorm with bias on the embeddings; fused QKV stored as [Q | K | V] blocks of n_embd rows, viewed
 at offsets 0, E and 2E; K and V stored token-major, V re-laid by cpy(permute(.., 1, 2, 0, 3)) at every use; ALiBi
 attention bias (ggml_alibi, bias_max 8) between the scale and the causal mask, the chain built out of place; biases on
 every matrix; a separate output.weight.  Synthetic weights follow the loader's names (lib.rs:56-83); 2-D weights are
 quantized, gains and biases stay f32."""
+import ctypes as C
+
 import numpy as np
 
 from . import ggml as G
@@ -51,63 +58,109 @@ class Bloom(Resident):
     the graph exactly as the reference does: it never calls set_offloading, so every node is CPU-backend and its
     result is mirrored to the host (and the ALiBi attention chain runs as four launches)."""
 
-    def __init__(self, hp, w, n_ctx=None, offload=True):
+    def __init__(self, hp, w, n_ctx=None, offload=True, kv_type=G.TYPE_F16):
         super().__init__(hp, w, tensor_shapes(hp), hp["n_embd"], n_ctx)
         self.offload = offload
+        self.kv_es = 2
+        if kv_type != G.TYPE_F16:  # the reference's memory_k_type = f32 (the executor's: the plan takes f16 K/V alone)
+            self.sctx.free()
+            n_kv, self.kv_es = hp["n_layer"] * self.C * hp["n_embd"], 4
+            self.sctx = G.Context(2 * n_kv * 4 + (1 << 16))
+            self.memory_k = self.sctx.new_tensor(kv_type, n_kv).set_name("memory_k").offload_no_scratch()
+            self.memory_v = self.sctx.new_tensor(kv_type, n_kv).set_name("memory_v").offload_no_scratch()
+        self.last_logits = None  # the last row of the last evaluation: its first maximum is the pending token
 
     def evaluate(self, tokens):
         """Bloom::evaluate (lib.rs:116-342): returns logits [N, n_vocab]."""
+        ctx0 = self._ctx0(len(tokens), kq_copies=4)
+        try:
+            return self._evaluate_in(ctx0, tokens)[0]
+        finally:
+            ctx0.free()
+
+    def infer_tokens_device(self, n):
+        """n greedy tokens from the last evaluation's logits on: the pending token (their first maximum) is evaluated as its
+        graph, and where that ran as the BLOOM plan the n - 1 tokens behind it are chained on the device
+        (ggml_hip_decode_greedy_chain: the argmax feeds the next replay, no graph is built on the host).  Where the entry
+        declines (option plan_bloom off, a shape the plan does not take, the context's end) the remaining tokens are stepped:
+        evaluate + argmax each.  Returns (ids [n], the logits [n_vocab] behind the last of them) — what the stepped loop
+        returns — and leaves n_past n further."""
+        if self.last_logits is None:
+            raise ValueError("infer_tokens_device: no evaluation to continue")
+        ids = np.zeros(n, np.int32)
+        if n < 1:
+            return ids, self.last_logits
+        ids[0] = int(np.argmax(self.last_logits))
+        ctx0 = self._ctx0(1, kq_copies=4)
+        done = 1
+        try:
+            _, gf = self._evaluate_in(ctx0, [int(ids[0])])
+            if n > 1:  # (ctx0 lives on: the entry is handed the graph it names the plan by)
+                tail = np.zeros(n - 1, np.int32)
+                logits = np.zeros(self.hp["n_vocab"], np.float32)
+                if G.lib().ggml_hip_decode_greedy_chain(C.cast(gf.ptr, C.c_void_p), n - 1, tail.ctypes.data, logits.ctypes.data) == 0:
+                    ids[1:] = tail
+                    self.n_past += n - 1
+                    self.last_logits = logits
+                    done = n
+        finally:
+            ctx0.free()
+        for i in range(done, n):
+            ids[i] = int(np.argmax(self.last_logits))
+            self.evaluate([int(ids[i])])
+        return ids, self.last_logits
+
+    def _evaluate_in(self, ctx0, tokens):
+        """evaluate's graph in ctx0, computed: (logits [N, n_vocab], the graph)."""
         hp, t = self.hp, self.t
         E, H, L, V = hp["n_embd"], hp["n_head"], hp["n_layer"], hp["n_vocab"]
         D, N, P, C = E // H, len(tokens), self.n_past, self.C
-        T = P + N
-        ctx0 = self._ctx0(N, kq_copies=4)
-        try:
-            off = (lambda x: x.offload()) if self.offload else (lambda x: x)
+        T, es = P + N, self.kv_es
+        off = (lambda x: x.offload()) if self.offload else (lambda x: x)
 
-            def ln(a, name):
-                return off(ctx0.op_add(off(ctx0.op_mul(off(ctx0.op_norm(a)), t[name + ".weight"])), t[name + ".bias"]))
+        def ln(a, name):
+            return off(ctx0.op_add(off(ctx0.op_mul(off(ctx0.op_norm(a)), t[name + ".weight"])), t[name + ".bias"]))
 
-            def linear(name, a):
-                return off(ctx0.op_add(off(ctx0.op_mul_mat(t[name + ".weight"], a)), t[name + ".bias"]))
+        def linear(name, a):
+            return off(ctx0.op_add(off(ctx0.op_mul_mat(t[name + ".weight"], a)), t[name + ".bias"]))
 
-            x = off(ctx0.op_get_rows(t["tok_embeddings.weight"], ctx0.tensor_from(np.asarray(tokens, np.int32))))
-            x = ln(x, "norm")  # :144-147
-            gf = ctx0.graph()
-            for il in range(L):
-                p = f"layers.{il}."
-                cur = ln(x, p + "attention_norm")  # :155-159
-                cur = linear(p + "attention.query_key_value", cur)  # :162-163
-                nb = cur.nb[1]
-                qc, kc, vc = (ctx0.op_view_2d(cur, E, N, nb, 4 * E * j) for j in range(3))  # :166-185
-                k = ctx0.op_view_1d(self.memory_k, N * E, 2 * E * (il * C + P))  # :188-203
-                v = ctx0.op_view_1d(self.memory_v, N * E, 2 * E * (il * C + P))
-                gf.build_forward_expand(off(ctx0.op_cpy(kc, k)))
-                gf.build_forward_expand(off(ctx0.op_cpy(vc, v)))
-                q = ctx0.op_permute(off(ctx0.op_cpy(qc, ctx0.new_tensor(G.TYPE_F32, D, H, N))), 0, 2, 1, 3)  # :206-212
-                kk = ctx0.op_permute(ctx0.op_reshape_3d(ctx0.op_view_1d(self.memory_k, T * E, il * C * 2 * E), D, H, T),
-                                     0, 2, 1, 3)  # :215-227
-                kq = off(ctx0.op_mul_mat(kk, q))  # :230
-                kq = off(ctx0.op_scale(kq, ctx0.new_f32(np.float32(1.0) / np.sqrt(np.float32(E) / np.float32(H)))))
-                kq = off(ctx0.op_alibi(kq, P, H, ALIBI_BIAS_MAX))  # :240
-                kq = off(ctx0.op_diag_mask_inf(kq, P))  # :243
-                kq = off(ctx0.op_soft_max(kq))  # :246
-                vt = off(ctx0.op_cpy(ctx0.op_permute(ctx0.op_reshape_3d(
-                    ctx0.op_view_1d(self.memory_v, T * E, il * C * 2 * E), D, H, T), 1, 2, 0, 3),
-                    ctx0.new_tensor(G.TYPE_F16, T, D, H)))  # :250-270
-                kqv = off(ctx0.op_mul_mat(vt, kq))  # :272
-                cur = off(ctx0.op_cpy(ctx0.op_permute(kqv, 0, 2, 1, 3), ctx0.new_tensor(G.TYPE_F32, E, N)))  # :275-281
-                cur = linear(p + "attention.wo", cur)  # :284-285
-                ff_in = off(ctx0.op_add(cur, x))  # :287
-                cur = ln(ff_in, p + "ffn_norm")  # :291-296
-                cur = off(ctx0.op_gelu(linear(p + "feed_forward.w1", cur)))  # :298-304
-                cur = linear(p + "feed_forward.w2", cur)  # :306-308
-                x = off(ctx0.op_add(cur, ff_in))  # :310
-            x = ln(x, "output_norm")  # :317-322
-            logits = ctx0.op_mul_mat(t["output.weight"], x)  # :327
-            gf.build_forward_expand(logits)
-            gf.compute()
-            self.n_past = T
-            return logits.read_data().reshape(N, V).copy()
-        finally:
-            ctx0.free()
+        x = off(ctx0.op_get_rows(t["tok_embeddings.weight"], ctx0.tensor_from(np.asarray(tokens, np.int32))))
+        x = ln(x, "norm")  # :144-147
+        gf = ctx0.graph()
+        for il in range(L):
+            p = f"layers.{il}."
+            cur = ln(x, p + "attention_norm")  # :155-159
+            cur = linear(p + "attention.query_key_value", cur)  # :162-163
+            nb = cur.nb[1]
+            qc, kc, vc = (ctx0.op_view_2d(cur, E, N, nb, 4 * E * j) for j in range(3))  # :166-185
+            k = ctx0.op_view_1d(self.memory_k, N * E, es * E * (il * C + P))  # :188-203
+            v = ctx0.op_view_1d(self.memory_v, N * E, es * E * (il * C + P))
+            gf.build_forward_expand(off(ctx0.op_cpy(kc, k)))
+            gf.build_forward_expand(off(ctx0.op_cpy(vc, v)))
+            q = ctx0.op_permute(off(ctx0.op_cpy(qc, ctx0.new_tensor(G.TYPE_F32, D, H, N))), 0, 2, 1, 3)  # :206-212
+            kk = ctx0.op_permute(ctx0.op_reshape_3d(ctx0.op_view_1d(self.memory_k, T * E, il * C * es * E), D, H, T),
+                                 0, 2, 1, 3)  # :215-227
+            kq = off(ctx0.op_mul_mat(kk, q))  # :230
+            kq = off(ctx0.op_scale(kq, ctx0.new_f32(np.float32(1.0) / np.sqrt(np.float32(E) / np.float32(H)))))
+            kq = off(ctx0.op_alibi(kq, P, H, ALIBI_BIAS_MAX))  # :240
+            kq = off(ctx0.op_diag_mask_inf(kq, P))  # :243
+            kq = off(ctx0.op_soft_max(kq))  # :246
+            vt = off(ctx0.op_cpy(ctx0.op_permute(ctx0.op_reshape_3d(
+                ctx0.op_view_1d(self.memory_v, T * E, il * C * es * E), D, H, T), 1, 2, 0, 3),
+                ctx0.new_tensor(G.TYPE_F16, T, D, H)))  # :250-270
+            kqv = off(ctx0.op_mul_mat(vt, kq))  # :272
+            cur = off(ctx0.op_cpy(ctx0.op_permute(kqv, 0, 2, 1, 3), ctx0.new_tensor(G.TYPE_F32, E, N)))  # :275-281
+            cur = linear(p + "attention.wo", cur)  # :284-285
+            ff_in = off(ctx0.op_add(cur, x))  # :287
+            cur = ln(ff_in, p + "ffn_norm")  # :291-296
+            cur = off(ctx0.op_gelu(linear(p + "feed_forward.w1", cur)))  # :298-304
+            cur = linear(p + "feed_forward.w2", cur)  # :306-308
+            x = off(ctx0.op_add(cur, ff_in))  # :310
+        x = ln(x, "output_norm")  # :317-322
+        logits = ctx0.op_mul_mat(t["output.weight"], x)  # :327
+        gf.build_forward_expand(logits)
+        gf.compute()
+        self.n_past = T
+        out = logits.read_data().reshape(N, V).copy()
+        self.last_logits = out[-1]
+        return out, gf

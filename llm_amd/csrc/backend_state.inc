@@ -86,7 +86,7 @@ struct Backend {
     size_t ws_off = 0;  // offset in the last chunk
     Timing timing;
     int opt_fuse = 1, opt_plan = 1, opt_plan_k = 1, opt_plan_multi = 1, opt_plan_prompt = 1, opt_graph = 1, opt_big = 1, opt_kbig = 1;
-    int opt_chain_k = 0, opt_prepare = 1, opt_plan_batch = 1, opt_plan_f16 = 1, opt_plan_batch_chain = 1, opt_plan_batch_sample = 1, opt_plan_sample_chain = 1, opt_plan_batch_k = 0, opt_plan_out_k = 1, opt_plan_mpt = 0, opt_plan_mpt_prompt = 0, opt_mpt_attn_stream = 1, opt_plan_mpt_chunk = 0, opt_plan_mpt_batch = 0;
+    int opt_chain_k = 0, opt_prepare = 1, opt_plan_batch = 1, opt_plan_f16 = 1, opt_plan_batch_chain = 1, opt_plan_batch_sample = 1, opt_plan_sample_chain = 1, opt_plan_batch_k = 0, opt_plan_out_k = 1, opt_plan_mpt = 0, opt_plan_mpt_prompt = 0, opt_mpt_attn_stream = 1, opt_plan_mpt_chunk = 0, opt_plan_mpt_batch = 0, opt_plan_bloom = 0;
     int opt_fuse_attn = 1, opt_fuse_wo = 1, opt_warm_mb = 24, opt_affine = 1;
     int opt_act_quant = 0, opt_mmq_i8 = 0;
     int opt_mmq_min = 32, opt_k_prompt_min = 12, opt_mmq_fuse = 3, opt_mmq_cols = 1, opt_mmq_t256 = 1, opt_attn_fused = 1;
@@ -102,7 +102,7 @@ struct Backend {
     uint64_t stat_plan_tokens = 0, stat_generic_graphs = 0, stat_split_tokens = 0, stat_prompt_plan_tokens = 0, stat_fused_tokens = 0, stat_kplan_tokens = 0, stat_fused_heads_tokens = 0, stat_fused_wo_tokens = 0, stat_fused_affine_tokens = 0, stat_prepared_tokens = 0;
     uint64_t stat_alibi_fused = 0;
     uint64_t stat_batch_tokens = 0, stat_batch_steps = 0, stat_batch_chain_steps = 0, stat_batch_chain_tokens = 0;
-    uint64_t stat_batch_sample_steps = 0, stat_batch_sample_tokens = 0, stat_batch_k_steps = 0, stat_out_k_tokens = 0, stat_mpt_plan_tokens = 0, stat_mpt_split_tokens = 0, stat_mpt_prompt_tokens = 0, stat_mpt_stream_tokens = 0, stat_mpt_chunk_tokens = 0, stat_mpt_batch_steps = 0;
+    uint64_t stat_batch_sample_steps = 0, stat_batch_sample_tokens = 0, stat_batch_k_steps = 0, stat_out_k_tokens = 0, stat_mpt_plan_tokens = 0, stat_mpt_split_tokens = 0, stat_mpt_prompt_tokens = 0, stat_mpt_stream_tokens = 0, stat_mpt_chunk_tokens = 0, stat_mpt_batch_steps = 0, stat_bloom_plan_tokens = 0;
     uint64_t stat_sample_chain_steps = 0, stat_sample_chain_tokens = 0;
     // the chains that stop (plan_run.inc chain_req_run): steps per group behind which the host looks at the columns' live flags, the
     // pinned words the flags are copied into (two sets: the host reads one while the next group's copy is in flight) and their events
@@ -230,6 +230,10 @@ static const OptRow g_options[] = {
     // decode_batch_steps, plan_mpt_batch.inc plan_launch_mpt_batch: the chunk plan's mat-vecs at N = B, K/V rows and ALiBi attention per column;
     // needs options plan_batch and mmq_cols).  Independent of the other three; 0 as they are: the entries answer -1 for MPT graphs.
     {"plan_mpt_batch", &Backend::opt_plan_mpt_batch, OPT_ENV | OPT_DROPS},
+    // ... and the BLOOM plan for the single-token graph of a BLOOM model with block-format weights (plan_match.inc match_bloom_decode,
+    // plan_decode.inc plan_launch_bloom: the MPT plan's five launches per layer with the graph's biases, kernels/bloom_plan.h).  0 for
+    // plan_mpt's reason: tests/test_alibi_families_gpu.py pins "single-token BLOOM steps run on the executor".
+    {"plan_bloom", &Backend::opt_plan_bloom, OPT_ENV | OPT_DROPS},
     {"plan_multi", &Backend::opt_plan_multi, OPT_ENV | OPT_DROPS},    // fused plan for prompt chunks of 2..8 tokens (kernels/decode_big8.h)
     {"plan_prompt", &Backend::opt_plan_prompt, OPT_ENV | OPT_DROPS},  // fused plan for prompt batches of >= mmq_min tokens (kernels/prompt.h)
     // ggml_hip_decode_batch: one decode step of 2..8 sessions of one model as one pass over the weights (0: it answers -1, the caller steps them one by one)
@@ -373,6 +377,7 @@ static const StatRow g_counters[] = {
     {"attn_split_tokens", &Backend::stat_split_tokens},           // tokens whose attention ran split over positions
     {"kplan_tokens", &Backend::stat_kplan_tokens},                // decode tokens of K-quant models that ran as the K plan
     {"mpt_plan_tokens", &Backend::stat_mpt_plan_tokens},          // decode tokens of MPT models that ran as the MPT plan (option plan_mpt), evaluations and greedy chains; counted in plan_tokens too, never in generic_graphs
+    {"bloom_plan_tokens", &Backend::stat_bloom_plan_tokens},      // decode tokens of BLOOM models that ran as the BLOOM plan (option plan_bloom), evaluations and greedy chains; counted in plan_tokens too, never in generic_graphs
     {"mpt_split_tokens", &Backend::stat_mpt_split_tokens},        // ... those of them whose attention ran split over the positions (option attn_split), evaluations and chain steps; counted in mpt_plan_tokens too
     {"mpt_prompt_tokens", &Backend::stat_mpt_prompt_tokens},      // prompt tokens of MPT models that ran as the MPT prompt plan (option plan_mpt_prompt); counted in prompt_plan_tokens too, never in generic_graphs
     {"mpt_chunk_tokens", &Backend::stat_mpt_chunk_tokens},        // tokens of MPT prompt chunks (2 .. 31 tokens) that ran as the MPT chunk plan (option plan_mpt_chunk); counted in plan_tokens too, as the LLaMA chunk plan's are, never in generic_graphs
@@ -644,6 +649,7 @@ void apply_act_quant() {
     const int v = g.opt_act_quant;
     HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(c_act_quant_scalar), &v, sizeof(v)));
     if (mpt_plan_set_act_quant(v)) die("option act_quant: the MPT plan's code object did not take it");  // (its own copy of the constant: mpt_plan.hip)
+    if (bloom_plan_set_act_quant(v)) die("option act_quant: the BLOOM plan's code object did not take it");  // (likewise: bloom_plan.hip)
     if (mpt_prompt_set_act_quant(v)) die("option act_quant: the MPT prompt plan's code object did not take it");  // (likewise: mpt_prompt.hip)
     if (mpt_chunk_set_act_quant(v)) die("option act_quant: the MPT chunk plan's code object did not take it");  // (likewise: mpt_chunk.hip)
     if (mpt_batch_set_act_quant(v)) die("option act_quant: the batched MPT step's code object did not take it");  // (likewise: mpt_batch.hip)

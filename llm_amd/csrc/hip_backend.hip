@@ -64,6 +64,7 @@
 #include "kernels/prompt_pack.h"
 #include "kernels/flash_attn.h"
 #include "kernels/mpt_plan.h"
+#include "kernels/bloom_plan.h"
 #include "kernels/mpt_prompt.h"
 #include "kernels/mpt_chunk.h"
 #include "kernels/mpt_batch.h"
@@ -973,6 +974,7 @@ int ggml_hip_bench_plan_class(int kclass, int replays, double *ms_total, int64_t
 #include "debug_quant_attn.inc"
 #include "debug_token.inc"
 #include "debug_mpt.inc"
+#include "debug_bloom.inc"
 #include "debug_mpt_prompt.inc"
 #include "debug_mpt_chunk.inc"
 #include "debug_mpt_batch.inc"

@@ -489,7 +489,11 @@ __global__ void __launch_bounds__(256) k_quant_row(const float *__restrict__ x, 
 //  are QWeight::nb blocks apart while the launch covers DecMmvqArgs::nb of them)
 // (EPI_QKV_TM_BATCH: k_mmq_cols alone, the batched MPT step's code object mpt_batch.hip — EPI_QKV_TM with column c's K and V rows at
 //  position BatchCols::pos[c] of session c's caches)
-enum { EPI_STORE = 0, EPI_ADD = 1, EPI_GATE = 2, EPI_QKV = 3, EPI_QKV_TM = 4, EPI_GELU = 5, EPI_ADD_KS = 6, EPI_QKV_TM_BATCH = 7 };
+// (EPI_QKV_TM_B, EPI_GELU_B, EPI_ADD_B: k_mmvq_big alone, the BLOOM plan's code object bloom_plan.hip — the forms of EPI_QKV_TM, EPI_GELU and
+//  EPI_ADD behind a matrix bias (BigArgs::bias): the bias is added to the finished dot as the graph's add(mul_mat, b) node adds it, and only
+//  then come the f16 rounding of the K/V rows, the GELU, or the residual — (dot + b) + res, two f32 roundings in that order)
+enum { EPI_STORE = 0, EPI_ADD = 1, EPI_GATE = 2, EPI_QKV = 3, EPI_QKV_TM = 4, EPI_GELU = 5, EPI_ADD_KS = 6, EPI_QKV_TM_BATCH = 7,
+       EPI_QKV_TM_B = 8, EPI_GELU_B = 9, EPI_ADD_B = 10 };
 
 struct DecMmvqArgs {
     QWeight w[3];        // STORE/ADD: w[0]; GATE: w[0]=w1, w[1]=w3; QKV: wq, wk, wv
@@ -519,7 +523,9 @@ struct DecMmvqArgs {
 //   XSRC_F32  : plain f32 row → Q8 (the FFN gate feeding w2), same idea.
 //   XSRC_LNORM: as XSRC_NORM with ggml's `norm` (LayerNorm without bias: mean, then the variance of the centred values, f64 sums as
 //               k_norm) in front of the gain; k_mmvq_big alone, instantiated in mpt_plan.hip only.
-enum { XSRC_Q8 = 0, XSRC_NORM = 1, XSRC_F32 = 2, XSRC_LNORM = 3 };
+//   XSRC_LNORM_B: XSRC_LNORM with the LayerNorm's bias (BigArgs::xb) behind the gain — BLOOM's norm -> mul -> add, the product and the
+//               sum rounded one after the other; k_mmvq_big alone, instantiated in bloom_plan.hip only.
+enum { XSRC_Q8 = 0, XSRC_NORM = 1, XSRC_F32 = 2, XSRC_LNORM = 3, XSRC_LNORM_B = 4 };
 
 // thread t of the 256 owns elements 4i..4i+3 with i = it*256 + t; a Q8 block = 8 consecutive threads
 template <bool F16_D, bool SC>

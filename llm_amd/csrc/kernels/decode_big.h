@@ -131,7 +131,10 @@ struct BigArgs {
     int probe;      // measurement only (ggml_hip_set_option("probe", n), tests/tools/launch_probe.py): 1 = return before
                     // the first weight request, 2 = return once x is staged and the ring requested, 3 = no epilogue stores, 4 = every
                     // other step's dots skipped, 5 = no wave reductions; 0 = normal
-    int64_t line_pad[8];  // to whole lines: the argument behind BigArgs in a fused kernel's segment starts a line
+    // the BLOOM plan's launches (bloom_plan.hip; null everywhere else): named in the first batch of argument loads by the forms that read them
+    const float *xb;    // XSRC_LNORM_B: the LayerNorm's bias
+    const float *bias;  // EPI_QKV_TM_B / EPI_GELU_B / EPI_ADD_B: the matrix's bias, one word per row
+    int64_t line_pad[6];  // to whole lines: the argument behind BigArgs in a fused kernel's segment starts a line
 };
 static_assert(alignof(BigArgs) == 8 && sizeof(BigArgs) == 384, "BigArgs: six 64-byte lines of the kernarg segment");
 static_assert(offsetof(BigArgs, xf) == 0 && offsetof(BigArgs, eps) == 60, "BigArgs: line 0 = activation and dealing");
@@ -163,7 +166,9 @@ __device__ __forceinline__ int big_entry_nb(const BigArgs &ba) {
     asm("" : "+s"(nb) : "s"(ba.hot), "s"(ba.G), "s"(ba.wdeal), "s"(ba.w[0].qs), "s"(ba.w[0].d), "s"(ba.M[0]));
     if constexpr (EPI == EPI_GATE) asm("" : "+s"(nb) : "s"(ba.w[1].qs), "s"(ba.w[1].d));
     if constexpr (EPI == EPI_QKV) asm("" : "+s"(nb) : "s"(ba.w[1].qs), "s"(ba.w[1].d), "s"(ba.w[2].qs), "s"(ba.w[2].d), "s"(ba.M[1]), "s"(ba.M[2]));
-    if constexpr (EPI == EPI_QKV || EPI == EPI_QKV_TM) asm("" : "+s"(nb) : "s"(ba.prm));
+    if constexpr (EPI == EPI_QKV || EPI == EPI_QKV_TM || EPI == EPI_QKV_TM_B) asm("" : "+s"(nb) : "s"(ba.prm));
+    if constexpr (EPI == EPI_QKV_TM_B || EPI == EPI_GELU_B || EPI == EPI_ADD_B) asm("" : "+s"(nb) : "s"(ba.bias));
+    if constexpr (XSRC == XSRC_LNORM_B) asm("" : "+s"(nb) : "s"(ba.xb));
     if constexpr (QT != QT_Q4_0) asm("" : "+s"(nb) : "s"(ba.wx[0].qs2));
     if constexpr (XSRC == XSRC_Q8) asm("" : "+s"(nb) : "s"(ba.x.lo));
     return nb;
@@ -226,12 +231,27 @@ struct BigX<XSRC_NORM> {
 // ggml's `norm` and the gain (MPT's LayerNorm: no bias): the same loads, the same 1024 staging threads, a second statistic
 template <>
 struct BigX<XSRC_LNORM> : BigX<XSRC_NORM> {};
+// ... and the LayerNorm's bias (BLOOM's): a third f32x4 per pass, loaded with the row and the gain, ahead of the weight stream
+template <>
+struct BigX<XSRC_LNORM_B> : BigX<XSRC_NORM> {
+    f32x4 b[MAXIT];
+    __device__ __forceinline__ void load(const BigArgs &a, int nb, int tid, int T) {
+        BigX<XSRC_NORM>::load(a, nb, tid, T);
+        const int n4 = nb * 8;
+#pragma unroll
+        for (int it = 0; it < MAXIT; it++) {
+            const int i4 = it * NT + tid;
+            b[it] = ((const f32x4 *)a.xb)[i4 < n4 ? i4 : 0];
+        }
+    }
+};
 // the row of xr.v as norm(x) * w, quantized into LDS.  k_norm's arithmetic (kernels/ops.h): mean = (float)(sum of x in f64 / n), then
 // variance = (float)(sum of the f32 squares of the f32 differences x - mean, in f64, / n), scale = 1 / sqrtf(variance + eps),
 // y = ((x - mean) * scale) * w — the two f64 sums in another order than k_norm's 256 threads take them (f64 sums of f32 terms: the
 // f32 they round to is the same but for ties of the f64 sum itself).  Three barriers: s_part is written twice.
-template <bool F16_D, bool YOUT>
-__device__ __forceinline__ void big_stage_lnorm(const BigArgs &a, const BigX<XSRC_LNORM> &xr, int nb, int tid, i32x4 *s_lo, i32x4 *s_hi,
+// XSRC_LNORM_B: y = (((x - mean) * scale) * w) + b, the product rounded before the sum (the graph's mul node, then its add node).
+template <bool F16_D, bool YOUT, int XSRC = XSRC_LNORM>
+__device__ __forceinline__ void big_stage_lnorm(const BigArgs &a, const BigX<XSRC> &xr, int nb, int tid, i32x4 *s_lo, i32x4 *s_hi,
                                                 float *s_d, int *s_sum, double *s_part, f32x4 *y_keep) {
     constexpr int MAXIT = BigX<XSRC_NORM>::MAXIT, NT = BigX<XSRC_NORM>::NT;  // T == NT (launcher)
     const int n4 = nb * 8, n_el = nb * 32;
@@ -285,6 +305,10 @@ __device__ __forceinline__ void big_stage_lnorm(const BigArgs &a, const BigX<XSR
         if (i4 < n4) {
 #pragma unroll
             for (int k = 0; k < 4; k++) y[k] = (c[it][k] * scale) * xr.w[it][k];
+            if constexpr (XSRC == XSRC_LNORM_B) {  // (the product above is rounded: the objects are built without contraction)
+#pragma unroll
+                for (int k = 0; k < 4; k++) y[k] = __fadd_rn(__fmul_rn(c[it][k] * scale, xr.w[it][k]), xr.b[it][k]);
+            }
             if constexpr (YOUT) y_keep[it] = y;
         }
         quant4_to_lds<F16_D>(y, i4, nb, tid, s_lo, s_hi, s_d, s_sum);
@@ -320,6 +344,8 @@ __device__ __forceinline__ void big_stage_x(const BigArgs &a, const BigX<XSRC> &
         }
     } else if constexpr (XSRC == XSRC_LNORM) {
         big_stage_lnorm<F16_D, YOUT>(a, xr, nb, tid, s_lo, s_hi, s_d, s_sum, s_part, y_keep);
+    } else if constexpr (XSRC == XSRC_LNORM_B) {
+        big_stage_lnorm<F16_D, YOUT, XSRC_LNORM_B>(a, xr, nb, tid, s_lo, s_hi, s_d, s_sum, s_part, y_keep);
     } else {
         constexpr int MAXIT = BigX<XSRC_NORM>::MAXIT, NT = BigX<XSRC_NORM>::NT;  // T == NT (launcher)
         {
@@ -413,7 +439,7 @@ __device__ __forceinline__ void big_body(const BigArgs &ba, const int bid, const
         store_at = ba.prm->store_at;
         if (ba.gran) epoch = *ba.epoch;
     }
-    if constexpr (EPI == EPI_QKV_TM) {
+    if constexpr (EPI == EPI_QKV_TM || EPI == EPI_QKV_TM_B) {
         n_past = ba.prm->n_past;
         store_at = ba.prm->store_at;
     }
@@ -457,9 +483,16 @@ __device__ __forceinline__ void big_body(const BigArgs &ba, const int bid, const
     const int S = nu * nbl;
     // EPI_ADD: lane i preloads the residual of unit i (a load issued in the epilogue would drain the queue)
     float res_pre = 0.0f;
-    if constexpr (EPI == EPI_ADD) {
+    if constexpr (EPI == EPI_ADD || EPI == EPI_ADD_B) {
         const int m = u_first + u_stride * lane;
         res_pre = ba.res[(lane < nu && m < Utot) ? m : 0];
+    }
+    // the biased epilogues: lane i's word of the matrix bias likewise — requested here, in front of the first weight step, it is among the
+    // loads every counted wait of the dot loop has behind it: the word rides under the weight stream and is there when the dots end
+    float bias_pre = 0.0f;
+    if constexpr (EPI == EPI_QKV_TM_B || EPI == EPI_GELU_B || EPI == EPI_ADD_B) {
+        const int m = u_first + u_stride * lane;  // (one row per unit, no affine dealing: the unit is the row)
+        bias_pre = ba.bias[(lane < nu && m < Utot) ? m : 0];
     }
 
     // unit -> (matrix, first row)
@@ -568,7 +601,7 @@ __device__ __forceinline__ void big_body(const BigArgs &ba, const int bid, const
             s_rope[2 * kk + 1] = rope_pre[1];
         }
     }
-    constexpr bool YTAP = (XSRC == XSRC_NORM || XSRC == XSRC_LNORM) && EPI == EPI_STORE;
+    constexpr bool YTAP = (XSRC == XSRC_NORM || XSRC == XSRC_LNORM || XSRC == XSRC_LNORM_B) && EPI == EPI_STORE;
     f32x4 y_keep[YTAP ? BigX<XSRC_NORM>::MAXIT : 1];  // the normed row for the embedding tap (stored in the epilogue)
     big_stage_x<F16_D, XSRC, YTAP>(ba, xr, nb, nbp, tid, T, s_lo, s_hi, s_d, s_sum, s_part, y_keep);
     const long long t_staged = ts ? big_now() : 0;
@@ -655,15 +688,21 @@ __device__ __forceinline__ void big_body(const BigArgs &ba, const int bid, const
             ba.dst[m0] = silu_table(myv[0]) * myv[1];
         } else if constexpr (EPI == EPI_GELU) {
             ba.dst[m0] = gelu_table(myv[0]);
-        } else if constexpr (EPI == EPI_QKV_TM) {  // row m0 of [Q | K | V], Egqa rows each: Q as f32, K and V as f16 (RNE, ggml's cpy) at position n_past
+        } else if constexpr (EPI == EPI_ADD_B) {  // the graph's add(add(mul_mat, b), res): two roundings, the bias first
+            ba.dst[m0] = __fadd_rn(__fadd_rn(myv[0], bias_pre), res_pre);
+        } else if constexpr (EPI == EPI_GELU_B) {
+            ba.dst[m0] = gelu_table(__fadd_rn(myv[0], bias_pre));
+        } else if constexpr (EPI == EPI_QKV_TM || EPI == EPI_QKV_TM_B) {  // row m0 of [Q | K | V], Egqa rows each: Q as f32, K and V as f16 (RNE, ggml's cpy) at position n_past
             const int Eq = ba.Egqa;
             const int p = store_at ? store_at : n_past;  // (store_at: a roofline replay parks its rows, see DecParams)
+            float v = myv[0];
+            if constexpr (EPI == EPI_QKV_TM_B) v = __fadd_rn(v, bias_pre);  // (the f32 sum is what the cpy nodes round)
             if (m0 < Eq)
-                ba.dst[m0] = myv[0];
+                ba.dst[m0] = v;
             else if (m0 < 2 * Eq)
-                ba.mem_k[(int64_t)p * Eq + (m0 - Eq)] = __float2half_rn(myv[0]);
+                ba.mem_k[(int64_t)p * Eq + (m0 - Eq)] = __float2half_rn(v);
             else
-                ba.mem_v[(int64_t)p * Eq + (m0 - 2 * Eq)] = __float2half_rn(myv[0]);
+                ba.mem_v[(int64_t)p * Eq + (m0 - 2 * Eq)] = __float2half_rn(v);
         } else {  // EPI_QKV, see k_mmvq_dec
             const int p = store_at ? store_at : n_past;
             __half h0, h1;  // the pair as f16: what the K/V cache holds, and what ggml's F16 mat-mul makes of Q (src1 -> f16)

@@ -45,7 +45,13 @@ static bool plan_weights_resident(const LlamaMatch &m) {
         for (int i = 0; i < LAYER_MATS; i++)
             if (!ok_q(l.at(i))) return false;
         if (!ok_raw(l.attn_norm) || !ok_raw(l.ffn_norm)) return false;
+        if (m.bloom)
+            for (const ggml_tensor *b : {l.attn_norm_b, l.ffn_norm_b, l.b_qkv, l.b_o, l.b_1, l.b_2})
+                if (!ok_raw(b)) return false;
     }
+    if (m.bloom)
+        for (const ggml_tensor *b : {m.norm_b, m.emb_norm, m.emb_norm_b})
+            if (!ok_raw(b)) return false;
     return true;
 }
 
@@ -63,6 +69,12 @@ static std::vector<uint64_t> plan_signature(const LlamaMatch &m, bool session = 
     if (m.mpt) {  // another family's plan altogether: its own words (a LLaMA signature never has 0x6d7074 here: the next word is a record)
         s.push_back(0x6d7074ull);
         s.push_back(f2u(m.alibi_bias_max));
+    }
+    if (m.bloom) {  // ... and BLOOM's, with the records MPT's graph has no counterpart of
+        s.push_back(0x626c6f6f6dull);
+        for (const ggml_tensor *t : {m.norm_b, m.emb_norm, m.emb_norm_b}) s.push_back(rec_id(t));
+        for (auto &l : m.layers)
+            for (const ggml_tensor *t : {l.attn_norm_b, l.ffn_norm_b, l.b_qkv, l.b_o, l.b_1, l.b_2}) s.push_back(rec_id(t));
     }
     for (const ggml_tensor *t : {m.wte, m.norm, m.output, m.stage_in, m.stage_out}) s.push_back(t ? rec_id(t) : 0);
     if (session)
@@ -301,6 +313,13 @@ static DecodePlan *build_plan(const LlamaMatch &m, std::vector<uint64_t> sig, bo
     else if (m.kquant) p->klw = plan_layer_weights<KWeight>(m, plan_kw);
     else p->lw = plan_layer_weights<QWeight>(m, plan_qw);
     for (auto &l : m.layers) p->ln.push_back({(const float *)dev_ptr(l.attn_norm), (const float *)dev_ptr(l.ffn_norm)});
+    if (m.bloom) {
+        auto f32 = [](const ggml_tensor *t) { return (const float *)dev_ptr(t); };
+        for (auto &l : m.layers) p->lb.push_back({f32(l.attn_norm_b), f32(l.ffn_norm_b), f32(l.b_qkv), f32(l.b_o), f32(l.b_1), f32(l.b_2)});
+        p->norm_b = f32(m.norm_b);
+        p->emb_norm = f32(m.emb_norm);
+        p->emb_norm_b = f32(m.emb_norm_b);
+    }
     // the results of every plan but a batched step's are the graph's own nodes; a batched step's are rows of the pool (plan_pool_layout)
     if (m.embedding && !batch && !m.mpt) p->emb_out = (float *)dev_ptr(m.embedding);
     if (m.logits && !batch && !m.mpt) p->logits_out = dev_ptr(m.logits);

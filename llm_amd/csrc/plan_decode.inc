@@ -819,12 +819,26 @@ static void launch_big_lnorm(int qt, int epi, const BigArgs &a) {
     b.G = sh.G;
     if (launch_mpt_big(g.stream, qt, epi, &b, sh.G, sh.lds)) die("MPT plan: no k_mmvq_big instantiation for type %d, epilogue %d", qt, epi);
 }
+// the ALiBi attention of layer il over token-major K and V, for the MPT plan and the BLOOM plan: q -> the merged heads' f32 row in k_att
+static void plan_attn_alibi(DecodePlan *p, LaunchCtx &cx, int il, int av) {
+    const LlamaMatch &m = p->m;
+    const int64_t E = m.E, Clds = mpt_attn_rows(m.C, m.H);
+    const double bytes = (double)(m.n_past + 1) * E * 4.0 + E * 8.0;
+    if (!cx.want(GGML_HIP_KCLASS_ATTN, bytes)) return;
+    Timed tm(GGML_HIP_KCLASS_ATTN, bytes);
+    const int rc = av == AV_SPLIT  // every CU pulls a piece of the cache: the three launches of kernels/mpt_plan.h
+                       ? launch_mpt_attn_split(g.stream, (int)m.H, p->att_S, p->q, p->mem_k_at(il), p->mem_v_at(il), p->prm, m.kq_scale, p->alibi,
+                                               (int)m.D, E, m.C, p->att_sc, p->att_pmax, p->att_part, p->k_att, attn_split_chunk_max(m.C, p->att_S) * 2)
+                       : launch_mpt_attn(g.stream, (int)m.H, p->q, p->mem_k_at(il), p->mem_v_at(il), p->prm, m.kq_scale, p->alibi, (int)m.D, E,
+                                         p->k_att, Clds, attn_decode_lds(Clds, m.D));
+    if (rc) die("%s plan: the attention's LDS opt-in failed", m.bloom ? "BLOOM" : "MPT");
+    HIP_CHECK(hipGetLastError());
+}
 static void plan_launch_mpt(DecodePlan *p, int av, LaunchCtx cx) {
     const LlamaMatch &m = p->m;
     const int qt = qt_of(m.wtype);
     const int64_t E = m.E, F = m.F, nbE = E / 32, nbF = F / 32;
     const double bb = (double)blk_bytes(qt);
-    const int64_t Clds = mpt_attn_rows(m.C, m.H);
     auto big_args = [&](const DecMmvqArgs &a, float *y_out) {
         return big_pack(a, y_out, nullptr, 0, nullptr, 0, nullptr, nullptr, 0, p->hot);  // (no timeline, no probe: the production instantiations)
     };
@@ -847,19 +861,7 @@ static void plan_launch_mpt(DecodePlan *p, int av, LaunchCtx cx) {
             a.mem_k = p->mem_k_at(il); a.mem_v = p->mem_v_at(il); a.Egqa = E; a.C = m.C; a.D = (int)m.D;
             cx.mmvq(0, 3.0 * E * nbE * bb + nbE * 40.0 + E * 8.0, [&] { launch_big_lnorm(qt, EPI_QKV_TM, big_args(a, nullptr)); });
         }
-        {
-            const double bytes = (double)(m.n_past + 1) * E * 4.0 + E * 8.0;
-            if (cx.want(GGML_HIP_KCLASS_ATTN, bytes)) {
-                Timed tm(GGML_HIP_KCLASS_ATTN, bytes);
-                const int rc = av == AV_SPLIT  // every CU pulls a piece of the cache: the three launches of kernels/mpt_plan.h
-                                   ? launch_mpt_attn_split(g.stream, (int)m.H, p->att_S, p->q, p->mem_k_at(il), p->mem_v_at(il), p->prm, m.kq_scale, p->alibi,
-                                                           (int)m.D, E, m.C, p->att_sc, p->att_pmax, p->att_part, p->k_att, attn_split_chunk_max(m.C, p->att_S) * 2)
-                                   : launch_mpt_attn(g.stream, (int)m.H, p->q, p->mem_k_at(il), p->mem_v_at(il), p->prm, m.kq_scale, p->alibi, (int)m.D, E,
-                                                     p->k_att, Clds, attn_decode_lds(Clds, m.D));
-                if (rc) die("MPT plan: the attention's LDS opt-in failed");
-                HIP_CHECK(hipGetLastError());
-            }
-        }
+        plan_attn_alibi(p, cx, il, av);
         residual(1, w.wo, p->k_att, nbE, p->xa, p->xb);
         {   // LayerNorm + up_proj + GELU
             DecMmvqArgs a;
@@ -875,9 +877,82 @@ static void plan_launch_mpt(DecodePlan *p, int av, LaunchCtx cx) {
     a.w[0] = p->output; a.xf = p->xa; a.xw = p->norm; a.eps = m.eps; a.nb = nbE; a.dst = (float *)dst.logits;
     cx.mmvq(4, (double)m.V * nbE * bb + nbE * 40.0 + m.V * 4.0, [&] { launch_big_lnorm(qt, EPI_STORE, big_args(a, dst.emb)); });
 }
+// ---------------------------------------------------------------------------------------------------
+// The BLOOM plan: single-token decode of a BLOOM graph (LlamaMatch::bloom), block-format weights.  The MPT plan's sequence with the
+// biases the graph has: one embedding launch (k_get_rows_lnorm: the row and its LayerNorm), then per layer
+//   LayerNorm(gain, bias) + query_key_value + bias + K/V store | ALiBi attention | wo + bias + residual |
+//   LayerNorm(gain, bias) + w1 + bias + GELU | w2 + bias + residual
+// then LayerNorm(gain, bias) + output.weight (no bias on it), which taps the embedding row.  All six mat-vec forms are k_mmvq_big out of
+// the plan's own code object (bloom_plan.hip: XSRC_LNORM_B, EPI_QKV_TM_B, EPI_GELU_B, EPI_ADD_B); the attention is the MPT plan's launch,
+// out of the MPT plan's code object, in either form (av).  Every dependency is a kernel boundary, one stream.  Kinds as the MPT plan's.
+// ---------------------------------------------------------------------------------------------------
+static void launch_big_bloom(int qt, int epi, int xsrc, const BigArgs &a, const float *xb, const float *bias) {
+    const BigShape sh = big_shape(xsrc, epi, a.nb, a.M[0]);
+    if (!sh.ok) die("BLOOM plan: a launch the matcher's preconditions exclude (%lld rows)", (long long)a.M[0]);
+    BigArgs b = a;
+    b.xb = xb;
+    b.bias = bias;
+    b.T = sh.W * 64;
+    if (xsrc == XSRC_LNORM_B) {  // all 16 waves stage the norm, W of them take rows (as launch_big does for XSRC_NORM)
+        b.wdeal = sh.W;
+        b.T = BigX<XSRC_NORM>::NT;
+    }
+    b.G = sh.G;
+    if (launch_bloom_big(g.stream, qt, epi, xsrc, &b, sh.G, b.T, sh.lds)) die("BLOOM plan: no k_mmvq_big instantiation for type %d, epilogue %d", qt, epi);
+}
+static void plan_launch_bloom(DecodePlan *p, int av, LaunchCtx cx) {
+    const LlamaMatch &m = p->m;
+    const int qt = qt_of(m.wtype);
+    const int64_t E = m.E, F = m.F, nbE = E / 32, nbF = F / 32;
+    const double bb = (double)blk_bytes(qt);
+    auto big_args = [&](const DecMmvqArgs &a, float *y_out) {
+        return big_pack(a, y_out, nullptr, 0, nullptr, 0, nullptr, nullptr, 0, p->hot);  // (no timeline, no probe: the production instantiations)
+    };
+    auto residual = [&](int kind, const QWeight &w, const float *bias, const float *xf, int64_t nb, const float *res, float *dst) {
+        DecMmvqArgs a;
+        memset(&a, 0, sizeof(a));
+        a.w[0] = w; a.xf = xf; a.nb = nb; a.dst = dst; a.res = res;
+        cx.mmvq(kind, (double)E * nb * bb + nb * 40.0 + E * 12.0, [&] { launch_big_bloom(qt, EPI_ADD_B, XSRC_F32, big_args(a, nullptr), nullptr, bias); });
+    };
+    cx.other((double)E * 12.6, [&] {
+        if (launch_bloom_embed(g.stream, qt, &p->wte, (const int *)&p->prm->token, p->emb_norm, p->emb_norm_b, m.eps, p->xa))
+            die("BLOOM plan: no k_get_rows_lnorm for type %d, %lld blocks", qt, (long long)nbE);
+    });
+    for (int il = 0; il < m.L; il++) {
+        const DecodePlan::LW &w = p->lw[il];
+        const DecodePlan::LayerNorms &ln = p->ln[il];
+        const DecodePlan::LayerBiases &lb = p->lb[il];
+        {   // LayerNorm + query_key_value + bias; q as f32, the K and V rows as f16 at position n_past of the layer's caches
+            DecMmvqArgs a;
+            memset(&a, 0, sizeof(a));
+            a.w[0] = w.wq; a.xf = p->xa; a.xw = ln.attn_norm; a.eps = m.eps; a.nb = nbE; a.dst = p->q; a.prm = p->prm;
+            a.mem_k = p->mem_k_at(il); a.mem_v = p->mem_v_at(il); a.Egqa = E; a.C = m.C; a.D = (int)m.D;
+            cx.mmvq(0, 3.0 * E * nbE * bb + nbE * 40.0 + E * 24.0,
+                    [&] { launch_big_bloom(qt, EPI_QKV_TM_B, XSRC_LNORM_B, big_args(a, nullptr), lb.attn_norm, lb.qkv); });
+        }
+        plan_attn_alibi(p, cx, il, av);
+        residual(1, w.wo, lb.wo, p->k_att, nbE, p->xa, p->xb);
+        {   // LayerNorm + w1 + bias + GELU
+            DecMmvqArgs a;
+            memset(&a, 0, sizeof(a));
+            a.w[0] = w.w1; a.xf = p->xb; a.xw = ln.ffn_norm; a.eps = m.eps; a.nb = nbE; a.dst = p->gate;
+            cx.mmvq(2, (double)F * nbE * bb + nbE * 40.0 + F * 8.0 + E * 4.0,
+                    [&] { launch_big_bloom(qt, EPI_GELU_B, XSRC_LNORM_B, big_args(a, nullptr), lb.ffn_norm, lb.w1); });
+        }
+        residual(3, w.w2, lb.w2, p->gate, nbF, p->xb, p->xa);
+    }
+    const ResultDst dst = plan_result_dst(p, cx);
+    DecMmvqArgs a;
+    memset(&a, 0, sizeof(a));
+    a.w[0] = p->output; a.xf = p->xa; a.xw = p->norm; a.eps = m.eps; a.nb = nbE; a.dst = (float *)dst.logits;
+    cx.mmvq(4, (double)m.V * nbE * bb + nbE * 40.0 + m.V * 4.0 + E * 4.0,
+            [&] { launch_big_bloom(qt, EPI_STORE, XSRC_LNORM_B, big_args(a, dst.emb), p->norm_b, nullptr); });
+}
 // the decode launches of a plan, whichever kind it is
 static void plan_launch_decode(DecodePlan *p, int av = AV_SHORT, LaunchCtx cx = {}) {
-    if (p->m.mpt)
+    if (p->m.bloom)
+        plan_launch_bloom(p, av, cx);
+    else if (p->m.mpt)
         plan_launch_mpt(p, av, cx);
     else if (p->m.f16w)
         plan_launch_f16(p, av, cx);

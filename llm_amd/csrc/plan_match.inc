@@ -434,13 +434,43 @@ static bool mpt_batch_shape_ok(const LlamaMatch &m, int B) {
     mc.N = 1;  // (a column ends at n_past + 1)
     return mpt_chunk_shape_ok(mc) && mpt_batch_attn_lds(m.C, B, mpt_batch_W(g.num_cus, m.H)) <= 150 * 1024;
 }
-static bool match_mpt_decode(ggml_cgraph *gr, LlamaMatch &m) {
+// ---------------------------------------------------------------------------------------------------
+// BLOOM (crates/models/bloom/src/lib.rs:116-342 as llm_amd/bloom.py builds it with every node offloaded) is the same walk with four additions
+// (`bloom`; option plan_bloom, the single-token graph alone: plan_decode.inc plan_launch_bloom):
+//   every LayerNorm is add(mul(norm(x), gain), bias) and every layer matrix add(mul_mat(w, .), bias) — the views at 0, E and 2E are views of
+//   the biased sum —, the residual adds name the product first (add(cur, x)), the embedding row passes a LayerNorm of its own
+//   (norm.weight / norm.bias) and the lm_head is output.weight, no bias on it, another tensor than tok_embeddings: 41 nodes per layer + 8.
+// Every add is claimed; a graph without the biases is MPT's, and MPT's matcher takes it or nobody does.
+// ---------------------------------------------------------------------------------------------------
+// the LayerNorm in front of a mat-vec: mul(norm(x), gain), or (bloom) add(mul(norm(x), gain), bias)
+static bool match_alibi_norm(const ggml_tensor *t, Claims &c, const ggml_tensor *&x, const ggml_tensor *&gain, const ggml_tensor *&bias, const LlamaMatch &m) {
+    if (m.bloom) {
+        MATCH(is_op(t, GGML_OP_ADD) && t->type == GGML_TYPE_F32 && !mirrored_to_host(t) && ggml_nelements(t) == m.N * m.E);
+        bias = t->src[1];
+        MATCH(is_leaf(bias) && bias->type == GGML_TYPE_F32 && ggml_nelements(bias) == m.E && bias->ne[0] == m.E);
+        c.take(t);
+        t = t->src[0];
+    }
+    return match_mpt_norm(t, c, x, gain, m);
+}
+static bool match_alibi_decode(ggml_cgraph *gr, LlamaMatch &m, const bool bloom) {
     const int n = gr->n_nodes;
     MATCH(n >= 39);
     Claims c;
     c.index(gr);
     auto dev_op = [&](const ggml_tensor *t, ggml_op op) { return is_op(t, op) && !mirrored_to_host(t); };
+    // a layer matrix's product: mul_mat itself, or (bloom) under add(mul_mat, bias) with one bias word per row; null: neither
+    auto product = [&](const ggml_tensor *t, const ggml_tensor *&bias, int64_t rows) -> const ggml_tensor * {
+        if (!bloom) return t;
+        if (!dev_op(t, GGML_OP_ADD) || t->type != GGML_TYPE_F32 || ggml_nelements(t) != rows) return nullptr;
+        bias = t->src[1];
+        if (!is_leaf(bias) || bias->type != GGML_TYPE_F32 || ggml_nelements(bias) != rows || bias->ne[0] != rows) return nullptr;
+        c.take(t);
+        return t->src[0];
+    };
+    const int ri = bloom ? 1 : 0;  // the residual's place in a residual add: add(x, cur) | add(cur, x)
     m.mpt = true;
+    m.bloom = bloom;
     m.eps = 1e-5f;  // ggml_norm's (op_norm)
     ggml_tensor *last = gr->nodes[n - 1];
     MATCH(is_op(last, GGML_OP_MUL_MAT) && last->type == GGML_TYPE_F32 && last->ne[1] >= 1 && last->ne[1] <= PROMPT_PLAN_MAX && last->ne[2] == 1 && last->ne[3] == 1);
@@ -451,7 +481,9 @@ static bool match_mpt_decode(ggml_cgraph *gr, LlamaMatch &m) {
     const bool chunk = m.N >= 2 && m.N <= MULTI_MAX_N && !prompt_ok;
     m.prompt = m.N > 1 && !chunk;
     const bool column = tl_mpt_batch_cols > 0;
-    if (column)
+    if (bloom)
+        MATCH(m.N == 1 && !column && g.opt_plan_bloom && g.opt_big);
+    else if (column)
         MATCH(m.N == 1 && g.opt_plan_mpt_batch && g.opt_mmq_cols);
     else if (chunk)
         MATCH(g.opt_plan_mpt_chunk && g.opt_mmq_cols);
@@ -470,13 +502,13 @@ static bool match_mpt_decode(ggml_cgraph *gr, LlamaMatch &m) {
     c.take(last);
     ggml_tensor *fin = last->src[1];
     const ggml_tensor *x = nullptr;
-    MATCH(match_mpt_norm(fin, c, x, m.norm, m));
+    MATCH(match_alibi_norm(fin, c, x, m.norm, m.norm_b, m));
     m.embedding = fin;
     {   // number of layers = length of the residual chain add(add(x, ..), ..) below the tail
         int cnt = 0;
         const ggml_tensor *y = x;
-        while (is_op(y, GGML_OP_ADD) && is_op(y->src[0], GGML_OP_ADD) && cnt < 4096) {
-            y = y->src[0]->src[0];
+        while (is_op(y, GGML_OP_ADD) && is_op(y->src[ri], GGML_OP_ADD) && cnt < 4096) {
+            y = y->src[ri]->src[ri];
             cnt++;
         }
         MATCH(cnt >= 1);
@@ -488,21 +520,21 @@ static bool match_mpt_decode(ggml_cgraph *gr, LlamaMatch &m) {
         LayerW &lw = m.layers[il];
         // x = add(inpFF, mul_mat(down_proj, gelu(mul_mat(up_proj, mul(norm(inpFF), norm_2)))))
         MATCH(dev_op(x, GGML_OP_ADD) && ggml_nelements(x) == N * m.E);
-        const ggml_tensor *inpFF = x->src[0], *dn = x->src[1];
+        const ggml_tensor *inpFF = x->src[ri], *dn = product(x->src[1 - ri], lw.b_2, m.E);
         MATCH(dev_op(dn, GGML_OP_MUL_MAT));
         lw.w2 = dn->src[0];
         const ggml_tensor *ge = dn->src[1];
         MATCH(dev_op(ge, GGML_OP_UNARY) && ge->op_params[0] == GGML_UNARY_OP_GELU);
-        const ggml_tensor *up = ge->src[0];
+        const ggml_tensor *up = product(ge->src[0], lw.b_1, m.F);
         MATCH(dev_op(up, GGML_OP_MUL_MAT));
         lw.w1 = lw.w3 = up->src[0];
         MATCH(is_leaf(lw.w1) && is_leaf(lw.w2) && lw.w1->ne[0] == m.E && lw.w1->ne[1] == m.F && lw.w2->ne[0] == m.F && lw.w2->ne[1] == m.E);
         c.take(x); c.take(dn); c.take(ge); c.take(up);
         const ggml_tensor *nx = nullptr;
-        MATCH(match_mpt_norm(up->src[1], c, nx, lw.ffn_norm, m) && nx == inpFF);
+        MATCH(match_alibi_norm(up->src[1], c, nx, lw.ffn_norm, lw.ffn_norm_b, m) && nx == inpFF);
         // inpFF = add(inpSA, mul_mat(out_proj, merged))
         MATCH(dev_op(inpFF, GGML_OP_ADD));
-        const ggml_tensor *inpSA = inpFF->src[0], *mo = inpFF->src[1];
+        const ggml_tensor *inpSA = inpFF->src[ri], *mo = product(inpFF->src[1 - ri], lw.b_o, m.E);
         MATCH(dev_op(mo, GGML_OP_MUL_MAT));
         lw.wo = mo->src[0];
         MATCH(is_leaf(lw.wo) && lw.wo->ne[0] == m.E && lw.wo->ne[1] == m.E);
@@ -576,20 +608,29 @@ static bool match_mpt_decode(ggml_cgraph *gr, LlamaMatch &m) {
         const ggml_tensor *qv = qcp->src[0];
         MATCH(is_op(qv, GGML_OP_VIEW) && qv->type == GGML_TYPE_F32 && ggml_nelements(qv) == N * m.E && qv->ne[0] == m.E && qv->ne[1] == N && qv->nb[0] == 4 &&
               (N == 1 || qv->nb[1] == (size_t)3 * m.E * 4));
-        const ggml_tensor *qkv = qv->src[0];
-        MATCH(dev_op(qkv, GGML_OP_MUL_MAT) && qkv->ne[0] == 3 * m.E && qkv->ne[1] == N && ggml_nelements(qkv) == N * 3 * m.E && ggml_is_contiguous(qkv) && view_offset(qv, qkv) == 0);
+        const ggml_tensor *qsum = qv->src[0];  // what the three views look into: the product, or (bloom) the product + bias
+        MATCH(qsum && qsum->ne[0] == 3 * m.E && qsum->ne[1] == N && ggml_nelements(qsum) == N * 3 * m.E && ggml_is_contiguous(qsum) && view_offset(qv, qsum) == 0);
+        const ggml_tensor *qkv = product(qsum, lw.b_qkv, 3 * m.E);
+        MATCH(dev_op(qkv, GGML_OP_MUL_MAT) && ggml_nelements(qkv) == N * 3 * m.E);
         lw.wq = lw.wk = lw.wv = qkv->src[0];
         MATCH(is_leaf(lw.wq) && lw.wq->ne[0] == m.E && lw.wq->ne[1] == 3 * m.E);
         c.take(kp); c.take(qp); c.take(kr); c.take(kv1); c.take(qcp); c.take(qv); c.take(qkv);
         const ggml_tensor *nx1 = nullptr;
-        MATCH(match_mpt_norm(qkv->src[1], c, nx1, lw.attn_norm, m) && nx1 == inpSA);
-        lw.cur = qkv;
+        MATCH(match_alibi_norm(qkv->src[1], c, nx1, lw.attn_norm, lw.attn_norm_b, m) && nx1 == inpSA);
+        lw.cur = qsum;
         x = inpSA;
+    }
+    if (bloom) {  // the LayerNorm on the embedding row
+        const ggml_tensor *row = nullptr;
+        MATCH(match_alibi_norm(x, c, row, m.emb_norm, m.emb_norm_b, m));
+        x = row;
     }
     MATCH(dev_op(x, GGML_OP_GET_ROWS));
     m.wte = x->src[0];
     m.embd = x->src[1];
-    MATCH(m.wte == m.output && is_leaf(m.embd) && m.embd->type == GGML_TYPE_I32 && m.embd->ne[0] == N && ggml_nelements(m.embd) == N && m.embd->data);
+    // MPT's lm_head is tied to the embedding; BLOOM's is a matrix of its own beside an embedding of the layers' type
+    MATCH(bloom ? m.wte != m.output && is_leaf(m.wte) && m.wte->type == m.wtype && m.wte->ne[0] == m.E && m.wte->ne[2] == 1 && m.wte->ne[3] == 1 : m.wte == m.output);
+    MATCH(is_leaf(m.embd) && m.embd->type == GGML_TYPE_I32 && m.embd->ne[0] == N && ggml_nelements(m.embd) == N && m.embd->data);
     c.take(x);
     // the K/V stores: cpy(view of qkv at E | 2E, view_1d(memory_k | memory_v) at position n_past of the layer)
     for (int i = 0; i < n; i++) {
@@ -621,6 +662,13 @@ static bool match_mpt_decode(ggml_cgraph *gr, LlamaMatch &m) {
         MATCH(m.n_past + m.N <= m.C && (mpt_attn_queries(m.D, (int64_t)m.n_past + m.N) != 0 || (g.opt_mpt_attn_stream && (m.D == 32 || m.D == 64 || m.D == 128))));
         return true;
     }
+    if (bloom) {  // the plan's launches, each as the device deals it (the lm_head of the 250 880 rows: 62 of the 64 rounds on 256 CUs)
+        MATCH(attn_decode_lds(mpt_attn_rows(m.C, m.H), m.D) <= ATTN_DECODE_LDS_MAX);
+        MATCH(big_shape(XSRC_LNORM_B, EPI_QKV_TM_B, m.E / 32, 3 * m.E).ok && big_shape(XSRC_LNORM_B, EPI_GELU_B, m.E / 32, m.F).ok &&
+              big_shape(XSRC_LNORM_B, EPI_STORE, m.E / 32, m.V).ok && big_shape(XSRC_F32, EPI_ADD_B, m.E / 32, m.E).ok &&
+              big_shape(XSRC_F32, EPI_ADD_B, m.F / 32, m.E).ok && m.F <= 24 * BIG_T);
+        return true;
+    }
     if (chunk) return mpt_chunk_shape_ok(m);
     if (column) return mpt_batch_shape_ok(m, tl_mpt_batch_cols);
     // k_attn_decode_alibi's arrays hold the context rounded up to 8 — or, where the split attention takes the longer rows (option
@@ -631,4 +679,6 @@ static bool match_mpt_decode(ggml_cgraph *gr, LlamaMatch &m) {
           big_shape(XSRC_F32, EPI_ADD, m.F / 32, m.E).ok && m.F <= 24 * BIG_T);
     return true;
 }
+static bool match_mpt_decode(ggml_cgraph *gr, LlamaMatch &m) { return match_alibi_decode(gr, m, false); }
+static bool match_bloom_decode(ggml_cgraph *gr, LlamaMatch &m) { return match_alibi_decode(gr, m, true); }
 #undef MATCH

@@ -249,9 +249,12 @@ static DecodePlan *resolve_plan(ggml_cgraph *gr, LlamaMatch &m) {
             return p;
         }
     }
-    if (!match_llama_decode(gr, m)) {  // not LLaMA's graph: MPT's (option plan_mpt), or nothing for the plans
+    if (!match_llama_decode(gr, m)) {  // not LLaMA's graph: MPT's (option plan_mpt), BLOOM's (option plan_bloom), or nothing for the plans
         m = LlamaMatch{};
-        if (!match_mpt_decode(gr, m)) return nullptr;
+        if (!match_mpt_decode(gr, m)) {
+            m = LlamaMatch{};
+            if (!g.opt_plan_bloom || !match_bloom_decode(gr, m)) return nullptr;
+        }
     }
     if (!plan_weights_resident(m)) {
         // first evaluation of a model: tok_embeddings is a leaf the caller never offloads (models/llama lib.rs:52);
@@ -382,6 +385,10 @@ static void count_token_forms(const LlamaMatch &m, int av) {
     if (av >= AV_FUSED2) g.stat_fused_heads_tokens++;
     if (m.kquant) g.stat_kplan_tokens += (uint64_t)m.N;
     if (m.out_k) g.stat_out_k_tokens += (uint64_t)m.N;
+    if (m.bloom) {  // (a BLOOM plan rides the MPT run path and keeps books of its own)
+        g.stat_bloom_plan_tokens++;
+        return;
+    }
     if (m.mpt && m.N == 1) g.stat_mpt_plan_tokens++;
     if (m.mpt && m.N > 1) g.stat_mpt_chunk_tokens += (uint64_t)m.N;
     if (m.mpt && long_ctx) g.stat_mpt_split_tokens++;
@@ -831,7 +838,7 @@ static int decode_chain(ggml_cgraph *last, int n, int32_t *out_tokens, float *la
         // (the chain's books are not count_token_forms': no fused_wo_tokens, fused_affine_tokens or split_tokens — values tests read; left as they are)
         if (av != AV_SPLIT && fused_qkv_shape(m, av_heads_split(av)).ok) g.stat_fused_tokens++;
         if (av >= AV_FUSED2) g.stat_fused_heads_tokens++;
-        if (m.mpt && av == AV_SPLIT) g.stat_mpt_split_tokens++;
+        if (m.mpt && !m.bloom && av == AV_SPLIT) g.stat_mpt_split_tokens++;
         if (use_graph) {
             VariantGraphs &vg = plain_graph(p, av, [&] { plan_launch_decode(p, av); });  // (captured here: the chain crossed into a variant no evaluation has captured yet)
             if (!vg.exec2) HIP_CHECK(hipGraphInstantiate(&vg.exec2, vg.graph, nullptr, nullptr, 0));
@@ -881,7 +888,7 @@ static int decode_chain(ggml_cgraph *last, int n, int32_t *out_tokens, float *la
     p->replays += use_graph ? (uint64_t)n : 0;
     g.stat_plan_tokens += (uint64_t)n;
     if (m.out_k) g.stat_out_k_tokens += (uint64_t)n;
-    if (m.mpt) g.stat_mpt_plan_tokens += (uint64_t)n;
+    if (m.mpt) (m.bloom ? g.stat_bloom_plan_tokens : g.stat_mpt_plan_tokens) += (uint64_t)n;
     g.chain_plan = nullptr;  // the caller's next evaluation re-arms it
     return 0;
 }

@@ -11,6 +11,7 @@
 //   chunk's launches with a per-column position and cache.
 // One more family has a plan over the same DecodePlan and run path: MPT's single-token graph (LlamaMatch::mpt, match_mpt_decode, plan_launch_mpt:
 // five launches per layer; option plan_mpt) — decode and the greedy chain alone, everything else of it runs on the generic executor.
+// BLOOM's single-token graph is MPT's with biases (LlamaMatch::bloom, match_bloom_decode, plan_launch_bloom; option plan_bloom): the same.
 // A block-format model whose output matrix alone is a K-quant (LlamaMatch::out_k: llama.cpp's "mostly Q4_0 ... Q8_0" files) takes the block
 // formats' sequences with the K plan's tail as its lm_head (plan_decode.inc plan_lm_head_k).
 // The first three and the last are captured once in a hipGraph per attention variant and replayed for the following tokens with only
@@ -54,6 +55,8 @@ struct LayerMats {
 struct LayerW : LayerMats<const ggml_tensor *> {
     const ggml_tensor *attn_norm = nullptr, *ffn_norm = nullptr;
     const ggml_tensor *cur = nullptr;  // the normed activation feeding wq/wk/wv (identity key for the KV stores)
+    // a BLOOM graph (LlamaMatch::bloom): the two LayerNorms' biases and the four matrices' (b_qkv: 3 E words, b_1: F, b_o and b_2: E)
+    const ggml_tensor *attn_norm_b = nullptr, *ffn_norm_b = nullptr, *b_qkv = nullptr, *b_o = nullptr, *b_1 = nullptr, *b_2 = nullptr;
     bool k_store = false, v_store = false;
 };
 static const int PROMPT_PLAN_MAX = 4096;  // tokens per evaluation the prompt plan accepts
@@ -72,6 +75,11 @@ struct LlamaMatch {
     // matrices per layer sit in the LLaMA names — wq = Wqkv (3 E rows), wo = out_proj, w1 = up_proj, w2 = down_proj; wk, wv and w3 name
     // wq and w1 again so that "for each matrix" needs no second form — F = 4 E, Hkv = H, eps is ggml_norm's, and K AND V are token-major
     bool mpt = false;
+    // a BLOOM graph (plan_match.inc match_bloom_decode; option plan_bloom): MPT's graph — mpt is set too: the same caches, the same attention,
+    // the same run path — with a bias on every LayerNorm and every matrix (LayerW, norm_b), a LayerNorm on the embedding row (emb_norm,
+    // emb_norm_b) and an output matrix of its own: the BLOOM plan (plan_launch_bloom), single-token decode alone
+    bool bloom = false;
+    const ggml_tensor *norm_b = nullptr, *emb_norm = nullptr, *emb_norm_b = nullptr;
     float alibi_bias_max = 0;
     float eps = 0, freq_base = 0, freq_scale = 0, kq_scale = 0;
     ggml_type wtype = GGML_TYPE_F32;
@@ -128,6 +136,11 @@ struct DecodePlan {
         const float *attn_norm, *ffn_norm;
     };
     std::vector<LayerNorms> ln;  // every kind of plan
+    struct LayerBiases {
+        const float *attn_norm, *ffn_norm, *qkv, *wo, *w1, *w2;
+    };
+    std::vector<LayerBiases> lb;  // a BLOOM plan
+    const float *norm_b = nullptr, *emb_norm = nullptr, *emb_norm_b = nullptr;  // ... the final norm's bias, the embedding norm's gain and bias
     F16W f_wte{}, f_output{};
     KWeight k_wte{}, k_output{};
     // K plan activations: f32 rows of wk / wv / the merged heads / w3, and ONE Q8_K row (max(E, F) wide) every mat-vec reads

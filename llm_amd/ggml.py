@@ -259,6 +259,8 @@ PROTOTYPES.update({
                                            C.c_void_p, C.c_float, C.c_int64, C.c_int, C.c_void_p]),
     "ggml_hip_debug_mpt": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_int64, C.c_void_p, C.c_void_p, C.c_int,
                                      C.c_int, C.c_int, C.c_int64, C.c_float, C.c_void_p]),
+    "ggml_hip_debug_bloom": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int64, C.c_void_p,
+                                       C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ggml_hip_debug_mpt_prompt": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int64, C.c_int,
                                             C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_float, C.c_void_p]),
     "ggml_hip_debug_mpt_chunk": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_int64, C.c_int, C.c_int,
